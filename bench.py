@@ -6,22 +6,28 @@ FTHead3 128/1024/1024/512, drop 0.1, fp32), synthetic data already resident in H
     python bench.py --gpus N --steps K --warmup W          (N > 1: this process starts the N ranks itself, as child processes)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N ...
     python bench.py --gpus 1 --spawn                        (one child, 1-rank RCCL group: the N>1 step sequence on one GPU)
+    python bench.py ... --full                               (+ everything besides the headline, below)
+    python bench.py ... --dump-outputs DIR                   (what the last timed step computed, as DIR/<name>.npy)
+
+A plain run sets up, warms up, times exactly --steps steps, writes --dump-outputs if given and prints the line; every other
+measurement (the repeat loops, the epoch sample, other shapes and sub-configurations, the roofline, the CPU baseline) runs only
+with --full.
 
 A step = graph plan build + zero grads + forward + MSE loss + backward + (N>1: one flat-bucket
 gradient all-reduce over RCCL) + Adam step, on a batch the model has not seen in the previous step
 (a pool of pre-collated batches, seeds 1000+i).  N > 1 (`--scaling both`, the default): the headline is STRONG scaling --
 the GLOBAL batch is 512 molecules (what SURVEY.md §8d quotes the metric on), split over the ranks by
-parallel.shard_indices (rank r owns molecules r::N of the same 512) -- and the same line carries `weak` (every rank owns 512
-molecules per step), `overlap_on` (two-graph step, the head's gradient exchange beside the encoder backward),
-`allreduce_alone` (the flat-buffer all-reduce by itself), `nccl_ranks` and the fastest rank's step time; `--scaling weak` /
-`strong` measure only that one.  At N = 1 the two are the same run.
+parallel.shard_indices (rank r owns molecules r::N of the same 512) -- and with --full the same line carries `weak` (every rank
+owns 512 molecules per step), `overlap_on` (two-graph step, the head's gradient exchange beside the encoder backward),
+`allreduce_alone` (the flat-buffer all-reduce by itself) and `nccl_ranks`; `--scaling weak` / `strong` measure only that one.
+At N = 1 the two are the same run.
 
 Default mode "graph": the batch is staged into fixed-capacity buffers (one kernel; the few % of padding are
 disconnected dummy rows, see fragnet_amd/graphstep.py) and plan + forward + loss + backward + gradient gather
 replay as ONE hipGraph; all-reduce and Adam follow on the stream.  `--eager` runs the same step launch by launch
 (hipGraph only around the prediction head).  Both count only the 512 real molecules per step.
 
-Besides the contract fields the JSON line carries
+Besides the contract fields the JSON line carries, with --full,
   roofline      for the dominant scatter work (bond-graph level, the largest of the four): algorithmic bytes (SURVEY.md
                 §8d closed forms B_agg / B_agg' on this batch's n, m -- the backward counted ONCE for its two passes
                 together) / launch time, measured here with HIP events on the launch stream over back-to-back launches
@@ -534,9 +540,16 @@ def parse_args(argv=None):
     ap.add_argument("--steps", type=int, default=30)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--pool", type=int, default=4, help="distinct pre-collated batches cycled through")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything besides the headline: four more timed loops (ms_per_step_repeats), the epoch sample, "
+                         "the round-3 shapes, the roofline, the CPU baseline; N > 1: the all-reduce alone, the ranks, overlap_on and weak.  "
+                         "Without it a run sets up, warms up, times --steps steps, writes --dump-outputs and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed -- loss, the parameters its Adam update left, its "
+                         "gradients -- as DIR/<name>.npy (float32); with the same arguments the inputs are the same in every run")
     ap.add_argument("--scaling", choices=("weak", "strong", "both"), default="both",
                     help="N>1 only.  both (default): the headline is the GLOBAL batch of 512 sharded over the ranks (strong, what SURVEY.md "
-                         "8d quotes the metric on) and the line carries a `weak` sub-object (512 molecules per rank); weak / strong: "
+                         "8d quotes the metric on) and with --full the line carries a `weak` sub-object (512 molecules per rank); weak / strong: "
                          "only that one")
     ap.add_argument("--spawn", action="store_true",
                     help="start the ranks as child processes even for --gpus 1 (one child, 1-rank RCCL group, the N>1 step sequence)")
@@ -574,7 +587,10 @@ def parse_args(argv=None):
     ap.add_argument("--library-head", action="store_true", help="A/B: head layers as library GEMMs + element-wise kernels instead of fn_dense_*")
     ap.add_argument("--tune", action="append", default=None, help="A/B: KEY=VALUE for fn_set_tuning (include/fragnet_hip.h FN_TUNE_*)")
     ap.add_argument("--scatter-blocks", type=int, default=None, help="A/B: resident workgroups of the scatter kernels (FN_TUNE_FWD_BLOCKS)")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def in_step_launch_times(args, rank, world, dev, scaling, overlap, shape_batches, replays=40):
@@ -708,6 +724,7 @@ class StepRun:
         if dist_on:
             torch.distributed.barrier()
         mine = time.perf_counter() - t0
+        self.last_loss = loss
         hi = torch.tensor([mine], dtype=torch.float64, device=self.dev)
         lo = hi.clone()
         if dist_on:
@@ -785,6 +802,37 @@ def epoch_sample(run, store, n_batches, dev):
                     "summed over the index spaces"}
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def step_outputs(run):
+    """What a caller of the timed step holds after its last step: the loss it returned, the parameters that step's Adam update left
+    and the gradients it computed (N > 1: averaged over the ranks).  Each parameter's slice of the optimiser's flat buffers, in the
+    model's parameter order, without the alignment padding between them."""
+    opt = run.opt
+
+    def unpadded(buf):
+        return torch.cat([buf[off: off + p.numel()] for p, off in zip(opt.params, opt.offsets)])
+
+    return {"loss": run.last_loss.detach().reshape(1), "parameters": unpadded(opt.flat.detach()), "gradients": unpadded(opt.grad)}
+
+
+def dump_outputs(out_dir, arrays, limit_bytes=DUMP_LIMIT_BYTES):
+    """--dump-outputs: every array as <out_dir>/<name>.npy, float64 kept, anything else as float32; at most ``limit_bytes`` in all."""
+    import numpy as np
+    out = {}
+    for name, a in arrays.items():
+        a = a.cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
+        out[name] = np.ascontiguousarray(a if a.dtype == np.float64 else a.astype(np.float32))
+    total = sum(a.nbytes for a in out.values())
+    if total > limit_bytes:
+        raise ValueError(f"--dump-outputs: {total} bytes, more than the {limit_bytes} allowed")
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return total
+
+
 def main():
     args = parse_args()
     # ---- N > 1 (or --spawn) without a launcher: this process becomes the PARENT of the ranks.  Nothing above or below this
@@ -848,18 +896,21 @@ def main():
         shape_batches = [store.collate(next(sampler)) for _ in range(args.shape_sample)]
     run = StepRun(args, rank, world, dev, head_scaling, head_overlap, force_distributed=spawned_single, shape_batches=shape_batches)
     elapsed, fastest, final_loss = run.timed(args.steps, args.warmup)
-    # the contract's K steps are the FIRST timed loop; four more loops of K steps give the spread
-    rep_ms = [elapsed / args.steps * 1e3]
-    for _ in range(4):
-        hi, _, _ = run.timed(args.steps, 0)
-        rep_ms.append(hi / args.steps * 1e3)
+    if args.dump_outputs and rank == 0:      # the contract's K steps' last one, before anything else runs on the model
+        dump_outputs(args.dump_outputs, step_outputs(run))
     extras = {}
-    extras["ms_per_step_repeats"] = {"n": len(rep_ms), "steps_each": args.steps, "min": round(min(rep_ms), 4),
-                                     "median": round(statistics.median(rep_ms), 4), "max": round(max(rep_ms), 4),
-                                     "note": "ms_per_step / value are the first loop's (the contract's K steps)"}
-    if store is not None and run.gstep is not None and args.epoch_batches > 0:
+    if args.full:
+        # the contract's K steps are the FIRST timed loop; four more loops of K steps give the spread
+        rep_ms = [elapsed / args.steps * 1e3]
+        for _ in range(4):
+            hi, _, _ = run.timed(args.steps, 0)
+            rep_ms.append(hi / args.steps * 1e3)
+        extras["ms_per_step_repeats"] = {"n": len(rep_ms), "steps_each": args.steps, "min": round(min(rep_ms), 4),
+                                         "median": round(statistics.median(rep_ms), 4), "max": round(max(rep_ms), 4),
+                                         "note": "ms_per_step / value are the first loop's (the contract's K steps)"}
+    if args.full and store is not None and run.gstep is not None and args.epoch_batches > 0:
         extras["epoch_sample"] = epoch_sample(run, store, args.epoch_batches, dev)
-    if store is not None and run.gstep is not None and not args.no_round3_shapes and args.epoch_batches > 0:      # (--epoch-batches 0: the traced runs, one configuration only)
+    if args.full and store is not None and run.gstep is not None and not args.no_round3_shapes and args.epoch_batches > 0:      # (--epoch-batches 0: the traced runs, one configuration only)
         # the same code under the shapes rounds 1-3 quoted their headline on (capacities from the timed pool itself + 2 %): what the
         # switch to sampled shapes costs, and the like-for-like figure against BENCH_r03
         import copy
@@ -873,7 +924,7 @@ def main():
                                                      "(646 k molecules/s, 0.792 ms in round 3); NOT the headline: a dataset's batches do not fit such shapes"}
         r3.release()
     sub_steps, sub_warm = max(5, min(args.steps, 20)), max(2, min(args.warmup, 5))
-    if dist_on:
+    if args.full and dist_on:
         extras["allreduce_alone"] = {"bytes": run.opt.nbytes, "us_per_call": round(allreduce_alone(run.opt, dev), 1),
                                      "what": "blocking all-reduce (AVG) of the flat gradient buffer, 20 back-to-back calls, max over ranks"}
         try:
@@ -897,7 +948,7 @@ def main():
         r.release()
         return out
 
-    if dist_on and not args.eager and args.shard_of <= 1:
+    if args.full and dist_on and not args.eager and args.shard_of <= 1:
         if overlap_sel == "both":
             extras["overlap_on"] = sub_run(head_scaling, True)
         if world > 1 and args.scaling == "both":
@@ -940,7 +991,7 @@ def main():
         line["step_achieved_GBps"] = round(job_bytes / (ms * 1e-3) / 1e9, 1)
         line["step_frac_of_hbm_peak"] = round(job_bytes / (ms * 1e-3) / 1e9 / (HBM_PEAK_GBPS * world), 4)
         line.update(extras)
-        if not args.no_roofline:
+        if args.full and not args.no_roofline:
             # the roofline object is quoted on the metric's configuration: a full 512-molecule batch (a rank of a strong-scaling
             # job holds only its shard)
             roof_batch = head["pool0"] if head["local_batch"] == PER_GPU_BATCH else make_pool(1, 0, dev, PER_GPU_BATCH)[0]
@@ -1082,7 +1133,7 @@ def main():
             kb = kernel_roofline(big, run.model, iters=20, alternatives=not one_pass)
             line["roofline"]["at_batch_2048"] = {k: {"us_per_launch": v["us_per_launch"], "GBps": v["GBps"],
                                                      "frac": round(v["GBps"] / HBM_PEAK_GBPS, 4)} for k, v in kb.items() if isinstance(v, dict)}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline()
             line["gpu_over_cpu"] = round(value / line["cpu_baseline"]["value"], 1)
         print(json.dumps(line), flush=True)

@@ -4,7 +4,7 @@
     cd /tmp && export TMPDIR=/tmp
     rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES SQ_WAIT_INST_ANY SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_ACTIVE_INST_ANY \\
               SQ_INSTS_VALU SQ_ACTIVE_INST_VALU --kernel-trace --output-format csv -d $REPO/gpurun_out/pmc_sq -o p \\
-              -- python3 $REPO/bench.py --steps 8 --warmup 2 --no-cpu-baseline --no-roofline
+              -- python3 $REPO/bench.py --full --steps 8 --warmup 2 --no-cpu-baseline --no-roofline
     rocprofv3 --pmc TA_BUSY_avr TA_TA_BUSY_sum GRBM_GUI_ACTIVE SQ_INSTS_VMEM SQ_INSTS_LDS SQ_INSTS_SALU \\
               --kernel-trace --output-format csv -d $REPO/gpurun_out/pmc_ta -o p -- python3 $REPO/bench.py ...(same)
     python tools/pmc_counters.py gpurun_out/pmc_sq k_linear128 > profiles/pmc_mfma_gemm.json

@@ -9,7 +9,7 @@ def main():
     d = json.load(open(sys.argv[1]))
     tag = sys.argv[2] if len(sys.argv) > 2 else "?"
     print(f"# SQ / TA counters of every kernel of the replayed training step ({tag}, final code)\n")
-    print(f"`bash tools/pmc_step_sq_ta.sh {tag}` on the GPU box: two separate `rocprofv3 --pmc ... --kernel-trace` passes over `bench.py --steps 8 --warmup 2 "
+    print(f"`bash tools/pmc_step_sq_ta.sh {tag}` on the GPU box: two separate `rocprofv3 --pmc ... --kernel-trace` passes over `bench.py --full --steps 8 --warmup 2 "
           "--no-cpu-baseline --no-roofline --epoch-batches 0 --no-round3-shapes`, means per kernel name (`tools/pmc_counters.py`; raw means in the "
           ".json beside this file).  Durations are under the counter pass (a few % above the plain trace).\n")
     print("* `MFMA busy` = SQ_VALU_MFMA_BUSY_CYCLES / (1024 SIMDs x the launch's cycles, GRBM_GUI_ACTIVE / 8): the share of SIMD-cycles the matrix pipe is busy")

@@ -4,7 +4,7 @@ the default bench command, held against the step's algorithmic bytes.
 
     cd /tmp && export TMPDIR=/tmp
     rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d /tmp/ps_fetch -o p -- python3 $REPO/bench.py --steps 8 --warmup 2 \\
-              --no-cpu-baseline --no-roofline --epoch-batches 0
+              --full --no-cpu-baseline --no-roofline --epoch-batches 0
     rocprofv3 --pmc WRITE_SIZE ... -d /tmp/ps_write ...          (separate passes: the two counters do not fit one TCC pass)
     python tools/pmc_step_traffic.py /tmp/ps_fetch /tmp/ps_write <step_algorithmic_GB> [step_sequence.txt] > profiles/r04_pmc_step.json
 

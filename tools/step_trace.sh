@@ -6,6 +6,6 @@ case "$OUT" in /*) ;; *) OUT="$R/$OUT";; esac
 mkdir -p "$(dirname "$OUT")"
 cd /tmp && export TMPDIR=/tmp
 rm -rf /tmp/pd_st
-timeout 300 rocprofv3 --kernel-trace --output-format rocpd -d /tmp/pd_st -o d -- python3 $R/bench.py --no-cpu-baseline --no-roofline "$@" > /dev/null 2>&1
+timeout 300 rocprofv3 --kernel-trace --output-format rocpd -d /tmp/pd_st -o d -- python3 $R/bench.py --full --no-cpu-baseline --no-roofline "$@" > /dev/null 2>&1
 DB=$(ls /tmp/pd_st/*/*.db /tmp/pd_st/*.db 2>/dev/null | head -1)
 python3 $R/tools/rocpd_sequence.py $DB > $OUT 2>&1
