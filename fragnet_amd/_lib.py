@@ -109,6 +109,16 @@ LOSS_MSE, LOSS_BCE = 0, 1
 SMALL_LINEAR_LOSS_MAX_K = 1024
 
 
+class HeadAct(C.Structure):
+    _fields_ = [("kind", i32), ("order", i32), ("p", f32), ("pad_", i32), ("seed", u64), ("offset", u64), ("offset_dev", vp),
+                ("prelu_w", vp), ("pre", vp), ("part", vp)]
+
+
+ACT_RELU, ACT_SILU, ACT_GELU, ACT_CELU, ACT_SELU, ACT_RELU6, ACT_LEAKYRELU, ACT_PRELU = range(8)     # FN_ACT_*
+ACT_DROP_THEN_ACT, ACT_ACT_THEN_DROP = 0, 1
+ACT_AT_DENSE_BWD, ACT_AT_SMALL_BWD, ACT_AT_SMALL_LOSS = 0, 1, 2
+
+
 class Encoder(C.Structure):
     _fields_ = [("n_layers", i32), ("heads", i32), ("k_atom0", i32), ("k_bond0", i32), ("k_fbond0", i32), ("k_fattr", i32),
                 ("training", i32), ("variant", i32), ("drop_p", f32), ("pad2_", f32), ("seed", u64), ("offset", u64), ("offset_dev", vp),
@@ -191,6 +201,12 @@ SIGNATURES = {
     "fn_small_linear_loss_f32": [vp, vp, vp, vp, vp, C.c_int, vp, vp, vp, f32, vp, i64, i64, i64, i64, vp],
     "fn_dense_bwd_tail_f32": [vp, vp, vp, vp, f32, vp, vp, i64, i64, i64, i64, C.POINTER(SmallDw), vp],
     "fn_small_linear_bwd_f32": [vp, vp, vp, vp, vp, vp, i64, i64, i64, f32, vp, vp],
+    "fn_dense_fwd_act_f32": [vp, vp, vp, vp, i64, i64, i64, C.POINTER(HeadAct), vp],
+    "fn_dense_bwd_act_f32": [vp, vp, vp, vp, C.POINTER(HeadAct), vp, vp, i64, i64, i64, i64, C.POINTER(SmallDw), vp],
+    "fn_small_linear_bwd_act_f32": [vp, vp, vp, vp, vp, vp, i64, i64, i64, C.POINTER(HeadAct), vp, vp],
+    "fn_small_linear_loss_act_f32": [vp, vp, vp, vp, vp, C.c_int, vp, vp, vp, C.POINTER(HeadAct), vp, i64, i64, i64, i64, vp],
+    "fn_head_act_parts": [C.c_int, i64, i64],
+    "fn_head_act_param_grad_f32": [vp, i64, vp, vp],
 }
 
 _lib = None
@@ -224,7 +240,7 @@ def load():
         fn.argtypes = argtypes
         if name == "fn_last_error":
             fn.restype = C.c_char_p
-        elif name.endswith("_ws") or name.endswith("_ws_floats"):
+        elif name.endswith("_ws") or name.endswith("_ws_floats") or name == "fn_head_act_parts":
             fn.restype = i64
         elif name == "fn_encoder_rng_blocks":
             fn.restype = u64

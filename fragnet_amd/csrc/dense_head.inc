@@ -45,6 +45,7 @@ struct DenseArgs {
     int lda, ldb;            // row strides (floats) of A's and Bsrc's arrays
     float gate_scale;
     fn_act_epilogue act;     // forward: y != null => OUT = relu?(dropout(.)) with act.p / seed / offset (applied in place)
+    fn_head_act hact;        // instances with a head activation kind (HA >= 0, head_act.inc): forward: this layer's; dX: the layer below's
     int tiles_i, tiles_j, first_block;
 };
 struct DensePair { DenseArgs a, b; int a_narrow, b_narrow; };      // one launch, two products (the two gradient products of a layer); a_narrow: 64 x 32 weight-gradient tiles
@@ -64,7 +65,8 @@ __device__ __forceinline__ void st2s(lds_f* p, float a, float b) { *reinterpret_
 
 // NC = 16-column groups of a forward / input-gradient tile: 4 (32 x 64) or 2 (32 x 32, for products with too few tiles to
 // occupy the chip; the input-gradient's W pieces are then 8-byte loads of columns 2n, 2n+1)
-template <int MODE, int NC = 4>
+// HA: -1 the ReLU path above (act / Z + gate_scale); >= 0 an activation kind of head_act.inc (T.hact) in the forward / input-gradient epilogue
+template <int MODE, int NC = 4, int HA = -1>
 __device__ __forceinline__ void dense_tile(const DenseArgs& T, int blk, lds_f* smem) {
     using Fr = DnFrag<MODE>;
     static_assert(NC == 4 || (NC == 2 && MODE != DN_DW), "narrow tiles exist for the forward and input-gradient products");
@@ -261,9 +263,12 @@ __device__ __forceinline__ void dense_tile(const DenseArgs& T, int blk, lds_f* s
         }
         __syncthreads();
     }
-    const bool act_on = MODE == DN_FWD && T.act.y != nullptr;
+    const bool act_on = HA < 0 && MODE == DN_FWD && T.act.y != nullptr;
     const float p = T.act.p, ik = p < 1.f ? 1.f / (1.f - p) : 0.f;
     const uint64_t rng = act_on && p > 0.f ? T.act.offset + (T.act.offset_dev ? *T.act.offset_dev : 0) : 0;
+    HactRun hr{};
+    if constexpr (HA >= 0 && MODE != DN_DW) hr = hact_run(T.hact, HA);
+    float dslope = 0.f;
     glb_f* OUT = G(T.OUT);
     constexpr int NP = MODE == DN_DW ? 4 : kDnWaves, PSZ = MODE == DN_DW ? 2 * kDnPart : 32 * TC, Q4 = TC / 4;
 #pragma unroll
@@ -279,14 +284,21 @@ __device__ __forceinline__ void dense_tile(const DenseArgs& T, int blk, lds_f* s
         }
         if (MODE == DN_DX && gi >= I && gi < T.I_out && gj < J) st4(OUT + (size_t)gi * J + gj, make_float4(0.f, 0.f, 0.f, 0.f));
         if (gi < I && gj < J) {                             // J % 4 == 0
-            if (MODE == DN_DX && T.Z) {                     // backward of the layer below's relu(dropout(.))
+            if (HA < 0 && MODE == DN_DX && T.Z) {           // backward of the layer below's relu(dropout(.))
                 const float4 z = ld4(G(T.Z) + (size_t)gi * J + gj);
                 const float gs = T.gate_scale;
                 v = make_float4(z.x > 0.f ? v.x * gs : 0.f, z.y > 0.f ? v.y * gs : 0.f, z.z > 0.f ? v.z * gs : 0.f, z.w > 0.f ? v.w * gs : 0.f);
             }
+            if constexpr (HA >= 0 && MODE == DN_DX)         // backward of the layer below's activation kind (its saved argument u)
+                v = hact_bwd4<HA>(T.hact, hr, v, ld4(G(T.hact.pre) + (size_t)gi * J + gj), (uint64_t)gi * J + gj, dslope);
             if (MODE == DN_FWD && T.bias) {
                 const float4 bb = ld4(G(T.bias) + gj);
                 v.x += bb.x;  v.y += bb.y;  v.z += bb.z;  v.w += bb.w;
+            }
+            if constexpr (HA >= 0 && MODE == DN_FWD) {
+                float4 u;
+                v = hact_fwd4<HA>(T.hact, hr, v, (uint64_t)gi * J + gj, u);
+                st4(G(T.hact.pre) + (size_t)gi * J + gj, u);
             }
             if (act_on) {
                 if (p > 0.f) {
@@ -299,6 +311,7 @@ __device__ __forceinline__ void dense_tile(const DenseArgs& T, int blk, lds_f* s
             st4(OUT + (size_t)gi * J + gj, v);
         }
     }
+    if constexpr (HA == FN_ACT_PRELU && MODE == DN_DX) hact_block_partial<kDnWaves>(dslope, T.hact.part, blk, smem);
 }
 
 // Weight-gradient tiles of 64 x 32 for layers whose 64 x 64 tiling gives too few workgroups (N = 1024, K = 128: 32 tiles; N = 128,
@@ -402,6 +415,7 @@ constexpr int kDtSlotFloats = (kDtM + kDtN) * kDtK;          // 24 KB
 constexpr int kDtPieces = (kDtM + kDtN) / 8;                 // 1-KiB pieces per slot (8 rows x 128 B each): 24 = 6 per wave
 constexpr int kDtLdsBytes = kDtSlots * kDtSlotFloats * 4;    // 96 KB: one workgroup per CU
 constexpr int kDtMinTiles = 192;
+template <int HA>
 __global__ __launch_bounds__(kDtThreads) void k_dense_fwd_tiles(const DenseArgs T) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int tid = threadIdx.x, l = tid & 63, n = l & 15, g = l >> 4;
@@ -464,9 +478,11 @@ __global__ __launch_bounds__(kDtThreads) void k_dense_fwd_tiles(const DenseArgs 
         }
     }
     // acc[4 t + u][e] = (row 32 tr + 16 t + 4 g + e, column 64 tc + 4 n + u) of the tile
-    const bool act_on = T.act.y != nullptr;
+    const bool act_on = HA < 0 && T.act.y != nullptr;
     const float p = T.act.p, ik = p < 1.f ? 1.f / (1.f - p) : 0.f;
     const uint64_t rng = act_on && p > 0.f ? T.act.offset + (T.act.offset_dev ? *T.act.offset_dev : 0) : 0;
+    HactRun hr{};
+    if constexpr (HA >= 0) hr = hact_run(T.hact, HA);
     glb_f* OUT = G(T.OUT);
     const int gj = j0 + 64 * tc + 4 * n;
     float4 bb = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -486,14 +502,20 @@ __global__ __launch_bounds__(kDtThreads) void k_dense_fwd_tiles(const DenseArgs 
                 }
                 if (T.act.relu) { v.x = fmaxf(v.x, 0.f);  v.y = fmaxf(v.y, 0.f);  v.z = fmaxf(v.z, 0.f);  v.w = fmaxf(v.w, 0.f); }
             }
+            if constexpr (HA >= 0) {
+                float4 u;
+                v = hact_fwd4<HA>(T.hact, hr, v, (uint64_t)gi * N + gj, u);
+                st4(G(T.hact.pre) + ((size_t)gi * N + gj), u);
+            }
             st4(OUT + ((size_t)gi * N + gj), v);
         }
 }
 
+template <int HA>
 __global__ __launch_bounds__(kDnThreads, 4) void k_dense_fwd(const DenseArgs T, const int narrow) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
-    if (narrow) dense_tile<DN_FWD, 2>(T, (int)blockIdx.x, (lds_f*)smem);
-    else dense_tile<DN_FWD, 4>(T, (int)blockIdx.x, (lds_f*)smem);
+    if (narrow) dense_tile<DN_FWD, 2, HA>(T, (int)blockIdx.x, (lds_f*)smem);
+    else dense_tile<DN_FWD, 4, HA>(T, (int)blockIdx.x, (lds_f*)smem);
 }
 // What the fused last Linear + loss launch (k_small_linear_loss) leaves for "the next launch": dW[C,K] = g^T x, db[C] = colsum(g) and the
 // loss value from its per-block partials.  These blocks ride at the end of the first k_dense_bwd launch of the head's backward.
@@ -582,11 +604,13 @@ __device__ __forceinline__ void small_dw_block(const SmallDw& S, int vb, lds_f* 
 
 // the two gradient products of a layer in one launch: blocks [0, b.first_block) the weight gradient, the rest the input gradient
 // (and, behind those, the riders of the fused last Linear: SmallDw)
+// (HA >= 0: the input gradient goes through the layer below's activation kind, head_act.inc)
+template <int HA>
 __global__ __launch_bounds__(kDnThreads, 4) void k_dense_bwd(const DensePair P, const SmallDw S) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int b = (int)blockIdx.x;
     if (S.first_block >= 0 && b >= S.first_block) { small_dw_block(S, b - S.first_block, (lds_f*)smem);  return; }
     if (b < P.b.first_block) { if (P.a_narrow) dense_dw_narrow(P.a, b, (lds_f*)smem); else dense_tile<DN_DW>(P.a, b, (lds_f*)smem); }
-    else if (P.b_narrow) dense_tile<DN_DX, 2>(P.b, b - P.b.first_block, (lds_f*)smem);
-    else dense_tile<DN_DX, 4>(P.b, b - P.b.first_block, (lds_f*)smem);
+    else if (P.b_narrow) dense_tile<DN_DX, 2, HA>(P.b, b - P.b.first_block, (lds_f*)smem);
+    else dense_tile<DN_DX, 4, HA>(P.b, b - P.b.first_block, (lds_f*)smem);
 }

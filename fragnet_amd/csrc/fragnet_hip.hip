@@ -848,16 +848,19 @@ __global__ __launch_bounds__(256) void k_small_linear(const float* __restrict__ 
     }
 }
 
+#include "head_act.inc"
+
 // backward of the above in one launch: g_x[m, k] = sum_c g[m, c] w[c, k];  dW[c, k] = sum_m g[m, c] x[m, k];
 // db[c] = sum_m g[m, c].  A block owns 16 columns k for all rows (deterministic sums, 64 rows in flight);
-// CM >= C bounds the registers.
-template <int CM>
+// CM >= C bounds the registers.  HACT: g_x goes through the activation kind `below` (head_act.inc) instead of the ReLU gate.
+template <int CM, bool HACT>
 __global__ __launch_bounds__(256) void k_small_linear_bwd(const float* __restrict__ g, const float* __restrict__ x,
                                                           const float* __restrict__ w, float* __restrict__ g_x,
                                                           float* __restrict__ dW, float* __restrict__ db, int64_t M, int K, int C,
-                                                          int64_t rows_per_chunk, float gate_scale) {
+                                                          int64_t rows_per_chunk, float gate_scale, const fn_head_act below) {
     // blockIdx.y = row chunk: dW / db then point at per-chunk partials [chunk][C*K] / [chunk][C] (k_sum_chunks finishes)
     __shared__ float4 sm[64][4];
+    __shared__ float s_slope[4];
     const int c4 = threadIdx.x & 3, rl = threadIdx.x >> 2;           // 4 float4 columns x 64 row lanes
     const int col = blockIdx.x * 16 + c4 * 4;
     const bool live = col < K;
@@ -866,6 +869,9 @@ __global__ __launch_bounds__(256) void k_small_linear_bwd(const float* __restric
     dW += (size_t)blockIdx.y * C * K;
     db += (size_t)blockIdx.y * C;
     float4 wv[CM], acc[CM];
+    HactRun hr{};
+    if (HACT) hr = hact_run(below, below.kind);
+    float dslope = 0.f;
 #pragma unroll
     for (int c = 0; c < CM; ++c) {
         wv[c] = (live && c < C) ? ld4(w + (size_t)c * K + col) : make_float4(0.f, 0.f, 0.f, 0.f);
@@ -897,7 +903,8 @@ __global__ __launch_bounds__(256) void k_small_linear_bwd(const float* __restric
                         acc[c].x += gv[u][c] * xv[u].x; acc[c].y += gv[u][c] * xv[u].y; acc[c].z += gv[u][c] * xv[u].z; acc[c].w += gv[u][c] * xv[u].w;
                     }
                 }
-                if (gate_scale > 0.f) {                             // x = relu(dropout(.)) of the layer below: its backward, fused
+                if (HACT) o = hact_bwd4_rt(below, hr, o, ld4(below.pre + m * K + col), (uint64_t)(m * K + col), dslope);
+                else if (gate_scale > 0.f) {                        // x = relu(dropout(.)) of the layer below: its backward, fused
                     o.x = xv[u].x > 0.f ? o.x * gate_scale : 0.f;  o.y = xv[u].y > 0.f ? o.y * gate_scale : 0.f;
                     o.z = xv[u].z > 0.f ? o.z * gate_scale : 0.f;  o.w = xv[u].w > 0.f ? o.w * gate_scale : 0.f;
                 }
@@ -927,6 +934,7 @@ __global__ __launch_bounds__(256) void k_small_linear_bwd(const float* __restric
             if (lane == 0) db[c] = t;
         }
     }
+    if (HACT && below.kind == FN_ACT_PRELU) hact_block_partial<4>(dslope, below.part, (int)(blockIdx.y * gridDim.x + blockIdx.x), s_slope);
 }
 
 // The last Linear of a head, the loss on its outputs and that Linear's INPUT gradient in one launch (round 4; VERDICT r3 item 4: three
@@ -937,13 +945,17 @@ __global__ __launch_bounds__(256) void k_small_linear_bwd(const float* __restric
 // call carries the blocks, dense_head.inc small_dw_*): dW = g^T x, db = colsum(g), and the loss value as per-block partial sums
 // (already divided by the denominator).  No ticket, no atomic: fixed-order sums only.  Numbers: y, g, g_x are bit-identical to
 // fn_small_linear_f32 -> fn_masked_mse/bce_f32 -> fn_small_linear_bwd_f32 (same operation order).
-template <int CM>
+// HACT: g_x goes through the activation kind `below` (head_act.inc) instead of the ReLU gate.
+template <int CM, bool HACT>
 __global__ __launch_bounds__(256) void k_small_linear_loss(const float* __restrict__ x, const float* __restrict__ w, const float* __restrict__ b,
                                                            const float* __restrict__ target, const float* __restrict__ row_w, const int kind,
                                                            float* __restrict__ y, float* __restrict__ g, float* __restrict__ g_x,
                                                            const float gate_scale, float* __restrict__ loss_part, const int64_t M, const int K,
-                                                           const int C, const int64_t M_out) {
-    __shared__ float s4[4];
+                                                           const int C, const int64_t M_out, const fn_head_act below) {
+    __shared__ float s4[4], s_slope[4];
+    HactRun hr{};
+    if (HACT) hr = hact_run(below, below.kind);
+    float dslope = 0.f;
     __shared__ float sden;
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     float cnt = 0.f;
@@ -1006,7 +1018,8 @@ __global__ __launch_bounds__(256) void k_small_linear_loss(const float* __restri
                         o.x += gc[c] * wc.x; o.y += gc[c] * wc.y; o.z += gc[c] * wc.z; o.w += gc[c] * wc.w;
                     }
                 }
-                if (gate_scale > 0.f) {                              // x = relu(dropout(.)) of the layer below: its backward, fused
+                if (HACT) o = hact_bwd4_rt(below, hr, o, ld4(below.pre + row * K + 4 * j), (uint64_t)(row * K + 4 * j), dslope);
+                else if (gate_scale > 0.f) {                         // x = relu(dropout(.)) of the layer below: its backward, fused
                     o.x = xv[q].x > 0.f ? o.x * gate_scale : 0.f;  o.y = xv[q].y > 0.f ? o.y * gate_scale : 0.f;
                     o.z = xv[q].z > 0.f ? o.z * gate_scale : 0.f;  o.w = xv[q].w > 0.f ? o.w * gate_scale : 0.f;
                 }
@@ -1019,6 +1032,7 @@ __global__ __launch_bounds__(256) void k_small_linear_loss(const float* __restri
     if (lane == 0) s4[wv] = lsum;
     __syncthreads();
     if (threadIdx.x == 0) loss_part[blockIdx.x] = ((s4[0] + s4[1]) + (s4[2] + s4[3])) / den;
+    if (HACT && below.kind == FN_ACT_PRELU) hact_block_partial<4>(dslope, below.part, (int)blockIdx.x, s_slope);
 }
 
 #include "linear128.inc"
@@ -2206,8 +2220,16 @@ int64_t fn_small_linear_bwd_ws(int64_t M, int64_t K, int64_t C) {
     return ch > 1 ? ch * C * (K + 1) : 0;
 }
 
-int fn_small_linear_bwd_f32(const float* g, const float* x, const float* w, float* g_x, float* dW, float* db, int64_t M, int64_t K,
-                            int64_t C, float gate_scale, float* ws, fn_stream_t stream) {
+// the activation handed to a backward as `below`: a known kind and order, its saved argument, the PReLU slope and partials
+static bool head_act_ok(const fn_head_act* h, bool need_part) {
+    return h->kind >= FN_ACT_RELU && h->kind <= FN_ACT_PRELU && (h->order == FN_ACT_DROP_THEN_ACT || h->order == FN_ACT_ACT_THEN_DROP) &&
+           h->p >= 0.f && h->p <= 1.f && h->pre && !((uintptr_t)h->pre & 15) &&
+           (h->kind != FN_ACT_PRELU || (h->prelu_w && (!need_part || h->part)));
+}
+
+static int small_linear_bwd(const float* g, const float* x, const float* w, float* g_x, float* dW, float* db, int64_t M, int64_t K,
+                            int64_t C, float gate_scale, const fn_head_act* below, float* ws, fn_stream_t stream) {
+    if (below && !head_act_ok(below, true)) return fail(FN_EINVAL, "fn_small_linear_bwd_act_f32: bad activation");
     if (M < 0 || K < 4 || (K & 3) || K > INT32_MAX || C < 1 || C > FN_SMALL_LINEAR_MAX)
         return fail(FN_EINVAL, "fn_small_linear_bwd_f32: K must be a multiple of 4 and 1 <= C <= FN_SMALL_LINEAR_MAX");
     if (!w || !dW || !db || (M > 0 && (!g || !x || !g_x)) || (((uintptr_t)x | (uintptr_t)w | (uintptr_t)g_x | (uintptr_t)dW | (uintptr_t)ws) & 15))
@@ -2218,9 +2240,14 @@ int fn_small_linear_bwd_f32(const float* g, const float* x, const float* w, floa
     float* db_o = ch > 1 ? ws + ch * C * K : db;
     const int64_t rpc = ch > 1 ? kTallChunk : (M > 0 ? M : 1);
     const dim3 grid((unsigned)((K + 15) / 16), (unsigned)ch);
-    if (C <= 1) hipLaunchKernelGGL(k_small_linear_bwd<1>, grid, dim3(256), 0, S(stream), g, x, w, g_x, dW_o, db_o, M, (int)K, (int)C, rpc, gate_scale);
-    else if (C <= 4) hipLaunchKernelGGL(k_small_linear_bwd<4>, grid, dim3(256), 0, S(stream), g, x, w, g_x, dW_o, db_o, M, (int)K, (int)C, rpc, gate_scale);
-    else hipLaunchKernelGGL(k_small_linear_bwd<FN_SMALL_LINEAR_MAX>, grid, dim3(256), 0, S(stream), g, x, w, g_x, dW_o, db_o, M, (int)K, (int)C, rpc, gate_scale);
+    const fn_head_act h = below ? *below : fn_head_act{};
+#define FN_SLB(CM, HA) hipLaunchKernelGGL((k_small_linear_bwd<CM, HA>), grid, dim3(256), 0, S(stream), g, x, w, g_x, dW_o, db_o, M, (int)K, (int)C, rpc, gate_scale, h)
+    if (below && M > 0) {
+        if (C <= 1) FN_SLB(1, true); else if (C <= 4) FN_SLB(4, true); else FN_SLB(FN_SMALL_LINEAR_MAX, true);
+    } else {
+        if (C <= 1) FN_SLB(1, false); else if (C <= 4) FN_SLB(4, false); else FN_SLB(FN_SMALL_LINEAR_MAX, false);
+    }
+#undef FN_SLB
     if (ch > 1) {
         hipLaunchKernelGGL(k_sum_chunks, dim3((unsigned)((C * K + 15) / 16)), dim3(256), 0, S(stream), ws, (int)ch, C * K, dW);
         hipLaunchKernelGGL(k_sum_chunks, dim3((unsigned)((C + 15) / 16)), dim3(256), 0, S(stream), ws + ch * C * K, (int)ch, C, db);
@@ -2228,11 +2255,22 @@ int fn_small_linear_bwd_f32(const float* g, const float* x, const float* w, floa
     return launch_status("fn_small_linear_bwd_f32");
 }
 
+int fn_small_linear_bwd_f32(const float* g, const float* x, const float* w, float* g_x, float* dW, float* db, int64_t M, int64_t K,
+                            int64_t C, float gate_scale, float* ws, fn_stream_t stream) {
+    return small_linear_bwd(g, x, w, g_x, dW, db, M, K, C, gate_scale, nullptr, ws, stream);
+}
+
+int fn_small_linear_bwd_act_f32(const float* g, const float* x, const float* w, float* g_x, float* dW, float* db, int64_t M, int64_t K,
+                                int64_t C, const fn_head_act* below, float* ws, fn_stream_t stream) {
+    return small_linear_bwd(g, x, w, g_x, dW, db, M, K, C, 0.f, below, ws, stream);
+}
+
 int64_t fn_small_linear_loss_ws(int64_t M_out) { return M_out > 0 ? (M_out + 3) / 4 : 0; }
 
-int fn_small_linear_loss_f32(const float* x, const float* w, const float* b, const float* target, const float* row_w, int kind,
-                             float* y, float* g, float* g_x, float gate_scale, float* loss_part, int64_t M, int64_t K, int64_t C,
-                             int64_t M_out, fn_stream_t stream) {
+static int small_linear_loss(const float* x, const float* w, const float* b, const float* target, const float* row_w, int kind,
+                             float* y, float* g, float* g_x, float gate_scale, const fn_head_act* below, float* loss_part, int64_t M,
+                             int64_t K, int64_t C, int64_t M_out, fn_stream_t stream) {
+    if (below && !head_act_ok(below, true)) return fail(FN_EINVAL, "fn_small_linear_loss_act_f32: bad activation");
     if (M < 0 || K < 4 || (K & 3) || K > FN_SMALL_LINEAR_LOSS_MAX_K || C < 1 || C > FN_SMALL_LINEAR_MAX || (kind != FN_LOSS_MSE && kind != FN_LOSS_BCE))
         return fail(FN_EINVAL, "fn_small_linear_loss_f32: K a multiple of 4 and <= FN_SMALL_LINEAR_LOSS_MAX_K, 1 <= C <= FN_SMALL_LINEAR_MAX, kind MSE or BCE");
     if (M_out < M) M_out = M;
@@ -2241,10 +2279,27 @@ int fn_small_linear_loss_f32(const float* x, const float* w, const float* b, con
         (((uintptr_t)x | (uintptr_t)w | (uintptr_t)g_x) & 15))
         return fail(FN_EINVAL, "fn_small_linear_loss_f32: null or misaligned buffer");
     const dim3 grid((unsigned)fn_small_linear_loss_ws(M_out));
-    if (C <= 1) hipLaunchKernelGGL(k_small_linear_loss<1>, grid, dim3(256), 0, S(stream), x, w, b, target, row_w, kind, y, g, g_x, gate_scale, loss_part, M, (int)K, (int)C, M_out);
-    else if (C <= 4) hipLaunchKernelGGL(k_small_linear_loss<4>, grid, dim3(256), 0, S(stream), x, w, b, target, row_w, kind, y, g, g_x, gate_scale, loss_part, M, (int)K, (int)C, M_out);
-    else hipLaunchKernelGGL(k_small_linear_loss<FN_SMALL_LINEAR_MAX>, grid, dim3(256), 0, S(stream), x, w, b, target, row_w, kind, y, g, g_x, gate_scale, loss_part, M, (int)K, (int)C, M_out);
+    const fn_head_act h = below ? *below : fn_head_act{};
+#define FN_SLL(CM, HA) hipLaunchKernelGGL((k_small_linear_loss<CM, HA>), grid, dim3(256), 0, S(stream), x, w, b, target, row_w, kind, y, g, g_x, gate_scale, loss_part, M, (int)K, (int)C, M_out, h)
+    if (below) {
+        if (C <= 1) FN_SLL(1, true); else if (C <= 4) FN_SLL(4, true); else FN_SLL(FN_SMALL_LINEAR_MAX, true);
+    } else {
+        if (C <= 1) FN_SLL(1, false); else if (C <= 4) FN_SLL(4, false); else FN_SLL(FN_SMALL_LINEAR_MAX, false);
+    }
+#undef FN_SLL
     return launch_status("fn_small_linear_loss_f32");
+}
+
+int fn_small_linear_loss_f32(const float* x, const float* w, const float* b, const float* target, const float* row_w, int kind,
+                             float* y, float* g, float* g_x, float gate_scale, float* loss_part, int64_t M, int64_t K, int64_t C,
+                             int64_t M_out, fn_stream_t stream) {
+    return small_linear_loss(x, w, b, target, row_w, kind, y, g, g_x, gate_scale, nullptr, loss_part, M, K, C, M_out, stream);
+}
+
+int fn_small_linear_loss_act_f32(const float* x, const float* w, const float* b, const float* target, const float* row_w, int kind,
+                                 float* y, float* g, float* g_x, const fn_head_act* below, float* loss_part, int64_t M, int64_t K,
+                                 int64_t C, int64_t M_out, fn_stream_t stream) {
+    return small_linear_loss(x, w, b, target, row_w, kind, y, g, g_x, 0.f, below, loss_part, M, K, C, M_out, stream);
 }
 
 // (static, not an anonymous namespace: inside this extern "C" block clang gives a namespace-scope function C linkage and exports it)
@@ -2253,29 +2308,61 @@ static bool dense_shape_ok(int64_t M, int64_t K, int64_t N) {
 }
 static int dense_tiles(int64_t n, int t) { return (int)((n + t - 1) / t); }
 
-int fn_dense_fwd_f32(const float* X, const float* W, const float* bias, float* Y, int64_t M, int64_t K, int64_t N,
-                     const fn_act_epilogue* act, fn_stream_t stream) {
+// the instances of a head activation kind (HA = -1: the ReLU path of fn_act_epilogue / gate_scale)
+typedef void (*DenseFwdK)(const DenseArgs, const int);
+typedef void (*DenseTilesK)(const DenseArgs);
+typedef void (*DenseBwdK)(const DensePair, const SmallDw);
+#define FN_HA_PICK(KER, HA)                                                                                                   \
+    switch (HA) {                                                                                                             \
+        case FN_ACT_RELU: return KER<FN_ACT_RELU>;  case FN_ACT_SILU: return KER<FN_ACT_SILU>;                                \
+        case FN_ACT_GELU: return KER<FN_ACT_GELU>;  case FN_ACT_CELU: return KER<FN_ACT_CELU>;                                \
+        case FN_ACT_SELU: return KER<FN_ACT_SELU>;  case FN_ACT_RELU6: return KER<FN_ACT_RELU6>;                              \
+        case FN_ACT_LEAKYRELU: return KER<FN_ACT_LEAKYRELU>;  case FN_ACT_PRELU: return KER<FN_ACT_PRELU>;                    \
+        default: return KER<-1>;                                                                                              \
+    }
+static DenseFwdK dense_fwd_k(int ha) { FN_HA_PICK(k_dense_fwd, ha) }
+static DenseTilesK dense_tiles_k(int ha) { FN_HA_PICK(k_dense_fwd_tiles, ha) }
+static DenseBwdK dense_bwd_k(int ha) { FN_HA_PICK(k_dense_bwd, ha) }
+#undef FN_HA_PICK
+
+static int dense_fwd(const float* X, const float* W, const float* bias, float* Y, int64_t M, int64_t K, int64_t N,
+                     const fn_act_epilogue* act, const fn_head_act* hact, fn_stream_t stream) {
     if (!dense_shape_ok(M, K, N)) return fail(FN_EINVAL, "fn_dense_fwd_f32: K and N must be multiples of 4, M <= FN_DENSE_MAX_ROWS");
     if (M == 0) return 0;
     if (!X || !W || !Y || (((uintptr_t)X | (uintptr_t)W | (uintptr_t)Y | (uintptr_t)bias) & 15))
         return fail(FN_EINVAL, "fn_dense_fwd_f32: null or misaligned buffer");
     if (act && (act->p < 0.f || act->p > 1.f)) return fail(FN_EINVAL, "fn_dense_fwd_f32: dropout probability outside [0, 1]");
+    if (hact && !head_act_ok(hact, false)) return fail(FN_EINVAL, "fn_dense_fwd_act_f32: bad activation (kind, order, p, pre, prelu_w)");
     DenseArgs T{};
     T.A = X;  T.Bsrc = W;  T.bias = bias;  T.OUT = Y;
     T.I = (int)M;  T.J = (int)N;  T.R = (int)K;  T.lda = (int)K;  T.ldb = (int)K;
     if (act) { T.act = *act;  T.act.y = Y; }
+    const int ha = hact ? hact->kind : -1;
+    if (hact) T.hact = *hact;
     // tall inputs: workgroup-shared 64 x 128 operand tiles (dense_head.inc, k_dense_fwd_tiles).  32-bit element offsets as elsewhere
     if (g_tune[FN_TUNE_DENSE_TILES] != 0 && K % kDtK == 0 && dense_tiles(M, kDtM) * dense_tiles(N, kDtN) >= kDtMinTiles) {
         T.tiles_i = dense_tiles(M, kDtM);  T.tiles_j = dense_tiles(N, kDtN);
-        if (int rc = allow_lds(k_dense_fwd_tiles, kDtLdsBytes)) return rc;
-        hipLaunchKernelGGL(k_dense_fwd_tiles, dim3((unsigned)(8 * ((T.tiles_i * T.tiles_j + 7) / 8))), dim3(kDtThreads), kDtLdsBytes, S(stream), T);
+        const DenseTilesK kern = dense_tiles_k(ha);
+        if (int rc = allow_lds(kern, kDtLdsBytes)) return rc;
+        hipLaunchKernelGGL(kern, dim3((unsigned)(8 * ((T.tiles_i * T.tiles_j + 7) / 8))), dim3(kDtThreads), kDtLdsBytes, S(stream), T);
         return launch_status("fn_dense_fwd_f32 (workgroup-shared tiles)");
     }
     T.tiles_i = dense_tiles(M, 32);  T.tiles_j = dense_tiles(N, kDnCols);
     const int narrow = T.tiles_i * T.tiles_j < 192;      // too few 32 x 64 tiles to occupy the chip: 32 x 32
     if (narrow) T.tiles_j = dense_tiles(N, 32);
-    hipLaunchKernelGGL(k_dense_fwd, dim3((unsigned)(T.tiles_i * T.tiles_j)), dim3(kDnThreads), kDnLdsBytes, S(stream), T, narrow);
+    hipLaunchKernelGGL(dense_fwd_k(ha), dim3((unsigned)(T.tiles_i * T.tiles_j)), dim3(kDnThreads), kDnLdsBytes, S(stream), T, narrow);
     return launch_status("fn_dense_fwd_f32");
+}
+
+int fn_dense_fwd_f32(const float* X, const float* W, const float* bias, float* Y, int64_t M, int64_t K, int64_t N,
+                     const fn_act_epilogue* act, fn_stream_t stream) {
+    return dense_fwd(X, W, bias, Y, M, K, N, act, nullptr, stream);
+}
+
+int fn_dense_fwd_act_f32(const float* X, const float* W, const float* bias, float* Y, int64_t M, int64_t K, int64_t N,
+                         const fn_head_act* act, fn_stream_t stream) {
+    if (!act) return fail(FN_EINVAL, "fn_dense_fwd_act_f32: act is required");
+    return dense_fwd(X, W, bias, Y, M, K, N, nullptr, act, stream);
 }
 
 int fn_dense_bwd_f32(const float* g_y, const float* X, const float* W, float* g_x, float gate_scale, float* dW, float* db,
@@ -2283,8 +2370,15 @@ int fn_dense_bwd_f32(const float* g_y, const float* X, const float* W, float* g_
     return fn_dense_bwd_tail_f32(g_y, X, W, g_x, gate_scale, dW, db, M, K, N, M_out, nullptr, stream);
 }
 
-int fn_dense_bwd_tail_f32(const float* g_y, const float* X, const float* W, float* g_x, float gate_scale, float* dW, float* db,
-                          int64_t M, int64_t K, int64_t N, int64_t M_out, const fn_small_dw* tail, fn_stream_t stream) {
+// the DX tiles of a dense backward with M_out rows and K input features (the tiling below)
+static void dense_dx_tiles(int64_t M_out, int64_t K, int* tiles_i, int* tiles_j, int* narrow) {
+    *tiles_i = dense_tiles(M_out, 32);  *tiles_j = dense_tiles(K, kDnCols);  *narrow = 0;
+    if (*tiles_i * *tiles_j < 192) { *narrow = 1;  *tiles_j = dense_tiles(K, 32); }
+}
+
+static int dense_bwd(const float* g_y, const float* X, const float* W, float* g_x, float gate_scale, const fn_head_act* below, float* dW,
+                     float* db, int64_t M, int64_t K, int64_t N, int64_t M_out, const fn_small_dw* tail, fn_stream_t stream) {
+    if (below && !head_act_ok(below, true)) return fail(FN_EINVAL, "fn_dense_bwd_act_f32: bad activation (kind, order, p, pre, prelu_w, part)");
     if (!dense_shape_ok(M, K, N)) return fail(FN_EINVAL, "fn_dense_bwd_f32: K and N must be multiples of 4, M <= FN_DENSE_MAX_ROWS");
     SmallDw sd{};
     sd.first_block = -1;
@@ -2310,6 +2404,7 @@ int fn_dense_bwd_tail_f32(const float* g_y, const float* X, const float* W, floa
     }
     int blocks = a.tiles_i * a.tiles_j;
     P.b.first_block = blocks;
+    int ha = -1;                                         // the instance: the layer below's activation kind once there is an input gradient
     if (M_out < M) M_out = M;
     if (M_out > FN_DENSE_MAX_ROWS) return fail(FN_EINVAL, "fn_dense_bwd_f32: M_out > FN_DENSE_MAX_ROWS");
     if (g_x && M_out > 0 && M == 0) {                    // no input rows: the padding rows of g_x are all there is, and they are zero
@@ -2320,16 +2415,41 @@ int fn_dense_bwd_tail_f32(const float* g_y, const float* X, const float* W, floa
         DenseArgs& b = P.b;                              // gX [M,K] = gy W, gated by X > 0
         b.A = g_y;  b.Bsrc = W;  b.OUT = g_x;  b.Z = gate_scale > 0.f ? X : nullptr;  b.gate_scale = gate_scale;
         b.I = (int)M;  b.I_out = (int)M_out;  b.J = (int)K;  b.R = (int)N;  b.lda = (int)N;  b.ldb = (int)K;
-        b.tiles_i = dense_tiles(M_out, 32);  b.tiles_j = dense_tiles(K, kDnCols);
-        if (b.tiles_i * b.tiles_j < 192) { P.b_narrow = 1;  b.tiles_j = dense_tiles(K, 32); }
+        if (below) ha = below->kind, b.hact = *below;
+        dense_dx_tiles(M_out, K, &b.tiles_i, &b.tiles_j, &P.b_narrow);
         blocks += b.tiles_i * b.tiles_j;
     }
     if (tail) {
         sd.first_block = blocks;
         blocks += (sd.K + 15) / 16 + 1;
     }
-    hipLaunchKernelGGL(k_dense_bwd, dim3((unsigned)blocks), dim3(kDnThreads), kDnLdsBytes, S(stream), P, sd);
+    hipLaunchKernelGGL(dense_bwd_k(ha), dim3((unsigned)blocks), dim3(kDnThreads), kDnLdsBytes, S(stream), P, sd);
     return launch_status("fn_dense_bwd_f32");
+}
+
+int fn_dense_bwd_tail_f32(const float* g_y, const float* X, const float* W, float* g_x, float gate_scale, float* dW, float* db,
+                          int64_t M, int64_t K, int64_t N, int64_t M_out, const fn_small_dw* tail, fn_stream_t stream) {
+    return dense_bwd(g_y, X, W, g_x, gate_scale, nullptr, dW, db, M, K, N, M_out, tail, stream);
+}
+
+int fn_dense_bwd_act_f32(const float* g_y, const float* X, const float* W, float* g_x, const fn_head_act* below, float* dW, float* db,
+                         int64_t M, int64_t K, int64_t N, int64_t M_out, const fn_small_dw* tail, fn_stream_t stream) {
+    return dense_bwd(g_y, X, W, g_x, 0.f, below, dW, db, M, K, N, M_out, tail, stream);
+}
+
+int64_t fn_head_act_parts(int where, int64_t rows, int64_t K) {
+    if (rows <= 0 || K <= 0) return 0;
+    if (where == FN_ACT_AT_SMALL_LOSS) return fn_small_linear_loss_ws(rows);
+    if (where == FN_ACT_AT_SMALL_BWD) return ((K + 15) / 16) * tall_chunks(rows);
+    int ti, tj, narrow;
+    dense_dx_tiles(rows, K, &ti, &tj, &narrow);
+    return (int64_t)ti * tj;
+}
+
+int fn_head_act_param_grad_f32(const float* part, int64_t n, float* grad, fn_stream_t stream) {
+    if (n < 0 || !grad || (n > 0 && !part)) return fail(FN_EINVAL, "fn_head_act_param_grad_f32: bad argument");
+    hipLaunchKernelGGL(k_head_act_param_grad, dim3(1), dim3(256), 0, S(stream), part, n, grad);
+    return launch_status("fn_head_act_param_grad_f32");
 }
 
 int fn_adam_f32(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2, float eps,

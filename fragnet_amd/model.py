@@ -13,7 +13,8 @@ order) are the reference's, so the same seed gives the same weights and referenc
 §3.3 -- two scalars per node and head, one scalar per edge and head, a destination-sorted segmented
 softmax-aggregate -- run by libfragnet_hip.so (fragnet_amd/ops.py); no [E, H, 3d] message tensor exists.
 Dense projections are the fp32-MFMA kernels of the library (ops.linear128; inside the engine they ride in the attention launches),
-ReLU heads the hand-written dense kernels (ops.mlp_head); only heads with other activations fall to torch.nn.functional.linear.
+the prediction heads the hand-written dense kernels (ops.mlp_head) for every `act` but rrelu, whose training slopes come from
+torch's generator; it, and inputs taller than the dense kernels take, stay on torch.nn.functional.linear.
 The parameters the reference constructs but never reads are constructed too and stay
 without gradient, exactly as there.  GPU tensors only: there is no CPU fallback.
 """
@@ -25,7 +26,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from . import engine, ops
+from . import _lib, engine, ops
 from ._lib import FN_D
 from .plan import LIVE_MOLS_KEY, plan_for
 
@@ -340,7 +341,45 @@ class FragNet(nn.Module):
 
 
 # ------------------------------------------------------------------------------------ heads
-class FTHead1(nn.Sequential):
+class _FusedHead:
+    """What the heads share for the hand-written path (ops.mlp_head): the attributes an owner sets, and the call."""
+
+    rng = None       # the encoder's Philox stream when the owning model attaches it (FragNetFineTune does)
+    live_rows = None  # set per call by the owning model: input rows >= live_rows are padding, their outputs are 0
+    loss_spec = None  # (kind, target, row weights) set per call by a training step that backpropagates the loss with gradient 1 right
+                      # away (graphstep.GraphedTrainStep): the last Linear, the loss and that Linear's backward then share a launch
+                      # (ops.mlp_head); the returned predictions carry the loss as ``_fragnet_loss``
+    _relu_any_dropout = False   # True: the ReLU kind takes the kernels whatever module sits in ``self.dropout`` (it reads its .p only)
+
+    def _fused_kind(self, enc, linears):
+        """the activation kind when ``linears`` run through ops.mlp_head, else None (torch): no Philox stream, CPU rows, rrelu, a
+        Linear without bias or a hidden width that is not a multiple of 4, a ``dropout`` that is not a plain nn.Dropout (a module put
+        in its place -- mask injection, a probe -- is called as before), and -- for the kinds other than ReLU -- shapes the dense
+        kernels do not take"""
+        kind = ops.head_act_kind(self.activation)
+        if self.rng is None or kind is None or not enc.is_cuda or any(l.bias is None for l in linears) \
+                or any(l.out_features % 4 != 0 for l in linears[:-1]):
+            return None
+        if type(self.dropout) is not nn.Dropout and not (kind == _lib.ACT_RELU and self._relu_any_dropout):
+            return None
+        if kind != _lib.ACT_RELU:
+            rows = enc.shape[0] if self.live_rows is None else max(0, min(int(self.live_rows), enc.shape[0]))
+            if not ops.mlp_head_dense_ok(rows, linears):
+                return None
+        return kind
+
+    def _fused(self, enc, linears, kind, order=_lib.ACT_DROP_THEN_ACT, in_drop=False):
+        act = None if kind == _lib.ACT_RELU else self.activation
+        kw = dict(act=act, order=order, in_drop=in_drop)
+        if self.loss_spec is not None:
+            out, loss = ops.mlp_head(enc, linears, self.dropout.p, self.training, self.rng, self.live_rows, loss=self.loss_spec, **kw)
+            if loss is not None:
+                out._fragnet_loss = (loss, self.loss_spec[1], self.loss_spec[2])
+            return out
+        return ops.mlp_head(enc, linears, self.dropout.p, self.training, self.rng, self.live_rows, **kw)     # one autograd node
+
+
+class FTHead1(_FusedHead, nn.Sequential):
     def __init__(self, emb_dim=128, h1=128, drop_ratio=0.2, n_classes=1):
         super().__init__()
         self.lin1 = nn.Linear(emb_dim * 2, h1)
@@ -349,29 +388,26 @@ class FTHead1(nn.Sequential):
         self.activation = nn.ReLU()
 
     def forward(self, enc):
+        linears = [self.lin1, self.out]
+        kind = self._fused_kind(enc, linears)
+        if kind is not None:       # dropout(relu(.)) = relu(dropout(.)) bit for bit: the ReLU instances behind an input dropout
+            return self._fused(enc, linears, kind, _lib.ACT_ACT_THEN_DROP, in_drop=True)
         return self.out(self.dropout(self.activation(self.lin1(self.dropout(enc)))))
 
 
-class _PredictorStack(nn.Sequential):
+class _PredictorStack(_FusedHead, nn.Sequential):
     """act(dropout(linear(x))) between layers, plain last layer -- gat2.py:631-637, 719-725, 745-751."""
 
-    rng = None       # the encoder's Philox stream when the owning model attaches it (FragNetFineTune does)
-    live_rows = None  # set per call by the owning model: input rows >= live_rows are padding, their outputs are 0
-    loss_spec = None  # (kind, target, row weights) set per call by a training step that backpropagates the loss with gradient 1 right
-                      # away (graphstep.GraphedTrainStep): the last Linear, the loss and that Linear's backward then share a launch
-                      # (ops.mlp_head); the returned predictions carry the loss as ``_fragnet_loss``
+    _relu_any_dropout = True
 
     def _run(self, enc):
-        fused = self.rng is not None and isinstance(self.activation, nn.ReLU) and enc.is_cuda
-        if fused and all(l.bias is not None for l in self.predictor) and all(l.out_features % 4 == 0 for l in self.predictor[:-1]):
-            if self.loss_spec is not None:
-                out, loss = ops.mlp_head(enc, list(self.predictor), self.dropout.p, self.training, self.rng, self.live_rows, loss=self.loss_spec)
-                if loss is not None:
-                    out._fragnet_loss = (loss, self.loss_spec[1], self.loss_spec[2])
-                return out
-            return ops.mlp_head(enc, list(self.predictor), self.dropout.p, self.training, self.rng, self.live_rows)     # one autograd node
+        linears = list(self.predictor)
+        kind = self._fused_kind(enc, linears)
+        if kind is not None:
+            return self._fused(enc, linears, kind)
+        relu = self.rng is not None and isinstance(self.activation, nn.ReLU) and enc.is_cuda
         for lin in self.predictor[:-1]:
-            if fused:    # relu(dropout(.)) as one kernel each way instead of two (same op as between encoder layers)
+            if relu:     # relu(dropout(.)) as one kernel each way instead of two (same op as between encoder layers)
                 enc = ops.dropout_act(lin(enc), self.dropout.p, self.training, True, self.rng)
             else:
                 enc = self.activation(self.dropout(lin(enc)))
@@ -391,7 +427,7 @@ class FTHead5(_PredictorStack):
         return self._run(enc)
 
 
-class FTHead4(nn.Module):
+class FTHead4(_FusedHead, nn.Module):
     def __init__(self, input_dim=128, h1=128, act="relu", n_classes=1, drop_ratio=0.2):
         super().__init__()
         self.activation = _ACTS[act]()
@@ -400,6 +436,10 @@ class FTHead4(nn.Module):
         self.out_proj = nn.Linear(h1, n_classes)
 
     def forward(self, x):
+        linears = [self.dense, self.out_proj]
+        kind = self._fused_kind(x, linears)
+        if kind is not None:
+            return self._fused(x, linears, kind, _lib.ACT_ACT_THEN_DROP, in_drop=True)
         return self.out_proj(self.dropout(self.activation(self.dense(self.dropout(x)))))
 
 
@@ -459,8 +499,7 @@ class FragNetFineTune(nn.Module):
         elif fthead == "FTHead4":
             self.fthead = FTHead4(n_classes=n_classes, h1=h1, drop_ratio=drop_ratio, act=act)
 
-        if isinstance(self.fthead, _PredictorStack):
-            self.fthead.rng = self.pretrain.rng
+        self.fthead.rng = self.pretrain.rng
 
     def forward(self, batch):
         x_atoms, x_frags, _, _ = self.pretrain(batch, edge_outputs=_KEEP_EDGE_OUTPUTS)

@@ -629,6 +629,43 @@ def _scratch(n_floats: int, device):
     return torch.empty(n_floats, dtype=torch.float32, device=device) if n_floats else None
 
 
+def mlp_head_dense_ok(rows: int, linears) -> bool:
+    """The shapes every launch of ``_MLPHead`` runs on the dense-head kernels for (the only path of the non-ReLU kinds)."""
+    return all(_dense_ok(rows, lin.weight) for lin in linears[:-1]) and linears[-1].out_features <= SMALL_LINEAR_MAX \
+        and linears[-1].in_features % 4 == 0
+
+
+def head_act_kind(act) -> Optional[int]:
+    """The kernels' activation kind (``_lib.ACT_*``) of a head's activation module as ``_ACTS`` builds it (model.py), or None where
+    torch keeps it: RReLU (its training slopes come from torch's generator) and non-default settings of the others."""
+    nn = torch.nn
+    t = type(act)
+    if isinstance(act, nn.ReLU):
+        return _lib.ACT_RELU
+    if t is nn.SiLU:
+        return _lib.ACT_SILU
+    if t is nn.GELU and act.approximate == "none":
+        return _lib.ACT_GELU
+    if t is nn.CELU and act.alpha == 1.0:
+        return _lib.ACT_CELU
+    if t is nn.SELU:
+        return _lib.ACT_SELU
+    if t is nn.ReLU6:
+        return _lib.ACT_RELU6
+    if t is nn.LeakyReLU and act.negative_slope == 0.01:
+        return _lib.ACT_LEAKYRELU
+    if t is nn.PReLU and act.weight.numel() == 1 and act.weight.dtype == torch.float32:
+        return _lib.ACT_PRELU
+    return None
+
+
+def _head_act(hact, p: float, draw, dev, prelu, pre, part=None):
+    """fn_head_act of one hidden layer: kind and order, its Philox draw, its saved argument, the PReLU slope and partials."""
+    kind, order = hact
+    seed, off = draw
+    return _lib.HeadAct(kind, order, float(p), 0, seed, off, _ptr(dev) if p > 0.0 else None, _ptr(prelu), pre.data_ptr(), _ptr(part))
+
+
 class _MLPHead(torch.autograd.Function):
     """FTHead1-5's predictor stack (gat2.py:631-637, 745-751) as one autograd node.
 
@@ -641,10 +678,14 @@ class _MLPHead(torch.autograd.Function):
     taken from the model's Philox stream in the same order as the unfused path, so both paths produce identical numbers.
     ``live``: input rows >= live are padding (static-shape batches): they are not computed, their outputs and input
     gradients are 0.
+    ``hact = (kind, order)``: the hidden layers' activation is another kind than the ReLU above (csrc/head_act.inc; dense shapes only):
+    the forward saves each layer's activation argument, the backward replays the masks from ``draws``; ``prelu`` (kind PReLU) is
+    the slope every hidden layer shares, read by the kernels from device memory, and its gradient is the fixed-order sum of one
+    partial per workgroup of the launches that run the layers' activation backward.
     """
 
     @staticmethod
-    def forward(ctx, x, p: float, draws, dev, live, loss, *params):
+    def forward(ctx, x, p: float, draws, dev, live, loss, hact, prelu, *params):
         n = len(params) // 2
         st = _stream_ptr(x.device)
         x = _f32c(x, "x")
@@ -654,10 +695,20 @@ class _MLPHead(torch.autograd.Function):
         acts = [h]
         dense = all(_dense_ok(live, params[2 * i]) for i in range(n - 1)) and params[-2].shape[0] <= SMALL_LINEAR_MAX \
             and params[-2].shape[1] % 4 == 0
+        if hact is not None and not dense:
+            raise _lib.FragnetHipError("mlp_head: activation kinds other than ReLU run on the dense-head kernels only (rows <= "
+                                       f"{DENSE_MAX_ROWS}, widths multiples of 4, <= {SMALL_LINEAR_MAX} outputs)")
+        pres = []
         for i in range(n - 1):
             W, b = params[2 * i], params[2 * i + 1]
             seed, off = draws[i]
-            if dense:
+            if hact is not None:
+                y = torch.empty((live, W.shape[0]), dtype=torch.float32, device=h.device)
+                pres.append(torch.empty_like(y))
+                spec = _head_act(hact, p, draws[i], dev, prelu, pres[-1])
+                _lib.call("fn_dense_fwd_act_f32", h.data_ptr(), W.data_ptr(), b.data_ptr(), y.data_ptr(), live, W.shape[1], W.shape[0],
+                          C.byref(spec), st)
+            elif dense:
                 y = torch.empty((live, W.shape[0]), dtype=torch.float32, device=h.device)
                 act = _lib.ActEpilogue(y.data_ptr(), float(p), 1, seed, off, _ptr(dev) if p > 0.0 else None)
                 _lib.call("fn_dense_fwd_f32", h.data_ptr(), W.data_ptr(), b.data_ptr(), y.data_ptr(), live, W.shape[1], W.shape[0],
@@ -673,8 +724,20 @@ class _MLPHead(torch.autograd.Function):
         ctx.p, ctx.dense, ctx.rows = float(p), dense, (M, live)
         ctx.params, ctx.slots = params, [grad_slot(q) for q in params]
         ctx.fused_loss = False
-        if loss is not None and dense and n > 1 and live > 0 and K <= _lib.SMALL_LINEAR_LOSS_MAX_K and loss[2].shape[0] == M \
-                and loss[1].numel() == M * C_out:
+        fuse = loss is not None and dense and n > 1 and live > 0 and K <= _lib.SMALL_LINEAR_LOSS_MAX_K and loss[2].shape[0] == M \
+            and loss[1].numel() == M * C_out
+        ctx.hact, ctx.draws, ctx.dev, ctx.pres, ctx.prelu, ctx.part, ctx.part_at = hact, draws, dev, pres, prelu, None, None
+        if prelu is not None:
+            ctx.prelu_slot = grad_slot(prelu)
+            if hact is not None and n > 1 and live > 0:
+                # one slice of partials per hidden layer: layer i < n - 2 in the input-gradient launch of layer i + 1, the top one in
+                # the last Linear's launch (its fused-loss forward, or its backward)
+                lib = _lib.load()
+                counts = [lib.fn_head_act_parts(_lib.ACT_AT_DENSE_BWD, live, params[2 * i].shape[0]) for i in range(n - 2)]
+                counts.append(lib.fn_head_act_parts(_lib.ACT_AT_SMALL_LOSS, M, K) if fuse else lib.fn_head_act_parts(_lib.ACT_AT_SMALL_BWD, live, K))
+                ctx.part = torch.empty(sum(counts), dtype=torch.float32, device=h.device)
+                ctx.part_at = [sum(counts[:i]) for i in range(n - 1)] + [sum(counts)]
+        if fuse:
             # last Linear + loss + its input gradient in one launch; dW / db / the loss value ride in the backward's first launch
             kind, tgt, row_w = loss
             tgt, row_w = _f32c(tgt, "y"), _f32c(row_w, "w")
@@ -684,8 +747,14 @@ class _MLPHead(torch.autograd.Function):
             parts = torch.empty(_lib.load().fn_small_linear_loss_ws(M), dtype=torch.float32, device=h.device)
             loss_t = torch.empty((), dtype=torch.float32, device=h.device)
             scale = 1.0 / (1.0 - p) if 0.0 < p < 1.0 else 1.0
-            _lib.call("fn_small_linear_loss_f32", h.data_ptr(), _f32c(W, "W").data_ptr(), b.data_ptr(), tgt.data_ptr(), row_w.data_ptr(),
-                      int(kind), out.data_ptr(), g.data_ptr(), gz.data_ptr(), scale, parts.data_ptr(), live, K, C_out, M, st)
+            if hact is not None:
+                below = _MLPHead._below(ctx, n - 2)
+                _lib.call("fn_small_linear_loss_act_f32", h.data_ptr(), _f32c(W, "W").data_ptr(), b.data_ptr(), tgt.data_ptr(),
+                          row_w.data_ptr(), int(kind), out.data_ptr(), g.data_ptr(), gz.data_ptr(), C.byref(below), parts.data_ptr(),
+                          live, K, C_out, M, st)
+            else:
+                _lib.call("fn_small_linear_loss_f32", h.data_ptr(), _f32c(W, "W").data_ptr(), b.data_ptr(), tgt.data_ptr(), row_w.data_ptr(),
+                          int(kind), out.data_ptr(), g.data_ptr(), gz.data_ptr(), scale, parts.data_ptr(), live, K, C_out, M, st)
             ctx.fused_loss = True
             ctx.save_for_backward(*acts, *params[0::2], g, gz, parts, loss_t)
             ctx.mark_non_differentiable(out)
@@ -700,6 +769,12 @@ class _MLPHead(torch.autograd.Function):
                 out = torch.cat([out, out.new_zeros((M - live, C_out))])
         ctx.save_for_backward(*acts, *params[0::2])
         return (out, None) if loss is not None else out
+
+    @staticmethod
+    def _below(ctx, i):
+        """fn_head_act of hidden layer i for the launch that runs its activation backward"""
+        part = None if ctx.part is None else ctx.part[ctx.part_at[i]:]
+        return _head_act(ctx.hact, ctx.p, ctx.draws[i], ctx.dev, ctx.prelu, ctx.pres[i], part)
 
     @staticmethod
     def backward(ctx, g, g_loss=None):
@@ -739,15 +814,22 @@ class _MLPHead(torch.autograd.Function):
             unit = _UNIT_GRAD.get(g.device)
             if g_loss is not None and not (unit is not None and g_loss.data_ptr() == unit.data_ptr()):
                 g, gz = g * g_loss, gz * g_loss
+                if ctx.part is not None:            # the top layer's slope partials, taken in the forward for d loss / d loss = 1
+                    ctx.part[ctx.part_at[n - 2]:].mul_(g_loss)
             tail = _lib.SmallDw(g.data_ptr(), h.data_ptr(), dW.data_ptr(), db.data_ptr(), parts.data_ptr(), loss_t.data_ptr(),
                                 parts.numel(), live, K, C_out)
             ctx.tail_keep = (g, gz)
         elif C_out <= SMALL_LINEAR_MAX and K % 4 == 0:
             gz = input_grad(h, n == 1) if (n > 1 or need_x) else torch.empty_like(h)
             ws = _scratch(_lib.load().fn_small_linear_bwd_ws(live, K, C_out), g.device)
-            # dense path: gz leaves gated by h > 0 (the backward of the top hidden layer's relu(dropout(.)))
-            _lib.call("fn_small_linear_bwd_f32", g.data_ptr(), h.data_ptr(), W.data_ptr(), gz.data_ptr(), dW.data_ptr(), db.data_ptr(),
-                      live, K, C_out, scale if (dense and n > 1) else 0.0, _ptr(ws), st)
+            if ctx.hact is not None and n > 1:     # gz leaves through the backward of the top hidden layer's activation kind
+                below = _MLPHead._below(ctx, n - 2)
+                _lib.call("fn_small_linear_bwd_act_f32", g.data_ptr(), h.data_ptr(), W.data_ptr(), gz.data_ptr(), dW.data_ptr(), db.data_ptr(),
+                          live, K, C_out, C.byref(below), _ptr(ws), st)
+            else:
+                # dense path: gz leaves gated by h > 0 (the backward of the top hidden layer's relu(dropout(.)))
+                _lib.call("fn_small_linear_bwd_f32", g.data_ptr(), h.data_ptr(), W.data_ptr(), gz.data_ptr(), dW.data_ptr(), db.data_ptr(),
+                          live, K, C_out, scale if (dense and n > 1) else 0.0, _ptr(ws), st)
         else:
             gz = g @ W
             torch.mm(g.t(), h, out=dW)
@@ -764,7 +846,12 @@ class _MLPHead(torch.autograd.Function):
             need_gx = i > 0 or need_x
             if dense:                                   # gz is d loss / d (pre-activation) already: one launch for the layer
                 gx = input_grad(h_in, i == 0, zeroed_by_kernel=True) if need_gx else None
-                if tail is not None:
+                if ctx.hact is not None and i > 0:      # through the backward of layer i - 1's activation kind
+                    below = _MLPHead._below(ctx, i - 1)
+                    _lib.call("fn_dense_bwd_act_f32", gz.data_ptr(), h_in.data_ptr(), W.data_ptr(), _ptr(gx), C.byref(below), dW.data_ptr(),
+                              db.data_ptr(), live, W.shape[1], W.shape[0], live, None if tail is None else C.byref(tail), st)
+                    tail = None
+                elif tail is not None:
                     _lib.call("fn_dense_bwd_tail_f32", gz.data_ptr(), h_in.data_ptr(), W.data_ptr(), _ptr(gx), scale if i > 0 else 0.0,
                               dW.data_ptr(), db.data_ptr(), live, W.shape[1], W.shape[0], M if i == 0 else live, C.byref(tail), st)
                     tail = None
@@ -782,20 +869,39 @@ class _MLPHead(torch.autograd.Function):
                 gz = gy @ W
                 if i == 0 and live < M:
                     gz = torch.cat([gz, gz.new_zeros((M - live, gz.shape[1]))])
-        return (gz if need_x else None, None, None, None, None, None, *grads)
+        g_prelu = None
+        if ctx.prelu is not None:
+            g_prelu = grad_buffer(ctx.prelu, ctx.prelu_slot)
+            if ctx.part is not None and ctx.part.numel():
+                _lib.call("fn_head_act_param_grad_f32", ctx.part.data_ptr(), ctx.part.numel(), g_prelu.data_ptr(), st)
+            else:
+                g_prelu.zero_()
+        return (gz if need_x else None, None, None, None, None, None, None, g_prelu, *grads)
 
 
 FUSED_HEAD_LOSS = os.environ.get("FRAGNET_FUSED_HEAD_LOSS", "1") != "0"       # False: last Linear, loss and the Linear's backward as three launches (A/B and tests)
 
 
-def mlp_head(x, linears, p: float, training: bool, rng: "PhiloxStream", live=None, loss=None):
+def mlp_head(x, linears, p: float, training: bool, rng: "PhiloxStream", live=None, loss=None, act=None,
+             order: int = _lib.ACT_DROP_THEN_ACT, in_drop: bool = False):
     """Runs ``linears`` (nn.Linear modules; relu(dropout(.)) after all but the last) through ``_MLPHead``.
+
+    ``act``: the hidden layers' activation module when it is not ReLU (``head_act_kind``), applied as act(dropout(.)) or, with
+    ``order = _lib.ACT_ACT_THEN_DROP``, dropout(act(.)) (FTHead1/4; for ReLU both orders are the same numbers); ``in_drop``: the input
+    is dropped first (FTHead1/4, one more Philox draw ahead of the layers').
 
     ``loss = (kind, target, row_weights)`` (kind: ``_lib.LOSS_MSE`` / ``_lib.LOSS_BCE``): the caller is a training step that will call
     ``backward`` on the loss with gradient 1 right away.  Returns ``(out, loss)``; ``loss`` is None when the fused launch does not
     apply (the caller then computes it from ``out``), else a scalar whose VALUE is complete once backward has run (the sum of the
     partials rides in the backward's first launch) and ``out`` carries no gradient."""
     p_eff = float(p) if training else 0.0
+    kind = _lib.ACT_RELU if act is None else head_act_kind(act)
+    if kind is None:
+        raise ValueError(f"mlp_head: no kernel for the activation {act!r}")
+    hact = None if kind == _lib.ACT_RELU else (kind, int(order))
+    prelu = act.weight if kind == _lib.ACT_PRELU else None
+    if in_drop:
+        x = dropout_act(x, p, training, False, rng)
     draws = []
     for lin in linears[:-1]:
         draws.append(rng.take(x.shape[0] * lin.out_features) if p_eff > 0.0 else (0, 0))
@@ -806,8 +912,8 @@ def mlp_head(x, linears, p: float, training: bool, rng: "PhiloxStream", live=Non
         params += [lin.weight, lin.bias]
     if loss is not None and not (FUSED_HEAD_LOSS and training and x.requires_grad and linears[-1].out_features <= SMALL_LINEAR_MAX
                                  and linears[-1].in_features % 4 == 0):
-        return _MLPHead.apply(x, p_eff, tuple(draws), rng.dev if p_eff > 0.0 else None, live, None, *params), None
-    return _MLPHead.apply(x, p_eff, tuple(draws), rng.dev if p_eff > 0.0 else None, live, loss, *params)
+        return _MLPHead.apply(x, p_eff, tuple(draws), rng.dev if p_eff > 0.0 else None, live, None, hact, prelu, *params), None
+    return _MLPHead.apply(x, p_eff, tuple(draws), rng.dev if p_eff > 0.0 else None, live, loss, hact, prelu, *params)
 
 
 # ======================================================================================

@@ -418,7 +418,8 @@ int fn_segment_softmax_bwd_f32(const float* probs, const float* g_probs, const i
 
 /* ------------------------------------------------------------------------------------------
  * Dense layers of the prediction heads, FTHead1-5 (gat2.py:569-751): Linear -> relu(dropout(.)) on [molecules, width],
- * fp32 matrix cores, 32x64 output tiles, the element-wise work fused in (csrc/dense_head.inc).
+ * fp32 matrix cores, 32x64 output tiles, the element-wise work fused in (csrc/dense_head.inc).  The heads' other activations, and
+ * FTHead1/4's dropout(act(.)) order, run on the same kernels through the fn_*_act_f32 entry points further down (fn_head_act).
  *   fn_dense_fwd_f32   Y[M,N] = X[M,K] W[N,K]^T + bias;  with act: Y = relu?(dropout(.)), the Philox stream of
  *                      fn_dropout_act_f32 over Y's elements (act->y is ignored: the activation is applied in place)
  *   fn_dense_bwd_f32   g_y = dL/d(X W^T + bias), i.e. already through the backward of this layer's own activation;
@@ -522,6 +523,62 @@ int fn_small_linear_loss_f32(const float* x /*[M,K]*/, const float* w /*[C,K]*/,
                              int64_t M, int64_t K, int64_t C, int64_t M_out, fn_stream_t stream);
 int fn_dense_bwd_tail_f32(const float* g_y, const float* X, const float* W, float* g_x, float gate_scale, float* dW, float* db,
                           int64_t M, int64_t K, int64_t N, int64_t M_out, const fn_small_dw* tail /*nullable*/, fn_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
+ * The other activations of the prediction heads (finetune `act`, gat2.py:693-705) on the same kernels (csrc/head_act.inc).
+ * A fn_head_act describes one hidden layer's  Linear -> dropout / act  pair, in either order:
+ *   FN_ACT_DROP_THEN_ACT   y = f(u), u = dropout(z)      FTHead2/3/5 (gat2.py:631-637, 719-725)
+ *   FN_ACT_ACT_THEN_DROP   y = dropout(f(u)), u = z      FTHead1/4 (gat2.py:569-587, 640-675)
+ * z = X W^T + b; the mask is the Philox stream of fn_dropout_act_f32 over the layer's [M,N] elements (seed, offset, offset_dev).
+ * f is torch's module: relu, silu, gelu (erf form), celu (alpha 1), selu, relu6, leakyrelu (slope 0.01), prelu (ONE slope,
+ * read from prelu_w in device memory when the kernel runs).  The forward writes u to `pre` [M,N]; a backward that is handed the
+ * same struct as `below` (the layer that produced its input X) reads u back, recomputes the mask from (seed, offset) and writes
+ *   g_x = keep * f'(u) * (g_y W)          (torch's f' at the kinks: relu / leakyrelu / prelu / celu / selu u > 0, relu6 0 < u < 6)
+ * and, for prelu, one partial sum of d loss / d slope = sum (u > 0 ? 0 : u * d loss / d f) per workgroup into `part`
+ * [fn_head_act_parts()]; fn_head_act_param_grad_f32 adds all partials of a head in a fixed order (no atomics).
+ *   fn_dense_fwd_act_f32            fn_dense_fwd_f32 with the activation above (act required)
+ *   fn_dense_bwd_act_f32            fn_dense_bwd_tail_f32 whose input gradient goes through `below` (NULL: no gate)
+ *   fn_small_linear_bwd_act_f32     fn_small_linear_bwd_f32 whose g_x goes through `below` (NULL: no gate)
+ *   fn_small_linear_loss_act_f32    fn_small_linear_loss_f32 whose g_x goes through `below` (NULL: no gate)
+ * fn_head_act_parts(where, rows, K): the partials one such call writes, where = FN_ACT_AT_*; rows = its M_out (M for the
+ * small-linear backward, which has no padding rows).  A call with M = 0 writes none.
+ * ------------------------------------------------------------------------------------------ */
+#define FN_ACT_RELU 0
+#define FN_ACT_SILU 1
+#define FN_ACT_GELU 2
+#define FN_ACT_CELU 3
+#define FN_ACT_SELU 4
+#define FN_ACT_RELU6 5
+#define FN_ACT_LEAKYRELU 6
+#define FN_ACT_PRELU 7
+#define FN_ACT_DROP_THEN_ACT 0
+#define FN_ACT_ACT_THEN_DROP 1
+#define FN_ACT_AT_DENSE_BWD 0
+#define FN_ACT_AT_SMALL_BWD 1
+#define FN_ACT_AT_SMALL_LOSS 2
+typedef struct fn_head_act {
+    int32_t kind;               /* FN_ACT_* */
+    int32_t order;              /* FN_ACT_DROP_THEN_ACT / FN_ACT_ACT_THEN_DROP */
+    float p;                    /* dropout probability (0 = none) */
+    int32_t pad_;
+    uint64_t seed, offset;
+    const uint64_t* offset_dev; /* nullable, see fn_act_epilogue */
+    const float* prelu_w;       /* [1], kind FN_ACT_PRELU */
+    float* pre;                 /* [M,N] the activation's argument u: written by the forward, read by the backward */
+    float* part;                /* backward, kind FN_ACT_PRELU: [fn_head_act_parts()] partial sums of d loss / d slope */
+} fn_head_act;
+int fn_dense_fwd_act_f32(const float* X, const float* W, const float* bias /*nullable*/, float* Y, int64_t M, int64_t K, int64_t N,
+                         const fn_head_act* act, fn_stream_t stream);
+int fn_dense_bwd_act_f32(const float* g_y, const float* X, const float* W, float* g_x /*nullable*/, const fn_head_act* below /*nullable*/,
+                         float* dW, float* db /*nullable*/, int64_t M, int64_t K, int64_t N, int64_t M_out,
+                         const fn_small_dw* tail /*nullable*/, fn_stream_t stream);
+int fn_small_linear_bwd_act_f32(const float* g, const float* x, const float* w, float* g_x, float* dW, float* db, int64_t M, int64_t K,
+                                int64_t C, const fn_head_act* below /*nullable*/, float* ws, fn_stream_t stream);
+int fn_small_linear_loss_act_f32(const float* x, const float* w, const float* b /*nullable*/, const float* target, const float* row_w,
+                                 int kind, float* y, float* g, float* g_x, const fn_head_act* below /*nullable*/, float* loss_part,
+                                 int64_t M, int64_t K, int64_t C, int64_t M_out, fn_stream_t stream);
+int64_t fn_head_act_parts(int where, int64_t rows, int64_t K);
+int fn_head_act_param_grad_f32(const float* part, int64_t n, float* grad /*[1], overwritten*/, fn_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
  * A batch out of a resident flat store in one launch (the data side of the path: the reference's collate_fn, dataset/data.py:877-948,
