@@ -131,6 +131,13 @@ class Encoder(C.Structure):
                 ("mol_contiguous", i32), ("no_backward", i32), ("pooled", vp), ("g_pooled", vp), ("adam_rider", vp)]
 
 
+class RowMasks(C.Structure):
+    _fields_ = [("atoms", vp), ("bonds", vp), ("fbonds", vp)]
+
+
+STATUS_BAD_REPLICA = 8      # FN_STATUS_BAD_REPLICA
+
+
 # name -> argtypes; every function returns int (0 ok / <0 argument error / >0 hipError_t) unless noted.
 SIGNATURES = {
     "fn_abi_version": [],
@@ -170,6 +177,8 @@ SIGNATURES = {
     "fn_encoder_bwd_ws_floats": [C.POINTER(Encoder)],
     "fn_encoder_rng_blocks": [C.POINTER(Encoder)],
     "fn_encoder_forward": [C.POINTER(Encoder), vp, vp, vp, vp, vp],
+    "fn_encoder_forward_masked": [C.POINTER(Encoder), C.POINTER(RowMasks), vp, vp, vp, vp, vp],
+    "fn_loo_row_masks_u8": [vp, i64, vp, vp, vp, vp, i64, vp, i64, vp, i64, vp, vp],
     "fn_encoder_backward": [C.POINTER(Encoder), vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(LayerWeights), vp, i64, vp],
     "fn_segment_sum_f32": [vp, i64, vp, vp, i32, vp, i64, i64, i64, vp],
     "fn_gather_rows_f32": [vp, vp, vp, i64, i64, vp],

@@ -840,6 +840,10 @@ int encoder_backward_one(const fn_encoder* e, const EncLayout& lay, const BwdLay
 
 }  // namespace
 
+// forward declaration: the pass behind fn_encoder_forward and fn_encoder_forward_masked (defined with them, below)
+static int encoder_forward_impl(const fn_encoder* e, const fn_row_masks* masks, float* out_atoms, float* out_frags, float* out_bond,
+                                float* out_fbond, fn_stream_t st);
+
 extern "C" {
 
 int fn_encoder_fused_tail(const fn_encoder* e) { return e && tail_mol_on(e) ? 1 : 0; }
@@ -850,6 +854,28 @@ uint64_t fn_encoder_rng_blocks(const fn_encoder* e) { return e ? rng_plan(e).tot
 
 int fn_encoder_forward(const fn_encoder* e, float* out_atoms, float* out_frags, float* out_bond, float* out_fbond,
                        fn_stream_t st) {
+    return encoder_forward_impl(e, nullptr, out_atoms, out_frags, out_bond, out_fbond, st);
+}
+
+int fn_encoder_forward_masked(const fn_encoder* e, const fn_row_masks* m, float* out_atoms, float* out_frags, float* out_bond,
+                              float* out_fbond, fn_stream_t st) {
+    if (!m || (!m->atoms && !m->bonds && !m->fbonds)) return encoder_forward_impl(e, nullptr, out_atoms, out_frags, out_bond, out_fbond, st);
+    // everything a masked pass can be refused for is decided here, before the first launch
+    FN_TRY(enc_check(e));
+    if (e->variant != 0) return fail(FN_EUNSUPPORTED, "fn_encoder_forward_masked: row masks exist for variant 0 (gat2); gat2_lite / gat2_edge have no masks in the reference");
+    if (e->training != 0) return fail(FN_EINVAL, "fn_encoder_forward_masked: a masked pass is an evaluation pass (training must be 0)");
+    if (e->no_backward == 0) return fail(FN_EINVAL, "fn_encoder_forward_masked: a masked pass has no backward (no_backward must be 1)");
+    if (e->heads != 4) return fail(FN_EUNSUPPORTED, "fn_encoder_forward_masked: the masked attention instances are built for four heads");
+    return encoder_forward_impl(e, m, out_atoms, out_frags, out_bond, out_fbond, st);
+}
+
+}  // extern "C" (reopened behind the pass itself)
+
+// masks == null: the plain pass.  Else the caller has checked that the descriptor is one a masked pass exists for, and every attention
+// level of the three masked index spaces launches forward kind 4 (gat_fwd.inc) with its byte array (null inside: no masked row there).
+// The fragment graph has no mask (gat2.py has none), and everything behind the three levels reads stored rows.
+static int encoder_forward_impl(const fn_encoder* e, const fn_row_masks* masks, float* out_atoms, float* out_frags, float* out_bond,
+                                float* out_fbond, fn_stream_t st) {
     FN_TRY(enc_check(e));
     if (!out_atoms || !out_frags) return fail(FN_EINVAL, "fn_encoder_forward: null output");
     if ((out_bond == nullptr) != (out_fbond == nullptr)) return fail(FN_EINVAL, "fn_encoder_forward: out_bond and out_fbond are wanted together or not at all");
@@ -876,6 +902,8 @@ int fn_encoder_forward(const fn_encoder* e, float* out_atoms, float* out_frags, 
     // real rows per index space (device words written by the prologue below): the kernels skip the padding behind them
     const int32_t* rr = pad_skip_on(e) ? reinterpret_cast<const int32_t*>(lay.real_rows) : nullptr;
     const int32_t *nr_atoms = rr, *nr_bonds = rr ? rr + 1 : nullptr, *nr_conns = rr ? rr + 3 : nullptr;
+    const fni::FwdMask mk_atoms{masks ? masks->atoms : nullptr}, mk_bonds{masks ? masks->bonds : nullptr}, mk_fbonds{masks ? masks->fbonds : nullptr};
+    const fni::FwdMask *pm_atoms = masks ? &mk_atoms : nullptr, *pm_bonds = masks ? &mk_bonds : nullptr, *pm_fbonds = masks ? &mk_fbonds : nullptr;
 
     const float* in_atoms = lay.in_atoms0 ? lay.in_atoms0 : e->x_atoms;
     const float* in_bond = e->bond_nodes;
@@ -1033,9 +1061,9 @@ int fn_encoder_forward(const fn_encoder* e, float* out_atoms, float* out_frags, 
         }
         if (l == 0) FN_TRY(prof_event(0, S(st)));
         if (with_pair.n) {
-            FN_TRY(launch_gat_fwd_pair_lin(gb, gfb, with_pair, H, S(st)));
+            FN_TRY(launch_gat_fwd_pair_lin(gb, gfb, with_pair, H, S(st), pm_bonds, pm_fbonds));
         } else {
-            FN_TRY(launch_gat_fwd_pair(gb, gfb, H, S(st)));
+            FN_TRY(launch_gat_fwd_pair(gb, gfb, H, S(st), pm_bonds, pm_fbonds));
         }
         if (l == 0) FN_TRY(prof_event(1, S(st)));
 
@@ -1061,7 +1089,7 @@ int fn_encoder_forward(const fn_encoder* e, float* out_atoms, float* out_frags, 
             ga.p_edge_major = one ? 1 : 0;
             if (no_bwd) ga.p_sorted = nullptr;
             ga.n_real = nr_atoms;
-            FN_TRY(launch_gat_fwd_lin(ga, T, H, S(st)));
+            FN_TRY(launch_gat_fwd_lin(ga, T, H, S(st), pm_atoms));
         } else {
             GatFwdArgs ga;
             FN_TRY(prep_gat_fwd(a.h_a, lay.s_dst_a, lay.s_src_a, w.a, wide, &et_a, &e->atom, 0.2f, (last || !ep_atoms.y) ? lay.atoms_new : nullptr, a.p_atom, nullptr, &ep_atoms,
@@ -1069,7 +1097,7 @@ int fn_encoder_forward(const fn_encoder* e, float* out_atoms, float* out_frags, 
             ga.p_edge_major = one ? 1 : 0;
             if (no_bwd) ga.p_sorted = nullptr;
             ga.n_real = nr_atoms;
-            FN_TRY(launch_gat_fwd(ga, H, S(st)));
+            FN_TRY(launch_gat_fwd(ga, H, S(st), pm_atoms));
         }
 
         // L3 atom -> fragment sum.  Like L4b below it is only ever read in the last layer (the next layer recomputes its own
@@ -1115,6 +1143,8 @@ int fn_encoder_forward(const fn_encoder* e, float* out_atoms, float* out_frags, 
     }
     return 0;
 }
+
+extern "C" {
 
 int fn_encoder_backward(const fn_encoder* e, const float* out_atoms, const float* out_frags, const float* out_bond,
                         const float* out_fbond, const float* g_atoms, const float* g_frags, const float* g_bond,

@@ -105,11 +105,16 @@ struct LinTasks {
 FNI_HIDDEN int prep_gat_fwd(const float* h, const float* s_dst, const float* s_src, const float* att, int att_w, const fn_edge_term* et,
                             const fn_gat_plan* plan, float neg_slope, float* out, float* p_sorted, float* probs_orig,
                             const fn_act_epilogue* act, int heads, GatFwdArgs* A, float* out2 = nullptr, float* sigma = nullptr);
-FNI_HIDDEN int launch_gat_fwd(const GatFwdArgs& A, int heads, hipStream_t st);
-FNI_HIDDEN int launch_gat_fwd_pair(const GatFwdArgs& A, const GatFwdArgs& B, int heads, hipStream_t st);
+// A non-null FwdMask makes a launch a MASKED evaluation launch (forward kind 4, gat_fwd.inc): rows[t] != 0 -> row t of the level is zero
+// for everything that reads it.  rows == null: a level of a masked pass that has no mask of its own.  In a two-level launch both come or neither.
+struct FwdMask { const uint8_t* rows; };
+FNI_HIDDEN bool fwd_kind_mk(const GatFwdArgs& A, int heads);
+FNI_HIDDEN int launch_gat_fwd(const GatFwdArgs& A, int heads, hipStream_t st, const FwdMask* mk = nullptr);
+FNI_HIDDEN int launch_gat_fwd_pair(const GatFwdArgs& A, const GatFwdArgs& B, int heads, hipStream_t st, const FwdMask* mka = nullptr, const FwdMask* mkb = nullptr);
 // gat_fwd_lin.hip: an attention pass + the K = 128 projection tiles that do not depend on it, in one launch
-FNI_HIDDEN int launch_gat_fwd_lin(const GatFwdArgs& A, LinTasks& T, int heads, hipStream_t st);
-FNI_HIDDEN int launch_gat_fwd_pair_lin(const GatFwdArgs& A, const GatFwdArgs& B, LinTasks& T, int heads, hipStream_t st);
+FNI_HIDDEN int launch_gat_fwd_lin(const GatFwdArgs& A, LinTasks& T, int heads, hipStream_t st, const FwdMask* mk = nullptr);
+FNI_HIDDEN int launch_gat_fwd_pair_lin(const GatFwdArgs& A, const GatFwdArgs& B, LinTasks& T, int heads, hipStream_t st, const FwdMask* mka = nullptr,
+                                       const FwdMask* mkb = nullptr);
 // ---- the one-pass attention backward (gat_bwd_one.hip / gat_bwd_one.inc)
 struct GatBwdOneArgs {
     const float *g_out, *h, *p_sorted, *cdot, *g_s_dst, *att;

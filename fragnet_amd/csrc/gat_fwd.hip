@@ -30,9 +30,34 @@ __global__ __launch_bounds__(kBlock, 4) void k_gat_fwd_rd(GatFwdArgs A) {       
     gat_fwd_body<H, 1, true, O2>(A, sWf, (int)blockIdx.x, (int)gridDim.x);
 }
 
+// ---- kind 4 (gat_fwd.inc): the masked evaluation forward of fn_encoder_forward_masked.  Kernels of their own -- the mask pointers are
+// kernel arguments beside the level's block, so that kinds 0-3 and their argument blocks stay what they were.  A null pointer is a level
+// without a mask of its own in a masked pass.
+template <int H, int KL>
+__global__ __launch_bounds__(kBlock, 4) void k_gat_fwd_m(GatFwdArgs A, const uint8_t* mk) {
+    __shared__ float sWf[8][kWfLd];
+    gat_fwd_body<H, KL, false, 4>(A, sWf, (int)blockIdx.x, (int)gridDim.x, mk);
+}
+template <int H, int KLA, int KLB, bool RDA>
+__global__ __launch_bounds__(kBlock, 4) void k_gat_fwd_pair_m(GatFwdArgs A, GatFwdArgs B, const uint8_t* mka, const uint8_t* mkb) {
+    __shared__ float sWf[8][kWfLd];
+    if ((int)blockIdx.x < A.nblk) gat_fwd_body<H, KLA, RDA, 4>(A, sWf, (int)blockIdx.x, A.nblk, mka);
+    else gat_fwd_body<H, KLB, false, 4>(B, sWf, (int)blockIdx.x - A.nblk, B.nblk, mkb);
+}
+template <int H>
+__global__ __launch_bounds__(kBlock, 4) void k_gat_fwd_rd_m(GatFwdArgs A, const uint8_t* mk) {
+    __shared__ float sWf[8][kWfLd];
+    gat_fwd_body<H, 1, true, 4>(A, sWf, (int)blockIdx.x, (int)gridDim.x, mk);
+}
+
 }  // namespace
 
 namespace fni {
+// what kind 4 takes for granted (fn_encoder_forward_masked checks the pass as a whole before its first launch; this is the per-launch guard)
+bool fwd_kind_mk(const GatFwdArgs& A, int heads) {
+    return heads == 4 && A.out2 == nullptr && A.p_edge_major == 0 && A.probs_orig == nullptr &&
+           (A.ep.y == nullptr || (A.ep.relu != 0 && !(A.ep.p > 0.f))) && (A.rd_out == nullptr || A.rd_J == heads);
+}
 int prep_gat_fwd(const float* h, const float* s_dst, const float* s_src, const float* att, int att_w,
                         const fn_edge_term* et, const fn_gat_plan* plan, float neg_slope, float* out, float* p_sorted,
                         float* probs_orig, const fn_act_epilogue* act, int heads, GatFwdArgs* A, float* out2,
@@ -66,9 +91,19 @@ int prep_gat_fwd(const float* h, const float* s_dst, const float* s_src, const f
     return 0;
 }
 
-int launch_gat_fwd(const GatFwdArgs& A, int heads, hipStream_t st) {
+int launch_gat_fwd(const GatFwdArgs& A, int heads, hipStream_t st, const FwdMask* mk) {
     if (A.nblk == 0) return 0;
     const int kl = edge_class(&A.et);
+    if (mk) {
+        if (!fwd_kind_mk(A, heads)) return fail(FN_EUNSUPPORTED, "attention forward: a masked level is a four-head evaluation level without second output");
+        if (A.rd_out) {
+            if (kl != 1) return fail(FN_EUNSUPPORTED, "attention forward: the row-dots epilogue exists for the single-attribute (bond graph) level");
+            hipLaunchKernelGGL((k_gat_fwd_rd_m<4>), dim3(A.nblk), dim3(kBlock), 0, st, A, mk->rows);
+        } else if (kl == 0) hipLaunchKernelGGL((k_gat_fwd_m<4, 0>), dim3(A.nblk), dim3(kBlock), 0, st, A, mk->rows);
+        else if (kl == 1) hipLaunchKernelGGL((k_gat_fwd_m<4, 1>), dim3(A.nblk), dim3(kBlock), 0, st, A, mk->rows);
+        else hipLaunchKernelGGL((k_gat_fwd_m<4, FN_MAX_EDGE_K>), dim3(A.nblk), dim3(kBlock), 0, st, A, mk->rows);
+        return launch_status("fn_gat_fwd_f32 (masked rows)");
+    }
     const bool o2 = A.out2 != nullptr;
     if (A.rd_out) {
         if (kl != 1) return fail(FN_EUNSUPPORTED, "attention forward: the row-dots epilogue exists for the single-attribute (bond graph) level");
@@ -95,11 +130,24 @@ int launch_gat_fwd(const GatFwdArgs& A, int heads, hipStream_t st) {
     return launch_status("fn_gat_fwd_f32");
 }
 // two levels, one launch, when their edge classes are (1, FN_MAX_EDGE_K) or (1, 1); two launches otherwise
-int launch_gat_fwd_pair(const GatFwdArgs& A, const GatFwdArgs& B, int heads, hipStream_t st) {
+int launch_gat_fwd_pair(const GatFwdArgs& A, const GatFwdArgs& B, int heads, hipStream_t st, const FwdMask* mka, const FwdMask* mkb) {
     const int ka = edge_class(&A.et), kb = edge_class(&B.et);
     if (A.nblk == 0 || B.nblk == 0 || ka != 1 || (kb != 1 && kb != FN_MAX_EDGE_K)) {
-        if (int rc = launch_gat_fwd(A, heads, st)) return rc;
-        return launch_gat_fwd(B, heads, st);
+        if (int rc = launch_gat_fwd(A, heads, st, mka)) return rc;
+        return launch_gat_fwd(B, heads, st, mkb);
+    }
+    if (mka || mkb) {
+        if (!mka || !mkb || !fwd_kind_mk(A, heads) || !fwd_kind_mk(B, heads))
+            return fail(FN_EUNSUPPORTED, "attention forward (two levels): masked levels are four-head evaluation levels without second output");
+        const dim3 grid(A.nblk + B.nblk);
+        if (A.rd_out) {
+            if (kb == 1) hipLaunchKernelGGL((k_gat_fwd_pair_m<4, 1, 1, true>), grid, dim3(kBlock), 0, st, A, B, mka->rows, mkb->rows);
+            else hipLaunchKernelGGL((k_gat_fwd_pair_m<4, 1, FN_MAX_EDGE_K, true>), grid, dim3(kBlock), 0, st, A, B, mka->rows, mkb->rows);
+        } else {
+            if (kb == 1) hipLaunchKernelGGL((k_gat_fwd_pair_m<4, 1, 1, false>), grid, dim3(kBlock), 0, st, A, B, mka->rows, mkb->rows);
+            else hipLaunchKernelGGL((k_gat_fwd_pair_m<4, 1, FN_MAX_EDGE_K, false>), grid, dim3(kBlock), 0, st, A, B, mka->rows, mkb->rows);
+        }
+        return launch_status("attention forward (two levels, masked rows)");
     }
     const bool o2 = A.out2 != nullptr;
     if (o2 != (B.out2 != nullptr)) {

@@ -61,7 +61,7 @@ __global__ __launch_bounds__(kBlock) void k_node_scalars(const float* __restrict
 //  * up to eight source rows are in flight per half-wave before the softmax needs anything;
 //  * a half-wave owns R CONSECUTIVE rows and software-pipelines them: while row i's gathers fly, the edge data of
 //    row i+1 and the extent of row i+2 are already being fetched, so a row costs one round trip, not four.
-struct FwdExtent { int beg, deg; float sd; };                 // deg < 0: no row
+struct FwdExtent { int beg, deg; float sd; int mk; };         // deg < 0: no row; mk: the row's mask byte (kind 4 only, else 0)
 struct FwdEdges { int src0, src1; float z0, z1; };            // the lane's two in-edges: source ids, edge terms
 struct FwdRaw {                                               // the same, as loaded (folded one iteration later)
     int pos;
@@ -87,11 +87,16 @@ using fni::GatFwdArgs;
 // training launches, whose run-time constants are then compile-time ones -- probabilities edge-major, no probs_orig, a level of at
 // least two edges, and an epilogue (if any) that is relu(dropout(.)) with p > 0 (fwd_kind_tr() on the host checks exactly that);
 // 3 the plain forward of the engine's EVALUATION launches: probabilities head-major, no probs_orig, >= 2 edges, an epilogue (if any)
-// that is a ReLU without dropout (fwd_kind_ev()).
+// that is a ReLU without dropout (fwd_kind_ev());
+// 4 the MASKED evaluation forward (fn_encoder_forward_masked): kind 3's constants -- except that a level may have fewer than two edges,
+// a batch of replicas of one small molecule has such levels -- plus one byte per destination row (rmask, 1 = this row is zero for
+// every reader).  The byte travels with the row's extent, two rows ahead, and acts on the finished row in registers, before the raw
+// store, the row-dots epilogue and the activation epilogue: none of the three sees memory in between.
 // Round 6: a third of this loop's issue slots were scalar bookkeeping and branches (profiles/r06_isa_mix.md); the tests of these
 // uniform flags inside the row loop were part of it: 0.761 -> 0.750 ms per step with them folded, bit-identical results.
 template <int H, int KL, bool RD = false, int O2 = 0>
-__device__ __forceinline__ void gat_fwd_rows(const GatFwdArgs& A, float (*sWf)[kWfLd], int blk0, int te, int rows_per_hw) {
+__device__ __forceinline__ void gat_fwd_rows(const GatFwdArgs& A, float (*sWf)[kWfLd], int blk0, int te, int rows_per_hw,
+                                             const uint8_t* __restrict__ rmask = nullptr) {
     const float* __restrict__ h = A.h;
     const float* __restrict__ s_dst = A.s_dst;
     const float* __restrict__ s_src = A.s_src;
@@ -100,7 +105,8 @@ __device__ __forceinline__ void gat_fwd_rows(const GatFwdArgs& A, float (*sWf)[k
     const float slope = A.slope;
     float* __restrict__ out = A.out;
     float* __restrict__ p_sorted = A.p_sorted;
-    constexpr bool TR = O2 == 2, EV = O2 == 3, KC = TR || EV;      // KC: a kind whose uniform flags are constants
+    constexpr bool MK = O2 == 4;
+    constexpr bool TR = O2 == 2, EV = O2 == 3 || MK, KC = TR || EV;      // KC: a kind whose uniform flags are constants
     float* __restrict__ probs_orig = KC ? nullptr : A.probs_orig;
     const bool wp = TR || p_sorted != nullptr;            // the engine's evaluation launches of a pass nobody differentiates save no probabilities
     const fn_act_epilogue& ep = A.ep;
@@ -120,9 +126,13 @@ __device__ __forceinline__ void gat_fwd_rows(const GatFwdArgs& A, float (*sWf)[k
     for (int k = 0; k < NE; ++k) wf[k] = (KL && k < K) ? sWf[head][k] : 0.f;
     const float wbias = KL ? sWf[head][K] : 0.f;
     const int tb = blk0 + (int)(threadIdx.x >> 5);
-    const bool pairs = KC ? true : m >= 2;                // paired edge loads need two edges in the level
+    const bool pairs = (KC && !MK) ? true : m >= 2;       // paired edge loads need two edges in the level
     const float* e_sorted = KL ? nullptr : et.s_sorted + (size_t)head * m;
     const int nr = A.n_real ? *A.n_real : n;              // rows behind it: padding of a static-shape batch -> rows without edges
+    // kind 4: a level without a mask of its own (only the atoms are masked, say) reads the bytes of its row extents instead and
+    // discards them -- the load stays unconditional, no branch in the row loop
+    const uint8_t* __restrict__ mk_p = (MK && rmask) ? rmask : reinterpret_cast<const uint8_t*>(pl.rowptr_d);
+    const int mk_on = (MK && rmask) ? 1 : 0;
 
     auto load_extent = [&](int t) {
         const int tc = t < n ? t : n - 1;
@@ -131,6 +141,8 @@ __device__ __forceinline__ void gat_fwd_rows(const GatFwdArgs& A, float (*sWf)[k
         x.beg = rp.x - pl.pos_base_d;
         x.deg = t < te ? (t < nr ? rp.y - rp.x : 0) : -1;
         x.sd = s_dst[(uint32_t)tc * H + head];
+        x.mk = 0;
+        if constexpr (MK) x.mk = mk_p[(uint32_t)tc] ? mk_on : 0;
         return x;
     };
     auto issue_edges = [&](const FwdExtent& x, FwdRawT<NE>& r) {
@@ -233,6 +245,7 @@ __device__ __forceinline__ void gat_fwd_rows(const GatFwdArgs& A, float (*sWf)[k
         // this row's stores, so that nothing at the top of the next iteration has to wait behind those stores
         const FwdEdges ed_n = fold_edges(nxt, raw);
         const float sd_cur = cur.sd;
+        const int mk_cur = cur.mk;
         cur = nxt;  nxt = nn;  ed = ed_n;
         float4 acc = make_float4(0.f, 0.f, 0.f, 0.f), acc2 = acc;
         // signed probabilities (sign bit = the LeakyReLU branch z <= 0): what the backward reads, and what out2 weighs by
@@ -340,6 +353,9 @@ __device__ __forceinline__ void gat_fwd_rows(const GatFwdArgs& A, float (*sWf)[k
                 if constexpr (o2) { const float q = l > 0.f ? p : slope * p;  fma4(acc2, q, row);  sg += q; }
             }
         }
+        if constexpr (MK) {      // a masked row is zero for all three readers below (selects, not a product: 0 * inf would be NaN)
+            acc.x = mk_cur ? 0.f : acc.x;  acc.y = mk_cur ? 0.f : acc.y;  acc.z = mk_cur ? 0.f : acc.z;  acc.w = mk_cur ? 0.f : acc.w;
+        }
         if (deg >= 0) {
             const uint32_t row_off = (uint32_t)t * (FN_D * 4) + lane * 16;          // (n <= 2^23 rows: fits)
             if (out) st4_off(out, row_off, acc);
@@ -376,7 +392,7 @@ __device__ __forceinline__ void gat_fwd_rows(const GatFwdArgs& A, float (*sWf)[k
 // a block owns kRows * R consecutive rows; its half-waves take them INTERLEAVED (row = base + i * kRows + hw), so
 // that at any moment the block works on kRows neighbouring rows whose source rows overlap (L1 reuse across waves)
 template <int H, int KL, bool RD = false, int O2 = 0>
-__device__ __forceinline__ void gat_fwd_body(const GatFwdArgs& A, float (*sWf)[kWfLd], int bid, int nblk) {
+__device__ __forceinline__ void gat_fwd_body(const GatFwdArgs& A, float (*sWf)[kWfLd], int bid, int nblk, const uint8_t* rmask = nullptr) {
     const int n = (int)A.pl.n, per = kRows * A.rows_per_hw;
     const int nr = A.n_real ? *A.n_real : n;
     const int blk0 = xcd_block_real(bid, nblk, A.n_real ? (nr + per - 1) / per : nblk) * per;      // real rows dealt evenly over the XCDs
@@ -397,6 +413,6 @@ __device__ __forceinline__ void gat_fwd_body(const GatFwdArgs& A, float (*sWf)[k
         return;
     }
     fold_edge_embed(A.et, A.att, A.att_w, H, sWf);
-    gat_fwd_rows<H, KL, RD, O2>(A, sWf, blk0, blk0 + per < n ? blk0 + per : n, A.rows_per_hw);
+    gat_fwd_rows<H, KL, RD, O2>(A, sWf, blk0, blk0 + per < n ? blk0 + per : n, A.rows_per_hw, rmask);
 }
 

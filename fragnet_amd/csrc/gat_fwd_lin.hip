@@ -32,6 +32,25 @@ __global__ __launch_bounds__(kBlock, 4) void k_gat_fwd_pair_lin(GatFwdArgs A, Ga
     else if (g < A.nblk + B.nblk) gat_fwd_body<H, KLB, false, O2>(B, sWf, g - A.nblk, B.nblk);
 }
 
+// kind 4 (masked evaluation forward): as in gat_fwd.hip, the mask pointers are kernel arguments of instances of their own
+template <int H, int KL>
+__global__ __launch_bounds__(kBlock, 4) void k_gat_fwd_lin_m(GatFwdArgs A, LinTasks T, int gat_base, const uint8_t* mk) {
+    extern __shared__ __attribute__((aligned(16))) float sBt[];
+    __shared__ float sWf[8][kWfLd];
+    int g;
+    if (lin_side_role(T, gat_base, &g)) { if (g < T.total) lin_side_block(sBt, T, g);  return; }
+    if (g < A.nblk) gat_fwd_body<H, KL, false, 4>(A, sWf, g, A.nblk, mk);
+}
+template <int H, int KLA, int KLB, bool RDA>
+__global__ __launch_bounds__(kBlock, 4) void k_gat_fwd_pair_lin_m(GatFwdArgs A, GatFwdArgs B, LinTasks T, int gat_base, const uint8_t* mka, const uint8_t* mkb) {
+    extern __shared__ __attribute__((aligned(16))) float sBt[];
+    __shared__ float sWf[8][kWfLd];
+    int g;
+    if (lin_side_role(T, gat_base, &g)) { if (g < T.total) lin_side_block(sBt, T, g);  return; }
+    if (g < A.nblk) gat_fwd_body<H, KLA, RDA, 4>(A, sWf, g, A.nblk, mka);
+    else if (g < A.nblk + B.nblk) gat_fwd_body<H, KLB, false, 4>(B, sWf, g - A.nblk, B.nblk, mkb);
+}
+
 }  // namespace
 
 namespace fni {
@@ -70,11 +89,16 @@ static bool lin_side_prepare(LinTasks& T, int gat_blocks, int* gat_base, int* gr
     return true;
 }
 
-int launch_gat_fwd_lin(const GatFwdArgs& A, LinTasks& T, int heads, hipStream_t st) {
+int launch_gat_fwd_lin(const GatFwdArgs& A, LinTasks& T, int heads, hipStream_t st, const FwdMask* mk) {
     int gb = 0, grid = 0;
     if (A.nblk == 0 || A.rd_out || edge_class(&A.et) != 0 || !lin_side_prepare(T, A.nblk, &gb, &grid)) {
-        if (int rc = launch_gat_fwd(A, heads, st)) return rc;
+        if (int rc = launch_gat_fwd(A, heads, st, mk)) return rc;
         return T.n ? launch_linear128_group(T, st) : 0;
+    }
+    if (mk) {
+        if (!fwd_kind_mk(A, heads)) return fail(FN_EUNSUPPORTED, "attention forward + projections: a masked level is a four-head evaluation level without second output");
+        hipLaunchKernelGGL((k_gat_fwd_lin_m<4, 0>), dim3(grid), dim3(kBlock), kLinSideLds, st, A, T, gb, mk->rows);
+        return launch_status("attention forward (masked rows) + projections of the next level");
     }
     const bool tr = fwd_kind_tr(A, heads), ev = fwd_kind_ev(A, heads);
     FN_DISPATCH_H(heads, {
@@ -85,16 +109,28 @@ int launch_gat_fwd_lin(const GatFwdArgs& A, LinTasks& T, int heads, hipStream_t 
     });
     return launch_status("attention forward + projections of the next level");
 }
-int launch_gat_fwd_pair_lin(const GatFwdArgs& A, const GatFwdArgs& B, LinTasks& T, int heads, hipStream_t st) {
+int launch_gat_fwd_pair_lin(const GatFwdArgs& A, const GatFwdArgs& B, LinTasks& T, int heads, hipStream_t st, const FwdMask* mka, const FwdMask* mkb) {
     const int ka = edge_class(&A.et), kb = edge_class(&B.et);
     int gb = 0, nwg = 0;
     const bool o2 = A.out2 != nullptr;
     if (A.nblk == 0 || B.nblk == 0 || ka != 1 || (kb != 1 && kb != FN_MAX_EDGE_K) || o2 != (B.out2 != nullptr) ||
         !lin_side_prepare(T, A.nblk + B.nblk, &gb, &nwg)) {
-        if (int rc = launch_gat_fwd_pair(A, B, heads, st)) return rc;
+        if (int rc = launch_gat_fwd_pair(A, B, heads, st, mka, mkb)) return rc;
         return T.n ? launch_linear128_group(T, st) : 0;
     }
     const dim3 grid(nwg);
+    if (mka || mkb) {
+        if (!mka || !mkb || !fwd_kind_mk(A, heads) || !fwd_kind_mk(B, heads))
+            return fail(FN_EUNSUPPORTED, "attention forward (two levels) + atom projection: masked levels are four-head evaluation levels without second output");
+        if (A.rd_out) {
+            if (kb == 1) hipLaunchKernelGGL((k_gat_fwd_pair_lin_m<4, 1, 1, true>), grid, dim3(kBlock), kLinSideLds, st, A, B, T, gb, mka->rows, mkb->rows);
+            else hipLaunchKernelGGL((k_gat_fwd_pair_lin_m<4, 1, FN_MAX_EDGE_K, true>), grid, dim3(kBlock), kLinSideLds, st, A, B, T, gb, mka->rows, mkb->rows);
+        } else {
+            if (kb == 1) hipLaunchKernelGGL((k_gat_fwd_pair_lin_m<4, 1, 1, false>), grid, dim3(kBlock), kLinSideLds, st, A, B, T, gb, mka->rows, mkb->rows);
+            else hipLaunchKernelGGL((k_gat_fwd_pair_lin_m<4, 1, FN_MAX_EDGE_K, false>), grid, dim3(kBlock), kLinSideLds, st, A, B, T, gb, mka->rows, mkb->rows);
+        }
+        return launch_status("attention forward (two levels, masked rows) + atom projection");
+    }
 #define FN_PAIR_LIN(KB, RD)                                                                                                  \
     do {                                                                                                                     \
         if constexpr (HH == 4) { if (o2 && tr) { hipLaunchKernelGGL((k_gat_fwd_pair_lin<HH, 1, KB, RD, 2>), grid, dim3(kBlock), kLinSideLds, st, A, B, T, gb);  break; } } \

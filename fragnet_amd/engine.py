@@ -198,10 +198,46 @@ def adam_rider_taken() -> bool:
     return taken
 
 
+def _row_mask(t, rows: int, name: str):
+    if t is None:
+        return None
+    if not torch.is_tensor(t) or t.dtype != torch.uint8 or not t.is_cuda or t.dim() != 1 or t.numel() != rows or not t.is_contiguous():
+        raise ValueError(f"row_masks: {name} must be a contiguous uint8 CUDA tensor of {rows} rows (1 = zero this row)")
+    return t
+
+
+def _masked_forward(plan, x_atoms, bond_nodes, fbond_nodes, cos_sorted, fattr_sorted, params, n_layers, heads, variant, edge_outputs, row_masks):
+    """fn_encoder_forward_masked: an evaluation pass nobody differentiates, so no autograd node -- the outputs are plain tensors."""
+    x_atoms, bond_nodes, fbond_nodes = _f32(x_atoms, "x_atoms"), _f32(bond_nodes, "node_features_bonds"), _f32(fbond_nodes, "node_features_fbonds")
+    params = tuple(_f32(p.detach(), "parameter") for p in params)
+    dev = x_atoms.device
+    lib = _lib.load()
+    e = _describe(plan, x_atoms, bond_nodes, fbond_nodes, cos_sorted, fattr_sorted, params, n_layers, heads, 0.0, False, 0, 0, None, variant, True)
+    names = ("mask_atoms", "mask_bonds", "mask_fbonds")
+    masks = [_row_mask(t, n, name) for t, n, name in zip(row_masks, (e.N, e.E, e.EF), names)]
+    m = _lib.RowMasks(*(None if t is None else t.data_ptr() for t in masks))
+    ws = torch.empty(lib.fn_encoder_ws_floats(C.byref(e)), dtype=torch.float32, device=dev)
+    e.ws, e.ws_floats = ws.data_ptr(), ws.numel()
+    outs = [torch.empty((n if (edge_outputs or k < 2) else 0, FN_D), dtype=torch.float32, device=dev) for k, n in enumerate((e.N, e.F, e.E, e.EF))]
+    pooled = torch.empty(0, dtype=torch.float32, device=dev)
+    if lib.fn_encoder_fused_tail(C.byref(e)):
+        pooled = torch.empty((e.n_mols, 2 * FN_D), dtype=torch.float32, device=dev)
+        e.pooled = pooled.data_ptr()
+    _lib.check(lib.fn_encoder_forward_masked(C.byref(e), C.byref(m), *((o.data_ptr() if (edge_outputs or k < 2) else None) for k, o in enumerate(outs)),
+                                             _stream_ptr(dev)), "fn_encoder_forward_masked")
+    plan.pending.pop("bond", None)
+    plan.pending.pop("frag" if variant == 2 else "fbond", None)
+    return tuple(outs) + (pooled,)
+
+
 def encoder_forward(layers, plan: GraphPlan, x_atoms, bond_nodes, fbond_nodes, cos_sorted, fattr_sorted, heads: int,
-                    drop_p: float, training: bool, rng, variant: int = 0, edge_outputs: bool = True) -> tuple:
+                    drop_p: float, training: bool, rng, variant: int = 0, edge_outputs: bool = True, row_masks=None) -> tuple:
     """Runs all ``layers`` (FragNetLayerA modules) + the inter-layer act(dropout(.)); returns the four outputs and, fifth,
-    the readout [n_mols, 256] when the fused fragment tail produced it (an empty tensor otherwise)."""
+    the readout [n_mols, 256] when the fused fragment tail produced it (an empty tensor otherwise).
+
+    ``row_masks``: None, or a triple (atoms [N], bonds [E], fragment bonds [EF]) of uint8 CUDA tensors or None -- 1 = that row of
+    the level's output is zero for every reader, in every layer (fn_encoder_forward_masked).  A masked pass is an evaluation pass
+    without a backward: in training mode, or with a gradient required anywhere, it raises."""
     params = [p for layer in layers for p in layer_param_list(layer)]
     n_layers = len(layers)
     # the C side takes widths from the batch and pointers from the parameters: a model built for other feature widths would
@@ -212,6 +248,15 @@ def encoder_forward(layers, plan: GraphPlan, x_atoms, bond_nodes, fbond_nodes, c
         if w.dim() != 2 or x.dim() != 2 or w.shape[1] != x.shape[1] or w.shape[0] != FN_D:
             raise RuntimeError(f"mat1 and mat2 shapes cannot be multiplied ({x.shape[0]}x{x.shape[-1]} and {w.shape[-1]}x{w.shape[0]}): "
                                f"layer 0 {name} expects {w.shape[-1]} input features, the batch has {x.shape[-1]}")
+    if row_masks is not None and len(row_masks) != 3:
+        raise ValueError("row_masks: a triple (atoms, bonds, fragment bonds)")
+    if row_masks is not None and any(t is not None for t in row_masks):
+        if training:
+            raise RuntimeError("row_masks: a masked pass is an evaluation pass (the model is in training mode)")
+        if torch.is_grad_enabled() and any(t.requires_grad for t in (x_atoms, bond_nodes, fbond_nodes, *params)):
+            raise RuntimeError("row_masks: the masked pass has no backward; run it under torch.no_grad()")
+        return _masked_forward(plan, x_atoms, bond_nodes, fbond_nodes, cos_sorted, fattr_sorted, params, len(layers), heads, int(variant),
+                               bool(edge_outputs), row_masks)
     p_eff = float(drop_p) if training else 0.0
     if p_eff > 0.0:
         # reserve the Philox offsets the engine will consume (fn_encoder_rng_blocks): x_atoms + 4 tensors per layer

@@ -293,6 +293,9 @@ class FragNet(nn.Module):
         not store the last layer's activated bond / fragment-bond rows; the third and fourth result are then empty tensors."""
         plan = plan_for(batch)
         p, train = self.dropout.p, self.training
+        row_masks = batch_row_masks(batch)
+        if row_masks is not None:
+            return self._forward_masked(batch, plan, row_masks, edge_outputs)
         if self.variant == "gat2_edge" and self.use_engine and not any(l.return_attentions for l in self.layers):
             # whole encoder in two C calls (fn_encoder.variant = 2); the placeholder fragment-bond input is never multiplied
             outs = engine.encoder_forward(self.layers, plan, batch["x_atoms"], batch["node_features_bonds"],
@@ -338,6 +341,32 @@ class FragNet(nn.Module):
             if not lite:
                 fbond_nodes = ops.dropout_act(fbond_nodes, p, train, True, self.rng)
         return x_atoms, x_frags, bond_nodes, (None if lite else fbond_nodes)
+
+
+    def _forward_masked(self, batch, plan, row_masks, edge_outputs):
+        """A batch that carries row masks (MASK_KEYS): one masked evaluation pass of the engine.  There is no per-level form of it."""
+        if self.variant != "gat2":
+            raise ValueError(f"row masks ({', '.join(MASK_KEYS)}): model_version {self.variant!r} has no masks (gat2 only)")
+        if not self.use_engine or any(l.return_attentions or l.bond_mask is not None or l.frag_bond_mask is not None
+                                      or l.atom_mask_individual is not None for l in self.layers):
+            raise ValueError("row masks in the batch run on the engine only: not with use_engine=False, return_attentions or the "
+                             "per-layer scalar mask attributes")
+        outs = engine.encoder_forward(self.layers, plan, batch["x_atoms"], batch["node_features_bonds"],
+                                      batch["node_features_fbonds"], plan.sorted_attr("bond", batch["edge_attr_bonds"], defer=True),
+                                      plan.sorted_attr("fbond", batch["edge_attr_fbonds"], defer=True), self.layers[0].num_heads,
+                                      self.dropout.p, self.training, self.rng, variant=0, edge_outputs=edge_outputs, row_masks=row_masks)
+        if outs[4].numel():
+            outs[0]._fragnet_readout = (outs[1], outs[4], outs[0]._version, outs[1]._version)
+        return outs[:4]
+
+
+MASK_KEYS = ("mask_atoms", "mask_bonds", "mask_fbonds")      # optional batch keys: uint8 [N] / [E] / [EF], 1 = zero this row in every layer
+
+
+def batch_row_masks(batch):
+    """The (atoms, bonds, fragment bonds) row masks a batch carries, or None when it carries none (the usual batch)."""
+    masks = tuple(batch.get(k) for k in MASK_KEYS)
+    return masks if any(m is not None for m in masks) else None
 
 
 # ------------------------------------------------------------------------------------ heads

@@ -802,6 +802,29 @@ uint64_t fn_encoder_rng_blocks(const fn_encoder* e);
  * graphs read their raw rows).  The other outputs do not change a bit. */
 int fn_encoder_forward(const fn_encoder* e, float* out_atoms /*[N,128]*/, float* out_frags /*[F,128]*/,
                        float* out_bond /*[E,128], nullable*/, float* out_fbond /*[EF,128], nullable*/, fn_stream_t stream);
+/* Row masks of an evaluation pass (leave-one-out attribution; the reference's bond_mask / atom_mask_individual / frag_bond_mask,
+ * gat2.py:173-176, 227-231, 275-278, as a per-batch input instead of one scalar index per layer).  One byte per row, non-zero = the
+ * row is ZERO for every reader, in EVERY layer: the bond level's new_bond [E], the atom level's x_atoms_new [N], the fragment-bond
+ * level's new_fbond [EF] -- set on the finished row inside the level's kernel, before the raw store, the atom graph's edge term and the
+ * activated store.  Each array is nullable (no masked row in that index space).  A bond is the two directed rows 2k, 2k + 1 of its
+ * molecule, and so is a fragment connection: whoever fills the arrays sets both (fn_loo_row_masks_u8 does).  There is no fragment mask.
+ * m == NULL or three NULL arrays: fn_encoder_forward itself, bit for bit.  Otherwise the pass needs variant == 0 (FN_EUNSUPPORTED),
+ * training == 0 and no_backward == 1 (FN_EINVAL) and heads == 4 (FN_EUNSUPPORTED): refused before anything is launched.  ABI 12. */
+typedef struct fn_row_masks {
+    const uint8_t *atoms /*[N]*/, *bonds /*[E]*/, *fbonds /*[EF]*/;
+} fn_row_masks;
+int fn_encoder_forward_masked(const fn_encoder* e, const fn_row_masks* m, float* out_atoms, float* out_frags, float* out_bond,
+                              float* out_fbond, fn_stream_t stream);
+/* The three masks of a batch of leave-one-out replicas, zero-filled and set in ONE launch.  replicas: int32 [n_mols][2] = (kind, local
+ * index) of molecule i of the batch; kind 0 masks nothing, 1 the atom `index`, 2 the bond `index` (directed rows 2 index, 2 index + 1),
+ * 3 the fragment connection `index` (rows 2 index, 2 index + 1), all local to the molecule.  *_off: int32 [n_mols + 1], first row of
+ * molecule i in the atom / directed-bond / directed-fragment-connection space (rows of a CollatedBatch's offsets table); they must end
+ * at N / E / EF.  The masks are 16-byte aligned device arrays of N / E / EF bytes.  A replica whose kind is not 0..3 or whose rows are
+ * not all inside its molecule writes nothing and ORs FN_STATUS_BAD_REPLICA into *status (device word, required). */
+#define FN_STATUS_BAD_REPLICA 8
+int fn_loo_row_masks_u8(const int32_t* replicas, int64_t n_mols, const int32_t* atom_off, const int32_t* bond_off,
+                        const int32_t* fbond_off, uint8_t* mask_atoms, int64_t N, uint8_t* mask_bonds, int64_t E,
+                        uint8_t* mask_fbonds, int64_t EF, int32_t* status, fn_stream_t stream);
 /* g_* are dL/d(out_*) (nullable = zero); out_* are the forward outputs (needed for the ReLU mask; out_bond / out_fbond may be
  * NULL where the forward pass was given NULL -- their gradients must then be NULL too). */
 int fn_encoder_backward(const fn_encoder* e, const float* out_atoms, const float* out_frags, const float* out_bond,

@@ -1,0 +1,191 @@
+"""Host side of the leave-one-out attributions (fragnet_amd/attribution.py, scripts/attribute_gat2.py) and the pin of the
+reference's fixture tests/golden/attr_loo_b6.npz (written by tests/golden/make_golden_attr.py) on the CPU: the oracle, with the
+reference's scalar mask attributes on every layer, against the reference's own leave-one-out predictions."""
+import json
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+from fragnet_amd import attribution as attr
+from tests import attr_common as ac
+from tests.conftest import GOLDEN, ROOT
+
+
+def _restated(na, nb, nf, kinds):
+    rows = []
+    if "atom" in kinds:
+        rows += [(1, i) for i in range(na)]
+    if "bond" in kinds:
+        rows += [(2, i) for i in range(nb) if i % 2 == 0]
+    if "fbond" in kinds:
+        rows += [(3, k) for k in range(nf // 2)]
+    return np.asarray(rows, dtype=np.int32).reshape(-1, 2)
+
+
+def test_replica_table_matches_a_plain_restatement():
+    rng = np.random.default_rng(0)
+    for kinds in (("atom", "bond", "fbond"), ("bond",), ("fbond", "atom")):
+        na = rng.integers(1, 60, size=40)
+        nb = 2 * rng.integers(0, 70, size=40)
+        nf = 2 * rng.integers(0, 9, size=40)
+        table = attr.replica_table(na, nb, nf, kinds)
+        assert len(table) == 40
+        for t, a, b, f in zip(table, na, nb, nf):
+            assert t.dtype == np.int32
+            np.testing.assert_array_equal(t, _restated(int(a), int(b), int(f), kinds))
+
+
+def test_single_fragment_molecule_has_no_fragment_bond_replica():
+    (t,) = attr.replica_table([7], [12], [0])
+    assert (t[:, 0] == attr.KIND_FBOND).sum() == 0 and t.shape[0] == 7 + 6
+    (t,) = attr.replica_table([7], [12], [0], kinds=("fbond",))
+    assert t.shape == (0, 2)
+    (t,) = attr.replica_table([7], [12], [1])        # the featuriser's placeholder row of a single-fragment molecule
+    assert (t[:, 0] == attr.KIND_FBOND).sum() == 0 and t.shape[0] == 7 + 6
+    with pytest.raises(ValueError):
+        attr.replica_table([7], [12], [3])
+
+
+def test_replica_table_refuses_bad_input():
+    with pytest.raises(ValueError):
+        attr.replica_table([3], [5], [0])            # odd number of directed bonds
+    with pytest.raises(ValueError):
+        attr.replica_table([3], [4], [0], kinds=("atoms",))
+    with pytest.raises(ValueError):
+        attr.replica_table([3, 4], [4], [0])
+
+
+def test_local_index_halves_bond_rows_only():
+    t = np.asarray([(1, 5), (2, 6), (3, 2), (2, 0)], dtype=np.int32)
+    np.testing.assert_array_equal(attr.local_index(t), [(1, 5), (2, 3), (3, 2), (2, 0)])
+    assert t[1, 1] == 6                               # a copy
+
+
+def _flatten(chunks):
+    return [(i, r) for c in chunks for i, r0, r1 in c for r in range(r0, r1)]
+
+
+def test_chunker_takes_every_replica_once_within_the_budget():
+    rng = np.random.default_rng(1)
+    rows = rng.integers(5, 120, size=50)
+    counts = rng.integers(0, 90, size=50)
+    for budget in (130, 1000, 10 ** 9):
+        chunks = attr.plan_chunks(rows, counts, budget)
+        assert _flatten(chunks) == [(i, r) for i in range(50) for r in range(counts[i])]        # all, once, in order
+        for c in chunks:
+            assert c and sum((r1 - r0) * rows[i] for i, r0, r1 in c) <= budget
+    assert len(attr.plan_chunks(rows, counts, 10 ** 9)) == 1
+
+
+def test_chunker_lets_a_molecule_span_chunks_and_survives_an_oversized_one():
+    chunks = attr.plan_chunks([10], [25], 100)
+    assert chunks == [[(0, 0, 10)], [(0, 10, 20)], [(0, 20, 25)]]
+    chunks = attr.plan_chunks([10, 500, 10], [3, 2, 3], 100)                 # the middle molecule alone exceeds the budget
+    assert _flatten(chunks) == [(0, 0), (0, 1), (0, 2), (1, 0), (1, 1), (2, 0), (2, 1), (2, 2)]
+    assert [(1, 0, 1)] in chunks and [(1, 1, 2)] in chunks
+    with pytest.raises(ValueError):
+        attr.plan_chunks([1], [1], 0)
+
+
+def test_collate_accepts_repeated_molecules():
+    """The replica batch is FlatMolStore.collate with repeated indices: same batch as collate_fn of the repeated list."""
+    from fragnet_amd import data
+    from fragnet_amd.dataset import FlatMolStore
+    mols = ac.molecules(4)
+    idx = [2, 2, 0, 3, 3, 3, 1]
+    got = FlatMolStore.from_records(mols).collate(idx)
+    want = data.collate_fn([mols[i] for i in idx])
+    for k, v in want.items():
+        assert torch.equal(got[k], v), k
+    assert torch.equal(got.offsets, want.offsets)
+
+
+def _fixture():
+    z = np.load(os.path.join(GOLDEN, "attr_loo_b6.npz"))
+    return z, json.loads(str(z["cfg"]))
+
+
+def test_oracle_matches_the_reference_leave_one_out_fixture():
+    """Pins tests/golden/attr_loo_b6.npz here: the oracle's scaled model has the reference's weights (checksums) and its
+    one-molecule, one-mask predictions are the reference's to fp32 round-off.  Also the condition the GPU tests rest on: the
+    attributions of this model are large against the tolerance they are held to (measured: atoms 0.94, bonds 0.75, fragment
+    bonds 0.45 of them above 10 x tolerance)."""
+    from fragnet_amd import data
+    from oracle import fragnet_ref as R
+    from tests.helpers import check_params_match
+    torch.set_num_threads(1)
+    z, cfg = _fixture()
+    assert (cfg["seed"], cfg["mol_seed"], cfg["n_mols"], cfg["head_scale"], cfg["att_scale"]) == (ac.SEED, ac.MOL_SEED, ac.N_MOLS, ac.HEAD_SCALE, ac.ATT_SCALE)
+    model = ac.build(R, cfg["ctor"], cfg["seed"], scaled=True)
+    check_params_match(model, json.loads(str(z["pkeys"])), z["psums"])
+    recs = ac.scalar_loo(model, ac.molecules(), data.collate_fn)
+    big = {k: [] for k in ac.MASK_ATTR}
+    for i, rec in enumerate(recs):
+        base = z[f"m{i}/pred_no_mask"]
+        np.testing.assert_allclose(rec["pred_no_mask"], base, atol=2e-5, rtol=2e-5)
+        for kind in ac.MASK_ATTR:
+            np.testing.assert_array_equal(rec[kind]["index"], z[f"m{i}/{kind}_index"])
+            np.testing.assert_allclose(rec[kind]["pred_mask"], z[f"m{i}/{kind}_pred_mask"], atol=2e-5, rtol=2e-5)
+            a = base[None, :] - z[f"m{i}/{kind}_pred_mask"]
+            big[kind] += list((np.abs(a) > 10 * ac.attr_tolerance(base)[None, :]).reshape(-1))
+    counts = {k: len(v) for k, v in big.items()}
+    assert counts == {"atom": 190, "bond": 187, "fbond": 22}
+    shares = {k: float(np.mean(v)) for k, v in big.items()}
+    assert all(s >= 0.25 for s in shares.values()), shares
+    assert float(np.mean(sum(big.values(), []))) >= 0.5, shares
+
+
+def test_fixture_holds_numbers_only_and_is_small():
+    z, _ = _fixture()
+    assert os.path.getsize(os.path.join(GOLDEN, "attr_loo_b6.npz")) < 64 * 1024
+    for k in z.files:
+        assert z[k].dtype.kind in "fiU", k
+
+
+SCRIPT = os.path.join(ROOT, "scripts", "attribute_gat2.py")
+
+
+def _script(*argv):
+    return subprocess.run([sys.executable, SCRIPT, *argv], capture_output=True, text=True, cwd=ROOT)
+
+
+def test_script_argument_handling():
+    r = _script("--help")
+    assert r.returncode == 0 and "--checkpoint" in r.stdout and "--max-rows" in r.stdout
+    r = _script("--config", "c.yaml", "--checkpoint", "m.pt", "--data", "d.pt")
+    assert r.returncode == 2 and "--out" in r.stderr
+    base = ["--config", "c.yaml", "--checkpoint", "m.pt", "--data", "d.pt"]
+    assert _script(*base, "--out", "a.txt").returncode == 2
+    assert _script(*base, "--out", "a.npz", "--kinds", "atom", "atom").returncode == 2
+    assert _script(*base, "--out", "a.npz", "--kinds", "fragment").returncode == 2
+    assert _script(*base, "--out", "a.npz", "--max-rows", "0").returncode == 2
+
+
+def test_script_parses_a_full_command_line():
+    sys.path.insert(0, os.path.join(ROOT, "scripts"))
+    try:
+        import attribute_gat2
+    finally:
+        sys.path.pop(0)
+    a = attribute_gat2.parse_args(["--config", "c.yaml", "--checkpoint", "m.pt", "--data", "d.pkl", "--out", "o/a.npz", "--kinds", "bond", "atom",
+                                   "--max-rows", "4096"])
+    assert (a.kinds, a.max_rows, a.batch_size, a.device) == (["bond", "atom"], 4096, 512, "cuda:0")
+
+
+def test_leave_one_out_refuses_what_it_cannot_do():
+    from fragnet_amd import _lib
+    from fragnet_amd.model import FragNetFineTune, FragNetFineTuneLite
+    mols = ac.molecules(2)
+    small = dict(num_layer=1, h1=8, h2=8, h3=8, h4=8)
+    with pytest.raises(ValueError, match="gat2"):
+        attr.leave_one_out(FragNetFineTuneLite(**small), mols)
+    with pytest.raises(ValueError, match="gat2"):
+        attr.leave_one_out(FragNetFineTune(variant="gat2_edge", **small), mols)
+    with pytest.raises(_lib.FragnetHipError):                      # a CPU model: no fallback
+        attr.leave_one_out(FragNetFineTune(**small), mols)
+    with pytest.raises(ValueError):
+        attr.leave_one_out(FragNetFineTune(**small), mols, kinds=("atoms",))
