@@ -108,7 +108,6 @@ FNI_HIDDEN int prep_gat_fwd(const float* h, const float* s_dst, const float* s_s
 // A non-null FwdMask makes a launch a MASKED evaluation launch (forward kind 4, gat_fwd.inc): rows[t] != 0 -> row t of the level is zero
 // for everything that reads it.  rows == null: a level of a masked pass that has no mask of its own.  In a two-level launch both come or neither.
 struct FwdMask { const uint8_t* rows; };
-FNI_HIDDEN bool fwd_kind_mk(const GatFwdArgs& A, int heads);
 FNI_HIDDEN int launch_gat_fwd(const GatFwdArgs& A, int heads, hipStream_t st, const FwdMask* mk = nullptr);
 FNI_HIDDEN int launch_gat_fwd_pair(const GatFwdArgs& A, const GatFwdArgs& B, int heads, hipStream_t st, const FwdMask* mka = nullptr, const FwdMask* mkb = nullptr);
 // gat_fwd_lin.hip: an attention pass + the K = 128 projection tiles that do not depend on it, in one launch
@@ -169,15 +168,47 @@ FNI_HIDDEN bool bad_edge_term(const fn_edge_term* et, int64_t m);
 namespace {
 inline hipStream_t S(fn_stream_t s) { return reinterpret_cast<hipStream_t>(s); }
 #define FN_TRY(expr) do { int rc_ = (expr); if (rc_) return rc_; } while (0)
-// forward kind 2 (gat_fwd.inc): this level's run-time flags are the engine's training constants
-inline bool fwd_kind_tr(const fni::GatFwdArgs& A, int heads) {
-    return fni::tune(FN_TUNE_ENGINE_CONST) != 0 && A.out2 != nullptr && A.p_edge_major != 0 && A.probs_orig == nullptr && A.pl.m >= 2 &&
-           (A.ep.y == nullptr || (A.ep.relu != 0 && A.ep.p > 0.f)) && (A.rd_out == nullptr || A.rd_J == heads);
+// ---- which KIND of the attention forward (the O2 template argument of its kernels) a launch takes.  The comment above gat_fwd_rows
+// (gat_fwd.inc) is the one description of what each kind takes for granted; it calls the kind 2 / kind 3 conditions below
+// fwd_kind_tr() / fwd_kind_ev().  masked: the launch comes with a FwdMask; such a launch is kind 4 or does not exist (kFwdNoKind).
+constexpr int kFwdNoKind = -1;
+inline int fwd_kind(const fni::GatFwdArgs& A, int heads, bool masked) {
+    const bool o2 = A.out2 != nullptr, drop = A.ep.p > 0.f;
+    // what the kinds with compile-time flags (2, 3, 4) share: four heads, no probs_orig, probabilities edge-major with the second output
+    // and head-major without, an epilogue (if any) that is a ReLU -- after dropout with the second output, without dropout otherwise --
+    // and row dots (if any) of every head
+    const bool flags = heads == 4 && A.probs_orig == nullptr && (A.p_edge_major != 0) == o2 &&
+                       (A.ep.y == nullptr || (A.ep.relu != 0 && drop == o2)) && (A.rd_out == nullptr || A.rd_J == heads);
+    if (masked) return flags && !o2 ? 4 : kFwdNoKind;                       // (a masked level may have fewer than two edges)
+    if (flags && fni::tune(FN_TUNE_ENGINE_CONST) != 0 && A.pl.m >= 2) return o2 ? 2 : 3;
+    return o2 ? 1 : 0;
 }
-// forward kind 3: the engine's evaluation launches (no second output, head-major probabilities, ReLU epilogue without dropout)
-inline bool fwd_kind_ev(const fni::GatFwdArgs& A, int heads) {
-    return fni::tune(FN_TUNE_ENGINE_CONST) != 0 && A.out2 == nullptr && A.p_edge_major == 0 && A.probs_orig == nullptr && A.pl.m >= 2 &&
-           (A.ep.y == nullptr || (A.ep.relu != 0 && !(A.ep.p > 0.f))) && (A.rd_out == nullptr || A.rd_J == heads);
+inline int fwd_kind_plain(int kind) { return kind == 2 ? 1 : kind == 3 ? 0 : kind; }     // kinds 2 / 3 are kinds 1 / 0 with constant flags
+// two levels in one launch run ONE kind: the kind both take, else the plain kind (0 / 1) both reduce to, else kFwdNoKind -- one level
+// with the second output and one without, or a masked launch in which a level has no FwdMask or is not kind 4.  The caller then runs
+// the levels one by one (unmasked) or fails (masked).
+inline int fwd_kind_pair(const fni::GatFwdArgs& A, const fni::GatFwdArgs& B, int heads, const fni::FwdMask* mka, const fni::FwdMask* mkb) {
+    const bool masked = mka || mkb;
+    if (masked && !(mka && mkb)) return kFwdNoKind;
+    const int ka = fwd_kind(A, heads, masked), kb = fwd_kind(B, heads, masked);
+    if (ka == kb) return ka;
+    if (masked) return kFwdNoKind;
+    return fwd_kind_plain(ka) == fwd_kind_plain(kb) ? fwd_kind_plain(ka) : kFwdNoKind;
+}
+// ---- run-time values to template arguments: with_const<V0, V1, ..>(v, f) calls f(std::integral_constant<int, Vi>{}) for the Vi equal to
+// v and returns whether there was one.  A kernel called from f is instantiated for the listed values and no others.
+template <int... Vs, class F> inline bool with_const(int v, F&& f) {
+    return ((v == Vs && (f(std::integral_constant<int, Vs>{}), true)) || ...);
+}
+#define FN_CV(c) decltype(c)::value
+template <class F> inline bool with_edge_class(int kl, F&& f) { return with_const<0, 1, FN_MAX_EDGE_K>(kl, f); }     // kl: edge_class(), below
+inline int bad_heads() { return fni::fail(FN_EUNSUPPORTED, "heads must be 1, 2, 4 or 8 (128 = heads * head_dim)"); }
+// (heads, kind) of an UNMASKED attention forward launch: f(H, O2).  Kinds 2 and 3 exist for four heads only (fwd_kind returns them for
+// no other count); kind 4 has kernels of its own (four heads)
+template <class F> inline int with_heads_kind(int heads, int kind, F&& f) {
+    const bool ok = kind >= 2 ? heads == 4 && with_const<2, 3>(kind, [&](auto k) { f(std::integral_constant<int, 4>{}, k); })
+                              : with_const<1, 2, 4, 8>(heads, [&](auto h) { with_const<0, 1>(kind, [&](auto k) { f(h, k); }); });
+    return ok ? 0 : bad_heads();
 }
 #define FN_DISPATCH_H(heads, CALL)                         \
     switch (heads) {                                       \
@@ -185,7 +216,7 @@ inline bool fwd_kind_ev(const fni::GatFwdArgs& A, int heads) {
         case 2: { constexpr int HH = 2; CALL; } break;     \
         case 4: { constexpr int HH = 4; CALL; } break;     \
         case 8: { constexpr int HH = 8; CALL; } break;     \
-        default: return fni::fail(FN_EUNSUPPORTED, "heads must be 1, 2, 4 or 8 (128 = heads * head_dim)"); \
+        default: return bad_heads();                       \
     }
 constexpr int kBlock = 256;
 constexpr int kRows = 8;          // rows (half-waves) per block
@@ -205,7 +236,26 @@ inline int flat_grid(int64_t work, int cap) {
 }
 // edge class of an attention level = the KL template argument of its kernels: 0 stored edge term, 1 / FN_MAX_EDGE_K raw attributes
 inline int edge_class(const fn_edge_term* et) { return et->mode == 0 ? 0 : (et->K == 1 ? 1 : FN_MAX_EDGE_K); }
+// the two-level forward kernels exist for two levels that are both there, the first of edge class 1, the second of class 1 or FN_MAX_EDGE_K
+inline bool fwd_pair_classes(const fni::GatFwdArgs& A, const fni::GatFwdArgs& B) {
+    return A.nblk != 0 && B.nblk != 0 && edge_class(&A.et) == 1 && edge_class(&B.et) != 0;
+}
 inline int lin_blocks(int64_t tiles, int iters) { return 2 * (int)((tiles + iters - 1) / iters); }     // 64 x 64 tiles: two column halves per row tile
+// lays the workgroups of a task group out: drops the tasks without rows, gives every other one the blocks [first, first + nblk) -- each
+// walks `iters` tiles of `tile_rows` rows --, compacts T.t[] and returns the block total
+inline int lin_layout(fni::LinTasks& T, int tile_rows, int iters) {
+    int blocks = 0, live = 0;
+    for (int i = 0; i < T.n; ++i) {
+        if (T.t[i].M <= 0) continue;
+        fni::LinTask t = T.t[i];
+        t.first = blocks;
+        t.nblk = lin_blocks((t.M + tile_rows - 1) / tile_rows, iters);
+        blocks += t.nblk;
+        T.t[live++] = t;
+    }
+    T.n = live;
+    return blocks;
+}
 
 constexpr int kWfLd = FN_MAX_EDGE_K + 1;
 

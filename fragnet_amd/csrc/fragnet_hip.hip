@@ -38,7 +38,7 @@ int launch_status(const char* where) {
     return 0;
 }
 
-// (S(), kBlock, kRows, kGridCap, kBwdRows, row_grid, flat_grid, edge_class, lin_blocks, FN_TRY, FN_DISPATCH_H: fn_internal.h)
+// (S(), kBlock, kRows, kGridCap, kBwdRows, row_grid, flat_grid, edge_class, lin_blocks, lin_layout, FN_TRY, FN_DISPATCH_H: fn_internal.h)
 constexpr int kRowDotsBwdBlocks = 512;    // blocks of k_row_dots_sorted_bwd (each writes one J*128-wide partial row)
 using fni::GatFwdArgs;
 using fni::prep_gat_fwd;
@@ -1774,27 +1774,13 @@ int linear128_group_impl(LinTasks& T, hipStream_t st) {
     int64_t total = 0;
     for (int i = 0; i < T.n; ++i) total += T.t[i].M > 0 ? (T.t[i].M + kLinRows - 1) / kLinRows : 0;
     const int iters = lin_iters(total);
-    int blocks = 0, live = 0;
-    for (int i = 0; i < T.n; ++i) {
-        if (T.t[i].M <= 0) continue;
-        LinTask t = T.t[i];
-        t.first = blocks;
-        t.nblk = lin_blocks((t.M + kLinRows - 1) / kLinRows, iters);
-        blocks += t.nblk;
-        T.t[live++] = t;
-    }
-    T.n = live;
+    int blocks = lin_layout(T, kLinRows, iters);
     T.K = 128;
-    if (!live) return 0;
+    if (!T.n) return 0;
     bool any_ra = false;
     for (int i = 0; i < T.n; ++i) any_ra |= T.t[i].ra.z != nullptr;
     if (any_ra) {                          // a RowAdd term must not get lost: the kernel variant that applies it (one tile per workgroup)
-        blocks = 0;
-        for (int i = 0; i < T.n; ++i) {
-            T.t[i].first = blocks;
-            T.t[i].nblk = lin_blocks((T.t[i].M + kLinRows - 1) / kLinRows, 1);
-            blocks += T.t[i].nblk;
-        }
+        blocks = lin_layout(T, kLinRows, 1);
         hipLaunchKernelGGL(k_linear128_multi_ra, dim3(blocks), dim3(kLinThreads), lds, st, T);
         return launch_status("grouped projection GEMM (+ row term)");
     }
@@ -1814,19 +1800,11 @@ int launch_linear128_small_group(LinTasks& T, hipStream_t st) {
     bool mixed = false;                          // a task with 20 < K <= 168 rides along (k_linear128_layer0)
     for (int i = 0; i < T.n; ++i) mixed |= T.t[i].M > 0 && T.t[i].K > 4 * KQ;
     const size_t lds = (size_t)(4 * (mixed ? 44 : KQ) * kLinLd) * sizeof(float);
-    int blocks = 0, live = 0;
-    for (int i = 0; i < T.n; ++i) {
-        if (T.t[i].M <= 0) continue;
-        LinTask t = T.t[i];
-        if (t.K < 1 || t.K > 168) return fail(FN_EINVAL, "layer-0 projection group: K must be 1..168");
-        t.first = blocks;
-        t.nblk = lin_blocks((t.M + kLinRows - 1) / kLinRows, 1);
-        blocks += t.nblk;
-        T.t[live++] = t;
-    }
-    T.n = live;
+    for (int i = 0; i < T.n; ++i)
+        if (T.t[i].M > 0 && (T.t[i].K < 1 || T.t[i].K > 168)) return fail(FN_EINVAL, "layer-0 projection group: K must be 1..168");
+    const int blocks = lin_layout(T, kLinRows, 1);
     T.K = 4 * KQ;
-    if (!live) return 0;
+    if (!T.n) return 0;
     if (mixed) hipLaunchKernelGGL(k_linear128_layer0, dim3(blocks), dim3(kLinThreads), lds, st, T);
     else hipLaunchKernelGGL((k_linear128_multi<KQ, false, false>), dim3(blocks), dim3(kLinThreads), lds, st, T);
     return launch_status("grouped projection GEMM (layer 0)");
@@ -1937,11 +1915,9 @@ static int prep_gat_bwd_dst(const float* g_out, const float* h, const float* p_s
 static int launch_gat_bwd_dst(const GatBwdDstArgs& A, int heads, hipStream_t st) {
     if (A.nblk == 0) return 0;
     const int kl = edge_class(&A.et);
-    FN_DISPATCH_H(heads, {
-        if (kl == 0) hipLaunchKernelGGL((k_gat_bwd_dst<HH, 0, kBwdRows>), dim3(A.nblk), dim3(kBwdRows * 32), 0, st, A);
-        else if (kl == 1) hipLaunchKernelGGL((k_gat_bwd_dst<HH, 1, kBwdRows>), dim3(A.nblk), dim3(kBwdRows * 32), 0, st, A);
-        else hipLaunchKernelGGL((k_gat_bwd_dst<HH, FN_MAX_EDGE_K, kBwdRows>), dim3(A.nblk), dim3(kBwdRows * 32), 0, st, A);
-    });
+    FN_DISPATCH_H(heads, with_edge_class(kl, [&](auto KL) {
+        hipLaunchKernelGGL((k_gat_bwd_dst<HH, FN_CV(KL), kBwdRows>), dim3(A.nblk), dim3(kBwdRows * 32), 0, st, A);
+    }));
     return launch_status("fn_gat_bwd_dst_f32");
 }
 

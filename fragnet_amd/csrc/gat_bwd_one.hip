@@ -72,23 +72,17 @@ int launch_gat_bwd_one(const GatBwdOneArgs& A, int heads, hipStream_t st) {
     if (A.nblk == 0) return 0;
     const int kl = edge_class(&A.et);
     if (heads == 4 && !A.dz_em && one_kind_en(A)) {      // the engine's launches (four heads)
-        if (kl == 0) hipLaunchKernelGGL((k_gat_bwd_one<4, 0, kBwdRows, false, true>), dim3(A.nblk), dim3(kBwdRows * 32), 0, st, A);
-        else if (kl == 1) hipLaunchKernelGGL((k_gat_bwd_one<4, 1, kBwdRows, false, true>), dim3(A.nblk), dim3(kBwdRows * 32), 0, st, A);
-        else hipLaunchKernelGGL((k_gat_bwd_one<4, FN_MAX_EDGE_K, kBwdRows, false, true>), dim3(A.nblk), dim3(kBwdRows * 32), 0, st, A);
+        with_edge_class(kl, [&](auto KL) { hipLaunchKernelGGL((k_gat_bwd_one<4, FN_CV(KL), kBwdRows, false, true>), dim3(A.nblk), dim3(kBwdRows * 32), 0, st, A); });
         return launch_status("fn_gat_bwd_one_f32");
     }
     if (A.dz_em) {            // the deferred form (DF): four heads
         if (heads != 4) return fail(FN_EUNSUPPORTED, "one-pass backward, deferred form: four heads");
-        if (kl == 0) hipLaunchKernelGGL((k_gat_bwd_one<4, 0, kBwdRows, true>), dim3(A.nblk), dim3(kBwdRows * 32), 0, st, A);
-        else if (kl == 1) hipLaunchKernelGGL((k_gat_bwd_one<4, 1, kBwdRows, true>), dim3(A.nblk), dim3(kBwdRows * 32), 0, st, A);
-        else hipLaunchKernelGGL((k_gat_bwd_one<4, FN_MAX_EDGE_K, kBwdRows, true>), dim3(A.nblk), dim3(kBwdRows * 32), 0, st, A);
+        with_edge_class(kl, [&](auto KL) { hipLaunchKernelGGL((k_gat_bwd_one<4, FN_CV(KL), kBwdRows, true>), dim3(A.nblk), dim3(kBwdRows * 32), 0, st, A); });
         return launch_status("fn_gat_bwd_one_f32 (deferred form)");
     }
-    FN_DISPATCH_H(heads, {
-        if (kl == 0) hipLaunchKernelGGL((k_gat_bwd_one<HH, 0, kBwdRows>), dim3(A.nblk), dim3(kBwdRows * 32), 0, st, A);
-        else if (kl == 1) hipLaunchKernelGGL((k_gat_bwd_one<HH, 1, kBwdRows>), dim3(A.nblk), dim3(kBwdRows * 32), 0, st, A);
-        else hipLaunchKernelGGL((k_gat_bwd_one<HH, FN_MAX_EDGE_K, kBwdRows>), dim3(A.nblk), dim3(kBwdRows * 32), 0, st, A);
-    });
+    FN_DISPATCH_H(heads, with_edge_class(kl, [&](auto KL) {
+        hipLaunchKernelGGL((k_gat_bwd_one<HH, FN_CV(KL), kBwdRows>), dim3(A.nblk), dim3(kBwdRows * 32), 0, st, A);
+    }));
     return launch_status("fn_gat_bwd_one_f32");
 }
 // bond (edge class 1) + atom (class 0) + fragment-bond (class FN_MAX_EDGE_K) levels as one launch; any of them may be absent

@@ -53,11 +53,6 @@ __global__ __launch_bounds__(kBlock, 4) void k_gat_fwd_rd_m(GatFwdArgs A, const 
 }  // namespace
 
 namespace fni {
-// what kind 4 takes for granted (fn_encoder_forward_masked checks the pass as a whole before its first launch; this is the per-launch guard)
-bool fwd_kind_mk(const GatFwdArgs& A, int heads) {
-    return heads == 4 && A.out2 == nullptr && A.p_edge_major == 0 && A.probs_orig == nullptr &&
-           (A.ep.y == nullptr || (A.ep.relu != 0 && !(A.ep.p > 0.f))) && (A.rd_out == nullptr || A.rd_J == heads);
-}
 int prep_gat_fwd(const float* h, const float* s_dst, const float* s_src, const float* att, int att_w,
                         const fn_edge_term* et, const fn_gat_plan* plan, float neg_slope, float* out, float* p_sorted,
                         float* probs_orig, const fn_act_epilogue* act, int heads, GatFwdArgs* A, float* out2,
@@ -91,82 +86,50 @@ int prep_gat_fwd(const float* h, const float* s_dst, const float* s_src, const f
     return 0;
 }
 
+// Which instance a launch takes: the kind from fwd_kind / fwd_kind_pair (fn_internal.h), the edge class(es) of the level(s), whether the
+// row dots ride in the epilogue.  Kernels exist for: kinds 2, 3, 4 -- four heads; row dots -- edge class 1; two levels -- classes (1, 1)
+// and (1, FN_MAX_EDGE_K).
 int launch_gat_fwd(const GatFwdArgs& A, int heads, hipStream_t st, const FwdMask* mk) {
     if (A.nblk == 0) return 0;
-    const int kl = edge_class(&A.et);
-    if (mk) {
-        if (!fwd_kind_mk(A, heads)) return fail(FN_EUNSUPPORTED, "attention forward: a masked level is a four-head evaluation level without second output");
-        if (A.rd_out) {
-            if (kl != 1) return fail(FN_EUNSUPPORTED, "attention forward: the row-dots epilogue exists for the single-attribute (bond graph) level");
-            hipLaunchKernelGGL((k_gat_fwd_rd_m<4>), dim3(A.nblk), dim3(kBlock), 0, st, A, mk->rows);
-        } else if (kl == 0) hipLaunchKernelGGL((k_gat_fwd_m<4, 0>), dim3(A.nblk), dim3(kBlock), 0, st, A, mk->rows);
-        else if (kl == 1) hipLaunchKernelGGL((k_gat_fwd_m<4, 1>), dim3(A.nblk), dim3(kBlock), 0, st, A, mk->rows);
-        else hipLaunchKernelGGL((k_gat_fwd_m<4, FN_MAX_EDGE_K>), dim3(A.nblk), dim3(kBlock), 0, st, A, mk->rows);
+    const int kl = edge_class(&A.et), kind = fwd_kind(A, heads, mk != nullptr);
+    if (kind == kFwdNoKind) return fail(FN_EUNSUPPORTED, "attention forward: a masked level is a four-head evaluation level without second output");
+    if (A.rd_out && kl != 1) return fail(FN_EUNSUPPORTED, "attention forward: the row-dots epilogue exists for the single-attribute (bond graph) level");
+    const dim3 grid(A.nblk), block(kBlock);
+    if (kind == 4) {
+        if (A.rd_out) hipLaunchKernelGGL((k_gat_fwd_rd_m<4>), grid, block, 0, st, A, mk->rows);
+        else with_edge_class(kl, [&](auto KL) { hipLaunchKernelGGL((k_gat_fwd_m<4, FN_CV(KL)>), grid, block, 0, st, A, mk->rows); });
         return launch_status("fn_gat_fwd_f32 (masked rows)");
     }
-    const bool o2 = A.out2 != nullptr;
     if (A.rd_out) {
-        if (kl != 1) return fail(FN_EUNSUPPORTED, "attention forward: the row-dots epilogue exists for the single-attribute (bond graph) level");
-        FN_DISPATCH_H(heads, {
-            if (o2) hipLaunchKernelGGL((k_gat_fwd_rd<HH, 1>), dim3(A.nblk), dim3(kBlock), 0, st, A);
-            else hipLaunchKernelGGL((k_gat_fwd_rd<HH>), dim3(A.nblk), dim3(kBlock), 0, st, A);
-        });
+        // k_gat_fwd_rd exists for the plain kinds 0 and 1 only (and as kind 4, above): a level that qualifies for kind 3 / 2 runs as 0 / 1 here
+        if (!with_const<1, 2, 4, 8>(heads, [&](auto H) { with_const<0, 1>(fwd_kind_plain(kind), [&](auto O2) {
+                hipLaunchKernelGGL((k_gat_fwd_rd<FN_CV(H), FN_CV(O2)>), grid, block, 0, st, A);
+            }); })) return bad_heads();
         return launch_status("fn_gat_fwd_f32 (+ row dots)");
     }
-#define FN_FWD1(KLV)                                                                                          \
-    do {                                                                                                      \
-        if constexpr (HH == 4) { if (o2 && tr) { hipLaunchKernelGGL((k_gat_fwd<HH, KLV, 2>), dim3(A.nblk), dim3(kBlock), 0, st, A);  break; } } \
-        if constexpr (HH == 4) { if (!o2 && ev) { hipLaunchKernelGGL((k_gat_fwd<HH, KLV, 3>), dim3(A.nblk), dim3(kBlock), 0, st, A);  break; } } \
-        if (o2) hipLaunchKernelGGL((k_gat_fwd<HH, KLV, 1>), dim3(A.nblk), dim3(kBlock), 0, st, A);            \
-        else hipLaunchKernelGGL((k_gat_fwd<HH, KLV>), dim3(A.nblk), dim3(kBlock), 0, st, A);                  \
-    } while (0)
-    const bool tr = fwd_kind_tr(A, heads), ev = fwd_kind_ev(A, heads);      // (four heads: the engine's launches take the kinds whose uniform flags are compile-time)
-    FN_DISPATCH_H(heads, {
-        if (kl == 0) FN_FWD1(0);
-        else if (kl == 1) FN_FWD1(1);
-        else FN_FWD1(FN_MAX_EDGE_K);
-    });
-#undef FN_FWD1
+    FN_TRY(with_heads_kind(heads, kind, [&](auto H, auto O2) {
+        with_edge_class(kl, [&](auto KL) { hipLaunchKernelGGL((k_gat_fwd<FN_CV(H), FN_CV(KL), FN_CV(O2)>), grid, block, 0, st, A); });
+    }));
     return launch_status("fn_gat_fwd_f32");
 }
-// two levels, one launch, when their edge classes are (1, FN_MAX_EDGE_K) or (1, 1); two launches otherwise
+// two levels, one launch, when their edge classes are (1, FN_MAX_EDGE_K) or (1, 1) and they have a kind in common; two launches otherwise
 int launch_gat_fwd_pair(const GatFwdArgs& A, const GatFwdArgs& B, int heads, hipStream_t st, const FwdMask* mka, const FwdMask* mkb) {
-    const int ka = edge_class(&A.et), kb = edge_class(&B.et);
-    if (A.nblk == 0 || B.nblk == 0 || ka != 1 || (kb != 1 && kb != FN_MAX_EDGE_K)) {
+    const int kb = edge_class(&B.et), kind = fwd_kind_pair(A, B, heads, mka, mkb), rd = A.rd_out != nullptr;
+    if (!fwd_pair_classes(A, B) || (kind == kFwdNoKind && !mka && !mkb)) {
         if (int rc = launch_gat_fwd(A, heads, st, mka)) return rc;
         return launch_gat_fwd(B, heads, st, mkb);
     }
-    if (mka || mkb) {
-        if (!mka || !mkb || !fwd_kind_mk(A, heads) || !fwd_kind_mk(B, heads))
-            return fail(FN_EUNSUPPORTED, "attention forward (two levels): masked levels are four-head evaluation levels without second output");
-        const dim3 grid(A.nblk + B.nblk);
-        if (A.rd_out) {
-            if (kb == 1) hipLaunchKernelGGL((k_gat_fwd_pair_m<4, 1, 1, true>), grid, dim3(kBlock), 0, st, A, B, mka->rows, mkb->rows);
-            else hipLaunchKernelGGL((k_gat_fwd_pair_m<4, 1, FN_MAX_EDGE_K, true>), grid, dim3(kBlock), 0, st, A, B, mka->rows, mkb->rows);
-        } else {
-            if (kb == 1) hipLaunchKernelGGL((k_gat_fwd_pair_m<4, 1, 1, false>), grid, dim3(kBlock), 0, st, A, B, mka->rows, mkb->rows);
-            else hipLaunchKernelGGL((k_gat_fwd_pair_m<4, 1, FN_MAX_EDGE_K, false>), grid, dim3(kBlock), 0, st, A, B, mka->rows, mkb->rows);
-        }
+    if (kind == kFwdNoKind) return fail(FN_EUNSUPPORTED, "attention forward (two levels): masked levels are four-head evaluation levels without second output");
+    const dim3 grid(A.nblk + B.nblk), block(kBlock);
+    if (kind == 4) {
+        with_const<1, FN_MAX_EDGE_K>(kb, [&](auto KB) { with_const<0, 1>(rd, [&](auto RD) {
+            hipLaunchKernelGGL((k_gat_fwd_pair_m<4, 1, FN_CV(KB), FN_CV(RD) != 0>), grid, block, 0, st, A, B, mka->rows, mkb->rows);
+        }); });
         return launch_status("attention forward (two levels, masked rows)");
     }
-    const bool o2 = A.out2 != nullptr;
-    if (o2 != (B.out2 != nullptr)) {
-        if (int rc = launch_gat_fwd(A, heads, st)) return rc;
-        return launch_gat_fwd(B, heads, st);
-    }
-#define FN_FWD2(KB, RD)                                                                                                            \
-    do {                                                                                                                           \
-        if constexpr (HH == 4) { if (o2 && tr) { hipLaunchKernelGGL((k_gat_fwd_pair<HH, 1, KB, RD, 2>), dim3(A.nblk + B.nblk), dim3(kBlock), 0, st, A, B);  break; } } \
-        if constexpr (HH == 4) { if (!o2 && ev) { hipLaunchKernelGGL((k_gat_fwd_pair<HH, 1, KB, RD, 3>), dim3(A.nblk + B.nblk), dim3(kBlock), 0, st, A, B);  break; } } \
-        if (o2) hipLaunchKernelGGL((k_gat_fwd_pair<HH, 1, KB, RD, 1>), dim3(A.nblk + B.nblk), dim3(kBlock), 0, st, A, B);          \
-        else hipLaunchKernelGGL((k_gat_fwd_pair<HH, 1, KB, RD>), dim3(A.nblk + B.nblk), dim3(kBlock), 0, st, A, B);                \
-    } while (0)
-    const bool tr = fwd_kind_tr(A, heads) && fwd_kind_tr(B, heads), ev = fwd_kind_ev(A, heads) && fwd_kind_ev(B, heads);
-    FN_DISPATCH_H(heads, {
-        if (A.rd_out) { if (kb == 1) FN_FWD2(1, true); else FN_FWD2(FN_MAX_EDGE_K, true); }
-        else { if (kb == 1) FN_FWD2(1, false); else FN_FWD2(FN_MAX_EDGE_K, false); }
-    });
-#undef FN_FWD2
+    FN_TRY(with_heads_kind(heads, kind, [&](auto H, auto O2) { with_const<1, FN_MAX_EDGE_K>(kb, [&](auto KB) { with_const<0, 1>(rd, [&](auto RD) {
+        hipLaunchKernelGGL((k_gat_fwd_pair<FN_CV(H), 1, FN_CV(KB), FN_CV(RD) != 0, FN_CV(O2)>), grid, block, 0, st, A, B);
+    }); }); }));
     return launch_status("attention forward (two levels)");
 }
 

@@ -70,18 +70,9 @@ static bool lin_side_prepare(LinTasks& T, int gat_blocks, int* gat_base, int* gr
     // one 64 x 64 tile per GEMM workgroup, all of them in front of the attention workgroups: the launch then takes what both
     // parts take back to back minus one kernel boundary (interleaving the two kinds, GEMM workgroups last, persistent GEMM
     // workgroups walking several tiles and raised wave priority all measured slower or equal: DESIGN.md section 4)
-    int blocks = 0, live = 0;
-    for (int i = 0; i < T.n; ++i) {
-        if (T.t[i].M <= 0) continue;
-        LinTask t = T.t[i];
-        t.first = blocks;
-        t.nblk = lin_blocks((t.M + kLinRows - 1) / kLinRows, 1);
-        blocks += t.nblk;
-        T.t[live++] = t;
-    }
-    T.n = live;
+    const int blocks = lin_layout(T, kLinRows, 1);
     T.K = FN_D;
-    if (!live) return false;
+    if (!T.n) return false;
     T.total = blocks;
     T.base = 0;
     *gat_base = blocks;
@@ -89,61 +80,42 @@ static bool lin_side_prepare(LinTasks& T, int gat_blocks, int* gat_base, int* gr
     return true;
 }
 
+// (a launch without a kind -- a masked level that is not kind 4, two levels without a common kind -- goes the plain way like every other
+// combination without a kernel: launch_gat_fwd / launch_gat_fwd_pair split it or refuse it)
 int launch_gat_fwd_lin(const GatFwdArgs& A, LinTasks& T, int heads, hipStream_t st, const FwdMask* mk) {
-    int gb = 0, grid = 0;
-    if (A.nblk == 0 || A.rd_out || edge_class(&A.et) != 0 || !lin_side_prepare(T, A.nblk, &gb, &grid)) {
+    int gb = 0, nwg = 0;
+    const int kind = fwd_kind(A, heads, mk != nullptr);
+    if (A.nblk == 0 || A.rd_out || edge_class(&A.et) != 0 || kind == kFwdNoKind || !lin_side_prepare(T, A.nblk, &gb, &nwg)) {
         if (int rc = launch_gat_fwd(A, heads, st, mk)) return rc;
         return T.n ? launch_linear128_group(T, st) : 0;
     }
-    if (mk) {
-        if (!fwd_kind_mk(A, heads)) return fail(FN_EUNSUPPORTED, "attention forward + projections: a masked level is a four-head evaluation level without second output");
-        hipLaunchKernelGGL((k_gat_fwd_lin_m<4, 0>), dim3(grid), dim3(kBlock), kLinSideLds, st, A, T, gb, mk->rows);
+    const dim3 grid(nwg), block(kBlock);
+    if (kind == 4) {
+        hipLaunchKernelGGL((k_gat_fwd_lin_m<4, 0>), grid, block, kLinSideLds, st, A, T, gb, mk->rows);
         return launch_status("attention forward (masked rows) + projections of the next level");
     }
-    const bool tr = fwd_kind_tr(A, heads), ev = fwd_kind_ev(A, heads);
-    FN_DISPATCH_H(heads, {
-        if constexpr (HH == 4) { if (A.out2 && tr) { hipLaunchKernelGGL((k_gat_fwd_lin<HH, 0, 2>), dim3(grid), dim3(kBlock), kLinSideLds, st, A, T, gb);  break; } }
-        if constexpr (HH == 4) { if (!A.out2 && ev) { hipLaunchKernelGGL((k_gat_fwd_lin<HH, 0, 3>), dim3(grid), dim3(kBlock), kLinSideLds, st, A, T, gb);  break; } }
-        if (A.out2) hipLaunchKernelGGL((k_gat_fwd_lin<HH, 0, 1>), dim3(grid), dim3(kBlock), kLinSideLds, st, A, T, gb);
-        else hipLaunchKernelGGL((k_gat_fwd_lin<HH, 0>), dim3(grid), dim3(kBlock), kLinSideLds, st, A, T, gb);
-    });
+    FN_TRY(with_heads_kind(heads, kind, [&](auto H, auto O2) {
+        hipLaunchKernelGGL((k_gat_fwd_lin<FN_CV(H), 0, FN_CV(O2)>), grid, block, kLinSideLds, st, A, T, gb);
+    }));
     return launch_status("attention forward + projections of the next level");
 }
 int launch_gat_fwd_pair_lin(const GatFwdArgs& A, const GatFwdArgs& B, LinTasks& T, int heads, hipStream_t st, const FwdMask* mka, const FwdMask* mkb) {
-    const int ka = edge_class(&A.et), kb = edge_class(&B.et);
     int gb = 0, nwg = 0;
-    const bool o2 = A.out2 != nullptr;
-    if (A.nblk == 0 || B.nblk == 0 || ka != 1 || (kb != 1 && kb != FN_MAX_EDGE_K) || o2 != (B.out2 != nullptr) ||
-        !lin_side_prepare(T, A.nblk + B.nblk, &gb, &nwg)) {
+    const int kb = edge_class(&B.et), kind = fwd_kind_pair(A, B, heads, mka, mkb), rd = A.rd_out != nullptr;
+    if (!fwd_pair_classes(A, B) || kind == kFwdNoKind || !lin_side_prepare(T, A.nblk + B.nblk, &gb, &nwg)) {
         if (int rc = launch_gat_fwd_pair(A, B, heads, st, mka, mkb)) return rc;
         return T.n ? launch_linear128_group(T, st) : 0;
     }
-    const dim3 grid(nwg);
-    if (mka || mkb) {
-        if (!mka || !mkb || !fwd_kind_mk(A, heads) || !fwd_kind_mk(B, heads))
-            return fail(FN_EUNSUPPORTED, "attention forward (two levels) + atom projection: masked levels are four-head evaluation levels without second output");
-        if (A.rd_out) {
-            if (kb == 1) hipLaunchKernelGGL((k_gat_fwd_pair_lin_m<4, 1, 1, true>), grid, dim3(kBlock), kLinSideLds, st, A, B, T, gb, mka->rows, mkb->rows);
-            else hipLaunchKernelGGL((k_gat_fwd_pair_lin_m<4, 1, FN_MAX_EDGE_K, true>), grid, dim3(kBlock), kLinSideLds, st, A, B, T, gb, mka->rows, mkb->rows);
-        } else {
-            if (kb == 1) hipLaunchKernelGGL((k_gat_fwd_pair_lin_m<4, 1, 1, false>), grid, dim3(kBlock), kLinSideLds, st, A, B, T, gb, mka->rows, mkb->rows);
-            else hipLaunchKernelGGL((k_gat_fwd_pair_lin_m<4, 1, FN_MAX_EDGE_K, false>), grid, dim3(kBlock), kLinSideLds, st, A, B, T, gb, mka->rows, mkb->rows);
-        }
+    const dim3 grid(nwg), block(kBlock);
+    if (kind == 4) {
+        with_const<1, FN_MAX_EDGE_K>(kb, [&](auto KB) { with_const<0, 1>(rd, [&](auto RD) {
+            hipLaunchKernelGGL((k_gat_fwd_pair_lin_m<4, 1, FN_CV(KB), FN_CV(RD) != 0>), grid, block, kLinSideLds, st, A, B, T, gb, mka->rows, mkb->rows);
+        }); });
         return launch_status("attention forward (two levels, masked rows) + atom projection");
     }
-#define FN_PAIR_LIN(KB, RD)                                                                                                  \
-    do {                                                                                                                     \
-        if constexpr (HH == 4) { if (o2 && tr) { hipLaunchKernelGGL((k_gat_fwd_pair_lin<HH, 1, KB, RD, 2>), grid, dim3(kBlock), kLinSideLds, st, A, B, T, gb);  break; } } \
-        if constexpr (HH == 4) { if (!o2 && ev) { hipLaunchKernelGGL((k_gat_fwd_pair_lin<HH, 1, KB, RD, 3>), grid, dim3(kBlock), kLinSideLds, st, A, B, T, gb);  break; } } \
-        if (o2) hipLaunchKernelGGL((k_gat_fwd_pair_lin<HH, 1, KB, RD, 1>), grid, dim3(kBlock), kLinSideLds, st, A, B, T, gb);   \
-        else hipLaunchKernelGGL((k_gat_fwd_pair_lin<HH, 1, KB, RD>), grid, dim3(kBlock), kLinSideLds, st, A, B, T, gb);      \
-    } while (0)
-    const bool tr = fwd_kind_tr(A, heads) && fwd_kind_tr(B, heads), ev = fwd_kind_ev(A, heads) && fwd_kind_ev(B, heads);
-    FN_DISPATCH_H(heads, {
-        if (A.rd_out) { if (kb == 1) FN_PAIR_LIN(1, true); else FN_PAIR_LIN(FN_MAX_EDGE_K, true); }
-        else { if (kb == 1) FN_PAIR_LIN(1, false); else FN_PAIR_LIN(FN_MAX_EDGE_K, false); }
-    });
-#undef FN_PAIR_LIN
+    FN_TRY(with_heads_kind(heads, kind, [&](auto H, auto O2) { with_const<1, FN_MAX_EDGE_K>(kb, [&](auto KB) { with_const<0, 1>(rd, [&](auto RD) {
+        hipLaunchKernelGGL((k_gat_fwd_pair_lin<FN_CV(H), 1, FN_CV(KB), FN_CV(RD) != 0, FN_CV(O2)>), grid, block, kLinSideLds, st, A, B, T, gb);
+    }); }); }));
     return launch_status("attention forward (two levels) + atom projection");
 }
 }  // namespace fni

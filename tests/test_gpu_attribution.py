@@ -74,20 +74,29 @@ def _replica_batches(store, max_rows):
     return out
 
 
-def test_masked_encoder_outputs_match_the_oracle_with_scalar_masks():
+_ORACLE_OUTPUTS = {}          # (molecule, kind, index) -> the oracle's four encoder outputs: computed once, shared by the cases below
+
+
+@pytest.mark.parametrize("fuse_rowdots,colaunch", [(1, 2), (1, 0), (0, 2), (0, 0)], ids=["default", "no-colaunch", "no-fused-rowdots", "neither"])
+def test_masked_encoder_outputs_match_the_oracle_with_scalar_masks(fuse_rowdots, colaunch):
     """Test 1 of the issue: every replica's four encoder outputs against the oracle on that molecule alone with that scalar mask
     on every layer; the masked element's own rows are exactly 0.0.  Condition on the inputs (oracle values), taken on the two
     outputs a finetune head pools (out_atoms, out_frags): every atom and bond replica moves one of them by >= 10 x tolerance;
     every fragment-bond replica too, except exact no-ops -- both outputs identical to the unmasked ones: the only connection of
     a two-fragment molecule is each fragment's single in-edge, and a softmax over one edge is 1 whatever its term -- at most 1 in
     10 of them.  Measured: minimum over atoms 1040 x, bonds 65 x, fragment bonds 13 x tolerance; 1 of 22 fragment-bond replicas is
-    a no-op (its own out_fbond rows still go to zero, which the comparison above checks)."""
-    from fragnet_amd import data
+    a no-op (its own out_fbond rows still go to zero, which the comparison above checks).
+    The cases: the masked pass on the default launches (the two bond levels with the atom projection riding, the row dots in the bond
+    level's epilogue, the atom level with the next layer's projections riding) and on the plain launchers it falls back to --
+    FN_TUNE_GEMM_COLAUNCH (14) = 0: the masked two-level launch and the masked atom level without riders; FN_TUNE_FUSE_ROWDOTS (7) = 0:
+    the bond level without the epilogue and the separate row-dots launch behind a masked level.  Same batch, same tolerances; and the
+    same bytes as the default launches: that equality was seen to hold on the commit before these cases existed, for all three."""
+    from fragnet_amd import _lib, data
     from fragnet_amd.plan import SPACES
     torch.set_num_threads(8)
     gold, net = _pair(scaled=False)
     mols = ac.molecules()
-    ref_cache = {}
+    ref_cache = _ORACLE_OUTPUTS
 
     def oracle(i, kind, index):
         key = (i, kind, index)
@@ -107,9 +116,22 @@ def test_masked_encoder_outputs_match_the_oracle_with_scalar_masks():
     assert 2 <= len(batches) <= 3
     moved = {"atom": [], "bond": [], "fbond": []}
     seen = 0
+
+    def encoder(batch, key7, key14):
+        try:
+            _lib.call("fn_set_tuning", 7, key7)
+            _lib.call("fn_set_tuning", 14, key14)
+            with torch.no_grad():
+                return [t.cpu().numpy() for t in net.pretrain(batch, edge_outputs=True)]
+        finally:
+            _lib.call("fn_set_tuning", 7, 1)
+            _lib.call("fn_set_tuning", 14, 2)
+
     for batch, reps in batches:
-        with torch.no_grad():
-            outs = [t.cpu().numpy() for t in net.pretrain(batch, edge_outputs=True)]
+        outs = encoder(batch, fuse_rowdots, colaunch)
+        if (fuse_rowdots, colaunch) != (1, 2):
+            for name, o, d in zip(("out_atoms", "out_frags", "out_bond", "out_fbond"), outs, encoder(batch, 1, 2)):
+                assert np.array_equal(o, d), f"{name} differs from the default launches' bytes"
         off = batch.offsets.cpu().numpy()
         rows = [off[SPACES.index(s)] for s in ("atom", "frag", "edge", "fedge")]
         for r, (i, kind, index) in enumerate(reps):
