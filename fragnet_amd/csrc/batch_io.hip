@@ -11,12 +11,7 @@ using fni::fail;
 using fni::launch_status;
 using fni::tune;
 
-__global__ void k_zero2_i32(int32_t* __restrict__ a, int64_t na, int32_t* __restrict__ b, int64_t nb) {
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < na + nb; i += (int64_t)gridDim.x * blockDim.x) {
-        if (i < na) a[i] = 0;
-        else b[i - na] = 0;
-    }
-}
+#include "zero2.inc"
 
 // =====================================================================================
 // Graph plan

@@ -1,5 +1,5 @@
 // Dense layers of the prediction heads on the fp32 matrix cores, with the element-wise work around them fused in
-// (included into the anonymous namespace of fragnet_hip.hip after mol_fused.inc, whose address-space helpers it uses).
+// (included into the anonymous namespace of head.hip behind head_act.inc; the address-space helpers it uses: fn_internal.h).
 //
 // Reference: FTHead1-5 (model/gat/gat2.py:569-751) are stacks of  act(dropout(Linear(x)))  on [molecules, width] with
 // molecules ~ 512 and widths 128 ... 1024: ~1 GFLOP per product, operands that fit the L2.  At that size the fp32 MFMA
@@ -61,7 +61,6 @@ __device__ __forceinline__ float2 ld2(const glb_f* p) {
     return make_float2(v.x, v.y);
 }
 __device__ __forceinline__ void st2s(lds_f* p, float a, float b) { *reinterpret_cast<FN_LDS f32x2*>(p) = (f32x2){a, b}; }
-#define DN_MFMA(ACC, AV, BV) ACC = __builtin_amdgcn_mfma_f32_16x16x4f32(AV, BV, ACC, 0, 0, 0)
 
 // NC = 16-column groups of a forward / input-gradient tile: 4 (32 x 64) or 2 (32 x 32, for products with too few tiles to
 // occupy the chip; the input-gradient's W pieces are then 8-byte loads of columns 2n, 2n+1)

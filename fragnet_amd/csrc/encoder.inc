@@ -415,7 +415,7 @@ int bwd_src_and_edge_term(const float* g_out, const float* h, const float* pz_sr
         hipLaunchKernelGGL(k_row_dots_sorted_bwd, dim3(T.nblk), dim3(kBlock), 0, st, T);
         return launch_status("edge-term backward");
     }
-    FN_DISPATCH_H(heads, hipLaunchKernelGGL((k_gat_bwd_src_rd<HH, kBwdRows>), dim3(A.nblk + T.nblk), dim3(kBlock), 0, st, A, T));
+    FN_TRY(with_heads(heads, [&](auto H) { hipLaunchKernelGGL((k_gat_bwd_src_rd<FN_CV(H), kBwdRows>), dim3(A.nblk + T.nblk), dim3(kBlock), 0, st, A, T); }));
     return launch_status("source pass + edge-term backward");
 }
 

@@ -168,6 +168,13 @@ FNI_HIDDEN bool bad_edge_term(const fn_edge_term* et, int64_t m);
 namespace {
 inline hipStream_t S(fn_stream_t s) { return reinterpret_cast<hipStream_t>(s); }
 #define FN_TRY(expr) do { int rc_ = (expr); if (rc_) return rc_; } while (0)
+// a launch with more than 64 KB of dynamic LDS has to be allowed per kernel first
+template <typename Kern> inline int allow_lds(Kern kern, size_t bytes) {
+    if (bytes <= 64 * 1024) return 0;
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+    if (e != hipSuccess) { (void)hipGetLastError(); return fni::fail((int)e, "hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed"); }
+    return 0;
+}
 // ---- which KIND of the attention forward (the O2 template argument of its kernels) a launch takes.  The comment above gat_fwd_rows
 // (gat_fwd.inc) is the one description of what each kind takes for granted; it calls the kind 2 / kind 3 conditions below
 // fwd_kind_tr() / fwd_kind_ev().  masked: the launch comes with a FwdMask; such a launch is kind 4 or does not exist (kFwdNoKind).
@@ -210,14 +217,8 @@ template <class F> inline int with_heads_kind(int heads, int kind, F&& f) {
                               : with_const<1, 2, 4, 8>(heads, [&](auto h) { with_const<0, 1>(kind, [&](auto k) { f(h, k); }); });
     return ok ? 0 : bad_heads();
 }
-#define FN_DISPATCH_H(heads, CALL)                         \
-    switch (heads) {                                       \
-        case 1: { constexpr int HH = 1; CALL; } break;     \
-        case 2: { constexpr int HH = 2; CALL; } break;     \
-        case 4: { constexpr int HH = 4; CALL; } break;     \
-        case 8: { constexpr int HH = 8; CALL; } break;     \
-        default: return bad_heads();                       \
-    }
+// the head count of every other launch: f(H)
+template <class F> inline int with_heads(int heads, F&& f) { return with_const<1, 2, 4, 8>(heads, f) ? 0 : bad_heads(); }
 constexpr int kBlock = 256;
 constexpr int kRows = 8;          // rows (half-waves) per block
 constexpr int kGridCap = 2048;    // memory-bound kernels: ~8 blocks per CU, grid-stride the rest
@@ -406,6 +407,7 @@ __device__ __forceinline__ void st1_off(float* base, uint32_t byte_off, float v)
 // flat_load / flat_store, which tick BOTH wait counters and so serialise with the LDS traffic.  Hot accesses cast to the global
 // (G()) or LDS address space.
 typedef float f32x4 __attribute__((ext_vector_type(4)));       // MFMA accumulator / 16-byte vector
+#define DN_MFMA(ACC, AV, BV) ACC = __builtin_amdgcn_mfma_f32_16x16x4f32(AV, BV, ACC, 0, 0, 0)      // dense_head.inc, wgrad128.inc
 #define FN_LDS __attribute__((address_space(3)))
 #define FN_GLB __attribute__((address_space(1)))
 typedef FN_LDS float lds_f;

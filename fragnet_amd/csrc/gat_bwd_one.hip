@@ -80,9 +80,9 @@ int launch_gat_bwd_one(const GatBwdOneArgs& A, int heads, hipStream_t st) {
         with_edge_class(kl, [&](auto KL) { hipLaunchKernelGGL((k_gat_bwd_one<4, FN_CV(KL), kBwdRows, true>), dim3(A.nblk), dim3(kBwdRows * 32), 0, st, A); });
         return launch_status("fn_gat_bwd_one_f32 (deferred form)");
     }
-    FN_DISPATCH_H(heads, with_edge_class(kl, [&](auto KL) {
-        hipLaunchKernelGGL((k_gat_bwd_one<HH, FN_CV(KL), kBwdRows>), dim3(A.nblk), dim3(kBwdRows * 32), 0, st, A);
-    }));
+    FN_TRY(with_heads(heads, [&](auto H) { with_edge_class(kl, [&](auto KL) {
+        hipLaunchKernelGGL((k_gat_bwd_one<FN_CV(H), FN_CV(KL), kBwdRows>), dim3(A.nblk), dim3(kBwdRows * 32), 0, st, A);
+    }); }));
     return launch_status("fn_gat_bwd_one_f32");
 }
 // bond (edge class 1) + atom (class 0) + fragment-bond (class FN_MAX_EDGE_K) levels as one launch; any of them may be absent
@@ -113,7 +113,9 @@ int launch_gat_bwd_one3(const GatBwdOneArgs& A, const GatBwdOneArgs& B, const Ga
         hipLaunchKernelGGL((k_gat_bwd_one3<4, kBwdRows, false, false, true>), dim3(A.nblk + B.nblk + C.nblk), dim3(kBwdRows * 32), 0, st, A, B, C, interleave);
         return launch_status("attention backward, one pass (bond + atom + fragment-bond levels)");
     }
-    FN_DISPATCH_H(heads, hipLaunchKernelGGL((k_gat_bwd_one3<HH, kBwdRows>), dim3(A.nblk + B.nblk + C.nblk), dim3(kBwdRows * 32), 0, st, A, B, C, interleave));
+    FN_TRY(with_heads(heads, [&](auto H) {
+        hipLaunchKernelGGL((k_gat_bwd_one3<FN_CV(H), kBwdRows>), dim3(A.nblk + B.nblk + C.nblk), dim3(kBwdRows * 32), 0, st, A, B, C, interleave);
+    }));
     return launch_status("attention backward, one pass (bond + atom + fragment-bond levels)");
 }
 int launch_gat_cu(CuTasks& T, int heads, hipStream_t st) {
@@ -130,7 +132,7 @@ int launch_gat_cu(CuTasks& T, int heads, hipStream_t st) {
     }
     T.n = live;
     if (!live) return 0;
-    FN_DISPATCH_H(heads, hipLaunchKernelGGL(k_gat_cu<HH>, dim3(blocks), dim3(kBlock), 0, st, T));
+    FN_TRY(with_heads(heads, [&](auto H) { hipLaunchKernelGGL(k_gat_cu<FN_CV(H)>, dim3(blocks), dim3(kBlock), 0, st, T); }));
     return launch_status("fn_gat_cu_f32");
 }
 

@@ -1,6 +1,6 @@
 // The activations of the prediction heads other than the ReLU fast path (include/fragnet_hip.h, fn_head_act), as epilogues of
 // the dense-head products (dense_head.inc) and of the last Linear's kernels (k_small_linear_bwd, k_small_linear_loss).  Included
-// into the anonymous namespace of fragnet_hip.hip.
+// into the anonymous namespace of head.hip.
 //
 // Reference: gat2.py:693-705 builds the head's activation from the finetune `act` key; torch's modules define f and f':
 //   silu   u sigma(u)                              sigma(u) (1 + u (1 - sigma(u)))

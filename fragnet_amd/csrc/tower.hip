@@ -307,12 +307,6 @@ __global__ __launch_bounds__(256) void k_tower_reduce(const TowerTasks T) {
     }
 }
 
-int set_lds(const void* kern, size_t bytes) {
-    hipError_t e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-    if (e != hipSuccess) { (void)hipGetLastError();  return fni::fail((int)e, "hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed"); }
-    return 0;
-}
-
 int check_towers(const fn_tower* tw, int n, bool bwd, const char* who) {
     if (!tw || n < 1 || n > FN_MAX_TOWERS) return fni::fail(FN_EINVAL, who);
     for (int i = 0; i < n; ++i) {
@@ -349,7 +343,7 @@ int fn_tower_fwd_f32(const fn_tower* towers, int n, fn_stream_t stream) {
     }
     if (!T.n) return 0;
     static bool once = false;
-    if (!once) { if (int rc = set_lds(reinterpret_cast<const void*>(k_tower_fwd), kFwdLds * sizeof(float))) return rc;  once = true; }
+    if (!once) { if (int rc = allow_lds(k_tower_fwd, kFwdLds * sizeof(float))) return rc;  once = true; }
     hipLaunchKernelGGL(k_tower_fwd, dim3(grid), dim3(256), kFwdLds * sizeof(float), reinterpret_cast<hipStream_t>(stream), T);
     return fni::launch_status("fn_tower_fwd_f32");
 }
@@ -375,7 +369,7 @@ int fn_tower_bwd_f32(const fn_tower* towers, int n, float* ws, fn_stream_t strea
         grid += T.nblk[T.n++];
     }
     static bool once = false;
-    if (!once) { if (int rc = set_lds(reinterpret_cast<const void*>(k_tower_bwd), kBwdLds * sizeof(float))) return rc;  once = true; }
+    if (!once) { if (int rc = allow_lds(k_tower_bwd, kBwdLds * sizeof(float))) return rc;  once = true; }
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     hipLaunchKernelGGL(k_tower_bwd, dim3(grid), dim3(512), kBwdLds * sizeof(float), st, T);
     if (int rc = fni::launch_status("fn_tower_bwd_f32")) return rc;

@@ -58,12 +58,27 @@ def test_head_act_kernels_match_float64(kind, order, p, M):
     """One hidden layer through fn_dense_fwd_act_f32 (M = 2048 runs the workgroup-shared-tile forward), then the layer above's
     backward through fn_dense_bwd_act_f32 / fn_small_linear_bwd_act_f32 / fn_small_linear_loss_act_f32 with it as `below`:
     outputs, the saved argument, g_x through the activation, dW, db, zero padding rows, and the PReLU slope's gradient."""
+    _check_head_act_kernels(kind, order, p, M, 3)
+
+
+@gpu
+@pytest.mark.parametrize("Cc", [1, 3, 5])
+@pytest.mark.parametrize("p", [0.0, 0.25])
+@pytest.mark.parametrize("order", [0, 1], ids=["act_of_dropout", "dropout_of_act"])
+@pytest.mark.parametrize("kind", ["silu", "prelu"])
+def test_head_act_last_linear_class_widths(kind, order, p, Cc):
+    """The same checks with 1, 3 and 5 outputs of the last Linear: the three class widths (1, 4, FN_SMALL_LINEAR_MAX) of
+    k_small_linear_bwd / k_small_linear_loss with an activation below (the test above runs three outputs, the middle width, only)."""
+    _check_head_act_kernels(kind, order, p, 37, Cc)
+
+
+def _check_head_act_kernels(kind, order, p, M, Cc):
     from fragnet_amd import _lib
     from fragnet_amd.plan import _stream_ptr
     dev = _dev()
     st = _stream_ptr(dev)
     lib = _lib.load()
-    K, N, N2, Cc = 256, (1024 if M == 2048 else 128), 64, 3
+    K, N, N2 = 256, (1024 if M == 2048 else 128), 64
     torch.manual_seed(M * 31 + KINDS.index(kind) * 7 + order + int(p * 4))
     x, w, b = torch.randn(M, K, device=dev), torch.randn(N, K, device=dev) / K ** 0.5, torch.randn(N, device=dev) * 0.5
     slope = torch.tensor([SLOPE], device=dev)
