@@ -614,7 +614,7 @@ __global__ void k_segment_softmax_bwd(const float* __restrict__ probs, const flo
 }
 
 // =====================================================================================
-// dropout + ReLU epilogue (Philox-4x32-10)
+// dropout + ReLU epilogue (Philox-4x32, seven rounds: philox4x32 in fn_internal.h)
 // =====================================================================================
 template <bool BWD>
 __device__ __forceinline__ void dropout_act_body(const float* __restrict__ a, const float* __restrict__ y_saved, float* __restrict__ o,

@@ -16,6 +16,7 @@ ATOL = 1e-4
 KINDS = ["relu", "silu", "gelu", "celu", "selu", "relu6", "leakyrelu", "prelu"]
 ACTS = ["silu", "gelu", "celu", "selu", "relu6", "leakyrelu", "prelu"]
 SLOPE = 0.23
+_KEEP_CHECKED = []
 
 
 def _dev():
@@ -46,6 +47,12 @@ def _keep(shape, p, seed, offset, dev):
     ones, k = torch.ones(shape, device=dev), torch.empty(shape, device=dev)
     if ones.numel():
         _lib.call("fn_dropout_act_f32", ones.data_ptr(), k.data_ptr(), ones.numel(), float(p), seed, offset, None, 0, _stream_ptr(dev))
+        if p > 0.0 and not _KEEP_CHECKED:
+            # once per session: the kernel's mask IS the documented stream (tests/philox_ref.py), not just what every kernel agrees on
+            from tests import philox_ref
+            want = torch.from_numpy(philox_ref.mask(ones.numel(), p, seed, offset)).view(k.shape)
+            assert torch.equal(k.cpu() != 0, want)
+            _KEEP_CHECKED.append(True)
     return k.double()
 
 
