@@ -1,7 +1,10 @@
 // Internal declarations shared by the translation units of libfragnet_hip.so (not part of the C-ABI: nothing here is exported).
 //  * device helpers every kernel file uses (vector loads, DPP reductions inside a head's lanes, Philox);
 //  * the per-molecule extents table (MolExt) the molecule-resident kernels are driven by;
-//  * host-side hooks into the error string / tuning table that live in fragnet_hip.hip.
+//  * host-side hooks (namespace fni): the error string and the tuning table, which live in fragnet_hip.hip, and the launchers one unit
+//    offers the others.  A hook's signature is made of C-ABI and fni:: types only: a type of a unit's unnamed namespace has no linkage
+//    to carry across units (the kernel argument blocks that stay unnamed -- GatBwdDstArgs, RowDotsBwdArgs, .. -- therefore travel as
+//    plain arguments, or the code that fills them is in an .inc both units include).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -31,8 +34,12 @@ struct MolExt {
 };
 static_assert(sizeof(MolExt) == 64, "MolExt is sixteen int32 (include/fragnet_hip.h documents it as int32 [n_mols][16])");
 
-// ---- argument blocks and host-side entry points shared by the translation units (the forward attention family lives in
-// gat_fwd.hip / gat_fwd_lin.hip, everything else in fragnet_hip.hip)
+// ---- argument blocks and host-side entry points shared by the translation units, grouped by the unit that defines them: the forward
+// attention family in gat_fwd.hip / gat_fwd_lin.hip, the one-pass attention backward in gat_bwd_one.hip, the operator surface (and the
+// grouped projection launches) in fragnet_hip.hip.  The engine, encoder.hip, offers nothing here: it is the caller of all of them, and
+// besides these hooks it calls the C-ABI's own single-operator entry points where a level or variant runs them one by one
+// (fn_gat_bwd_dst_f32, fn_gat_fwd_f32, fn_node_scalars_f32, fn_row_dots_sorted_f32, fn_dropout_act_f32, fn_linear128_f32,
+// fn_segment_sum_f32).
 struct GatFwdArgs {
     const float *h, *s_dst, *s_src, *att;
     int att_w;
@@ -161,7 +168,15 @@ FNI_HIDDEN int launch_gat_bwd_one3(const GatBwdOneArgs& A, const GatBwdOneArgs& 
 FNI_HIDDEN int launch_gat_cu(CuTasks& T, int heads, hipStream_t st);
 FNI_HIDDEN int launch_gsd_seg(const GsdSegTasks& T, int blocks, hipStream_t st);
 // fragnet_hip.hip
-FNI_HIDDEN int launch_linear128_group(LinTasks& T, hipStream_t st);
+FNI_HIDDEN int launch_linear128_group(LinTasks& T, hipStream_t st);           // up to three K = 128 products (k_linear128_multi / _multi_ra)
+FNI_HIDDEN int launch_linear128_small_group(LinTasks& T, hipStream_t st);     // layer 0's raw-feature projections, each task with its own K <= 168
+// fn_linear128_f32 with the node scalars of the attention level it feeds as its epilogue (ns.att == null: fn_linear128_f32 itself)
+FNI_HIDDEN int launch_linear128_ns(const float* X, int K, const float* Bt, const float* bias, float* Y, int64_t M, const fn_act_epilogue* act_bwd,
+                                   NodeScalarEpi ns, fn_stream_t stream);
+// out[i, :] = table[index[i], :] (+ addend[i, :], which may alias out), rows of w4 float4 (k_gather_rows4); where: the launch's name in fn_last_error()
+FNI_HIDDEN int launch_gather_rows4(const float* table, const int64_t* index, float* out, int64_t rows, int64_t w4, const float* addend, hipStream_t st,
+                                   const char* where);
+FNI_HIDDEN int prof_event(int i, hipStream_t st);                             // records event i of fn_debug_set_profile_events, if set
 FNI_HIDDEN bool bad_edge_term(const fn_edge_term* et, int64_t m);
 }  // namespace fni
 

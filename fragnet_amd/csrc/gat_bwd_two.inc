@@ -1,6 +1,9 @@
 // gat_bwd_two.inc -- the general TWO-PASS backward of an attention level (destination pass + source pass; rounds 1-3) and the
-// by-source attention read-out (k_attn_by_src): device code, included inside the anonymous namespace of fragnet_hip.hip behind
-// gat_fwd.inc.  The engine's default since round 4 is the one-pass backward (gat_bwd_one.inc); these kernels serve head counts and
+// by-source attention read-out (k_attn_by_src): device code and the host-side argument preparation, included inside the anonymous
+// namespace of fragnet_hip.hip (the destination pass, k_attn_by_src) and of encoder.hip (the source pass, the finalize and the combined
+// launches that run the same bodies)
+// behind gat_fwd.inc.  Templates and inline functions only: a __global__ function that is no template would be compiled into both
+// units (k_gat_finalize, the stand-alone launch of gat_finalize_body, is in encoder.hip for that reason, beside k_reduce_tasks).  The engine's default since round 4 is the one-pass backward (gat_bwd_one.inc); these kernels serve head counts and
 // hand-built graphs the one-pass kernel does not take, the fragment graph inside the tail (mol_tail.inc shares their row cores) and
 // the operator path's fallback (fn_gat_bwd_dst_f32 / fn_gat_bwd_src_f32).
 
@@ -395,7 +398,7 @@ __device__ __forceinline__ float block_sum_1024(float v, float* s16) {
 
 // blocks 0..255: one column each of the column-major [256][FN_MAX_PART] a_dst/a_src partials; block 256 (mode 2
 // only): the [n_e, H*(K+1)] edge-embedding partials and the chain rule through the folded weights.
-// (body shared by k_gat_finalize and the deferred task-table kernel k_reduce_tasks; vb = virtual block index,
+// (body shared by k_gat_finalize and the deferred task-table kernel k_reduce_tasks, both in encoder.hip; vb = virtual block index,
 // sm = 1200 floats of shared memory)
 __device__ __forceinline__ void gat_finalize_body(int vb, float* sm, const float* __restrict__ part_a, int n_a,
                                                   const float* __restrict__ part_e, int n_e, const fn_edge_term& et,
@@ -469,15 +472,6 @@ __device__ __forceinline__ void gat_finalize_body(int vb, float* sm, const float
     }
 }
 
-__global__ __launch_bounds__(1024) void k_gat_finalize(const float* __restrict__ part_a, int n_a,
-                                                       const float* __restrict__ part_e, int n_e, fn_edge_term et,
-                                                       const float* __restrict__ att, int att_w, int dst_off,
-                                                       int src_off, float* __restrict__ g_att,
-                                                       float* __restrict__ g_embW, float* __restrict__ g_embb, int H) {
-    __shared__ float sm[1200];
-    gat_finalize_body(blockIdx.x, sm, part_a, n_a, part_e, n_e, et, att, att_w, dst_off, src_off, g_att, g_embW, g_embb, H);
-}
-
 template <int H>
 __global__ void k_attn_by_src(const float* __restrict__ p_sorted, fn_gat_plan pl, float* __restrict__ attn) {
     const int64_t total = pl.n * H;
@@ -491,3 +485,57 @@ __global__ void k_attn_by_src(const float* __restrict__ p_sorted, fn_gat_plan pl
     }
 }
 
+// ---- host side: argument validation + launch geometry of the two passes (shared by the single-level C-ABI entry points in
+// fragnet_hip.hip and the engine's combined launches in encoder.hip, which carry these argument blocks inside launches of their own:
+// k_tail_bwd, k_gat_bwd_src_rd); nblk == 0 means "nothing to do"
+inline int prep_gat_bwd_dst(const float* g_out, const float* h, const float* p_sorted, const fn_edge_term* et,
+                            const fn_gat_plan* plan, float neg_slope, float* dz_sorted, float* g_s_orig, float* pz_src,
+                            float* g_s_dst, float* part_e, int* n_part_e, int heads, GatBwdDstArgs* A) {
+    if (!g_out || !h || !plan || !g_s_dst || !n_part_e || !et) return fni::fail(FN_EINVAL, "fn_gat_bwd_dst_f32: bad argument");
+    if (et->mode != 0 && fni::bad_edge_term(et, plan ? plan->m : 1)) return fni::fail(FN_EINVAL, "fn_gat_bwd_dst_f32: bad edge term");
+    if (plan->m > 0 && (!p_sorted || !pz_src || !plan->spos_d || (et->mode == 0 && !dz_sorted && !g_s_orig)))
+        return fni::fail(FN_EINVAL, "fn_gat_bwd_dst_f32: null edge buffer");
+    if (et->mode == 2 && !part_e) return fni::fail(FN_EINVAL, "fn_gat_bwd_dst_f32: null part_e");
+    if (heads != 1 && heads != 2 && heads != 4 && heads != 8) return fni::fail(FN_EUNSUPPORTED, "heads must be 1, 2, 4 or 8 (128 = heads * head_dim)");
+    *n_part_e = 0;
+    *A = GatBwdDstArgs{g_out, h, p_sorted, *et, *plan, neg_slope, dz_sorted, g_s_orig, pz_src, g_s_dst, part_e, 1, 0};
+    if (plan->n == 0) return 0;
+    if (plan->n > (1 << 23) || plan->m * heads > (1 << 29))
+        return fni::fail(FN_EUNSUPPORTED, "fn_gat_bwd_dst_f32: level too large for 32-bit byte offsets (n <= 2^23 rows, m*heads <= 2^29)");
+    // R rows per half-wave; one edge-parameter partial row per block, hence at most FN_MAX_PART blocks.
+    // Unlike the forward kernel this one wants R SMALL: its (p, dz) stores are scattered 8-byte writes into source
+    // order, vmcnt counts loads and stores in one in-order queue, so every extra row per wave waits behind the
+    // previous row's slow stores (B=2048: R=4 56 us, R=8 84 us; B=512: 16 us at any R)
+    const int64_t groups = (plan->n + kBwdRows - 1) / kBwdRows;
+    // rows per half-wave: ~groups / 1536 (three at ESOL batch 512: 0.926 -> 0.902 ms per step against one row each), but at most
+    // three -- the (p, dz) stores into source order are scattered and every further row waits behind them (B = 2048: 56 us at
+    // four rows, 84 us at eight) -- unless the level is so large that the partial rows would not fit FN_MAX_PART
+    const int64_t resident = fni::tune(FN_TUNE_DST_BLOCKS) > 0 && fni::tune(FN_TUNE_DST_BLOCKS) < FN_MAX_PART ? fni::tune(FN_TUNE_DST_BLOCKS) : FN_MAX_PART;
+    const int64_t need = (groups + FN_MAX_PART - 1) / FN_MAX_PART, want = (groups + resident - 1) / resident;
+    A->rows_per_hw = (int)std::max<int64_t>(need, std::min<int64_t>(want, 3));
+    A->nblk = (int)((plan->n + (int64_t)kBwdRows * A->rows_per_hw - 1) / ((int64_t)kBwdRows * A->rows_per_hw));
+    *n_part_e = (et->mode == 2) ? A->nblk : 0;
+    return 0;
+}
+
+inline int prep_gat_bwd_src(const float* g_out, const float* h, const float* pz_src, const float* g_s_dst, const float* att,
+                            int att_w, int dst_off, int src_off, const fn_gat_plan* plan, float* g_h, float* part_a,
+                            int* n_part_a, int heads, GatBwdSrcArgs* A) {
+    if (!g_out || !h || !g_s_dst || !att || !plan || !g_h || !part_a || !n_part_a) return fni::fail(FN_EINVAL, "fn_gat_bwd_src_f32: bad argument");
+    if (plan->m > 0 && !pz_src) return fni::fail(FN_EINVAL, "fn_gat_bwd_src_f32: null edge buffer");
+    if ((att_w | dst_off | src_off) & 3) return fni::fail(FN_EINVAL, "fn_gat_bwd_src_f32: att blocks must be 16-byte aligned");
+    if (heads != 1 && heads != 2 && heads != 4 && heads != 8) return fni::fail(FN_EUNSUPPORTED, "heads must be 1, 2, 4 or 8 (128 = heads * head_dim)");
+    *n_part_a = 0;
+    *A = GatBwdSrcArgs{g_out, h, pz_src, g_s_dst, att, att_w, dst_off, src_off, *plan, g_h, part_a, 1, 0};
+    if (plan->n == 0) return 0;
+    if (plan->n > (1 << 23) || plan->m * heads > (1 << 28))
+        return fni::fail(FN_EUNSUPPORTED, "fn_gat_bwd_src_f32: level too large for 32-bit byte offsets (n <= 2^23 rows, m*heads <= 2^28)");
+    // every block writes 256 partial sums column-major (scattered): at most 1024 blocks, each half-wave pipelining R rows
+    const int64_t groups = (plan->n + kBwdRows - 1) / kBwdRows;
+    int64_t resident = (int64_t)fni::tune(FN_TUNE_SRC_BLOCKS);
+    if (resident > 1024 || resident < 1) resident = 1024;
+    A->rows_per_hw = (int)((groups + resident - 1) / resident);
+    A->nblk = (int)((plan->n + (int64_t)kBwdRows * A->rows_per_hw - 1) / ((int64_t)kBwdRows * A->rows_per_hw));
+    *n_part_a = A->nblk;
+    return 0;
+}

@@ -1,5 +1,6 @@
-// gat_fwd.inc -- device code of the attention forward (included, inside the anonymous namespace, by gat_fwd.hip, gat_fwd_lin.hip and --
-// for the molecule-resident fragment tail, which runs the row core on its own rows -- fragnet_hip.hip).  GatFwdArgs: fn_internal.h.
+// gat_fwd.inc -- device code of the attention forward (included, inside the anonymous namespace, by gat_fwd.hip, gat_fwd_lin.hip, by
+// encoder.hip -- for the molecule-resident fragment tail, which runs the row core on its own rows -- and by fragnet_hip.hip, for
+// k_node_scalars and the helpers gat_bwd_two.inc shares).  Templates only.  GatFwdArgs: fn_internal.h.
 // folded edge-embedding weights: Wf[h][k] = sum_c att[h, mid+c] * embW[c,k],  Wf[h][K] = sum_c att[h, mid+c] * embb[c]
 __device__ __forceinline__ void fold_edge_embed(const fn_edge_term& et, const float* att, int att_w, int H,
                                                 float (*sWf)[kWfLd]) {

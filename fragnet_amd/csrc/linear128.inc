@@ -1,5 +1,6 @@
 // linear128.inc -- the fp32-MFMA [M,K] x [K,128] tile body and its fused epilogues (included, inside the anonymous namespace, by
-// fragnet_hip.hip and by gat_fwd_lin.hip, whose launches carry projection tiles beside an attention pass).  Argument blocks: fn_internal.h.
+// fragnet_hip.hip -- the projection launches --, by encoder.hip -- k_lin_rd_cu, the input-gradient products beside the edge term's backward --
+// and by gat_fwd_lin.hip, whose launches carry projection tiles beside an attention pass).  Templates only.  Argument blocks: fn_internal.h.
 // =====================================================================================
 // Projection GEMMs on the fp32 matrix cores (v_mfma_f32_16x16x4_f32: exact fp32 FMA chains, so the 1e-4
 // parity budget is untouched).  All three node projections have N = 128 outputs and K <= 168 inputs:

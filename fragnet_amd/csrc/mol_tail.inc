@@ -1,4 +1,5 @@
-// Molecule-resident fragment tail of the encoder (included by fragnet_hip.hip, inside its anonymous namespace).
+// Molecule-resident fragment tail of the encoder (included by encoder.hip, inside its anonymous namespace, behind gat_fwd.inc,
+// gat_bwd_two.inc and the row-dots backward, whose row cores its global-memory path runs).
 //
 // The last layer's fragment levels are tiny per molecule (ESOL: 3.6 fragments, 6 fragment-graph edges, 26 atoms) and ran as a
 // chain of small launches that each cost their latency floor (~5 us however little they do):
