@@ -135,6 +135,10 @@ class RowMasks(C.Structure):
     _fields_ = [("atoms", vp), ("bonds", vp), ("fbonds", vp)]
 
 
+class AttnReadout(C.Structure):
+    _fields_ = [("atoms", vp), ("frags", vp), ("bonds", vp), ("fbonds", vp)]
+
+
 STATUS_BAD_REPLICA = 8      # FN_STATUS_BAD_REPLICA
 
 
@@ -178,6 +182,7 @@ SIGNATURES = {
     "fn_encoder_rng_blocks": [C.POINTER(Encoder)],
     "fn_encoder_forward": [C.POINTER(Encoder), vp, vp, vp, vp, vp],
     "fn_encoder_forward_masked": [C.POINTER(Encoder), C.POINTER(RowMasks), vp, vp, vp, vp, vp],
+    "fn_encoder_forward_attn": [C.POINTER(Encoder), C.POINTER(AttnReadout), vp, vp, vp, vp, vp],
     "fn_loo_row_masks_u8": [vp, i64, vp, vp, vp, vp, i64, vp, i64, vp, i64, vp, vp],
     "fn_encoder_backward": [C.POINTER(Encoder), vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(LayerWeights), vp, i64, vp],
     "fn_segment_sum_f32": [vp, i64, vp, vp, i32, vp, i64, i64, i64, vp],

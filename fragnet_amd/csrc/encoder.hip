@@ -1763,8 +1763,8 @@ int encoder_backward_one(const fn_encoder* e, const EncLayout& lay, const BwdLay
 }  // namespace
 
 // forward declaration: the pass behind fn_encoder_forward and fn_encoder_forward_masked (defined with them, below)
-static int encoder_forward_impl(const fn_encoder* e, const fn_row_masks* masks, float* out_atoms, float* out_frags, float* out_bond,
-                                float* out_fbond, fn_stream_t st);
+static int encoder_forward_impl(const fn_encoder* e, const fn_row_masks* masks, const fn_attn_readout* readout, float* out_atoms,
+                                float* out_frags, float* out_bond, float* out_fbond, fn_stream_t st);
 
 extern "C" {
 
@@ -1776,19 +1776,29 @@ uint64_t fn_encoder_rng_blocks(const fn_encoder* e) { return e ? rng_plan(e).tot
 
 int fn_encoder_forward(const fn_encoder* e, float* out_atoms, float* out_frags, float* out_bond, float* out_fbond,
                        fn_stream_t st) {
-    return encoder_forward_impl(e, nullptr, out_atoms, out_frags, out_bond, out_fbond, st);
+    return encoder_forward_impl(e, nullptr, nullptr, out_atoms, out_frags, out_bond, out_fbond, st);
 }
 
 int fn_encoder_forward_masked(const fn_encoder* e, const fn_row_masks* m, float* out_atoms, float* out_frags, float* out_bond,
                               float* out_fbond, fn_stream_t st) {
-    if (!m || (!m->atoms && !m->bonds && !m->fbonds)) return encoder_forward_impl(e, nullptr, out_atoms, out_frags, out_bond, out_fbond, st);
+    if (!m || (!m->atoms && !m->bonds && !m->fbonds)) return encoder_forward_impl(e, nullptr, nullptr, out_atoms, out_frags, out_bond, out_fbond, st);
     // everything a masked pass can be refused for is decided here, before the first launch
     FN_TRY(enc_check(e));
     if (e->variant != 0) return fail(FN_EUNSUPPORTED, "fn_encoder_forward_masked: row masks exist for variant 0 (gat2); gat2_lite / gat2_edge have no masks in the reference");
     if (e->training != 0) return fail(FN_EINVAL, "fn_encoder_forward_masked: a masked pass is an evaluation pass (training must be 0)");
     if (e->no_backward == 0) return fail(FN_EINVAL, "fn_encoder_forward_masked: a masked pass has no backward (no_backward must be 1)");
     if (e->heads != 4) return fail(FN_EUNSUPPORTED, "fn_encoder_forward_masked: the masked attention instances are built for four heads");
-    return encoder_forward_impl(e, m, out_atoms, out_frags, out_bond, out_fbond, st);
+    return encoder_forward_impl(e, m, nullptr, out_atoms, out_frags, out_bond, out_fbond, st);
+}
+
+int fn_encoder_forward_attn(const fn_encoder* e, const fn_attn_readout* r, float* out_atoms, float* out_frags, float* out_bond,
+                            float* out_fbond, fn_stream_t st) {
+    if (!r || (!r->atoms && !r->frags && !r->bonds && !r->fbonds)) return encoder_forward_impl(e, nullptr, nullptr, out_atoms, out_frags, out_bond, out_fbond, st);
+    // everything a read-out pass can be refused for is decided here, before the first launch
+    FN_TRY(enc_check(e));
+    if (e->variant != 0) return fail(FN_EUNSUPPORTED, "fn_encoder_forward_attn: the attention read-out exists for variant 0 (gat2); the reference's gat2_lite / gat2_edge Viz classes cannot run");
+    if (e->training != 0) return fail(FN_EINVAL, "fn_encoder_forward_attn: a read-out pass is an evaluation pass (training must be 0)");
+    return encoder_forward_impl(e, nullptr, r, out_atoms, out_frags, out_bond, out_fbond, st);
 }
 
 }  // extern "C" (reopened behind the pass itself)
@@ -1796,8 +1806,10 @@ int fn_encoder_forward_masked(const fn_encoder* e, const fn_row_masks* m, float*
 // masks == null: the plain pass.  Else the caller has checked that the descriptor is one a masked pass exists for, and every attention
 // level of the three masked index spaces launches forward kind 4 (gat_fwd.inc) with its byte array (null inside: no masked row there).
 // The fragment graph has no mask (gat2.py has none), and everything behind the three levels reads stored rows.
-static int encoder_forward_impl(const fn_encoder* e, const fn_row_masks* masks, float* out_atoms, float* out_frags, float* out_bond,
-                                float* out_fbond, fn_stream_t st) {
+// readout != null (never together with masks; the caller has checked variant 0 and an evaluation pass): the last layer's levels store
+// their probabilities whatever no_backward says, and ONE more launch behind the last level sums them by source (attn_readout.hip).
+static int encoder_forward_impl(const fn_encoder* e, const fn_row_masks* masks, const fn_attn_readout* readout, float* out_atoms,
+                                float* out_frags, float* out_bond, float* out_fbond, fn_stream_t st) {
     FN_TRY(enc_check(e));
     if (!out_atoms || !out_frags) return fail(FN_EINVAL, "fn_encoder_forward: null output");
     if ((out_bond == nullptr) != (out_fbond == nullptr)) return fail(FN_EINVAL, "fn_encoder_forward: out_bond and out_fbond are wanted together or not at all");
@@ -1969,7 +1981,10 @@ static int encoder_forward_impl(const fn_encoder* e, const fn_row_masks* masks, 
         if (!no_fb) FN_TRY(prep_gat_fwd(a.h_fb, lay.s_dst_fb, lay.s_src_fb, w.f_a_b, 3 * d, &et_fb, &e->fbond, 0.2f, (last || !ep_fbond.y) ? a.new_fbond : nullptr,
                                         a.p_fbond, nullptr, &ep_fbond, H, &gfb, a.o2_fbond, a.sg_fbond));
         gb.p_edge_major = gfb.p_edge_major = one ? 1 : 0;
-        if (no_bwd) gb.p_sorted = gfb.p_sorted = nullptr;
+        // (a read-out pass keeps the last layer's: the slots exist in every workspace; same kernel instances, one more store per edge)
+        const bool keep_p = readout && last;
+        if (no_bwd && !(keep_p && readout->bonds)) gb.p_sorted = nullptr;
+        if (no_bwd && !(keep_p && readout->fbonds)) gfb.p_sorted = nullptr;
         if (drop_edge_out) gb.ep.y = gfb.ep.y = nullptr;
         gb.n_real = nr_bonds;  gfb.n_real = nr_conns;
         // (evaluation passes only, like FN_TUNE_FWD_BLOCKS_EVAL_LARGE: a training pass gets fewer, longer-lived half-waves from prep_gat_fwd
@@ -2009,7 +2024,7 @@ static int encoder_forward_impl(const fn_encoder* e, const fn_row_masks* masks, 
             FN_TRY(prep_gat_fwd(a.h_a, lay.s_dst_a, lay.s_src_a, w.a, wide, &et_a, &e->atom, 0.2f, ep_atoms.y ? nullptr : lay.atoms_new, a.p_atom, nullptr, &ep_atoms, H, &ga,
                                 a.o2_atom, a.sg_atom));
             ga.p_edge_major = one ? 1 : 0;
-            if (no_bwd) ga.p_sorted = nullptr;
+            if (no_bwd && !(keep_p && readout->atoms)) ga.p_sorted = nullptr;
             ga.n_real = nr_atoms;
             FN_TRY(launch_gat_fwd_lin(ga, T, H, S(st), pm_atoms));
         } else {
@@ -2017,7 +2032,7 @@ static int encoder_forward_impl(const fn_encoder* e, const fn_row_masks* masks, 
             FN_TRY(prep_gat_fwd(a.h_a, lay.s_dst_a, lay.s_src_a, w.a, wide, &et_a, &e->atom, 0.2f, (last || !ep_atoms.y) ? lay.atoms_new : nullptr, a.p_atom, nullptr, &ep_atoms,
                                 H, &ga, a.o2_atom, a.sg_atom));
             ga.p_edge_major = one ? 1 : 0;
-            if (no_bwd) ga.p_sorted = nullptr;
+            if (no_bwd && !(keep_p && readout->atoms)) ga.p_sorted = nullptr;
             ga.n_real = nr_atoms;
             FN_TRY(launch_gat_fwd(ga, H, S(st), pm_atoms));
         }
@@ -2060,6 +2075,12 @@ static int encoder_forward_impl(const fn_encoder* e, const fn_row_masks* masks, 
         }
         in_atoms = y_atoms;  in_bond = y_bond;  in_fbond = y_fbond;
         ka = kb = kfb = FN_D;
+    }
+    if (readout) {      // the fragment level stores its probabilities on all three tail paths, under no_backward too (a.p_frag above)
+        const LayerActs& a = lay.L[e->n_layers - 1];
+        const fni::AttnReadoutTask tasks[4] = {{e->bond, a.p_bond, readout->bonds, nr_bonds}, {e->fbond, a.p_fbond, readout->fbonds, nr_conns},
+                                               {e->atom, a.p_atom, readout->atoms, nr_atoms}, {e->frag, a.p_frag, readout->frags, rr ? rr + 2 : nullptr}};
+        FN_TRY(fni::launch_attn_readout(tasks, 4, H, S(st)));
     }
     return 0;
 }

@@ -176,6 +176,16 @@ FNI_HIDDEN int launch_linear128_ns(const float* X, int K, const float* Bt, const
 // out[i, :] = table[index[i], :] (+ addend[i, :], which may alias out), rows of w4 float4 (k_gather_rows4); where: the launch's name in fn_last_error()
 FNI_HIDDEN int launch_gather_rows4(const float* table, const int64_t* index, float* out, int64_t rows, int64_t w4, const float* addend, hipStream_t st,
                                    const char* where);
+// attn_readout.hip: the by-source sums of stored probabilities (p: signed, head-major [H][m]) of up to four levels in ONE launch --
+// out[s][h] = sum over the items of source s, in by-source order, of |p[h][.]|.  A task without `out` is skipped, a level without
+// items zero-fills its rows; n_real: nullable device word, sources at or behind it are padding (0)
+struct AttnReadoutTask {
+    fn_gat_plan pl;
+    const float* p;
+    float* out;               // [pl.n][heads]
+    const int32_t* n_real;
+};
+FNI_HIDDEN int launch_attn_readout(const AttnReadoutTask* tasks, int n_tasks, int heads, hipStream_t st);
 FNI_HIDDEN int prof_event(int i, hipStream_t st);                             // records event i of fn_debug_set_profile_events, if set
 FNI_HIDDEN bool bad_edge_term(const fn_edge_term* et, int64_t m);
 }  // namespace fni

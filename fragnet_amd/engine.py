@@ -230,10 +230,55 @@ def _masked_forward(plan, x_atoms, bond_nodes, fbond_nodes, cos_sorted, fattr_so
     return tuple(outs) + (pooled,)
 
 
+_KEEP_ATTN_WS = None      # tests: a list that collects (descriptor, workspace) of every read-out pass (the stored probabilities live there)
+
+
+def _attn_forward(plan, x_atoms, bond_nodes, fbond_nodes, cos_sorted, fattr_sorted, params, n_layers, heads, variant, edge_outputs):
+    """fn_encoder_forward_attn: an evaluation pass nobody differentiates (no autograd node) that also returns the last layer's four
+    by-source attention sums, each [n, heads] for every node of its level."""
+    x_atoms, bond_nodes, fbond_nodes = _f32(x_atoms, "x_atoms"), _f32(bond_nodes, "node_features_bonds"), _f32(fbond_nodes, "node_features_fbonds")
+    params = tuple(_f32(p.detach(), "parameter") for p in params)
+    dev = x_atoms.device
+    lib = _lib.load()
+    e = _describe(plan, x_atoms, bond_nodes, fbond_nodes, cos_sorted, fattr_sorted, params, n_layers, heads, 0.0, False, 0, 0, None, variant,
+                  not _EVAL_SAVES)
+    # a batch without fragment connections (EF == 0: one-fragment molecules stripped of their placeholder row) has empty fragment-bond
+    # tensors, whose data_ptr() is null; the descriptor wants a pointer for every input, read or not: a stand-in that no launch reads
+    # (a level of no rows launches nothing)
+    stand_in = None
+    if e.EF == 0 or plan.levels["fbond"].m == 0:
+        stand_in = torch.zeros(max(e.k_fbond0, e.k_fattr, FN_D), dtype=torch.float32, device=dev)
+        e.fbond_nodes = e.fbond_nodes or stand_in.data_ptr()
+        e.fattr_sorted = e.fattr_sorted or stand_in.data_ptr()
+    ws = torch.empty(lib.fn_encoder_ws_floats(C.byref(e)), dtype=torch.float32, device=dev)
+    e.ws, e.ws_floats = ws.data_ptr(), ws.numel()
+    outs = [torch.empty((n if (edge_outputs or k < 2) else 0, FN_D), dtype=torch.float32, device=dev) for k, n in enumerate((e.N, e.F, e.E, e.EF))]
+    attn = [torch.empty((n, heads), dtype=torch.float32, device=dev) for n in (e.N, e.F, e.E, e.EF)]      # atoms, frags, bonds, fbonds
+    r = _lib.AttnReadout(*(t.data_ptr() for t in attn))
+    pooled = torch.empty(0, dtype=torch.float32, device=dev)
+    if lib.fn_encoder_fused_tail(C.byref(e)):
+        pooled = torch.empty((e.n_mols, 2 * FN_D), dtype=torch.float32, device=dev)
+        e.pooled = pooled.data_ptr()
+    # (out_bond and out_fbond are wanted together: an output of no rows gets the stand-in's pointer too)
+    ptrs = [(o.data_ptr() or (stand_in.data_ptr() if stand_in is not None else None)) if (edge_outputs or k < 2) else None for k, o in enumerate(outs)]
+    _lib.check(lib.fn_encoder_forward_attn(C.byref(e), C.byref(r), *ptrs, _stream_ptr(dev)), "fn_encoder_forward_attn")
+    plan.pending.pop("bond", None)
+    plan.pending.pop("frag" if variant == 2 else "fbond", None)
+    if _KEEP_ATTN_WS is not None:
+        _KEEP_ATTN_WS.append((e, ws))
+    return tuple(outs) + (pooled,) + tuple(attn)
+
+
 def encoder_forward(layers, plan: GraphPlan, x_atoms, bond_nodes, fbond_nodes, cos_sorted, fattr_sorted, heads: int,
-                    drop_p: float, training: bool, rng, variant: int = 0, edge_outputs: bool = True, row_masks=None) -> tuple:
+                    drop_p: float, training: bool, rng, variant: int = 0, edge_outputs: bool = True, row_masks=None,
+                    attn_readout: bool = False) -> tuple:
     """Runs all ``layers`` (FragNetLayerA modules) + the inter-layer act(dropout(.)); returns the four outputs and, fifth,
     the readout [n_mols, 256] when the fused fragment tail produced it (an empty tensor otherwise).
+
+    ``attn_readout=True``: four more tensors follow -- the last layer's by-source attention sums of the atom, fragment, bond and
+    fragment-bond levels (the reference's ``summed_attn_weights_*``), each [n, heads] with a row for EVERY node of its level
+    (fn_encoder_forward_attn).  Like a masked pass it is an evaluation pass without a backward: in training mode, or with a gradient
+    required anywhere, it raises; it exists for model_version gat2 and not together with row masks.
 
     ``row_masks``: None, or a triple (atoms [N], bonds [E], fragment bonds [EF]) of uint8 CUDA tensors or None -- 1 = that row of
     the level's output is zero for every reader, in every layer (fn_encoder_forward_masked).  A masked pass is an evaluation pass
@@ -250,6 +295,16 @@ def encoder_forward(layers, plan: GraphPlan, x_atoms, bond_nodes, fbond_nodes, c
                                f"layer 0 {name} expects {w.shape[-1]} input features, the batch has {x.shape[-1]}")
     if row_masks is not None and len(row_masks) != 3:
         raise ValueError("row_masks: a triple (atoms, bonds, fragment bonds)")
+    if attn_readout:
+        if row_masks is not None and any(t is not None for t in row_masks):
+            raise ValueError("attn_readout: there is no attention read-out of a masked pass (row_masks)")
+        if int(variant) != 0:
+            raise ValueError("attn_readout: the attention read-out exists for model_version gat2 (the reference's lite / edge Viz classes cannot run)")
+        if training:
+            raise RuntimeError("attn_readout: a read-out pass is an evaluation pass (the model is in training mode)")
+        if torch.is_grad_enabled() and any(t.requires_grad for t in (x_atoms, bond_nodes, fbond_nodes, *params)):
+            raise RuntimeError("attn_readout: the read-out pass has no backward; run it under torch.no_grad()")
+        return _attn_forward(plan, x_atoms, bond_nodes, fbond_nodes, cos_sorted, fattr_sorted, params, len(layers), heads, 0, bool(edge_outputs))
     if row_masks is not None and any(t is not None for t in row_masks):
         if training:
             raise RuntimeError("row_masks: a masked pass is an evaluation pass (the model is in training mode)")

@@ -815,6 +815,24 @@ typedef struct fn_row_masks {
 } fn_row_masks;
 int fn_encoder_forward_masked(const fn_encoder* e, const fn_row_masks* m, float* out_atoms, float* out_frags, float* out_bond,
                               float* out_fbond, fn_stream_t stream);
+/* Attention read-out of an evaluation pass: the LAST layer's summed_attn_weights_atoms / _frags / _bonds / _fbonds of the reference,
+ * scatter_add(attn_probs, source) at gat2.py:219, 312, 165, 268 -- what fragnet/vizualize/model.py returns and viz.py draws.  Each
+ * pointer is nullable (that level's sums are not wanted); a tensor has one row per node of its level, [n, heads] floats, and rows
+ * without out-edges are 0 (the reference's scatter_add without dim_size stops at source.max() + 1: its tensor is a prefix of this one).
+ * The pass is fn_encoder_forward's, launch for launch, except that the last layer's bond, fragment-bond, atom and fragment levels store
+ * their probabilities under no_backward too (same kernels: one more store per edge; the outputs are the plain pass's bits), plus ONE
+ * launch behind the last level (csrc/attn_readout.hip): attn[s][h] = sum_k |p[h m + dpos_s[beg_s + k]]| in ascending by-source position
+ * = ascending original edge id (the atom level's self loops last), the reference's sequential order -- reproducible bit for bit and
+ * equal to fn_attn_by_src_f32 on the same probabilities.  A level without edges reads nothing and zero-fills its tensor in that launch.
+ * r == NULL or four NULL pointers: fn_encoder_forward itself, bit for bit.  Otherwise the pass needs variant == 0 (FN_EUNSUPPORTED:
+ * the reference's gat2_lite / gat2_edge Viz classes cannot run) and training == 0 (FN_EINVAL): refused before anything is launched.
+ * Both values of no_backward and every head count fn_encoder_forward evaluates are accepted.  There is no read-out of a masked pass
+ * (fn_encoder_forward_masked takes none).  Inner layers store and sum nothing: the reference returns the last layer's only.  ABI 12. */
+typedef struct fn_attn_readout {
+    float *atoms /*[N,H]*/, *frags /*[F,H]*/, *bonds /*[E,H]*/, *fbonds /*[EF,H]*/;
+} fn_attn_readout;
+int fn_encoder_forward_attn(const fn_encoder* e, const fn_attn_readout* r, float* out_atoms, float* out_frags, float* out_bond,
+                            float* out_fbond, fn_stream_t stream);
 /* The three masks of a batch of leave-one-out replicas, zero-filled and set in ONE launch.  replicas: int32 [n_mols][2] = (kind, local
  * index) of molecule i of the batch; kind 0 masks nothing, 1 the atom `index`, 2 the bond `index` (directed rows 2 index, 2 index + 1),
  * 3 the fragment connection `index` (rows 2 index, 2 index + 1), all local to the molecule.  *_off: int32 [n_mols + 1], first row of
