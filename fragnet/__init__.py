@@ -11,8 +11,11 @@
     fragnet.dataset.dataset           load_pickle_dataset, load_data_parts (finetune_gat2.py:2, pretrain_gat2.py:6)
     fragnet.train.utils               EarlyStopping, TrainerFineTune     (finetune_gat2.py:4,9)
     fragnet.train.pretrain.pretrain_utils   Trainer                      (pretrain_gat2.py:13)
+    fragnet.model.cdrp.model          CDRPModel, MLP                     (finetune_cdrp.py:18)
+    fragnet.dataset.data              collate_fn_cdrp                    (finetune_cdrp.py:6)
+    fragnet.train.finetune.trainer_cdrp     TrainerFineTune              (finetune_cdrp.py:9)
     fragnet.vizualize.model           FragNetViz, FragNetFineTuneViz, FragNetFineTuneBaseViz, FragNetPreTrainViz (vizualize/viz.py)
 
-Model versions outside the accelerated hot path (masked pretraining heads, gcn / gat v1, DTA, CDRP; SURVEY.md section 2 rows
+Model versions outside the accelerated hot path (masked pretraining heads, gcn / gat v1, DTA; SURVEY.md section 2 rows
 10-19) are named here only to fail with a clear message when constructed.
 """

@@ -221,6 +221,11 @@ SIGNATURES = {
     "fn_small_linear_loss_act_f32": [vp, vp, vp, vp, vp, C.c_int, vp, vp, vp, C.POINTER(HeadAct), vp, i64, i64, i64, i64, vp],
     "fn_head_act_parts": [C.c_int, i64, i64],
     "fn_head_act_param_grad_f32": [vp, i64, vp, vp],
+    "fn_cdrp_gene_fwd_f32": [vp, vp, vp, vp, i64, i64, i64, vp],
+    "fn_cdrp_gene_bwd_f32": [vp, vp, vp, vp, vp, i64, i64, i64, vp],
+    "fn_cdrp_pair_loss_ws": [i64],
+    "fn_cdrp_pair_fwd_f32": [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, i64, i64, i64, i64, vp],
+    "fn_cdrp_pair_bwd_f32": [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, vp, i64, i64, i64, i64, i64, vp],
 }
 
 _lib = None

@@ -122,3 +122,16 @@ def batch_to(batch: Dict[str, torch.Tensor], device) -> Dict[str, torch.Tensor]:
         out["edge_index_fbonds"] = eifb
         out["edge_attr_fbonds"] = out["node_features_fbonds"][eifb[0]] + out["node_features_fbonds"][eifb[1]]
     return out
+
+
+def collate_fn_cdrp(data_list: List) -> Dict[str, torch.Tensor]:
+    """Cancer-drug-response batch dict (17 keys) -- reference data.py:1112-1187: the finetune batch plus ``gene_expr`` [B, gene_dim],
+    each record's ``gene_expr.view(1, -1)`` stacked and cast with ``.type(torch.long)`` exactly as the reference does (truncation toward
+    zero; the model casts it back with ``.float()``, and the tower's first kernel reads the int64 rows directly)."""
+    out = _collate_common(data_list)
+    out["y"] = torch.cat([d.y for d in data_list], dim=0).type(torch.float)
+    out["gene_expr"] = torch.cat([d.gene_expr.view(1, -1) for d in data_list], dim=0).type(torch.long)
+    return out
+
+
+BATCH_KEYS_CDRP = BATCH_KEYS_FT + ("gene_expr",)

@@ -1046,3 +1046,215 @@ def bond_graph(edge_index: torch.Tensor, atom_batch: torch.Tensor, n_mols: int, 
     out = torch.empty((2, n), dtype=torch.int64, device=dev)
     _lib.call("fn_bond_graph_fill", edge_index.data_ptr(), atom_batch.data_ptr(), E, N, n_mols, mode, ws.data_ptr(), out.data_ptr(), n, st)
     return out
+
+
+# ======================================================================================
+# cancer drug response model (reference model/cdrp/model.py): the cell-line tower MLP(gene_dim) and the pair head, csrc/cdrp.hip
+# ======================================================================================
+PAIR_HEAD_SHAPES = ((128, 512), (1, 128))        # fc1, fc2: the widths fn_cdrp_pair_*_f32 is built for
+
+
+def _i64c(t: torch.Tensor, name: str) -> torch.Tensor:
+    if not t.is_cuda:
+        raise _lib.FragnetHipError(f"{name}: fragnet_amd kernels need GPU tensors (got {t.device}); there is no CPU fallback")
+    if t.dtype != torch.int64:
+        raise TypeError(f"{name}: expected int64 (collate_fn_cdrp's gene_expr), got {t.dtype}")
+    return t if t.is_contiguous() else t.contiguous()
+
+
+def _gene_shapes(gene, W, b):
+    if gene.dim() != 2 or W.dim() != 2 or W.shape[1] != gene.shape[1] or b.shape != (W.shape[0],):
+        raise ValueError(f"gene_linear: gene_expr {tuple(gene.shape)} does not match weight {tuple(W.shape)} / bias {tuple(b.shape)}")
+
+
+class _GeneLinear(torch.autograd.Function):
+    """relu(gene_expr.float() @ W.T + b) on the int64 rows of ``collate_fn_cdrp`` (MLP.forward's first layer): one launch each way, any
+    ``gene_dim`` (no multiple-of-4 rule: fn_cdrp_gene_fwd_f32 / fn_cdrp_gene_bwd_f32).  No gradient for ``gene_expr``: it is data."""
+
+    @staticmethod
+    def forward(ctx, gene, W, b):
+        gene, W, b = _i64c(gene, "gene_expr"), _f32c(W, "weight"), _f32c(b, "bias")
+        _gene_shapes(gene, W, b)
+        M, K = gene.shape
+        y = torch.empty((M, W.shape[0]), dtype=torch.float32, device=gene.device)
+        _lib.call("fn_cdrp_gene_fwd_f32", gene.data_ptr(), W.data_ptr(), b.data_ptr(), y.data_ptr(), M, K, W.shape[0], _stream_ptr(gene.device))
+        ctx.params, ctx.slots = (W, b), (grad_slot(W), grad_slot(b))
+        ctx.save_for_backward(gene, y)
+        return y
+
+    @staticmethod
+    def backward(ctx, g):
+        gene, y = ctx.saved_tensors
+        g = _f32c(g, "g")
+        (W, b), slots = ctx.params, ctx.slots
+        dW, db = grad_buffer(W, slots[0]), grad_buffer(b, slots[1])
+        _lib.call("fn_cdrp_gene_bwd_f32", g.data_ptr(), y.data_ptr(), gene.data_ptr(), dW.data_ptr(), db.data_ptr(), gene.shape[0], gene.shape[1],
+                  W.shape[0], _stream_ptr(g.device))
+        return None, dW, db
+
+
+def gene_linear(gene_expr, weight, bias):
+    return _GeneLinear.apply(gene_expr, weight, bias)
+
+
+class _CellTower(torch.autograd.Function):
+    """MLP(gene_dim) (model/cdrp/model.py:7-22: Linear gene_dim -> 1024 -> 256 -> 64 -> 256, a ReLU after EVERY Linear, no dropout) as one
+    autograd node: the first layer on the int64 rows (fn_cdrp_gene_fwd_f32), the others fn_dense_fwd_f32 with the ReLU epilogue (p = 0);
+    backward top-down with fn_dense_bwd_f32 (gate_scale = 1: each launch hands the layer below its gradient already through that
+    layer's ReLU) and fn_cdrp_gene_bwd_f32.  The incoming gradient goes through the last ReLU first -- unless the pair head's backward
+    produced it, which has done that already (``_fn_relu_gated``)."""
+
+    @staticmethod
+    def forward(ctx, gene, *params):
+        gene = _i64c(gene, "gene_expr")
+        params = tuple(_f32c(q, "tower parameter") for q in params)
+        _gene_shapes(gene, params[0], params[1])
+        M, K = gene.shape
+        dev, st = gene.device, _stream_ptr(gene.device)
+        h = torch.empty((M, params[0].shape[0]), dtype=torch.float32, device=dev)
+        _lib.call("fn_cdrp_gene_fwd_f32", gene.data_ptr(), params[0].data_ptr(), params[1].data_ptr(), h.data_ptr(), M, K, h.shape[1], st)
+        acts = [h]
+        for i in range(1, len(params) // 2):
+            W, b = params[2 * i], params[2 * i + 1]
+            y = torch.empty((M, W.shape[0]), dtype=torch.float32, device=dev)
+            act = _lib.ActEpilogue(y.data_ptr(), 0.0, 1, 0, 0, None)
+            _lib.call("fn_dense_fwd_f32", h.data_ptr(), W.data_ptr(), b.data_ptr(), y.data_ptr(), M, W.shape[1], W.shape[0], C.byref(act), st)
+            h = y
+            acts.append(h)
+        ctx.params, ctx.slots = params, [grad_slot(q) for q in params]
+        ctx.save_for_backward(gene, *acts)
+        return h
+
+    @staticmethod
+    def backward(ctx, g):
+        gene, *acts = ctx.saved_tensors
+        P, slots = ctx.params, ctx.slots
+        n = len(P) // 2
+        M = gene.shape[0]
+        st = _stream_ptr(gene.device)
+        tag = getattr(g, "_fn_relu_gated", None)
+        gated = tag is not None and tag.data_ptr() == acts[-1].data_ptr() and tag.shape == acts[-1].shape
+        g = _f32c(g, "g")
+        if not gated:
+            gy, top = torch.empty_like(g), acts[-1]
+            colsum = torch.empty(top.shape[1], dtype=torch.float32, device=g.device)
+            ws = _scratch(_lib.load().fn_gate_colsum_ws(M, top.shape[1]), g.device)
+            _lib.call("fn_gate_colsum_f32", g.data_ptr(), top.data_ptr(), gy.data_ptr(), colsum.data_ptr(), M, top.shape[1], 1.0, _ptr(ws), st)
+            g = gy
+        grads = [None] * (2 * n)
+        for i in range(n - 1, 0, -1):
+            W, x = P[2 * i], acts[i - 1]
+            dW, db = grad_buffer(P[2 * i], slots[2 * i]), grad_buffer(P[2 * i + 1], slots[2 * i + 1])
+            gx = torch.empty_like(x)
+            _lib.call("fn_dense_bwd_f32", g.data_ptr(), x.data_ptr(), W.data_ptr(), gx.data_ptr(), 1.0, dW.data_ptr(), db.data_ptr(), M, W.shape[1],
+                      W.shape[0], M, st)
+            grads[2 * i], grads[2 * i + 1] = dW, db
+            g = gx
+        dW, db = grad_buffer(P[0], slots[0]), grad_buffer(P[1], slots[1])
+        _lib.call("fn_cdrp_gene_bwd_f32", g.data_ptr(), None, gene.data_ptr(), dW.data_ptr(), db.data_ptr(), M, gene.shape[1], P[0].shape[0], st)
+        grads[0], grads[1] = dW, db
+        return (None, *grads)
+
+
+def cell_tower(gene_expr, linears):
+    """The cell-line tower on ``gene_expr`` [B, gene_dim] int64: relu(Linear(.)) for every Linear of ``linears`` (MLP.predictor), as
+    ``_CellTower``.  More than ``DENSE_MAX_ROWS`` rows, or a Linear behind the first whose widths are not multiples of 4 (or a first one
+    whose output width is not), fall back to plain torch ops on ``gene_expr.float()`` -- library GEMMs, the way ``mlp_head`` treats tall inputs."""
+    if not gene_expr.is_cuda:
+        raise _lib.FragnetHipError(f"cell_tower: fragnet_amd kernels need GPU tensors (got {gene_expr.device}); there is no CPU fallback")
+    linears = list(linears)
+    rows = gene_expr.shape[0]
+    ok = gene_expr.dtype == torch.int64 and gene_expr.dim() == 2 and rows <= DENSE_MAX_ROWS and linears[0].out_features % 4 == 0 \
+        and all(lin.bias is not None for lin in linears) and all(_dense_ok(rows, lin.weight) for lin in linears[1:])
+    if not ok:
+        v = gene_expr.float()
+        for lin in linears:
+            v = torch.relu(torch.nn.functional.linear(v, lin.weight, lin.bias))
+        return v
+    return _CellTower.apply(gene_expr, *[q for lin in linears for q in (lin.weight, lin.bias)])
+
+
+class _PairHead(torch.autograd.Function):
+    """fc2(fc1(cat(drug_enc, cell_enc))) (model/cdrp/model.py:35-42; nothing between the two Linears) for 256 + 256 -> 128 -> 1: one launch
+    each way (fn_cdrp_pair_fwd_f32 / fn_cdrp_pair_bwd_f32), the two inputs read where they are.  With ``target`` the forward also leaves
+    d MSE / d out and the loss partials, and the node returns (out, loss): ``out`` then carries no gradient and the VALUE of ``loss`` is
+    complete once backward has run (its sum rides in the backward launch), as with ``_MLPHead``'s fused loss.  The gradient handed to
+    ``cell_enc`` is already through the backward of the ReLU that produced it (tagged ``_fn_relu_gated`` for ``_CellTower``; applying
+    that gate again, as a plain autograd ReLU would, changes nothing)."""
+
+    @staticmethod
+    def forward(ctx, drug, cell, target, W1, b1, w2, b2):
+        drug, cell = _f32c(drug, "drug_enc"), _f32c(cell, "cell_enc")
+        W1, b1, w2, b2 = (_f32c(q, "pair-head parameter") for q in (W1, b1, w2, b2))
+        M, dev = drug.shape[0], drug.device
+        Kd, Kc, H, C_out = drug.shape[1], cell.shape[1], W1.shape[0], w2.shape[0]
+        if cell.shape[0] != M or W1.shape[1] != Kd + Kc or w2.shape[1] != H or b1.shape != (H,) or b2.shape != (C_out,):
+            raise ValueError("pair_head: drug_enc / cell_enc / fc1 / fc2 shapes do not fit together")
+        st = _stream_ptr(dev)
+        h = torch.empty((M, H), dtype=torch.float32, device=dev)
+        out = torch.empty((M, C_out), dtype=torch.float32, device=dev)
+        g = parts = loss_t = None
+        if target is not None:
+            target = _f32c(target, "y").reshape(-1)
+            if target.numel() != M * C_out:
+                raise ValueError(f"pair_head: {target.numel()} targets for {M} rows")
+            g = torch.empty(M, dtype=torch.float32, device=dev)
+            parts = torch.empty(_lib.load().fn_cdrp_pair_loss_ws(M), dtype=torch.float32, device=dev)
+            loss_t = torch.empty((), dtype=torch.float32, device=dev)
+        _lib.call("fn_cdrp_pair_fwd_f32", drug.data_ptr(), cell.data_ptr(), W1.data_ptr(), b1.data_ptr(), w2.data_ptr(), b2.data_ptr(),
+                  _ptr(target), h.data_ptr(), out.data_ptr(), _ptr(g), _ptr(parts), M, Kd, Kc, H, C_out, st)
+        ctx.params, ctx.slots = (W1, b1, w2, b2), [grad_slot(q) for q in (W1, b1, w2, b2)]
+        ctx.fused = target is not None
+        if ctx.fused:
+            ctx.save_for_backward(drug, cell, h, g, parts, loss_t)
+            ctx.mark_non_differentiable(out)
+            ctx.set_materialize_grads(False)
+            return out, loss_t
+        ctx.save_for_backward(drug, cell, h)
+        return out
+
+    @staticmethod
+    def backward(ctx, g_out, g_loss=None):
+        drug, cell, h = ctx.saved_tensors[:3]
+        M, dev = drug.shape[0], drug.device
+        parts = loss_t = None
+        if ctx.fused:
+            g, parts, loss_t = ctx.saved_tensors[3:]
+            unit = _UNIT_GRAD.get(dev)
+            if g_loss is not None and not (unit is not None and g_loss.data_ptr() == unit.data_ptr()):
+                g = g * g_loss
+        else:
+            g = _f32c(g_out, "g").reshape(-1)
+        P, slots = ctx.params, ctx.slots
+        dW1, db1, dW2, db2 = (grad_buffer(q, s) for q, s in zip(P, slots))
+        g_drug, g_cell = torch.empty_like(drug), torch.empty_like(cell)
+        _lib.call("fn_cdrp_pair_bwd_f32", g.data_ptr(), drug.data_ptr(), cell.data_ptr(), h.data_ptr(), P[0].data_ptr(), P[2].data_ptr(),
+                  g_drug.data_ptr(), g_cell.data_ptr(), dW1.data_ptr(), db1.data_ptr(), dW2.data_ptr(), db2.data_ptr(), _ptr(parts),
+                  0 if parts is None else parts.numel(), _ptr(loss_t), M, drug.shape[1], cell.shape[1], P[0].shape[0], P[2].shape[0],
+                  _stream_ptr(dev))
+        g_cell._fn_relu_gated = cell
+        return (g_drug if ctx.needs_input_grad[0] else None, g_cell if ctx.needs_input_grad[1] else None, None, dW1, db1, dW2, db2)
+
+
+def pair_head(drug_enc, cell_enc, fc1, fc2, loss=None):
+    """``fc2(fc1(cat(drug_enc, cell_enc)))`` as ``_PairHead``; ``cell_enc`` must be the output of a ReLU (the tower's: its gradient comes
+    back gated by ``cell_enc > 0``).  ``loss = (_lib.LOSS_MSE, y, None)``, in the style of ``mlp_head``: the caller is a training step that
+    calls ``backward`` on the loss right away; returns ``(out, loss)`` with ``loss`` None where the fused launch does not apply (the caller
+    then computes it from ``out``).  Other widths than 256 + 256 -> 128 -> 1, Linears without bias or more than ``DENSE_MAX_ROWS`` rows
+    fall back to plain torch ops (``torch.cat`` + two library GEMMs)."""
+    if not (drug_enc.is_cuda and cell_enc.is_cuda):
+        raise _lib.FragnetHipError("pair_head: fragnet_amd kernels need GPU tensors; there is no CPU fallback")
+    ok = (tuple(fc1.weight.shape), tuple(fc2.weight.shape)) == PAIR_HEAD_SHAPES and fc1.bias is not None and fc2.bias is not None \
+        and drug_enc.shape[1:] == cell_enc.shape[1:] == (FN_D * 2,) and drug_enc.shape[0] <= DENSE_MAX_ROWS
+    if not ok:
+        out = fc2(fc1(torch.cat((drug_enc, cell_enc), 1)))
+        return (out, None) if loss is not None else out
+    params = (fc1.weight, fc1.bias, fc2.weight, fc2.bias)
+    if loss is None:
+        return _PairHead.apply(drug_enc, cell_enc, None, *params)
+    kind, y, row_w = loss
+    fuse = FUSED_HEAD_LOSS and kind == _lib.LOSS_MSE and row_w is None and torch.is_grad_enabled() and drug_enc.shape[0] > 0 \
+        and (drug_enc.requires_grad or cell_enc.requires_grad or any(q.requires_grad for q in params))
+    if not fuse:
+        return _PairHead.apply(drug_enc, cell_enc, None, *params), None
+    return _PairHead.apply(drug_enc, cell_enc, y, *params)

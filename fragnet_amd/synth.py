@@ -322,6 +322,19 @@ def synth_molecules(B: int, seed: int, profile: str = "esol", pretrain_targets: 
     return [make_molecule(rng, mu, p_cut, n_tasks, pretrain_targets, p_salt) for _ in range(B)]
 
 
+def attach_gene_expr(mols: List[MolRecord], gene_dim: int, seed: int, pinned=()) -> List[MolRecord]:
+    """Gives every record a ``gene_expr`` float vector [gene_dim] drawn from N(0, 2.5) -- the cell-line input of a cancer-drug-response
+    record (reference dataset/cdrp.py; collate_fn_cdrp truncates it to int64: negatives, zeros and values up to about +-8).  ``pinned``:
+    values written over the leading entries of the FIRST record (fixtures place truncation cases there).  Returns ``mols``."""
+    rng = np.random.default_rng(seed)
+    for i, m in enumerate(mols):
+        v = rng.normal(0.0, 2.5, size=gene_dim).astype(np.float32)
+        if i == 0:
+            v[:len(pinned)] = np.asarray(pinned, dtype=np.float32)
+        m.gene_expr = torch.from_numpy(v)
+    return mols
+
+
 # ----------------------------------------------------------------------------------------
 # The one molecule whose fragmentation the reference publishes:
 # CC[NH+](CCCl)CCOc1cccc2ccccc12.[Cl-] with explicit H (41 atoms, 7 fragments),

@@ -25,7 +25,7 @@ import numpy as np
 import torch
 import yaml
 
-from . import parallel
+from . import _lib, parallel
 from .dataset import BatchSampler, FlatMolStore
 
 
@@ -277,6 +277,35 @@ class TrainerFineTune:
             if ok.any() and len(np.unique(t[ok, c])) == 2:
                 aucs.append(roc_auc_score(t[ok, c], p[ok, c]))
         return -float(np.mean(aucs)) if aucs else float("nan"), t, p
+
+
+class TrainerFineTuneCDRP(TrainerFineTune):
+    """The reference's ``trainer_cdrp.TrainerFineTune`` for a ``cdrp.CDRPModel`` (regression, MSE on ``model(batch).view(-1)``): the
+    loops are ``TrainerFineTune``'s.  A training step takes the model's fused-loss call (last Linear pair, loss and its gradient in one
+    launch).  ``label_mean`` / ``label_sdev`` are what the reference's driver passes and its trainer never reads; accepted and ignored."""
+
+    def __init__(self, target_pos=None, target_type="regr", n_multi_task_heads=0):
+        if target_type != "regr":
+            raise NotImplementedError(f"target_type {target_type!r} is outside the FragNet gat2 hot path")
+        super().__init__(target_pos=target_pos, target_type=target_type, n_multi_task_heads=n_multi_task_heads)
+
+    def _loss(self, model, batch):
+        if model.training and torch.is_grad_enabled():
+            out, loss = model(batch, loss=(_lib.LOSS_MSE, batch["y"], None))
+            if loss is not None:
+                return loss
+        else:
+            out = model(batch)
+        return self.loss_fn(out.view(-1), batch["y"])
+
+    def train(self, model, loader, optimizer, scheduler=None, device=None, val_loader=None, label_mean=None, label_sdev=None):
+        return super().train(model, loader, optimizer, scheduler=scheduler, device=device, val_loader=val_loader)
+
+    def validate(self, model, loader, device=None, label_mean=None, label_sdev=None):
+        return super().validate(model, loader, device=device)
+
+    def test(self, model, loader, device=None, label_mean=None, label_sdev=None):
+        return super().test(model, loader, device=device)
 
 
 class PretrainTrainer:

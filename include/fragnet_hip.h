@@ -850,6 +850,44 @@ int fn_encoder_backward(const fn_encoder* e, const float* out_atoms, const float
                         const float* g_fbond, const fn_layer_weights* grads /*[n_layers]*/, float* scratch,
                         int64_t scratch_floats, fn_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Cancer drug response model, CDRP (reference model/cdrp/model.py: CDRPModel = FragNet encoder + MLP(gene_dim) cell-line tower + the
+ * pair head fc2(fc1(cat(drug_enc, cell_enc)))); csrc/cdrp.hip.  Entry points added under ABI 12 (nothing existing changes).
+ * fp32 accumulate on the fp32 matrix cores, no atomics, sums over rows in a fixed order.  M <= FN_DENSE_MAX_ROWS throughout; M = 0 is
+ * legal: the forward calls launch nothing, the backward calls write zeros to the weight-gradient outputs.
+ *   fn_cdrp_gene_fwd_f32   Y[M,N] = relu(float(G[M,K]) W[N,K]^T + bias): the tower's first Linear on the int64 rows collate_fn_cdrp
+ *                          produces (the conversion, round to nearest like .float(), is part of the load).  K >= 1 is ANY length (903 in
+ *                          the reference's configs) -- rows of G and W need element alignment only, the K tail is handled in the kernel,
+ *                          nothing is padded; N a multiple of 4; K, N <= 65536.
+ *   fn_cdrp_gene_bwd_f32   dW[N,K] = g^T float(G),  db[N] = column sums of g (nullable).  g = g_y when y_gate == NULL: g_y is then already
+ *                          through this layer's ReLU (what fn_dense_bwd_f32 of the layer above hands down with gate_scale = 1);
+ *                          with y_gate = the saved output Y, g = g_y where Y > 0 and 0 elsewhere.  No input gradient: gene_expr is data.
+ * Tower layers 2-4 (1024 -> 256 -> 64 -> 256, ReLU after each, no dropout) are fn_dense_fwd_f32 (ReLU epilogue, p = 0) and
+ * fn_dense_bwd_f32 (gate_scale = 1).
+ *   fn_cdrp_pair_fwd_f32   h[M,H] = drug[M,Kd] W1[:, :Kd]^T + cell[M,Kc] W1[:, Kd:]^T + b1 (W1 [H, Kd + Kc]; no cat is written; h is saved
+ *                          for the backward), out[M] = h w2 + b2 (w2 [C,H], C = 1).  With target [M] (nullable): g[M] = d MSE / d out =
+ *                          2 (out - target) / M and loss_part[fn_cdrp_pair_loss_ws(M)] = per-workgroup partial sums of mean((out - target)^2),
+ *                          whose sum in order is the loss.  One launch.
+ *   fn_cdrp_pair_bwd_f32   from g[M] = d loss / d out (the forward's, or the caller's): dW2[C,H], db2[C], dW1[H, Kd + Kc], db1[H],
+ *                          g_drug[M,Kd], and g_cell[M,Kc] ALREADY through the backward of the ReLU that produced cell (0 where cell <= 0),
+ *                          so the tower's fn_dense_bwd_f32 receives its g_y ready.  loss != NULL: loss[0] = sum of the n_part partials in a
+ *                          fixed order.  One launch.
+ * The pair head is built for the reference's widths only, Kd = Kc = 256, H = 128, C = 1: anything else returns FN_EUNSUPPORTED (with the
+ * reason in fn_last_error) before anything is launched or written.  drug, cell, h, W1, g_drug, g_cell, dW1: 16-byte aligned.
+ * ------------------------------------------------------------------------------------------ */
+int fn_cdrp_gene_fwd_f32(const int64_t* G, const float* W, const float* bias /*nullable*/, float* Y, int64_t M, int64_t K, int64_t N,
+                         fn_stream_t stream);
+int fn_cdrp_gene_bwd_f32(const float* g_y, const float* y_gate /*nullable*/, const int64_t* G, float* dW, float* db /*nullable*/, int64_t M,
+                         int64_t K, int64_t N, fn_stream_t stream);
+int64_t fn_cdrp_pair_loss_ws(int64_t M);
+int fn_cdrp_pair_fwd_f32(const float* drug, const float* cell, const float* W1, const float* b1, const float* w2, const float* b2,
+                         const float* target /*nullable*/, float* h, float* out, float* g /*nullable without target*/,
+                         float* loss_part /*nullable without target*/, int64_t M, int64_t Kd, int64_t Kc, int64_t H, int64_t C,
+                         fn_stream_t stream);
+int fn_cdrp_pair_bwd_f32(const float* g, const float* drug, const float* cell, const float* h, const float* W1, const float* w2,
+                         float* g_drug, float* g_cell, float* dW1, float* db1, float* dW2, float* db2, const float* loss_part /*nullable*/,
+                         int64_t n_part, float* loss /*nullable*/, int64_t M, int64_t Kd, int64_t Kc, int64_t H, int64_t C, fn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
