@@ -14,8 +14,11 @@
     fragnet.model.cdrp.model          CDRPModel, MLP                     (finetune_cdrp.py:18)
     fragnet.dataset.data              collate_fn_cdrp                    (finetune_cdrp.py:6)
     fragnet.train.finetune.trainer_cdrp     TrainerFineTune              (finetune_cdrp.py:9)
+    fragnet.model.dta.model           DTAModel2, DTAModel                (finetune_dta.py:17)
+    fragnet.dataset.data              collate_fn_dta                     (finetune_dta.py:6)
+    fragnet.train.finetune.trainer_dta      TrainerFineTune              (finetune_dta.py:9)
     fragnet.vizualize.model           FragNetViz, FragNetFineTuneViz, FragNetFineTuneBaseViz, FragNetPreTrainViz (vizualize/viz.py)
 
-Model versions outside the accelerated hot path (masked pretraining heads, gcn / gat v1, DTA; SURVEY.md section 2 rows
+Model versions outside the accelerated hot path (masked pretraining heads, gcn / gat v1, DTA's transformer tower; SURVEY.md section 2 rows
 10-19) are named here only to fail with a clear message when constructed.
 """

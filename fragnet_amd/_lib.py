@@ -226,6 +226,12 @@ SIGNATURES = {
     "fn_cdrp_pair_loss_ws": [i64],
     "fn_cdrp_pair_fwd_f32": [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, i64, i64, i64, i64, vp],
     "fn_cdrp_pair_bwd_f32": [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, vp, i64, i64, i64, i64, i64, vp],
+    "fn_dta_conv_fwd_f32": [vp, vp, vp, vp, vp, vp, i64, i64, i64, i64, i64, i64, vp],
+    "fn_dta_conv_bwd_ws": [i64, i64, i64, i64],
+    "fn_dta_conv_bwd_f32": [vp, vp, vp, vp, vp, vp, vp, vp, i64, i64, i64, i64, i64, i64, vp],
+    "fn_dta_pair_loss_ws": [i64],
+    "fn_dta_pair_fwd_f32": [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, i64, i64, i64, i64, vp],
+    "fn_dta_pair_bwd_f32": [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, vp, i64, i64, i64, i64, i64, vp],
 }
 
 _lib = None

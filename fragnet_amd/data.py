@@ -135,3 +135,23 @@ def collate_fn_cdrp(data_list: List) -> Dict[str, torch.Tensor]:
 
 
 BATCH_KEYS_CDRP = BATCH_KEYS_FT + ("gene_expr",)
+
+
+DTA_VOCAB = 26           # nn.Embedding(25 + 1, 300) of DTAModel2: token 0 is the padding behind a sequence, 1..25 the residues
+
+
+def collate_fn_dta(data_list: List) -> Dict[str, torch.Tensor]:
+    """Drug-target-affinity batch dict (17 keys) -- reference data.py:1035-1109: the finetune batch plus ``protein`` [B, length], each
+    record's ``protein.view(1, -1)`` stacked and cast with ``.type(torch.long)`` exactly as the reference does.  A token outside
+    [0, 25] raises ValueError here, on the host: the reference's nn.Embedding raises for it, the protein-tower kernels cannot (they
+    skip such a position instead of indexing with it)."""
+    out = _collate_common(data_list)
+    out["y"] = torch.cat([d.y for d in data_list], dim=0).type(torch.float)
+    protein = torch.cat([d.protein.view(1, -1) for d in data_list], dim=0).type(torch.long)
+    if protein.numel() and (int(protein.min()) < 0 or int(protein.max()) >= DTA_VOCAB):
+        raise ValueError(f"collate_fn_dta: protein tokens must lie in [0, {DTA_VOCAB - 1}] (got {int(protein.min())} .. {int(protein.max())})")
+    out["protein"] = protein
+    return out
+
+
+BATCH_KEYS_DTA = BATCH_KEYS_FT + ("protein",)

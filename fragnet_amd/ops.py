@@ -1258,3 +1258,163 @@ def pair_head(drug_enc, cell_enc, fc1, fc2, loss=None):
     if not fuse:
         return _PairHead.apply(drug_enc, cell_enc, None, *params), None
     return _PairHead.apply(drug_enc, cell_enc, y, *params)
+
+
+# ======================================================================================
+# drug-target affinity model (reference model/dta/model.py, DTAModel2): the protein tower and the pair head 256 + 300, csrc/dta.hip
+# ======================================================================================
+DTA_PAIR_HEAD_SHAPES = ((128, 556), (1, 128))    # fc1, fc2: the widths fn_dta_pair_*_f32 is built for
+DTA_CONV_FILTERS, DTA_CONV_KS, DTA_CONV_MAX_V, DTA_CONV_MAX_L, DTA_CONV_MAX_D = 32, 8, 32, 4096, 512      # fn_dta_conv_*_f32's instance / limits
+
+
+class _ProteinTower(torch.autograd.Function):
+    """fc1_xt(conv_xt_1(embedding_xt(tokens)).view(B, -1)) (model/dta/model.py:134-138; no activation anywhere) as one autograd node.
+    The convolution runs in its histogram form (fn_dta_conv_fwd_f32: the [B, L, D] embedded tensor is never built, the per-sample
+    histogram A is saved for the backward), Linear(F J, 300) on fn_dense_fwd_f32 reading the convolution's output in place; backward:
+    fn_dense_bwd_f32 (no gate: nothing sits between the two layers), then fn_dta_conv_bwd_f32 for the convolution's weight and bias
+    and the embedding table.  No gradient for ``tokens``: they are data."""
+
+    @staticmethod
+    def forward(ctx, tokens, E, Wc, bc, Wf, bf):
+        tokens = _i64c(tokens, "protein tokens")
+        E, Wc, bc, Wf, bf = (_f32c(q, "protein-tower parameter") for q in (E, Wc, bc, Wf, bf))
+        M, L = tokens.shape
+        V, D = E.shape
+        F_, KS = Wc.shape[0], Wc.shape[2]
+        K, N = F_ * (D - KS + 1), Wf.shape[0]
+        dev, st = tokens.device, _stream_ptr(tokens.device)
+        A = torch.empty((M, V, F_ * KS), dtype=torch.float32, device=dev)
+        conv = torch.empty((M, K), dtype=torch.float32, device=dev)
+        _lib.call("fn_dta_conv_fwd_f32", tokens.data_ptr(), E.data_ptr(), Wc.data_ptr(), bc.data_ptr(), A.data_ptr(), conv.data_ptr(), M, L, D, V,
+                  F_, KS, st)
+        xt = torch.empty((M, N), dtype=torch.float32, device=dev)
+        _lib.call("fn_dense_fwd_f32", conv.data_ptr(), Wf.data_ptr(), bf.data_ptr(), xt.data_ptr(), M, K, N, None, st)
+        ctx.params, ctx.slots = (E, Wc, bc, Wf, bf), [grad_slot(q) for q in (E, Wc, bc, Wf, bf)]
+        ctx.save_for_backward(tokens, A, conv)
+        return xt
+
+    @staticmethod
+    def backward(ctx, g):
+        tokens, A, conv = ctx.saved_tensors
+        g = _f32c(g, "g")
+        (E, Wc, bc, Wf, bf), slots = ctx.params, ctx.slots
+        dE, dWc, dbc, dWf, dbf = (grad_buffer(q, s) for q, s in zip(ctx.params, slots))
+        M, L = tokens.shape
+        V, D = E.shape
+        K, N = conv.shape[1], Wf.shape[0]
+        st = _stream_ptr(g.device)
+        g_conv = torch.empty_like(conv)
+        _lib.call("fn_dense_bwd_f32", g.data_ptr(), conv.data_ptr(), Wf.data_ptr(), g_conv.data_ptr(), 0.0, dWf.data_ptr(), dbf.data_ptr(), M, K, N,
+                  M, st)
+        ws = _scratch(_lib.load().fn_dta_conv_bwd_ws(M, L, D, V), g.device)
+        _lib.call("fn_dta_conv_bwd_f32", g_conv.data_ptr(), tokens.data_ptr(), E.data_ptr(), A.data_ptr(), dWc.data_ptr(), dbc.data_ptr(),
+                  dE.data_ptr(), _ptr(ws), M, L, D, V, Wc.shape[0], Wc.shape[2], st)
+        return None, dE, dWc, dbc, dWf, dbf
+
+
+def _protein_tower_ok(tokens, embedding, conv, fc) -> bool:
+    W = conv.weight
+    if tokens.dim() != 2 or W.dim() != 3 or conv.bias is None or fc.bias is None:
+        return False
+    plain_conv = tuple(conv.stride) == (1,) and tuple(conv.dilation) == (1,) and conv.groups == 1 and conv.padding in ((0,), "valid") \
+        and conv.padding_mode == "zeros"
+    plain_emb = embedding.padding_idx is None and embedding.max_norm is None and not embedding.scale_grad_by_freq and not embedding.sparse
+    V, D = embedding.weight.shape
+    return plain_conv and plain_emb and tuple(W.shape) == (DTA_CONV_FILTERS, tokens.shape[1], DTA_CONV_KS) and V <= DTA_CONV_MAX_V \
+        and DTA_CONV_KS <= D <= DTA_CONV_MAX_D and 1 <= tokens.shape[1] <= DTA_CONV_MAX_L \
+        and fc.in_features == DTA_CONV_FILTERS * (D - DTA_CONV_KS + 1) and _dense_ok(tokens.shape[0], fc.weight)
+
+
+def protein_tower(tokens, embedding, conv, fc):
+    """The protein tower of ``DTAModel2`` on ``tokens`` [B, L] int64: ``fc(conv(embedding(tokens)).view(B, -1))`` with ``embedding`` an
+    nn.Embedding(V, D), ``conv`` an nn.Conv1d(L, 32, 8) (it only holds the parameters) and ``fc`` an nn.Linear(32 (D - 7), .), as
+    ``_ProteinTower``.  More than ``DENSE_MAX_ROWS`` rows or other shapes than fn_dta_conv_*_f32 is built for (32 filters of 8, V <= 32,
+    8 <= D <= 512, L <= 4096, plain stride / padding / dilation) fall back to plain torch ops (embedding, library convolution and GEMM)."""
+    if not tokens.is_cuda:
+        raise _lib.FragnetHipError(f"protein_tower: fragnet_amd kernels need GPU tensors (got {tokens.device}); there is no CPU fallback")
+    if tokens.dtype != torch.int64:
+        raise TypeError(f"protein_tower: expected int64 tokens (collate_fn_dta's protein), got {tokens.dtype}")
+    if not _protein_tower_ok(tokens, embedding, conv, fc):
+        return fc(conv(embedding(tokens)).flatten(1))
+    return _ProteinTower.apply(tokens, embedding.weight, conv.weight, conv.bias, fc.weight, fc.bias)
+
+
+class _PairHeadDTA(torch.autograd.Function):
+    """fc2(fc1(cat(drug_enc, xt))) (model/dta/model.py:141-144; nothing between the two Linears) for 256 + 300 -> 128 -> 1: one launch each
+    way (fn_dta_pair_fwd_f32 / fn_dta_pair_bwd_f32), the two inputs read where they are.  The fused-loss convention is ``_PairHead``'s:
+    with ``target`` the node returns (out, loss), ``out`` carries no gradient and the VALUE of ``loss`` is complete once backward has
+    run.  Unlike ``_PairHead`` the gradient of the second input is NOT gated: ``xt`` is a Linear's output."""
+
+    @staticmethod
+    def forward(ctx, drug, xt, target, W1, b1, w2, b2):
+        drug, xt = _f32c(drug, "drug_enc"), _f32c(xt, "xt")
+        W1, b1, w2, b2 = (_f32c(q, "pair-head parameter") for q in (W1, b1, w2, b2))
+        M, dev = drug.shape[0], drug.device
+        Kd, Kx, H, C_out = drug.shape[1], xt.shape[1], W1.shape[0], w2.shape[0]
+        if xt.shape[0] != M or W1.shape[1] != Kd + Kx or w2.shape[1] != H or b1.shape != (H,) or b2.shape != (C_out,):
+            raise ValueError("pair_head_dta: drug_enc / xt / fc1 / fc2 shapes do not fit together")
+        st = _stream_ptr(dev)
+        h = torch.empty((M, H), dtype=torch.float32, device=dev)
+        out = torch.empty((M, C_out), dtype=torch.float32, device=dev)
+        g = parts = loss_t = None
+        if target is not None:
+            target = _f32c(target, "y").reshape(-1)
+            if target.numel() != M * C_out:
+                raise ValueError(f"pair_head_dta: {target.numel()} targets for {M} rows")
+            g = torch.empty(M, dtype=torch.float32, device=dev)
+            parts = torch.empty(_lib.load().fn_dta_pair_loss_ws(M), dtype=torch.float32, device=dev)
+            loss_t = torch.empty((), dtype=torch.float32, device=dev)
+        _lib.call("fn_dta_pair_fwd_f32", drug.data_ptr(), xt.data_ptr(), W1.data_ptr(), b1.data_ptr(), w2.data_ptr(), b2.data_ptr(),
+                  _ptr(target), h.data_ptr(), out.data_ptr(), _ptr(g), _ptr(parts), M, Kd, Kx, H, C_out, st)
+        ctx.params, ctx.slots = (W1, b1, w2, b2), [grad_slot(q) for q in (W1, b1, w2, b2)]
+        ctx.fused = target is not None
+        if ctx.fused:
+            ctx.save_for_backward(drug, xt, h, g, parts, loss_t)
+            ctx.mark_non_differentiable(out)
+            ctx.set_materialize_grads(False)
+            return out, loss_t
+        ctx.save_for_backward(drug, xt, h)
+        return out
+
+    @staticmethod
+    def backward(ctx, g_out, g_loss=None):
+        drug, xt, h = ctx.saved_tensors[:3]
+        M, dev = drug.shape[0], drug.device
+        parts = loss_t = None
+        if ctx.fused:
+            g, parts, loss_t = ctx.saved_tensors[3:]
+            unit = _UNIT_GRAD.get(dev)
+            if g_loss is not None and not (unit is not None and g_loss.data_ptr() == unit.data_ptr()):
+                g = g * g_loss
+        else:
+            g = _f32c(g_out, "g").reshape(-1)
+        P, slots = ctx.params, ctx.slots
+        dW1, db1, dW2, db2 = (grad_buffer(q, s) for q, s in zip(P, slots))
+        g_drug, g_xt = torch.empty_like(drug), torch.empty_like(xt)
+        _lib.call("fn_dta_pair_bwd_f32", g.data_ptr(), drug.data_ptr(), xt.data_ptr(), h.data_ptr(), P[0].data_ptr(), P[2].data_ptr(),
+                  g_drug.data_ptr(), g_xt.data_ptr(), dW1.data_ptr(), db1.data_ptr(), dW2.data_ptr(), db2.data_ptr(), _ptr(parts),
+                  0 if parts is None else parts.numel(), _ptr(loss_t), M, drug.shape[1], xt.shape[1], P[0].shape[0], P[2].shape[0],
+                  _stream_ptr(dev))
+        return (g_drug if ctx.needs_input_grad[0] else None, g_xt if ctx.needs_input_grad[1] else None, None, dW1, db1, dW2, db2)
+
+
+def pair_head_dta(drug_enc, xt, fc1, fc2, loss=None):
+    """``fc2(fc1(cat(drug_enc, xt)))`` as ``_PairHeadDTA``; ``loss = (_lib.LOSS_MSE, y, None)`` as for ``pair_head``: returns
+    ``(out, loss)`` with ``loss`` None where the fused launch does not apply.  Other widths than 256 + 300 -> 128 -> 1, Linears without
+    bias or more than ``DENSE_MAX_ROWS`` rows fall back to plain torch ops (``torch.cat`` + two library GEMMs)."""
+    if not (drug_enc.is_cuda and xt.is_cuda):
+        raise _lib.FragnetHipError("pair_head_dta: fragnet_amd kernels need GPU tensors; there is no CPU fallback")
+    ok = (tuple(fc1.weight.shape), tuple(fc2.weight.shape)) == DTA_PAIR_HEAD_SHAPES and fc1.bias is not None and fc2.bias is not None \
+        and drug_enc.shape[1:] == (FN_D * 2,) and xt.shape[1:] == (DTA_PAIR_HEAD_SHAPES[0][1] - FN_D * 2,) and drug_enc.shape[0] <= DENSE_MAX_ROWS
+    if not ok:
+        out = fc2(fc1(torch.cat((drug_enc, xt), 1)))
+        return (out, None) if loss is not None else out
+    params = (fc1.weight, fc1.bias, fc2.weight, fc2.bias)
+    if loss is None:
+        return _PairHeadDTA.apply(drug_enc, xt, None, *params)
+    kind, y, row_w = loss
+    fuse = FUSED_HEAD_LOSS and kind == _lib.LOSS_MSE and row_w is None and torch.is_grad_enabled() and drug_enc.shape[0] > 0 \
+        and (drug_enc.requires_grad or xt.requires_grad or any(q.requires_grad for q in params))
+    if not fuse:
+        return _PairHeadDTA.apply(drug_enc, xt, None, *params), None
+    return _PairHeadDTA.apply(drug_enc, xt, y, *params)

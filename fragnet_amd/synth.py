@@ -335,6 +335,25 @@ def attach_gene_expr(mols: List[MolRecord], gene_dim: int, seed: int, pinned=())
     return mols
 
 
+def attach_protein(mols: List[MolRecord], seed: int, length: int = 1000, pinned=None) -> List[MolRecord]:
+    """Gives every record a ``protein`` float vector [length] -- the target input of a drug-target-affinity record as the reference's
+    dataset/dta.py (CreateData.encode_protein) writes it: residue tokens 1..25 over a prefix of random length, 0 behind it.  The first
+    record is full length.  ``pinned``: {record index: sequence of tokens}, written over that record's vector (zero-padded; fixtures place
+    their edge cases there).  Returns ``mols``."""
+    rng = np.random.default_rng(seed)
+    pinned = {int(k): v for k, v in dict(pinned or {}).items()}
+    for i, m in enumerate(mols):
+        n = length if i == 0 else int(rng.integers(1, length + 1))
+        v = np.zeros(length, dtype=np.float32)
+        v[:n] = rng.integers(1, 26, size=n)
+        if i in pinned:
+            seq = np.asarray(pinned[i], dtype=np.float32)
+            v[:] = 0.0
+            v[:len(seq)] = seq
+        m.protein = torch.from_numpy(v)
+    return mols
+
+
 # ----------------------------------------------------------------------------------------
 # The one molecule whose fragmentation the reference publishes:
 # CC[NH+](CCCl)CCOc1cccc2ccccc12.[Cl-] with explicit H (41 atoms, 7 fragments),

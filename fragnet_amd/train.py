@@ -308,6 +308,49 @@ class TrainerFineTuneCDRP(TrainerFineTune):
         return super().test(model, loader, device=device)
 
 
+class TrainerFineTuneDTA(TrainerFineTune):
+    """The reference's ``trainer_dta.TrainerFineTune`` for a ``dta.DTAModel2`` (regression only).  Unlike the CDRP trainer this one USES
+    ``label_mean`` / ``label_sdev``: ``train`` fits ``(y - mean) / (sdev + 1e-5)`` (trainer_dta.py:42), ``validate`` and ``test``
+    de-normalise the output (``out * sdev + mean``) and compare it with the raw ``y`` (trainer_dta.py:65, 83).  A training step takes the
+    model's fused-loss call on the normalised target.  Returned losses are sums of per-batch losses over ``len(loader.dataset)``, as in
+    the reference.  The defaults mean = 0, sdev = 1 leave everything but the 1e-5 as it is."""
+
+    def __init__(self, target_pos=None, target_type="regr", n_multi_task_heads=0):
+        if target_type != "regr":
+            raise NotImplementedError(f"target_type {target_type!r} is outside the FragNet gat2 hot path")
+        super().__init__(target_pos=target_pos, target_type=target_type, n_multi_task_heads=n_multi_task_heads)
+        self._norm = (0.0, 1.0)
+
+    def _loss(self, model, batch):
+        mean, sdev = self._norm
+        if model.training and torch.is_grad_enabled():
+            y = (batch["y"] - mean) / (sdev + 1e-5)
+            out, loss = model(batch, loss=(_lib.LOSS_MSE, y, None))
+            if loss is not None:
+                return loss
+            return self.loss_fn(out.view(-1), y)
+        return self.loss_fn(model(batch).view(-1) * sdev + mean, batch["y"])
+
+    @staticmethod
+    def _stats(label_mean, label_sdev):
+        return (0.0 if label_mean is None else float(label_mean), 1.0 if label_sdev is None else float(label_sdev))
+
+    def train(self, model, loader, optimizer, scheduler=None, device=None, val_loader=None, label_mean=None, label_sdev=None):
+        self._norm = self._stats(label_mean, label_sdev)
+        return super().train(model, loader, optimizer, scheduler=scheduler, device=device, val_loader=val_loader)
+
+    def validate(self, model, loader, device=None, label_mean=None, label_sdev=None):
+        self._norm = self._stats(label_mean, label_sdev)
+        return super().validate(model, loader, device=device)
+
+    def test(self, model, loader, device=None, label_mean=None, label_sdev=None):
+        """(mse, true, pred) with ``pred`` de-normalised."""
+        mean, sdev = self._stats(label_mean, label_sdev)
+        _, t, p = super().test(model, loader, device=device)
+        p = p * np.float32(sdev) + np.float32(mean)
+        return float(((t - p) ** 2).mean()), t, p
+
+
 class PretrainTrainer:
     def __init__(self, loss_fn=None):
         self.loss_fn = loss_fn

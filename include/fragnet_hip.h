@@ -888,6 +888,46 @@ int fn_cdrp_pair_bwd_f32(const float* g, const float* drug, const float* cell, c
                          float* g_drug, float* g_cell, float* dW1, float* db1, float* dW2, float* db2, const float* loss_part /*nullable*/,
                          int64_t n_part, float* loss /*nullable*/, int64_t M, int64_t Kd, int64_t Kc, int64_t H, int64_t C, fn_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Drug-target affinity model, DTA (reference model/dta/model.py: DTAModel2 = FragNet encoder + protein tower Embedding(V, D) ->
+ * Conv1d(L -> F, KS) along the embedding axis -> Linear(F J, 300), J = D - KS + 1, no activation anywhere -> the pair head
+ * fc2(fc1(cat(drug_enc, xt)))); csrc/dta.hip.  Entry points added under ABI 12 (nothing existing changes).  fp32 accumulate, no atomics,
+ * every sum over positions, samples or rows in a fixed order.  M <= FN_DENSE_MAX_ROWS throughout; M = 0 is legal: the forward calls
+ * launch nothing, the backward calls write zeros to the gradient outputs.
+ * The convolution runs in its histogram form (the layer is linear in the V-row table E):
+ *     A[b, v, f, k] = sum of W[f, c, k] over the positions c with tok[b, c] = v;   conv[b, f, j] = bias[f] + sum_v sum_k A[b, v, f, k] E[v, j + k]
+ *   fn_dta_conv_fwd_f32    tok[M,L] int64 (what collate_fn_dta produces), E[V,D], W[F,L,KS], bias[F] -> conv[M, F J], laid out as the
+ *                          reference's conv_xt.view(-1, F J) so that the dense layer reads it in place, and A[M, V, F KS] (note the
+ *                          order: v outermost), saved for the backward.  Two launches (histogram, contraction).
+ *   fn_dta_conv_bwd_f32    from g_conv[M, F J]: dW[F,L,KS], dbias[F], dE[V,D]; no input gradient (tokens are data).  Three launches:
+ *                          per sample G[b, v, f, k] = sum_j g[b, f, j] E[v, j + k] and the sample's shares of dE and dbias; the gather
+ *                          dW[f, c, k] = sum_b G[b, tok[b, c], f, k] (samples in order; more than 32 samples: up to 16 partial sums); the
+ *                          sums of the partials in order.  ws: fn_dta_conv_bwd_ws(M, L, D, V) floats, 16-byte aligned.
+ * Built instance: F = 32, KS = 8, 1 <= V <= 32 -- anything else returns FN_EUNSUPPORTED before anything is launched or written.
+ * Run-time: 1 <= L <= 4096 and ANY 8 <= D <= 512 (no multiple-of-4 rule: E, W, conv, g_conv, dE need element alignment only, the tails
+ * are masked, nothing is padded in memory); outside: FN_EINVAL.  A, dW, ws: 16-byte aligned.
+ * A token outside [0, V) is never used to index memory: it falls into no bin (its position contributes nothing to conv) and its
+ * dW[:, c, :] terms are absent (0 from every sample that has such a token there).  torch raises instead; collate_fn_dta checks on the host.
+ *   fn_dta_pair_fwd_f32 / fn_dta_pair_bwd_f32 / fn_dta_pair_loss_ws
+ *                          the pair head as fn_cdrp_pair_*_f32, same arguments and contract, for Kd = 256, Kx = 300, H = 128, C = 1 (W1
+ *                          [128, 556]; 300 = 18 x 16 + 12: the reduction's tail is masked) with ONE difference: g_xt[M,300] is NOT gated --
+ *                          xt is the output of a Linear, not of a ReLU.  Other widths: FN_EUNSUPPORTED.  drug, xt, h, W1, g_drug, g_xt,
+ *                          dW1: 16-byte aligned.
+ * ------------------------------------------------------------------------------------------ */
+int fn_dta_conv_fwd_f32(const int64_t* tok, const float* E, const float* W, const float* bias, float* A, float* conv, int64_t M, int64_t L,
+                        int64_t D, int64_t V, int64_t F, int64_t KS, fn_stream_t stream);
+int64_t fn_dta_conv_bwd_ws(int64_t M, int64_t L, int64_t D, int64_t V);
+int fn_dta_conv_bwd_f32(const float* g_conv, const int64_t* tok, const float* E, const float* A, float* dW, float* dbias, float* dE, float* ws,
+                        int64_t M, int64_t L, int64_t D, int64_t V, int64_t F, int64_t KS, fn_stream_t stream);
+int64_t fn_dta_pair_loss_ws(int64_t M);
+int fn_dta_pair_fwd_f32(const float* drug, const float* xt, const float* W1, const float* b1, const float* w2, const float* b2,
+                        const float* target /*nullable*/, float* h, float* out, float* g /*nullable without target*/,
+                        float* loss_part /*nullable without target*/, int64_t M, int64_t Kd, int64_t Kx, int64_t H, int64_t C,
+                        fn_stream_t stream);
+int fn_dta_pair_bwd_f32(const float* g, const float* drug, const float* xt, const float* h, const float* W1, const float* w2,
+                        float* g_drug, float* g_xt, float* dW1, float* db1, float* dW2, float* db2, const float* loss_part /*nullable*/,
+                        int64_t n_part, float* loss /*nullable*/, int64_t M, int64_t Kd, int64_t Kx, int64_t H, int64_t C, fn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

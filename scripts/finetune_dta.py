@@ -1,0 +1,97 @@
+#!/usr/bin/env python3
+"""Counterpart of the reference's fragnet/train/finetune/finetune_dta.py: same CLI (--config X.yaml), same YAML schema (finetune.*,
+pretrain.chkpoint_name -> model.drug_model.pretrain), same checkpoint format (plain state_dict), on the MI355X path.  The model is
+DTAModel2, as in the reference's driver.  Datasets are pickled lists of per-molecule records with a ``protein`` token vector
+(scripts/make_synthetic_dta_dataset.py writes synthetic ones).  ``label_mean`` / ``label_sdev`` are the mean and standard deviation
+of the training labels (the reference reads them from the training csv's ``affinity`` column: the same numbers); the trainer fits the
+normalised label and reports de-normalised predictions.
+
+    python scripts/finetune_dta.py --config exps/ft/dta_synth/config.yaml
+"""
+import argparse
+import json
+import os
+import pickle
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import numpy as np
+import torch
+from torch.utils.data import DataLoader
+
+from fragnet_amd import data, train
+from fragnet_amd.dta import DTAModel2, FragNetFineTuneBase
+from fragnet_amd.dataset import load_pickle_dataset
+from fragnet_amd.model import FragNetPreTrain
+
+
+class _OnDevice:
+    """a DataLoader whose batches arrive on the GPU (data.batch_to keeps the collate's layout promise)"""
+
+    def __init__(self, loader, device):
+        self.loader, self.device, self.dataset = loader, device, loader.dataset
+
+    def __iter__(self):
+        return (data.batch_to(b, self.device) for b in self.loader)
+
+    def __len__(self):
+        return len(self.loader)
+
+
+if __name__ == "__main__":
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--config", default="config.yaml")
+    cli = ap.parse_args()
+    args = train.load_config(cli.config, config=cli.config)
+    train.seed_everything(args.seed)
+    device = torch.device("cuda", 0)
+    torch.cuda.set_device(device)
+    exp_dir = args["exp_dir"]
+    os.makedirs(exp_dir, exist_ok=True)
+    ft, m = args.finetune, args.finetune.model
+    if args.model_version != "gat2":
+        raise SystemExit("DTA: model_version gat2 is on the accelerated path")
+    if ft.target_type != "regr":
+        raise SystemExit("DTA: target_type regr only")
+    gat2 = FragNetFineTuneBase(n_classes=m.n_classes, atom_features=args.atom_features, frag_features=args.frag_features,
+                               edge_features=args.edge_features, num_layer=m.num_layer, drop_ratio=m.drop_ratio, num_heads=m.num_heads,
+                               emb_dim=m.emb_dim, h1=m.h1, h2=m.h2, h3=m.h3, h4=m.h4, act=m.act, fthead=m.fthead)
+    model = DTAModel2(gat2)
+    pt = args.pretrain
+    if pt.get("chkpoint_name") and os.path.exists(str(pt.chkpoint_name)):
+        modelpt = FragNetPreTrain(num_layer=pt.num_layer, drop_ratio=pt.drop_ratio, num_heads=pt.num_heads, emb_dim=pt.emb_dim,
+                                  atom_features=args.atom_features, frag_features=args.frag_features, edge_features=args.edge_features,
+                                  fedge_in=args.fedge_in, fbond_edge_in=args.fbond_edge_in)
+        modelpt.load_state_dict(torch.load(pt.chkpoint_name, map_location="cpu"))
+        model.drug_model.pretrain.load_state_dict(modelpt.pretrain.state_dict())
+        print("loaded pretrained encoder", pt.chkpoint_name)
+    model.to(device)
+    sets = {k: load_pickle_dataset(ft[k].path) for k in ("train", "val", "test")}
+    train_loader = _OnDevice(DataLoader(sets["train"], collate_fn=data.collate_fn_dta, batch_size=ft.batch_size, shuffle=True, drop_last=True), device)
+    val_loader = _OnDevice(DataLoader(sets["val"], collate_fn=data.collate_fn_dta, batch_size=64, shuffle=False), device)
+    test_loader = _OnDevice(DataLoader(sets["test"], collate_fn=data.collate_fn_dta, batch_size=64, shuffle=False), device)
+    trainer = train.TrainerFineTuneDTA(target_type=ft.target_type)
+    labels = np.array([float(r.y) for r in sets["train"]])
+    stats = dict(label_mean=float(labels.mean()), label_sdev=float(labels.std()))
+    with open(os.path.join(exp_dir, "train_stats.pkl"), "wb") as f:
+        pickle.dump({"mean": stats["label_mean"], "sdev": stats["label_sdev"]}, f)
+    optimizer = train.make_optimizer(model, float(ft.lr), next(iter(train_loader)), lambda mdl, b: trainer._loss(mdl, b))
+    stopper = train.EarlyStopping(patience=ft.es_patience, verbose=True, chkpoint_name=ft.chkpoint_name)
+    log = open(os.path.join(exp_dir, "log.jsonl"), "a")
+    for epoch in range(ft.n_epochs):
+        train_loss = trainer.train(model=model, loader=train_loader, optimizer=optimizer, scheduler=None, device=device, val_loader=val_loader,
+                                   **stats)
+        val_loss, _, _ = trainer.test(model=model, loader=val_loader, device=device, **stats)
+        print("epoch: ", epoch, train_loss, val_loss)
+        log.write(json.dumps({"epoch": epoch, "Loss/train": train_loss, "Loss/val": val_loss}) + "\n")
+        log.flush()
+        stopper(val_loss, model)
+        if stopper.early_stop:
+            print("Early stopping")
+            break
+    model.load_state_dict(torch.load(ft.chkpoint_name, map_location=device))
+    for name, loader in (("val_res", val_loader), ("test_res", test_loader)):
+        score, true, pred = trainer.test(model=model, loader=loader, device=device, **stats)
+        with open(os.path.join(exp_dir, f"{name}_{args.seed}.pkl"), "wb") as f:
+            pickle.dump({"acc": score ** 0.5, "true": true, "pred": pred, "smiles": [getattr(r, "smiles", None) for r in loader.dataset]}, f)
+        print(f"{name} rmse: {score ** 0.5}")
