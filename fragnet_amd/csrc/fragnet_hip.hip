@@ -173,6 +173,39 @@ __global__ __launch_bounds__(kBlock) void k_pool_cat(const float* __restrict__ x
         out[s * 2 * FN_D + blockIdx.y * FN_D + threadIdx.x] = v;
     }
 }
+// leave-group-out form of k_pool_cat (fragment contributions, fragnet/vizualize/model_attr.py:186-205: the rows of one fragment are set
+// to 0.0 in the encoder's final x_atoms, x_frags stays): output row r is molecule row_mol[r] pooled without the atoms whose group is
+// row_group[r].  Same partition (half-wave hw takes rows hw, hw + 8, ...) and same order of additions as k_pool_cat; an atom that is
+// left out enters the sum as 0.0, so a row equals k_pool_cat's of the same table with those rows overwritten by 0.0, bit for bit, and
+// a row that leaves nothing out equals k_pool_cat's row of its molecule.  grid (R, 2) like k_pool_cat's (B, 2).
+__global__ __launch_bounds__(kBlock) void k_pool_cat_groups(const float* __restrict__ x_atoms, const float* __restrict__ x_frags,
+                                                            fn_seg_plan sa, fn_seg_plan sf, const int64_t* __restrict__ atom_group,
+                                                            const int32_t* __restrict__ row_mol, const int64_t* __restrict__ row_group,
+                                                            float* __restrict__ out) {
+    __shared__ float sS[kRows][FN_D];
+    const fn_seg_plan& sp = blockIdx.y ? sf : sa;
+    const float* src = blockIdx.y ? x_frags : x_atoms;
+    const int lane = threadIdx.x & 31, hw = threadIdx.x >> 5;
+    const int64_t r = blockIdx.x;
+    const int64_t s = row_mol[r];
+    const int64_t leave = blockIdx.y ? -1 : row_group[r];      // < 0: nothing is left out (ungrouped atoms carry ids < 0 too)
+    const int beg = sp.rowptr[s] - sp.pos_base, deg = sp.rowptr[s + 1] - sp.rowptr[s];
+    float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+    for (int i = hw; i < deg; i += kRows) {
+        const int32_t row = sp.perm[beg + i];
+        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (leave < 0 || atom_group[row] != leave) v = ld4(src + (size_t)row * FN_D + lane * 4);
+        acc.x += v.x; acc.y += v.y; acc.z += v.z; acc.w += v.w;
+    }
+    st4(&sS[hw][lane * 4], acc);
+    __syncthreads();
+    if (threadIdx.x < FN_D) {
+        float v = 0.f;
+#pragma unroll
+        for (int w = 0; w < kRows; ++w) v += sS[w][threadIdx.x];
+        out[(size_t)r * 2 * FN_D + blockIdx.y * FN_D + threadIdx.x] = v;
+    }
+}
 // its backward: g_atoms[i,:] = g[batch[i], 0:128], g_frags[f,:] = g[frag_batch[f], 128:256]
 __global__ void k_pool_cat_bwd(const float* __restrict__ g, const int64_t* __restrict__ batch, const int64_t* __restrict__ frag_batch,
                                float* __restrict__ g_atoms, float* __restrict__ g_frags, int64_t N, int64_t F) {
@@ -820,6 +853,21 @@ int fn_pool_cat_f32(const float* x_atoms, const float* x_frags, const fn_seg_pla
     hipLaunchKernelGGL(k_pool_cat, dim3((unsigned)mol_atoms->n_seg, 2), dim3(kBlock), 0, S(stream), x_atoms, x_frags, *mol_atoms,
                        *mol_frags, out);
     return launch_status("fn_pool_cat_f32");
+}
+
+int fn_pool_cat_groups_f32(const float* x_atoms, const float* x_frags, const fn_seg_plan* mol_atoms, const fn_seg_plan* mol_frags,
+                           const int64_t* atom_group, const int32_t* row_mol, const int64_t* row_group, int64_t R, float* out,
+                           fn_stream_t stream) {
+    if (!mol_atoms || !mol_frags || mol_atoms->n_seg != mol_frags->n_seg || R < 0 || R > 0x7fffffffLL)
+        return fail(FN_EINVAL, "fn_pool_cat_groups_f32: bad argument");
+    if (R == 0) return 0;
+    if (mol_atoms->n_seg == 0) return fail(FN_EINVAL, "fn_pool_cat_groups_f32: output rows of a batch without molecules");
+    if (!out || !row_mol || !row_group || (mol_atoms->n_items > 0 && (!x_atoms || !atom_group || !mol_atoms->perm)) ||
+        (mol_frags->n_items > 0 && (!x_frags || !mol_frags->perm)) || !mol_atoms->rowptr || !mol_frags->rowptr)
+        return fail(FN_EINVAL, "fn_pool_cat_groups_f32: null buffer");
+    hipLaunchKernelGGL(k_pool_cat_groups, dim3((unsigned)R, 2), dim3(kBlock), 0, S(stream), x_atoms, x_frags, *mol_atoms, *mol_frags,
+                       atom_group, row_mol, row_group, out);
+    return launch_status("fn_pool_cat_groups_f32");
 }
 
 int fn_pool_cat_bwd_f32(const float* g, const int64_t* batch, const int64_t* frag_batch, float* g_atoms, float* g_frags,

@@ -338,6 +338,36 @@ def pool_cat(x_atoms, x_frags, plan):
     return _PoolCat.apply(x_atoms, x_frags, plan)
 
 
+def pool_cat_groups(x_atoms, x_frags, plan, atom_group, row_mol, row_group, check: bool = True):
+    """The leave-group-out read-out (fn_pool_cat_groups_f32): row r of the result [R, 256] is ``pool_cat``'s row of molecule
+    ``row_mol[r]`` without the atoms i with ``atom_group[i] == row_group[r]`` (``row_group[r] < 0``: the unmasked row; an atom with
+    ``atom_group < 0`` is in no group).  ``atom_group`` int64 [N], ``row_mol`` int32 [R], ``row_group`` int64 [R], on the batch's
+    device.  An evaluation read-out: no autograd node.  ``row_mol`` is checked here, on the host (one synchronisation: the kernel has
+    no status word); ``check=False``: the caller built ``row_mol`` on the host and has checked it there."""
+    x_atoms, x_frags = _f32c(x_atoms, "x_atoms"), _f32c(x_frags, "x_frags")
+    dev = x_atoms.device
+    sa, sf = plan.segs["mol_atoms"], plan.segs["mol_frags"]
+    if x_atoms.shape != (sa.n_items, FN_D) or x_frags.shape != (sf.n_items, FN_D):
+        raise ValueError("pool_cat_groups: feature tables do not match the batch / frag_batch index")
+    for t, name, dtype, rows in ((atom_group, "atom_group", torch.int64, sa.n_items), (row_mol, "row_mol", torch.int32, None),
+                                 (row_group, "row_group", torch.int64, row_mol.shape[0] if torch.is_tensor(row_mol) else None)):
+        if not torch.is_tensor(t) or not t.is_cuda:
+            raise _lib.FragnetHipError(f"pool_cat_groups: {name} must be a GPU tensor; there is no CPU fallback")
+        if t.dtype != dtype or t.dim() != 1 or not t.is_contiguous() or t.device != dev or (rows is not None and t.shape[0] != rows):
+            raise ValueError(f"pool_cat_groups: {name} must be a contiguous {dtype} vector" + (f" of {rows} entries" if rows is not None else "")
+                             + f" on {dev}")
+    R = int(row_mol.shape[0])
+    out = torch.empty((R, 2 * FN_D), dtype=torch.float32, device=dev)
+    if R == 0:
+        return out
+    if check and bool(((row_mol < 0) | (row_mol >= sa.n_seg)).any()):
+        raise IndexError(f"pool_cat_groups: row_mol must lie in [0, {sa.n_seg}) (got {int(row_mol.min())} .. {int(row_mol.max())})")
+    a, f = _seg_struct(sa), _seg_struct(sf)
+    _lib.call("fn_pool_cat_groups_f32", x_atoms.data_ptr(), x_frags.data_ptr(), C.byref(a), C.byref(f), atom_group.data_ptr(),
+              row_mol.data_ptr(), row_group.data_ptr(), R, out.data_ptr(), _stream_ptr(dev))
+    return out
+
+
 class _MaskedMSE(torch.autograd.Function):
     """sum_i w_i |out_i - y_i|^2 / (sum_i w_i * T): loss and d loss / d out from one single-block kernel."""
 

@@ -634,6 +634,15 @@ int fn_edge_concat_f32(const float* x /*[N,128]*/, const float* e_attr /*[E,128]
 struct fn_seg_plan;
 int fn_pool_cat_f32(const float* x_atoms /*[N,128]*/, const float* x_frags /*[F,128]*/, const struct fn_seg_plan* mol_atoms,
                     const struct fn_seg_plan* mol_frags, float* out /*[B,256]*/, fn_stream_t stream);
+/* leave-group-out read-out (fragment contributions: fragnet/vizualize/model_attr.py masks a fragment's atom rows AFTER the encoder):
+ * out[r, 0:128] = sum of x_atoms[i, :] over the atoms i of molecule row_mol[r] with atom_group[i] != row_group[r] (row_group[r] < 0:
+ * every atom; an atom_group < 0 is in no group), out[r, 128:256] = that molecule's fragment sum.  Partition and order of additions are
+ * fn_pool_cat_f32's, a left-out atom enters as 0.0: a row that leaves nothing out is fn_pool_cat_f32's row of its molecule, a masked
+ * row is fn_pool_cat_f32's of the table with those rows overwritten by 0.0, bit for bit.  Rows in any order, molecules may repeat;
+ * R == 0 launches nothing.  row_mol must lie in [0, n_seg): the caller validates it (the kernel has no status word). */
+int fn_pool_cat_groups_f32(const float* x_atoms /*[N,128]*/, const float* x_frags /*[F,128]*/, const struct fn_seg_plan* mol_atoms,
+                           const struct fn_seg_plan* mol_frags, const int64_t* atom_group /*[N]*/, const int32_t* row_mol /*[R]*/,
+                           const int64_t* row_group /*[R]*/, int64_t R, float* out /*[R,256]*/, fn_stream_t stream);
 int fn_pool_cat_bwd_f32(const float* g /*[B,256]*/, const int64_t* batch /*[N]*/, const int64_t* frag_batch /*[F]*/,
                         float* g_atoms /*[N,128]*/, float* g_frags /*[F,128]*/, int64_t N, int64_t F, fn_stream_t stream);
 int fn_masked_mse_f32(const float* out /*[B,T]*/, const float* y /*[B,T]*/, const float* w /*[B]*/, int64_t B, int T,
