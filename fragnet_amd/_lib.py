@@ -224,16 +224,15 @@ SIGNATURES = {
     "fn_head_act_param_grad_f32": [vp, i64, vp, vp],
     "fn_cdrp_gene_fwd_f32": [vp, vp, vp, vp, i64, i64, i64, vp],
     "fn_cdrp_gene_bwd_f32": [vp, vp, vp, vp, vp, i64, i64, i64, vp],
-    "fn_cdrp_pair_loss_ws": [i64],
-    "fn_cdrp_pair_fwd_f32": [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, i64, i64, i64, i64, vp],
-    "fn_cdrp_pair_bwd_f32": [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, vp, i64, i64, i64, i64, i64, vp],
     "fn_dta_conv_fwd_f32": [vp, vp, vp, vp, vp, vp, i64, i64, i64, i64, i64, i64, vp],
     "fn_dta_conv_bwd_ws": [i64, i64, i64, i64],
     "fn_dta_conv_bwd_f32": [vp, vp, vp, vp, vp, vp, vp, vp, i64, i64, i64, i64, i64, i64, vp],
-    "fn_dta_pair_loss_ws": [i64],
-    "fn_dta_pair_fwd_f32": [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, i64, i64, i64, i64, vp],
-    "fn_dta_pair_bwd_f32": [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, vp, i64, i64, i64, i64, i64, vp],
 }
+# the pair heads of the CDRP and the DTA model: two instances of one kernel template (csrc/pair_head.hip), the same signatures
+for _fam in ("fn_cdrp_pair", "fn_dta_pair"):
+    SIGNATURES[_fam + "_loss_ws"] = [i64]
+    SIGNATURES[_fam + "_fwd_f32"] = [vp] * 11 + [i64] * 5 + [vp]
+    SIGNATURES[_fam + "_bwd_f32"] = [vp] * 13 + [i64, vp] + [i64] * 5 + [vp]
 
 _lib = None
 

@@ -8,10 +8,8 @@
 //         G[b, v, f, k] = sum_j g[b, f, j] E[v, j + k]        dW[f, c, k] = sum_b G[b, tok[b, c], f, k]        dbias[f] = sum_b sum_j g[b, f, j]
 //         dE[v, d]      = sum_b sum_f sum_k A[b, v, f, k] g[b, f, d - k]                   (terms with d - k outside [0, J) are absent)
 //     A token outside [0, V) falls into no bin and is gathered from nowhere: it never indexes memory.
-//   * the pair head fc2(fc1(cat(drug_enc, xt))) with nothing between the two Linears, 256 + 300 -> 128 -> 1, and the MSE loss on it:
-//     cdrp.hip's pair head at another width (300 = 18 x 16 + 12: the last MFMA step is masked) and WITHOUT the gate on the second half's
-//     gradient: xt is the output of a Linear, not of a ReLU.
-// Linear(F J, 300) between the two is fn_dense_fwd_f32 / fn_dense_bwd_f32 (dense_head.inc).
+// Linear(F J, 300) behind it is fn_dense_fwd_f32 / fn_dense_bwd_f32 (dense_head.inc); the pair head fc2(fc1(cat(drug_enc, xt))),
+// fn_dta_pair_*, is the <300, false> instance of pair_head.hip.
 // Arithmetic: fp32 in, fp32 accumulate, no atomics, every sum over positions, samples or rows in a fixed order.
 #include <stdint.h>
 
@@ -246,180 +244,6 @@ __global__ __launch_bounds__(256) void k_dta_combine(const float* __restrict__ d
     }
 }
 
-// ---- (f) the pair head, fixed widths: cdrp.hip's kernels with a second half of 300 columns and no gate
-constexpr int kIn0 = 256, kIn1 = 300, kInT = kIn0 + kIn1, kHid = 128, kPairRows = 16;
-
-// forward: h[M,128] = drug W1[:, :256]^T + xt W1[:, 256:]^T + b1 (saved), out[M] = h w2 + b2 and, with a target, g[M] = d MSE / d out
-// and one loss partial per workgroup (already divided by M: their sum in order IS the loss).  A workgroup = 16 rows, wave w the 32
-// columns [32 w, + 32) of h over the 556-long reduction: 16 full steps of the drug half, 18 full steps of the xt half and one of which
-// the last quarter (k = 300 .. 303) is masked.
-__device__ __forceinline__ void pair_step(const float* xp, const float* wp0, const float* wp1, bool ok, f32x4& acc0, f32x4& acc1) {
-    const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
-    const float4 a = ok ? ld4(xp) : z, p = ok ? ld4(wp0) : z, q = ok ? ld4(wp1) : z;
-    DN_MFMA(acc0, a.x, p.x);  DN_MFMA(acc1, a.x, q.x);
-    DN_MFMA(acc0, a.y, p.y);  DN_MFMA(acc1, a.y, q.y);
-    DN_MFMA(acc0, a.z, p.z);  DN_MFMA(acc1, a.z, q.z);
-    DN_MFMA(acc0, a.w, p.w);  DN_MFMA(acc1, a.w, q.w);
-}
-
-__global__ __launch_bounds__(256) void k_dta_pair_fwd(const float* __restrict__ drug, const float* __restrict__ xt,
-                                                      const float* __restrict__ W1, const float* __restrict__ b1,
-                                                      const float* __restrict__ w2, const float* __restrict__ b2,
-                                                      const float* __restrict__ target, float* __restrict__ h, float* __restrict__ out,
-                                                      float* __restrict__ g, float* __restrict__ loss_part, int M) {
-    __shared__ float sh[kPairRows][kHid + 1];
-    __shared__ float sd[kPairRows];
-    const int l = threadIdx.x & 63, n = l & 15, gq = l >> 4, wv = threadIdx.x >> 6;
-    const int i0 = blockIdx.x * kPairRows, j0 = wv * 32;
-    const int row = min(i0 + n, M - 1);
-    f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
-    {
-        const float* xp = drug + (size_t)row * kIn0 + 4 * gq;
-        const float* wp0 = W1 + (size_t)(j0 + n) * kInT + 4 * gq;
-        const float* wp1 = wp0 + (size_t)16 * kInT;
-#pragma unroll 4
-        for (int k0 = 0; k0 < kIn0; k0 += 16) pair_step(xp + k0, wp0 + k0, wp1 + k0, true, acc0, acc1);
-    }
-    {
-        const float* xp = xt + (size_t)row * kIn1 + 4 * gq;
-        const float* wp0 = W1 + (size_t)(j0 + n) * kInT + kIn0 + 4 * gq;
-        const float* wp1 = wp0 + (size_t)16 * kInT;
-        constexpr int kfull = kIn1 & ~15;
-#pragma unroll 2
-        for (int k0 = 0; k0 < kfull; k0 += 16) pair_step(xp + k0, wp0 + k0, wp1 + k0, true, acc0, acc1);
-        if (kfull < kIn1) pair_step(xp + kfull, wp0 + kfull, wp1 + kfull, kfull + 4 * gq < kIn1, acc0, acc1);
-    }
-#pragma unroll
-    for (int u = 0; u < 2; ++u) {
-        const int col = j0 + 16 * u + n;
-        const float bb = b1[col];
-        const f32x4 acc = u ? acc1 : acc0;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const int r = 4 * gq + e;
-            const float v = acc[e] + bb;
-            sh[r][col] = v;
-            if (i0 + r < M) h[(size_t)(i0 + r) * kHid + col] = v;
-        }
-    }
-    __syncthreads();
-    const int r = threadIdx.x >> 4, sub = threadIdx.x & 15;
-    float t = 0.f;
-#pragma unroll
-    for (int c = 0; c < kHid / 16; ++c) t = fmaf(sh[r][sub + 16 * c], w2[sub + 16 * c], t);
-    t += __shfl_xor(t, 8);  t += __shfl_xor(t, 4);  t += __shfl_xor(t, 2);  t += __shfl_xor(t, 1);
-    if (sub == 0) {
-        float d2 = 0.f;
-        if (i0 + r < M) {
-            const float o = t + b2[0];
-            out[i0 + r] = o;
-            if (target) {
-                const float d = o - target[i0 + r];
-                g[i0 + r] = 2.f * d / (float)M;
-                d2 = d * d;
-            }
-        }
-        sd[r] = d2;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0 && target) {
-        float s = sd[0];
-        for (int q = 1; q < kPairRows; ++q) s += sd[q];
-        loss_part[blockIdx.x] = s / (float)M;
-    }
-}
-
-// backward, one launch; d loss / d h = g w2^T has rank one (cdrp.hip):
-//   g_x[m, k] = g[m] v[k],  v = W1^T w2 [556] -- BOTH halves as they are: neither input is a ReLU output here
-//   dW1[c, k] = w2[c] u[k], u = [drug | xt]^T g [556],   db1[c] = w2[c] db2,   db2 = sum_m g[m],   dW2[c] = sum_m g[m] h[m, c]
-// Workgroups [0, row_blocks): 32 rows of g_drug / g_xt each; the next 35: 16 columns of u each (the last one 12) for all rows, then their
-// 128 x 16 block of dW1; the last: dW2, db2, db1 and, with loss != null, loss[0] = sum of the forward's partials.
-constexpr int kPairBwdRows = 32, kPairColBlocks = (kInT + 15) / 16;
-__global__ __launch_bounds__(256) void k_dta_pair_bwd(const float* __restrict__ g, const float* __restrict__ drug,
-                                                      const float* __restrict__ xt, const float* __restrict__ h,
-                                                      const float* __restrict__ W1, const float* __restrict__ w2,
-                                                      float* __restrict__ g_drug, float* __restrict__ g_xt, float* __restrict__ dW1,
-                                                      float* __restrict__ db1, float* __restrict__ dW2, float* __restrict__ db2,
-                                                      const float* __restrict__ loss_part, int n_part, float* __restrict__ loss, int M,
-                                                      int row_blocks) {
-    __shared__ __attribute__((aligned(16))) float sm[1024 + 16];            // v [556] / 64 x 4 float4 partials + their 16 sums / 8 x 128 partials
-    __shared__ float s1[8];
-    const int t = threadIdx.x, b = blockIdx.x;
-    if (b < row_blocks) {
-        for (int k = t; k < kInT; k += 256) {
-            float v = 0.f;
-#pragma unroll 8
-            for (int c = 0; c < kHid; ++c) v = fmaf(w2[c], W1[(size_t)c * kInT + k], v);
-            sm[k] = v;
-        }
-        __syncthreads();
-        const int m0 = b * kPairBwdRows;
-        for (int e = t; e < kPairBwdRows * (kInT / 4); e += 256) {
-            const int m = m0 + e / (kInT / 4), k = 4 * (e % (kInT / 4));
-            if (m >= M) break;
-            const float gm = g[m];
-            const float4 o = make_float4(gm * sm[k], gm * sm[k + 1], gm * sm[k + 2], gm * sm[k + 3]);
-            if (k < kIn0) st4(g_drug + (size_t)m * kIn0 + k, o);
-            else st4(g_xt + (size_t)m * kIn1 + (k - kIn0), o);
-        }
-        return;
-    }
-    if (b < row_blocks + kPairColBlocks) {
-        const int c4 = t & 3, rl = t >> 2;
-        const int col = (b - row_blocks) * 16 + 4 * c4;              // of [drug | xt]; 256 = 16 blocks: a block's columns lie in one half
-        const bool ok = col < kInT;
-        const float* x = col < kIn0 ? drug + col : xt + (col - kIn0);
-        const int ldx = col < kIn0 ? kIn0 : kIn1;
-        float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (ok)
-            for (int m = rl; m < M; m += 64) fma4(acc, g[m], ld4(x + (size_t)m * ldx));
-        st4(sm + 4 * (rl * 4 + c4), acc);
-        __syncthreads();
-        if (rl == 0) {
-            float4 s = ld4(sm + 4 * c4);
-            for (int q = 1; q < 64; ++q) { const float4 o = ld4(sm + 4 * (q * 4 + c4));  s.x += o.x;  s.y += o.y;  s.z += o.z;  s.w += o.w; }
-            st4(sm + 1024 + 4 * c4, s);
-        }
-        __syncthreads();
-        if (!ok) return;
-        const float4 u = ld4(sm + 1024 + 4 * c4);
-#pragma unroll
-        for (int rep = 0; rep < 2; ++rep) {
-            const int c = rl + 64 * rep;
-            const float w = w2[c];
-            st4(dW1 + (size_t)c * kInT + col, make_float4(w * u.x, w * u.y, w * u.z, w * u.w));
-        }
-        return;
-    }
-    {                                                                 // dW2: 32 float4 columns x 8 row lanes
-        const int c4 = t & 31, rl = t >> 5;
-        float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
-        for (int m = rl; m < M; m += 8) fma4(acc, g[m], ld4(h + (size_t)m * kHid + 4 * c4));
-        st4(sm + 4 * (rl * 32 + c4), acc);
-        const int lane = t & 63, wv = t >> 6;
-        if (wv == 0) {                                                // db2
-            float s = 0.f;
-            for (int m = lane; m < M; m += 64) s += g[m];
-            for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off);
-            if (lane == 0) s1[0] = s;
-        }
-        if (wv == 3 && loss) {                                        // the loss value: the forward left one partial per workgroup
-            float s = 0.f;
-            for (int i = lane; i < n_part; i += 64) s += loss_part[i];
-            for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off);
-            if (lane == 0) loss[0] = s;
-        }
-        __syncthreads();
-        if (t < kHid) {
-            float s = sm[t];
-            for (int q = 1; q < 8; ++q) s += sm[q * kHid + t];
-            dW2[t] = s;
-            db1[t] = w2[t] * s1[0];
-        }
-        if (t == 0) db2[0] = s1[0];
-    }
-}
-
 // ---- host side
 bool conv_instance_ok(int64_t V, int64_t F, int64_t KS) { return F == kF && KS == kKS && V >= 1 && V <= kVMax; }
 int conv_unsupported() {
@@ -427,17 +251,6 @@ int conv_unsupported() {
 }
 bool conv_dims_ok(int64_t M, int64_t L, int64_t D) { return M >= 0 && M <= FN_DENSE_MAX_ROWS && L >= 1 && L <= kLMax && D >= kDMin && D <= kDMax; }
 int conv_dims_bad(const char* what) { return fail(FN_EINVAL, what); }
-bool pair_widths_ok(int64_t Kd, int64_t Kx, int64_t H, int64_t C) { return Kd == kIn0 && Kx == kIn1 && H == kHid && C == 1; }
-int pair_unsupported() {
-    return fail(FN_EUNSUPPORTED, "fn_dta_pair_*_f32: the pair head is 256 + 300 -> 128 -> 1 (Kd = 256, Kx = 300, H = 128, C = 1); other widths are not built");
-}
-bool misaligned(unsigned mask, const void* a, const void* b = nullptr, const void* c = nullptr, const void* d = nullptr, const void* e = nullptr) {
-    return (((uintptr_t)a | (uintptr_t)b | (uintptr_t)c | (uintptr_t)d | (uintptr_t)e) & mask) != 0;
-}
-int zero_async(float* p, int64_t n, fn_stream_t stream, const char* where) {
-    if (hipMemsetAsync(p, 0, (size_t)n * sizeof(float), S(stream)) != hipSuccess) return launch_status(where);
-    return 0;
-}
 int64_t up4(int64_t n) { return (n + 3) & ~(int64_t)3; }
 int dw_parts(int64_t M) { return (int)((M + kDwRows - 1) / kDwRows < kDwPartsMax ? (M + kDwRows - 1) / kDwRows : kDwPartsMax); }
 }  // namespace
@@ -497,42 +310,5 @@ int fn_dta_conv_bwd_f32(const float* g_conv, const int64_t* tok, const float* E,
     hipLaunchKernelGGL(k_dta_combine, dim3((unsigned)(w_blocks + e_blocks + 1)), dim3(256), 0, S(stream), dW_part, parts, dW, w_quads, dE_part, dE,
                        e_elems, db_part, dbias, (int)M, w_blocks, e_blocks);
     return launch_status("fn_dta_conv_bwd_f32");
-}
-
-int64_t fn_dta_pair_loss_ws(int64_t M) { return M > 0 ? (M + kPairRows - 1) / kPairRows : 0; }
-
-int fn_dta_pair_fwd_f32(const float* drug, const float* xt, const float* W1, const float* b1, const float* w2, const float* b2,
-                        const float* target, float* h, float* out, float* g, float* loss_part, int64_t M, int64_t Kd, int64_t Kx, int64_t H,
-                        int64_t C, fn_stream_t stream) {
-    if (!pair_widths_ok(Kd, Kx, H, C)) return pair_unsupported();
-    if (M < 0 || M > FN_DENSE_MAX_ROWS) return fail(FN_EINVAL, "fn_dta_pair_fwd_f32: 0 <= M <= FN_DENSE_MAX_ROWS");
-    if (M == 0) return 0;
-    if (!drug || !xt || !W1 || !b1 || !w2 || !b2 || !h || !out || (target && (!g || !loss_part)) || misaligned(15, drug, xt, W1))
-        return fail(FN_EINVAL, "fn_dta_pair_fwd_f32: null or misaligned buffer");
-    hipLaunchKernelGGL(k_dta_pair_fwd, dim3((unsigned)fn_dta_pair_loss_ws(M)), dim3(256), 0, S(stream), drug, xt, W1, b1, w2, b2, target, h, out, g,
-                       loss_part, (int)M);
-    return launch_status("fn_dta_pair_fwd_f32");
-}
-
-int fn_dta_pair_bwd_f32(const float* g, const float* drug, const float* xt, const float* h, const float* W1, const float* w2, float* g_drug,
-                        float* g_xt, float* dW1, float* db1, float* dW2, float* db2, const float* loss_part, int64_t n_part, float* loss,
-                        int64_t M, int64_t Kd, int64_t Kx, int64_t H, int64_t C, fn_stream_t stream) {
-    if (!pair_widths_ok(Kd, Kx, H, C)) return pair_unsupported();
-    if (M < 0 || M > FN_DENSE_MAX_ROWS || n_part < 0 || n_part > INT32_MAX) return fail(FN_EINVAL, "fn_dta_pair_bwd_f32: 0 <= M <= FN_DENSE_MAX_ROWS");
-    if (!W1 || !w2 || !dW1 || !db1 || !dW2 || !db2 || (M > 0 && (!g || !drug || !xt || !h || !g_drug || !g_xt)) ||
-        (loss && n_part > 0 && !loss_part) || misaligned(15, drug, xt, h, g_drug, g_xt) || misaligned(15, dW1))
-        return fail(FN_EINVAL, "fn_dta_pair_bwd_f32: null or misaligned buffer");
-    if (M == 0) {                                         // no rows: the sums are empty
-        FN_TRY(zero_async(dW1, kHid * kInT, stream, "fn_dta_pair_bwd_f32 (no rows)"));
-        FN_TRY(zero_async(db1, kHid, stream, "fn_dta_pair_bwd_f32 (no rows)"));
-        FN_TRY(zero_async(dW2, kHid, stream, "fn_dta_pair_bwd_f32 (no rows)"));
-        FN_TRY(zero_async(db2, 1, stream, "fn_dta_pair_bwd_f32 (no rows)"));
-        if (loss) FN_TRY(zero_async(loss, 1, stream, "fn_dta_pair_bwd_f32 (no rows)"));
-        return 0;
-    }
-    const int row_blocks = (int)((M + kPairBwdRows - 1) / kPairBwdRows);
-    hipLaunchKernelGGL(k_dta_pair_bwd, dim3((unsigned)(row_blocks + kPairColBlocks + 1)), dim3(256), 0, S(stream), g, drug, xt, h, W1, w2, g_drug,
-                       g_xt, dW1, db1, dW2, db2, loss_part, (int)n_part, loss, (int)M, row_blocks);
-    return launch_status("fn_dta_pair_bwd_f32");
 }
 }  // extern "C"

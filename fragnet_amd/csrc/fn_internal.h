@@ -200,6 +200,16 @@ template <typename Kern> inline int allow_lds(Kern kern, size_t bytes) {
     if (e != hipSuccess) { (void)hipGetLastError(); return fni::fail((int)e, "hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed"); }
     return 0;
 }
+// n floats of zeros on the stream; where: the step's name in fn_last_error()
+inline int zero_async(float* p, int64_t n, fn_stream_t stream, const char* where) {
+    if (hipMemsetAsync(p, 0, (size_t)n * sizeof(float), S(stream)) != hipSuccess) return fni::launch_status(where);
+    return 0;
+}
+// whether one of up to five pointers (null: none) has a bit of `mask` set: 3 / 7 / 15 for 4- / 8- / 16-byte alignment
+inline bool misaligned(unsigned mask, const void* a, const void* b = nullptr, const void* c = nullptr, const void* d = nullptr,
+                       const void* e = nullptr) {
+    return (((uintptr_t)a | (uintptr_t)b | (uintptr_t)c | (uintptr_t)d | (uintptr_t)e) & mask) != 0;
+}
 // ---- which KIND of the attention forward (the O2 template argument of its kernels) a launch takes.  The comment above gat_fwd_rows
 // (gat_fwd.inc) is the one description of what each kind takes for granted; it calls the kind 2 / kind 3 conditions below
 // fwd_kind_tr() / fwd_kind_ev().  masked: the launch comes with a FwdMask; such a launch is kind 4 or does not exist (kFwdNoKind).

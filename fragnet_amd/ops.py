@@ -11,7 +11,7 @@ plus the fused per-level op the model uses (gat_level) and the small epilogues a
 from __future__ import annotations
 
 import ctypes as C
-from typing import Optional
+from typing import NamedTuple, Optional
 
 import os
 
@@ -1079,11 +1079,8 @@ def bond_graph(edge_index: torch.Tensor, atom_batch: torch.Tensor, n_mols: int, 
 
 
 # ======================================================================================
-# cancer drug response model (reference model/cdrp/model.py): the cell-line tower MLP(gene_dim) and the pair head, csrc/cdrp.hip
+# cancer drug response model (reference model/cdrp/model.py): the cell-line tower MLP(gene_dim), csrc/cdrp.hip, and the pair head, csrc/pair_head.hip
 # ======================================================================================
-PAIR_HEAD_SHAPES = ((128, 512), (1, 128))        # fc1, fc2: the widths fn_cdrp_pair_*_f32 is built for
-
-
 def _i64c(t: torch.Tensor, name: str) -> torch.Tensor:
     if not t.is_cuda:
         raise _lib.FragnetHipError(f"{name}: fragnet_amd kernels need GPU tensors (got {t.device}); there is no CPU fallback")
@@ -1204,22 +1201,40 @@ def cell_tower(gene_expr, linears):
     return _CellTower.apply(gene_expr, *[q for lin in linears for q in (lin.weight, lin.bias)])
 
 
+class _PairInstance(NamedTuple):
+    """One built instance of the pair-head kernels (csrc/pair_head.hip): 256 + ``width`` -> 128 -> 1."""
+    prefix: str          # entry points <prefix>_loss_ws, <prefix>_fwd_f32, <prefix>_bwd_f32
+    width: int           # of the second input
+    gated: bool          # the second input is the output of a ReLU: its gradient comes back zero where it is <= 0
+    name: str            # the public function, in error messages
+    second: str          # the second input, in error messages
+
+    @property
+    def shapes(self):    # fc1, fc2: the widths the entry points are built for
+        return (FN_D, 2 * FN_D + self.width), (1, FN_D)
+
+
+_PAIR_CDRP = _PairInstance("fn_cdrp_pair", 256, True, "pair_head", "cell_enc")
+_PAIR_DTA = _PairInstance("fn_dta_pair", 300, False, "pair_head_dta", "xt")
+
+
 class _PairHead(torch.autograd.Function):
-    """fc2(fc1(cat(drug_enc, cell_enc))) (model/cdrp/model.py:35-42; nothing between the two Linears) for 256 + 256 -> 128 -> 1: one launch
-    each way (fn_cdrp_pair_fwd_f32 / fn_cdrp_pair_bwd_f32), the two inputs read where they are.  With ``target`` the forward also leaves
-    d MSE / d out and the loss partials, and the node returns (out, loss): ``out`` then carries no gradient and the VALUE of ``loss`` is
-    complete once backward has run (its sum rides in the backward launch), as with ``_MLPHead``'s fused loss.  The gradient handed to
-    ``cell_enc`` is already through the backward of the ReLU that produced it (tagged ``_fn_relu_gated`` for ``_CellTower``; applying
-    that gate again, as a plain autograd ReLU would, changes nothing)."""
+    """fc2(fc1(cat(drug_enc, second))) (model/cdrp/model.py:35-42, model/dta/model.py:141-144; nothing between the two Linears) for
+    256 + ``inst.width`` -> 128 -> 1: one launch each way (<prefix>_fwd_f32 / <prefix>_bwd_f32), the two inputs read where they are.
+    With ``target`` the forward also leaves d MSE / d out and the loss partials, and the node returns (out, loss): ``out`` then carries
+    no gradient and the VALUE of ``loss`` is complete once backward has run (its sum rides in the backward launch), as with
+    ``_MLPHead``'s fused loss.  Where ``inst.gated`` (CDRP's ``cell_enc``) the gradient handed to the second input is already through the
+    backward of the ReLU that produced it (tagged ``_fn_relu_gated`` for ``_CellTower``; applying that gate again, as a plain autograd
+    ReLU would, changes nothing); otherwise (DTA's ``xt``, a Linear's output) it is NOT gated."""
 
     @staticmethod
-    def forward(ctx, drug, cell, target, W1, b1, w2, b2):
-        drug, cell = _f32c(drug, "drug_enc"), _f32c(cell, "cell_enc")
+    def forward(ctx, inst, drug, x1, target, W1, b1, w2, b2):
+        drug, x1 = _f32c(drug, "drug_enc"), _f32c(x1, inst.second)
         W1, b1, w2, b2 = (_f32c(q, "pair-head parameter") for q in (W1, b1, w2, b2))
         M, dev = drug.shape[0], drug.device
-        Kd, Kc, H, C_out = drug.shape[1], cell.shape[1], W1.shape[0], w2.shape[0]
-        if cell.shape[0] != M or W1.shape[1] != Kd + Kc or w2.shape[1] != H or b1.shape != (H,) or b2.shape != (C_out,):
-            raise ValueError("pair_head: drug_enc / cell_enc / fc1 / fc2 shapes do not fit together")
+        Kd, K1, H, C_out = drug.shape[1], x1.shape[1], W1.shape[0], w2.shape[0]
+        if x1.shape[0] != M or W1.shape[1] != Kd + K1 or w2.shape[1] != H or b1.shape != (H,) or b2.shape != (C_out,):
+            raise ValueError(f"{inst.name}: drug_enc / {inst.second} / fc1 / fc2 shapes do not fit together")
         st = _stream_ptr(dev)
         h = torch.empty((M, H), dtype=torch.float32, device=dev)
         out = torch.empty((M, C_out), dtype=torch.float32, device=dev)
@@ -1227,25 +1242,25 @@ class _PairHead(torch.autograd.Function):
         if target is not None:
             target = _f32c(target, "y").reshape(-1)
             if target.numel() != M * C_out:
-                raise ValueError(f"pair_head: {target.numel()} targets for {M} rows")
+                raise ValueError(f"{inst.name}: {target.numel()} targets for {M} rows")
             g = torch.empty(M, dtype=torch.float32, device=dev)
-            parts = torch.empty(_lib.load().fn_cdrp_pair_loss_ws(M), dtype=torch.float32, device=dev)
+            parts = torch.empty(getattr(_lib.load(), inst.prefix + "_loss_ws")(M), dtype=torch.float32, device=dev)
             loss_t = torch.empty((), dtype=torch.float32, device=dev)
-        _lib.call("fn_cdrp_pair_fwd_f32", drug.data_ptr(), cell.data_ptr(), W1.data_ptr(), b1.data_ptr(), w2.data_ptr(), b2.data_ptr(),
-                  _ptr(target), h.data_ptr(), out.data_ptr(), _ptr(g), _ptr(parts), M, Kd, Kc, H, C_out, st)
-        ctx.params, ctx.slots = (W1, b1, w2, b2), [grad_slot(q) for q in (W1, b1, w2, b2)]
+        _lib.call(inst.prefix + "_fwd_f32", drug.data_ptr(), x1.data_ptr(), W1.data_ptr(), b1.data_ptr(), w2.data_ptr(), b2.data_ptr(),
+                  _ptr(target), h.data_ptr(), out.data_ptr(), _ptr(g), _ptr(parts), M, Kd, K1, H, C_out, st)
+        ctx.inst, ctx.params, ctx.slots = inst, (W1, b1, w2, b2), [grad_slot(q) for q in (W1, b1, w2, b2)]
         ctx.fused = target is not None
         if ctx.fused:
-            ctx.save_for_backward(drug, cell, h, g, parts, loss_t)
+            ctx.save_for_backward(drug, x1, h, g, parts, loss_t)
             ctx.mark_non_differentiable(out)
             ctx.set_materialize_grads(False)
             return out, loss_t
-        ctx.save_for_backward(drug, cell, h)
+        ctx.save_for_backward(drug, x1, h)
         return out
 
     @staticmethod
     def backward(ctx, g_out, g_loss=None):
-        drug, cell, h = ctx.saved_tensors[:3]
+        drug, x1, h = ctx.saved_tensors[:3]
         M, dev = drug.shape[0], drug.device
         parts = loss_t = None
         if ctx.fused:
@@ -1257,13 +1272,35 @@ class _PairHead(torch.autograd.Function):
             g = _f32c(g_out, "g").reshape(-1)
         P, slots = ctx.params, ctx.slots
         dW1, db1, dW2, db2 = (grad_buffer(q, s) for q, s in zip(P, slots))
-        g_drug, g_cell = torch.empty_like(drug), torch.empty_like(cell)
-        _lib.call("fn_cdrp_pair_bwd_f32", g.data_ptr(), drug.data_ptr(), cell.data_ptr(), h.data_ptr(), P[0].data_ptr(), P[2].data_ptr(),
-                  g_drug.data_ptr(), g_cell.data_ptr(), dW1.data_ptr(), db1.data_ptr(), dW2.data_ptr(), db2.data_ptr(), _ptr(parts),
-                  0 if parts is None else parts.numel(), _ptr(loss_t), M, drug.shape[1], cell.shape[1], P[0].shape[0], P[2].shape[0],
+        g_drug, g_x1 = torch.empty_like(drug), torch.empty_like(x1)
+        _lib.call(ctx.inst.prefix + "_bwd_f32", g.data_ptr(), drug.data_ptr(), x1.data_ptr(), h.data_ptr(), P[0].data_ptr(), P[2].data_ptr(),
+                  g_drug.data_ptr(), g_x1.data_ptr(), dW1.data_ptr(), db1.data_ptr(), dW2.data_ptr(), db2.data_ptr(), _ptr(parts),
+                  0 if parts is None else parts.numel(), _ptr(loss_t), M, drug.shape[1], x1.shape[1], P[0].shape[0], P[2].shape[0],
                   _stream_ptr(dev))
-        g_cell._fn_relu_gated = cell
-        return (g_drug if ctx.needs_input_grad[0] else None, g_cell if ctx.needs_input_grad[1] else None, None, dW1, db1, dW2, db2)
+        if ctx.inst.gated:
+            g_x1._fn_relu_gated = x1
+        return (None, g_drug if ctx.needs_input_grad[1] else None, g_x1 if ctx.needs_input_grad[2] else None, None, dW1, db1, dW2, db2)
+
+
+def _pair_head(inst, drug_enc, x1, fc1, fc2, loss):
+    """``pair_head`` / ``pair_head_dta``: the instance is the caller's choice, never guessed from ``fc1``'s width -- whether the second
+    gradient is gated says where the second input came from."""
+    if not (drug_enc.is_cuda and x1.is_cuda):
+        raise _lib.FragnetHipError(f"{inst.name}: fragnet_amd kernels need GPU tensors; there is no CPU fallback")
+    ok = (tuple(fc1.weight.shape), tuple(fc2.weight.shape)) == inst.shapes and fc1.bias is not None and fc2.bias is not None \
+        and drug_enc.shape[1:] == (FN_D * 2,) and x1.shape[1:] == (inst.width,) and drug_enc.shape[0] <= DENSE_MAX_ROWS
+    if not ok:
+        out = fc2(fc1(torch.cat((drug_enc, x1), 1)))
+        return (out, None) if loss is not None else out
+    params = (fc1.weight, fc1.bias, fc2.weight, fc2.bias)
+    if loss is None:
+        return _PairHead.apply(inst, drug_enc, x1, None, *params)
+    kind, y, row_w = loss
+    fuse = FUSED_HEAD_LOSS and kind == _lib.LOSS_MSE and row_w is None and torch.is_grad_enabled() and drug_enc.shape[0] > 0 \
+        and (drug_enc.requires_grad or x1.requires_grad or any(q.requires_grad for q in params))
+    if not fuse:
+        return _PairHead.apply(inst, drug_enc, x1, None, *params), None
+    return _PairHead.apply(inst, drug_enc, x1, y, *params)
 
 
 def pair_head(drug_enc, cell_enc, fc1, fc2, loss=None):
@@ -1272,28 +1309,12 @@ def pair_head(drug_enc, cell_enc, fc1, fc2, loss=None):
     calls ``backward`` on the loss right away; returns ``(out, loss)`` with ``loss`` None where the fused launch does not apply (the caller
     then computes it from ``out``).  Other widths than 256 + 256 -> 128 -> 1, Linears without bias or more than ``DENSE_MAX_ROWS`` rows
     fall back to plain torch ops (``torch.cat`` + two library GEMMs)."""
-    if not (drug_enc.is_cuda and cell_enc.is_cuda):
-        raise _lib.FragnetHipError("pair_head: fragnet_amd kernels need GPU tensors; there is no CPU fallback")
-    ok = (tuple(fc1.weight.shape), tuple(fc2.weight.shape)) == PAIR_HEAD_SHAPES and fc1.bias is not None and fc2.bias is not None \
-        and drug_enc.shape[1:] == cell_enc.shape[1:] == (FN_D * 2,) and drug_enc.shape[0] <= DENSE_MAX_ROWS
-    if not ok:
-        out = fc2(fc1(torch.cat((drug_enc, cell_enc), 1)))
-        return (out, None) if loss is not None else out
-    params = (fc1.weight, fc1.bias, fc2.weight, fc2.bias)
-    if loss is None:
-        return _PairHead.apply(drug_enc, cell_enc, None, *params)
-    kind, y, row_w = loss
-    fuse = FUSED_HEAD_LOSS and kind == _lib.LOSS_MSE and row_w is None and torch.is_grad_enabled() and drug_enc.shape[0] > 0 \
-        and (drug_enc.requires_grad or cell_enc.requires_grad or any(q.requires_grad for q in params))
-    if not fuse:
-        return _PairHead.apply(drug_enc, cell_enc, None, *params), None
-    return _PairHead.apply(drug_enc, cell_enc, y, *params)
+    return _pair_head(_PAIR_CDRP, drug_enc, cell_enc, fc1, fc2, loss)
 
 
 # ======================================================================================
-# drug-target affinity model (reference model/dta/model.py, DTAModel2): the protein tower and the pair head 256 + 300, csrc/dta.hip
+# drug-target affinity model (reference model/dta/model.py, DTAModel2): the protein tower, csrc/dta.hip, and the pair head 256 + 300, csrc/pair_head.hip
 # ======================================================================================
-DTA_PAIR_HEAD_SHAPES = ((128, 556), (1, 128))    # fc1, fc2: the widths fn_dta_pair_*_f32 is built for
 DTA_CONV_FILTERS, DTA_CONV_KS, DTA_CONV_MAX_V, DTA_CONV_MAX_L, DTA_CONV_MAX_D = 32, 8, 32, 4096, 512      # fn_dta_conv_*_f32's instance / limits
 
 
@@ -1369,82 +1390,8 @@ def protein_tower(tokens, embedding, conv, fc):
     return _ProteinTower.apply(tokens, embedding.weight, conv.weight, conv.bias, fc.weight, fc.bias)
 
 
-class _PairHeadDTA(torch.autograd.Function):
-    """fc2(fc1(cat(drug_enc, xt))) (model/dta/model.py:141-144; nothing between the two Linears) for 256 + 300 -> 128 -> 1: one launch each
-    way (fn_dta_pair_fwd_f32 / fn_dta_pair_bwd_f32), the two inputs read where they are.  The fused-loss convention is ``_PairHead``'s:
-    with ``target`` the node returns (out, loss), ``out`` carries no gradient and the VALUE of ``loss`` is complete once backward has
-    run.  Unlike ``_PairHead`` the gradient of the second input is NOT gated: ``xt`` is a Linear's output."""
-
-    @staticmethod
-    def forward(ctx, drug, xt, target, W1, b1, w2, b2):
-        drug, xt = _f32c(drug, "drug_enc"), _f32c(xt, "xt")
-        W1, b1, w2, b2 = (_f32c(q, "pair-head parameter") for q in (W1, b1, w2, b2))
-        M, dev = drug.shape[0], drug.device
-        Kd, Kx, H, C_out = drug.shape[1], xt.shape[1], W1.shape[0], w2.shape[0]
-        if xt.shape[0] != M or W1.shape[1] != Kd + Kx or w2.shape[1] != H or b1.shape != (H,) or b2.shape != (C_out,):
-            raise ValueError("pair_head_dta: drug_enc / xt / fc1 / fc2 shapes do not fit together")
-        st = _stream_ptr(dev)
-        h = torch.empty((M, H), dtype=torch.float32, device=dev)
-        out = torch.empty((M, C_out), dtype=torch.float32, device=dev)
-        g = parts = loss_t = None
-        if target is not None:
-            target = _f32c(target, "y").reshape(-1)
-            if target.numel() != M * C_out:
-                raise ValueError(f"pair_head_dta: {target.numel()} targets for {M} rows")
-            g = torch.empty(M, dtype=torch.float32, device=dev)
-            parts = torch.empty(_lib.load().fn_dta_pair_loss_ws(M), dtype=torch.float32, device=dev)
-            loss_t = torch.empty((), dtype=torch.float32, device=dev)
-        _lib.call("fn_dta_pair_fwd_f32", drug.data_ptr(), xt.data_ptr(), W1.data_ptr(), b1.data_ptr(), w2.data_ptr(), b2.data_ptr(),
-                  _ptr(target), h.data_ptr(), out.data_ptr(), _ptr(g), _ptr(parts), M, Kd, Kx, H, C_out, st)
-        ctx.params, ctx.slots = (W1, b1, w2, b2), [grad_slot(q) for q in (W1, b1, w2, b2)]
-        ctx.fused = target is not None
-        if ctx.fused:
-            ctx.save_for_backward(drug, xt, h, g, parts, loss_t)
-            ctx.mark_non_differentiable(out)
-            ctx.set_materialize_grads(False)
-            return out, loss_t
-        ctx.save_for_backward(drug, xt, h)
-        return out
-
-    @staticmethod
-    def backward(ctx, g_out, g_loss=None):
-        drug, xt, h = ctx.saved_tensors[:3]
-        M, dev = drug.shape[0], drug.device
-        parts = loss_t = None
-        if ctx.fused:
-            g, parts, loss_t = ctx.saved_tensors[3:]
-            unit = _UNIT_GRAD.get(dev)
-            if g_loss is not None and not (unit is not None and g_loss.data_ptr() == unit.data_ptr()):
-                g = g * g_loss
-        else:
-            g = _f32c(g_out, "g").reshape(-1)
-        P, slots = ctx.params, ctx.slots
-        dW1, db1, dW2, db2 = (grad_buffer(q, s) for q, s in zip(P, slots))
-        g_drug, g_xt = torch.empty_like(drug), torch.empty_like(xt)
-        _lib.call("fn_dta_pair_bwd_f32", g.data_ptr(), drug.data_ptr(), xt.data_ptr(), h.data_ptr(), P[0].data_ptr(), P[2].data_ptr(),
-                  g_drug.data_ptr(), g_xt.data_ptr(), dW1.data_ptr(), db1.data_ptr(), dW2.data_ptr(), db2.data_ptr(), _ptr(parts),
-                  0 if parts is None else parts.numel(), _ptr(loss_t), M, drug.shape[1], xt.shape[1], P[0].shape[0], P[2].shape[0],
-                  _stream_ptr(dev))
-        return (g_drug if ctx.needs_input_grad[0] else None, g_xt if ctx.needs_input_grad[1] else None, None, dW1, db1, dW2, db2)
-
-
 def pair_head_dta(drug_enc, xt, fc1, fc2, loss=None):
-    """``fc2(fc1(cat(drug_enc, xt)))`` as ``_PairHeadDTA``; ``loss = (_lib.LOSS_MSE, y, None)`` as for ``pair_head``: returns
+    """``fc2(fc1(cat(drug_enc, xt)))`` as ``_PairHead``, not gated (``xt`` is a Linear's output); ``loss = (_lib.LOSS_MSE, y, None)`` as for ``pair_head``: returns
     ``(out, loss)`` with ``loss`` None where the fused launch does not apply.  Other widths than 256 + 300 -> 128 -> 1, Linears without
     bias or more than ``DENSE_MAX_ROWS`` rows fall back to plain torch ops (``torch.cat`` + two library GEMMs)."""
-    if not (drug_enc.is_cuda and xt.is_cuda):
-        raise _lib.FragnetHipError("pair_head_dta: fragnet_amd kernels need GPU tensors; there is no CPU fallback")
-    ok = (tuple(fc1.weight.shape), tuple(fc2.weight.shape)) == DTA_PAIR_HEAD_SHAPES and fc1.bias is not None and fc2.bias is not None \
-        and drug_enc.shape[1:] == (FN_D * 2,) and xt.shape[1:] == (DTA_PAIR_HEAD_SHAPES[0][1] - FN_D * 2,) and drug_enc.shape[0] <= DENSE_MAX_ROWS
-    if not ok:
-        out = fc2(fc1(torch.cat((drug_enc, xt), 1)))
-        return (out, None) if loss is not None else out
-    params = (fc1.weight, fc1.bias, fc2.weight, fc2.bias)
-    if loss is None:
-        return _PairHeadDTA.apply(drug_enc, xt, None, *params)
-    kind, y, row_w = loss
-    fuse = FUSED_HEAD_LOSS and kind == _lib.LOSS_MSE and row_w is None and torch.is_grad_enabled() and drug_enc.shape[0] > 0 \
-        and (drug_enc.requires_grad or xt.requires_grad or any(q.requires_grad for q in params))
-    if not fuse:
-        return _PairHeadDTA.apply(drug_enc, xt, None, *params), None
-    return _PairHeadDTA.apply(drug_enc, xt, y, *params)
+    return _pair_head(_PAIR_DTA, drug_enc, xt, fc1, fc2, loss)

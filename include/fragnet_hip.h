@@ -861,7 +861,8 @@ int fn_encoder_backward(const fn_encoder* e, const float* out_atoms, const float
 
 /* ------------------------------------------------------------------------------------------
  * Cancer drug response model, CDRP (reference model/cdrp/model.py: CDRPModel = FragNet encoder + MLP(gene_dim) cell-line tower + the
- * pair head fc2(fc1(cat(drug_enc, cell_enc)))); csrc/cdrp.hip.  Entry points added under ABI 12 (nothing existing changes).
+ * pair head fc2(fc1(cat(drug_enc, cell_enc)))); csrc/cdrp.hip, the pair head csrc/pair_head.hip.  Entry points added under ABI 12
+ * (nothing existing changes).
  * fp32 accumulate on the fp32 matrix cores, no atomics, sums over rows in a fixed order.  M <= FN_DENSE_MAX_ROWS throughout; M = 0 is
  * legal: the forward calls launch nothing, the backward calls write zeros to the weight-gradient outputs.
  *   fn_cdrp_gene_fwd_f32   Y[M,N] = relu(float(G[M,K]) W[N,K]^T + bias): the tower's first Linear on the int64 rows collate_fn_cdrp
@@ -883,6 +884,9 @@ int fn_encoder_backward(const fn_encoder* e, const float* out_atoms, const float
  *                          fixed order.  One launch.
  * The pair head is built for the reference's widths only, Kd = Kc = 256, H = 128, C = 1: anything else returns FN_EUNSUPPORTED (with the
  * reason in fn_last_error) before anything is launched or written.  drug, cell, h, W1, g_drug, g_cell, dW1: 16-byte aligned.
+ * fn_cdrp_pair_* and fn_dta_pair_* (below) are the two instances of ONE kernel template (csrc/pair_head.hip), <second width, gate> =
+ * <256, true> and <300, false>: the same arguments, checks, tile shapes and order of operations; they differ in the second input's width
+ * and in whether its gradient is gated, in nothing else.
  * ------------------------------------------------------------------------------------------ */
 int fn_cdrp_gene_fwd_f32(const int64_t* G, const float* W, const float* bias /*nullable*/, float* Y, int64_t M, int64_t K, int64_t N,
                          fn_stream_t stream);
@@ -900,9 +904,9 @@ int fn_cdrp_pair_bwd_f32(const float* g, const float* drug, const float* cell, c
 /* ------------------------------------------------------------------------------------------
  * Drug-target affinity model, DTA (reference model/dta/model.py: DTAModel2 = FragNet encoder + protein tower Embedding(V, D) ->
  * Conv1d(L -> F, KS) along the embedding axis -> Linear(F J, 300), J = D - KS + 1, no activation anywhere -> the pair head
- * fc2(fc1(cat(drug_enc, xt)))); csrc/dta.hip.  Entry points added under ABI 12 (nothing existing changes).  fp32 accumulate, no atomics,
- * every sum over positions, samples or rows in a fixed order.  M <= FN_DENSE_MAX_ROWS throughout; M = 0 is legal: the forward calls
- * launch nothing, the backward calls write zeros to the gradient outputs.
+ * fc2(fc1(cat(drug_enc, xt)))); csrc/dta.hip, the pair head csrc/pair_head.hip.  Entry points added under ABI 12 (nothing existing
+ * changes).  fp32 accumulate, no atomics, every sum over positions, samples or rows in a fixed order.  M <= FN_DENSE_MAX_ROWS
+ * throughout; M = 0 is legal: the forward calls launch nothing, the backward calls write zeros to the gradient outputs.
  * The convolution runs in its histogram form (the layer is linear in the V-row table E):
  *     A[b, v, f, k] = sum of W[f, c, k] over the positions c with tok[b, c] = v;   conv[b, f, j] = bias[f] + sum_v sum_k A[b, v, f, k] E[v, j + k]
  *   fn_dta_conv_fwd_f32    tok[M,L] int64 (what collate_fn_dta produces), E[V,D], W[F,L,KS], bias[F] -> conv[M, F J], laid out as the
@@ -918,9 +922,9 @@ int fn_cdrp_pair_bwd_f32(const float* g, const float* drug, const float* cell, c
  * A token outside [0, V) is never used to index memory: it falls into no bin (its position contributes nothing to conv) and its
  * dW[:, c, :] terms are absent (0 from every sample that has such a token there).  torch raises instead; collate_fn_dta checks on the host.
  *   fn_dta_pair_fwd_f32 / fn_dta_pair_bwd_f32 / fn_dta_pair_loss_ws
- *                          the pair head as fn_cdrp_pair_*_f32, same arguments and contract, for Kd = 256, Kx = 300, H = 128, C = 1 (W1
- *                          [128, 556]; 300 = 18 x 16 + 12: the reduction's tail is masked) with ONE difference: g_xt[M,300] is NOT gated --
- *                          xt is the output of a Linear, not of a ReLU.  Other widths: FN_EUNSUPPORTED.  drug, xt, h, W1, g_drug, g_xt,
+ *                          the <300, false> instance of the pair head (fn_cdrp_pair_*_f32 above is <256, true>), same arguments and
+ *                          contract, for Kd = 256, Kx = 300, H = 128, C = 1 (W1 [128, 556]; 300 = 18 x 16 + 12: the reduction's tail is
+ *                          masked) with ONE difference: g_xt[M,300] is NOT gated -- xt is the output of a Linear, not of a ReLU.  Other widths: FN_EUNSUPPORTED.  drug, xt, h, W1, g_drug, g_xt,
  *                          dW1: 16-byte aligned.
  * ------------------------------------------------------------------------------------------ */
 int fn_dta_conv_fwd_f32(const int64_t* tok, const float* E, const float* W, const float* bias, float* A, float* conv, int64_t M, int64_t L,
