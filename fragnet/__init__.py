@@ -6,6 +6,7 @@
     fragnet.model.gat.gat2_lite       FragNetFineTune                    (finetune_gat2.py:144)
     fragnet.model.gat.gat2_edge       FragNetFineTune                    (finetune_gat2.py:166)
     fragnet.model.gat.gat2_pretrain   FragNetPreTrain                    (finetune_gat2.py:216)
+    fragnet.model.gcn.gcn2            FragNetFineTune, FragNet, FragNetLayer (finetune_gat2.py:102, model_version gcn2)
     fragnet.model.gat.pretrain_heads  FragNetPreTrain, PretrainTask      (pretrain_gat2.py:12)
     fragnet.dataset.data              collate_fn, collate_fn_pt          (finetune_gat2.py:6, pretrain_gat2.py:15)
     fragnet.dataset.dataset           load_pickle_dataset, load_data_parts (finetune_gat2.py:2, pretrain_gat2.py:6)
@@ -19,6 +20,6 @@
     fragnet.train.finetune.trainer_dta      TrainerFineTune              (finetune_dta.py:9)
     fragnet.vizualize.model           FragNetViz, FragNetFineTuneViz, FragNetFineTuneBaseViz, FragNetPreTrainViz (vizualize/viz.py)
 
-Model versions outside the accelerated hot path (masked pretraining heads, gcn / gat v1, DTA's transformer tower; SURVEY.md section 2 rows
+Model versions outside the accelerated hot path (masked pretraining heads, gcn.py / gcn3.py / gat v1, DTA's transformer tower; SURVEY.md section 2 rows
 10-19) are named here only to fail with a clear message when constructed.
 """

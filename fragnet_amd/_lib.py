@@ -227,6 +227,8 @@ SIGNATURES = {
     "fn_dta_conv_fwd_f32": [vp, vp, vp, vp, vp, vp, i64, i64, i64, i64, i64, i64, vp],
     "fn_dta_conv_bwd_ws": [i64, i64, i64, i64],
     "fn_dta_conv_bwd_f32": [vp, vp, vp, vp, vp, vp, vp, vp, i64, i64, i64, i64, i64, i64, vp],
+    "fn_gcn_coef_f32": [C.POINTER(GatPlan), vp, vp],
+    "fn_gcn_aggregate_f32": [vp, C.POINTER(GatPlan), C.c_int, vp, vp, C.POINTER(ActEpilogue), vp],
 }
 # the pair heads of the CDRP and the DTA model: two instances of one kernel template (csrc/pair_head.hip), the same signatures
 for _fam in ("fn_cdrp_pair", "fn_dta_pair"):

@@ -1395,3 +1395,143 @@ def pair_head_dta(drug_enc, xt, fc1, fc2, loss=None):
     ``(out, loss)`` with ``loss`` None where the fused launch does not apply.  Other widths than 256 + 300 -> 128 -> 1, Linears without
     bias or more than ``DENSE_MAX_ROWS`` rows fall back to plain torch ops (``torch.cat`` + two library GEMMs)."""
     return _pair_head(_PAIR_DTA, drug_enc, xt, fc1, fc2, loss)
+
+
+# ======================================================================================
+# graph-convolution baseline (reference model/gcn/gcn2.py, model_version gcn2): the degree-normalised neighbour sum, csrc/gcn.hip, and the
+# fragment MLP on the dense kernels
+# ======================================================================================
+def gcn_coef(level: Level) -> torch.Tensor:
+    """deg^-1/2 per node of ``level`` (gcn2.py:51-53: out-degree of the graph with self loops, 0 where it is 0), from the row extents of
+    the level's by-source CSR.  The same table for every layer and both directions: callers compute it once per batch."""
+    dev = level.keep[0].device
+    coef = torch.empty(level.n, dtype=torch.float32, device=dev)
+    _lib.call("fn_gcn_coef_f32", C.byref(level.c), coef.data_ptr(), _stream_ptr(dev))
+    return coef
+
+
+class _GcnAggregate(torch.autograd.Function):
+    """y[i] = c[i] sum_{k in seg(i)} c[nbr(k)] x[nbr(k)] over ``level``'s by-destination CSR (fn_gcn_aggregate_f32), optionally with
+    relu?(dropout(.)) as the launch's epilogue.  Returns the raw rows, the activated rows, or both (raw, activated).  Backward: the
+    gradient of the activated rows goes through fn_dropout_act_bwd_f32 first (the saved output gates the ReLU), the raw rows' gradient is
+    added to it, and ONE launch of the same kernel on the by-source CSR gathers the sum (the weight c[s] c[t] is symmetric)."""
+
+    @staticmethod
+    def forward(ctx, x, coef, level: Level, want_raw: bool, epi):
+        x = _f32c(x, "x")
+        n = level.n
+        if x.shape != (n, FN_D):
+            raise ValueError(f"gcn_aggregate: x must be [{n}, {FN_D}], got {tuple(x.shape)}")
+        if coef is not None:
+            coef = _f32c(coef, "coef")
+            if coef.shape != (n,) or coef.device != x.device:
+                raise ValueError(f"gcn_aggregate: coef must be [{n}] on {x.device}, got {tuple(coef.shape)} on {coef.device}")
+        if not want_raw and epi is None:
+            raise ValueError("gcn_aggregate: neither the raw nor the activated rows were asked for")
+        dev = x.device
+        out = torch.empty((n, FN_D), dtype=torch.float32, device=dev) if want_raw else None
+        y = act = None
+        if epi is not None:
+            p, relu, seed, offset, rdev = epi
+            y = torch.empty((n, FN_D), dtype=torch.float32, device=dev)
+            act = _lib.ActEpilogue(y.data_ptr(), float(p), int(relu), seed, offset, _ptr(rdev) if p > 0.0 else None)
+        _lib.call("fn_gcn_aggregate_f32", x.data_ptr(), C.byref(level.c), 0, _ptr(coef), _ptr(out), None if act is None else C.byref(act),
+                  _stream_ptr(dev))
+        ctx.level, ctx.epi, ctx.coef, ctx.want_raw = level, epi, coef, want_raw
+        if epi is not None and epi[1]:
+            ctx.save_for_backward(y)
+        ctx.set_materialize_grads(False)
+        if want_raw and epi is not None:
+            return out, y
+        return out if want_raw else y
+
+    @staticmethod
+    def backward(ctx, *gs):
+        level, epi, coef = ctx.level, ctx.epi, ctx.coef
+        g_raw = gs[0] if ctx.want_raw else None
+        g_act = gs[-1] if epi is not None else None
+        if g_raw is None and g_act is None:
+            return None, None, None, None, None
+        g = None if g_raw is None else _f32c(g_raw, "g_out")
+        dev = (g if g is not None else g_act).device
+        st = _stream_ptr(dev)
+        if g_act is not None:
+            p, relu, seed, offset, rdev = epi
+            g_act = _f32c(g_act, "g_y")
+            y = ctx.saved_tensors[0] if relu else None
+            gated = torch.empty_like(g_act)
+            _lib.call("fn_dropout_act_bwd_f32", g_act.data_ptr(), _ptr(y), gated.data_ptr(), g_act.numel(), float(p), seed, offset,
+                      _ptr(rdev) if p > 0.0 else None, int(relu), st)
+            g = gated if g is None else gated.add_(g)      # both outputs were read (the last layer): autograd's own accumulation, done here
+        g_x = torch.empty((level.n, FN_D), dtype=torch.float32, device=dev)
+        _lib.call("fn_gcn_aggregate_f32", g.data_ptr(), C.byref(level.c), 1, _ptr(coef), g_x.data_ptr(), None, st)
+        return g_x, None, None, None, None
+
+
+def gcn_aggregate(x, level: Level, coef=None, act=None, raw=None):
+    """The graph convolution's neighbour sum on ``level`` (a plan level: the atom graph with its loop items, or the fragment graph).
+    ``coef``: ``gcn_coef(level)`` for the normalised form, None for the plain sum.  ``act = (p, training, relu, rng)``: also apply
+    relu?(dropout(.)) in the same launch, drawing from the Philox stream ``rng`` like ``dropout_act``.  ``raw`` (default: True without
+    ``act``, False with it): return the rows before the activation; with both, the result is (raw, activated)."""
+    if not x.is_cuda:
+        raise _lib.FragnetHipError(f"gcn_aggregate: fragnet_amd kernels need GPU tensors (got {x.device}); there is no CPU fallback")
+    epi = None
+    if act is not None:
+        p, training, relu, rng = act
+        p_eff = float(p) if training else 0.0
+        if not 0.0 <= p_eff <= 1.0:
+            raise ValueError(f"gcn_aggregate: dropout probability {p_eff} outside [0, 1]")
+        if p_eff > 0.0 or relu:
+            seed, off = rng.take(level.n * FN_D) if p_eff > 0.0 else (0, 0)
+            epi = (p_eff, bool(relu), seed, off, rng.dev if p_eff > 0.0 else None)
+    want_raw = bool(raw) if raw is not None else epi is None
+    if epi is None:
+        want_raw = True
+    return _GcnAggregate.apply(x, coef, level, want_raw, epi)
+
+
+class _FragMLP(torch.autograd.Function):
+    """Linear(K -> H) -> ReLU -> Linear(H -> N) (gcn2.py:26-28, ``frag_mlp``) on the dense kernels: fn_dense_fwd_f32 with the ReLU epilogue
+    at p = 0, then without one; backward top-down with fn_dense_bwd_f32 (gate_scale = 1 hands the hidden layer its gradient through its
+    ReLU), as ``_CellTower``."""
+
+    @staticmethod
+    def forward(ctx, x, W1, b1, W2, b2):
+        x = _f32c(x, "x")
+        W1, b1, W2, b2 = (_f32c(q, "frag_mlp parameter") for q in (W1, b1, W2, b2))
+        M, dev, st = x.shape[0], x.device, _stream_ptr(x.device)
+        h = torch.empty((M, W1.shape[0]), dtype=torch.float32, device=dev)
+        y = torch.empty((M, W2.shape[0]), dtype=torch.float32, device=dev)
+        if M:
+            act = _lib.ActEpilogue(h.data_ptr(), 0.0, 1, 0, 0, None)
+            _lib.call("fn_dense_fwd_f32", x.data_ptr(), W1.data_ptr(), b1.data_ptr(), h.data_ptr(), M, W1.shape[1], W1.shape[0], C.byref(act), st)
+            _lib.call("fn_dense_fwd_f32", h.data_ptr(), W2.data_ptr(), b2.data_ptr(), y.data_ptr(), M, W2.shape[1], W2.shape[0], None, st)
+        ctx.params, ctx.slots = (W1, b1, W2, b2), [grad_slot(q) for q in (W1, b1, W2, b2)]
+        ctx.save_for_backward(x, h)
+        return y
+
+    @staticmethod
+    def backward(ctx, g):
+        x, h = ctx.saved_tensors
+        g = _f32c(g, "g")
+        (W1, b1, W2, b2), slots = ctx.params, ctx.slots
+        dW1, db1, dW2, db2 = (grad_buffer(q, s) for q, s in zip(ctx.params, slots))
+        M, st = x.shape[0], _stream_ptr(x.device)
+        g_h = torch.empty_like(h)
+        _lib.call("fn_dense_bwd_f32", g.data_ptr(), h.data_ptr(), W2.data_ptr(), g_h.data_ptr(), 1.0, dW2.data_ptr(), db2.data_ptr(), M, W2.shape[1],
+                  W2.shape[0], M, st)
+        g_x = torch.empty_like(x) if ctx.needs_input_grad[0] else None
+        _lib.call("fn_dense_bwd_f32", g_h.data_ptr(), x.data_ptr(), W1.data_ptr(), _ptr(g_x), 0.0, dW1.data_ptr(), db1.data_ptr(), M, W1.shape[1],
+                  W1.shape[0], M, st)
+        return g_x, dW1, db1, dW2, db2
+
+
+def frag_mlp(x, lin1, lin2):
+    """``lin2(relu(lin1(x)))`` as ``_FragMLP``.  More than ``DENSE_MAX_ROWS`` rows, a Linear without bias or widths that are not multiples
+    of 4 fall back to plain torch ops (library GEMMs), the way ``mlp_head`` and ``cell_tower`` treat tall inputs."""
+    if not x.is_cuda:
+        raise _lib.FragnetHipError(f"frag_mlp: fragnet_amd kernels need GPU tensors (got {x.device}); there is no CPU fallback")
+    rows = x.shape[0]
+    if lin1.bias is None or lin2.bias is None or not (_dense_ok(rows, lin1.weight) and _dense_ok(rows, lin2.weight)):
+        return torch.nn.functional.linear(torch.relu(torch.nn.functional.linear(x, lin1.weight, lin1.bias)), lin2.weight, lin2.bias)
+    return _FragMLP.apply(x, lin1.weight, lin1.bias, lin2.weight, lin2.bias)

@@ -279,6 +279,32 @@ class GraphPlan:
         return plan
 
     @classmethod
+    def gcn_specs(cls, batch: Dict[str, torch.Tensor], n_mols: int) -> List[dict]:
+        """The CSR tasks model_version gcn2 reads (gcn2.py:48-65, 187-188): the atom graph with its self loops, the fragment graph,
+        the atom -> fragment sum and the two molecule-membership sums of the read-out.  No bond-graph and no fragment-bond-graph task:
+        those hold most of a batch's items and this model never looks at them."""
+        N, F = batch["x_atoms"].shape[0], batch["x_frags"].shape[0]
+        ei, fi = batch["edge_index"], batch["frag_index"]
+        return [
+            dict(kind="gat", name="atom", dst=ei[1], src=ei[0], n=N, n_loops=N),
+            dict(kind="gat", name="frag", dst=fi[1], src=fi[0], n=F, n_loops=0),
+            dict(kind="seg", name="a2f", key=batch["atom_to_frag_ids"], n_seg=F),
+            dict(kind="seg", name="mol_atoms", key=batch["batch"], n_seg=n_mols),
+            dict(kind="seg", name="mol_frags", key=batch["frag_batch"], n_seg=n_mols),
+        ]
+
+    @classmethod
+    def for_gcn(cls, batch: Dict[str, torch.Tensor], n_mols: Optional[int] = None):
+        """The reduced plan of model_version gcn2 (``gcn_specs``), built by the general builder (fn_plan_build)."""
+        if n_mols is None:
+            n_mols = batch["y"].shape[0] if "y" in batch else int(batch["batch"].max()) + 1
+        plan = cls(cls.gcn_specs(batch, n_mols), batch["x_atoms"].device)
+        plan.n_mols = n_mols
+        plan.mol_contiguous = bool(getattr(batch, "mol_contiguous", False))
+        plan.real_mols = None
+        return plan
+
+    @classmethod
     def segments_only(cls, index: torch.Tensor, n_seg: int):
         plan = cls([dict(kind="seg", name="s", key=index, n_seg=n_seg)], index.device)
         return plan
@@ -358,4 +384,16 @@ def plan_for(batch: Dict[str, torch.Tensor], edge_ends: bool = False) -> GraphPl
     if plan is None or (edge_ends and "edge_src" not in plan.segs):
         plan = GraphPlan.from_batch(batch, edge_ends=edge_ends)
         batch[PLAN_KEY] = plan
+    return plan
+
+
+GCN_PLAN_KEY = "_fragnet_gcn_plan"
+
+
+def gcn_plan_for(batch: Dict[str, torch.Tensor]) -> GraphPlan:
+    """``GraphPlan.for_gcn`` of the batch, cached on the batch dict under a key of its own (the full plan's key stays the full plan's)."""
+    plan = batch.get(GCN_PLAN_KEY)
+    if plan is None:
+        plan = GraphPlan.for_gcn(batch)
+        batch[GCN_PLAN_KEY] = plan
     return plan

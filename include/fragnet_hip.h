@@ -941,6 +941,25 @@ int fn_dta_pair_bwd_f32(const float* g, const float* drug, const float* xt, cons
                         float* g_drug, float* g_xt, float* dW1, float* db1, float* dW2, float* db2, const float* loss_part /*nullable*/,
                         int64_t n_part, float* loss /*nullable*/, int64_t M, int64_t Kd, int64_t Kx, int64_t H, int64_t C, fn_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Graph-convolution baseline, model_version gcn2 (reference model/gcn/gcn2.py:48-65); csrc/gcn.hip.  Entry points added under ABI 12
+ * (nothing existing changes).  The aggregate is a degree-normalised neighbour sum over one of a level's two CSRs:
+ *     y[i] = c[i] * sum over the items k of row i, in plan order, of c[nbr(k)] * x[nbr(k)]
+ *   fn_gcn_coef_f32        c[i] = (extent of row i in the level's by-SOURCE CSR)^-1/2, 0 where the extent is 0: the reference's
+ *                          degree(source) of the graph with self loops (the plan's loop items are counted), gcn2.py:51-53.  Once per
+ *                          batch: the table is the same for every layer and both directions.
+ *   fn_gcn_aggregate_f32   by_source = 0: rows are destinations, items the in-edges (rowptr_d, src_d, the loop item last) -- the forward;
+ *                          by_source = 1: rows are sources, items the out-edges (rowptr_s, dst_s) -- the backward of the former, since
+ *                          the weight c[s] c[t] is symmetric.  coef NULL: all ones (the fragment graph: gcn2.py:61-65).  out (nullable):
+ *                          the raw rows; act (nullable, with act->y): y = relu?(dropout(raw)) on the Philox stream of fn_dropout_act_f32
+ *                          over the [n,128] elements, so fn_dropout_act_bwd_f32 is its backward.  At least one of the two outputs.  A row
+ *                          without items is written as zeros.  Items are added in plan order (ascending edge id), no atomics: results are
+ *                          reproducible bit for bit.  x, out, y: [n,128], 16-byte aligned, x distinct from the outputs; n <= 2^23.
+ * ------------------------------------------------------------------------------------------ */
+int fn_gcn_coef_f32(const fn_gat_plan* plan, float* coef /*[n]*/, fn_stream_t stream);
+int fn_gcn_aggregate_f32(const float* x, const fn_gat_plan* plan, int by_source, const float* coef /*nullable*/, float* out /*nullable*/,
+                         const fn_act_epilogue* act /*nullable*/, fn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

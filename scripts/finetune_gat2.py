@@ -33,13 +33,22 @@ if __name__ == "__main__":
     exp_dir = args["exp_dir"]
     os.makedirs(exp_dir, exist_ok=True)
     ft, m = args.finetune, args.finetune.model
-    if args.model_version not in ("gat2", "gat2_lite", "gat2_edge"):
-        raise SystemExit("model_version gat2, gat2_lite and gat2_edge are on the accelerated path")
-    model = FragNetFineTune(n_classes=m.n_classes, atom_features=args.atom_features, frag_features=args.frag_features,
-                            edge_features=args.edge_features, num_layer=m.num_layer, drop_ratio=m.drop_ratio,
-                            num_heads=m.num_heads, emb_dim=m.emb_dim, h1=m.h1, h2=m.h2, h3=m.h3, h4=m.h4, act=m.act,
-                            fthead=m.fthead, variant=args.model_version)
+    if args.model_version not in ("gat2", "gat2_lite", "gat2_edge", "gcn2"):
+        raise SystemExit("model_version gat2, gat2_lite, gat2_edge and gcn2 are on the accelerated path")
+    gcn = args.model_version == "gcn2"
+    if gcn:      # finetune_gat2.py:99-117: the graph-convolution baseline takes no num_heads
+        from fragnet_amd.gcn import FragNetFineTune as FragNetFineTuneGCN
+        model = FragNetFineTuneGCN(n_classes=m.n_classes, atom_features=args.atom_features, frag_features=args.frag_features,
+                                   edge_features=args.edge_features, num_layer=m.num_layer, drop_ratio=m.drop_ratio,
+                                   emb_dim=m.emb_dim, h1=m.h1, h2=m.h2, h3=m.h3, h4=m.h4, act=m.act, fthead=m.fthead)
+    else:
+        model = FragNetFineTune(n_classes=m.n_classes, atom_features=args.atom_features, frag_features=args.frag_features,
+                                edge_features=args.edge_features, num_layer=m.num_layer, drop_ratio=m.drop_ratio,
+                                num_heads=m.num_heads, emb_dim=m.emb_dim, h1=m.h1, h2=m.h2, h3=m.h3, h4=m.h4, act=m.act,
+                                fthead=m.fthead, variant=args.model_version)
     pt = args.pretrain
+    if gcn and pt.get("chkpoint_name") and os.path.exists(str(pt.chkpoint_name)):
+        raise SystemExit("model_version gcn2: no pretrained encoder to load (gcn2.py's own FragNetPreTrain is not on the accelerated path)")
     if pt.get("chkpoint_name") and os.path.exists(str(pt.chkpoint_name)):
         modelpt = FragNetPreTrain(num_layer=pt.num_layer, drop_ratio=pt.drop_ratio, num_heads=pt.num_heads, emb_dim=pt.emb_dim,
                                   atom_features=args.atom_features, frag_features=args.frag_features,
@@ -59,7 +68,7 @@ if __name__ == "__main__":
     # whole-step hipGraph over static shapes (fragnet_amd/graphstep.py); `finetune.graph_step: false` in the YAML keeps
     # the launch-by-launch step (then only the prediction head is graph-captured)
     graph_step = None
-    if ft.get("graph_step", True) and ft.target_type in ("regr", "clsf"):
+    if not gcn and ft.get("graph_step", True) and ft.target_type in ("regr", "clsf"):      # (the captured step is the gat2 engine's: gcn2 takes the eager step)
         from fragnet_amd import graphstep
         sample = [probe] + [b for _, b in zip(range(7), iter(train_loader))]
         shapes = graphstep.StaticShapes.from_batches(sample, margin=0.05, heads=m.num_heads)
