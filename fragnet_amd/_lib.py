@@ -139,6 +139,18 @@ class AttnReadout(C.Structure):
     _fields_ = [("atoms", vp), ("frags", vp), ("bonds", vp), ("fbonds", vp)]
 
 
+FN_MAX_DX_TASKS = 3
+
+
+class LinearDxTask(C.Structure):
+    _fields_ = [("g", vp), ("W", vp), ("dx", vp), ("delta", vp), ("dots", vp), ("M", i64), ("K", i32), ("pad_", i32)]
+
+
+class InputGrads(C.Structure):
+    _fields_ = [("dx_atoms", vp), ("dx_bonds", vp), ("dx_fbonds", vp), ("delta_atoms", vp), ("delta_bonds", vp), ("delta_fbonds", vp),
+                ("dots_atoms", vp), ("dots_bonds", vp), ("dots_fbonds", vp)]
+
+
 STATUS_BAD_REPLICA = 8      # FN_STATUS_BAD_REPLICA
 
 
@@ -176,6 +188,7 @@ SIGNATURES = {
     "fn_linear128_f32": [vp, C.c_int, vp, vp, vp, i64, C.POINTER(ActEpilogue), vp],
     "fn_linear128_wgrad_ws": [i64, C.c_int],
     "fn_linear128_wgrad_f32": [vp, vp, C.c_int, i64, vp, vp, vp, vp],
+    "fn_linear_dx_f32": [C.POINTER(LinearDxTask), C.c_int, vp],
     "fn_encoder_fused_tail": [C.POINTER(Encoder)],
     "fn_encoder_ws_floats": [C.POINTER(Encoder)],
     "fn_encoder_bwd_ws_floats": [C.POINTER(Encoder)],
@@ -185,6 +198,7 @@ SIGNATURES = {
     "fn_encoder_forward_attn": [C.POINTER(Encoder), C.POINTER(AttnReadout), vp, vp, vp, vp, vp],
     "fn_loo_row_masks_u8": [vp, i64, vp, vp, vp, vp, i64, vp, i64, vp, i64, vp, vp],
     "fn_encoder_backward": [C.POINTER(Encoder), vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(LayerWeights), vp, i64, vp],
+    "fn_encoder_backward_inputs": [C.POINTER(Encoder), vp, i64, C.POINTER(InputGrads), vp],
     "fn_segment_sum_f32": [vp, i64, vp, vp, i32, vp, i64, i64, i64, vp],
     "fn_gather_rows_f32": [vp, vp, vp, i64, i64, vp],
     "fn_segment_softmax_f32": [vp, vp, vp, i32, vp, i64, i64, vp],

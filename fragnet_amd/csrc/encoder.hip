@@ -2283,6 +2283,32 @@ int fn_encoder_backward(const fn_encoder* e, const float* out_atoms, const float
     return rq.flush(true);
 }
 
+// the three layer-0 rows of the scratch fn_encoder_backward left behind, times the three layer-0 weights: one launch (input_grad.hip)
+int fn_encoder_backward_inputs(const fn_encoder* e, const float* scratch, int64_t scratch_floats, const fn_input_grads* in, fn_stream_t st) {
+    FN_TRY(enc_check(e));
+    if (!scratch || !in) return fail(FN_EINVAL, "fn_encoder_backward_inputs: null argument");
+    if (e->variant == 2) return fail(FN_EUNSUPPORTED, "fn_encoder_backward_inputs: input gradients exist for variants 0 (gat2) and 1 (gat2_lite), not for gat2_edge");
+    if (e->variant == 1 && (in->dx_fbonds || in->dots_fbonds))
+        return fail(FN_EINVAL, "fn_encoder_backward_inputs: gat2_lite has no fragment-bond level (dx_fbonds / dots_fbonds must be null)");
+    if (e->training && e->drop_p > 0.f)
+        return fail(FN_EUNSUPPORTED, "fn_encoder_backward_inputs: a training pass with drop_p > 0 (the input dropout's gate on x_atoms would have to be replayed)");
+    if (!e->training && e->no_backward != 0)
+        return fail(FN_EINVAL, "fn_encoder_backward_inputs: the forward pass of this descriptor saved nothing for a backward pass (fn_encoder.no_backward)");
+    if (!form_matches_forward(e))
+        return fail(FN_EINVAL, "fn_encoder_backward_inputs: FN_TUNE_BWD_ONE / FN_TUNE_DEFER_GSD changed since the forward pass that wrote this workspace");
+    if (defer_on(e, 0))
+        return fail(FN_EUNSUPPORTED, "fn_encoder_backward_inputs: the deferred backward form of layer 0 (FN_TUNE_DEFER_GSD = 1) leaves the g_s_dst a_dst term out of the rows this call reads");
+    const BwdLayout bw = bwd_layout(e, const_cast<float*>(scratch));
+    if (bw.total > scratch_floats) return fail(FN_EINVAL, "fn_encoder_backward_inputs: scratch too small");
+    const fn_layer_weights& w0 = e->w[0];
+    const fn_linear_dx_task tasks[FN_MAX_DX_TASKS] = {
+        {bw.atom[0].g_h, w0.proj_a_w, in->dx_atoms, in->delta_atoms, in->dots_atoms, e->N, e->k_atom0, 0},
+        {bw.bond[0].g_h, w0.proj_b_w, in->dx_bonds, in->delta_bonds, in->dots_bonds, e->E, e->k_bond0, 0},
+        {bw.fbond[0].g_h, w0.proj_fb_w, in->dx_fbonds, in->delta_fbonds, in->dots_fbonds, e->variant == 1 ? 0 : e->EF, e->k_fbond0, 0},
+    };
+    return fni::launch_linear_dx(tasks, FN_MAX_DX_TASKS, S(st));
+}
+
 // ---- the operator entry points of the kernel families that live in this unit
 int fn_gat_bwd_src_f32(const float* g_out, const float* h, const float* pz_src,
                        const float* g_s_dst, const float* att, int att_w, int dst_off, int src_off,

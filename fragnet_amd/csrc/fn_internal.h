@@ -186,6 +186,8 @@ struct AttnReadoutTask {
     const int32_t* n_real;
 };
 FNI_HIDDEN int launch_attn_readout(const AttnReadoutTask* tasks, int n_tasks, int heads, hipStream_t st);
+// input_grad.hip: up to FN_MAX_DX_TASKS products dx = g W (+ row dots with a caller table) in ONE launch; fn_linear_dx_f32 itself
+FNI_HIDDEN int launch_linear_dx(const fn_linear_dx_task* tasks, int n_tasks, hipStream_t st);
 FNI_HIDDEN int prof_event(int i, hipStream_t st);                             // records event i of fn_debug_set_profile_events, if set
 FNI_HIDDEN bool bad_edge_term(const fn_edge_term* et, int64_t m);
 }  // namespace fni

@@ -145,7 +145,10 @@ class _EncoderFn(torch.autograd.Function):
         for l in range(n_layers):
             for k, name in enumerate(LAYER_FIELDS):
                 setattr(gw[l], name, grads[l * NP + k].data_ptr())
-        scratch = torch.empty(lib.fn_encoder_bwd_ws_floats(C.byref(e)), dtype=torch.float32, device=dev)
+        # gradients of the three input tables (layer 0's projections, fn_encoder_backward_inputs): only where one is asked for.  The
+        # scratch is then zero-filled: a level no gradient reaches is not written by the pass, and its input gradient is zero
+        need_in = tuple(ctx.needs_input_grad[:3])
+        scratch = (torch.zeros if any(need_in) else torch.empty)(lib.fn_encoder_bwd_ws_floats(C.byref(e)), dtype=torch.float32, device=dev)
         rider = take_adam_rider()                # an optimiser slice that rides in this pass's last launch (arm_adam_rider)
         e.adam_rider = None if rider is None else C.addressof(rider)
         if rider is not None:
@@ -159,6 +162,7 @@ class _EncoderFn(torch.autograd.Function):
             if rider is not None:
                 _ADAM_RIDER[1] = bool(rider.launched)        # the library's word that a launch carried the slice, not ours that we offered it
         e.g_pooled = None
+        g_in = _input_grads(ctx, e, scratch, need_in, dev) if any(need_in) else (None, None, None)
         out = []
         have_frags = gs[1] is not None or g_pooled is not None
         any_grad = have_frags or any(g is not None for g in gs)
@@ -170,7 +174,58 @@ class _EncoderFn(torch.autograd.Function):
                 if ctx.variant == 2 and (k in EDGE_DEAD or (k in EDGE_LAST_ONLY and not (l == n_layers - 1 and have_frags))):
                     live = False
                 out.append(grads[l * NP + k] if live else None)
-        return (None,) * 16 + tuple(out)
+        return tuple(g_in) + (None,) * 13 + tuple(out)
+
+
+def _input_grads(ctx, e, scratch, need, dev):
+    """The second C call of a backward pass whose inputs require a gradient: dL/d(x_atoms), dL/d(bond nodes), dL/d(fragment-bond
+    nodes) in one launch.  With deltas armed (arm_input_dots) the launch writes the row dots <gradient, delta> instead, and the
+    tables themselves only when the armer asked to keep them."""
+    lite = ctx.variant == 1
+    xs = ctx.keep[1:4]
+    armed = take_input_dots_request()
+    deltas, keep = (armed if armed is not None else ((None, None, None), True))
+    live = [bool(n) and not (k == 2 and lite) for k, n in enumerate(need)]        # gat2_lite never reads the fragment-bond nodes
+    dx = [torch.empty_like(x) if (lv and keep) else None for x, lv in zip(xs, live)]
+    dots = [torch.empty(x.shape[0], dtype=torch.float32, device=dev) if (lv and d is not None) else None for x, lv, d in zip(xs, live, deltas)]
+    for x, d, name in zip(xs, deltas, ("x_atoms", "node_features_bonds", "node_features_fbonds")):
+        if d is not None and (d.shape != x.shape or d.device != x.device or d.dtype != torch.float32 or not d.is_contiguous()):
+            raise ValueError(f"arm_input_dots: the delta of {name} must be a contiguous float32 tensor of shape {tuple(x.shape)} on {x.device}")
+    ptr = lambda ts: [None if t is None or t.numel() == 0 else t.data_ptr() for t in ts]
+    ig = _lib.InputGrads(*ptr(dx), *ptr([d if o is not None else None for d, o in zip(deltas, dots)]), *ptr(dots))
+    _lib.check(_lib.load().fn_encoder_backward_inputs(C.byref(e), scratch.data_ptr(), scratch.numel(), C.byref(ig), _stream_ptr(dev)),
+               "fn_encoder_backward_inputs")
+    if armed is not None:
+        _INPUT_DOTS[1] = tuple(dots)
+    return tuple(dx)
+
+
+_INPUT_DOTS = [None, None]        # [armed (deltas, keep_dx), the dots of the backward pass that took them]
+
+
+def arm_input_dots(deltas, keep_dx: bool = False) -> None:
+    """The next encoder backward pass of this process whose inputs require a gradient also writes, per row of each input table with a
+    delta, ``dots[m] = sum_k grad[m, k] * delta[m, k]`` (ascending k, in the launch that forms the gradient: fn_linear_dx_task.dots).
+    ``deltas``: (atoms [N, Ka], bond nodes [E, Kb], fragment-bond nodes [EF, Kf]), each a contiguous float32 tensor or None.
+    ``keep_dx=False``: the gradient tables themselves are not written, and the inputs' ``.grad`` stays None.  ``take_input_dots()``
+    hands the result out.  Per process, like arm_adam_rider."""
+    if len(deltas) != 3:
+        raise ValueError("arm_input_dots: a triple (atoms, bond nodes, fragment-bond nodes)")
+    _INPUT_DOTS[0], _INPUT_DOTS[1] = (tuple(deltas), bool(keep_dx)), None
+
+
+def take_input_dots_request():
+    r = _INPUT_DOTS[0]
+    _INPUT_DOTS[0] = None
+    return r
+
+
+def take_input_dots():
+    """The (atoms, bond nodes, fragment-bond nodes) row dots of the backward pass that followed arm_input_dots -- None where there was
+    no delta or no gradient -- or None if no such pass ran; disarms either way."""
+    d = _INPUT_DOTS[1]
+    _INPUT_DOTS[0], _INPUT_DOTS[1] = None, None
+    return d
 
 
 _ADAM_RIDER = [None, False]       # [armed fn_adam_slice, was it handed to a backward pass]
@@ -313,6 +368,13 @@ def encoder_forward(layers, plan: GraphPlan, x_atoms, bond_nodes, fbond_nodes, c
         return _masked_forward(plan, x_atoms, bond_nodes, fbond_nodes, cos_sorted, fattr_sorted, params, len(layers), heads, int(variant),
                                bool(edge_outputs), row_masks)
     p_eff = float(drop_p) if training else 0.0
+    if torch.is_grad_enabled() and any(t.requires_grad for t in (x_atoms, bond_nodes, fbond_nodes)):
+        # input gradients (fn_encoder_backward_inputs): refused here, before the forward, where the backward could not serve them
+        if int(variant) == 2:
+            raise NotImplementedError("input gradients: the engine differentiates its inputs for gat2 and gat2_lite, not for gat2_edge")
+        if p_eff > 0.0:
+            raise NotImplementedError("input gradients: a training pass with dropout (drop_ratio > 0) gates x_atoms with a mask the backward "
+                                      "would have to replay from the Philox stream; use eval() or drop_ratio = 0")
     if p_eff > 0.0:
         # reserve the Philox offsets the engine will consume (fn_encoder_rng_blocks): x_atoms + 4 tensors per layer
         N, E = x_atoms.shape[0], bond_nodes.shape[0]

@@ -66,10 +66,10 @@ def _two_layer(width: int) -> nn.Sequential:
 
 def _project(x, lin: nn.Linear):
     """``lin(x)`` for the 128-wide node projections (gat2.py:138,186,241): the hand-written fp32-MFMA kernel with its own
-    backward (ops.linear128) wherever it applies -- GPU rows, 128 outputs, K <= 168, an input gradient only for K == 128 --
+    backward (ops.linear128) wherever it applies -- GPU rows, 128 outputs, K <= 168, input gradient included --
     so that the per-level path (return_attentions, masks, per-op tests) issues no library GEMM either."""
     w = lin.weight
-    if x.is_cuda and lin.bias is not None and w.shape[0] == FN_D and w.shape[1] <= 168 and (w.shape[1] == FN_D or not x.requires_grad):
+    if x.is_cuda and lin.bias is not None and w.shape[0] == FN_D and w.shape[1] <= 168:
         return ops.linear128(x, w, lin.bias)
     return F.linear(x, w, lin.bias)
 

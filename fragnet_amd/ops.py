@@ -226,7 +226,8 @@ def row_dots_sorted(feat, A, off: int, level: Level):
 # node projections on the fp32 matrix cores
 # ======================================================================================
 class _Linear128(torch.autograd.Function):
-    """y = x @ W.T + b with W [128, K] (nn.Linear(K, 128)); K <= 168.  Input gradient only for K == 128."""
+    """y = x @ W.T + b with W [128, K] (nn.Linear(K, 128)); K <= 168.  The input gradient is the K = 128 product kernel at K == 128
+    (layers >= 1) and the ragged-width product of csrc/input_grad.hip (linear_dx) at every other K (layer 0)."""
 
     @staticmethod
     def forward(ctx, x, weight, bias):
@@ -251,10 +252,11 @@ class _Linear128(torch.autograd.Function):
         st = _stream_ptr(x.device)
         gx = None
         if ctx.x_needs_grad:
-            if K != FN_D:
-                raise NotImplementedError("linear128: input gradient is implemented for K == 128 (layers >= 1)")
             gx = torch.empty_like(x)
-            _lib.call("fn_linear128_f32", g.data_ptr(), FN_D, weight.data_ptr(), None, gx.data_ptr(), M, None, st)
+            if K != FN_D:
+                linear_dx([(g, weight, gx, None, None)])
+            else:
+                _lib.call("fn_linear128_f32", g.data_ptr(), FN_D, weight.data_ptr(), None, gx.data_ptr(), M, None, st)
         ws = torch.empty(_lib.load().fn_linear128_wgrad_ws(M, K), dtype=torch.float32, device=x.device)
         gw = torch.empty_like(weight)
         gb = torch.empty(FN_D, dtype=torch.float32, device=x.device)
@@ -264,6 +266,37 @@ class _Linear128(torch.autograd.Function):
 
 def linear128(x, weight, bias):
     return _Linear128.apply(x, weight, bias)
+
+
+def linear_dx(tasks) -> None:
+    """Up to three products ``dx = g @ W`` in one launch (fn_linear_dx_f32): the input gradient of ``nn.Linear(K, 128)`` for any
+    1 <= K <= 168.  A task is ``(g [M, 128], W [128, K], dx_out, delta, dots_out)``: ``dx_out`` (None, or a contiguous float32 tensor
+    of at least M * K elements) receives the rows unpadded, ``dots_out`` (None, or at least M elements) receives
+    ``sum_k dx[m, k] * delta[m, k]`` in ascending k for the caller's ``delta [M, K]``.  Nothing past M * K / M elements is written."""
+    if not 1 <= len(tasks) <= _lib.FN_MAX_DX_TASKS:
+        raise ValueError(f"linear_dx: 1 to {_lib.FN_MAX_DX_TASKS} tasks")
+    arr = (_lib.LinearDxTask * len(tasks))()
+    keep = []
+    dev = None
+    for i, (g, W, dx, delta, dots) in enumerate(tasks):
+        g, W = _f32c(g, "g"), _f32c(W, "weight")
+        if g.dim() != 2 or g.shape[1] != FN_D or W.dim() != 2 or W.shape[0] != FN_D:
+            raise ValueError("linear_dx: g must be [M, 128] and weight [128, K]")
+        M, K = g.shape[0], W.shape[1]
+        if delta is not None:
+            delta = _f32c(delta, "delta")
+            if tuple(delta.shape) != (M, K):
+                raise ValueError(f"linear_dx: delta must be [{M}, {K}]")
+        if dots is not None and delta is None:
+            raise ValueError("linear_dx: dots needs a delta table")
+        for out, need, name in ((dx, M * K, "dx_out"), (dots, M, "dots_out")):
+            if out is not None and (not out.is_cuda or out.dtype != torch.float32 or not out.is_contiguous() or out.numel() < need):
+                raise ValueError(f"linear_dx: {name} must be a contiguous float32 GPU tensor of at least {need} elements")
+        dev = g.device
+        keep.append((g, W, delta))
+        arr[i] = _lib.LinearDxTask(_ptr(g) if M else None, _ptr(W), _ptr(dx) if M else None, _ptr(delta) if M else None,
+                                   _ptr(dots) if M else None, M, K, 0)
+    _lib.call("fn_linear_dx_f32", arr, len(tasks), _stream_ptr(dev))
 
 
 # ======================================================================================

@@ -398,6 +398,26 @@ int fn_linear128_f32(const float* X, int K, const float* Bt, const float* bias /
 int64_t fn_linear128_wgrad_ws(int64_t M, int K);
 int fn_linear128_wgrad_f32(const float* dY, const float* X, int K, int64_t M, float* ws, float* dW, float* db,
                            fn_stream_t stream);
+/* The input gradient of the layer-0 projections (csrc/input_grad.hip), what autograd returns for the INPUT of projection_b(bond nodes),
+ * projection_a(x_atoms) and projection_fb(fragment-bond nodes) at gat2.py:138, 186, 241 (nn.Linear: dL/dx = dL/dy W):
+ *   dx[m, k] = sum_j g[m, j] W[j, k]      g [M,128] = dL/d(projection output), 16-byte aligned; W [128,K] the Linear's weight as stored;
+ *                                         1 <= K <= 168 (anything else: FN_EUNSUPPORTED); a dx row is K floats, element-aligned, unpadded
+ *   dots[m]  = sum_k dx[m, k] delta[m, k] in ascending k, delta [M,K] the caller's table: gradient x input (delta = x) or integrated
+ *                                         gradients' (x - x0) . grad, without dx in memory
+ * dx and dots are each nullable (a task with neither, or with M = 0, launches nothing); dots needs delta.  Up to FN_MAX_DX_TASKS tasks
+ * are ONE launch.  fp32 in, fp32 accumulate on the fp32 matrix cores, no atomics; every output element is a sum in a fixed order that
+ * does not depend on the grid: two runs agree bit for bit.  Added under ABI 12 (nothing existing changes). */
+#define FN_MAX_DX_TASKS 3
+typedef struct fn_linear_dx_task {
+    const float* g;            /* [M,128] */
+    const float* W;            /* [128,K] */
+    float* dx;                 /* [M,K], nullable */
+    const float* delta;        /* [M,K], nullable when dots is */
+    float* dots;               /* [M], nullable */
+    int64_t M;
+    int32_t K, pad_;
+} fn_linear_dx_task;
+int fn_linear_dx_f32(const fn_linear_dx_task* tasks, int n_tasks, fn_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
  * torch_scatter.scatter_add / scatter_softmax along dim 0 on a CSR built by fn_plan_build
@@ -858,6 +878,28 @@ int fn_encoder_backward(const fn_encoder* e, const float* out_atoms, const float
                         const float* out_fbond, const float* g_atoms, const float* g_frags, const float* g_bond,
                         const float* g_fbond, const fn_layer_weights* grads /*[n_layers]*/, float* scratch,
                         int64_t scratch_floats, fn_stream_t stream);
+/* Gradients with respect to the encoder's three INPUT feature tables, after fn_encoder_backward: x_atoms feeds projection_a only
+ * (gat2.py:186), the bond nodes projection_b (gat2.py:138), the fragment-bond nodes projection_fb (gat2.py:241) -- all of layer 0, whose
+ * dL/d(projection output) rows fn_encoder_backward leaves in its scratch (per layer and level, never reused).  This call multiplies them
+ * by the three weights in ONE launch (fn_linear_dx_f32's kernel).  e / scratch / scratch_floats: those of the fn_encoder_backward call
+ * that precedes it on the same stream, untouched in between.  in: up to three dx tables and up to three (delta, dots) pairs as in
+ * fn_linear_dx_task, every pointer nullable (all NULL: nothing is launched).
+ * A separate call and not an argument of fn_encoder_backward: that call's signature, launches and bits stay what they were for every
+ * caller that differentiates the parameters only.
+ * Rows of a level the backward pass did not reach (no gradient arrived there) are not written by it: a caller that cannot rule that out
+ * hands fn_encoder_backward a zero-filled scratch, and reads zeros here.
+ * Refused before anything is launched: variant 2, gat2_edge (FN_EUNSUPPORTED); fragment-bond outputs with variant 1, gat2_lite, which has
+ * no fragment-bond level (FN_EINVAL); a training pass with drop_p > 0 (FN_EUNSUPPORTED: the input dropout's gate on x_atoms, gat2.py:396,
+ * would have to be replayed); a descriptor whose evaluation forward ran with no_backward (FN_EINVAL); the deferred backward form of layer 0
+ * (FN_TUNE_DEFER_GSD = 1: its rows lack the g_s_dst a_dst term, FN_EUNSUPPORTED -- the mixed form, 2, keeps layer 0 complete and is
+ * served); FN_TUNE_BWD_ONE / FN_TUNE_DEFER_GSD changed since the forward (FN_EINVAL).  Added under ABI 12. */
+typedef struct fn_input_grads {
+    float *dx_atoms /*[N,k_atom0]*/, *dx_bonds /*[E,k_bond0]*/, *dx_fbonds /*[EF,k_fbond0]*/;
+    const float *delta_atoms, *delta_bonds, *delta_fbonds;     /* same shapes */
+    float *dots_atoms /*[N]*/, *dots_bonds /*[E]*/, *dots_fbonds /*[EF]*/;
+} fn_input_grads;
+int fn_encoder_backward_inputs(const fn_encoder* e, const float* scratch, int64_t scratch_floats, const fn_input_grads* in,
+                               fn_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
  * Cancer drug response model, CDRP (reference model/cdrp/model.py: CDRPModel = FragNet encoder + MLP(gene_dim) cell-line tower + the
