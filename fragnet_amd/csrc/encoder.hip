@@ -942,18 +942,32 @@ struct Bump {
     }
 };
 
-struct LayerActs {           // kept from forward for backward
-    float *h_b, *h_a, *h_fb, *frags, *new_bond, *new_fbond, *p_bond, *p_atom, *p_fbond, *p_frag;
-    float *y_atoms, *y_frags, *y_bond, *y_fbond;    // post dropout+ReLU outputs (null for the last layer: caller's buffers)
-    // one-pass backward (FN_TUNE_BWD_ONE, training): the forward's second output rows and their weight sums, per level
-    float *o2_bond, *o2_atom, *o2_fbond, *sg_bond, *sg_atom, *sg_fbond;
+// The three projected attention levels of a layer.  The value is the level's slot in the per-layer tables of the workspace: the
+// transposed projection weights (EncLayout::bt) and the deferred form's R matrices (EncLayout::rmat) of layer l's level v are entry
+// 3 l + v.  The fragment graph is a fourth level without a projection (no slot); only the last layer's ever runs.
+enum Level : int { LV_BOND = 0, LV_ATOM = 1, LV_FBOND = 2, LV_FRAG = 3 };
+constexpr int kLevels = 3;
+constexpr Level kProjected[kLevels] = {LV_BOND, LV_ATOM, LV_FBOND};
+inline int64_t level_rows(const fn_encoder* e, Level v) { return v == LV_BOND ? e->E : v == LV_ATOM ? e->N : v == LV_FBOND ? e->EF : e->F; }
+inline const fn_gat_plan& level_plan(const fn_encoder* e, Level v) { return v == LV_BOND ? e->bond : v == LV_ATOM ? e->atom : v == LV_FBOND ? e->fbond : e->frag; }
+inline int level_k0(const fn_encoder* e, Level v) { return v == LV_BOND ? e->k_bond0 : v == LV_ATOM ? e->k_atom0 : v == LV_FBOND ? e->k_fbond0 : 0; }
+
+struct LevelActs {           // a level's rows, kept from forward for backward
+    float *h, *raw, *p;      // projected rows (fragment graph: the fragment sums), raw output rows (atom level: EncLayout::atoms_new, one
+                             // buffer for all layers; fragment graph: none), probabilities
+    float* y;                // post dropout+ReLU output (null for the last layer: caller's buffers)
+    float *o2, *sg;          // one-pass backward (FN_TUNE_BWD_ONE, training): the forward's second output rows and their weight sums
+};
+struct LayerActs {
+    LevelActs lv[kLevels + 1];       // by Level
 };
 
 struct EncLayout {
     LayerActs L[FN_MAX_LAYERS];
     float* in_atoms0;        // dropout(x_atoms) when training with p > 0, else null (use x_atoms)
-    // forward scratch
-    float *atoms_new, *frags_new, *s_sorted, *s_dst, *s_src, *s_dst_a, *s_src_a, *s_dst_fb, *s_src_fb, *bt;
+    // forward scratch (s_dst / s_src: a level's node scalars; the bond level's pair is sized for the largest index space and also
+    // serves the fragment graph, which runs when the bond level is done)
+    float *atoms_new, *frags_new, *s_sorted, *s_dst[kLevels], *s_src[kLevels], *bt;
     float* mol_ext;          // MolExt[n_mols] for the molecule-resident backward (null without molecule CSRs)
     float *xs_bond, *xs_fbond;   // one-pass backward: the two raw edge attributes in source order ([1][bond.m], [k_fattr][fbond.m])
     float* real_rows;            // pad_skip_on: int32 [4] = real atoms, bonds, fragments, connections (written by the forward prologue)
@@ -1022,21 +1036,22 @@ EncLayout enc_layout(const fn_encoder* e, float* ws) {
     const bool drop = e->training && e->drop_p > 0.f;
     for (int l = 0; l < e->n_layers; ++l) {
         LayerActs& a = o.L[l];
-        a.h_b = b.take(e->E * FN_D);  a.h_a = b.take(e->N * FN_D);  a.h_fb = b.take(e->EF * FN_D);  a.frags = b.take(e->F * FN_D);
-        a.new_bond = b.take(e->E * FN_D);  a.new_fbond = b.take(e->EF * FN_D);
-        a.p_bond = b.take(e->bond.m * H);  a.p_atom = b.take(e->atom.m * H);
-        a.p_fbond = b.take(e->fbond.m * H);  a.p_frag = b.take(e->frag.m * H);
+        for (Level v : kProjected) a.lv[v].h = b.take(level_rows(e, v) * FN_D);
+        a.lv[LV_FRAG].h = b.take(e->F * FN_D);
+        a.lv[LV_BOND].raw = b.take(e->E * FN_D);  a.lv[LV_FBOND].raw = b.take(e->EF * FN_D);
+        for (Level v : kProjected) a.lv[v].p = b.take(level_plan(e, v).m * H);
+        a.lv[LV_FRAG].p = b.take(e->frag.m * H);
         if (l + 1 < e->n_layers) {
-            a.y_atoms = b.take(e->N * FN_D);  a.y_frags = b.take(e->F * FN_D);
-            a.y_bond = b.take(e->E * FN_D);  a.y_fbond = b.take(e->EF * FN_D);
+            a.lv[LV_ATOM].y = b.take(e->N * FN_D);  a.lv[LV_FRAG].y = b.take(e->F * FN_D);
+            a.lv[LV_BOND].y = b.take(e->E * FN_D);  a.lv[LV_FBOND].y = b.take(e->EF * FN_D);
         }
     }
     if (one_pass_on(e)) {
         for (int l = 0; l < e->n_layers; ++l) {
             if (defer_on(e, l)) continue;
             LayerActs& a = o.L[l];
-            a.o2_bond = b.take(e->E * FN_D);  a.o2_atom = b.take(e->N * FN_D);  a.o2_fbond = b.take(e->EF * FN_D);
-            a.sg_bond = b.take(e->E * H);  a.sg_atom = b.take(e->N * H);  a.sg_fbond = b.take(e->EF * H);
+            for (Level v : kProjected) a.lv[v].o2 = b.take(level_rows(e, v) * FN_D);
+            for (Level v : kProjected) a.lv[v].sg = b.take(level_rows(e, v) * H);
         }
         o.xs_bond = b.take(e->bond.m);
         o.xs_fbond = b.take(e->fbond.m * e->k_fattr);
@@ -1045,15 +1060,15 @@ EncLayout enc_layout(const fn_encoder* e, float* ws) {
     o.rmat = defer_on(e) ? b.take((int64_t)3 * e->n_layers * 512) : nullptr;
     o.in_atoms0 = drop ? b.take(e->N * e->k_atom0) : nullptr;
     o.atoms_new = b.take(e->N * FN_D);
+    for (int l = 0; l < e->n_layers; ++l) o.L[l].lv[LV_ATOM].raw = o.atoms_new;
     o.frags_new = b.take(e->F * FN_D);
     o.s_sorted = b.take(std::max(e->atom.m, e->frag.m) * H);
     const int64_t nmax = max4(e->E, e->N, e->EF, e->F);
-    o.s_dst = b.take(nmax * H);
-    o.s_src = b.take(nmax * H);
-    o.s_dst_a = b.take(e->N * H);
-    o.s_src_a = b.take(e->N * H);
-    o.s_dst_fb = b.take(e->EF * H);
-    o.s_src_fb = b.take(e->EF * H);
+    for (Level v : kProjected) {
+        const int64_t n = v == LV_BOND ? nmax : level_rows(e, v);
+        o.s_dst[v] = b.take(n * H);
+        o.s_src[v] = b.take(n * H);
+    }
     o.bt = b.take((int64_t)3 * e->n_layers * 192 * FN_D);
     o.mol_ext = e->n_mols > 0 ? b.take(e->n_mols * (int64_t)(sizeof(MolExt) / sizeof(float))) : nullptr;
     o.total = b.used;
@@ -1083,9 +1098,9 @@ struct LevelScratch {
     float *dz_em, *upart;    // its deferred form: dz at destination-order slots [m][H]; the weight-gradient kernels' side product U | S per block
 };
 struct BwdLayout {
-    float *g_pre_atoms, *g_pre_frags, *g_pre_bond, *g_pre_fbond;   // grads w.r.t. pre-activation layer outputs (the chain)
+    float* g_pre[kLevels + 1];   // by Level: grads w.r.t. pre-activation layer outputs (the chain)
     float* g_frags;
-    LevelScratch bond[FN_MAX_LAYERS], atom[FN_MAX_LAYERS], fbond[FN_MAX_LAYERS], frag;
+    LevelScratch lv[FN_MAX_LAYERS][kLevels], frag;
     int64_t total;
 };
 
@@ -1093,8 +1108,8 @@ BwdLayout bwd_layout(const fn_encoder* e, float* ws) {
     BwdLayout o{};
     Bump b(ws);
     const int H = e->heads;
-    o.g_pre_atoms = b.take(e->N * FN_D);  o.g_pre_frags = b.take(e->F * FN_D);
-    o.g_pre_bond = b.take(e->E * FN_D);   o.g_pre_fbond = b.take(e->EF * FN_D);
+    o.g_pre[LV_ATOM] = b.take(e->N * FN_D);  o.g_pre[LV_FRAG] = b.take(e->F * FN_D);
+    o.g_pre[LV_BOND] = b.take(e->E * FN_D);  o.g_pre[LV_FBOND] = b.take(e->EF * FN_D);
     o.g_frags = b.take(e->F * FN_D);
     auto level = [&](LevelScratch& s, int64_t n, int64_t m, int k0, bool edge_params, bool row_dots, bool proj, bool one = false, bool df = false) {
         s.g_h = b.take(n * FN_D);
@@ -1110,11 +1125,10 @@ BwdLayout bwd_layout(const fn_encoder* e, float* ws) {
         s.part_rd = row_dots ? b.take((int64_t)FN_MAX_PART * H * FN_D) : nullptr;
         s.wg_ws = proj ? b.take(fn_linear128_wgrad_ws(n, k0 > FN_D ? k0 : FN_D)) : nullptr;
     };
-    for (int l = 0; l < e->n_layers; ++l) {
-        level(o.bond[l], e->E, e->bond.m, e->k_bond0, true, false, true, one_pass_on(e), defer_on(e, l));
-        level(o.atom[l], e->N, e->atom.m, e->k_atom0, false, true, true, one_pass_on(e), defer_on(e, l));
-        level(o.fbond[l], e->EF, e->fbond.m, e->k_fbond0, true, false, true, one_pass_on(e), defer_on(e, l));
-    }
+    // the atom level's edge term is a table of row dots (parameter partials part_rd); the other two embed a raw attribute (part_e)
+    for (int l = 0; l < e->n_layers; ++l)
+        for (Level v : kProjected)
+            level(o.lv[l][v], level_rows(e, v), level_plan(e, v).m, level_k0(e, v), v != LV_ATOM, v == LV_ATOM, true, one_pass_on(e), defer_on(e, l));
     level(o.frag, e->F, e->frag.m, 0, e->variant == 2, true, false);      // gat2_edge: the fragment graph has edge-embedding partials
     o.total = b.used;
     return o;
@@ -1141,6 +1155,127 @@ RngPlan rng_plan(const fn_encoder* e) {
     r.total = off - e->offset;
     return r;
 }
+
+// ---- the level view: everything the passes need to know about one attention level of one layer, described ONCE.  A plain struct on
+// the stack, built where a level is used; the forward, both backward forms and the parameter work all read the same description.
+struct LevelWeights {        // a level's parameters inside a fn_layer_weights (the engine's, or the caller's gradient block)
+    float *att, *W, *bias, *embW, *embb;      // attention vector, projection, edge-attribute embedding (null: the level has none)
+};
+inline LevelWeights level_weights(const fn_layer_weights& w, Level v, int variant = 0) {
+    switch (v) {
+        case LV_BOND: return {w.a_b, w.proj_b_w, w.proj_b_b, w.emb_b_w, w.emb_b_b};
+        case LV_ATOM: return {w.a, w.proj_a_w, w.proj_a_b, nullptr, nullptr};
+        case LV_FBOND: return {w.f_a_b, w.proj_fb_w, w.proj_fb_b, w.emb_fb_w, w.emb_fb_b};
+        default: break;
+    }
+    // the fragment graph: gat2_edge embeds the connection attribute there (with the fragment-bond level's Linear, which it does not run)
+    return {w.f, nullptr, nullptr, variant == 2 ? w.emb_fb_w : nullptr, variant == 2 ? w.emb_fb_b : nullptr};
+}
+struct LevelView {
+    Level lv;  int layer, H;
+    const fn_gat_plan* pl;  int64_t rows;
+    // attention vector [H][att_w]: destination block at 0, source block at src_off; mid_off: the block of the edge term (bond /
+    // fragment-bond level: the embedded attribute's, d wide; atom level / fragment graph: dotted with the raw bond / fragment-bond rows)
+    const float* att;  int att_w, src_off, mid_off;
+    const float *W, *bias, *Wt;     // projection [128][K], its bias, the transposed copy the forward prologue leaves in the workspace
+    const float* x;  int K;         // the projection's input rows: the level's activated output of the layer below, raw features (K wide) at layer 0
+    // edge term as the attention kernels take it (x_src: the source-order attribute table of the one-pass backward, null otherwise).
+    // Atom level and gat2's fragment graph: mode 0, a table of row dots; the forward points s_sorted at the table it fills
+    fn_edge_term et;
+    const int32_t* n_real;          // pad_skip_on: device word, rows at or behind it are padding; else null
+    float *s_dst, *s_src;           // node-scalar scratch of the forward
+    LevelActs a;                    // what the forward keeps of the level
+    int rng_slot;                   // RngPlan::y[layer][.]: ordered atoms, frags, bond, fbond -- NOT the Level order
+    const float* rmat;              // deferred form: the projection's R [4][128] (null unless defer_on)
+};
+LevelView level_view(const fn_encoder* e, const EncLayout& lay, int l, Level v) {
+    const int d = FN_D / e->heads;
+    const LevelWeights w = level_weights(e->w[l], v, e->variant);
+    const int32_t* rr = reinterpret_cast<const int32_t*>(lay.real_rows);       // (null unless pad_skip_on: enc_layout)
+    LevelView o{};
+    o.lv = v;  o.layer = l;  o.H = e->heads;
+    o.pl = &level_plan(e, v);  o.rows = level_rows(e, v);
+    o.att = w.att;
+    o.a = lay.L[l].lv[v];
+    if (v == LV_BOND || v == LV_FBOND) { o.att_w = 3 * d;  o.src_off = 2 * d; }
+    else { o.att_w = 2 * d + FN_D;  o.src_off = d + FN_D; }
+    o.mid_off = d;
+    if (v != LV_FRAG) {
+        o.W = w.W;  o.bias = w.bias;  o.K = l ? FN_D : level_k0(e, v);
+        o.Wt = lay.bt + (size_t)(3 * l + v) * 192 * FN_D;
+        o.rmat = lay.rmat ? lay.rmat + (size_t)(3 * l + v) * 512 : nullptr;
+        o.s_dst = lay.s_dst[v];  o.s_src = lay.s_src[v];
+    } else { o.s_dst = lay.s_dst[LV_BOND];  o.s_src = lay.s_src[LV_BOND]; }
+    switch (v) {
+        case LV_BOND:
+            o.x = l ? lay.L[l - 1].lv[v].y : e->bond_nodes;
+            o.et = fn_edge_term{2, 1, d, d, nullptr, e->cos_sorted, w.embW, w.embb, lay.xs_bond};
+            o.n_real = rr ? rr + 1 : nullptr;  o.rng_slot = 2;
+            break;
+        case LV_ATOM:
+            o.x = l ? lay.L[l - 1].lv[v].y : (lay.in_atoms0 ? lay.in_atoms0 : e->x_atoms);
+            o.n_real = rr;  o.rng_slot = 0;
+            break;
+        case LV_FBOND:
+            o.x = l ? lay.L[l - 1].lv[v].y : e->fbond_nodes;
+            o.et = fn_edge_term{2, e->k_fattr, d, d, nullptr, e->fattr_sorted, w.embW, w.embb, lay.xs_fbond};
+            o.n_real = rr ? rr + 3 : nullptr;  o.rng_slot = 3;
+            break;
+        case LV_FRAG:        // gat2_edge: the connection attribute rides on the fragment graph's edges, embedded 128 wide
+            if (e->variant == 2) o.et = fn_edge_term{2, e->k_fattr, FN_D, d, nullptr, e->fattr_sorted, w.embW, w.embb, nullptr};
+            o.n_real = rr ? rr + 2 : nullptr;  o.rng_slot = 1;
+            break;
+    }
+    return o;
+}
+// the act(dropout(.)) epilogue that writes (forward) or replays (backward: the gate of an input-gradient product) the level's output y
+inline fn_act_epilogue act_epilogue(const fn_encoder* e, const RngPlan& rng, const LevelView& v, float* y) {
+    return fn_act_epilogue{y, e->training ? e->drop_p : 0.f, 1, e->seed, rng.y[v.layer][v.rng_slot], e->offset_dev};
+}
+// dL/d(relu(dropout(x))) = gate_scale * dL/dy where y > 0
+inline float gate_scale(const fn_encoder* e) {
+    const float p = e->training ? e->drop_p : 0.f;
+    return p > 0.f ? (p < 1.f ? 1.f / (1.f - p) : 0.f) : 1.f;
+}
+// the four outputs of the encoder, or the gradients w.r.t. them, by Level (null: not stored / zero)
+struct EncOutputs { const float* y[kLevels + 1]; };
+
+// the deferred term of a level's g_h rows (deferred form of the one-pass backward), for the product that reads them and for the
+// weight-gradient kernels (all null: the level's layer is not deferred, or the level has no edges)
+struct DeferTerm { const float* dz; const float* gsd_c; GsdEpi gs; const float* a_dst; int att_w; };
+inline DeferTerm defer_term(const LevelView& v, const LevelScratch& sc) {
+    if (!sc.dz_em || v.pl->m <= 0) return DeferTerm{nullptr, nullptr, GsdEpi{nullptr, nullptr, 0, nullptr, nullptr}, nullptr, 0};
+    return DeferTerm{sc.dz_em, sc.g_s_dst, GsdEpi{sc.dz_em, v.pl->rowptr_d, v.pl->pos_base_d, v.rmat, sc.g_s_dst}, v.att, v.att_w};
+}
+
+// the level's edge term as the forward's attention kernels take it (mode 0: the table of row dots the forward fills)
+inline fn_edge_term fwd_edge_term(const LevelView& v, const float* s_sorted) {
+    fn_edge_term et = v.et;
+    et.x_src = nullptr;
+    if (et.mode == 0) et.s_sorted = s_sorted;
+    return et;
+}
+// the node scalars <h[row, head], att dst / src block> of a level, as the epilogue of its projection
+inline NodeScalarEpi node_scalars(const LevelView& v) { return NodeScalarEpi{v.att, v.s_dst, v.s_src, v.att_w, 0, v.src_off, v.H}; }
+// the level's projection h = x W^T + b (+ node scalars) as a task of a grouped launch.  k_task != 0: a launch whose tasks have
+// reduction lengths of their own (layer 0's raw features)
+inline LinTask proj_task(const LevelView& v, int k_task = 0) {
+    LinTask t{v.W, v.x, v.Wt, v.bias, v.a.h, v.rows, fn_act_epilogue{nullptr, 0.f, 0, 0, 0, nullptr}, node_scalars(v), 0, 0, k_task};
+    t.n_real = v.n_real;
+    return t;
+}
+
+// a level's parameter work: the attention vector's and edge embedding's gradients from the partial rows its pass wrote (n_a, n_e),
+// and the projection's weight gradient from its g_h rows
+struct ParamWork {
+    int n_a = 0, n_e = 0;
+    // one-pass backward: the finalize task and the product leave in the same pair of launches (reserve), and
+    bool one_pass = false;
+    const DeferTerm* df = nullptr;   // ... the rows lack the deferred term
+    bool up = false;                 // ... whose dL/da_dst comes out of the product's side product U | S (else: k_gsd_seg, layer 0)
+    bool link = false;               // ... the product tells the finalize task how many partial rows of U | S there are
+    int n_rd = 0;                    // two-pass atom level: partial rows of the edge term's dL/da[:, mid block], reduced between the two
+};
 
 // weight-gradient partials only (the reduction is deferred); *grid = partial rows written, *cls = kernel class
 int wgrad_partials(const float* dY, const float* X, int K, int64_t M, float* ws, hipStream_t st, int* grid, int* cls) {
@@ -1194,15 +1329,17 @@ struct ReduceQueue {
         if (T.n + tasks > kMaxReduceTasks || W.n == kMaxWgradTasks || W0.n == kMaxWgradTasks) return flush();
         return 0;
     }
-    // up != null: the deferred form (ReduceTask::up); n_up is filled in when the level's weight-gradient product is queued (wgrad below)
-    int finalize(const float* part_a, int n_a, const float* part_e, int n_e, const fn_edge_term& et, const float* att, int att_w,
-                 int dst_off, int src_off, float* g_att, float* g_embW, float* g_embb, int H, const float* up = nullptr,
-                 const float* upW = nullptr, const float* upb = nullptr, int upK = 0) {
+    // dL/d(attention vector, edge embedding) of a level from the n_a / n_e partial rows its pass left in the level's scratch
+    // up != null: the deferred form (ReduceTask::up, with the projection it belongs to); n_up is filled in when the level's
+    // weight-gradient product is queued (wgrad below)
+    int finalize(const LevelView& v, const LevelWeights& g, const LevelScratch& sc, int n_a, int n_e, const float* up = nullptr,
+                 bool up_proj = false) {
         ReduceTask t{};
-        t.kind = RT_FINALIZE;  t.H = H;  t.p0 = part_a;  t.n0 = n_a;  t.p1 = part_e;  t.n1 = n_e;  t.et = et;
-        t.att = att;  t.att_w = att_w;  t.dst_off = dst_off;  t.src_off = src_off;  t.o0 = g_att;  t.o1 = g_embW;  t.o2 = g_embb;
-        t.up = up;  t.upW = upW;  t.upb = upb;  t.upK = upK;  t.n_up = 0;
-        return push(t, 2 * FN_D / 32 + (et.mode == 2 ? 1 : 0) + (up ? 4 : 0));
+        t.kind = RT_FINALIZE;  t.H = v.H;  t.p0 = sc.part_a;  t.n0 = n_a;  t.p1 = sc.part_e;  t.n1 = n_e;  t.et = v.et;
+        t.att = v.att;  t.att_w = v.att_w;  t.dst_off = 0;  t.src_off = v.src_off;  t.o0 = g.att;  t.o1 = g.embW;  t.o2 = g.embb;
+        t.up = up;  t.n_up = 0;
+        if (up_proj) { t.upW = v.W;  t.upb = v.bias;  t.upK = v.K; }
+        return push(t, 2 * FN_D / 32 + (v.et.mode == 2 ? 1 : 0) + (up ? 4 : 0));
     }
     int colsum(const float* part, int n_rows, int cols, float* out, int ld, int off) {
         ReduceTask t{};
@@ -1210,23 +1347,26 @@ struct ReduceQueue {
         if (cols % 32) return fail(FN_EINVAL, "deferred column sum: column count must be a multiple of 32");
         return push(t, cols / 32);
     }
-    // dW [128,K], db [128] of a projection: partial kernel now (on `launch_on`), reduction with the rest
-    // gsd != null: the deferred term (WgradTask::gsd ..); fin: index in T of the level's RT_FINALIZE task (queued just before, reserve())
-    int wgrad(const float* dY, const float* X, int K, int64_t M, float* ws, float* dW, float* db, hipStream_t launch_on,
-              const int32_t* n_real = nullptr, const float* gsd = nullptr, const float* a_dst = nullptr, int att_w = 0, float* upart = nullptr,
-              int fin = -1) {
+    // dW [128,K], db [128] of a level's projection from its g_h rows: partial kernel now (on `launch_on`), reduction with the rest
+    // df.gsd_c != null: the deferred term (WgradTask::gsd ..); fin: index in T of the level's RT_FINALIZE task (queued just before, reserve())
+    int wgrad(const LevelView& v, const LevelWeights& g, const LevelScratch& sc, hipStream_t launch_on, const DeferTerm& df = DeferTerm{},
+              float* upart = nullptr, int fin = -1) {
+        const float* gsd = df.gsd_c;
+        const int K = v.K;
+        const int64_t M = v.rows;
+        float* ws = sc.wg_ws;
         if (gsd && !(defer_wgrad && (K == FN_D ? tune(FN_TUNE_WGRAD_DIRECT) != 0 : (defer_mixed && K <= 192))))
             return fail(FN_EUNSUPPORTED, "weight gradient: the deferred term needs the grouped direct kernels");
         if (M == 0) {
             hipLaunchKernelGGL(k_zero2_i32, dim3(flat_grid(128 * (K + 1), kGridCap)), dim3(kBlock), 0, launch_on,
-                               reinterpret_cast<int32_t*>(dW), (int64_t)128 * K, reinterpret_cast<int32_t*>(db), (int64_t)128);
+                               reinterpret_cast<int32_t*>(g.W), (int64_t)128 * K, reinterpret_cast<int32_t*>(g.bias), (int64_t)128);
             return launch_status("weight gradient (empty)");
         }
         ReduceTask t{};
         int grid = 0;
         if (K == FN_D && defer_wgrad) {   // partial product joins the grouped launch in flush(); its block count is set there
             if (W.n == kMaxWgradTasks || T.n == kMaxReduceTasks) { if (int rc = flush()) return rc; }
-            W.t[W.n] = WgradTask{dY, X, ws, M, 0, 0, 0, n_real, gsd, a_dst, att_w, upart};
+            W.t[W.n] = WgradTask{sc.g_h, v.x, ws, M, 0, 0, 0, v.n_real, gsd, df.a_dst, df.att_w, upart};
             w_fin[W.n] = gsd ? fin : -1;
             w_reduce[W.n++] = T.n;
             t.cls = tune(FN_TUNE_WGRAD_DIRECT) ? 4 : 2;
@@ -1240,58 +1380,20 @@ struct ReduceQueue {
             const int mult = std::max(1, K > FN_D ? tv / 10 : tv % 10);          // tens: the wide product (atoms), units: the narrow ones
             const int rpb = wgrad_rows_per_block(M) * mult;
             grid = (int)((M + rpb - 1) / rpb);
-            W0.t[W0.n++] = WgradTask{dY, X, ws, M, rpb, w0blocks, K, n_real, gsd, a_dst, att_w, upart};
+            W0.t[W0.n++] = WgradTask{sc.g_h, v.x, ws, M, rpb, w0blocks, K, v.n_real, gsd, df.a_dst, df.att_w, upart};
             if (gsd && fin >= 0) T.t[fin].n_up = grid;
             w0blocks += grid;
             t.cls = K <= 32 ? 1 : K <= 128 ? 2 : 3;              // the instantiation k_linear128_wgrad_mixed runs for this K
-        } else if (int rc = wgrad_partials(dY, X, K, M, ws, launch_on, &grid, &t.cls)) return rc;
-        t.kind = RT_WGRAD;  t.p0 = ws;  t.n0 = grid;  t.K = K;  t.o0 = dW;  t.o1 = db;
+        } else if (int rc = wgrad_partials(sc.g_h, v.x, K, M, ws, launch_on, &grid, &t.cls)) return rc;
+        t.kind = RT_WGRAD;  t.p0 = ws;  t.n0 = grid;  t.K = K;  t.o0 = g.W;  t.o1 = g.bias;
         // partial width of the instantiation that wrote them (the mixed launch runs K <= 16 in the K <= 32 class)
         const int64_t pw = t.cls == 1 ? wgrad_part_width(32) : wgrad_part_width(K);
         return push(t, (int)((pw + 1023) / 1024));
     }
-    int flush_wgrad() {
-        size_t lds0 = 0;
-        if (W0.n) {
-            int kmax = 0;
-            for (int i = 0; i < W0.n; ++i) kmax = std::max(kmax, W0.t[i].K);
-            const int xw = kmax <= 32 ? 32 : kmax <= 128 ? 128 : 192;
-            lds0 = (size_t)2 * kWgChunk * (kBtLd + xw + 16) * sizeof(float);
-        }
-        if (W0.n && W.n && tune(FN_TUNE_WGRAD_DIRECT) == 1 && tune(FN_TUNE_GEMM_COLAUNCH) != 0) {
-            // both groups in one launch (k_wgrad_all): block counts of the K = 128 group as below
-            int64_t total = 0;
-            for (int i = 0; i < W.n; ++i) total += W.t[i].M;
-            const int64_t target = tune(FN_TUNE_WGRAD_BLOCKS) > 0 ? tune(FN_TUNE_WGRAD_BLOCKS) : 256;
-            const int group_rpb = (int)(((total + target - 1) / target + kWgChunk - 1) / kWgChunk * kWgChunk);
-            wblocks = 0;
-            for (int i = 0; i < W.n; ++i) {
-                WgradTask& t = W.t[i];
-                t.rpb = std::max(group_rpb, wgrad_rows_per_block(t.M));
-                t.first = wblocks;
-                const int grid = (int)((t.M + t.rpb - 1) / t.rpb);
-                T.t[w_reduce[i]].n0 = grid;
-                if (w_fin[i] >= 0) T.t[w_fin[i]].n_up = grid;
-                wblocks += grid;
-            }
-            W.K = FN_D;
-            const size_t lds = std::max(lds0, (size_t)wd_lds_bytes<2>());
-            if (int rc = allow_lds(k_wgrad_all, lds)) return rc;
-            hipLaunchKernelGGL(k_wgrad_all, dim3(wblocks + w0blocks), dim3(512), lds, st, W, W0, wblocks);
-            W.n = 0;  wblocks = 0;  W0.n = 0;  w0blocks = 0;
-            return launch_status("weight-gradient partials (all products)");
-        }
-        if (W0.n) {
-            const size_t lds = lds0;
-            if (int rc = allow_lds(k_linear128_wgrad_mixed, lds)) return rc;
-            hipLaunchKernelGGL(k_linear128_wgrad_mixed, dim3(w0blocks), dim3(512), lds, st, W0);
-            W0.n = 0;  w0blocks = 0;
-            if (int rc = launch_status("weight-gradient partials (layer 0)")) return rc;
-        }
-        if (W.n == 0) return 0;
-        // rows per block from the WHOLE group: ~256 blocks (one per CU) instead of ~256 per product, which for the nine
-        // products of a backward pass was 1.6 k blocks writing 104 MB of 64-KB partials (now ~16 MB); never fewer rows
-        // than the per-product rule, so the partial workspace sized by fn_linear128_wgrad_ws still fits
+    // block counts of the K = 128 group.  Rows per block from the WHOLE group: ~256 blocks (one per CU) instead of ~256 per product,
+    // which for the nine products of a backward pass was 1.6 k blocks writing 104 MB of 64-KB partials (now ~16 MB); never fewer rows
+    // than the per-product rule, so the partial workspace sized by fn_linear128_wgrad_ws still fits
+    void size_group128() {
         int64_t total = 0;
         for (int i = 0; i < W.n; ++i) total += W.t[i].M;
         const int64_t target = tune(FN_TUNE_WGRAD_BLOCKS) > 0 ? tune(FN_TUNE_WGRAD_BLOCKS) : 256;
@@ -1307,6 +1409,32 @@ struct ReduceQueue {
             wblocks += grid;
         }
         W.K = FN_D;
+    }
+    int flush_wgrad() {
+        size_t lds0 = 0;
+        if (W0.n) {
+            int kmax = 0;
+            for (int i = 0; i < W0.n; ++i) kmax = std::max(kmax, W0.t[i].K);
+            const int xw = kmax <= 32 ? 32 : kmax <= 128 ? 128 : 192;
+            lds0 = (size_t)2 * kWgChunk * (kBtLd + xw + 16) * sizeof(float);
+        }
+        if (W0.n && W.n && tune(FN_TUNE_WGRAD_DIRECT) == 1 && tune(FN_TUNE_GEMM_COLAUNCH) != 0) {
+            size_group128();         // both groups in one launch (k_wgrad_all)
+            const size_t lds = std::max(lds0, (size_t)wd_lds_bytes<2>());
+            if (int rc = allow_lds(k_wgrad_all, lds)) return rc;
+            hipLaunchKernelGGL(k_wgrad_all, dim3(wblocks + w0blocks), dim3(512), lds, st, W, W0, wblocks);
+            W.n = 0;  wblocks = 0;  W0.n = 0;  w0blocks = 0;
+            return launch_status("weight-gradient partials (all products)");
+        }
+        if (W0.n) {
+            const size_t lds = lds0;
+            if (int rc = allow_lds(k_linear128_wgrad_mixed, lds)) return rc;
+            hipLaunchKernelGGL(k_linear128_wgrad_mixed, dim3(w0blocks), dim3(512), lds, st, W0);
+            W0.n = 0;  w0blocks = 0;
+            if (int rc = launch_status("weight-gradient partials (layer 0)")) return rc;
+        }
+        if (W.n == 0) return 0;
+        size_group128();
         if (tune(FN_TUNE_WGRAD_DIRECT)) {
             if (int rc = allow_lds(k_wgrad128_multi<2>, wd_lds_bytes<2>())) return rc;
             hipLaunchKernelGGL(k_wgrad128_multi<2>, dim3(wblocks), dim3(wd_threads<2>()), wd_lds_bytes<2>(), st, W);
@@ -1319,6 +1447,14 @@ struct ReduceQueue {
         W.n = 0;  wblocks = 0;
         return launch_status("grouped weight-gradient partials");
     }
+    // a level's parameter work (ParamWork), queued in the order finalize, [column sum], weight gradient
+    int level_params(const LevelView& v, const LevelWeights& g, const LevelScratch& sc, const ParamWork& o, hipStream_t launch_on) {
+        const DeferTerm df = o.df ? *o.df : DeferTerm{};
+        if (o.one_pass) { if (int rc = reserve(2)) return rc; }
+        if (int rc = finalize(v, g, sc, o.n_a, o.n_e, o.up && df.dz ? sc.upart : nullptr, o.link)) return rc;
+        if (o.n_rd) { if (int rc = colsum(sc.part_rd, o.n_rd, v.H * FN_D, g.att, v.att_w, v.mid_off)) return rc; }
+        return wgrad(v, g, sc, launch_on, df, o.up ? sc.upart : nullptr, o.link ? last_index : -1);
+    }
 };
 
 // the source pass alone (fn_gat_bwd_src_f32)
@@ -1328,17 +1464,18 @@ int launch_gat_bwd_src(const GatBwdSrcArgs& A, int heads, hipStream_t st) {
     return launch_status("fn_gat_bwd_src_f32");
 }
 
-// source pass of a level + backward of its edge term <feat[e], att[:, mid block]> as ONE launch (k_gat_bwd_src_rd); they
-// share nothing but their input dz.  *n_rd = blocks of the edge-term part (0: the level has no real edges).
-int bwd_src_and_edge_term(const float* g_out, const float* h, const float* pz_src, const float* g_s_dst, const float* att, int att_w,
-                          int dst_off, int src_off, const fn_gat_plan* plan, float* g_h, float* part_a, int* n_part_a,
-                          const float* dz_orig, const float* feat, int mid_off, float* g_feat, float* part_rd, bool accumulate,
-                          int* n_rd, int heads, hipStream_t st) {
+// source pass of a two-pass level + backward of its edge term <feat[e], att[:, mid block]> as ONE launch (k_gat_bwd_src_rd); they
+// share nothing but their input dz.  g_out / g_h: the level's gradient rows in and out; feat: the raw rows of the level that provides
+// the edge features, g_feat their gradient rows (accumulate: they hold a gradient already).  *n_rd = blocks of the edge-term part (0:
+// the level has no real edges).
+int bwd_src_and_edge_term(const LevelView& v, const LevelScratch& sc, const float* g_out, float* g_h, const float* feat, float* g_feat,
+                          bool accumulate, int* n_part_a, int* n_rd, hipStream_t st) {
+    const int heads = v.H;
     GatBwdSrcArgs A;
-    if (int rc = prep_gat_bwd_src(g_out, h, pz_src, g_s_dst, att, att_w, dst_off, src_off, plan, g_h, part_a, n_part_a, heads, &A)) return rc;
-    *n_rd = plan->m_real > 0 ? row_grid(plan->m_real, tune(FN_TUNE_RD_BLOCKS) > 0 ? tune(FN_TUNE_RD_BLOCKS) : kRowDotsBwdBlocks) : 0;
+    if (int rc = prep_gat_bwd_src(g_out, v.a.h, sc.pz, sc.g_s_dst, v.att, v.att_w, 0, v.src_off, v.pl, g_h, sc.part_a, n_part_a, heads, &A)) return rc;
+    *n_rd = v.pl->m_real > 0 ? row_grid(v.pl->m_real, tune(FN_TUNE_RD_BLOCKS) > 0 ? tune(FN_TUNE_RD_BLOCKS) : kRowDotsBwdBlocks) : 0;
     if (*n_rd == 0) return launch_gat_bwd_src(A, heads, st);
-    const RowDotsBwdArgs T{dz_orig, feat, att, att_w, mid_off, heads, *plan, g_feat, part_rd, accumulate ? (const float*)g_feat : nullptr, 1, *n_rd};
+    const RowDotsBwdArgs T{sc.dz, feat, v.att, v.att_w, v.mid_off, heads, *v.pl, g_feat, sc.part_rd, accumulate ? (const float*)g_feat : nullptr, 1, *n_rd};
     if (A.nblk == 0) {
         hipLaunchKernelGGL(k_row_dots_sorted_bwd, dim3(T.nblk), dim3(kBlock), 0, st, T);
         return launch_status("edge-term backward");
@@ -1398,16 +1535,16 @@ int enc_check(const fn_encoder* e) {
     return 0;
 }
 
-int launch_tail_fwd(const fn_encoder* e, const EncLayout& lay, const LayerActs& a, const fn_layer_weights& w,
-                    const fn_act_epilogue& ep_frags, const float* y_atoms, hipStream_t st) {
-    const int H = e->heads, d = FN_D / H, wide = 2 * d + FN_D;
+int launch_tail_fwd(const fn_encoder* e, const EncLayout& lay, const LevelView& vf, const fn_act_epilogue& ep_frags, const float* y_atoms,
+                    hipStream_t st) {
+    const int H = e->heads;
     TailFwdArgs T{};
     T.ext = reinterpret_cast<const MolExt*>(lay.mol_ext);  T.n_mols = (int)e->n_mols;  T.counts_dev = e->counts_dev;
     T.atoms_new = lay.atoms_new;  T.a2f_rowptr = e->a2f.rowptr;  T.a2f_perm = e->a2f.perm;  T.a2f_base = e->a2f.pos_base;  T.a2f_items = (int)e->a2f.n_items;
-    T.frags = a.frags;  T.att = w.f;  T.att_w = wide;  T.dst_off = 0;  T.src_off = d + FN_D;  T.mid_off = d;
-    T.s_dst = lay.s_dst;  T.s_src = lay.s_src;  T.feat = a.new_fbond;  T.s_sorted = lay.s_sorted;
-    const fn_edge_term et_f{0, 0, 0, 0, lay.s_sorted, nullptr, nullptr, nullptr};
-    FN_TRY(prep_gat_fwd(a.frags, lay.s_dst, lay.s_src, w.f, wide, &et_f, &e->frag, 0.2f, nullptr, a.p_frag, nullptr, &ep_frags, H, &T.G));
+    T.frags = vf.a.h;  T.att = vf.att;  T.att_w = vf.att_w;  T.dst_off = 0;  T.src_off = vf.src_off;  T.mid_off = vf.mid_off;
+    T.s_dst = vf.s_dst;  T.s_src = vf.s_src;  T.feat = lay.L[vf.layer].lv[LV_FBOND].raw;  T.s_sorted = lay.s_sorted;
+    const fn_edge_term et_f = fwd_edge_term(vf, lay.s_sorted);
+    FN_TRY(prep_gat_fwd(vf.a.h, vf.s_dst, vf.s_src, vf.att, vf.att_w, &et_f, vf.pl, 0.2f, nullptr, vf.a.p, nullptr, &ep_frags, H, &T.G));
     T.y_atoms = y_atoms;  T.pooled = e->pooled;  T.force_global = tune(FN_TUNE_MOL_TAIL) == 2;
     if (((uintptr_t)y_atoms | (uintptr_t)ep_frags.y | (uintptr_t)e->pooled) & 15) return fail(FN_EINVAL, "fragment tail: outputs must be 16-byte aligned");
     const dim3 grid((unsigned)e->n_mols);
@@ -1415,26 +1552,28 @@ int launch_tail_fwd(const fn_encoder* e, const EncLayout& lay, const LayerActs& 
     return launch_status("fragment tail, molecule-resident (sums + fragment graph + readout)");
 }
 
-// partial rows written: one per molecule (*n_part), for rq.finalize (part_a) and rq.colsum (part_rd)
-int launch_tail_bwd(const fn_encoder* e, const EncLayout& lay, const LayerActs& a, const fn_layer_weights& w, const BwdLayout& bw, const float* y_atoms,
-                    const float* y_frags, const float* g_atoms, const float* g_frags, float gate_scale, bool accumulate_fbond,
+// y / gy: the forward's outputs and the gradients w.r.t. them (atoms and fragments are read).  Partial rows written: one per
+// molecule (*n_part), for rq.finalize (part_a) and rq.colsum (part_rd)
+// one_pass_dots: the last layer's atom and fragment-bond levels run the one-pass backward next: their rows' dots from here
+int launch_tail_bwd(const fn_encoder* e, const EncLayout& lay, const BwdLayout& bw, const EncOutputs& y, const EncOutputs& gy, bool accumulate_fbond,
                     int* n_part, hipStream_t st, bool one_pass_dots = false, bool* rider_done = nullptr) {
-    const int H = e->heads, d = FN_D / H, wide = 2 * d + FN_D;
+    const int H = e->heads, l = e->n_layers - 1;
+    const LevelView vf = level_view(e, lay, l, LV_FRAG), va = level_view(e, lay, l, LV_ATOM), vfb = level_view(e, lay, l, LV_FBOND);
     const LevelScratch& sf = bw.frag;
+    const float *y_atoms = y.y[LV_ATOM], *y_frags = y.y[LV_FRAG], *g_atoms = gy.y[LV_ATOM], *g_frags = gy.y[LV_FRAG];
     TailBwdArgs T{};
     T.ext = reinterpret_cast<const MolExt*>(lay.mol_ext);  T.n_mols = (int)e->n_mols;  T.counts_dev = e->counts_dev;
-    T.g_atoms = g_atoms;  T.g_frags = g_frags;  T.g_pooled = e->g_pooled;  T.y_atoms = y_atoms;  T.y_frags = y_frags;  T.scale = gate_scale;
-    T.g_pre_atoms = bw.g_pre_atoms;  T.g_pre_frags = bw.g_pre_frags;  T.a2f_index = e->a2f.index;  T.n_atoms = e->N;  T.force_global = tune(FN_TUNE_MOL_TAIL) == 2;
-    const fn_edge_term et_f{0, 0, 0, 0, nullptr, nullptr, nullptr, nullptr};
+    T.g_atoms = g_atoms;  T.g_frags = g_frags;  T.g_pooled = e->g_pooled;  T.y_atoms = y_atoms;  T.y_frags = y_frags;  T.scale = gate_scale(e);
+    T.g_pre_atoms = bw.g_pre[LV_ATOM];  T.g_pre_frags = bw.g_pre[LV_FRAG];  T.a2f_index = e->a2f.index;  T.n_atoms = e->N;  T.force_global = tune(FN_TUNE_MOL_TAIL) == 2;
     int n_e = 0, n_a = 0;
-    FN_TRY(prep_gat_bwd_dst(bw.g_pre_frags, a.frags, a.p_frag, &et_f, &e->frag, 0.2f, nullptr, sf.dz, sf.pz, sf.g_s_dst, nullptr, &n_e, H, &T.D));
-    FN_TRY(prep_gat_bwd_src(bw.g_pre_frags, a.frags, sf.pz, sf.g_s_dst, w.f, wide, 0, d + FN_D, &e->frag, bw.g_frags, sf.part_a, &n_a, H, &T.S));
-    T.R = RowDotsBwdArgs{sf.dz, a.new_fbond, w.f, wide, d, H, e->frag, bw.g_pre_fbond, sf.part_rd,
-                         accumulate_fbond ? (const float*)bw.g_pre_fbond : (const float*)nullptr, 1, 0};
-    if (one_pass_dots) {         // the last layer's atom and fragment-bond levels run the one-pass backward next: their rows' dots from here
-        const int l = e->n_layers - 1;
-        T.cu_out = lay.atoms_new;  T.cu_out2 = a.o2_atom;  T.cu_sigma = a.sg_atom;  T.cu_c = bw.atom[l].cdot;  T.cu_u = bw.atom[l].g_s_dst;
-        if (H == 4) { T.R.cu_out2 = a.o2_fbond;  T.R.cu_sigma = a.sg_fbond;  T.R.cu_c = bw.fbond[l].cdot;  T.R.cu_u = bw.fbond[l].g_s_dst; }
+    FN_TRY(prep_gat_bwd_dst(bw.g_pre[LV_FRAG], vf.a.h, vf.a.p, &vf.et, vf.pl, 0.2f, nullptr, sf.dz, sf.pz, sf.g_s_dst, nullptr, &n_e, H, &T.D));
+    FN_TRY(prep_gat_bwd_src(bw.g_pre[LV_FRAG], vf.a.h, sf.pz, sf.g_s_dst, vf.att, vf.att_w, 0, vf.src_off, vf.pl, bw.g_frags, sf.part_a, &n_a, H, &T.S));
+    T.R = RowDotsBwdArgs{sf.dz, vfb.a.raw, vf.att, vf.att_w, vf.mid_off, H, *vf.pl, bw.g_pre[LV_FBOND], sf.part_rd,
+                         accumulate_fbond ? (const float*)bw.g_pre[LV_FBOND] : (const float*)nullptr, 1, 0};
+    if (one_pass_dots) {
+        const LevelScratch &sa = bw.lv[l][LV_ATOM], &sfb = bw.lv[l][LV_FBOND];
+        T.cu_out = va.a.raw;  T.cu_out2 = va.a.o2;  T.cu_sigma = va.a.sg;  T.cu_c = sa.cdot;  T.cu_u = sa.g_s_dst;
+        if (H == 4) { T.R.cu_out2 = vfb.a.o2;  T.R.cu_sigma = vfb.a.sg;  T.R.cu_c = sfb.cdot;  T.R.cu_u = sfb.g_s_dst; }
     }
     if (((uintptr_t)y_atoms | (uintptr_t)y_frags | (uintptr_t)g_atoms | (uintptr_t)g_frags | (uintptr_t)e->g_pooled) & 15)
         return fail(FN_EINVAL, "fragment tail backward: gradients must be 16-byte aligned");
@@ -1457,6 +1596,81 @@ int launch_tail_bwd(const fn_encoder* e, const EncLayout& lay, const LayerActs& 
     return rc;
 }
 
+// ---- the last layer's output gradients, for both backward forms: the gates of relu(dropout(.)) of the four outputs (one launch; y > 0
+// already encodes the mask), the fragment graph -- the only layer whose fragment level is ever read -- and the scatter of
+// dL/d(fragment sums) back to the atoms.  Leaves the pre-activation gradients of the last layer's three projected levels in bw.g_pre.
+struct LastGrads {
+    bool have[kLevels];                          // by Level: g_pre holds the level's gradient rows (else: zero, not written)
+    bool tail_dots_atoms, tail_dots_fbond;       // one-pass form: the fragment tail's launch wrote the level's dots as well
+};
+// one_pass: the caller runs the one-pass backward next -- the molecule-resident tail writes the dots of the rows it finishes and may
+// carry the Adam rider (which then leaves rq)
+int last_layer_output_grads(const fn_encoder* e, const EncLayout& lay, const BwdLayout& bw, const EncOutputs& y, const EncOutputs& gy,
+                            const fn_layer_weights* grads, ReduceQueue& rq, bool one_pass, hipStream_t hs, LastGrads* out) {
+    const int H = e->heads, l = e->n_layers - 1;
+    const bool lite = e->variant == 1, edge = e->variant == 2;
+    const LevelView vf = level_view(e, lay, l, LV_FRAG);
+    const LevelWeights gf = level_weights(grads[l], LV_FRAG, e->variant);
+    const LevelScratch& sf = bw.frag;
+    // molecule-resident tail (csrc/mol_tail.inc): the atoms' and fragments' gates, the fragment graph's two passes, its edge term's
+    // backward and the scatter to the atoms are ONE launch below; the readout's gradient enters there
+    const bool tail_mol = tail_mol_on(e) && (gy.y[LV_FRAG] != nullptr || e->g_pooled != nullptr);
+    bool have_atoms = gy.y[LV_ATOM] != nullptr, have_fbond = gy.y[LV_FBOND] != nullptr;
+    const bool have_frags = gy.y[LV_FRAG] != nullptr;
+    GateTasks G{};
+    auto add = [&](Level v) {
+        if (!gy.y[v]) return;
+        GateTask& t = G.t[G.n++];
+        t.g = gy.y[v];  t.y = y.y[v];  t.o = bw.g_pre[v];  t.n4 = (level_rows(e, v) * FN_D + 3) / 4;  t.first = G.blocks;  t.nblk = flat_grid(t.n4, 512);
+        G.blocks += t.nblk;
+    };
+    if (!tail_mol) { add(LV_ATOM);  add(LV_FRAG); }
+    add(LV_BOND);
+    add(LV_FBOND);
+    if (G.blocks) {
+        G.scale = gate_scale(e);
+        hipLaunchKernelGGL(k_gate_many, dim3(G.blocks), dim3(kBlock), 0, hs, G);
+        FN_TRY(launch_status("fn_encoder_backward: activation backward"));
+    }
+    bool have_g_frags_h = false;
+    const float* g_frags_h = bw.g_frags;      // dL/d(fragment sums), scattered back to the atoms below
+    int n_a = 0, n_e = 0;
+    if (tail_mol) {
+        int n_part = 0;
+        bool rode = false;
+        FN_TRY(launch_tail_bwd(e, lay, bw, y, gy, have_fbond, &n_part, hs, one_pass, one_pass ? &rode : nullptr));
+        if (rode) rq.rider = nullptr;          // the head's Adam slice went with this launch
+        FN_TRY(rq.finalize(vf, gf, sf, n_part, 0));
+        FN_TRY(rq.colsum(sf.part_rd, n_part, H * FN_D, gf.att, vf.att_w, vf.mid_off));
+        have_atoms = have_fbond = true;        // g_pre of the atoms and fragment bonds is complete (scatter to the atoms included)
+        out->tail_dots_atoms = one_pass;  out->tail_dots_fbond = one_pass && H == 4;
+    } else if (have_frags && lite) {
+        g_frags_h = bw.g_pre[LV_FRAG];         // no fragment graph in between
+        have_g_frags_h = true;
+    } else if (have_frags && edge) {   // gat2_edge: the edge term's parameters are the cnx_attr Linear (emb_fb_*) and f's middle block
+        FN_TRY(fn_gat_bwd_dst_f32(bw.g_pre[LV_FRAG], vf.a.h, vf.a.p, &vf.et, vf.pl, 0.2f, nullptr, nullptr, sf.pz, sf.g_s_dst, sf.part_e, &n_e, H, hs));
+        FN_TRY(fn_gat_bwd_src_f32(bw.g_pre[LV_FRAG], vf.a.h, sf.pz, sf.g_s_dst, vf.att, vf.att_w, 0, vf.src_off, vf.pl, bw.g_frags, sf.part_a, &n_a, H, hs));
+        FN_TRY(rq.finalize(vf, gf, sf, n_a, n_e));
+        have_g_frags_h = true;
+    } else if (have_frags) {
+        FN_TRY(fn_gat_bwd_dst_f32(bw.g_pre[LV_FRAG], vf.a.h, vf.a.p, &vf.et, vf.pl, 0.2f, nullptr, sf.dz, sf.pz, sf.g_s_dst, nullptr, &n_e, H, hs));
+        // source pass + edge term <new_fbond, f[:, d:d+128]> (dL/dnew_fbond accumulates into g_pre of the fragment bonds, dL/df mid block)
+        int gr = 0;
+        FN_TRY(bwd_src_and_edge_term(vf, sf, bw.g_pre[LV_FRAG], bw.g_frags, lay.L[l].lv[LV_FBOND].raw, bw.g_pre[LV_FBOND], have_fbond, &n_a, &gr, hs));
+        if (gr) have_fbond = true;
+        FN_TRY(rq.finalize(vf, gf, sf, n_a, 0));
+        if (gr) FN_TRY(rq.colsum(sf.part_rd, gr, H * FN_D, gf.att, vf.att_w, vf.mid_off));
+        have_g_frags_h = true;
+    }
+    // atom -> fragment sum: dL/datoms_new += dL/dfrags[a2f]
+    if (have_g_frags_h) {
+        FN_TRY(launch_gather_rows4(g_frags_h, e->a2f.index, bw.g_pre[LV_ATOM], e->N, 32, have_atoms ? (const float*)bw.g_pre[LV_ATOM] : (const float*)nullptr, hs,
+                                   "fn_encoder_backward: gather(a2f)"));
+        have_atoms = true;
+    }
+    out->have[LV_ATOM] = have_atoms;  out->have[LV_BOND] = gy.y[LV_BOND] != nullptr;  out->have[LV_FBOND] = have_fbond;
+    return 0;
+}
 
 // ---- fn_encoder_backward with every attention level as ONE source-owner pass (csrc/gat_bwd_one.inc, FN_TUNE_BWD_ONE).
 // Gradient flows atom level -> bond levels only (through the edge term <new_bond[e], a[:, mid]>), so the atom level of layer l and
@@ -1469,228 +1683,130 @@ int launch_tail_bwd(const fn_encoder* e, const EncLayout& lay, const LayerActs& 
 // finishes, which is all the next L1 needs besides the rows themselves.  Rows whose gradient is completed elsewhere (the last
 // layer's: by the fragment tail / the gates / the edge-term backward) get their dots from k_gat_cu.  Weight-gradient partial
 // products and parameter reductions are queued for the two launches at the very end, as in the two-pass path.
-int encoder_backward_one(const fn_encoder* e, const EncLayout& lay, const BwdLayout& bw, const RngPlan& rng, const float* out_atoms,
-                         const float* out_frags, const float* out_bond, const float* out_fbond, const float* g_atoms, const float* g_frags,
-                         const float* g_bond, const float* g_fbond, const fn_layer_weights* grads, hipStream_t hs) {
-    const int H = e->heads, d = FN_D / H, wide = 2 * d + FN_D, NL = e->n_layers;
-    const float p = e->training ? e->drop_p : 0.f;
-    const bool lite = e->variant == 1, edge = e->variant == 2, no_fb = lite || edge;
-    const float gate_scale = p > 0.f ? (p < 1.f ? 1.f / (1.f - p) : 0.f) : 1.f;
+int encoder_backward_one(const fn_encoder* e, const EncLayout& lay, const BwdLayout& bw, const RngPlan& rng, const EncOutputs& y,
+                         const EncOutputs& gy, const fn_layer_weights* grads, hipStream_t hs) {
+    const int H = e->heads, NL = e->n_layers;
+    const bool no_fb = e->variant != 0;          // gat2_lite / gat2_edge: neither has a fragment-bond graph
     ReduceQueue rq;
     rq.st = hs;
     rq.defer_wgrad = true;
     rq.defer_mixed = tune(FN_TUNE_GEMM_COLAUNCH) != 0;
     rq.rider = e->adam_rider;
-    const fn_edge_term et_a{0, 0, 0, 0, nullptr, nullptr, nullptr, nullptr};
-    auto et_bond = [&](const fn_layer_weights& w) { return fn_edge_term{2, 1, d, d, nullptr, e->cos_sorted, w.emb_b_w, w.emb_b_b, lay.xs_bond}; };
-    auto et_fbond = [&](const fn_layer_weights& w) { return fn_edge_term{2, e->k_fattr, d, d, nullptr, e->fattr_sorted, w.emb_fb_w, w.emb_fb_b, lay.xs_fbond}; };
-    // a launch's resident workgroups are shared out among the levels it carries by their items (edges + rows: a bond row gathers
-    // twelve gradient rows where an atom row gathers four)
-    const int64_t one_total = tune(FN_TUNE_ONE_BLOCKS) > 0 ? tune(FN_TUNE_ONE_BLOCKS) : 768;
-    const int32_t* rr = pad_skip_on(e) ? reinterpret_cast<const int32_t*>(lay.real_rows) : nullptr;
-    const int32_t *nr_atoms = rr, *nr_bonds = rr ? rr + 1 : nullptr, *nr_conns = rr ? rr + 3 : nullptr;
-    auto one_level = [&](const float* g_out, const float* h, const float* p_sorted, const fn_edge_term& et, const float* att, int att_w,
-                         int src_off, const fn_gat_plan& pl, const LevelScratch& sc, float* g_s_orig, int* n_a, int* n_e, GatBwdOneArgs* A,
-                         int64_t rows_in_launch) -> int {
-        // (sharing a fixed total out by items -- fewer, longer-lived workgroups -- measured 40-50 us against 33 for the launch of layer l)
-        const int64_t share = 0;  (void)rows_in_launch;  (void)one_total;
-        FN_TRY(prep_gat_bwd_one(g_out, h, p_sorted, sc.cdot, sc.g_s_dst, &et, att, att_w, 0, src_off, &pl, 0.2f, sc.g_h, nullptr, g_s_orig,
-                                sc.part_a, n_a, sc.part_e, n_e, H, A, share));
+    struct Parts { int n_a = 0, n_e = 0; };      // partial rows a level's pass wrote (attention vector / edge embedding)
+    // a level's pass, prepared for the launch that carries it.  (Sharing a fixed total of workgroups out among the levels of a launch by
+    // their items -- fewer, longer-lived workgroups -- measured 40-50 us against 33 for the launch of layer l: every level sizes itself)
+    auto one_level = [&](const LevelView& v, const LevelScratch& sc, Parts* n, GatBwdOneArgs* A) -> int {
+        // (sc.dz: the atom level's dL/d(edge term) in original edge order; the other levels have none)
+        FN_TRY(prep_gat_bwd_one(bw.g_pre[v.lv], v.a.h, v.a.p, sc.cdot, sc.g_s_dst, &v.et, v.att, v.att_w, 0, v.src_off, v.pl, 0.2f, sc.g_h, nullptr, sc.dz,
+                                sc.part_a, &n->n_a, sc.part_e, &n->n_e, H, A));
         A->p_edge_major = 1;
-        A->n_real = &pl == &e->bond ? nr_bonds : (&pl == &e->atom ? nr_atoms : nr_conns);
+        A->n_real = v.n_real;
         A->dz_em = sc.dz_em;                                // non-null (this level's layer is deferred, bwd_layout): dz at destination-order slots, no g_s_dst read
         return 0;
     };
-    // the deferred term of a level's g_h rows, for the product that reads them / the weight-gradient kernels (null: not deferred)
-    struct DeferTerm { const float* dz; const float* gsd_c; GsdEpi gs; const float* a_dst; int att_w; };
-    // z: the projection's slot in EncLayout::rmat (3 l + {0: bond, 1: atom, 2: fragment bond}; layer 0 has no product)
-    auto gs_of = [&](const fn_gat_plan& pl, const LevelScratch& sc, const float* att, int att_w, int z) {
-        if (!sc.dz_em || pl.m <= 0) return DeferTerm{nullptr, nullptr, GsdEpi{nullptr, nullptr, 0, nullptr, nullptr}, nullptr, 0};
-        return DeferTerm{sc.dz_em, sc.g_s_dst, GsdEpi{sc.dz_em, pl.rowptr_d, pl.pos_base_d, lay.rmat + (size_t)z * 512, sc.g_s_dst}, att, att_w};
+    auto scratch = [&](const LevelView& v) -> const LevelScratch& { return bw.lv[v.layer][v.lv]; };
+    // rows of level v whose gradient is complete but whose dots no epilogue wrote: a task of k_gat_cu
+    auto cu_add = [&](CuTasks& T, const LevelView& v) {
+        const LevelScratch& sc = scratch(v);
+        if (v.rows > 0) T.t[T.n++] = CuTask{bw.g_pre[v.lv], v.a.raw, v.a.o2, v.a.sg, 1.f, sc.cdot, sc.g_s_dst, v.rows, 0, 0};
+    };
+    // ... or the epilogue of the product that finishes them (raw: the product's rows are gradients of the raw rows; else of y, whose
+    // saved copy stands in -- an inner layer's atom and fragment-bond rows get gradient through relu(dropout(.)) only)
+    auto cu_epi = [&](const LevelView& v, bool raw, bool dots = true) {
+        const LevelScratch& sc = scratch(v);
+        return CuEpi{raw ? v.a.raw : nullptr, v.a.o2, v.a.sg, dots ? sc.cdot : nullptr, sc.g_s_dst, H};
+    };
+    // deferred form, layer 0: g_s_dst and dL/da_dst of a level from its dz segments (k_gsd_seg), one block per block of the level's pass
+    auto seg_task = [&](const LevelView& v, const LevelScratch& sc, int n_a) {
+        return GsdSegTask{sc.dz_em, v.pl->rowptr_d, v.pl->pos_base_d, v.rows, sc.g_s_dst, v.n_real, v.a.h, sc.part_a, 0, n_a};
     };
 
-    bool have_atoms = false, have_bond = false, have_fbond = false;       // g_pre_* of the CURRENT layer complete, dots written
-    bool tail_dots_atoms = false, tail_dots_fbond = false;                // the fragment tail's launch wrote the last layer's dots
+    // ---- the last layer's output gradients: gates, the fragment levels, the scatter to the atoms
+    LastGrads top{};
+    FN_TRY(last_layer_output_grads(e, lay, bw, y, gy, grads, rq, true, hs, &top));
+    // g_pre of the CURRENT layer complete, dots written
+    bool have_atoms = top.have[LV_ATOM], have_bond = top.have[LV_BOND], have_fbond = top.have[LV_FBOND] && !no_fb;
     CuTasks cu_now{};         // rows of the current layer whose dots no product epilogue wrote
-    auto cu_add = [&](CuTasks& T, const float* g, const float* out, const float* out2, const float* sigma, const LevelScratch& sc, int64_t n) {
-        if (n > 0) T.t[T.n++] = CuTask{g, out, out2, sigma, 1.f, sc.cdot, sc.g_s_dst, n, 0, 0};
-    };
-
-    {   // ---- the last layer's output gradients: gates, the fragment levels, the scatter to the atoms
-        const int l = NL - 1;
-        const fn_layer_weights& w = e->w[l];
-        const fn_layer_weights& g = grads[l];
-        const LayerActs& a = lay.L[l];
-        const LevelScratch& sf = bw.frag;
-        const bool tail_mol = tail_mol_on(e) && (g_frags != nullptr || e->g_pooled != nullptr);
-        have_atoms = g_atoms != nullptr;  have_bond = g_bond != nullptr;  have_fbond = g_fbond != nullptr;
-        bool have_frags = g_frags != nullptr;
-        GateTasks G{};
-        auto add = [&](const float* gy, const float* y, float* o, int64_t numel) {
-            if (!gy) return;
-            GateTask& t = G.t[G.n++];
-            t.g = gy;  t.y = y;  t.o = o;  t.n4 = (numel + 3) / 4;  t.first = G.blocks;  t.nblk = flat_grid(t.n4, 512);
-            G.blocks += t.nblk;
-        };
-        if (!tail_mol) {
-            add(g_atoms, out_atoms, bw.g_pre_atoms, e->N * FN_D);
-            add(g_frags, out_frags, bw.g_pre_frags, e->F * FN_D);
-        }
-        add(g_bond, out_bond, bw.g_pre_bond, e->E * FN_D);
-        add(g_fbond, out_fbond, bw.g_pre_fbond, e->EF * FN_D);
-        if (G.blocks) {
-            G.scale = gate_scale;
-            hipLaunchKernelGGL(k_gate_many, dim3(G.blocks), dim3(kBlock), 0, hs, G);
-            FN_TRY(launch_status("fn_encoder_backward: activation backward"));
-        }
-        bool have_g_frags_h = false;
-        const float* g_frags_h = bw.g_frags;
-        int n_a = 0, n_e = 0;
-        if (tail_mol) {
-            int n_part = 0;
-            bool rode = false;
-            FN_TRY(launch_tail_bwd(e, lay, a, w, bw, out_atoms, out_frags, g_atoms, g_frags, gate_scale, have_fbond, &n_part, hs, true, &rode));
-            if (rode) rq.rider = nullptr;          // the head's Adam slice went with this launch
-            const fn_edge_term et_f{0, 0, 0, 0, nullptr, nullptr, nullptr, nullptr};
-            FN_TRY(rq.finalize(bw.frag.part_a, n_part, nullptr, 0, et_f, w.f, wide, 0, d + FN_D, g.f, nullptr, nullptr, H));
-            FN_TRY(rq.colsum(bw.frag.part_rd, n_part, H * FN_D, g.f, wide, d));
-            have_atoms = have_fbond = true;
-            tail_dots_atoms = true;  tail_dots_fbond = H == 4;
-        } else if (have_frags && lite) {
-            g_frags_h = bw.g_pre_frags;
-            have_g_frags_h = true;
-        } else if (have_frags && edge) {
-            fn_edge_term et_f{2, e->k_fattr, FN_D, d, nullptr, e->fattr_sorted, w.emb_fb_w, w.emb_fb_b};
-            FN_TRY(fn_gat_bwd_dst_f32(bw.g_pre_frags, a.frags, a.p_frag, &et_f, &e->frag, 0.2f, nullptr, nullptr, sf.pz, sf.g_s_dst, sf.part_e, &n_e, H, hs));
-            FN_TRY(fn_gat_bwd_src_f32(bw.g_pre_frags, a.frags, sf.pz, sf.g_s_dst, w.f, wide, 0, d + FN_D, &e->frag, bw.g_frags, sf.part_a, &n_a, H, hs));
-            FN_TRY(rq.finalize(sf.part_a, n_a, sf.part_e, n_e, et_f, w.f, wide, 0, d + FN_D, g.f, g.emb_fb_w, g.emb_fb_b, H));
-            have_g_frags_h = true;
-        } else if (have_frags) {
-            fn_edge_term et_f{0, 0, 0, 0, nullptr, nullptr, nullptr, nullptr};
-            FN_TRY(fn_gat_bwd_dst_f32(bw.g_pre_frags, a.frags, a.p_frag, &et_f, &e->frag, 0.2f, nullptr, sf.dz, sf.pz, sf.g_s_dst, nullptr, &n_e, H, hs));
-            int gr = 0;
-            FN_TRY(bwd_src_and_edge_term(bw.g_pre_frags, a.frags, sf.pz, sf.g_s_dst, w.f, wide, 0, d + FN_D, &e->frag, bw.g_frags, sf.part_a, &n_a,
-                                         sf.dz, a.new_fbond, d, bw.g_pre_fbond, sf.part_rd, have_fbond, &gr, H, hs));
-            if (gr) have_fbond = true;
-            FN_TRY(rq.finalize(sf.part_a, n_a, nullptr, 0, et_f, w.f, wide, 0, d + FN_D, g.f, nullptr, nullptr, H));
-            if (gr) FN_TRY(rq.colsum(sf.part_rd, gr, H * FN_D, g.f, wide, d));
-            have_g_frags_h = true;
-        }
-        if (have_g_frags_h) {
-            FN_TRY(launch_gather_rows4(g_frags_h, e->a2f.index, bw.g_pre_atoms, e->N, 32, have_atoms ? (const float*)bw.g_pre_atoms : (const float*)nullptr, hs,
-                                       "fn_encoder_backward: gather(a2f)"));
-            have_atoms = true;
-        }
-        if (no_fb) have_fbond = false;
-        if (have_atoms && !tail_dots_atoms) cu_add(cu_now, bw.g_pre_atoms, lay.atoms_new, a.o2_atom, a.sg_atom, bw.atom[l], e->N);
-    }
+    if (have_atoms && !top.tail_dots_atoms) cu_add(cu_now, level_view(e, lay, NL - 1, LV_ATOM));
 
     GsdSegTasks seg0{};       // deferred form: layer 0's levels have no input-gradient product to form g_s_dst in: k_gsd_seg at the end
     bool pend_b = false, pend_fb = false;        // bond / fragment-bond level of layer l+1: gradient rows and dots ready, pass not launched
     for (int l = NL - 1; l >= 0; --l) {
-        const fn_layer_weights& w = e->w[l];
-        const fn_layer_weights& g = grads[l];
-        const LayerActs& a = lay.L[l];
         const bool last = l + 1 == NL;
-        const float* in_atoms = l ? lay.L[l - 1].y_atoms : (lay.in_atoms0 ? lay.in_atoms0 : e->x_atoms);
-        const int ka = l ? FN_D : e->k_atom0;
-        const LevelScratch& sa = bw.atom[l];
+        // this layer's levels (the atom level runs now; the other two receive their gradient rows), the atom level below, and the bond /
+        // fragment-bond levels of layer l+1, which run now
+        const LevelView va = level_view(e, lay, l, LV_ATOM), vb = level_view(e, lay, l, LV_BOND), vfb = level_view(e, lay, l, LV_FBOND);
+        const LevelView va_below = l ? level_view(e, lay, l - 1, LV_ATOM) : LevelView{};
+        const LevelView vb_up = last ? LevelView{} : level_view(e, lay, l + 1, LV_BOND), vfb_up = last ? LevelView{} : level_view(e, lay, l + 1, LV_FBOND);
+        const LevelWeights ga = level_weights(grads[l], LV_ATOM);
+        const LevelScratch& sa = bw.lv[l][LV_ATOM];
         if (cu_now.n) { FN_TRY(launch_gat_cu(cu_now, H, hs));  cu_now = CuTasks{}; }
 
         // ---- L1: the atom level of this layer beside the bond / fragment-bond levels of layer l+1
         GatBwdOneArgs oB{}, oA{}, oFB{};
-        int na_b = 0, ne_b = 0, na_a = 0, ne_a = 0, na_fb = 0, ne_fb = 0;
-        const int64_t rows_l1 = (pend_b ? e->bond.m + e->E : 0) + (have_atoms ? e->atom.m + e->N : 0) + (pend_fb ? e->fbond.m + e->EF : 0);
-        if (pend_b) {
-            const fn_layer_weights& wn = e->w[l + 1];
-            FN_TRY(one_level(bw.g_pre_bond, lay.L[l + 1].h_b, lay.L[l + 1].p_bond, et_bond(wn), wn.a_b, 3 * d, 2 * d, e->bond, bw.bond[l + 1], nullptr, &na_b, &ne_b, &oB, rows_l1));
-        }
-        if (have_atoms) FN_TRY(one_level(bw.g_pre_atoms, a.h_a, a.p_atom, et_a, w.a, wide, d + FN_D, e->atom, sa, sa.dz, &na_a, &ne_a, &oA, rows_l1));
-        if (pend_fb) {
-            const fn_layer_weights& wn = e->w[l + 1];
-            FN_TRY(one_level(bw.g_pre_fbond, lay.L[l + 1].h_fb, lay.L[l + 1].p_fbond, et_fbond(wn), wn.f_a_b, 3 * d, 2 * d, e->fbond, bw.fbond[l + 1], nullptr, &na_fb, &ne_fb, &oFB, rows_l1));
-        }
+        Parts nb, na, nfb;
+        if (pend_b) FN_TRY(one_level(vb_up, scratch(vb_up), &nb, &oB));
+        if (have_atoms) FN_TRY(one_level(va, sa, &na, &oA));
+        if (pend_fb) FN_TRY(one_level(vfb_up, scratch(vfb_up), &nfb, &oFB));
         FN_TRY(launch_gat_bwd_one3(oB, oA, oFB, H, hs));
 
         // ---- L2: input-gradient products of what L1 produced (+ the atom graph's edge term), and the deferred parameter work
         LinTasks T{};
         CuTasks cu_after{};       // rows finished in L2 whose dots the epilogue could not write
-        auto product = [&](const float* gh, const float* W, const float* Wt, float* gy, int64_t rows, const fn_act_epilogue& mk, const RowAdd* ra,
-                           const CuEpi& cu, const int32_t* n_real, const GsdEpi& gs) {
+        // dX of level v's projection: the gradient rows of the same level one layer down (`below`), gated by that layer's dropout mask and ReLU
+        auto product = [&](const LevelView& v, const LevelView& below, const RowAdd* ra, const CuEpi& cu, const GsdEpi& gs) {
             LinTask& t = T.t[T.n++];
-            t = LinTask{Wt, gh, W, nullptr, gy, rows, mk, NodeScalarEpi{nullptr, nullptr, nullptr, 0, 0, 0, 0}, 0, 0};
+            t = LinTask{v.Wt, scratch(v).g_h, v.W, nullptr, bw.g_pre[v.lv], v.rows, act_epilogue(e, rng, below, below.a.y),
+                        NodeScalarEpi{nullptr, nullptr, nullptr, 0, 0, 0, 0}, 0, 0};
             if (ra) t.ra = *ra;
             t.cu = cu;
             t.gs = gs;
-            t.n_real = n_real;
+            t.n_real = v.n_real;
         };
         bool nxt_bond = false, nxt_fbond = false, nxt_atoms = false;
         const bool rd_rows_ride = have_atoms && pend_b && H == 4 && e->atom.m_real == e->E && e->E > 0;   // the bond product of layer l+1 carries the rows' term
         const int gr = have_atoms && e->atom.m_real > 0 ? row_grid(e->atom.m_real, tune(FN_TUNE_RD_BLOCKS) > 0 ? tune(FN_TUNE_RD_BLOCKS) : kRowDotsBwdBlocks) : 0;
         if (pend_b) {        // layer l+1's bond level: parameter work + dL/d(pre-activation bond output of layer l)
-            const fn_layer_weights& wn = e->w[l + 1];
-            const fn_layer_weights& gn = grads[l + 1];
-            const LevelScratch& sb = bw.bond[l + 1];
-            const DeferTerm gsb = gs_of(e->bond, sb, wn.a_b, 3 * d, 3 * (l + 1));
-            FN_TRY(rq.reserve(2));
-            FN_TRY(rq.finalize(sb.part_a, na_b, sb.part_e, ne_b, et_bond(wn), wn.a_b, 3 * d, 0, 2 * d, gn.a_b, gn.emb_b_w, gn.emb_b_b, H,
-                               gsb.dz ? sb.upart : nullptr, wn.proj_b_w, wn.proj_b_b, FN_D));
-            FN_TRY(rq.wgrad(sb.g_h, a.y_bond, FN_D, e->E, sb.wg_ws, gn.proj_b_w, gn.proj_b_b, hs, nr_bonds, gsb.gsd_c, gsb.a_dst, gsb.att_w, sb.upart, rq.last_index));
-            const fn_act_epilogue mk{const_cast<float*>(a.y_bond), p, 1, e->seed, rng.y[l][2], e->offset_dev};
-            const RowAdd ra{sa.dz, w.a + d, wide};
+            const DeferTerm df = defer_term(vb_up, scratch(vb_up));
+            FN_TRY(rq.level_params(vb_up, level_weights(grads[l + 1], LV_BOND), scratch(vb_up), ParamWork{nb.n_a, nb.n_e, true, &df, true, true}, hs));
+            const RowAdd ra{sa.dz, va.att + va.mid_off, va.att_w};
             // the rows are complete in this epilogue unless the edge term's rows' part is added behind the product (no RowAdd carrier)
             const bool complete = rd_rows_ride || gr == 0;
-            const CuEpi cu{a.new_bond, a.o2_bond, a.sg_bond, complete ? bw.bond[l].cdot : nullptr, bw.bond[l].g_s_dst, H};
-            product(sb.g_h, wn.proj_b_w, lay.bt + (size_t)(3 * (l + 1)) * 192 * FN_D, bw.g_pre_bond, e->E, mk, rd_rows_ride ? &ra : nullptr, cu, nr_bonds, gsb.gs);
-            if (!complete) cu_add(cu_after, bw.g_pre_bond, a.new_bond, a.o2_bond, a.sg_bond, bw.bond[l], e->E);
+            product(vb_up, vb, rd_rows_ride ? &ra : nullptr, cu_epi(vb, true, complete), df.gs);
+            if (!complete) cu_add(cu_after, vb);
             nxt_bond = true;
         }
         if (pend_fb) {
-            const fn_layer_weights& wn = e->w[l + 1];
-            const fn_layer_weights& gn = grads[l + 1];
-            const LevelScratch& sfb = bw.fbond[l + 1];
-            const DeferTerm gsf = gs_of(e->fbond, sfb, wn.f_a_b, 3 * d, 3 * (l + 1) + 2);
-            FN_TRY(rq.reserve(2));
-            FN_TRY(rq.finalize(sfb.part_a, na_fb, sfb.part_e, ne_fb, et_fbond(wn), wn.f_a_b, 3 * d, 0, 2 * d, gn.f_a_b, gn.emb_fb_w, gn.emb_fb_b, H,
-                               gsf.dz ? sfb.upart : nullptr, wn.proj_fb_w, wn.proj_fb_b, FN_D));
-            FN_TRY(rq.wgrad(sfb.g_h, a.y_fbond, FN_D, e->EF, sfb.wg_ws, gn.proj_fb_w, gn.proj_fb_b, hs, nr_conns, gsf.gsd_c, gsf.a_dst, gsf.att_w, sfb.upart, rq.last_index));
-            const fn_act_epilogue mk{const_cast<float*>(a.y_fbond), p, 1, e->seed, rng.y[l][3], e->offset_dev};
-            // this layer's fragment-bond rows get gradient through relu(dropout(.)) only (the fragment graph's edge term exists in the
-            // last layer alone): the gate's saved output stands in for the raw row
-            const CuEpi cu{nullptr, a.o2_fbond, a.sg_fbond, bw.fbond[l].cdot, bw.fbond[l].g_s_dst, H};
-            product(sfb.g_h, wn.proj_fb_w, lay.bt + (size_t)(3 * (l + 1) + 2) * 192 * FN_D, bw.g_pre_fbond, e->EF, mk, nullptr, cu, nr_conns, gsf.gs);
+            const DeferTerm df = defer_term(vfb_up, scratch(vfb_up));
+            FN_TRY(rq.level_params(vfb_up, level_weights(grads[l + 1], LV_FBOND), scratch(vfb_up), ParamWork{nfb.n_a, nfb.n_e, true, &df, true, true}, hs));
+            // (the fragment graph's edge term, the only reader of raw fragment-bond rows, exists in the last layer alone)
+            product(vfb_up, vfb, nullptr, cu_epi(vfb, false), df.gs);
             nxt_fbond = true;
         }
         RowDotsBwdArgs R{};
         if (have_atoms) {
-            const DeferTerm gsa = gs_of(e->atom, sa, w.a, wide, 3 * l + 1);
+            const DeferTerm df = defer_term(va, sa);
             // (layer 0 has no input-gradient product to form g_s_dst in: k_gsd_seg at the end of the pass, which also leaves dL/da_dst)
-            const bool seg_a = gsa.dz && l == 0 && na_a > 0;
-            if (seg_a) seg0.t[seg0.n++] = GsdSegTask{sa.dz_em, e->atom.rowptr_d, e->atom.pos_base_d, e->N, sa.g_s_dst, nr_atoms, a.h_a, sa.part_a, 0, na_a};
-            const bool up_a = gsa.dz && !seg_a;
-            FN_TRY(rq.reserve(2));
-            FN_TRY(rq.finalize(sa.part_a, na_a, nullptr, 0, et_a, w.a, wide, 0, d + FN_D, g.a, nullptr, nullptr, H,
-                               up_a ? sa.upart : nullptr, w.proj_a_w, w.proj_a_b, ka));
-            FN_TRY(rq.wgrad(sa.g_h, in_atoms, ka, e->N, sa.wg_ws, g.proj_a_w, g.proj_a_b, hs, nr_atoms, gsa.gsd_c, gsa.a_dst, gsa.att_w,
-                            up_a ? sa.upart : nullptr, rq.last_index));
+            const bool seg_a = df.dz && l == 0 && na.n_a > 0;
+            if (seg_a) seg0.t[seg0.n++] = seg_task(va, sa, na.n_a);
+            FN_TRY(rq.level_params(va, ga, sa, ParamWork{na.n_a, 0, true, &df, df.dz && !seg_a, true}, hs));
             if (l) {
-                const fn_act_epilogue mk{const_cast<float*>(lay.L[l - 1].y_atoms), p, 1, e->seed, rng.y[l - 1][0], e->offset_dev};
-                const CuEpi cu{nullptr, lay.L[l - 1].o2_atom, lay.L[l - 1].sg_atom, bw.atom[l - 1].cdot, bw.atom[l - 1].g_s_dst, H};
-                product(sa.g_h, w.proj_a_w, lay.bt + (size_t)(3 * l + 1) * 192 * FN_D, bw.g_pre_atoms, e->N, mk, nullptr, cu, nr_atoms, gsa.gs);
+                product(va, va_below, nullptr, cu_epi(va_below, false), df.gs);
                 nxt_atoms = true;
             }
             // the edge term <new_bond[e], a[:, d:d+128]> of the atom graph: parameter partials always; the rows' term (dL/dnew_bond)
             // rides in the bond product above, or -- no product to ride in (top layer, H != 4) -- is written / accumulated here
             if (gr) {
                 const bool have_b_now = pend_b || (last && have_bond);
-                R = RowDotsBwdArgs{sa.dz, a.new_bond, w.a, wide, d, H, e->atom, rd_rows_ride ? nullptr : bw.g_pre_bond, sa.part_rd,
-                                   (!rd_rows_ride && have_b_now) ? (const float*)bw.g_pre_bond : nullptr, 1, gr};
-                R.n_real = nr_bonds;
-                FN_TRY(rq.colsum(sa.part_rd, gr, H * FN_D, g.a, wide, d));
+                R = RowDotsBwdArgs{sa.dz, vb.a.raw, va.att, va.att_w, va.mid_off, H, *va.pl, rd_rows_ride ? nullptr : bw.g_pre[LV_BOND], sa.part_rd,
+                                   (!rd_rows_ride && have_b_now) ? (const float*)bw.g_pre[LV_BOND] : nullptr, 1, gr};
+                R.n_real = vb.n_real;
+                FN_TRY(rq.colsum(sa.part_rd, gr, H * FN_D, ga.att, va.att_w, va.mid_off));
                 if (!pend_b) {
                     // the bond rows of this layer are finished by the edge term's rows' part: with four heads it writes their dots too
-                    if (H == 4 && e->atom.m_real == e->E) { R.cu_out2 = a.o2_bond;  R.cu_sigma = a.sg_bond;  R.cu_c = bw.bond[l].cdot;  R.cu_u = bw.bond[l].g_s_dst; }
-                    else cu_add(cu_after, bw.g_pre_bond, a.new_bond, a.o2_bond, a.sg_bond, bw.bond[l], e->E);
+                    const LevelScratch& sb = scratch(vb);
+                    if (H == 4 && e->atom.m_real == e->E) { R.cu_out2 = vb.a.o2;  R.cu_sigma = vb.a.sg;  R.cu_c = sb.cdot;  R.cu_u = sb.g_s_dst; }
+                    else cu_add(cu_after, vb);
                 }
                 nxt_bond = true;
             }
@@ -1704,8 +1820,8 @@ int encoder_backward_one(const fn_encoder* e, const EncLayout& lay, const BwdLay
 
         // ---- what the next iteration's L1 finds
         if (last) {
-            if (have_bond && !nxt_bond) cu_add(cu_after, bw.g_pre_bond, a.new_bond, a.o2_bond, a.sg_bond, bw.bond[l], e->E);
-            if (have_fbond && !tail_dots_fbond) cu_add(cu_after, bw.g_pre_fbond, a.new_fbond, a.o2_fbond, a.sg_fbond, bw.fbond[l], e->EF);
+            if (have_bond && !nxt_bond) cu_add(cu_after, vb);
+            if (have_fbond && !top.tail_dots_fbond) cu_add(cu_after, vfb);
             nxt_bond = nxt_bond || have_bond;
             nxt_fbond = nxt_fbond || have_fbond;
         }
@@ -1717,20 +1833,18 @@ int encoder_backward_one(const fn_encoder* e, const EncLayout& lay, const BwdLay
     }
     {   // the bond / fragment-bond levels of layer 0
         if (cu_now.n) FN_TRY(launch_gat_cu(cu_now, H, hs));
-        const fn_layer_weights& w0 = e->w[0];
-        const fn_layer_weights& g0 = grads[0];
+        const LevelView vb = level_view(e, lay, 0, LV_BOND), vfb = level_view(e, lay, 0, LV_FBOND);
+        const LevelScratch &sb = scratch(vb), &sfb = scratch(vfb);
         GatBwdOneArgs oB{}, oFB{};
-        int na_b = 0, ne_b = 0, na_fb = 0, ne_fb = 0;
-        const int64_t rows_l1 = (pend_b ? e->bond.m + e->E : 0) + (pend_fb ? e->fbond.m + e->EF : 0);
-        if (pend_b) FN_TRY(one_level(bw.g_pre_bond, lay.L[0].h_b, lay.L[0].p_bond, et_bond(w0), w0.a_b, 3 * d, 2 * d, e->bond, bw.bond[0], nullptr, &na_b, &ne_b, &oB, rows_l1));
-        if (pend_fb) FN_TRY(one_level(bw.g_pre_fbond, lay.L[0].h_fb, lay.L[0].p_fbond, et_fbond(w0), w0.f_a_b, 3 * d, 2 * d, e->fbond, bw.fbond[0], nullptr, &na_fb, &ne_fb, &oFB, rows_l1));
+        Parts nb, nfb;
+        if (pend_b) FN_TRY(one_level(vb, sb, &nb, &oB));
+        if (pend_fb) FN_TRY(one_level(vfb, sfb, &nfb, &oFB));
         FN_TRY(prof_event(2, hs));
         FN_TRY(launch_gat_bwd_one3(oB, GatBwdOneArgs{}, oFB, H, hs));
         FN_TRY(prof_event(3, hs));
-        const DeferTerm gsb = gs_of(pend_b ? e->bond : fn_gat_plan{}, bw.bond[0], w0.a_b, 3 * d, 0);
-        const DeferTerm gsf = gs_of(pend_fb ? e->fbond : fn_gat_plan{}, bw.fbond[0], w0.f_a_b, 3 * d, 2);
-        if (gsb.dz && na_b > 0) seg0.t[seg0.n++] = GsdSegTask{gsb.dz, e->bond.rowptr_d, e->bond.pos_base_d, e->E, bw.bond[0].g_s_dst, nr_bonds, lay.L[0].h_b, bw.bond[0].part_a, 0, na_b};
-        if (gsf.dz && na_fb > 0) seg0.t[seg0.n++] = GsdSegTask{gsf.dz, e->fbond.rowptr_d, e->fbond.pos_base_d, e->EF, bw.fbond[0].g_s_dst, nr_conns, lay.L[0].h_fb, bw.fbond[0].part_a, 0, na_fb};
+        const DeferTerm dfb = pend_b ? defer_term(vb, sb) : DeferTerm{}, dff = pend_fb ? defer_term(vfb, sfb) : DeferTerm{};
+        if (dfb.dz && nb.n_a > 0) seg0.t[seg0.n++] = seg_task(vb, sb, nb.n_a);
+        if (dff.dz && nfb.n_a > 0) seg0.t[seg0.n++] = seg_task(vfb, sfb, nfb.n_a);
         if (seg0.n) {         // g_s_dst and dL/da_dst of layer 0's levels (the inner layers' come out of their products' epilogues and the
             int blocks = 0;   // weight-gradient kernels' side product): one small launch, a block per block of the level's pass
             for (int i = 0; i < seg0.n; ++i) {
@@ -1743,18 +1857,8 @@ int encoder_backward_one(const fn_encoder* e, const EncLayout& lay, const BwdLay
             FN_TRY(launch_gsd_seg(seg0, blocks, hs));
             FN_TRY(launch_status("one-pass backward, deferred form: g_s_dst of layer 0"));
         }
-        if (pend_b) {
-            FN_TRY(rq.reserve(2));
-            FN_TRY(rq.finalize(bw.bond[0].part_a, na_b, bw.bond[0].part_e, ne_b, et_bond(w0), w0.a_b, 3 * d, 0, 2 * d, g0.a_b, g0.emb_b_w, g0.emb_b_b, H));
-            FN_TRY(rq.wgrad(bw.bond[0].g_h, e->bond_nodes, e->k_bond0, e->E, bw.bond[0].wg_ws, g0.proj_b_w, g0.proj_b_b, hs, nr_bonds,
-                            gsb.gsd_c, gsb.a_dst, gsb.att_w, nullptr, -1));
-        }
-        if (pend_fb) {
-            FN_TRY(rq.reserve(2));
-            FN_TRY(rq.finalize(bw.fbond[0].part_a, na_fb, bw.fbond[0].part_e, ne_fb, et_fbond(w0), w0.f_a_b, 3 * d, 0, 2 * d, g0.f_a_b, g0.emb_fb_w, g0.emb_fb_b, H));
-            FN_TRY(rq.wgrad(bw.fbond[0].g_h, e->fbond_nodes, e->k_fbond0, e->EF, bw.fbond[0].wg_ws, g0.proj_fb_w, g0.proj_fb_b, hs, nr_conns,
-                            gsf.gsd_c, gsf.a_dst, gsf.att_w, nullptr, -1));
-        }
+        if (pend_b) FN_TRY(rq.level_params(vb, level_weights(grads[0], LV_BOND), sb, ParamWork{nb.n_a, nb.n_e, true, &dfb}, hs));
+        if (pend_fb) FN_TRY(rq.level_params(vfb, level_weights(grads[0], LV_FBOND), sfb, ParamWork{nfb.n_a, nfb.n_e, true, &dff}, hs));
     }
     return rq.flush(true);
 }
@@ -1818,40 +1922,30 @@ static int encoder_forward_impl(const fn_encoder* e, const fn_row_masks* masks, 
     if (lay.total > e->ws_floats) return fail(FN_EINVAL, "fn_encoder_forward: workspace too small");
     latch_form(e);
     const RngPlan rng = rng_plan(e);
-    const int H = e->heads, d = FN_D / H;
+    const int H = e->heads;
     const float p = e->training ? e->drop_p : 0.f;
-    const int wide = 2 * d + FN_D;             // width of a / f
     const bool lite = e->variant == 1, edge = e->variant == 2;      // gat2_lite / gat2_edge: neither has a fragment-bond graph
     const bool no_fb = lite || edge;
     // the atom graph's edge term <new_bond, a[:, d:d+128]> is produced by the bond-graph kernel's epilogue (one launch less per layer)
     const bool fuse_rd = tune(FN_TUNE_FUSE_ROWDOTS) != 0 && e->atom.m > 0 && e->atom.m_real == e->E;
     // projections ride along with the attention launches they do not depend on (k_gat_*_lin); needs the node scalars in the GEMM epilogue
     const bool colaunch = H >= 2 && tune(FN_TUNE_GEMM_COLAUNCH) != 0;
-    const fn_act_epilogue no_act_l{nullptr, 0.f, 0, 0, 0, nullptr};
     // the backward will be one source-owner pass per level: the attention kernels also write out2 / sigma, probabilities edge-major
     const bool one = one_pass_on(e);
     // an evaluation pass that nobody differentiates (fn_encoder.no_backward) saves nothing for a backward pass: no probabilities, and no
     // raw bond rows once the atom graph's edge term is formed in the bond level's own launch
     const bool no_bwd = !e->training && e->no_backward != 0;
-    // real rows per index space (device words written by the prologue below): the kernels skip the padding behind them
-    const int32_t* rr = pad_skip_on(e) ? reinterpret_cast<const int32_t*>(lay.real_rows) : nullptr;
-    const int32_t *nr_atoms = rr, *nr_bonds = rr ? rr + 1 : nullptr, *nr_conns = rr ? rr + 3 : nullptr;
     const fni::FwdMask mk_atoms{masks ? masks->atoms : nullptr}, mk_bonds{masks ? masks->bonds : nullptr}, mk_fbonds{masks ? masks->fbonds : nullptr};
     const fni::FwdMask *pm_atoms = masks ? &mk_atoms : nullptr, *pm_bonds = masks ? &mk_bonds : nullptr, *pm_fbonds = masks ? &mk_fbonds : nullptr;
 
-    const float* in_atoms = lay.in_atoms0 ? lay.in_atoms0 : e->x_atoms;
-    const float* in_bond = e->bond_nodes;
-    const float* in_fbond = e->fbond_nodes;
-    int ka = e->k_atom0, kb = e->k_bond0, kfb = e->k_fbond0;
-
     {   // one launch: W^T of every projection, dropout(x_atoms), destination-order edge attributes
         EncPrologue A{};
-        for (int l = 0; l < e->n_layers; ++l) {
-            A.tm.W[3 * l] = e->w[l].proj_b_w;       A.tm.K[3 * l] = l ? FN_D : e->k_bond0;
-            A.tm.W[3 * l + 1] = e->w[l].proj_a_w;   A.tm.K[3 * l + 1] = l ? FN_D : e->k_atom0;
-            A.tm.W[3 * l + 2] = e->w[l].proj_fb_w;  A.tm.K[3 * l + 2] = l ? FN_D : e->k_fbond0;
-            if (!A.tm.W[3 * l] || !A.tm.W[3 * l + 1] || !A.tm.W[3 * l + 2]) return fail(FN_EINVAL, "fn_encoder_forward: null projection weight");
-        }
+        for (int l = 0; l < e->n_layers; ++l)
+            for (Level v : kProjected) {
+                const LevelView lv = level_view(e, lay, l, v);
+                A.tm.W[3 * l + v] = lv.W;  A.tm.K[3 * l + v] = lv.K;
+                if (!lv.W) return fail(FN_EINVAL, "fn_encoder_forward: null projection weight");
+            }
         A.bt_base = lay.bt;
         A.n_t = 24 * 3 * e->n_layers;
         if (lay.in_atoms0) {
@@ -1890,10 +1984,10 @@ static int encoder_forward_impl(const fn_encoder* e, const fn_row_masks* masks, 
         if (defer_on(e)) {        // R of every K = 128 projection (layers >= 1): slot 3 l + {0: bond, 1: atom, 2: fragment bond}
             for (int l = 1; l < e->n_layers; ++l) {
                 if (!defer_on(e, l)) continue;
-                const fn_layer_weights& wl = e->w[l];
-                A.rW[3 * l] = wl.proj_b_w;       A.rA[3 * l] = wl.a_b;        A.rAw[3 * l] = 3 * d;
-                A.rW[3 * l + 1] = wl.proj_a_w;   A.rA[3 * l + 1] = wl.a;      A.rAw[3 * l + 1] = wide;
-                A.rW[3 * l + 2] = wl.proj_fb_w;  A.rA[3 * l + 2] = wl.f_a_b;  A.rAw[3 * l + 2] = 3 * d;
+                for (Level v : kProjected) {
+                    const LevelView lv = level_view(e, lay, l, v);
+                    A.rW[3 * l + v] = lv.W;  A.rA[3 * l + v] = lv.att;  A.rAw[3 * l + v] = lv.att_w;
+                }
             }
             A.rOut = lay.rmat;
             A.n_r = 2 * 3 * e->n_layers;
@@ -1903,90 +1997,79 @@ static int encoder_forward_impl(const fn_encoder* e, const fn_row_masks* masks, 
     }
 
     for (int l = 0; l < e->n_layers; ++l) {
-        const fn_layer_weights& w = e->w[l];
-        const LayerActs& a = lay.L[l];
+        const LevelView vb = level_view(e, lay, l, LV_BOND), va = level_view(e, lay, l, LV_ATOM), vfb = level_view(e, lay, l, LV_FBOND);
+        const LevelView vf = level_view(e, lay, l, LV_FRAG);
         const bool last = l + 1 == e->n_layers;
-        const float* bt_b = lay.bt + (size_t)(3 * l) * 192 * FN_D;
-        const float* bt_a = lay.bt + (size_t)(3 * l + 1) * 192 * FN_D;
-        const float* bt_fb = lay.bt + (size_t)(3 * l + 2) * 192 * FN_D;
 
-        float* y_atoms = last ? out_atoms : a.y_atoms;
-        float* y_frags = last ? out_frags : a.y_frags;
+        float* y_atoms = last ? out_atoms : va.a.y;
+        float* y_frags = last ? out_frags : vf.a.y;
         // out_bond / out_fbond == null: the caller reads neither (a finetune head pools atoms and fragments only, gat2.py:816-826): the last
         // layer's activated bond / fragment-bond rows are not stored.  The launches are prepared with a stand-in pointer (shape and instance
         // as with the store) and the epilogue's target is cleared afterwards.
         const bool drop_edge_out = last && out_bond == nullptr;
-        float* y_bond = last ? (out_bond ? out_bond : a.new_bond) : a.y_bond;
-        float* y_fbond = last ? (out_fbond ? out_fbond : a.new_fbond) : a.y_fbond;
+        float* y_bond = last ? (out_bond ? out_bond : vb.a.raw) : vb.a.y;
+        float* y_fbond = last ? (out_fbond ? out_fbond : vfb.a.raw) : vfb.a.y;
         // act(dropout(.)) of the four layer outputs rides in the producing kernels' epilogues
-        const fn_act_epilogue ep_atoms{y_atoms, p, 1, e->seed, rng.y[l][0], e->offset_dev}, ep_frags{y_frags, p, 1, e->seed, rng.y[l][1], e->offset_dev};
-        const fn_act_epilogue ep_bond{y_bond, p, 1, e->seed, rng.y[l][2], e->offset_dev}, ep_fbond{y_fbond, p, 1, e->seed, rng.y[l][3], e->offset_dev};
+        const fn_act_epilogue ep_atoms = act_epilogue(e, rng, va, y_atoms), ep_frags = act_epilogue(e, rng, vf, y_frags);
+        const fn_act_epilogue ep_bond = act_epilogue(e, rng, vb, y_bond), ep_fbond = act_epilogue(e, rng, vfb, y_fbond);
         // L1 bond graph
         const bool fuse_ns = H >= 2;         // a head's columns fit one wave's 64-column half for H >= 2
-        auto project = [&](const float* x, int k, const float* bt, const float* bias, float* hout, int64_t rows,
-                           const float* att, int att_w, int src_off, float* sdst, float* ssrc, fn_stream_t sq) -> int {
-            if (fuse_ns) return launch_linear128_ns(x, k, bt, bias, hout, rows, nullptr, NodeScalarEpi{att, sdst, ssrc, att_w, 0, src_off, H}, sq);
-            FN_TRY(fn_linear128_f32(x, k, bt, bias, hout, rows, nullptr, sq));
-            return fn_node_scalars_f32(hout, att, att_w, 0, src_off, sdst, ssrc, rows, H, sq);
+        auto project = [&](const LevelView& v) -> int {       // a level's projection as a launch of its own
+            if (fuse_ns) return launch_linear128_ns(v.x, v.K, v.Wt, v.bias, v.a.h, v.rows, nullptr, node_scalars(v), st);
+            FN_TRY(fn_linear128_f32(v.x, v.K, v.Wt, v.bias, v.a.h, v.rows, nullptr, st));
+            return fn_node_scalars_f32(v.a.h, v.att, v.att_w, 0, v.src_off, v.s_dst, v.s_src, v.rows, H, st);
         };
         // layers >= 1: the three projections (K = 128) depend only on the previous layer.  With co-launching (FN_TUNE_GEMM_COLAUNCH)
         // the bond / fragment-bond projections already ran beside the previous layer's atom level and the atom projection rides
         // with this layer's bond levels below; otherwise one grouped launch for the three
         const bool grouped = l > 0 && fuse_ns;
         bool atoms_projected = false;
-        const fn_act_epilogue no_act{nullptr, 0.f, 0, 0, 0, nullptr};
         LinTasks with_pair{};                      // rides with the bond + fragment-bond launch of this layer
         if (grouped && colaunch) {
             with_pair.n = 1;
-            with_pair.t[0] = LinTask{w.proj_a_w, in_atoms, bt_a, w.proj_a_b, a.h_a, e->N, no_act,
-                                     NodeScalarEpi{w.a, lay.s_dst_a, lay.s_src_a, wide, 0, d + FN_D, H}, 0, 0};
-            with_pair.t[0].n_real = nr_atoms;
+            with_pair.t[0] = proj_task(va);
         } else if (grouped) {
             LinTasks T{};
             T.n = no_fb ? 2 : 3;
-            T.t[0] = LinTask{w.proj_b_w, in_bond, bt_b, w.proj_b_b, a.h_b, e->E, no_act,
-                             NodeScalarEpi{w.a_b, lay.s_dst, lay.s_src, 3 * d, 0, 2 * d, H}, 0, 0};
-            T.t[1] = LinTask{w.proj_a_w, in_atoms, bt_a, w.proj_a_b, a.h_a, e->N, no_act,
-                             NodeScalarEpi{w.a, lay.s_dst_a, lay.s_src_a, wide, 0, d + FN_D, H}, 0, 0};
-            T.t[2] = LinTask{w.proj_fb_w, in_fbond, bt_fb, w.proj_fb_b, a.h_fb, e->EF, no_act,
-                             NodeScalarEpi{w.f_a_b, lay.s_dst_fb, lay.s_src_fb, 3 * d, 0, 2 * d, H}, 0, 0};
-            T.t[0].n_real = nr_bonds;  T.t[1].n_real = nr_atoms;  T.t[2].n_real = nr_conns;
+            T.t[0] = proj_task(vb);  T.t[1] = proj_task(va);  T.t[2] = proj_task(vfb);
             FN_TRY(launch_linear128_group(T, S(st)));
-        } else if (l == 0 && fuse_ns && !no_fb && kb <= 20 && kfb <= 20) {
+        } else if (l == 0 && fuse_ns && !no_fb && vb.K <= 20 && vfb.K <= 20) {
             LinTasks T{};                               // layer 0: both edge-feature projections have K <= 20 -> one launch
             T.n = 2;
-            T.t[0] = LinTask{w.proj_b_w, in_bond, bt_b, w.proj_b_b, a.h_b, e->E, fn_act_epilogue{nullptr, 0.f, 0, 0, 0, nullptr},
-                             NodeScalarEpi{w.a_b, lay.s_dst, lay.s_src, 3 * d, 0, 2 * d, H}, 0, 0, kb};
-            T.t[1] = LinTask{w.proj_fb_w, in_fbond, bt_fb, w.proj_fb_b, a.h_fb, e->EF, fn_act_epilogue{nullptr, 0.f, 0, 0, 0, nullptr},
-                             NodeScalarEpi{w.f_a_b, lay.s_dst_fb, lay.s_src_fb, 3 * d, 0, 2 * d, H}, 0, 0, kfb};
-            if (colaunch && ka > 20 && ka <= 168) {     // the atom features' projection needs nothing of the bond levels either: same launch
-                T.t[2] = T.t[1];  T.t[1] = T.t[0];      // its (longer) workgroups first
-                T.t[0] = LinTask{w.proj_a_w, in_atoms, bt_a, w.proj_a_b, a.h_a, e->N, fn_act_epilogue{nullptr, 0.f, 0, 0, 0, nullptr},
-                                 NodeScalarEpi{w.a, lay.s_dst_a, lay.s_src_a, wide, 0, d + FN_D, H}, 0, 0, ka};
+            T.t[0] = proj_task(vb, vb.K);  T.t[1] = proj_task(vfb, vfb.K);
+            if (colaunch && va.K > 20 && va.K <= 168) {     // the atom features' projection needs nothing of the bond levels either: same launch
+                T.t[2] = T.t[1];  T.t[1] = T.t[0];          // its (longer) workgroups first
+                T.t[0] = proj_task(va, va.K);
                 T.n = 3;
                 atoms_projected = true;
             }
-            for (int q = 0; q < T.n; ++q) T.t[q].n_real = T.t[q].M == e->N && T.t[q].Y == a.h_a ? nr_atoms : (T.t[q].Y == a.h_b ? nr_bonds : nr_conns);
             FN_TRY(launch_linear128_small_group(T, S(st)));
         } else {
-            FN_TRY(project(in_bond, kb, bt_b, w.proj_b_b, a.h_b, e->E, w.a_b, 3 * d, 2 * d, lay.s_dst, lay.s_src, st));
-            if (!no_fb) FN_TRY(project(in_fbond, kfb, bt_fb, w.proj_fb_b, a.h_fb, e->EF, w.f_a_b, 3 * d, 2 * d, lay.s_dst_fb, lay.s_src_fb, st));
+            FN_TRY(project(vb));
+            if (!no_fb) FN_TRY(project(vfb));
         }
-        fn_edge_term et_b{2, 1, d, d, nullptr, e->cos_sorted, w.emb_b_w, w.emb_b_b};
-        fn_edge_term et_fb{2, e->k_fattr, d, d, nullptr, e->fattr_sorted, w.emb_fb_w, w.emb_fb_b};
+        // a level's attention pass, prepared: raw_out = where its raw rows go (null: nobody reads them)
+        auto prep = [&](const LevelView& v, float* raw_out, const fn_act_epilogue& ep, GatFwdArgs* A) -> int {
+            const fn_edge_term et = fwd_edge_term(v, lay.s_sorted);
+            return prep_gat_fwd(v.a.h, v.s_dst, v.s_src, v.att, v.att_w, &et, v.pl, 0.2f, raw_out, v.a.p, nullptr, &ep, H, A, v.a.o2, v.a.sg);
+        };
+        // ... and what the engine sets on it whether the level runs or not (an absent level of a two-level launch still takes part in
+        // the choice of the launch's kind).  p_wanted: a read-out pass keeps the last layer's probabilities: the slots exist in every
+        // workspace; same kernel instances, one more store per edge
+        const bool keep_p = readout && last;
+        auto finish = [&](const LevelView& v, GatFwdArgs* A, bool p_wanted) {
+            A->p_edge_major = one ? 1 : 0;
+            if (no_bwd && !(keep_p && p_wanted)) A->p_sorted = nullptr;
+            A->n_real = v.n_real;
+        };
         // L1 bond graph and L4a fragment-bond graph: neither reads the other's output -> one launch for both
         GatFwdArgs gb, gfb{};
-        FN_TRY(prep_gat_fwd(a.h_b, lay.s_dst, lay.s_src, w.a_b, 3 * d, &et_b, &e->bond, 0.2f, (no_bwd && fuse_rd && ep_bond.y) ? nullptr : a.new_bond, a.p_bond, nullptr, &ep_bond, H, &gb, a.o2_bond, a.sg_bond));
+        FN_TRY(prep(vb, (no_bwd && fuse_rd && ep_bond.y) ? nullptr : vb.a.raw, ep_bond, &gb));
         // (the raw fragment-bond rows are the fragment graph's edge attribute: read in the last layer only, like the raw atom rows below)
-        if (!no_fb) FN_TRY(prep_gat_fwd(a.h_fb, lay.s_dst_fb, lay.s_src_fb, w.f_a_b, 3 * d, &et_fb, &e->fbond, 0.2f, (last || !ep_fbond.y) ? a.new_fbond : nullptr,
-                                        a.p_fbond, nullptr, &ep_fbond, H, &gfb, a.o2_fbond, a.sg_fbond));
-        gb.p_edge_major = gfb.p_edge_major = one ? 1 : 0;
-        // (a read-out pass keeps the last layer's: the slots exist in every workspace; same kernel instances, one more store per edge)
-        const bool keep_p = readout && last;
-        if (no_bwd && !(keep_p && readout->bonds)) gb.p_sorted = nullptr;
-        if (no_bwd && !(keep_p && readout->fbonds)) gfb.p_sorted = nullptr;
+        if (!no_fb) FN_TRY(prep(vfb, (last || !ep_fbond.y) ? vfb.a.raw : nullptr, ep_fbond, &gfb));
+        finish(vb, &gb, readout && readout->bonds);
+        finish(vfb, &gfb, readout && readout->fbonds);
         if (drop_edge_out) gb.ep.y = gfb.ep.y = nullptr;
-        gb.n_real = nr_bonds;  gfb.n_real = nr_conns;
         // (evaluation passes only, like FN_TUNE_FWD_BLOCKS_EVAL_LARGE: a training pass gets fewer, longer-lived half-waves from prep_gat_fwd
         // on purpose, and the cap was only ever measured forward-only)
         if (const int tail_rows = tune(FN_TUNE_FWD_TAIL_ROWS); !(ep_fbond.y && ep_fbond.p > 0.f) && tail_rows > 0 && gfb.rows_per_hw > tail_rows) {
@@ -1994,7 +2077,7 @@ static int encoder_forward_impl(const fn_encoder* e, const fn_row_masks* masks, 
             gfb.nblk = (int)((e->fbond.n + (int64_t)kRows * tail_rows - 1) / ((int64_t)kRows * tail_rows));
         }
         if (fuse_rd) {
-            gb.rd_A = w.a + d;  gb.rd_lda = wide;  gb.rd_J = H;  gb.rd_out = lay.s_sorted;  gb.rd_pos = e->atom.inv_d;  gb.rd_m = e->atom.m;
+            gb.rd_A = va.att + va.mid_off;  gb.rd_lda = va.att_w;  gb.rd_J = H;  gb.rd_out = lay.s_sorted;  gb.rd_pos = e->atom.inv_d;  gb.rd_m = e->atom.m;
         }
         if (l == 0) FN_TRY(prof_event(0, S(st)));
         if (with_pair.n) {
@@ -2005,81 +2088,70 @@ static int encoder_forward_impl(const fn_encoder* e, const fn_row_masks* masks, 
         if (l == 0) FN_TRY(prof_event(1, S(st)));
 
         // L2 atom graph (+ self loops), edge term = <new_bond, a[:, d:d+128]>
-        if (!grouped && !atoms_projected) FN_TRY(project(in_atoms, ka, bt_a, w.proj_a_b, a.h_a, e->N, w.a, wide, d + FN_D, lay.s_dst_a, lay.s_src_a, st));
-        if (!fuse_rd) FN_TRY(fn_row_dots_sorted_f32(a.new_bond, w.a, wide, d, H, &e->atom, lay.s_sorted, st));
-        fn_edge_term et_a{0, 0, 0, 0, lay.s_sorted, nullptr, nullptr, nullptr};
+        if (!grouped && !atoms_projected) FN_TRY(project(va));
+        if (!fuse_rd) FN_TRY(fn_row_dots_sorted_f32(vb.a.raw, va.att, va.att_w, va.mid_off, H, va.pl, lay.s_sorted, st));
+        GatFwdArgs ga;
         if (colaunch && !last) {
             // the next layer's bond / fragment-bond projections read this layer's bond-level outputs, not its atom level: same launch
-            const fn_layer_weights& wn = e->w[l + 1];
-            const LayerActs& an = lay.L[l + 1];
             LinTasks T{};
             T.n = no_fb ? 1 : 2;
-            T.t[0] = LinTask{wn.proj_b_w, y_bond, lay.bt + (size_t)(3 * (l + 1)) * 192 * FN_D, wn.proj_b_b, an.h_b, e->E, no_act_l,
-                             NodeScalarEpi{wn.a_b, lay.s_dst, lay.s_src, 3 * d, 0, 2 * d, H}, 0, 0};
-            T.t[1] = LinTask{wn.proj_fb_w, y_fbond, lay.bt + (size_t)(3 * (l + 1) + 2) * 192 * FN_D, wn.proj_fb_b, an.h_fb, e->EF, no_act_l,
-                             NodeScalarEpi{wn.f_a_b, lay.s_dst_fb, lay.s_src_fb, 3 * d, 0, 2 * d, H}, 0, 0};
-            T.t[0].n_real = nr_bonds;  T.t[1].n_real = nr_conns;
-            GatFwdArgs ga;
+            T.t[0] = proj_task(level_view(e, lay, l + 1, LV_BOND));  T.t[1] = proj_task(level_view(e, lay, l + 1, LV_FBOND));
             // (an inner layer's raw atom rows are read by nobody -- the fragment sums exist in the last layer only -- so only y is stored)
-            FN_TRY(prep_gat_fwd(a.h_a, lay.s_dst_a, lay.s_src_a, w.a, wide, &et_a, &e->atom, 0.2f, ep_atoms.y ? nullptr : lay.atoms_new, a.p_atom, nullptr, &ep_atoms, H, &ga,
-                                a.o2_atom, a.sg_atom));
-            ga.p_edge_major = one ? 1 : 0;
-            if (no_bwd && !(keep_p && readout->atoms)) ga.p_sorted = nullptr;
-            ga.n_real = nr_atoms;
+            FN_TRY(prep(va, ep_atoms.y ? nullptr : va.a.raw, ep_atoms, &ga));
+            finish(va, &ga, readout && readout->atoms);
             FN_TRY(launch_gat_fwd_lin(ga, T, H, S(st), pm_atoms));
         } else {
-            GatFwdArgs ga;
-            FN_TRY(prep_gat_fwd(a.h_a, lay.s_dst_a, lay.s_src_a, w.a, wide, &et_a, &e->atom, 0.2f, (last || !ep_atoms.y) ? lay.atoms_new : nullptr, a.p_atom, nullptr, &ep_atoms,
-                                H, &ga, a.o2_atom, a.sg_atom));
-            ga.p_edge_major = one ? 1 : 0;
-            if (no_bwd && !(keep_p && readout->atoms)) ga.p_sorted = nullptr;
-            ga.n_real = nr_atoms;
+            FN_TRY(prep(va, (last || !ep_atoms.y) ? va.a.raw : nullptr, ep_atoms, &ga));
+            finish(va, &ga, readout && readout->atoms);
             FN_TRY(launch_gat_fwd(ga, H, S(st), pm_atoms));
         }
 
         // L3 atom -> fragment sum.  Like L4b below it is only ever read in the last layer (the next layer recomputes its own
         // sum from its own atoms before first use, gat2.py:234), so inner layers skip it too.
+        float* frags = vf.a.h;
         const bool tail_mol = last && tail_mol_on(e);      // sums + fragment graph + readout: one molecule-resident launch
         const bool tail_fused = !tail_mol && last && !lite && !edge && H > 1 && e->F > 0 && e->N >= 4 * e->F && e->frag.m > 0 &&
-                                !(((uintptr_t)lay.atoms_new | (uintptr_t)a.frags) & 15);
-        if (last && !tail_fused && !tail_mol) FN_TRY(fn_segment_sum_f32(lay.atoms_new, FN_D, e->a2f.rowptr, e->a2f.perm, e->a2f.pos_base, a.frags, e->F, FN_D, e->N, st));
+                                !(((uintptr_t)lay.atoms_new | (uintptr_t)frags) & 15);
+        if (last && !tail_fused && !tail_mol) FN_TRY(fn_segment_sum_f32(lay.atoms_new, FN_D, e->a2f.rowptr, e->a2f.perm, e->a2f.pos_base, frags, e->F, FN_D, e->N, st));
 
         // L4b fragment graph on the raw fragment sums.  Only the last layer's result is ever read: the next layer
         // overwrites x_frags with its own atom->fragment sum before first use (gat2.py:234), so inner
         // layers skip this level entirely (the reference computes it and throws it away).
+        const fn_edge_term et_f = fwd_edge_term(vf, lay.s_sorted);
         if (last && lite) {      // gat2_lite: the encoder's fragment output is act(dropout(.)) of the plain fragment sums
-            FN_TRY(fn_dropout_act_f32(a.frags, y_frags, e->F * FN_D, p, e->seed, rng.y[l][1], e->offset_dev, 1, st));
+            FN_TRY(fn_dropout_act_f32(frags, y_frags, e->F * FN_D, p, e->seed, rng.y[l][vf.rng_slot], e->offset_dev, 1, st));
         } else if (last && edge) {   // gat2_edge (gat2_edge.py:148-172): edge term = <Linear(8 -> 128)(cnx_attr), f[:, d:d+128]>, folded in-kernel
-            FN_TRY(fn_node_scalars_f32(a.frags, w.f, wide, 0, d + FN_D, lay.s_dst, lay.s_src, e->F, H, st));
-            fn_edge_term et_f{2, e->k_fattr, FN_D, d, nullptr, e->fattr_sorted, w.emb_fb_w, w.emb_fb_b};
-            FN_TRY(fn_gat_fwd_f32(a.frags, lay.s_dst, lay.s_src, w.f, wide, &et_f, &e->frag, 0.2f, nullptr, a.p_frag, nullptr, nullptr, nullptr, 0, &ep_frags, H, st));
+            FN_TRY(fn_node_scalars_f32(frags, vf.att, vf.att_w, 0, vf.src_off, vf.s_dst, vf.s_src, e->F, H, st));
+            FN_TRY(fn_gat_fwd_f32(frags, vf.s_dst, vf.s_src, vf.att, vf.att_w, &et_f, vf.pl, 0.2f, nullptr, vf.a.p, nullptr, nullptr, nullptr, 0, &ep_frags, H, st));
         } else if (last && tail_mol) {
-            FN_TRY(launch_tail_fwd(e, lay, a, w, ep_frags, y_atoms, S(st)));
+            FN_TRY(launch_tail_fwd(e, lay, vf, ep_frags, y_atoms, S(st)));
         } else if (last) {
             if (tail_fused) {                                // atom -> fragment sum + node scalars + edge term: one launch
                 FragTailArgs T{};
-                T.src = lay.atoms_new;  T.rowptr = e->a2f.rowptr;  T.perm = e->a2f.perm;  T.pos_base = e->a2f.pos_base;  T.out = a.frags;
-                T.n_seg = e->F;  T.att = w.f;  T.att_w = wide;  T.dst_off = 0;  T.src_off = d + FN_D;  T.s_dst = lay.s_dst;  T.s_src = lay.s_src;
+                T.src = lay.atoms_new;  T.rowptr = e->a2f.rowptr;  T.perm = e->a2f.perm;  T.pos_base = e->a2f.pos_base;  T.out = frags;
+                T.n_seg = e->F;  T.att = vf.att;  T.att_w = vf.att_w;  T.dst_off = 0;  T.src_off = vf.src_off;  T.s_dst = vf.s_dst;  T.s_src = vf.s_src;
                 T.nblk_seg = (int)(e->F < 8 * kGridCap ? e->F : 8 * kGridCap);
-                T.feat = a.new_fbond;  T.A = w.f;  T.lda = wide;  T.off = d;  T.pl = e->frag;  T.s_sorted = lay.s_sorted;
+                T.feat = vfb.a.raw;  T.A = vf.att;  T.lda = vf.att_w;  T.off = vf.mid_off;  T.pl = e->frag;  T.s_sorted = lay.s_sorted;
                 T.nblk_rd = row_grid(e->frag.m, kGridCap);
                 const dim3 grid((unsigned)(T.nblk_seg + T.nblk_rd));
                 with_const<2, 4, 8>(H, [&](auto h) { hipLaunchKernelGGL((k_frag_tail<FN_CV(h)>), grid, dim3(kBlock), 0, S(st), T); });      // (tail_fused: H > 1)
                 FN_TRY(launch_status("fragment tail (sum + node scalars + edge term)"));
             } else {
-            FN_TRY(fn_row_dots_sorted_f32(a.new_fbond, w.f, wide, d, H, &e->frag, lay.s_sorted, st));
-            FN_TRY(fn_node_scalars_f32(a.frags, w.f, wide, 0, d + FN_D, lay.s_dst, lay.s_src, e->F, H, st));
+                FN_TRY(fn_row_dots_sorted_f32(vfb.a.raw, vf.att, vf.att_w, vf.mid_off, H, vf.pl, lay.s_sorted, st));
+                FN_TRY(fn_node_scalars_f32(frags, vf.att, vf.att_w, 0, vf.src_off, vf.s_dst, vf.s_src, e->F, H, st));
             }
-            fn_edge_term et_f{0, 0, 0, 0, lay.s_sorted, nullptr, nullptr, nullptr};
-            FN_TRY(fn_gat_fwd_f32(a.frags, lay.s_dst, lay.s_src, w.f, wide, &et_f, &e->frag, 0.2f, nullptr, a.p_frag, nullptr, nullptr, nullptr, 0, &ep_frags, H, st));
+            FN_TRY(fn_gat_fwd_f32(frags, vf.s_dst, vf.s_src, vf.att, vf.att_w, &et_f, vf.pl, 0.2f, nullptr, vf.a.p, nullptr, nullptr, nullptr, 0, &ep_frags, H, st));
         }
-        in_atoms = y_atoms;  in_bond = y_bond;  in_fbond = y_fbond;
-        ka = kb = kfb = FN_D;
     }
-    if (readout) {      // the fragment level stores its probabilities on all three tail paths, under no_backward too (a.p_frag above)
-        const LayerActs& a = lay.L[e->n_layers - 1];
-        const fni::AttnReadoutTask tasks[4] = {{e->bond, a.p_bond, readout->bonds, nr_bonds}, {e->fbond, a.p_fbond, readout->fbonds, nr_conns},
-                                               {e->atom, a.p_atom, readout->atoms, nr_atoms}, {e->frag, a.p_frag, readout->frags, rr ? rr + 2 : nullptr}};
+    if (readout) {      // the fragment level stores its probabilities on all three tail paths, under no_backward too (its p above)
+        const int l = e->n_layers - 1;
+        const Level order[4] = {LV_BOND, LV_FBOND, LV_ATOM, LV_FRAG};
+        float* const sums[4] = {readout->bonds, readout->fbonds, readout->atoms, readout->frags};
+        fni::AttnReadoutTask tasks[4];
+        for (int q = 0; q < 4; ++q) {
+            const LevelView v = level_view(e, lay, l, order[q]);
+            tasks[q] = fni::AttnReadoutTask{*v.pl, v.a.p, sums[q], v.n_real};
+        }
         FN_TRY(fni::launch_attn_readout(tasks, 4, H, S(st)));
     }
     return 0;
@@ -2108,12 +2180,10 @@ int fn_encoder_backward(const fn_encoder* e, const float* out_atoms, const float
     if (bw.total > scratch_floats) return fail(FN_EINVAL, "fn_encoder_backward: scratch too small");
     const RngPlan rng = rng_plan(e);
     if (e->g_pooled && !tail_mol_on(e)) return fail(FN_EINVAL, "fn_encoder_backward: dL/d(readout) is only taken by the fused fragment tail (fn_encoder_fused_tail)");
-    if (one_pass_on(e)) return encoder_backward_one(e, lay, bw, rng, out_atoms, out_frags, out_bond, out_fbond, g_atoms, g_frags, g_bond, g_fbond, grads, S(st));
-    const int H = e->heads, d = FN_D / H;
-    const float p = e->training ? e->drop_p : 0.f;
-    const int wide = 2 * d + FN_D;
+    const EncOutputs y{{out_bond, out_atoms, out_fbond, out_frags}}, gy{{g_bond, g_atoms, g_fbond, g_frags}};      // by Level
+    if (one_pass_on(e)) return encoder_backward_one(e, lay, bw, rng, y, gy, grads, S(st));
+    const int H = e->heads;
     hipStream_t hs = S(st);
-    const bool lite = e->variant == 1, edge = e->variant == 2;
     ReduceQueue rq;
     rq.st = hs;                      // all parameter-gradient reductions run as one launch at the very end
     rq.defer_wgrad = true;           // ... and so do the K = 128 weight-gradient partial products
@@ -2121,164 +2191,66 @@ int fn_encoder_backward(const fn_encoder* e, const float* out_atoms, const float
     rq.rider = e->adam_rider;
 
     // (This is the general path: any head count, hand-built atom graphs, gat2_edge's fragment graph.  The configurations the one-pass
-    // backward covers never get here, so its launches run in plain dependency order: per layer the gates, the fragment levels (last
-    // layer), the atom level's two passes, the bond and fragment-bond levels' two passes each, and one grouped launch for the layer's
+    // backward covers never get here, so its launches run in plain dependency order: the last layer's gates and fragment levels, then
+    // per layer the atom level's two passes, the bond and fragment-bond levels' two passes each, and one grouped launch for the layer's
     // input-gradient products.  The co-launched / pipelined forms of rounds 2-3 are retired: tools/probe/retired/.)
-    // gradients w.r.t. the current layer's post-activation outputs (null = zero)
-    bool pre_atoms = false, pre_bond = false, pre_fbond = false;   // g_pre_* already hold layer l's pre-activation grads
-    const float* gy_atoms = g_atoms;
-    const float* gy_frags = g_frags;
-    const float* gy_bond = g_bond;
-    const float* gy_fbond = g_fbond;
+    // ---- through act(dropout(.)): gradients of the pre-activation tensors.  For the last layer they come from the caller's output
+    // gradients (and the fragment graph, which only that layer runs: a layer's x_frags input is dead in the reference, overwritten at
+    // gat2.py:234); for inner layers the input-gradient GEMMs of layer l+1 write them (mask and ReLU gate fused into their epilogue)
+    LastGrads top{};
+    FN_TRY(last_layer_output_grads(e, lay, bw, y, gy, grads, rq, false, hs, &top));
+    bool have[kLevels] = {top.have[LV_BOND], top.have[LV_ATOM], top.have[LV_FBOND]};      // by Level: g_pre holds layer l's gradient rows
 
+    struct Parts { int n_a = 0, n_e = 0; };
     for (int l = e->n_layers - 1; l >= 0; --l) {
-        const fn_layer_weights& w = e->w[l];
+        const LevelView vb = level_view(e, lay, l, LV_BOND), va = level_view(e, lay, l, LV_ATOM), vfb = level_view(e, lay, l, LV_FBOND);
+        const LevelScratch &sb = bw.lv[l][LV_BOND], &sa = bw.lv[l][LV_ATOM], &sfb = bw.lv[l][LV_FBOND];
         const fn_layer_weights& g = grads[l];
-        const LayerActs& a = lay.L[l];
-        const bool last = l + 1 == e->n_layers;
-        const float* y_atoms = last ? out_atoms : a.y_atoms;
-        const float* y_frags = last ? out_frags : a.y_frags;
-        const float* y_bond = last ? out_bond : a.y_bond;
-        const float* y_fbond = last ? out_fbond : a.y_fbond;
-        const float* in_atoms = l ? lay.L[l - 1].y_atoms : (lay.in_atoms0 ? lay.in_atoms0 : e->x_atoms);
-        const float* in_bond = l ? lay.L[l - 1].y_bond : e->bond_nodes;
-        const float* in_fbond = l ? lay.L[l - 1].y_fbond : e->fbond_nodes;
-        const int ka = l ? FN_D : e->k_atom0, kb = l ? FN_D : e->k_bond0, kfb = l ? FN_D : e->k_fbond0;
-        const LevelScratch &sb = bw.bond[l], &sa = bw.atom[l], &sfb = bw.fbond[l], &sf = bw.frag;
-        int n_a = 0, n_e = 0;
-        // the three input-gradient products of a layer feed layer l-1 only: one grouped launch at the end of the layer
+        // the three input-gradient products of a layer feed layer l-1 only: one grouped launch at the end of the layer.  A product
+        // writes dL/d(pre-activation output of the level one layer down), gated by that layer's dropout mask and ReLU
         LinTasks dxT{};
-        // Wt: the transposed copy the forward prologue left in the workspace
-        auto input_grad = [&](const float* gh, const float* W, const float* Wt, float* gy, int64_t rows, const fn_act_epilogue& mk) -> int {
-            dxT.t[dxT.n++] = LinTask{Wt, gh, W, nullptr, gy, rows, mk, NodeScalarEpi{nullptr, nullptr, nullptr, 0, 0, 0, 0}, 0, 0};
-            return 0;
+        bool nxt[kLevels] = {false, false, false};     // what this layer hands to layer l-1
+        auto input_grad = [&](const LevelView& v, const LevelScratch& sc) {
+            const LevelView below = level_view(e, lay, l - 1, v.lv);
+            dxT.t[dxT.n++] = LinTask{v.Wt, sc.g_h, v.W, nullptr, bw.g_pre[v.lv], v.rows, act_epilogue(e, rng, below, below.a.y),
+                                     NodeScalarEpi{nullptr, nullptr, nullptr, 0, 0, 0, 0}, 0, 0};
+            nxt[v.lv] = true;
         };
-        const float* bt_b = lay.bt + (size_t)(3 * l) * 192 * FN_D;
-        const float* bt_a = lay.bt + (size_t)(3 * l + 1) * 192 * FN_D;
-        const float* bt_fb = lay.bt + (size_t)(3 * l + 2) * 192 * FN_D;
-
-        // ---- through act(dropout(.)): gradients of the pre-activation tensors.  For the last layer they come from
-        // the caller's output gradients; for inner layers the input-gradient GEMMs of layer l+1 already wrote them
-        // (mask and ReLU gate fused into their epilogue), flagged by pre_* below.
-        bool have_atoms = gy_atoms != nullptr || pre_atoms, have_frags = gy_frags != nullptr;
-        bool have_bond = gy_bond != nullptr || pre_bond, have_fbond = gy_fbond != nullptr || pre_fbond;
-        // last layer, molecule-resident tail (csrc/mol_tail.inc): the atoms' and fragments' gates, the fragment graph's two passes,
-        // its edge term's backward and the scatter to the atoms are ONE launch below; the readout's gradient enters there
-        const bool tail_mol = last && tail_mol_on(e) && (gy_frags != nullptr || e->g_pooled != nullptr);
-        const float gate_scale = p > 0.f ? (p < 1.f ? 1.f / (1.f - p) : 0.f) : 1.f;
-        {   // backward of relu(dropout(.)) of up to four layer outputs in one launch; y > 0 already encodes the mask
-            GateTasks G{};
-            auto add = [&](const float* g, const float* y, float* o, int64_t numel) {
-                if (!g) return;
-                GateTask& t = G.t[G.n++];
-                t.g = g;  t.y = y;  t.o = o;  t.n4 = (numel + 3) / 4;  t.first = G.blocks;  t.nblk = flat_grid(t.n4, 512);
-                G.blocks += t.nblk;
-            };
-            if (!tail_mol) {
-                add(gy_atoms, y_atoms, bw.g_pre_atoms, e->N * FN_D);
-                add(gy_frags, y_frags, bw.g_pre_frags, e->F * FN_D);
-            }
-            add(gy_bond, y_bond, bw.g_pre_bond, e->E * FN_D);
-            add(gy_fbond, y_fbond, bw.g_pre_fbond, e->EF * FN_D);
-            if (G.blocks) {
-                G.scale = gate_scale;
-                hipLaunchKernelGGL(k_gate_many, dim3(G.blocks), dim3(kBlock), 0, S(st), G);
-                FN_TRY(launch_status("fn_encoder_backward: activation backward"));
-            }
-        }
-        bool nxt_atoms = false, nxt_bond = false, nxt_fbond = false;     // what this layer hands to layer l-1
-
-        // ---- L4b fragment graph (only where its output is consumed: the last layer, reference fact SURVEY §0.8)
-        bool have_g_frags_h = false;
-        const float* g_frags_h = bw.g_frags;      // dL/d(fragment sums), scattered back to the atoms below
-        if (tail_mol) {
-            int n_part = 0;
-            FN_TRY(launch_tail_bwd(e, lay, a, w, bw, y_atoms, y_frags, gy_atoms, gy_frags, gate_scale, have_fbond, &n_part, hs));
-            const fn_edge_term et_f{0, 0, 0, 0, nullptr, nullptr, nullptr, nullptr};
-            FN_TRY(rq.finalize(bw.frag.part_a, n_part, nullptr, 0, et_f, w.f, wide, 0, d + FN_D, g.f, nullptr, nullptr, H));
-            FN_TRY(rq.colsum(bw.frag.part_rd, n_part, H * FN_D, g.f, wide, d));
-            have_atoms = have_fbond = true;        // g_pre_atoms and g_pre_fbond are complete (scatter to the atoms included)
-        } else if (have_frags && lite) {
-            g_frags_h = bw.g_pre_frags;            // no fragment graph in between
-            have_g_frags_h = true;
-        } else if (have_frags && edge) {   // gat2_edge: the edge term's parameters are the cnx_attr Linear (emb_fb_*) and f's middle block
-            fn_edge_term et_f{2, e->k_fattr, FN_D, d, nullptr, e->fattr_sorted, w.emb_fb_w, w.emb_fb_b};
-            FN_TRY(fn_gat_bwd_dst_f32(bw.g_pre_frags, a.frags, a.p_frag, &et_f, &e->frag, 0.2f, nullptr, nullptr, sf.pz, sf.g_s_dst, sf.part_e, &n_e, H, st));
-            FN_TRY(fn_gat_bwd_src_f32(bw.g_pre_frags, a.frags, sf.pz, sf.g_s_dst, w.f, wide, 0, d + FN_D, &e->frag, bw.g_frags, sf.part_a, &n_a, H, st));
-            FN_TRY(rq.finalize(sf.part_a, n_a, sf.part_e, n_e, et_f, w.f, wide, 0, d + FN_D, g.f, g.emb_fb_w, g.emb_fb_b, H));
-            have_g_frags_h = true;
-        } else if (have_frags) {
-            fn_edge_term et_f{0, 0, 0, 0, nullptr, nullptr, nullptr, nullptr};
-            FN_TRY(fn_gat_bwd_dst_f32(bw.g_pre_frags, a.frags, a.p_frag, &et_f, &e->frag, 0.2f, nullptr, sf.dz, sf.pz, sf.g_s_dst, nullptr, &n_e, H, st));
-            // source pass + edge term <new_fbond, f[:, d:d+128]> (dL/dnew_fbond accumulates into g_pre_fbond, dL/df mid block)
-            int gr = 0;
-            FN_TRY(bwd_src_and_edge_term(bw.g_pre_frags, a.frags, sf.pz, sf.g_s_dst, w.f, wide, 0, d + FN_D, &e->frag, bw.g_frags, sf.part_a, &n_a,
-                                         sf.dz, a.new_fbond, d, bw.g_pre_fbond, sf.part_rd, have_fbond, &gr, H, hs));
-            if (gr) have_fbond = true;
-            FN_TRY(rq.finalize(sf.part_a, n_a, nullptr, 0, et_f, w.f, wide, 0, d + FN_D, g.f, nullptr, nullptr, H));
-            if (gr) FN_TRY(rq.colsum(sf.part_rd, gr, H * FN_D, g.f, wide, d));
-            have_g_frags_h = true;
-        }
-
-        // ---- L3 atom -> fragment sum: dL/datoms_new += dL/dfrags[a2f]
-        if (have_g_frags_h) {
-            FN_TRY(launch_gather_rows4(g_frags_h, e->a2f.index, bw.g_pre_atoms, e->N, 32, have_atoms ? (const float*)bw.g_pre_atoms : (const float*)nullptr, hs,
-                                       "fn_encoder_backward: gather(a2f)"));
-            have_atoms = true;
-        }
 
         // ---- L2 atom graph
-        if (have_atoms) {
-            fn_edge_term et_a{0, 0, 0, 0, nullptr, nullptr, nullptr, nullptr};
-            FN_TRY(fn_gat_bwd_dst_f32(bw.g_pre_atoms, a.h_a, a.p_atom, &et_a, &e->atom, 0.2f, nullptr, sa.dz, sa.pz, sa.g_s_dst, nullptr, &n_e, H, st));
-            // source pass + the edge term <new_bond, a[:, d:d+128]> (dL/dnew_bond accumulates into g_pre_bond, dL/da mid block)
-            int gr = 0;
-            FN_TRY(bwd_src_and_edge_term(bw.g_pre_atoms, a.h_a, sa.pz, sa.g_s_dst, w.a, wide, 0, d + FN_D, &e->atom, sa.g_h, sa.part_a, &n_a,
-                                         sa.dz, a.new_bond, d, bw.g_pre_bond, sa.part_rd, have_bond, &gr, H, hs));
-            if (gr) have_bond = true;
-            FN_TRY(rq.finalize(sa.part_a, n_a, nullptr, 0, et_a, w.a, wide, 0, d + FN_D, g.a, nullptr, nullptr, H));
-            if (gr) FN_TRY(rq.colsum(sa.part_rd, gr, H * FN_D, g.a, wide, d));
-            FN_TRY(rq.wgrad(sa.g_h, in_atoms, ka, e->N, sa.wg_ws, g.proj_a_w, g.proj_a_b, hs));
-            if (l) {
-                const fn_act_epilogue mk{const_cast<float*>(lay.L[l - 1].y_atoms), p, 1, e->seed, rng.y[l - 1][0], e->offset_dev};
-                FN_TRY(input_grad(sa.g_h, w.proj_a_w, bt_a, bw.g_pre_atoms, e->N, mk));
-                nxt_atoms = true;
-            }
+        if (have[LV_ATOM]) {
+            int n_a = 0, n_e = 0, gr = 0;
+            FN_TRY(fn_gat_bwd_dst_f32(bw.g_pre[LV_ATOM], va.a.h, va.a.p, &va.et, va.pl, 0.2f, nullptr, sa.dz, sa.pz, sa.g_s_dst, nullptr, &n_e, H, st));
+            // source pass + the edge term <new_bond, a[:, d:d+128]> (dL/dnew_bond accumulates into g_pre of the bonds, dL/da mid block)
+            FN_TRY(bwd_src_and_edge_term(va, sa, bw.g_pre[LV_ATOM], sa.g_h, vb.a.raw, bw.g_pre[LV_BOND], have[LV_BOND], &n_a, &gr, hs));
+            if (gr) have[LV_BOND] = true;
+            FN_TRY(rq.level_params(va, level_weights(g, LV_ATOM), sa, ParamWork{n_a, 0, false, nullptr, false, false, gr}, hs));
+            if (l) input_grad(va, sa);
         }
 
-        // ---- L1 bond graph and L4a fragment-bond graph
-        if (have_bond || have_fbond) {
-            fn_edge_term et_b{2, 1, d, d, nullptr, e->cos_sorted, w.emb_b_w, w.emb_b_b};
-            fn_edge_term et_fb{2, e->k_fattr, d, d, nullptr, e->fattr_sorted, w.emb_fb_w, w.emb_fb_b};
-            int n_a_b = 0, n_e_b = 0, n_a_fb = 0, n_e_fb = 0;
-            // both destination passes, then both source passes
-            if (have_bond) FN_TRY(fn_gat_bwd_dst_f32(bw.g_pre_bond, a.h_b, a.p_bond, &et_b, &e->bond, 0.2f, nullptr, nullptr, sb.pz, sb.g_s_dst, sb.part_e, &n_e_b, H, st));
-            if (have_fbond) FN_TRY(fn_gat_bwd_dst_f32(bw.g_pre_fbond, a.h_fb, a.p_fbond, &et_fb, &e->fbond, 0.2f, nullptr, nullptr, sfb.pz, sfb.g_s_dst, sfb.part_e, &n_e_fb, H, st));
-            if (have_bond) FN_TRY(fn_gat_bwd_src_f32(bw.g_pre_bond, a.h_b, sb.pz, sb.g_s_dst, w.a_b, 3 * d, 0, 2 * d, &e->bond, sb.g_h, sb.part_a, &n_a_b, H, st));
-            if (have_fbond) FN_TRY(fn_gat_bwd_src_f32(bw.g_pre_fbond, a.h_fb, sfb.pz, sfb.g_s_dst, w.f_a_b, 3 * d, 0, 2 * d, &e->fbond, sfb.g_h, sfb.part_a, &n_a_fb, H, st));
-            if (have_fbond) {
-                if (l) {     // dL/d(pre-activation fbond output of layer l-1), gated by that layer's dropout mask and ReLU
-                    const fn_act_epilogue mk{const_cast<float*>(lay.L[l - 1].y_fbond), p, 1, e->seed, rng.y[l - 1][3], e->offset_dev};
-                    FN_TRY(input_grad(sfb.g_h, w.proj_fb_w, bt_fb, bw.g_pre_fbond, e->EF, mk));
-                    nxt_fbond = true;
-                }
-                FN_TRY(rq.finalize(sfb.part_a, n_a_fb, sfb.part_e, n_e_fb, et_fb, w.f_a_b, 3 * d, 0, 2 * d, g.f_a_b, g.emb_fb_w, g.emb_fb_b, H));
-                FN_TRY(rq.wgrad(sfb.g_h, in_fbond, kfb, e->EF, sfb.wg_ws, g.proj_fb_w, g.proj_fb_b, hs));
-            }
-            if (have_bond) {
-                FN_TRY(rq.finalize(sb.part_a, n_a_b, sb.part_e, n_e_b, et_b, w.a_b, 3 * d, 0, 2 * d, g.a_b, g.emb_b_w, g.emb_b_b, H));
-                    FN_TRY(rq.wgrad(sb.g_h, in_bond, kb, e->E, sb.wg_ws, g.proj_b_w, g.proj_b_b, hs));
-                if (l) {
-                    const fn_act_epilogue mk{const_cast<float*>(lay.L[l - 1].y_bond), p, 1, e->seed, rng.y[l - 1][2], e->offset_dev};
-                    FN_TRY(input_grad(sb.g_h, w.proj_b_w, bt_b, bw.g_pre_bond, e->E, mk));
-                    nxt_bond = true;
-                }
-            }
+        // ---- L1 bond graph and L4a fragment-bond graph: both destination passes, then both source passes
+        Parts nb, nfb;
+        auto dst_pass = [&](const LevelView& v, const LevelScratch& sc, Parts* n) {
+            return fn_gat_bwd_dst_f32(bw.g_pre[v.lv], v.a.h, v.a.p, &v.et, v.pl, 0.2f, nullptr, nullptr, sc.pz, sc.g_s_dst, sc.part_e, &n->n_e, H, st);
+        };
+        auto src_pass = [&](const LevelView& v, const LevelScratch& sc, Parts* n) {
+            return fn_gat_bwd_src_f32(bw.g_pre[v.lv], v.a.h, sc.pz, sc.g_s_dst, v.att, v.att_w, 0, v.src_off, v.pl, sc.g_h, sc.part_a, &n->n_a, H, st);
+        };
+        if (have[LV_BOND]) FN_TRY(dst_pass(vb, sb, &nb));
+        if (have[LV_FBOND]) FN_TRY(dst_pass(vfb, sfb, &nfb));
+        if (have[LV_BOND]) FN_TRY(src_pass(vb, sb, &nb));
+        if (have[LV_FBOND]) FN_TRY(src_pass(vfb, sfb, &nfb));
+        // (the fragment-bond level's product and parameter work are queued before the bond level's)
+        if (have[LV_FBOND]) {
+            if (l) input_grad(vfb, sfb);
+            FN_TRY(rq.level_params(vfb, level_weights(g, LV_FBOND), sfb, ParamWork{nfb.n_a, nfb.n_e}, hs));
+        }
+        if (have[LV_BOND]) {
+            FN_TRY(rq.level_params(vb, level_weights(g, LV_BOND), sb, ParamWork{nb.n_a, nb.n_e}, hs));
+            if (l) input_grad(vb, sb);
         }
         if (dxT.n) FN_TRY(launch_linear128_group(dxT, hs));
-        pre_atoms = nxt_atoms;  pre_bond = nxt_bond;  pre_fbond = nxt_fbond;
-        gy_atoms = gy_bond = gy_fbond = nullptr;
-        gy_frags = nullptr;        // a layer's x_frags input is dead in the reference (overwritten at gat2.py:234)
+        for (Level v : kProjected) have[v] = nxt[v];
     }
     return rq.flush(true);
 }
@@ -2302,9 +2274,9 @@ int fn_encoder_backward_inputs(const fn_encoder* e, const float* scratch, int64_
     if (bw.total > scratch_floats) return fail(FN_EINVAL, "fn_encoder_backward_inputs: scratch too small");
     const fn_layer_weights& w0 = e->w[0];
     const fn_linear_dx_task tasks[FN_MAX_DX_TASKS] = {
-        {bw.atom[0].g_h, w0.proj_a_w, in->dx_atoms, in->delta_atoms, in->dots_atoms, e->N, e->k_atom0, 0},
-        {bw.bond[0].g_h, w0.proj_b_w, in->dx_bonds, in->delta_bonds, in->dots_bonds, e->E, e->k_bond0, 0},
-        {bw.fbond[0].g_h, w0.proj_fb_w, in->dx_fbonds, in->delta_fbonds, in->dots_fbonds, e->variant == 1 ? 0 : e->EF, e->k_fbond0, 0},
+        {bw.lv[0][LV_ATOM].g_h, w0.proj_a_w, in->dx_atoms, in->delta_atoms, in->dots_atoms, e->N, e->k_atom0, 0},
+        {bw.lv[0][LV_BOND].g_h, w0.proj_b_w, in->dx_bonds, in->delta_bonds, in->dots_bonds, e->E, e->k_bond0, 0},
+        {bw.lv[0][LV_FBOND].g_h, w0.proj_fb_w, in->dx_fbonds, in->delta_fbonds, in->dots_fbonds, e->variant == 1 ? 0 : e->EF, e->k_fbond0, 0},
     };
     return fni::launch_linear_dx(tasks, FN_MAX_DX_TASKS, S(st));
 }

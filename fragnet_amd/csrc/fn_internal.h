@@ -162,7 +162,7 @@ struct GsdSegTasks { GsdSegTask t[3]; int n; };
 FNI_HIDDEN int prep_gat_bwd_one(const float* g_out, const float* h, const float* p_sorted, const float* cdot, const float* g_s_dst,
                                 const fn_edge_term* et, const float* att, int att_w, int dst_off, int src_off, const fn_gat_plan* plan,
                                 float neg_slope, float* g_h, float* dz_sorted, float* g_s_orig, float* part_a, int* n_part_a, float* part_e,
-                                int* n_part_e, int heads, GatBwdOneArgs* A, int64_t share = 0);
+                                int* n_part_e, int heads, GatBwdOneArgs* A);
 FNI_HIDDEN int launch_gat_bwd_one(const GatBwdOneArgs& A, int heads, hipStream_t st);
 FNI_HIDDEN int launch_gat_bwd_one3(const GatBwdOneArgs& A, const GatBwdOneArgs& B, const GatBwdOneArgs& C, int heads, hipStream_t st);
 FNI_HIDDEN int launch_gat_cu(CuTasks& T, int heads, hipStream_t st);

@@ -19,7 +19,7 @@ static bool one_pass_heads(int heads) { return heads == 2 || heads == 4 || heads
 int prep_gat_bwd_one(const float* g_out, const float* h, const float* p_sorted, const float* cdot, const float* g_s_dst,
                             const fn_edge_term* et, const float* att, int att_w, int dst_off, int src_off, const fn_gat_plan* plan,
                             float neg_slope, float* g_h, float* dz_sorted, float* g_s_orig, float* part_a, int* n_part_a, float* part_e,
-                            int* n_part_e, int heads, GatBwdOneArgs* A, int64_t share) {
+                            int* n_part_e, int heads, GatBwdOneArgs* A) {
     if (!g_out || !h || !cdot || !g_s_dst || !att || !plan || !g_h || !part_a || !n_part_a || !n_part_e || !et)
         return fail(FN_EINVAL, "fn_gat_bwd_one_f32: bad argument");
     if (et->mode != 0 && bad_edge_term(et, plan ? plan->m : 1)) return fail(FN_EINVAL, "fn_gat_bwd_one_f32: bad edge term");
@@ -45,9 +45,9 @@ int prep_gat_bwd_one(const float* g_out, const float* h, const float* p_sorted, 
         return fail(FN_EUNSUPPORTED, "fn_gat_bwd_one_f32: level too large for 32-bit byte offsets (n <= 2^23 rows, m*heads <= 2^28)");
     // persistent half-waves pipelining R rows each; every block writes one row of partial sums (<= 1024 blocks).  The kernel runs
     // three workgroups per CU (its twelve gradient rows in flight cost the fourth), so 768 are resident at once: a launch of more
-    // pays a second, mostly empty round.  share > 0: this level's part of a launch that carries several (by rows)
+    // pays a second, mostly empty round
     const int64_t groups = (plan->n + kBwdRows - 1) / kBwdRows;
-    int64_t resident = share > 0 ? share : (int64_t)tune(FN_TUNE_ONE_BLOCKS);
+    int64_t resident = (int64_t)tune(FN_TUNE_ONE_BLOCKS);
     if (resident > FN_MAX_PART || resident < 1) resident = 1024;
     A->rows_per_hw = (int)((groups + resident - 1) / resident);
     A->nblk = (int)((plan->n + (int64_t)kBwdRows * A->rows_per_hw - 1) / ((int64_t)kBwdRows * A->rows_per_hw));
