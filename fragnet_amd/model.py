@@ -382,20 +382,15 @@ class _FusedHead:
 
     def _fused_kind(self, enc, linears):
         """the activation kind when ``linears`` run through ops.mlp_head, else None (torch): no Philox stream, CPU rows, rrelu, a
-        Linear without bias or a hidden width that is not a multiple of 4, a ``dropout`` that is not a plain nn.Dropout (a module put
-        in its place -- mask injection, a probe -- is called as before), and -- for the kinds other than ReLU -- shapes the dense
-        kernels do not take"""
+        ``dropout`` that is not a plain nn.Dropout (a module put in its place -- mask injection, a probe -- is called as before), or
+        no route for these Linears, rows and kind (``ops.head_route``)"""
         kind = ops.head_act_kind(self.activation)
-        if self.rng is None or kind is None or not enc.is_cuda or any(l.bias is None for l in linears) \
-                or any(l.out_features % 4 != 0 for l in linears[:-1]):
+        if self.rng is None or kind is None or not enc.is_cuda:
             return None
         if type(self.dropout) is not nn.Dropout and not (kind == _lib.ACT_RELU and self._relu_any_dropout):
             return None
-        if kind != _lib.ACT_RELU:
-            rows = enc.shape[0] if self.live_rows is None else max(0, min(int(self.live_rows), enc.shape[0]))
-            if not ops.mlp_head_dense_ok(rows, linears):
-                return None
-        return kind
+        rows = enc.shape[0] if self.live_rows is None else max(0, min(int(self.live_rows), enc.shape[0]))
+        return kind if ops.head_route(rows, linears, kind) is not None else None
 
     def _fused(self, enc, linears, kind, order=_lib.ACT_DROP_THEN_ACT, in_drop=False):
         act = None if kind == _lib.ACT_RELU else self.activation

@@ -401,19 +401,20 @@ def pool_cat_groups(x_atoms, x_frags, plan, atom_group, row_mol, row_group, chec
     return out
 
 
-class _MaskedMSE(torch.autograd.Function):
-    """sum_i w_i |out_i - y_i|^2 / (sum_i w_i * T): loss and d loss / d out from one single-block kernel."""
+class _MaskedLoss(torch.autograd.Function):
+    """A loss over a padded batch, loss and d loss / d out from one single-block kernel ``fn_<name>_f32``:
+    ``masked_mse``: sum_i w_i |out_i - y_i|^2 / (sum_i w_i * T); ``masked_bce``: compute_bce_loss (train/utils.py:297-304)."""
 
     @staticmethod
-    def forward(ctx, out, y, w):
+    def forward(ctx, name, out, y, w):
         B = w.shape[0]
         out2, y2 = _f32c(out, "out").reshape(B, -1), _f32c(y, "y").reshape(B, -1)
         if out2.shape != y2.shape:
-            raise ValueError(f"masked_mse: prediction {tuple(out.shape)} vs target {tuple(y.shape)}")
+            raise ValueError(f"{name}: prediction {tuple(out.shape)} vs target {tuple(y.shape)}")
         w = _f32c(w, "w")
         loss = torch.empty((), dtype=torch.float32, device=out.device)
         g = torch.empty_like(out2)
-        _lib.call("fn_masked_mse_f32", out2.data_ptr(), y2.data_ptr(), w.data_ptr(), B, out2.shape[1], loss.data_ptr(),
+        _lib.call(f"fn_{name}_f32", out2.data_ptr(), y2.data_ptr(), w.data_ptr(), B, out2.shape[1], loss.data_ptr(),
                   g.data_ptr(), _stream_ptr(out.device))
         ctx.save_for_backward(g)
         ctx.shape = out.shape
@@ -422,45 +423,17 @@ class _MaskedMSE(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g_loss):
         (g,) = ctx.saved_tensors
-        unit = _UNIT_GRAD.get(g.device)
-        if unit is not None and g_loss.data_ptr() == unit.data_ptr():      # d loss / d loss = 1: nothing to multiply
-            return g.reshape(ctx.shape), None, None
-        return (g * g_loss).reshape(ctx.shape), None, None
+        if _is_unit_grad(g_loss):      # d loss / d loss = 1: nothing to multiply
+            return None, g.reshape(ctx.shape), None, None
+        return None, (g * g_loss).reshape(ctx.shape), None, None
 
 
 def masked_mse(out, y, w):
-    return _MaskedMSE.apply(out, y, w)
-
-
-class _MaskedBCE(torch.autograd.Function):
-    """compute_bce_loss (train/utils.py:297-304) over a padded batch: loss and gradient from one single-block kernel."""
-
-    @staticmethod
-    def forward(ctx, out, y, w):
-        B = w.shape[0]
-        out2, y2 = _f32c(out, "out").reshape(B, -1), _f32c(y, "y").reshape(B, -1)
-        if out2.shape != y2.shape:
-            raise ValueError(f"masked_bce: prediction {tuple(out.shape)} vs target {tuple(y.shape)}")
-        w = _f32c(w, "w")
-        loss = torch.empty((), dtype=torch.float32, device=out.device)
-        g = torch.empty_like(out2)
-        _lib.call("fn_masked_bce_f32", out2.data_ptr(), y2.data_ptr(), w.data_ptr(), B, out2.shape[1], loss.data_ptr(),
-                  g.data_ptr(), _stream_ptr(out.device))
-        ctx.save_for_backward(g)
-        ctx.shape = out.shape
-        return loss
-
-    @staticmethod
-    def backward(ctx, g_loss):
-        (g,) = ctx.saved_tensors
-        unit = _UNIT_GRAD.get(g.device)
-        if unit is not None and g_loss.data_ptr() == unit.data_ptr():
-            return g.reshape(ctx.shape), None, None
-        return (g * g_loss).reshape(ctx.shape), None, None
+    return _MaskedLoss.apply("masked_mse", out, y, w)
 
 
 def masked_bce(out, y, w):
-    return _MaskedBCE.apply(out, y, w)
+    return _MaskedLoss.apply("masked_bce", out, y, w)
 
 
 class _MaskedMSEMulti(torch.autograd.Function):
@@ -494,8 +467,7 @@ class _MaskedMSEMulti(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g_loss):
-        unit = _UNIT_GRAD.get(g_loss.device)
-        one = unit is not None and g_loss.data_ptr() == unit.data_ptr()
+        one = _is_unit_grad(g_loss)
         out = [None, None]
         for g, shape in zip(ctx.saved_tensors, ctx.shapes):
             out += [(g if one else g * g_loss).reshape(shape), None, None]
@@ -519,6 +491,12 @@ def unit_grad(device):
     if device not in _UNIT_GRAD:
         _UNIT_GRAD[device] = torch.ones((), dtype=torch.float32, device=device)
     return _UNIT_GRAD[device]
+
+
+def _is_unit_grad(t) -> bool:
+    """``t`` is the persistent scalar of ``unit_grad``: the gradient is 1, a backward has nothing to multiply"""
+    unit = _UNIT_GRAD.get(t.device)
+    return unit is not None and t.data_ptr() == unit.data_ptr()
 
 
 class _GatherRows(torch.autograd.Function):
@@ -675,279 +653,272 @@ def dropout_act(x, p: float, training: bool, relu: bool, rng: PhiloxStream):
 
 
 # ======================================================================================
-# prediction head: Linear -> relu(dropout(.)) stack with a hand-written backward
+# prediction head: Linear -> act(dropout(.)) stack with a hand-written backward
 # ======================================================================================
 SMALL_LINEAR_MAX = 16        # FN_SMALL_LINEAR_MAX
-
-
 DENSE_MAX_ROWS = 4096        # FN_DENSE_MAX_ROWS
 DENSE_HEAD = True            # hidden layers through fn_dense_fwd/bwd_f32 (False: library GEMMs + the element-wise kernels)
+FUSED_HEAD_LOSS = os.environ.get("FRAGNET_FUSED_HEAD_LOSS", "1") != "0"       # False: last Linear, loss and the Linear's backward as three launches (A/B and tests)
 
 
 def _dense_ok(rows: int, W) -> bool:
     return DENSE_HEAD and rows <= DENSE_MAX_ROWS and W.shape[0] % 4 == 0 and W.shape[1] % 4 == 0 and W.is_contiguous()
 
 
+def _small_ok(W) -> bool:        # the last Linear's shapes fn_small_linear(_bwd)_f32 take
+    return W.shape[0] <= SMALL_LINEAR_MAX and W.shape[1] % 4 == 0
+
+
 def _scratch(n_floats: int, device):
     return torch.empty(n_floats, dtype=torch.float32, device=device) if n_floats else None
 
 
-def mlp_head_dense_ok(rows: int, linears) -> bool:
-    """The shapes every launch of ``_MLPHead`` runs on the dense-head kernels for (the only path of the non-ReLU kinds)."""
-    return all(_dense_ok(rows, lin.weight) for lin in linears[:-1]) and linears[-1].out_features <= SMALL_LINEAR_MAX \
-        and linears[-1].in_features % 4 == 0
+def head_route(rows: int, linears, kind: int = _lib.ACT_RELU, params=None) -> Optional[str]:
+    """Which node ``mlp_head`` runs ``linears`` on for ``rows`` live rows and the activation ``kind``.  "dense": the hidden Linears on
+    fn_dense_*_f32, the last one on fn_small_linear_*_f32 (``_DenseHead``); "tall": library GEMMs (``_TallHead``), ReLU only; None: no
+    kernel path -- a Linear without bias, a hidden output width that is no multiple of 4, another kind than ReLU off the dense route
+    (``params``: the Linears' weight, bias, weight, ... where the caller has collected them already)."""
+    params = [q for lin in linears for q in (lin.weight, lin.bias)] if params is None else params
+    dense = True
+    for i in range(0, len(params) - 2, 2):
+        if params[i + 1] is None or params[i].shape[0] % 4 != 0:
+            return None
+        dense = dense and _dense_ok(rows, params[i])
+    if params[-1] is None:
+        return None
+    return "dense" if dense and _small_ok(params[-2]) else "tall" if kind == _lib.ACT_RELU else None
+
+
+def head_fuses_loss(route, rows: int, x, linears, loss, training: bool) -> bool:
+    """Whether ``mlp_head(loss=...)`` runs the last Linear, the loss and that Linear's backward in one launch: the dense route behind
+    at least one hidden layer, a training step whose input takes a gradient, live rows, one target and one weight per padded row."""
+    (_, tgt, row_w), last, M = loss, linears[-1], x.shape[0]
+    return bool(FUSED_HEAD_LOSS and training and x.requires_grad and route == "dense" and len(linears) > 1 and rows > 0
+                and last.in_features <= _lib.SMALL_LINEAR_LOSS_MAX_K and row_w.shape[0] == M and tgt.numel() == M * last.out_features)
 
 
 def head_act_kind(act) -> Optional[int]:
     """The kernels' activation kind (``_lib.ACT_*``) of a head's activation module as ``_ACTS`` builds it (model.py), or None where
     torch keeps it: RReLU (its training slopes come from torch's generator) and non-default settings of the others."""
-    nn = torch.nn
-    t = type(act)
+    nn, t = torch.nn, type(act)
     if isinstance(act, nn.ReLU):
         return _lib.ACT_RELU
-    if t is nn.SiLU:
-        return _lib.ACT_SILU
-    if t is nn.GELU and act.approximate == "none":
-        return _lib.ACT_GELU
-    if t is nn.CELU and act.alpha == 1.0:
-        return _lib.ACT_CELU
-    if t is nn.SELU:
-        return _lib.ACT_SELU
-    if t is nn.ReLU6:
-        return _lib.ACT_RELU6
-    if t is nn.LeakyReLU and act.negative_slope == 0.01:
-        return _lib.ACT_LEAKYRELU
-    if t is nn.PReLU and act.weight.numel() == 1 and act.weight.dtype == torch.float32:
-        return _lib.ACT_PRELU
-    return None
+    if (t is nn.GELU and act.approximate != "none") or (t is nn.CELU and act.alpha != 1.0) or (t is nn.LeakyReLU and act.negative_slope != 0.01) \
+            or (t is nn.PReLU and not (act.weight.numel() == 1 and act.weight.dtype == torch.float32)):
+        return None
+    return {nn.SiLU: _lib.ACT_SILU, nn.GELU: _lib.ACT_GELU, nn.CELU: _lib.ACT_CELU, nn.SELU: _lib.ACT_SELU, nn.ReLU6: _lib.ACT_RELU6,
+            nn.LeakyReLU: _lib.ACT_LEAKYRELU, nn.PReLU: _lib.ACT_PRELU}.get(t)
 
 
-def _head_act(hact, p: float, draw, dev, prelu, pre, part=None):
-    """fn_head_act of one hidden layer: kind and order, its Philox draw, its saved argument, the PReLU slope and partials."""
-    kind, order = hact
-    seed, off = draw
-    return _lib.HeadAct(kind, order, float(p), 0, seed, off, _ptr(dev) if p > 0.0 else None, _ptr(prelu), pre.data_ptr(), _ptr(part))
+class _Relu(NamedTuple):
+    """The activation behind one hidden layer, as the launches take it (the twin exports of csrc/head.hip differ in that one slot), is
+    a ``_lib.HeadAct`` or, for relu(dropout(.)), this: the forward's epilogue and the gate scale of its backward (the saved output encodes
+    the mask).  The kernels read a scale of 0 as "no gate", so p >= 1 (all dropped) gets a positive value, not 1 / (1 - p) = inf or 0."""
+    epilogue: Optional[_lib.ActEpilogue]
+    gate: float
 
 
-class _MLPHead(torch.autograd.Function):
-    """FTHead1-5's predictor stack (gat2.py:631-637, 745-751) as one autograd node.
+_NO_GATE = _Relu(None, 0.0)        # what a gradient leaves through where no activation sits below: the head's input, a tall layer
 
-    On molecule-sized inputs (``_dense_ok``) every hidden layer is ONE launch each way (csrc/dense_head.inc, fp32 matrix
-    cores): forward = product + bias + relu(dropout(.)); backward = weight gradient + bias gradient + input gradient, the
-    latter already through the backward of the layer below's relu(dropout(.)) (the saved output encodes the mask, so no
-    Philox replay).  The last Linear (n_classes outputs) is one launch each way, too.  Taller inputs (the pretrain towers
-    run on every atom / bond) keep library GEMMs (addmm / mm) with the element-wise work fused around them
-    (``fn_dropout_act_f32`` in place, ``fn_gate_colsum_f32``).  ``draws`` = the (seed, offset) of each hidden layer's mask,
-    taken from the model's Philox stream in the same order as the unfused path, so both paths produce identical numbers.
-    ``live``: input rows >= live are padding (static-shape batches): they are not computed, their outputs and input
-    gradients are 0.
-    ``hact = (kind, order)``: the hidden layers' activation is another kind than the ReLU above (csrc/head_act.inc; dense shapes only):
-    the forward saves each layer's activation argument, the backward replays the masks from ``draws``; ``prelu`` (kind PReLU) is
-    the slope every hidden layer shares, read by the kernels from device memory, and its gradient is the fixed-order sum of one
-    partial per workgroup of the launches that run the layers' activation backward.
-    """
+
+def _gate_scale(p: float) -> float:
+    return 1.0 / (1.0 - p) if 0.0 < p < 1.0 else 1.0
+
+
+def _dense_fwd(act, h, W, b, y, st):
+    """one hidden layer: y = act(h W^T + b), one launch"""
+    entry, spec = ("fn_dense_fwd_act_f32", act) if isinstance(act, _lib.HeadAct) else ("fn_dense_fwd_f32", act.epilogue)
+    _lib.call(entry, h.data_ptr(), W.data_ptr(), b.data_ptr(), y.data_ptr(), h.shape[0], W.shape[1], W.shape[0], C.byref(spec), st)
+
+
+def _dense_bwd(below, gz, h_in, W, gx, dW, db, M_out, tail, st):
+    """one hidden layer's backward: dW, db, the input gradient ``gx`` (``M_out`` rows) through the backward of ``below``; ``tail`` rides"""
+    entry, spec = ("fn_dense_bwd_act_f32", C.byref(below)) if isinstance(below, _lib.HeadAct) else ("fn_dense_bwd_tail_f32", below.gate)
+    _lib.call(entry, gz.data_ptr(), h_in.data_ptr(), W.data_ptr(), _ptr(gx), spec, dW.data_ptr(), db.data_ptr(), h_in.shape[0],
+              W.shape[1], W.shape[0], M_out, None if tail is None else C.byref(tail), st)
+
+
+def _small_fwd(h, W, b, out, st):
+    """the last Linear (``_small_ok``); ``out`` may have more rows than ``h``: the kernel zeroes them"""
+    _lib.call("fn_small_linear_f32", h.data_ptr(), _f32c(W, "W").data_ptr(), b.data_ptr(), out.data_ptr(), h.shape[0], W.shape[1], W.shape[0],
+              out.shape[0], st)
+
+
+def _small_bwd(below, g, h, W, gz, dW, db, st):
+    """the last Linear's backward: dW, db and its input gradient ``gz`` through the backward of the activation ``below``"""
+    C_out, K = W.shape
+    ws = _scratch(_lib.load().fn_small_linear_bwd_ws(h.shape[0], K, C_out), g.device)
+    entry, spec = ("fn_small_linear_bwd_act_f32", C.byref(below)) if isinstance(below, _lib.HeadAct) else ("fn_small_linear_bwd_f32", below.gate)
+    _lib.call(entry, g.data_ptr(), h.data_ptr(), W.data_ptr(), gz.data_ptr(), dW.data_ptr(), db.data_ptr(), h.shape[0], K, C_out, spec, _ptr(ws), st)
+
+
+def _small_loss(below, h, W, b, loss, out, g, gz, parts, st):
+    """last Linear + loss + d loss / d out (``g``) + the Linear's input gradient through ``below`` (``gz``); dW / db ride in a ``SmallDw``"""
+    kind, tgt, row_w = loss
+    entry, spec = ("fn_small_linear_loss_act_f32", C.byref(below)) if isinstance(below, _lib.HeadAct) else ("fn_small_linear_loss_f32", below.gate)
+    _lib.call(entry, h.data_ptr(), _f32c(W, "W").data_ptr(), b.data_ptr(), tgt.data_ptr(), row_w.data_ptr(), int(kind), out.data_ptr(),
+              g.data_ptr(), gz.data_ptr(), spec, parts.data_ptr(), h.shape[0], W.shape[1], W.shape[0], out.shape[0], st)
+
+
+def _input_grad(like, M: int, last: bool, zeroed_by_kernel: bool = False):
+    """buffer of d loss / d (input of a layer); the head's own input gradient (``last``) has all M rows, the padding rows 0"""
+    full = torch.empty((M if last else like.shape[0], like.shape[1]), dtype=torch.float32, device=like.device)
+    if not zeroed_by_kernel and full.shape[0] > like.shape[0]:
+        full[like.shape[0]:].zero_()
+    return full
+
+
+def _head_saved(ctx):
+    """a head node's saved tensors by name -- (slope partials, the fused loss's g, gz, loss partials, loss value; None where there are
+    none), the layers' inputs (live rows), the weights -- and the parameters' gradient buffers, each claimed once per pass"""
+    part, g, gz, parts, loss_t, *rest = ctx.saved_tensors
+    n = len(ctx.params) // 2
+    return (part, g, gz, parts, loss_t), rest[:n], rest[n:2 * n], [grad_buffer(q, slot) for q, slot in zip(ctx.params, ctx.slots)]
+
+
+class _DenseHead(torch.autograd.Function):
+    """FTHead1-5's predictor stack (gat2.py:631-637, 745-751) on route "dense": every Linear is ONE launch each way (csrc/head.hip),
+    padding rows written as 0 by the kernels.  ``hact = (kind, order)``: another kind than ReLU (csrc/head_act.inc), with ``prelu`` the
+    slope the layers share.  ``loss`` (``head_fuses_loss``): returns (out, loss), ``out`` without gradient.  DESIGN.md section 1.
+    Precondition (``mlp_head`` sees to it): ``head_route`` says "dense" for these rows, parameters and kind."""
 
     @staticmethod
-    def forward(ctx, x, p: float, draws, dev, live, loss, hact, prelu, *params):
-        n = len(params) // 2
-        st = _stream_ptr(x.device)
-        x = _f32c(x, "x")
-        M = x.shape[0]
-        live = M if live is None else max(0, min(int(live), M))
-        h = x[:live]
-        acts = [h]
-        dense = all(_dense_ok(live, params[2 * i]) for i in range(n - 1)) and params[-2].shape[0] <= SMALL_LINEAR_MAX \
-            and params[-2].shape[1] % 4 == 0
-        if hact is not None and not dense:
-            raise _lib.FragnetHipError("mlp_head: activation kinds other than ReLU run on the dense-head kernels only (rows <= "
-                                       f"{DENSE_MAX_ROWS}, widths multiples of 4, <= {SMALL_LINEAR_MAX} outputs)")
-        pres = []
+    def forward(ctx, x, live, p: float, draws, dev, hact, prelu, loss, *params):
+        n, st, x = len(params) // 2, _stream_ptr(x.device), _f32c(x, "x")
+        M, h = x.shape[0], x[:live]
+        xs, pres, acts = [h], [], []
         for i in range(n - 1):
             W, b = params[2 * i], params[2 * i + 1]
-            seed, off = draws[i]
-            if hact is not None:
-                y = torch.empty((live, W.shape[0]), dtype=torch.float32, device=h.device)
+            y = torch.empty((live, W.shape[0]), dtype=torch.float32, device=h.device)
+            if hact is None:
+                acts.append(_Relu(_lib.ActEpilogue(y.data_ptr(), p, 1, *draws[i], _ptr(dev)), _gate_scale(p)))
+            else:
                 pres.append(torch.empty_like(y))
-                spec = _head_act(hact, p, draws[i], dev, prelu, pres[-1])
-                _lib.call("fn_dense_fwd_act_f32", h.data_ptr(), W.data_ptr(), b.data_ptr(), y.data_ptr(), live, W.shape[1], W.shape[0],
-                          C.byref(spec), st)
-            elif dense:
-                y = torch.empty((live, W.shape[0]), dtype=torch.float32, device=h.device)
-                act = _lib.ActEpilogue(y.data_ptr(), float(p), 1, seed, off, _ptr(dev) if p > 0.0 else None)
-                _lib.call("fn_dense_fwd_f32", h.data_ptr(), W.data_ptr(), b.data_ptr(), y.data_ptr(), live, W.shape[1], W.shape[0],
-                          C.byref(act), st)
-            else:
-                y = torch.addmm(b, h, W.t())
-                _lib.call("fn_dropout_act_f32", y.data_ptr(), y.data_ptr(), y.numel(), float(p), seed, off,
-                          _ptr(dev) if p > 0.0 else None, 1, st)
+                acts.append(_lib.HeadAct(*hact, p, 0, *draws[i], _ptr(dev), _ptr(prelu), pres[-1].data_ptr(), None))
+            _dense_fwd(acts[-1], h, W, b, y, st)
             h = y
-            acts.append(h)
-        W, b = params[-2], params[-1]
-        C_out, K = W.shape
-        ctx.p, ctx.dense, ctx.rows = float(p), dense, (M, live)
+            xs.append(h)
+        (W, b), (C_out, K), part, part_at = params[-2:], params[-2].shape, None, ()
+        if prelu is not None and n > 1 and live > 0:
+            # one slice of partials per hidden layer: layer i < n - 2 in the input-gradient launch of layer i + 1, the top one in
+            # the last Linear's launch (its fused-loss forward, or its backward)
+            lib = _lib.load()
+            counts = [lib.fn_head_act_parts(_lib.ACT_AT_DENSE_BWD, live, params[2 * i].shape[0]) for i in range(n - 2)]
+            counts.append(lib.fn_head_act_parts(_lib.ACT_AT_SMALL_LOSS, M, K) if loss is not None else lib.fn_head_act_parts(_lib.ACT_AT_SMALL_BWD, live, K))
+            part = torch.empty(sum(counts), dtype=torch.float32, device=h.device)
+            part_at = tuple(sum(counts[:i]) for i in range(n - 1))
+            for act, at in zip(acts, part_at):
+                act.part = part.data_ptr() + 4 * at
         ctx.params, ctx.slots = params, [grad_slot(q) for q in params]
-        ctx.fused_loss = False
-        fuse = loss is not None and dense and n > 1 and live > 0 and K <= _lib.SMALL_LINEAR_LOSS_MAX_K and loss[2].shape[0] == M \
-            and loss[1].numel() == M * C_out
-        ctx.hact, ctx.draws, ctx.dev, ctx.pres, ctx.prelu, ctx.part, ctx.part_at = hact, draws, dev, pres, prelu, None, None
-        if prelu is not None:
-            ctx.prelu_slot = grad_slot(prelu)
-            if hact is not None and n > 1 and live > 0:
-                # one slice of partials per hidden layer: layer i < n - 2 in the input-gradient launch of layer i + 1, the top one in
-                # the last Linear's launch (its fused-loss forward, or its backward)
-                lib = _lib.load()
-                counts = [lib.fn_head_act_parts(_lib.ACT_AT_DENSE_BWD, live, params[2 * i].shape[0]) for i in range(n - 2)]
-                counts.append(lib.fn_head_act_parts(_lib.ACT_AT_SMALL_LOSS, M, K) if fuse else lib.fn_head_act_parts(_lib.ACT_AT_SMALL_BWD, live, K))
-                ctx.part = torch.empty(sum(counts), dtype=torch.float32, device=h.device)
-                ctx.part_at = [sum(counts[:i]) for i in range(n - 1)] + [sum(counts)]
-        if fuse:
-            # last Linear + loss + its input gradient in one launch; dW / db / the loss value ride in the backward's first launch
-            kind, tgt, row_w = loss
-            tgt, row_w = _f32c(tgt, "y"), _f32c(row_w, "w")
-            out = torch.empty((M, C_out), dtype=torch.float32, device=h.device)
-            g = torch.empty((live, C_out), dtype=torch.float32, device=h.device)
-            gz = torch.empty_like(h)
-            parts = torch.empty(_lib.load().fn_small_linear_loss_ws(M), dtype=torch.float32, device=h.device)
-            loss_t = torch.empty((), dtype=torch.float32, device=h.device)
-            scale = 1.0 / (1.0 - p) if 0.0 < p < 1.0 else 1.0
-            if hact is not None:
-                below = _MLPHead._below(ctx, n - 2)
-                _lib.call("fn_small_linear_loss_act_f32", h.data_ptr(), _f32c(W, "W").data_ptr(), b.data_ptr(), tgt.data_ptr(),
-                          row_w.data_ptr(), int(kind), out.data_ptr(), g.data_ptr(), gz.data_ptr(), C.byref(below), parts.data_ptr(),
-                          live, K, C_out, M, st)
-            else:
-                _lib.call("fn_small_linear_loss_f32", h.data_ptr(), _f32c(W, "W").data_ptr(), b.data_ptr(), tgt.data_ptr(), row_w.data_ptr(),
-                          int(kind), out.data_ptr(), g.data_ptr(), gz.data_ptr(), scale, parts.data_ptr(), live, K, C_out, M, st)
-            ctx.fused_loss = True
-            ctx.save_for_backward(*acts, *params[0::2], g, gz, parts, loss_t)
-            ctx.mark_non_differentiable(out)
-            ctx.set_materialize_grads(False)            # no zero-filled gradient for the predictions (a fill launch per step)
-            return out, loss_t
-        if C_out <= SMALL_LINEAR_MAX and K % 4 == 0:
-            out = torch.empty((M, C_out), dtype=torch.float32, device=h.device)        # the kernel zeroes the padding rows
-            _lib.call("fn_small_linear_f32", h.data_ptr(), _f32c(W, "W").data_ptr(), b.data_ptr(), out.data_ptr(), live, K, C_out, M, st)
+        # the rest of what backward needs: ``dev`` is what ``acts`` point to, kept alive but not saved (the stream moves it in place)
+        ctx.state = (M, acts, dev, prelu, None if prelu is None else grad_slot(prelu), part_at, loss is not None)
+        out = torch.empty((M, C_out), dtype=torch.float32, device=h.device)        # the kernels zero the padding rows
+        if loss is None:
+            _small_fwd(h, W, b, out, st)
+            ctx.save_for_backward(part, None, None, None, None, *xs, *params[0::2], *pres)
+            return out
+        loss = (loss[0], _f32c(loss[1], "y"), _f32c(loss[2], "w"))
+        g = torch.empty((live, C_out), dtype=torch.float32, device=h.device)
+        gz = torch.empty_like(h)
+        parts = torch.empty(_lib.load().fn_small_linear_loss_ws(M), dtype=torch.float32, device=h.device)
+        loss_t = torch.empty((), dtype=torch.float32, device=h.device)
+        _small_loss(acts[-1], h, W, b, loss, out, g, gz, parts, st)
+        ctx.save_for_backward(part, g, gz, parts, loss_t, *xs, *params[0::2], *pres)
+        ctx.mark_non_differentiable(out)
+        ctx.set_materialize_grads(False)            # no zero-filled gradient for the predictions (a fill launch per step)
+        return out, loss_t
+
+    @staticmethod
+    def backward(ctx, g_out, g_loss=None):
+        (part, g, gz, parts, loss_t), xs, Ws, grads = _head_saved(ctx)
+        M, acts, _, prelu, prelu_slot, part_at, fused_loss = ctx.state
+        n, live, st, need_x = len(Ws), xs[0].shape[0], _stream_ptr(xs[0].device), ctx.needs_input_grad[0]
+        W, h, dW, db, tail = Ws[-1], xs[-1], grads[-2], grads[-1], None
+        if fused_loss:
+            # the forward's launch left g = d loss / d out and gz for d loss / d loss = 1; dW / db / the loss value ride below
+            if g_loss is not None and not _is_unit_grad(g_loss):
+                g, gz = g * g_loss, gz * g_loss
+                if part is not None:            # the top layer's slope partials, taken in the forward for d loss / d loss = 1
+                    part[part_at[n - 2]:].mul_(g_loss)
+            tail = _lib.SmallDw(g.data_ptr(), h.data_ptr(), dW.data_ptr(), db.data_ptr(), parts.data_ptr(), loss_t.data_ptr(),
+                                parts.numel(), live, W.shape[1], W.shape[0])
+        else:
+            g = _f32c(g_out, "g")[:live]
+            gz = _input_grad(h, M, n == 1) if (n > 1 or need_x) else torch.empty_like(h)
+            _small_bwd(acts[-1] if n > 1 else _NO_GATE, g, h, W, gz, dW, db, st)
+        for i in range(n - 2, -1, -1):          # gz is d loss / d (pre-activation) already: one launch for the layer
+            gx = _input_grad(xs[i], M, i == 0, zeroed_by_kernel=True) if (i > 0 or need_x) else None
+            _dense_bwd(acts[i - 1] if i > 0 else _NO_GATE, gz, xs[i], Ws[i], gx, grads[2 * i], grads[2 * i + 1], M if i == 0 else live, tail, st)
+            tail, gz = None, gx
+        g_prelu = None if prelu is None else grad_buffer(prelu, prelu_slot)
+        if part is not None and part.numel():       # (there are partials only where there is a slope)
+            _lib.call("fn_head_act_param_grad_f32", part.data_ptr(), part.numel(), g_prelu.data_ptr(), st)
+        elif prelu is not None:
+            g_prelu.zero_()
+        return (gz if need_x else None, None, None, None, None, None, g_prelu, None, *grads)
+
+
+class _TallHead(torch.autograd.Function):
+    """The same stack on route "tall" (the pretrain towers run on every atom / bond), ReLU only: library GEMMs (addmm / mm) with the
+    element-wise work fused around them (``fn_dropout_act_f32`` in place, ``fn_gate_colsum_f32``); padding rows written here.
+    Precondition: ``head_route`` says "tall"."""
+
+    @staticmethod
+    def forward(ctx, x, live, p: float, draws, dev, *params):
+        n, st, x = len(params) // 2, _stream_ptr(x.device), _f32c(x, "x")
+        M, h = x.shape[0], x[:live]
+        xs = [h]
+        for i in range(n - 1):
+            h = torch.addmm(params[2 * i + 1], h, params[2 * i].t())
+            _lib.call("fn_dropout_act_f32", h.data_ptr(), h.data_ptr(), h.numel(), p, *draws[i], _ptr(dev), 1, st)
+            xs.append(h)
+        W, b = params[-2], params[-1]
+        if _small_ok(W):
+            out = torch.empty((M, W.shape[0]), dtype=torch.float32, device=h.device)
+            _small_fwd(h, W, b, out, st)
         else:
             out = torch.addmm(b, h, W.t())
             if live < M:
-                out = torch.cat([out, out.new_zeros((M - live, C_out))])
-        ctx.save_for_backward(*acts, *params[0::2])
-        return (out, None) if loss is not None else out
+                out = torch.cat([out, out.new_zeros((M - live, W.shape[0]))])
+        ctx.params, ctx.slots, ctx.state = params, [grad_slot(q) for q in params], (M, _gate_scale(p))
+        ctx.save_for_backward(None, None, None, None, None, *xs, *params[0::2])
+        return out
 
     @staticmethod
-    def _below(ctx, i):
-        """fn_head_act of hidden layer i for the launch that runs its activation backward"""
-        part = None if ctx.part is None else ctx.part[ctx.part_at[i]:]
-        return _head_act(ctx.hact, ctx.p, ctx.draws[i], ctx.dev, ctx.prelu, ctx.pres[i], part)
+    def backward(ctx, g):
+        _, xs, Ws, grads = _head_saved(ctx)
+        M, gate = ctx.state
+        n, live, st, need_x = len(Ws), xs[0].shape[0], _stream_ptr(xs[0].device), ctx.needs_input_grad[0]
+        g = _f32c(g, "g")[:live]
+        W, h, dW, db = Ws[-1], xs[-1], grads[-2], grads[-1]
 
-    @staticmethod
-    def backward(ctx, g, g_loss=None):
-        saved = ctx.saved_tensors
-        fused = None
-        if ctx.fused_loss:
-            saved, fused = saved[:-4], saved[-4:]
-        n = len(saved) // 2
-        acts, Ws = saved[:n], saved[n:]
-        M, live = ctx.rows
-        if fused is None:
-            g = _f32c(g, "g")[:live]
-        st = _stream_ptr(acts[0].device)
-        grads = [None] * (2 * n)
-        W, h = Ws[-1], acts[-1]
-        C_out, K = W.shape
-        P, slots = ctx.params, ctx.slots
-        dense, need_x = ctx.dense, ctx.needs_input_grad[0]
-        # gate scale of the fused backward of relu(dropout(.)): the kernels read 0 as "no gate", so p >= 1 (every element dropped:
-        # the saved outputs are all 0 and the gate lets nothing through) passes a positive value, not 1 / (1 - p) = inf or 0
-        scale = 1.0 / (1.0 - ctx.p) if 0.0 < ctx.p < 1.0 else 1.0
-        dW, db = grad_buffer(P[-2], slots[-2]), grad_buffer(P[-1], slots[-1])
-
-        def input_grad(like, last, zeroed_by_kernel=False):
-            """buffer of d loss / d (input of a layer); the head's own input gradient has all M rows (padding rows 0)"""
-            if not last or live == M:
-                return torch.empty_like(like)
-            full = torch.empty((M, like.shape[1]), dtype=torch.float32, device=like.device)
-            if not zeroed_by_kernel:
-                full[live:].zero_()
-            return full
-
-        tail = None
-        if fused is not None:
-            # the forward's fused launch left g = d loss / d out and gz (for d loss / d loss = 1); the sums over rows ride below
-            g, gz, parts, loss_t = fused
-            unit = _UNIT_GRAD.get(g.device)
-            if g_loss is not None and not (unit is not None and g_loss.data_ptr() == unit.data_ptr()):
-                g, gz = g * g_loss, gz * g_loss
-                if ctx.part is not None:            # the top layer's slope partials, taken in the forward for d loss / d loss = 1
-                    ctx.part[ctx.part_at[n - 2]:].mul_(g_loss)
-            tail = _lib.SmallDw(g.data_ptr(), h.data_ptr(), dW.data_ptr(), db.data_ptr(), parts.data_ptr(), loss_t.data_ptr(),
-                                parts.numel(), live, K, C_out)
-            ctx.tail_keep = (g, gz)
-        elif C_out <= SMALL_LINEAR_MAX and K % 4 == 0:
-            gz = input_grad(h, n == 1) if (n > 1 or need_x) else torch.empty_like(h)
-            ws = _scratch(_lib.load().fn_small_linear_bwd_ws(live, K, C_out), g.device)
-            if ctx.hact is not None and n > 1:     # gz leaves through the backward of the top hidden layer's activation kind
-                below = _MLPHead._below(ctx, n - 2)
-                _lib.call("fn_small_linear_bwd_act_f32", g.data_ptr(), h.data_ptr(), W.data_ptr(), gz.data_ptr(), dW.data_ptr(), db.data_ptr(),
-                          live, K, C_out, C.byref(below), _ptr(ws), st)
-            else:
-                # dense path: gz leaves gated by h > 0 (the backward of the top hidden layer's relu(dropout(.)))
-                _lib.call("fn_small_linear_bwd_f32", g.data_ptr(), h.data_ptr(), W.data_ptr(), gz.data_ptr(), dW.data_ptr(), db.data_ptr(),
-                          live, K, C_out, scale if (dense and n > 1) else 0.0, _ptr(ws), st)
+        def padded(gx):         # the head's own input gradient: all M rows
+            return torch.cat([gx, gx.new_zeros((M - live, gx.shape[1]))]) if live < M else gx
+        if _small_ok(W):        # (behind a hidden layer: a single small Linear is route "dense")
+            gz = torch.empty_like(h)
+            _small_bwd(_NO_GATE, g, h, W, gz, dW, db, st)
         else:
             gz = g @ W
             torch.mm(g.t(), h, out=dW)
             torch.sum(g, 0, out=db)
-            if n == 1 and live < M:
-                gz = torch.cat([gz, gz.new_zeros((M - live, K))])
-        grads[-2], grads[-1] = dW, db
-        # (running the weight-gradient GEMMs on a side stream beside the gate -> input-gradient chain was measured: a
-        # two-branch hipGraph replays 9 % slower on ROCm 7.2 than the serial one, HISTORY.md section 4)
+            if n == 1:
+                gz = padded(gz)
         for i in range(n - 2, -1, -1):
-            z, h_in, W = acts[i + 1], acts[i], Ws[i]
-            dW, db = grad_buffer(P[2 * i], slots[2 * i]), grad_buffer(P[2 * i + 1], slots[2 * i + 1])
-            grads[2 * i], grads[2 * i + 1] = dW, db
-            need_gx = i > 0 or need_x
-            if dense:                                   # gz is d loss / d (pre-activation) already: one launch for the layer
-                gx = input_grad(h_in, i == 0, zeroed_by_kernel=True) if need_gx else None
-                if ctx.hact is not None and i > 0:      # through the backward of layer i - 1's activation kind
-                    below = _MLPHead._below(ctx, i - 1)
-                    _lib.call("fn_dense_bwd_act_f32", gz.data_ptr(), h_in.data_ptr(), W.data_ptr(), _ptr(gx), C.byref(below), dW.data_ptr(),
-                              db.data_ptr(), live, W.shape[1], W.shape[0], live, None if tail is None else C.byref(tail), st)
-                    tail = None
-                elif tail is not None:
-                    _lib.call("fn_dense_bwd_tail_f32", gz.data_ptr(), h_in.data_ptr(), W.data_ptr(), _ptr(gx), scale if i > 0 else 0.0,
-                              dW.data_ptr(), db.data_ptr(), live, W.shape[1], W.shape[0], M if i == 0 else live, C.byref(tail), st)
-                    tail = None
-                else:
-                    _lib.call("fn_dense_bwd_f32", gz.data_ptr(), h_in.data_ptr(), W.data_ptr(), _ptr(gx), scale if i > 0 else 0.0, dW.data_ptr(),
-                              db.data_ptr(), live, W.shape[1], W.shape[0], M if i == 0 else live, st)
-                gz = gx
-                continue
+            z = xs[i + 1]
             gy = torch.empty_like(z)
             ws = _scratch(_lib.load().fn_gate_colsum_ws(z.shape[0], z.shape[1]), z.device)
-            _lib.call("fn_gate_colsum_f32", gz.data_ptr(), z.data_ptr(), gy.data_ptr(), db.data_ptr(), z.shape[0], z.shape[1], scale,
-                      _ptr(ws), st)
-            torch.mm(gy.t(), h_in, out=dW)
-            if need_gx:
-                gz = gy @ W
-                if i == 0 and live < M:
-                    gz = torch.cat([gz, gz.new_zeros((M - live, gz.shape[1]))])
-        g_prelu = None
-        if ctx.prelu is not None:
-            g_prelu = grad_buffer(ctx.prelu, ctx.prelu_slot)
-            if ctx.part is not None and ctx.part.numel():
-                _lib.call("fn_head_act_param_grad_f32", ctx.part.data_ptr(), ctx.part.numel(), g_prelu.data_ptr(), st)
-            else:
-                g_prelu.zero_()
-        return (gz if need_x else None, None, None, None, None, None, None, g_prelu, *grads)
-
-
-FUSED_HEAD_LOSS = os.environ.get("FRAGNET_FUSED_HEAD_LOSS", "1") != "0"       # False: last Linear, loss and the Linear's backward as three launches (A/B and tests)
+            _lib.call("fn_gate_colsum_f32", gz.data_ptr(), z.data_ptr(), gy.data_ptr(), grads[2 * i + 1].data_ptr(), z.shape[0], z.shape[1],
+                      gate, _ptr(ws), st)
+            torch.mm(gy.t(), xs[i], out=grads[2 * i])
+            if i > 0 or need_x:
+                gz = padded(gy @ Ws[i]) if i == 0 else gy @ Ws[i]
+        return (gz if need_x else None, None, None, None, None, *grads)
 
 
 def mlp_head(x, linears, p: float, training: bool, rng: "PhiloxStream", live=None, loss=None, act=None,
              order: int = _lib.ACT_DROP_THEN_ACT, in_drop: bool = False):
-    """Runs ``linears`` (nn.Linear modules; relu(dropout(.)) after all but the last) through ``_MLPHead``.
+    """Runs ``linears`` (nn.Linear modules; relu(dropout(.)) after all but the last) as one autograd node, ``_DenseHead`` or
+    ``_TallHead`` as ``head_route`` says.  ``live``: input rows >= live are padding (static-shape batches).
 
     ``act``: the hidden layers' activation module when it is not ReLU (``head_act_kind``), applied as act(dropout(.)) or, with
     ``order = _lib.ACT_ACT_THEN_DROP``, dropout(act(.)) (FTHead1/4; for ReLU both orders are the same numbers); ``in_drop``: the input
@@ -961,22 +932,27 @@ def mlp_head(x, linears, p: float, training: bool, rng: "PhiloxStream", live=Non
     kind = _lib.ACT_RELU if act is None else head_act_kind(act)
     if kind is None:
         raise ValueError(f"mlp_head: no kernel for the activation {act!r}")
-    hact = None if kind == _lib.ACT_RELU else (kind, int(order))
-    prelu = act.weight if kind == _lib.ACT_PRELU else None
+    rows = x.shape[0] if live is None else max(0, min(int(live), x.shape[0]))
+    params = [q for lin in linears for q in (lin.weight, lin.bias)]
+    route = head_route(rows, linears, kind, params)
+    if route is None and head_route(rows, linears, params=params) is None:
+        raise ValueError("mlp_head: Linear layers need a bias, hidden ones an output width that is a multiple of 4")
+    if route is None:
+        raise _lib.FragnetHipError("mlp_head: activation kinds other than ReLU run on the dense-head kernels only (rows <= "
+                                   f"{DENSE_MAX_ROWS}, widths multiples of 4, <= {SMALL_LINEAR_MAX} outputs)")
     if in_drop:
         x = dropout_act(x, p, training, False, rng)
-    draws = []
-    for lin in linears[:-1]:
-        draws.append(rng.take(x.shape[0] * lin.out_features) if p_eff > 0.0 else (0, 0))
-    params = []
-    for lin in linears:
-        if lin.bias is None or (lin.out_features % 4 != 0 and lin is not linears[-1]):
-            raise ValueError("mlp_head: Linear layers need a bias, hidden ones an output width that is a multiple of 4")
-        params += [lin.weight, lin.bias]
-    if loss is not None and not (FUSED_HEAD_LOSS and training and x.requires_grad and linears[-1].out_features <= SMALL_LINEAR_MAX
-                                 and linears[-1].in_features % 4 == 0):
-        return _MLPHead.apply(x, p_eff, tuple(draws), rng.dev if p_eff > 0.0 else None, live, None, hact, prelu, *params), None
-    return _MLPHead.apply(x, p_eff, tuple(draws), rng.dev if p_eff > 0.0 else None, live, loss, hact, prelu, *params)
+    draws = tuple(rng.take(x.shape[0] * lin.out_features) if p_eff > 0.0 else (0, 0) for lin in linears[:-1])
+    args = (x, rows, p_eff, draws, rng.dev if p_eff > 0.0 else None)
+    hact = None if kind == _lib.ACT_RELU else (kind, int(order))
+    prelu = act.weight if kind == _lib.ACT_PRELU else None
+    if route == "tall":
+        out = _TallHead.apply(*args, *params)
+    elif loss is not None and head_fuses_loss(route, rows, x, linears, loss, training):
+        return _DenseHead.apply(*args, hact, prelu, loss, *params)
+    else:
+        out = _DenseHead.apply(*args, hact, prelu, None, *params)
+    return (out, None) if loss is not None else out
 
 
 # ======================================================================================
@@ -1256,7 +1232,7 @@ class _PairHead(torch.autograd.Function):
     256 + ``inst.width`` -> 128 -> 1: one launch each way (<prefix>_fwd_f32 / <prefix>_bwd_f32), the two inputs read where they are.
     With ``target`` the forward also leaves d MSE / d out and the loss partials, and the node returns (out, loss): ``out`` then carries
     no gradient and the VALUE of ``loss`` is complete once backward has run (its sum rides in the backward launch), as with
-    ``_MLPHead``'s fused loss.  Where ``inst.gated`` (CDRP's ``cell_enc``) the gradient handed to the second input is already through the
+    ``_DenseHead``'s fused loss.  Where ``inst.gated`` (CDRP's ``cell_enc``) the gradient handed to the second input is already through the
     backward of the ReLU that produced it (tagged ``_fn_relu_gated`` for ``_CellTower``; applying that gate again, as a plain autograd
     ReLU would, changes nothing); otherwise (DTA's ``xt``, a Linear's output) it is NOT gated."""
 
@@ -1298,8 +1274,7 @@ class _PairHead(torch.autograd.Function):
         parts = loss_t = None
         if ctx.fused:
             g, parts, loss_t = ctx.saved_tensors[3:]
-            unit = _UNIT_GRAD.get(dev)
-            if g_loss is not None and not (unit is not None and g_loss.data_ptr() == unit.data_ptr()):
+            if g_loss is not None and not _is_unit_grad(g_loss):
                 g = g * g_loss
         else:
             g = _f32c(g_out, "g").reshape(-1)

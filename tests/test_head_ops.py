@@ -516,3 +516,275 @@ def test_head_with_fused_loss_equals_head_then_loss(loss_kind, n_classes, p):
     torch.testing.assert_close(x_c.grad, 3.0 * x_b.grad, atol=1e-7, rtol=1e-5)
     torch.testing.assert_close(loss_c, loss_b, atol=1e-6, rtol=1e-5)
     torch.testing.assert_close(head_c.predictor[-1].weight.grad, 3.0 * head_b.predictor[-1].weight.grad, atol=1e-6, rtol=1e-5)
+
+
+# ------------------------------------------------------------------------------------------------ the tall route of ops.mlp_head
+# (library GEMMs around fn_dropout_act_f32 / fn_gate_colsum_f32: an input width that is no multiple of 4, more than DENSE_MAX_ROWS
+# rows, or ops.DENSE_HEAD off), on the smallest shapes that reach each of its branches
+TALL_CASES = {
+    "odd_input_small_last": ((5, 6), (6, 8, 4, 3), 0.25),      # hidden layers tall, last Linear on the small kernel without a gate
+    "wide_last": ((5, 6), (6, 8, 20), 0.25),                   # last Linear wider than SMALL_LINEAR_MAX: addmm / mm / sum
+    "many_rows": ((4100, 8), (8, 8, 1), 0.1),                  # > DENSE_MAX_ROWS rows; > 2048: the chunked workspaces of both kernels
+}
+
+
+class _PaddedDraws:
+    """A PhiloxStream whose draws are sized as if the input had ``padded`` rows instead of ``rows`` (mlp_head draws per padded row)."""
+
+    def __init__(self, stream, rows, padded):
+        self.stream, self.rows, self.padded = stream, rows, padded
+
+    dev = None
+
+    def take(self, numel):
+        assert numel % self.rows == 0
+        return self.stream.take(numel // self.rows * self.padded)
+
+
+def _linears(dims, dev, seed=3):
+    torch.manual_seed(seed)
+    return [torch.nn.Linear(dims[i], dims[i + 1]).to(dev) for i in range(len(dims) - 1)]
+
+
+def _loop_head(x, lins, p, rng):
+    """the layer-by-layer loop of test_fused_head_equals_layer_by_layer_path"""
+    from fragnet_amd import ops
+    h = x
+    for lin in lins[:-1]:
+        h = ops.dropout_act(lin(h), p, True, True, rng)
+    return lins[-1](h)
+
+
+def _float64_head(x, lins, live=None):
+    """relu between the Linears in float64 on the CPU (p = 0); rows behind ``live`` are padding: output 0, no gradient"""
+    xd = x.detach().cpu().double().requires_grad_(True)
+    ps = [(lin.weight.detach().cpu().double().requires_grad_(True), lin.bias.detach().cpu().double().requires_grad_(True)) for lin in lins]
+    h = xd if live is None else xd[:live]
+    for i, (w, b) in enumerate(ps):
+        h = h @ w.t() + b
+        if i < len(ps) - 1:
+            h = torch.relu(h)
+    if live is not None:
+        h = torch.cat([h, h.new_zeros((x.shape[0] - live, h.shape[1]))])
+    return h, xd, [q for wb in ps for q in wb]
+
+
+def _backward(out, t, x, lins):
+    """(input gradient, parameter gradients) of sum(out * t), the parameters' .grad cleared afterwards"""
+    (out * t.to(out.device, out.dtype)).sum().backward()
+    got = x.grad, [q.grad for lin in lins for q in (lin.weight, lin.bias)]
+    for lin in lins:
+        lin.weight.grad = lin.bias.grad = None
+    return got
+
+
+def _assert_head_close(got, want):
+    """(out, input gradient, parameter gradients) at the tolerances of test_fused_head_equals_layer_by_layer_path"""
+    torch.testing.assert_close(got[0], want[0].to(got[0].device, torch.float32), atol=1e-5, rtol=1e-5)
+    torch.testing.assert_close(got[1], want[1].to(got[1].device, torch.float32), atol=1e-5, rtol=1e-4)
+    assert len(got[2]) == len(want[2])
+    for i, (a, b) in enumerate(zip(got[2], want[2])):
+        torch.testing.assert_close(a, b.to(a.device, torch.float32), atol=2e-5, rtol=1e-4, msg=lambda m, i=i: f"parameter {i}: {m}")
+
+
+def _mlp_head_run(x0, lins, p, t, rng, live=None):
+    from fragnet_amd import ops
+    x = x0.detach().clone().requires_grad_(True)
+    out = ops.mlp_head(x, lins, p, True, rng, live)
+    return (out.detach(), *_backward(out, t, x, lins))
+
+
+def _check_against_float64(x0, lins, t, live=None):
+    from fragnet_amd import ops
+    rng = ops.PhiloxStream(seed=11)
+    got = _mlp_head_run(x0, lins, 0.0, t, rng, live)
+    assert rng.offset == 0
+    ref, xd, ps = _float64_head(x0, lins, live)
+    (ref * t.cpu().double()).sum().backward()
+    _assert_head_close(got, (ref.detach(), xd.grad, [q.grad for q in ps]))
+
+
+@gpu
+@pytest.mark.parametrize("case", list(TALL_CASES))
+def test_tall_head_equals_layer_by_layer_path_and_float64(case):
+    """ops.mlp_head where the hidden layers take library GEMMs: outputs, input gradient, every parameter gradient and the stream's
+    final offset against the layer-by-layer loop under the same Philox draws, and against float64 torch without dropout."""
+    from fragnet_amd import ops
+    dev = _dev()
+    shape, dims, p = TALL_CASES[case]
+    lins = _linears(dims, dev)
+    assert ops.head_route(shape[0], lins, ops._lib.ACT_RELU) == "tall"
+    x0 = torch.randn(shape, device=dev)
+    t = torch.randn(shape[0], dims[-1], device=dev)
+    rng_a, rng_b = ops.PhiloxStream(seed=11), ops.PhiloxStream(seed=11)
+    got = _mlp_head_run(x0, lins, p, t, rng_a)
+    x_b = x0.detach().clone().requires_grad_(True)
+    out_b = _loop_head(x_b, lins, p, rng_b)
+    _assert_head_close(got, (out_b.detach(), *_backward(out_b, t, x_b, lins)))
+    assert rng_a.offset == rng_b.offset == sum((shape[0] * w + 3) // 4 for w in dims[1:-1])
+    _check_against_float64(x0, lins, t)
+
+
+@gpu
+@pytest.mark.parametrize("p", [0.25, 0.0])
+def test_tall_head_skips_padding_rows(p):
+    """live rows on the tall route, bit for bit as test_fused_head_skips_padding_rows: nine rows of which five are live against the
+    five alone (whose stream draws per padded row, as the head's does)."""
+    from fragnet_amd import ops
+    dev = _dev()
+    dims = (6, 8, 4, 3)
+    lins = _linears(dims, dev)
+    x0 = torch.randn(9, 6, device=dev)
+    t = torch.randn(9, 3, device=dev)
+    rng_a, rng_b = ops.PhiloxStream(seed=11), ops.PhiloxStream(seed=11)
+    out_a, gx_a, gp_a = _mlp_head_run(x0, lins, p, t, rng_a, live=5)
+    out_b, gx_b, gp_b = _mlp_head_run(x0[:5], lins, p, t[:5], _PaddedDraws(rng_b, 5, 9))
+    assert out_a.shape == (9, 3) and torch.equal(out_a[:5], out_b) and not out_a[5:].any()
+    assert gx_a.shape == (9, 6) and torch.equal(gx_a[:5], gx_b) and not gx_a[5:].any()
+    for i, (a, b) in enumerate(zip(gp_a, gp_b)):
+        assert torch.equal(a, b), i
+    assert rng_a.offset == rng_b.offset == (sum((9 * w + 3) // 4 for w in dims[1:-1]) if p else 0)
+    if not p:
+        _check_against_float64(x0, lins, t, live=5)
+
+
+@gpu
+@pytest.mark.parametrize("dense_head,K", [(True, 8), (False, 8), (False, 6)], ids=["dense_head_on", "dense_head_off", "library_last_linear"])
+def test_single_linear_head_with_padding_rows(dense_head, K):
+    """One Linear (no hidden layer) with live rows: its input gradient is the head's own, all rows of it, padding rows 0.  K = 8 runs
+    the small kernel each way whatever ops.DENSE_HEAD says (with no hidden layer there is nothing for the flag to decide); K = 6
+    is the library GEMM with the padding rows concatenated."""
+    from fragnet_amd import ops
+    dev = _dev()
+    lins = _linears((K, 3), dev)
+    x0 = torch.randn(5, K, device=dev)
+    t = torch.randn(5, 3, device=dev)
+    before = ops.DENSE_HEAD
+    try:
+        ops.DENSE_HEAD = dense_head
+        assert ops.head_route(3, lins, ops._lib.ACT_RELU) == ("dense" if K == 8 else "tall")
+        rng = ops.PhiloxStream(seed=11)
+        out_a, gx_a, gp_a = _mlp_head_run(x0, lins, 0.25, t, rng, live=3)
+        out_b, gx_b, gp_b = _mlp_head_run(x0[:3], lins, 0.25, t[:3], ops.PhiloxStream(seed=11))
+        assert rng.offset == 0
+        assert out_a.shape == (5, 3) and torch.equal(out_a[:3], out_b) and not out_a[3:].any()
+        assert gx_a.shape == (5, K) and torch.equal(gx_a[:3], gx_b) and not gx_a[3:].any()
+        for i, (a, b) in enumerate(zip(gp_a, gp_b)):
+            assert torch.equal(a, b), i
+        _check_against_float64(x0, lins, t, live=3)
+    finally:
+        ops.DENSE_HEAD = before
+
+
+@gpu
+def test_fthead3_on_the_tall_route_equals_the_dense_route():
+    """FTHead3 with ops.DENSE_HEAD off (what bench.py --library-head measures) against the same head on the dense kernels."""
+    from fragnet_amd import ops
+    from fragnet_amd.model import FTHead3
+    dev = _dev()
+    torch.manual_seed(3)
+    head_a = FTHead3(input_dim=128, drop_ratio=0.1, n_classes=1).to(dev).train()
+    head_b = copy.deepcopy(head_a)
+    x0 = torch.randn(64, 256, device=dev)
+    t = torch.randn(64, 1, device=dev)
+    res = []
+    before = ops.DENSE_HEAD
+    try:
+        for head, flag in ((head_a, False), (head_b, True)):
+            ops.DENSE_HEAD = flag
+            assert ops.head_route(64, list(head.predictor), ops._lib.ACT_RELU) == ("dense" if flag else "tall")
+            head.rng = ops.PhiloxStream(seed=11)
+            x = x0.detach().clone().requires_grad_(True)
+            out = head(x)
+            res.append((out.detach(), *_backward(out, t, x, list(head.predictor))))
+    finally:
+        ops.DENSE_HEAD = before
+    _assert_head_close(res[0], res[1])
+    assert head_a.rng.offset == head_b.rng.offset > 0
+
+
+# ------------------------------------------------------------------------------------------------ the route decision (host only)
+def _stack(*dims, bias=True):
+    return [torch.nn.Linear(dims[i], dims[i + 1], bias=bias) for i in range(len(dims) - 1)]
+
+
+def _strided(lin):
+    lin.weight = torch.nn.Parameter(torch.zeros(lin.in_features, lin.out_features).t())
+    assert not lin.weight.is_contiguous()
+    return lin
+
+
+def test_head_route_table():
+    """ops.head_route: which node a head runs on -- rows, widths, strides, biases, the activation kind and ops.DENSE_HEAD."""
+    from fragnet_amd import _lib, ops
+    relu, others = _lib.ACT_RELU, [_lib.ACT_SILU, _lib.ACT_GELU, _lib.ACT_CELU, _lib.ACT_SELU, _lib.ACT_RELU6, _lib.ACT_LEAKYRELU, _lib.ACT_PRELU]
+    assert ops.DENSE_HEAD and ops.DENSE_MAX_ROWS == 4096 and ops.SMALL_LINEAR_MAX == 16
+
+    def both(rows, lins, want_relu, want_others):
+        assert ops.head_route(rows, lins) == ops.head_route(rows, lins, relu) == want_relu
+        for kind in others:
+            assert ops.head_route(rows, lins, kind) == want_others, kind
+
+    for rows in (0, 1, 4096):
+        both(rows, _stack(8, 8, 4, 3), "dense", "dense")
+    both(4097, _stack(8, 8, 4, 3), "tall", None)
+    both(4097, _stack(8, 3), "dense", "dense")                      # a single Linear: no hidden layer for the row bound to hold for
+    both(5, _stack(6, 8, 4, 3), "tall", None)                       # first layer: input width
+    both(5, _stack(8, 6, 4, 3), None, None)                         # first layer: output width
+    both(5, _stack(8, 8, 6, 3), None, None)                         # a hidden layer's output width (= the last layer's input width)
+    both(5, _stack(8, 8, 4, 16), "dense", "dense")                  # last layer: 16 / 17 outputs
+    both(5, _stack(8, 8, 4, 17), "tall", None)
+    both(5, _stack(8, 3), "dense", "dense")                         # last layer alone: input width
+    both(5, _stack(6, 3), "tall", None)
+    both(5, _stack(6, 17), "tall", None)
+    lins = _stack(8, 8, 4, 3)
+    _strided(lins[1])
+    both(5, lins, "tall", None)                                     # a hidden weight that is not contiguous
+    lins = _stack(8, 8, 4, 3)
+    _strided(lins[-1])
+    both(5, lins, "dense", "dense")                                 # (the last Linear's is made contiguous for its launch)
+    for i in range(3):
+        lins = _stack(8, 8, 4, 3)
+        lins[i] = torch.nn.Linear(lins[i].in_features, lins[i].out_features, bias=False)
+        both(5, lins, None, None)
+    before = ops.DENSE_HEAD
+    try:
+        ops.DENSE_HEAD = False
+        both(5, _stack(8, 8, 4, 3), "tall", None)
+        both(5, _stack(8, 8, 6, 3), None, None)
+        both(5, _stack(8, 3), "dense", "dense")                     # no hidden layer: nothing for the flag to decide
+    finally:
+        ops.DENSE_HEAD = before
+
+
+def test_head_fuses_loss_table():
+    """ops.head_fuses_loss: when mlp_head(loss=...) folds the loss into the last Linear's launch."""
+    from fragnet_amd import _lib, ops
+    lins = _stack(8, 8, 4, 3)
+
+    def fuses(M=6, rows=5, lins=lins, route=None, grad=True, training=True, n_w=None, n_t=None):
+        x = torch.zeros(M, lins[0].in_features, requires_grad=grad)
+        loss = (_lib.LOSS_MSE, torch.zeros(M * lins[-1].out_features if n_t is None else n_t), torch.zeros(M if n_w is None else n_w))
+        got = ops.head_fuses_loss(ops.head_route(rows, lins) if route is None else route, rows, x, lins, loss, training)
+        assert isinstance(got, bool)
+        return got
+
+    before = ops.FUSED_HEAD_LOSS
+    try:
+        ops.FUSED_HEAD_LOSS = True
+        _fuses_loss_rows(fuses)
+        ops.FUSED_HEAD_LOSS = False
+        assert not fuses()
+    finally:
+        ops.FUSED_HEAD_LOSS = before
+
+
+def _fuses_loss_rows(fuses):
+    assert fuses() and fuses(rows=6) and fuses(rows=1) and fuses(M=4096, rows=4096)
+    assert not fuses(rows=0)                                        # nothing live
+    assert not fuses(grad=False) and not fuses(training=False)
+    assert not fuses(M=4100, rows=4097)                             # tall
+    assert not fuses(lins=_stack(6, 8, 4, 3)) and not fuses(lins=_stack(8, 8, 4, 17)) and not fuses(route="tall")
+    assert not fuses(lins=_stack(8, 3))                             # no hidden layer to carry the riders
+    assert fuses(lins=_stack(8, 1024, 3)) and not fuses(lins=_stack(8, 1028, 3))        # SMALL_LINEAR_LOSS_MAX_K
+    assert not fuses(n_w=5) and not fuses(n_t=6 * 3 - 1)            # one weight per padded row, one target per prediction
