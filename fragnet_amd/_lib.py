@@ -16,6 +16,7 @@ FN_D = 128
 FN_MAX_TASKS = 16
 FN_MAX_EDGE_K = 8
 FN_MAX_PART = 4096
+FN_GEOM_MAX_ATOMS, FN_GEOM_MAX_BONDS = 1024, 4096
 ROLE_PLAIN, ROLE_DST, ROLE_SRC = 0, 1, 2
 FN_EINVAL, FN_EUNSUPPORTED, FN_ETOOMANY = -1, -2, -3
 
@@ -216,6 +217,8 @@ SIGNATURES = {
     "fn_bond_graph_ws": [i64, i64],
     "fn_bond_graph_count": [vp, vp, i64, i64, i64, C.c_int, vp, vp, vp],
     "fn_bond_graph_fill": [vp, vp, i64, i64, i64, C.c_int, vp, vp, i64, vp],
+    "fn_bond_cos_f32": [vp, vp, vp, i64, i64, i64, vp, vp],
+    "fn_pretrain_geometry_f32": [vp, vp, vp, i64, i64, i64, i64, i64, vp, vp, vp, vp],
     "fn_masked_bce_f32": [vp, vp, vp, i64, C.c_int, vp, vp, vp],
     "fn_masked_mse_multi_ws": [C.c_int],
     "fn_masked_mse_multi_f32": [C.POINTER(MseTask), C.c_int, vp, vp, vp, vp],

@@ -76,6 +76,8 @@ def _collate_common(data_list: List) -> Dict[str, torch.Tensor]:
     out.offsets = mol_offsets({k: torch.as_tensor(v, dtype=torch.long) for k, v in per_mol.items()})
     out.max_per_mol = {k: max(v) for k, v in per_mol.items()}
     out.max_per_mol["mol"] = 1
+    if getattr(data_list[0], "positions", None) is not None:      # one conformer per record: the geometry keys can be derived from it (batch_to)
+        out["positions"] = cat0("positions").to(torch.float)
     return out
 
 
@@ -121,6 +123,16 @@ def batch_to(batch: Dict[str, torch.Tensor], device) -> Dict[str, torch.Tensor]:
         eifb = ops.bond_graph(out["frag_index"], out["frag_batch"], int(out["y"].shape[0]), fragments=True)
         out["edge_index_fbonds"] = eifb
         out["edge_attr_fbonds"] = out["node_features_fbonds"][eifb[0]] + out["node_features_fbonds"][eifb[1]]
+    if "positions" in out and out["positions"].is_cuda and "edge_index_bonds_graph" in out:
+        # a batch collated from a store that keeps coordinates instead of the tensors derived from them (FlatMolStore.without_geometry)
+        from . import ops
+        if "edge_attr_bonds" not in out:
+            out["edge_attr_bonds"] = ops.bond_cos(out["positions"], out["edge_index"], out["edge_index_bonds_graph"])
+        if "bnd_lngth" not in out:
+            m = getattr(out, "max_per_mol", None)
+            out["bnd_lngth"], out["bnd_angl"], out["dh_angl"] = ops.pretrain_geometry(
+                out["positions"], out["edge_index"], out["batch"], int(out["y"].shape[0]),
+                max_per_mol=(m["atom"], m["edge"]) if m else None)
     return out
 
 

@@ -20,6 +20,7 @@ _ROW_FIELDS = {           # concatenated along dim 0
     "x_atoms": "atom", "edge_attr": "edge", "cnx_attr": "fedge", "x_frags": "frag", "atom_id_frag_id": "atom",
     "node_features_bonds": "edge", "edge_attr_bonds": "bedge", "node_feautures_fbondg": "fedge",
     "edge_attr_fbondg": "fbedge", "bnd_lngth": "edge", "bnd_angl": "atom", "dh_angl": "edge",
+    "positions": "atom",       # optional: one conformer, [n, 3] float32 (the four GEOMETRY tensors are functions of it)
 }
 _COL_FIELDS = {"edge_index": "edge", "frag_index": "fedge", "edge_index_bonds": "bedge", "edge_index_fbondg": "fbedge"}
 _COUNT_OF = {"atom": "x_atoms", "edge": "edge_attr", "fedge": "cnx_attr", "frag": "x_frags", "bedge": "edge_attr_bonds",
@@ -49,7 +50,7 @@ class FlatMolStore:
                  smiles: Optional[List[str]] = None):
         self.t, self.off, self.y, self.smiles = tensors, offsets, y, smiles
         self.n = int(y.shape[0])
-        self.has_pretrain_targets = "bnd_lngth" in tensors
+        self.has_pretrain_targets = "bnd_lngth" in tensors or "positions" in tensors
 
     def __len__(self):
         return self.n
@@ -73,7 +74,31 @@ class FlatMolStore:
             offsets[space] = torch.cat([torch.zeros(1, dtype=torch.long), torch.cumsum(counts, 0)])
         y = torch.cat([r.y.reshape(1, -1) if r.y.dim() > 1 else r.y.reshape(1) for r in records], dim=0).to(torch.float)
         smiles = [getattr(r, "smiles", "") for r in records]
-        return cls(tensors, offsets, y, smiles)
+        store = cls(tensors, offsets, y, smiles)
+        store._check_positions()
+        return store
+
+    MIN_BOND_DISTANCE = 1e-3
+
+    def _check_positions(self):
+        """Coordinates are refused where they are attached if two bonded atoms (nearly) coincide: the geometry divides by their distance,
+        as the reference does (whose fix_zero_pos nudges coincident atoms apart by 1e-4 per coordinate before it featurises)."""
+        pos = self.t.get("positions")
+        if pos is None:
+            return
+        n_atoms = int(self.off["atom"][-1])
+        if pos.dtype != torch.float32 or tuple(pos.shape) != (n_atoms, 3):
+            raise ValueError(f"positions: expected float32 [{n_atoms}, 3], got {pos.dtype} {tuple(pos.shape)}")
+        ei = self.t["edge_index"]
+        first = self.off["atom"][:-1].to(ei.device)
+        per_mol = (self.off["edge"][1:] - self.off["edge"][:-1]).to(ei.device)
+        g = ei + torch.repeat_interleave(first, per_mol, output_size=ei.shape[1])      # stored ids are molecule-local
+        if g.numel():
+            d = (pos[g[0]] - pos[g[1]]).norm(dim=1)
+            if not bool((d >= self.MIN_BOND_DISTANCE).all()):        # NaN coordinates fail this too
+                k = int(torch.nonzero(~(d >= self.MIN_BOND_DISTANCE))[0])
+                raise ValueError(f"positions: bonded atoms {int(g[0, k])} and {int(g[1, k])} (store rows) are closer than "
+                                 f"{self.MIN_BOND_DISTANCE} (distance {float(d[k]):.3g}): the bond geometry is undefined")
 
     def to(self, device) -> "FlatMolStore":
         return FlatMolStore({k: v.to(device) for k, v in self.t.items()}, {k: v.to(device) for k, v in self.off.items()},
@@ -89,6 +114,7 @@ class FlatMolStore:
         if blob.get("format") != "fragnet_amd.flat.v1":
             raise ValueError(f"{path}: not a fragnet_amd flat store")
         store = cls(blob["tensors"], blob["offsets"], blob["y"], blob.get("smiles"))
+        store._check_positions()
         return store.to(device) if device is not None else store
 
     def replicate(self, k: int) -> "FlatMolStore":
@@ -113,6 +139,28 @@ class FlatMolStore:
         and the connection features on the GPU (ops.bond_graph, SURVEY §8 row f4: the reference's pair rules in the
         reference's order, so the stored cos(theta) rows ``edge_attr_bonds`` still line up)."""
         return FlatMolStore({k: v for k, v in self.t.items() if k not in self.DERIVED}, self.off, self.y, self.smiles)
+
+    GEOMETRY = ("edge_attr_bonds", "bnd_lngth", "bnd_angl", "dh_angl")
+
+    def without_geometry(self) -> "FlatMolStore":
+        """The same store minus the float tensors that are pure functions of ``positions``: the bond-graph edge attribute
+        ``edge_attr_bonds`` (one float per bond-graph edge) and the pretraining targets ``bnd_lngth``, ``bnd_angl``, ``dh_angl``.
+        ``collate`` on a GPU store then computes them for the batch from the collated coordinates (ops.bond_cos, ops.pretrain_geometry),
+        in the rows of the batch's bond-graph index, stored or rebuilt -- composes with ``without_bond_graph_index()`` in either order.
+        The ``bedge`` offsets stay: ``bond_graph_edges()`` and the row totals of a batch read them."""
+        if "positions" not in self.t:
+            raise ValueError("without_geometry: the store has no positions to derive the geometry tensors from")
+        return FlatMolStore({k: v for k, v in self.t.items() if k not in self.GEOMETRY}, self.off, self.y, self.smiles)
+
+    def _fill_geometry(self, out, pretrain: bool, n_mols: int):
+        """The derived float tensors of a batch collated on the GPU from a store that keeps coordinates instead of them."""
+        from . import ops
+        if out.get("edge_attr_bonds") is None:
+            out["edge_attr_bonds"] = ops.bond_cos(out["positions"], out["edge_index"], out["edge_index_bonds_graph"])
+        if pretrain and "bnd_lngth" not in out:
+            m = self.max_per_mol()
+            out["bnd_lngth"], out["bnd_angl"], out["dh_angl"] = ops.pretrain_geometry(
+                out["positions"], out["edge_index"], out["batch"], n_mols, max_per_mol=(m["atom"], m["edge"]))
 
     def bond_graph_edges(self) -> torch.Tensor:
         """Per-molecule bond-graph edge counts: the dominant cost, used to balance shards (parallel.shard_indices)."""
@@ -167,7 +215,7 @@ class FlatMolStore:
             "atom_to_frag_ids": t["atom_id_frag_id"][rows["atom"]] + base["frag"][seg["atom"]],
             "node_features_bonds": t["node_features_bonds"][rows["edge"]],
             "edge_index_bonds_graph": None,      # filled below (stored index, or rebuilt on the device)
-            "edge_attr_bonds": t["edge_attr_bonds"][rows["bedge"]],
+            "edge_attr_bonds": t["edge_attr_bonds"][rows["bedge"]] if "edge_attr_bonds" in t else None,      # else from positions, below
             "node_features_fbonds": t["node_feautures_fbondg"][rows["fedge"]],
             "edge_index_fbonds": None,           # filled below too
             "edge_attr_fbonds": None,
@@ -189,11 +237,19 @@ class FlatMolStore:
             out["edge_attr_fbonds"] = out["node_features_fbonds"][eifb[0]] + out["node_features_fbonds"][eifb[1]]      # data.py:291-303
         else:
             del out["edge_index_fbonds"], out["edge_attr_fbonds"]
-        if pretrain:
+        if pretrain and "bnd_lngth" in t:
             out["bnd_lngth"] = t["bnd_lngth"][rows["edge"]]
             out["bnd_angl"] = t["bnd_angl"][rows["atom"]]
             out["dh_angl"] = t["dh_angl"][rows["edge"]]
         out["y"] = self.y[idx]
+        if "positions" in t:
+            out["positions"] = t["positions"][rows["atom"]]
+            if dev.type == "cuda":            # after the index tensors exist; a CPU store leaves the derived keys to data.batch_to(batch, gpu)
+                self._fill_geometry(out, pretrain, int(idx.numel()))
+        if out.get("edge_attr_bonds", 0) is None:
+            if "positions" not in t:
+                raise KeyError("edge_attr_bonds: the store holds neither the tensor nor the positions to derive it from")
+            del out["edge_attr_bonds"]
         # the per-molecule offsets of the batch (plan.CollatedBatch.offsets): cumulative lengths, already on the device;
         # molecule extents are bounded by the store's own maxima (no device synchronisation here)
         if all(s in length for s in ("atom", "edge", "bedge", "frag", "fedge", "fbedge")):
@@ -223,6 +279,9 @@ class FlatMolStore:
         rows_spec = dict(self._FUSED_ROWS)
         if pretrain:
             rows_spec.update(self._FUSED_PT)
+        if "positions" in t:            # a store with coordinates: they ride as one more field, and a derived tensor it dropped is computed below
+            rows_spec = {k: v for k, v in rows_spec.items() if v[0] not in self.GEOMETRY or v[0] in t}
+            rows_spec["positions"] = ("positions", "atom")
         need = [v[0] for v in rows_spec.values()] + [v[0] for v in self._FUSED_IDS.values()]
         if any(k not in t for k in need):
             return None
@@ -291,6 +350,8 @@ class FlatMolStore:
             timing.append((ev0, ev1))
         slot[1] = torch.cuda.Event()
         slot[1].record(torch.cuda.current_stream(dev))      # the pinned buffer is free again once the launch above has read it
+        if "positions" in t:
+            self._fill_geometry(out, pretrain, B)
         out._keep = (tab_d,)
         out.offsets = off_d
         out.max_per_mol = self.max_per_mol()

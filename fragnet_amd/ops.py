@@ -1071,7 +1071,7 @@ def bond_graph(edge_index: torch.Tensor, atom_batch: torch.Tensor, n_mols: int, 
     """``edge_index_bonds_graph`` [2, Eb] (int64, global bond ids) of a collated batch from its ``edge_index`` [2, E] and
     ``batch`` vector -- the reference's get_bond_pair_bond_graph + one-bond-fragment rule (dataset/data.py:116-127,
     157-182) on the GPU, in the reference's order, so a dataset can ship without its largest tensor (the per-pair
-    cos(theta) attribute still has to be stored: it needs 3-D coordinates).  ``fragments=True``: ``edge_index_fbonds`` from
+    cos(theta) attribute is stored, or computed from atom coordinates in the same rows: ``bond_cos``).  ``fragments=True``: ``edge_index_fbonds`` from
     ``frag_index`` and ``frag_batch`` (get_bond_pair_fbond_graph, data.py:131-154).  One host sync to learn Eb."""
     if not edge_index.is_cuda or edge_index.dtype != torch.int64 or atom_batch.dtype != torch.int64:
         raise _lib.FragnetHipError("bond_graph: int64 GPU tensors expected (there is no CPU fallback)")
@@ -1085,6 +1085,64 @@ def bond_graph(edge_index: torch.Tensor, atom_batch: torch.Tensor, n_mols: int, 
     out = torch.empty((2, n), dtype=torch.int64, device=dev)
     _lib.call("fn_bond_graph_fill", edge_index.data_ptr(), atom_batch.data_ptr(), E, N, n_mols, mode, ws.data_ptr(), out.data_ptr(), n, st)
     return out
+
+
+# ======================================================================================
+# geometry of a collated batch from atom coordinates (dataset side; csrc/geometry.hip)
+# ======================================================================================
+def _geom_inputs(positions, edge_index, what):
+    if not (positions.is_cuda and edge_index.is_cuda):
+        raise _lib.FragnetHipError(f"{what}: fragnet_amd kernels need GPU tensors; there is no CPU fallback (synth.geometry_from_positions "
+                                   "is the host evaluation)")
+    if positions.dtype != torch.float32 or positions.dim() != 2 or positions.shape[1] != 3:
+        raise TypeError(f"{what}: positions must be float32 [N, 3], got {positions.dtype} {tuple(positions.shape)}")
+    if edge_index.dtype != torch.int64 or edge_index.dim() != 2 or edge_index.shape[0] != 2:
+        raise TypeError(f"{what}: edge_index must be int64 [2, E], got {edge_index.dtype} {tuple(edge_index.shape)}")
+    return positions.contiguous(), edge_index.contiguous()
+
+
+def bond_cos(positions: torch.Tensor, edge_index: torch.Tensor, edge_index_bonds_graph: torch.Tensor) -> torch.Tensor:
+    """``edge_attr_bonds`` [Eb, 1] of a collated batch from its atom coordinates [N, 3]: for the bond-graph edge (bond i, bond j) the
+    cosine of the angle at the atom the two bonds share -- the clamped dot product of the two unit vectors, what the reference gets from
+    RDKit's GetAngleRad and np.cos (dataset/data.py:185-211) -- and exactly 1 for the two directions of one bond (one-bond fragments).
+    Rows follow ``edge_index_bonds_graph``, stored or rebuilt by ``bond_graph``.  One launch, no synchronisation."""
+    positions, edge_index = _geom_inputs(positions, edge_index, "bond_cos")
+    if not edge_index_bonds_graph.is_cuda:
+        raise _lib.FragnetHipError("bond_cos: fragnet_amd kernels need GPU tensors; there is no CPU fallback")
+    if edge_index_bonds_graph.dtype != torch.int64 or edge_index_bonds_graph.dim() != 2 or edge_index_bonds_graph.shape[0] != 2:
+        raise TypeError("bond_cos: edge_index_bonds_graph must be int64 [2, Eb]")
+    eib = edge_index_bonds_graph.contiguous()
+    out = torch.empty((eib.shape[1], 1), dtype=torch.float32, device=positions.device)
+    _lib.call("fn_bond_cos_f32", positions.data_ptr(), edge_index.data_ptr(), eib.data_ptr(), positions.shape[0], edge_index.shape[1],
+              eib.shape[1], out.data_ptr(), _stream_ptr(positions.device))
+    return out
+
+
+def pretrain_geometry(positions: torch.Tensor, edge_index: torch.Tensor, batch: torch.Tensor, n_mols: int, max_per_mol=None):
+    """The three pretraining targets of a collated batch from its atom coordinates (reference get_bond_angle_dhangle, dataset/data.py:
+    224-260, quirks included -- DESIGN.md "Geometry from coordinates"): ``(bnd_lngth [E, 1], bnd_angl [N, 1], dh_angl [E, 1])`` = the
+    SQUARED bond length, 3 S_a^2 and S_src S_dst (3 - sigma_e^2).  ``batch`` [N] is the collated atom -> molecule vector (non-decreasing,
+    bonds grouped by molecule).  ``max_per_mol``: (atoms, directed bonds) of the largest molecule when the caller knows them on the host
+    (a store does); None reads them back from the device, one synchronisation.  Molecules beyond 1024 atoms / 4096 directed bonds are
+    refused.  Sums run in edge order without atomics: bit-identical from run to run."""
+    positions, edge_index = _geom_inputs(positions, edge_index, "pretrain_geometry")
+    if not batch.is_cuda:
+        raise _lib.FragnetHipError("pretrain_geometry: fragnet_amd kernels need GPU tensors; there is no CPU fallback")
+    if batch.dtype != torch.int64 or batch.dim() != 1 or batch.shape[0] != positions.shape[0]:
+        raise TypeError("pretrain_geometry: batch must be int64 [N]")
+    batch = batch.contiguous()
+    N, E, dev = positions.shape[0], edge_index.shape[1], positions.device
+    if max_per_mol is None:
+        max_atoms = int(torch.bincount(batch, minlength=1).max()) if N else 0
+        max_bonds = int(torch.bincount(batch[edge_index[0]], minlength=1).max()) if E else 0
+    else:
+        max_atoms, max_bonds = (int(v) for v in max_per_mol)
+    bl = torch.empty((E, 1), dtype=torch.float32, device=dev)
+    ba = torch.empty((N, 1), dtype=torch.float32, device=dev)
+    dh = torch.empty((E, 1), dtype=torch.float32, device=dev)
+    _lib.call("fn_pretrain_geometry_f32", positions.data_ptr(), edge_index.data_ptr(), batch.data_ptr(), N, E, int(n_mols), max_atoms,
+              max_bonds, bl.data_ptr(), ba.data_ptr(), dh.data_ptr(), _stream_ptr(dev))
+    return bl, ba, dh
 
 
 # ======================================================================================

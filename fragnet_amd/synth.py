@@ -65,6 +65,7 @@ class MolRecord:
     bnd_angl: Optional[torch.Tensor] = None    # [n, 1]
     dh_angl: Optional[torch.Tensor] = None     # [e, 1]
     smiles: str = ""
+    positions: Optional[torch.Tensor] = None   # [n, 3] f32: one conformer (attach_positions)
 
 
 def bond_graph_pairs(ends: np.ndarray) -> np.ndarray:
@@ -351,6 +352,101 @@ def attach_protein(mols: List[MolRecord], seed: int, length: int = 1000, pinned=
             v[:] = 0.0
             v[:len(seq)] = seq
         m.protein = torch.from_numpy(v)
+    return mols
+
+
+# ----------------------------------------------------------------------------------------
+# Geometry from one conformer: the bond-graph edge attribute and the three pretraining targets as the reference's featuriser derives
+# them (dataset/data.py:185-211 get_edge_attr_bond_graph, :224-260 get_bond_angle_dhangle), restated from their definitions:
+#   u_e = (p[src] - p[dst]) / |p[src] - p[dst]|,  sigma_e = u_x + u_y + u_z,  S_a = sum of sigma_e over the bonds leaving a, ascending e
+#   bnd_lngth[e] = |p[src] - p[dst]|^2     (squared: the reference takes no root)
+#   bnd_angl[a]  = 3 S_a^2                 (the reference sums the unit vectors of an atom over ALL components into one scalar)
+#   dh_angl[e]   = S_src S_dst (3 - sigma_e^2)
+#   cos[j]       = 1 for the two directions of one bond, else the clamped dot product of the unit vectors from the shared atom
+# ----------------------------------------------------------------------------------------
+def geometry_from_positions(positions, edge_index, edge_index_bonds=None, dtype=np.float32):
+    """Host evaluation (NumPy, ``dtype`` arithmetic) of what ops.bond_cos / ops.pretrain_geometry compute on the GPU, for one molecule or
+    a whole batch (ids only have to be consistent).  Returns a dict of torch tensors: ``bnd_lngth`` [e, 1], ``bnd_angl`` [n, 1],
+    ``dh_angl`` [e, 1] and, when ``edge_index_bonds`` [2, eb] is given, ``edge_attr_bonds`` [eb, 1]."""
+    p = np.asarray(positions, dtype=dtype).reshape(-1, 3)
+    ei = np.asarray(edge_index, dtype=np.int64).reshape(2, -1)
+    src, dst = ei
+    n = p.shape[0]
+    d = p[src] - p[dst]
+    l2 = (d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]) + d[:, 2] * d[:, 2]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        u = d / np.sqrt(l2)[:, None]
+    sigma = (u[:, 0] + u[:, 1]) + u[:, 2]
+    S = np.zeros(n, dtype=dtype)
+    np.add.at(S, src, sigma)                                  # unbuffered, in edge order
+    out = {"bnd_lngth": l2.reshape(-1, 1), "bnd_angl": (dtype(3.0) * (S * S)).reshape(-1, 1),
+           "dh_angl": ((S[src] * S[dst]) * (dtype(3.0) - sigma * sigma)).reshape(-1, 1)}
+    if edge_index_bonds is not None:
+        n1, n2 = np.asarray(edge_index_bonds, dtype=np.int64).reshape(2, -1)
+        a1, b1, a2, b2 = src[n1], dst[n1], src[n2], dst[n2]
+        rev = (a1 == b2) & (b1 == a2)
+        first = (a1 == a2) | (a1 == b2)                       # the shared atom is bond 1's source, else its destination
+        c = np.where(first, a1, b1)
+        o0 = np.where(first, b1, a1)
+        o1 = np.where(c == a2, b2, a2)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            v0, v1 = p[o0] - p[c], p[o1] - p[c]
+            u0 = v0 / np.sqrt((v0 * v0).sum(1))[:, None]
+            u1 = v1 / np.sqrt((v1 * v1).sum(1))[:, None]
+        cos = np.clip((u0[:, 0] * u1[:, 0] + u0[:, 1] * u1[:, 1]) + u0[:, 2] * u1[:, 2], -1.0, 1.0)
+        out["edge_attr_bonds"] = np.where(rev, dtype(1.0), cos).reshape(-1, 1)
+    return {k: torch.from_numpy(np.ascontiguousarray(v, dtype=np.float32)) for k, v in out.items()}
+
+
+def _place_atoms(rng, n: int, edge_index: np.ndarray) -> np.ndarray:
+    """Breadth-first placement: a component starts at an origin drawn from N(0, 3^2) at its lowest atom; every newly reached neighbour
+    (ascending id) sits U(0.9, 1.6) from its parent in a uniformly random direction, redrawn while it lands within 0.5 of a placed atom."""
+    nbrs = [[] for _ in range(n)]
+    for a, b in zip(edge_index[0].tolist(), edge_index[1].tolist()):
+        nbrs[a].append(b)
+    pos = np.zeros((n, 3))
+    placed = np.zeros(n, dtype=bool)
+
+    def put(a, draw):
+        for _ in range(10000):
+            cand = draw()
+            if not placed.any() or np.min(np.linalg.norm(pos[placed] - cand, axis=1)) >= 0.5:
+                pos[a], placed[a] = cand, True
+                return
+        raise RuntimeError("attach_positions: no free place for an atom")
+
+    def beside(parent):
+        v = rng.normal(size=3)
+        return pos[parent] + rng.uniform(0.9, 1.6) * v / np.linalg.norm(v)
+
+    for root in range(n):
+        if placed[root]:
+            continue
+        put(root, lambda: rng.normal(0.0, 3.0, size=3))
+        queue = [root]
+        while queue:
+            a = queue.pop(0)
+            for b in sorted(set(nbrs[a])):
+                if not placed[b]:
+                    put(b, lambda: beside(a))
+                    queue.append(b)
+    return pos.astype(np.float32)
+
+
+def attach_positions(mols: List[MolRecord], seed: int) -> List[MolRecord]:
+    """Gives every record ``positions`` [n, 3] (one synthetic conformer; an RNG of its own, so synth_molecules' stream is untouched) and
+    OVERWRITES ``edge_attr_bonds`` -- and ``bnd_lngth`` / ``bnd_angl`` / ``dh_angl`` where the record has them -- with the values
+    geometry_from_positions derives from those positions, so that a store with and one without the derived tensors describe the same
+    molecules.  Ring-closure bonds get whatever length the placement leaves them.  Returns ``mols``."""
+    rng = np.random.default_rng(seed)
+    for m in mols:
+        ei = m.edge_index.numpy()
+        pos = _place_atoms(rng, int(m.x_atoms.shape[0]), ei)
+        geo = geometry_from_positions(pos, ei, m.edge_index_bonds.numpy())
+        m.positions = torch.from_numpy(pos)
+        m.edge_attr_bonds = geo["edge_attr_bonds"]
+        if m.bnd_lngth is not None:
+            m.bnd_lngth, m.bnd_angl, m.dh_angl = geo["bnd_lngth"], geo["bnd_angl"], geo["dh_angl"]
     return mols
 
 

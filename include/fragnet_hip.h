@@ -473,8 +473,8 @@ int fn_dropout_act_bwd_f32(const float* g_y, const float* y, float* g_x, int64_t
  * molecule sharing exactly one atom, i-major / j ascending, then per molecule the mutual pairs of its two-atom
  * components (lowest atom first).  Bond id = column of the batched, molecule-contiguous edge_index [2, E];
  * atom_mol [N] = molecule of every atom (the batch vector).  Two calls because Eb is only known on the device:
- * count (fills ws, writes *total = Eb), then fill into out [2, total].  The cos(theta) attribute needs coordinates
- * and is not produced.  ws: fn_bond_graph_ws(E, B) int32.
+ * count (fills ws, writes *total = Eb), then fill into out [2, total].  The cos(theta) attribute needs coordinates:
+ * fn_bond_cos_f32 below, in the rows of this index.  ws: fn_bond_graph_ws(E, B) int32.
  * ------------------------------------------------------------------------------------------ */
 /* mode FN_GRAPH_BONDS: the rule above on edge_index / batch.  mode FN_GRAPH_FBONDS: the fragment-bond graph of
  * data.py:131-154 on frag_index / frag_batch -- a molecule with exactly two connection nodes pairs the ones whose
@@ -487,6 +487,30 @@ int fn_bond_graph_count(const int64_t* edge_index /*[2,E]*/, const int64_t* atom
                         int mode, int32_t* ws, int64_t* total /*device [1]*/, fn_stream_t stream);
 int fn_bond_graph_fill(const int64_t* edge_index, const int64_t* atom_mol, int64_t E, int64_t N, int64_t B, int mode,
                        const int32_t* ws, int64_t* out /*[2,total]*/, int64_t total, fn_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Geometry of a collated batch from atom coordinates (dataset-side; reference fragnet/dataset/data.py:185-211
+ * get_edge_attr_bond_graph and :224-260 get_bond_angle_dhangle; csrc/geometry.hip).  pos [N, 3] fp32, src, dst = edge_index
+ * [2, E]; u_e = (pos[src] - pos[dst]) / |.|, sigma_e = u_x + u_y + u_z, S_a = sum of sigma_e over the bonds leaving atom a in
+ * ascending e.  All outputs fp32, no atomics (bit-identical from run to run), no allocation, no host synchronisation.
+ *   fn_bond_cos_f32: out[j] for bond-graph edge (n1, n2) = edge_index_bonds_graph[:, j]: exactly 1 when the two bonds are the
+ *     two directions of one bond (one-bond fragments), else the dot product, clamped to [-1, 1], of the unit vectors from the
+ *     atom the two bonds share to their other atoms.  One flat launch.
+ *   fn_pretrain_geometry_f32: bnd_lngth[e] = |pos[src] - pos[dst]|^2 (squared, as the reference stores it), bnd_angl[a] =
+ *     3 S_a^2 (0 for an atom without bonds), dh_angl[e] = S_src S_dst (3 - sigma_e^2).  One workgroup per molecule: atom_mol
+ *     [N] (the batch vector, values 0 .. B-1) must be non-decreasing and the bonds grouped by molecule in the same order, as
+ *     every collate of this project lays a batch out.  max_atoms / max_bonds: the caller's bound on one molecule's atoms and
+ *     directed bonds; above FN_GEOM_MAX_ATOMS / FN_GEOM_MAX_BONDS the call returns FN_EUNSUPPORTED (a molecule that exceeds
+ *     the limits although the caller said otherwise gets NaN rows).
+ * Coincident bonded atoms divide by zero as in the reference; an id outside its table gives a NaN row and is not dereferenced.
+ * ------------------------------------------------------------------------------------------ */
+#define FN_GEOM_MAX_ATOMS 1024
+#define FN_GEOM_MAX_BONDS 4096
+int fn_bond_cos_f32(const float* pos /*[N,3]*/, const int64_t* edge_index /*[2,E]*/, const int64_t* edge_index_bonds_graph /*[2,Eb]*/,
+                    int64_t N, int64_t E, int64_t Eb, float* out /*[Eb]*/, fn_stream_t stream);
+int fn_pretrain_geometry_f32(const float* pos /*[N,3]*/, const int64_t* edge_index /*[2,E]*/, const int64_t* atom_mol /*[N]*/, int64_t N,
+                             int64_t E, int64_t B, int64_t max_atoms, int64_t max_bonds, float* bnd_lngth /*[E]*/,
+                             float* bnd_angl /*[N]*/, float* dh_angl /*[E]*/, fn_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
  * Prediction-head small ops (FTHead1-5, gat2.py:631-637, 719-725, 745-751: Linear -> dropout -> act stacks on
