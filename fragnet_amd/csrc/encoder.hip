@@ -38,12 +38,9 @@ using fni::launch_gat_fwd_pair_lin;
 using fni::GatBwdOneArgs;
 using fni::CuTask;
 using fni::CuTasks;
-using fni::GsdSegTask;
-using fni::GsdSegTasks;
 using fni::prep_gat_bwd_one;
 using fni::launch_gat_bwd_one3;
 using fni::launch_gat_cu;
-using fni::launch_gsd_seg;
 using fni::launch_linear128_group;
 using fni::launch_linear128_small_group;
 using fni::launch_linear128_ns;
@@ -124,7 +121,7 @@ __device__ __forceinline__ void row_dots_sorted_bwd_range(const RowDotsBwdArgs& 
                     if ((lane & 7) == 0) {
                         const int64_t at = e * 4 + (lane >> 3);
                         T.cu_c[at] = cc;
-                        if (T.cu_u) T.cu_u[at] = uu - cc * sgm[u];      // (null: the deferred one-pass backward wants c only)
+                        if (T.cu_u) T.cu_u[at] = uu - cc * sgm[u];
                     }
                 }
             }
@@ -276,16 +273,13 @@ __global__ void k_gate_many(GateTasks G) {
 #include "linear128.inc"
 
 // the one-pass backward's second launch of a layer: input-gradient products (one 64 x 64 tile per workgroup; RowAdd epilogue where a
-// task carries one; the epilogue also writes the dot c = <g, out> of the rows it finishes, CuEpi)  ||  the parameter-gradient partials of
-// the atom graph's edge term
-// (GS: the deferred form -- every lane sums one dz segment into g_s_dst, one more MFMA step adds the rank-4 term, GsdEpi; c is the only dot left)
-// (GO: the mixed form's boundary launches -- deferred rows in, rows of a layer with a second forward output out: both epilogues)
-template <bool GS = false, bool GO = false>
+// task carries one; the epilogue also writes the dots c = <g, out>, u = <g, out2> - c sigma of the rows it finishes, CuEpi)  ||  the
+// parameter-gradient partials of the atom graph's edge term
 __global__ __launch_bounds__(kBlock, 3) void k_lin_rd_cu(LinTasks T, RowDotsBwdArgs R) {
     extern __shared__ __attribute__((aligned(16))) float sBt[];
     __shared__ float sR[kRows][FN_D];
     const int b = (int)blockIdx.x;
-    if (b < T.total) { lin_side_block<true, GS, GO>(sBt, T, b);  return; }
+    if (b < T.total) { lin_side_block<true>(sBt, T, b);  return; }
     row_dots_sorted_bwd_body(R, sR, b - T.total, R.nblk);
 }
 
@@ -392,9 +386,6 @@ struct EncPrologue {
     const float* ssr[2];  const float* sss[2];  float* sso[2];  int n_ss[2];   // the same two attributes in SOURCE order (one-pass backward): from raw, else from sorted
     float* zp;  int64_t zn;  int n_z;                               // buffer zeroed once per forward (edge-term scratch: loop positions stay 0)
     MolExtArgs mx;  int n_x;                                        // molecule extents for the molecule-resident backward (256 molecules per block)
-    // deferred one-pass backward (GsdEpi): R[z][h][k] = sum_{c < 32} att[z][h * att_w[z] + c] * W[z][(32 h + c) * 128 + k] for the K = 128
-    // projections z (four heads; two blocks per matrix)
-    const float* rW[3 * FN_MAX_LAYERS];  const float* rA[3 * FN_MAX_LAYERS];  int rAw[3 * FN_MAX_LAYERS];  float* rOut;  int n_r;
 };
 __global__ __launch_bounds__(256) void k_enc_prologue(EncPrologue A) {
     __shared__ float tile[32][33];
@@ -431,36 +422,16 @@ __global__ __launch_bounds__(256) void k_enc_prologue(EncPrologue A) {
         return;
     }
     b -= A.n_z;
-    if (b < A.n_x) { mol_extents_body(A.mx, b);  return; }
-    b -= A.n_x;
-    if (b < A.n_r) {
-        const int z = b >> 1, o = (b & 1) * 256 + (int)threadIdx.x, hh = o >> 7, k = o & 127;
-        const float* W = A.rW[z];
-        const float* a = A.rA[z] + hh * A.rAw[z];
-        float acc = 0.f;
-        if (W) {
-#pragma unroll 8
-            for (int c = 0; c < 32; ++c) acc = fmaf(a[c], W[(size_t)(32 * hh + c) * 128 + k], acc);
-        }
-        A.rOut[(size_t)z * 512 + o] = acc;
-    }
+    if (b < A.n_x) mol_extents_body(A.mx, b);
 }
 
 // Weight gradient: block = `rows_per_block` rows in chunks of 32 staged through double-buffered LDS.  Wave w owns
 // output rows o in [32(w&3), +32) and the (w>>2)-th group of CTW 16-column tiles of X, so NH = 2 column groups
 // put two waves on every SIMD.  part [grid][128*K + 128]: dW partial followed by the db partial.
 constexpr int kWgChunk = 32;
-// gsd != null (four heads): the deferred form of the one-pass attention backward, see wgrad128.inc -- the dY rows get their missing
-// term g_s_dst[row] a_dst as they are fetched, and the block also leaves U[h][k] = sum_rows g_s_dst[row, h] X[row, k], S[h] =
-// sum_rows g_s_dst[row, h] in upart [grid][4 K + 4] (the chunk's g_s_dst rows travel in the padding columns of the X tile)
-// (GD: compile-time, like DF in wgrad128.inc -- as a run-time test inside fetch / stash it slowed the plain products down)
-template <int CTW, int NH, bool GD = false>
+template <int CTW, int NH>
 __device__ __forceinline__ void wgrad_body(float* smem, const float* __restrict__ dY, const float* __restrict__ X, int K,
-                                           int64_t M, int rows_per_block, float* __restrict__ part, int bid,
-                                           const float* __restrict__ gsd_ = nullptr, const float* __restrict__ a_dst = nullptr,
-                                           int att_w = 0, float* __restrict__ upart_ = nullptr) {
-    const float* __restrict__ gsd = GD ? gsd_ : nullptr;
-    float* __restrict__ upart = GD ? upart_ : nullptr;
+                                           int64_t M, int rows_per_block, float* __restrict__ part, int bid) {
     constexpr int NT = 256 * NH;
     constexpr int XW = 16 * CTW * NH;            // padded X width held in LDS
     constexpr int XLD = XW + 16;                 // XW is a multiple of 32 for every instantiation but <1,1>
@@ -476,17 +447,6 @@ __device__ __forceinline__ void wgrad_body(float* smem, const float* __restrict_
     constexpr int XPT = (kWgChunk * XW + NT - 1) / NT;        // X scalars per thread per chunk
     float4 ry[YPT];
     float rx[XPT];
-    float4 rg = make_float4(0.f, 0.f, 0.f, 0.f);           // threads 0..31: the chunk row's g_s_dst (deferred term)
-    // the term is added where the dY operand leaves LDS: the lane's two columns 32 wo + i, + 16 belong to head wo, so a step costs one
-    // more LDS read (the row's g_s_dst[wo], staged in the X tile's padding columns) and two FMAs.  (Per-thread scalar loads of
-    // g_s_dst in the fetch made the layer-0 workgroups -- latency-bound, one round trip per chunk, the tail of the launch -- 60 % longer.)
-    const int wo_ = (tid >> 6) & 3;
-    const float ad0 = GD ? a_dst[wo_ * att_w + (tid & 15)] : 0.f, ad1 = GD ? a_dst[wo_ * att_w + 16 + (tid & 15)] : 0.f;
-    constexpr int UP = (XW + NT / 4 - 1) / (NT / 4);        // U columns per thread: thread = (head tid & 3, column tid >> 2 [+ NT / 4])
-    float uacc[UP];
-#pragma unroll
-    for (int q = 0; q < UP; ++q) uacc[q] = 0.f;
-    float sacc = 0.f;
     auto fetch = [&](int c) {
         const int64_t base = m_begin + (int64_t)c * kWgChunk;
 #pragma unroll
@@ -494,7 +454,6 @@ __device__ __forceinline__ void wgrad_body(float* smem, const float* __restrict_
             const int idx = tid + q * NT, r = idx >> 5, c4 = idx & 31;
             ry[q] = (base + r < m_end) ? ld4(dY + (base + r) * 128 + c4 * 4) : make_float4(0.f, 0.f, 0.f, 0.f);
         }
-        if (GD && tid < kWgChunk) rg = (base + tid < m_end) ? ld4(gsd + (base + tid) * 4) : make_float4(0.f, 0.f, 0.f, 0.f);
 #pragma unroll
         for (int q = 0; q < XPT; ++q) {
             const int idx = tid + q * NT, r = idx / XW, cc = idx % XW;
@@ -512,7 +471,6 @@ __device__ __forceinline__ void wgrad_body(float* smem, const float* __restrict_
             const int idx = tid + q * NT, r = idx / XW, cc = idx % XW;
             if (r < kWgChunk) sX[(buf * kWgChunk + r) * XLD + cc] = rx[q];
         }
-        if (GD && tid < kWgChunk) st4(sX + (buf * kWgChunk + tid) * XLD + XW, rg);       // the row's padding columns XW .. XW + 3
     };
 
     f32x4 acc[2][CTW];
@@ -531,12 +489,7 @@ __device__ __forceinline__ void wgrad_body(float* smem, const float* __restrict_
         for (int s = 0; s < kWgChunk / 4; ++s) {
             const float* yrow = sY + (buf * kWgChunk + 4 * s + kq) * kBtLd + 32 * wo + i;
             const float* xrow = sX + (buf * kWgChunk + 4 * s + kq) * XLD + 16 * CTW * wc + i;
-            float a0 = yrow[0], a1 = yrow[16];
-            if constexpr (GD) {
-                const float gq = sX[(buf * kWgChunk + 4 * s + kq) * XLD + XW + wo];
-                a0 = fmaf(gq, ad0, a0);
-                a1 = fmaf(gq, ad1, a1);
-            }
+            const float a0 = yrow[0], a1 = yrow[16];
             bsum[0] += a0;
             bsum[1] += a1;
             float bv[CTW];
@@ -548,31 +501,8 @@ __device__ __forceinline__ void wgrad_body(float* smem, const float* __restrict_
                 acc[1][cc] = __builtin_amdgcn_mfma_f32_16x16x4f32(a1, bv[cc], acc[1][cc], 0, 0, 0);
             }
         }
-        if (GD && upart) {  // the side product U, S of this chunk (rows past the end were stashed as zeros)
-            const int hh = tid & 3;
-#pragma unroll 8
-            for (int r = 0; r < kWgChunk; ++r) {
-                const float* xr = sX + (buf * kWgChunk + r) * XLD;
-                const float g = xr[XW + hh];
-#pragma unroll
-                for (int q = 0; q < UP; ++q) {
-                    const int k = (tid >> 2) + q * (NT / 4);
-                    if (k < XW) uacc[q] = fmaf(g, xr[k], uacc[q]);
-                }
-                sacc += g;
-            }
-        }
         if (c + 1 < n_chunks) stash(buf ^ 1);
         __syncthreads();
-    }
-    if (GD && upart) {
-        float* up = upart + (size_t)bid * (4 * K + 4);
-#pragma unroll
-        for (int q = 0; q < UP; ++q) {
-            const int k = (tid >> 2) + q * (NT / 4);
-            if (k < K) up[(tid & 3) * K + k] = uacc[q];
-        }
-        if (tid < 4) up[4 * K + tid] = sacc;
     }
     // partials are written in the accumulators' native layout: one coalesced 16-byte store per lane and tile;
     // k_wgrad_reduce maps them back to dW[o][col] while summing over blocks
@@ -611,11 +541,6 @@ struct WgradTask {
     int rpb, first;
     int K;                    // k_linear128_wgrad_mixed only: this product's reduction length (0 elsewhere: WgradTasks::K)
     const int32_t* n_real;    // nullable device word: rows at or behind *n_real are padding (zero gradient rows) and are not read
-    // the deferred form of the one-pass attention backward (wgrad128.inc): dY lacks g_s_dst[row] a_dst; gsd == null: nothing to add
-    const float* gsd;         // [M][4]
-    const float* a_dst;       // att + dst_off: head h's 32 floats at a_dst + h * att_w
-    int att_w;
-    float* upart;             // [blocks][4 K + 4]: U[h][k] = sum_rows gsd[row, h] X[row, k], then S[h] = sum_rows gsd[row, h]
 };
 constexpr int kMaxWgradTasks = 3 * FN_MAX_LAYERS;
 struct WgradTasks {
@@ -642,11 +567,7 @@ __global__ __launch_bounds__(512) void k_linear128_wgrad_mixed(WgradTasks T) {
     const WgradTask& t = T.t[ti];
     const int bid = (int)blockIdx.x - t.first;
     const int64_t M = t.n_real && *t.n_real < t.M ? (int64_t)*t.n_real : t.M;
-    if (t.gsd) {
-        if (t.K <= 32) wgrad_body<1, 2, true>(smem, t.dY, t.X, t.K, M, t.rpb, t.part, bid, t.gsd, t.a_dst, t.att_w, t.upart);
-        else if (t.K <= 128) wgrad_body<4, 2, true>(smem, t.dY, t.X, t.K, M, t.rpb, t.part, bid, t.gsd, t.a_dst, t.att_w, t.upart);
-        else wgrad_body<6, 2, true>(smem, t.dY, t.X, t.K, M, t.rpb, t.part, bid, t.gsd, t.a_dst, t.att_w, t.upart);
-    } else if (t.K <= 32) wgrad_body<1, 2>(smem, t.dY, t.X, t.K, M, t.rpb, t.part, bid);
+    if (t.K <= 32) wgrad_body<1, 2>(smem, t.dY, t.X, t.K, M, t.rpb, t.part, bid);
     else if (t.K <= 128) wgrad_body<4, 2>(smem, t.dY, t.X, t.K, M, t.rpb, t.part, bid);
     else wgrad_body<6, 2>(smem, t.dY, t.X, t.K, M, t.rpb, t.part, bid);
 }
@@ -659,8 +580,7 @@ __global__ __launch_bounds__(512) void k_wgrad_all(const WgradTasks W, const Wgr
     if ((int)blockIdx.x < n128) {
         int ti = 0;
         while (ti + 1 < W.n && (int)blockIdx.x >= W.t[ti + 1].first) ++ti;
-        if (W.t[ti].gsd) wgrad128_block<2, true>(W.t[ti], (int)blockIdx.x - W.t[ti].first, smem);
-        else wgrad128_block<2, false>(W.t[ti], (int)blockIdx.x - W.t[ti].first, smem);
+        wgrad128_block<2>(W.t[ti], (int)blockIdx.x - W.t[ti].first, smem);
         return;
     }
     const int b = (int)blockIdx.x - n128;
@@ -669,11 +589,7 @@ __global__ __launch_bounds__(512) void k_wgrad_all(const WgradTasks W, const Wgr
     const WgradTask& t = W0.t[ti];
     const int bid = b - t.first;
     const int64_t M = t.n_real && *t.n_real < t.M ? (int64_t)*t.n_real : t.M;
-    if (t.gsd) {
-        if (t.K <= 32) wgrad_body<1, 2, true>(smem, t.dY, t.X, t.K, M, t.rpb, t.part, bid, t.gsd, t.a_dst, t.att_w, t.upart);
-        else if (t.K <= 128) wgrad_body<4, 2, true>(smem, t.dY, t.X, t.K, M, t.rpb, t.part, bid, t.gsd, t.a_dst, t.att_w, t.upart);
-        else wgrad_body<6, 2, true>(smem, t.dY, t.X, t.K, M, t.rpb, t.part, bid, t.gsd, t.a_dst, t.att_w, t.upart);
-    } else if (t.K <= 32) wgrad_body<1, 2>(smem, t.dY, t.X, t.K, M, t.rpb, t.part, bid);
+    if (t.K <= 32) wgrad_body<1, 2>(smem, t.dY, t.X, t.K, M, t.rpb, t.part, bid);
     else if (t.K <= 128) wgrad_body<4, 2>(smem, t.dY, t.X, t.K, M, t.rpb, t.part, bid);
     else wgrad_body<6, 2>(smem, t.dY, t.X, t.K, M, t.rpb, t.part, bid);
 }
@@ -729,10 +645,6 @@ struct ReduceTask {
     int att_w, dst_off, src_off, K;
     float *o0, *o1, *o2;
     int ld, off, cls, pad_;
-    // RT_FINALIZE, deferred form of the one-pass backward (gat_bwd_one.inc DF, four heads): the level's pass left no dL/da_dst partials;
-    // four extra blocks (one per head) form it from the weight-gradient kernels' side product: dL/da_dst[c] = sum_k W[c, k] U[h(c), k] + b[c] S[h(c)]
-    const float *up, *upW, *upb;      // up [n_up][4 upK + 4] per-block partials of U | S; the projection's weight [128][upK] and bias; up == null: none
-    int n_up, upK;
 };
 constexpr int kMaxReduceTasks = 36;      // one launch for all 30 tasks of a 4-layer backward pass (5.5 KB of kernel arguments)
 struct ReduceTasks {
@@ -808,34 +720,6 @@ __device__ __forceinline__ void wgrad_reduce_strip(int vb, float* sm, const floa
     }
 }
 
-// the four extra blocks (one per head) of a deferred level's RT_FINALIZE task (ReduceTask::up); sm: 4096 floats
-__device__ __forceinline__ void adst_from_u_body(const ReduceTask& t, float* sm, int hh) {
-    const int K = t.upK, UW = 4 * K + 4, tid = threadIdx.x;
-    // column sums of this head's K columns of the partial rows (+ its S): 256 columns x 4 row groups, four loads in flight
-    const int col = tid & 255, rg = tid >> 8;
-    const float* src = t.up + (col < K ? hh * K + col : 4 * K + hh);
-    float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
-    if (col <= K) {
-        int r = rg;
-        for (; r + 12 < t.n_up; r += 16) {
-            a0 += src[(size_t)r * UW];        a1 += src[(size_t)(r + 4) * UW];
-            a2 += src[(size_t)(r + 8) * UW];  a3 += src[(size_t)(r + 12) * UW];
-        }
-        for (; r < t.n_up; r += 4) a0 += src[(size_t)r * UW];
-    }
-    sm[rg * 256 + col] = (a0 + a1) + (a2 + a3);
-    __syncthreads();
-    if (tid < 256) sm[1024 + tid] = (sm[tid] + sm[256 + tid]) + (sm[512 + tid] + sm[768 + tid]);       // U[hh][0..K), then S[hh] at K
-    __syncthreads();
-    const float* U = sm + 1024;
-    const int c = hh * 32 + (tid >> 5), part = tid & 31;     // 32 columns of the head x 32 lanes
-    float a = 0.f;
-    for (int k = part; k < K; k += 32) a = fmaf(t.upW[(size_t)c * K + k], U[k], a);
-#pragma unroll
-    for (int off = 16; off > 0; off >>= 1) a += __shfl_xor(a, off);
-    if (part == 0) t.o0[hh * t.att_w + t.dst_off + (c & 31)] = fmaf(t.upb[c], U[K], a);
-}
-
 // the stand-alone launch of gat_finalize_body (fn_gat_bwd_finalize_f32): beside the task-table kernel that runs the same body
 __global__ __launch_bounds__(1024) void k_gat_finalize(const float* __restrict__ part_a, int n_a,
                                                        const float* __restrict__ part_e, int n_e, fn_edge_term et,
@@ -855,17 +739,14 @@ __global__ __launch_bounds__(1024) void k_reduce_tasks(ReduceTasks T, AdamRide R
     const int vb = (int)blockIdx.x - T.first[ti];
     if (t.kind == RT_FINALIZE) {
         if (vb < 2 * FN_D / 32) {
-            if (t.up && vb < FN_D / 32) return;             // deferred form: dL/da_dst comes from the extra block below, not from partials
             const int col = vb * 32 + (threadIdx.x >> 5);
             const float v = colmajor_sum_32(t.p0 + (size_t)col * FN_MAX_PART, t.n0);
             if ((threadIdx.x & 31) == 0) {
                 const int DH = FN_D / t.H, cc = col & 127, part = col >> 7;
                 t.o0[(cc / DH) * t.att_w + (part ? t.src_off : t.dst_off) + (cc % DH)] = v;
             }
-        } else if (vb == 2 * FN_D / 32 && t.et.mode == 2) {
+        } else {             // (the one block behind them: a level with an embedded edge attribute, mode 2)
             gat_finalize_body(2 * FN_D, sm, t.p0, t.n0, t.p1, t.n1, t.et, t.att, t.att_w, t.dst_off, t.src_off, t.o0, t.o1, t.o2, t.H);
-        } else {
-            adst_from_u_body(t, sm, vb - 2 * FN_D / 32 - (t.et.mode == 2 ? 1 : 0));
         }
     } else if (t.kind == RT_COLSUM) {
         const int col = vb * 32 + (threadIdx.x >> 5);
@@ -943,8 +824,8 @@ struct Bump {
 };
 
 // The three projected attention levels of a layer.  The value is the level's slot in the per-layer tables of the workspace: the
-// transposed projection weights (EncLayout::bt) and the deferred form's R matrices (EncLayout::rmat) of layer l's level v are entry
-// 3 l + v.  The fragment graph is a fourth level without a projection (no slot); only the last layer's ever runs.
+// transposed projection weights (EncLayout::bt) of layer l's level v are entry 3 l + v.  The fragment graph is a fourth level without
+// a projection (no slot); only the last layer's ever runs.
 enum Level : int { LV_BOND = 0, LV_ATOM = 1, LV_FBOND = 2, LV_FRAG = 3 };
 constexpr int kLevels = 3;
 constexpr Level kProjected[kLevels] = {LV_BOND, LV_ATOM, LV_FBOND};
@@ -971,7 +852,6 @@ struct EncLayout {
     float* mol_ext;          // MolExt[n_mols] for the molecule-resident backward (null without molecule CSRs)
     float *xs_bond, *xs_fbond;   // one-pass backward: the two raw edge attributes in source order ([1][bond.m], [k_fattr][fbond.m])
     float* real_rows;            // pad_skip_on: int32 [4] = real atoms, bonds, fragments, connections (written by the forward prologue)
-    float* rmat;                 // defer_on: R [3 n_layers][4][128] of the K = 128 projections (GsdEpi; written by the forward prologue)
     int64_t total;
 };
 
@@ -991,26 +871,10 @@ bool one_pass_on(const fn_encoder* e) {
            e->atom.m_real == e->E;
 }
 
-// the deferred form of the one-pass backward (gat_bwd_one.inc DF, FN_TUNE_DEFER_GSD): no second output in the forward.  Four heads
-// (the 16-lane segment sums and the rank-4 epilogue are written for them), gat2, and the grouped direct weight-gradient kernels
-// bit l set: layer l's three levels run the deferred form.  FN_TUNE_DEFER_GSD = 1: every layer; 2: the MIXED form -- layers >= 1
-// deferred, layer 0 with the second forward output (layer 0 has no input-gradient product to form g_s_dst in and its weight-gradient
-// kernels are the K = 167 / 17 / 6 ones: k_gsd_seg and their deferred-term variants were what the all-layer form paid most for)
-uint32_t defer_mask(const fn_encoder* e) {
-    const int key = tune(FN_TUNE_DEFER_GSD);
-    if (key == 0 || !(one_pass_on(e) && e->heads == 4 && e->variant == 0 && tune(FN_TUNE_GEMM_COLAUNCH) != 0 && tune(FN_TUNE_WGRAD_DIRECT) == 1))
-        return 0;
-    const uint32_t all = (1u << e->n_layers) - 1u;
-    return key == 2 ? (all & ~1u) : all;
-}
-bool defer_on(const fn_encoder* e) { return defer_mask(e) != 0; }
-bool defer_on(const fn_encoder* e, int l) { return ((defer_mask(e) >> l) & 1u) != 0; }
-
-// The form a forward pass ran in (bit 0: one-pass backward = out2 / sigma or dz tables exist; bit 1: its deferred form = no out2 /
-// sigma, rmat written), latched per activation workspace: fn_encoder_backward refuses a descriptor whose form -- read from the
-// process-wide tuning table -- is no longer the one its forward wrote the workspace in (FN_TUNE_BWD_ONE / FN_TUNE_DEFER_GSD flipped
-// in between would leave out2 / sigma / rmat null or unwritten for the other half).
-int enc_form(const fn_encoder* e) { return (one_pass_on(e) ? 1 : 0) | (int)(defer_mask(e) << 1); }
+// The form a forward pass ran in (1: one-pass backward = out2 / sigma exist; 0: two passes), latched per activation workspace:
+// fn_encoder_backward refuses a descriptor whose form -- read from the process-wide tuning table -- is no longer the one its forward
+// wrote the workspace in (FN_TUNE_BWD_ONE flipped in between would leave out2 / sigma null or unwritten for the other half).
+int enc_form(const fn_encoder* e) { return one_pass_on(e) ? 1 : 0; }
 struct FormLatch { const float* ws; int form; };
 FormLatch g_form_latch[64];
 int g_form_latch_next = 0;
@@ -1048,7 +912,6 @@ EncLayout enc_layout(const fn_encoder* e, float* ws) {
     }
     if (one_pass_on(e)) {
         for (int l = 0; l < e->n_layers; ++l) {
-            if (defer_on(e, l)) continue;
             LayerActs& a = o.L[l];
             for (Level v : kProjected) a.lv[v].o2 = b.take(level_rows(e, v) * FN_D);
             for (Level v : kProjected) a.lv[v].sg = b.take(level_rows(e, v) * H);
@@ -1057,7 +920,6 @@ EncLayout enc_layout(const fn_encoder* e, float* ws) {
         o.xs_fbond = b.take(e->fbond.m * e->k_fattr);
     }
     o.real_rows = pad_skip_on(e) ? b.take(64) : nullptr;
-    o.rmat = defer_on(e) ? b.take((int64_t)3 * e->n_layers * 512) : nullptr;
     o.in_atoms0 = drop ? b.take(e->N * e->k_atom0) : nullptr;
     o.atoms_new = b.take(e->N * FN_D);
     for (int l = 0; l < e->n_layers; ++l) o.L[l].lv[LV_ATOM].raw = o.atoms_new;
@@ -1095,7 +957,6 @@ bool tail_mol_on(const fn_encoder* e) {
 struct LevelScratch {
     float *g_h, *dz, *pz, *g_s_dst, *part_a, *part_e, *part_rd, *wg_ws;
     float* cdot;             // one-pass backward: c[n, H] = <g, out> per head (no pz then)
-    float *dz_em, *upart;    // its deferred form: dz at destination-order slots [m][H]; the weight-gradient kernels' side product U | S per block
 };
 struct BwdLayout {
     float* g_pre[kLevels + 1];   // by Level: grads w.r.t. pre-activation layer outputs (the chain)
@@ -1111,11 +972,8 @@ BwdLayout bwd_layout(const fn_encoder* e, float* ws) {
     o.g_pre[LV_ATOM] = b.take(e->N * FN_D);  o.g_pre[LV_FRAG] = b.take(e->F * FN_D);
     o.g_pre[LV_BOND] = b.take(e->E * FN_D);  o.g_pre[LV_FBOND] = b.take(e->EF * FN_D);
     o.g_frags = b.take(e->F * FN_D);
-    auto level = [&](LevelScratch& s, int64_t n, int64_t m, int k0, bool edge_params, bool row_dots, bool proj, bool one = false, bool df = false) {
+    auto level = [&](LevelScratch& s, int64_t n, int64_t m, int k0, bool edge_params, bool row_dots, bool proj, bool one = false) {
         s.g_h = b.take(n * FN_D);
-        s.dz_em = one && df ? b.take(m * H) : nullptr;
-        // (a weight-gradient launch has at most n / wgrad_rows_per_block(n) + 1 blocks per product)
-        s.upart = one && df && proj ? b.take((n / wgrad_rows_per_block(n) + 2) * (int64_t)(4 * (k0 > FN_D ? k0 : FN_D) + 4)) : nullptr;
         s.dz = row_dots ? b.take(m * H) : nullptr;
         s.pz = one ? nullptr : b.take(2 * m * H);
         s.cdot = one ? b.take(n * H) : nullptr;
@@ -1128,7 +986,7 @@ BwdLayout bwd_layout(const fn_encoder* e, float* ws) {
     // the atom level's edge term is a table of row dots (parameter partials part_rd); the other two embed a raw attribute (part_e)
     for (int l = 0; l < e->n_layers; ++l)
         for (Level v : kProjected)
-            level(o.lv[l][v], level_rows(e, v), level_plan(e, v).m, level_k0(e, v), v != LV_ATOM, v == LV_ATOM, true, one_pass_on(e), defer_on(e, l));
+            level(o.lv[l][v], level_rows(e, v), level_plan(e, v).m, level_k0(e, v), v != LV_ATOM, v == LV_ATOM, true, one_pass_on(e));
     level(o.frag, e->F, e->frag.m, 0, e->variant == 2, true, false);      // gat2_edge: the fragment graph has edge-embedding partials
     o.total = b.used;
     return o;
@@ -1186,7 +1044,6 @@ struct LevelView {
     float *s_dst, *s_src;           // node-scalar scratch of the forward
     LevelActs a;                    // what the forward keeps of the level
     int rng_slot;                   // RngPlan::y[layer][.]: ordered atoms, frags, bond, fbond -- NOT the Level order
-    const float* rmat;              // deferred form: the projection's R [4][128] (null unless defer_on)
 };
 LevelView level_view(const fn_encoder* e, const EncLayout& lay, int l, Level v) {
     const int d = FN_D / e->heads;
@@ -1203,7 +1060,6 @@ LevelView level_view(const fn_encoder* e, const EncLayout& lay, int l, Level v) 
     if (v != LV_FRAG) {
         o.W = w.W;  o.bias = w.bias;  o.K = l ? FN_D : level_k0(e, v);
         o.Wt = lay.bt + (size_t)(3 * l + v) * 192 * FN_D;
-        o.rmat = lay.rmat ? lay.rmat + (size_t)(3 * l + v) * 512 : nullptr;
         o.s_dst = lay.s_dst[v];  o.s_src = lay.s_src[v];
     } else { o.s_dst = lay.s_dst[LV_BOND];  o.s_src = lay.s_src[LV_BOND]; }
     switch (v) {
@@ -1240,14 +1096,6 @@ inline float gate_scale(const fn_encoder* e) {
 // the four outputs of the encoder, or the gradients w.r.t. them, by Level (null: not stored / zero)
 struct EncOutputs { const float* y[kLevels + 1]; };
 
-// the deferred term of a level's g_h rows (deferred form of the one-pass backward), for the product that reads them and for the
-// weight-gradient kernels (all null: the level's layer is not deferred, or the level has no edges)
-struct DeferTerm { const float* dz; const float* gsd_c; GsdEpi gs; const float* a_dst; int att_w; };
-inline DeferTerm defer_term(const LevelView& v, const LevelScratch& sc) {
-    if (!sc.dz_em || v.pl->m <= 0) return DeferTerm{nullptr, nullptr, GsdEpi{nullptr, nullptr, 0, nullptr, nullptr}, nullptr, 0};
-    return DeferTerm{sc.dz_em, sc.g_s_dst, GsdEpi{sc.dz_em, v.pl->rowptr_d, v.pl->pos_base_d, v.rmat, sc.g_s_dst}, v.att, v.att_w};
-}
-
 // the level's edge term as the forward's attention kernels take it (mode 0: the table of row dots the forward fills)
 inline fn_edge_term fwd_edge_term(const LevelView& v, const float* s_sorted) {
     fn_edge_term et = v.et;
@@ -1269,11 +1117,6 @@ inline LinTask proj_task(const LevelView& v, int k_task = 0) {
 // and the projection's weight gradient from its g_h rows
 struct ParamWork {
     int n_a = 0, n_e = 0;
-    // one-pass backward: the finalize task and the product leave in the same pair of launches (reserve), and
-    bool one_pass = false;
-    const DeferTerm* df = nullptr;   // ... the rows lack the deferred term
-    bool up = false;                 // ... whose dL/da_dst comes out of the product's side product U | S (else: k_gsd_seg, layer 0)
-    bool link = false;               // ... the product tells the finalize task how many partial rows of U | S there are
     int n_rd = 0;                    // two-pass atom level: partial rows of the edge term's dL/da[:, mid block], reduced between the two
 };
 
@@ -1294,9 +1137,6 @@ struct ReduceQueue {
     int blocks = 0, wblocks = 0, w0blocks = 0;
     bool defer_mixed = false;
     int w_reduce[kMaxWgradTasks] = {};      // index in T of each grouped product's reduction
-    int w_fin[kMaxWgradTasks] = {};         // ... and of its level's RT_FINALIZE task when the product carries the deferred term (n_up is set at flush)
-    int last_index = -1;                    // index in T of the task pushed last
-    bool defer_wgrad = false;
     hipStream_t st = nullptr;
     // launches whatever the caller still holds back that the queued tasks read (the pipelined backward's pending source pass):
     // a flush in the middle of a pass -- more than kMaxReduceTasks / kMaxWgradTasks queued, i.e. six or more layers -- would
@@ -1318,28 +1158,16 @@ struct ReduceQueue {
         if (T.n == kMaxReduceTasks) { if (int rc = flush()) return rc; }
         t.first = blocks;  t.nblk = nblk;
         T.first[T.n] = blocks;
-        last_index = T.n;
         T.t[T.n++] = t;
         blocks += nblk;
         return 0;
     }
-    // room for `tasks` more reductions and one more product in every group WITHOUT a flush in between: a deferred level's finalize
-    // task and its weight-gradient product must leave in the same pair of launches (the first reads what the second's partner wrote)
-    int reserve(int tasks) {
-        if (T.n + tasks > kMaxReduceTasks || W.n == kMaxWgradTasks || W0.n == kMaxWgradTasks) return flush();
-        return 0;
-    }
     // dL/d(attention vector, edge embedding) of a level from the n_a / n_e partial rows its pass left in the level's scratch
-    // up != null: the deferred form (ReduceTask::up, with the projection it belongs to); n_up is filled in when the level's
-    // weight-gradient product is queued (wgrad below)
-    int finalize(const LevelView& v, const LevelWeights& g, const LevelScratch& sc, int n_a, int n_e, const float* up = nullptr,
-                 bool up_proj = false) {
+    int finalize(const LevelView& v, const LevelWeights& g, const LevelScratch& sc, int n_a, int n_e) {
         ReduceTask t{};
         t.kind = RT_FINALIZE;  t.H = v.H;  t.p0 = sc.part_a;  t.n0 = n_a;  t.p1 = sc.part_e;  t.n1 = n_e;  t.et = v.et;
         t.att = v.att;  t.att_w = v.att_w;  t.dst_off = 0;  t.src_off = v.src_off;  t.o0 = g.att;  t.o1 = g.embW;  t.o2 = g.embb;
-        t.up = up;  t.n_up = 0;
-        if (up_proj) { t.upW = v.W;  t.upb = v.bias;  t.upK = v.K; }
-        return push(t, 2 * FN_D / 32 + (v.et.mode == 2 ? 1 : 0) + (up ? 4 : 0));
+        return push(t, 2 * FN_D / 32 + (v.et.mode == 2 ? 1 : 0));
     }
     int colsum(const float* part, int n_rows, int cols, float* out, int ld, int off) {
         ReduceTask t{};
@@ -1348,15 +1176,10 @@ struct ReduceQueue {
         return push(t, cols / 32);
     }
     // dW [128,K], db [128] of a level's projection from its g_h rows: partial kernel now (on `launch_on`), reduction with the rest
-    // df.gsd_c != null: the deferred term (WgradTask::gsd ..); fin: index in T of the level's RT_FINALIZE task (queued just before, reserve())
-    int wgrad(const LevelView& v, const LevelWeights& g, const LevelScratch& sc, hipStream_t launch_on, const DeferTerm& df = DeferTerm{},
-              float* upart = nullptr, int fin = -1) {
-        const float* gsd = df.gsd_c;
+    int wgrad(const LevelView& v, const LevelWeights& g, const LevelScratch& sc, hipStream_t launch_on) {
         const int K = v.K;
         const int64_t M = v.rows;
         float* ws = sc.wg_ws;
-        if (gsd && !(defer_wgrad && (K == FN_D ? tune(FN_TUNE_WGRAD_DIRECT) != 0 : (defer_mixed && K <= 192))))
-            return fail(FN_EUNSUPPORTED, "weight gradient: the deferred term needs the grouped direct kernels");
         if (M == 0) {
             hipLaunchKernelGGL(k_zero2_i32, dim3(flat_grid(128 * (K + 1), kGridCap)), dim3(kBlock), 0, launch_on,
                                reinterpret_cast<int32_t*>(g.W), (int64_t)128 * K, reinterpret_cast<int32_t*>(g.bias), (int64_t)128);
@@ -1364,13 +1187,12 @@ struct ReduceQueue {
         }
         ReduceTask t{};
         int grid = 0;
-        if (K == FN_D && defer_wgrad) {   // partial product joins the grouped launch in flush(); its block count is set there
+        if (K == FN_D) {   // partial product joins the grouped launch in flush(); its block count is set there
             if (W.n == kMaxWgradTasks || T.n == kMaxReduceTasks) { if (int rc = flush()) return rc; }
-            W.t[W.n] = WgradTask{sc.g_h, v.x, ws, M, 0, 0, 0, v.n_real, gsd, df.a_dst, df.att_w, upart};
-            w_fin[W.n] = gsd ? fin : -1;
+            W.t[W.n] = WgradTask{sc.g_h, v.x, ws, M, 0, 0, 0, v.n_real};
             w_reduce[W.n++] = T.n;
             t.cls = tune(FN_TUNE_WGRAD_DIRECT) ? 4 : 2;
-        } else if (defer_wgrad && defer_mixed && K <= 192) {      // layer 0's products: one launch for them too (flush_wgrad)
+        } else if (defer_mixed && K <= 192) {      // layer 0's products: one launch for them too (flush_wgrad)
             if (W0.n == kMaxWgradTasks || T.n == kMaxReduceTasks) { if (int rc = flush()) return rc; }
             // rows per block: a multiple of the per-product rule (FN_TUNE_WGRAD0_ROWS).  Fewer, longer blocks = fewer partial
             // rows to write and to reduce: at 1 x layer 0's atom product alone wrote 217 partials of 98 KB (21 MB, more than the
@@ -1380,8 +1202,7 @@ struct ReduceQueue {
             const int mult = std::max(1, K > FN_D ? tv / 10 : tv % 10);          // tens: the wide product (atoms), units: the narrow ones
             const int rpb = wgrad_rows_per_block(M) * mult;
             grid = (int)((M + rpb - 1) / rpb);
-            W0.t[W0.n++] = WgradTask{sc.g_h, v.x, ws, M, rpb, w0blocks, K, v.n_real, gsd, df.a_dst, df.att_w, upart};
-            if (gsd && fin >= 0) T.t[fin].n_up = grid;
+            W0.t[W0.n++] = WgradTask{sc.g_h, v.x, ws, M, rpb, w0blocks, K, v.n_real};
             w0blocks += grid;
             t.cls = K <= 32 ? 1 : K <= 128 ? 2 : 3;              // the instantiation k_linear128_wgrad_mixed runs for this K
         } else if (int rc = wgrad_partials(sc.g_h, v.x, K, M, ws, launch_on, &grid, &t.cls)) return rc;
@@ -1405,7 +1226,6 @@ struct ReduceQueue {
             t.first = wblocks;
             const int grid = (int)((t.M + t.rpb - 1) / t.rpb);
             T.t[w_reduce[i]].n0 = grid;
-            if (w_fin[i] >= 0) T.t[w_fin[i]].n_up = grid;
             wblocks += grid;
         }
         W.K = FN_D;
@@ -1449,11 +1269,9 @@ struct ReduceQueue {
     }
     // a level's parameter work (ParamWork), queued in the order finalize, [column sum], weight gradient
     int level_params(const LevelView& v, const LevelWeights& g, const LevelScratch& sc, const ParamWork& o, hipStream_t launch_on) {
-        const DeferTerm df = o.df ? *o.df : DeferTerm{};
-        if (o.one_pass) { if (int rc = reserve(2)) return rc; }
-        if (int rc = finalize(v, g, sc, o.n_a, o.n_e, o.up && df.dz ? sc.upart : nullptr, o.link)) return rc;
+        if (int rc = finalize(v, g, sc, o.n_a, o.n_e)) return rc;
         if (o.n_rd) { if (int rc = colsum(sc.part_rd, o.n_rd, v.H * FN_D, g.att, v.att_w, v.mid_off)) return rc; }
-        return wgrad(v, g, sc, launch_on, df, o.up ? sc.upart : nullptr, o.link ? last_index : -1);
+        return wgrad(v, g, sc, launch_on);
     }
 };
 
@@ -1492,6 +1310,7 @@ static int launch_lin_rd(LinTasks& T, const RowDotsBwdArgs& R, hipStream_t st) {
         if (T.t[i].M <= 0) continue;
         LinTask t = T.t[i];
         if (((uintptr_t)t.X | (uintptr_t)t.Bt | (uintptr_t)t.Y | (uintptr_t)t.bias | (uintptr_t)t.mk.y) & 15) aligned = false;
+        if (t.cu.c && !t.cu.out2) return fail(FN_EINVAL, "input-gradient products: a task's dots need out2 / sigma");
         t.first = blocks;
         t.nblk = lin_blocks((t.M + kLinRows - 1) / kLinRows, 1);
         blocks += t.nblk;
@@ -1506,16 +1325,7 @@ static int launch_lin_rd(LinTasks& T, const RowDotsBwdArgs& R, hipStream_t st) {
         return 0;
     }
     if (!aligned) return fail(FN_EINVAL, "input-gradient products: operands must be 16-byte aligned");
-    bool gs = false, go = false, plain_o2 = false;
-    for (int i = 0; i < T.n; ++i) {
-        gs = gs || T.t[i].gs.dz != nullptr;
-        go = go || (T.t[i].cu.c && T.t[i].cu.out2);          // rows of a layer that has its second forward output
-        plain_o2 = plain_o2 || (T.t[i].cu.c && !T.t[i].cu.out2);
-    }
-    if (!gs && plain_o2) return fail(FN_EINVAL, "input-gradient products: a task's dots need out2 / sigma (its layer is not deferred)");
-    if (gs && go) hipLaunchKernelGGL((k_lin_rd_cu<true, true>), dim3(blocks + R.nblk), dim3(kBlock), kLinSideLdsGs, st, T, R);
-    else if (gs) hipLaunchKernelGGL(k_lin_rd_cu<true>, dim3(blocks + R.nblk), dim3(kBlock), kLinSideLdsGs, st, T, R);
-    else hipLaunchKernelGGL(k_lin_rd_cu<false>, dim3(blocks + R.nblk), dim3(kBlock), kLinSideLds, st, T, R);
+    hipLaunchKernelGGL(k_lin_rd_cu, dim3(blocks + R.nblk), dim3(kBlock), kLinSideLds, st, T, R);
     return launch_status("input-gradient products (+ row dots) + edge-term backward");
 }
 
@@ -1689,7 +1499,6 @@ int encoder_backward_one(const fn_encoder* e, const EncLayout& lay, const BwdLay
     const bool no_fb = e->variant != 0;          // gat2_lite / gat2_edge: neither has a fragment-bond graph
     ReduceQueue rq;
     rq.st = hs;
-    rq.defer_wgrad = true;
     rq.defer_mixed = tune(FN_TUNE_GEMM_COLAUNCH) != 0;
     rq.rider = e->adam_rider;
     struct Parts { int n_a = 0, n_e = 0; };      // partial rows a level's pass wrote (attention vector / edge embedding)
@@ -1701,7 +1510,6 @@ int encoder_backward_one(const fn_encoder* e, const EncLayout& lay, const BwdLay
                                 sc.part_a, &n->n_a, sc.part_e, &n->n_e, H, A));
         A->p_edge_major = 1;
         A->n_real = v.n_real;
-        A->dz_em = sc.dz_em;                                // non-null (this level's layer is deferred, bwd_layout): dz at destination-order slots, no g_s_dst read
         return 0;
     };
     auto scratch = [&](const LevelView& v) -> const LevelScratch& { return bw.lv[v.layer][v.lv]; };
@@ -1716,10 +1524,6 @@ int encoder_backward_one(const fn_encoder* e, const EncLayout& lay, const BwdLay
         const LevelScratch& sc = scratch(v);
         return CuEpi{raw ? v.a.raw : nullptr, v.a.o2, v.a.sg, dots ? sc.cdot : nullptr, sc.g_s_dst, H};
     };
-    // deferred form, layer 0: g_s_dst and dL/da_dst of a level from its dz segments (k_gsd_seg), one block per block of the level's pass
-    auto seg_task = [&](const LevelView& v, const LevelScratch& sc, int n_a) {
-        return GsdSegTask{sc.dz_em, v.pl->rowptr_d, v.pl->pos_base_d, v.rows, sc.g_s_dst, v.n_real, v.a.h, sc.part_a, 0, n_a};
-    };
 
     // ---- the last layer's output gradients: gates, the fragment levels, the scatter to the atoms
     LastGrads top{};
@@ -1729,7 +1533,6 @@ int encoder_backward_one(const fn_encoder* e, const EncLayout& lay, const BwdLay
     CuTasks cu_now{};         // rows of the current layer whose dots no product epilogue wrote
     if (have_atoms && !top.tail_dots_atoms) cu_add(cu_now, level_view(e, lay, NL - 1, LV_ATOM));
 
-    GsdSegTasks seg0{};       // deferred form: layer 0's levels have no input-gradient product to form g_s_dst in: k_gsd_seg at the end
     bool pend_b = false, pend_fb = false;        // bond / fragment-bond level of layer l+1: gradient rows and dots ready, pass not launched
     for (int l = NL - 1; l >= 0; --l) {
         const bool last = l + 1 == NL;
@@ -1754,44 +1557,37 @@ int encoder_backward_one(const fn_encoder* e, const EncLayout& lay, const BwdLay
         LinTasks T{};
         CuTasks cu_after{};       // rows finished in L2 whose dots the epilogue could not write
         // dX of level v's projection: the gradient rows of the same level one layer down (`below`), gated by that layer's dropout mask and ReLU
-        auto product = [&](const LevelView& v, const LevelView& below, const RowAdd* ra, const CuEpi& cu, const GsdEpi& gs) {
+        auto product = [&](const LevelView& v, const LevelView& below, const RowAdd* ra, const CuEpi& cu) {
             LinTask& t = T.t[T.n++];
             t = LinTask{v.Wt, scratch(v).g_h, v.W, nullptr, bw.g_pre[v.lv], v.rows, act_epilogue(e, rng, below, below.a.y),
                         NodeScalarEpi{nullptr, nullptr, nullptr, 0, 0, 0, 0}, 0, 0};
             if (ra) t.ra = *ra;
             t.cu = cu;
-            t.gs = gs;
             t.n_real = v.n_real;
         };
         bool nxt_bond = false, nxt_fbond = false, nxt_atoms = false;
         const bool rd_rows_ride = have_atoms && pend_b && H == 4 && e->atom.m_real == e->E && e->E > 0;   // the bond product of layer l+1 carries the rows' term
         const int gr = have_atoms && e->atom.m_real > 0 ? row_grid(e->atom.m_real, tune(FN_TUNE_RD_BLOCKS) > 0 ? tune(FN_TUNE_RD_BLOCKS) : kRowDotsBwdBlocks) : 0;
         if (pend_b) {        // layer l+1's bond level: parameter work + dL/d(pre-activation bond output of layer l)
-            const DeferTerm df = defer_term(vb_up, scratch(vb_up));
-            FN_TRY(rq.level_params(vb_up, level_weights(grads[l + 1], LV_BOND), scratch(vb_up), ParamWork{nb.n_a, nb.n_e, true, &df, true, true}, hs));
+            FN_TRY(rq.level_params(vb_up, level_weights(grads[l + 1], LV_BOND), scratch(vb_up), ParamWork{nb.n_a, nb.n_e}, hs));
             const RowAdd ra{sa.dz, va.att + va.mid_off, va.att_w};
             // the rows are complete in this epilogue unless the edge term's rows' part is added behind the product (no RowAdd carrier)
             const bool complete = rd_rows_ride || gr == 0;
-            product(vb_up, vb, rd_rows_ride ? &ra : nullptr, cu_epi(vb, true, complete), df.gs);
+            product(vb_up, vb, rd_rows_ride ? &ra : nullptr, cu_epi(vb, true, complete));
             if (!complete) cu_add(cu_after, vb);
             nxt_bond = true;
         }
         if (pend_fb) {
-            const DeferTerm df = defer_term(vfb_up, scratch(vfb_up));
-            FN_TRY(rq.level_params(vfb_up, level_weights(grads[l + 1], LV_FBOND), scratch(vfb_up), ParamWork{nfb.n_a, nfb.n_e, true, &df, true, true}, hs));
+            FN_TRY(rq.level_params(vfb_up, level_weights(grads[l + 1], LV_FBOND), scratch(vfb_up), ParamWork{nfb.n_a, nfb.n_e}, hs));
             // (the fragment graph's edge term, the only reader of raw fragment-bond rows, exists in the last layer alone)
-            product(vfb_up, vfb, nullptr, cu_epi(vfb, false), df.gs);
+            product(vfb_up, vfb, nullptr, cu_epi(vfb, false));
             nxt_fbond = true;
         }
         RowDotsBwdArgs R{};
         if (have_atoms) {
-            const DeferTerm df = defer_term(va, sa);
-            // (layer 0 has no input-gradient product to form g_s_dst in: k_gsd_seg at the end of the pass, which also leaves dL/da_dst)
-            const bool seg_a = df.dz && l == 0 && na.n_a > 0;
-            if (seg_a) seg0.t[seg0.n++] = seg_task(va, sa, na.n_a);
-            FN_TRY(rq.level_params(va, ga, sa, ParamWork{na.n_a, 0, true, &df, df.dz && !seg_a, true}, hs));
+            FN_TRY(rq.level_params(va, ga, sa, ParamWork{na.n_a, 0}, hs));
             if (l) {
-                product(va, va_below, nullptr, cu_epi(va_below, false), df.gs);
+                product(va, va_below, nullptr, cu_epi(va_below, false));
                 nxt_atoms = true;
             }
             // the edge term <new_bond[e], a[:, d:d+128]> of the atom graph: parameter partials always; the rows' term (dL/dnew_bond)
@@ -1842,23 +1638,8 @@ int encoder_backward_one(const fn_encoder* e, const EncLayout& lay, const BwdLay
         FN_TRY(prof_event(2, hs));
         FN_TRY(launch_gat_bwd_one3(oB, GatBwdOneArgs{}, oFB, H, hs));
         FN_TRY(prof_event(3, hs));
-        const DeferTerm dfb = pend_b ? defer_term(vb, sb) : DeferTerm{}, dff = pend_fb ? defer_term(vfb, sfb) : DeferTerm{};
-        if (dfb.dz && nb.n_a > 0) seg0.t[seg0.n++] = seg_task(vb, sb, nb.n_a);
-        if (dff.dz && nfb.n_a > 0) seg0.t[seg0.n++] = seg_task(vfb, sfb, nfb.n_a);
-        if (seg0.n) {         // g_s_dst and dL/da_dst of layer 0's levels (the inner layers' come out of their products' epilogues and the
-            int blocks = 0;   // weight-gradient kernels' side product): one small launch, a block per block of the level's pass
-            for (int i = 0; i < seg0.n; ++i) {
-                // (any block count up to the pass's own: the pass left zeros in the rows of part_a this launch does not overwrite.  Fewer,
-                // longer blocks: every block ends with 128 scattered 4-byte stores into the column-major partials)
-                seg0.t[i].nblk = std::min(seg0.t[i].nblk, std::max(1, tune(FN_TUNE_SRC_BLOCKS)));
-                seg0.t[i].first = blocks;
-                blocks += seg0.t[i].nblk;
-            }
-            FN_TRY(launch_gsd_seg(seg0, blocks, hs));
-            FN_TRY(launch_status("one-pass backward, deferred form: g_s_dst of layer 0"));
-        }
-        if (pend_b) FN_TRY(rq.level_params(vb, level_weights(grads[0], LV_BOND), sb, ParamWork{nb.n_a, nb.n_e, true, &dfb}, hs));
-        if (pend_fb) FN_TRY(rq.level_params(vfb, level_weights(grads[0], LV_FBOND), sfb, ParamWork{nfb.n_a, nfb.n_e, true, &dff}, hs));
+        if (pend_b) FN_TRY(rq.level_params(vb, level_weights(grads[0], LV_BOND), sb, ParamWork{nb.n_a, nb.n_e}, hs));
+        if (pend_fb) FN_TRY(rq.level_params(vfb, level_weights(grads[0], LV_FBOND), sfb, ParamWork{nfb.n_a, nfb.n_e}, hs));
     }
     return rq.flush(true);
 }
@@ -1981,18 +1762,7 @@ static int encoder_forward_impl(const fn_encoder* e, const fn_row_masks* masks, 
         if (fuse_rd) {
             A.zp = lay.s_sorted;  A.zn = e->atom.m * H;  A.n_z = flat_grid(A.zn, 64);
         }
-        if (defer_on(e)) {        // R of every K = 128 projection (layers >= 1): slot 3 l + {0: bond, 1: atom, 2: fragment bond}
-            for (int l = 1; l < e->n_layers; ++l) {
-                if (!defer_on(e, l)) continue;
-                for (Level v : kProjected) {
-                    const LevelView lv = level_view(e, lay, l, v);
-                    A.rW[3 * l + v] = lv.W;  A.rA[3 * l + v] = lv.att;  A.rAw[3 * l + v] = lv.att_w;
-                }
-            }
-            A.rOut = lay.rmat;
-            A.n_r = 2 * 3 * e->n_layers;
-        }
-        hipLaunchKernelGGL(k_enc_prologue, dim3(A.n_t + A.n_d + A.n_s[0] + A.n_s[1] + A.n_ss[0] + A.n_ss[1] + A.n_z + A.n_x + A.n_r), dim3(256), 0, S(st), A);
+        hipLaunchKernelGGL(k_enc_prologue, dim3(A.n_t + A.n_d + A.n_s[0] + A.n_s[1] + A.n_ss[0] + A.n_ss[1] + A.n_z + A.n_x), dim3(256), 0, S(st), A);
         FN_TRY(launch_status("fn_encoder_forward: prologue"));
     }
 
@@ -2174,7 +1944,7 @@ int fn_encoder_backward(const fn_encoder* e, const float* out_atoms, const float
     if (!e->training && e->no_backward != 0)
         return fail(FN_EINVAL, "fn_encoder_backward: the forward pass of this descriptor saved nothing for a backward pass (fn_encoder.no_backward)");
     if (!form_matches_forward(e))
-        return fail(FN_EINVAL, "fn_encoder_backward: FN_TUNE_BWD_ONE / FN_TUNE_DEFER_GSD changed since the forward pass that wrote this workspace");
+        return fail(FN_EINVAL, "fn_encoder_backward: FN_TUNE_BWD_ONE changed since the forward pass that wrote this workspace");
     const EncLayout lay = enc_layout(e, e->ws);
     const BwdLayout bw = bwd_layout(e, scratch);
     if (bw.total > scratch_floats) return fail(FN_EINVAL, "fn_encoder_backward: scratch too small");
@@ -2185,8 +1955,8 @@ int fn_encoder_backward(const fn_encoder* e, const float* out_atoms, const float
     const int H = e->heads;
     hipStream_t hs = S(st);
     ReduceQueue rq;
-    rq.st = hs;                      // all parameter-gradient reductions run as one launch at the very end
-    rq.defer_wgrad = true;           // ... and so do the K = 128 weight-gradient partial products
+    rq.st = hs;                      // all parameter-gradient reductions run as one launch at the very end, and so do the K = 128
+                                     // weight-gradient partial products (ReduceQueue::wgrad)
     rq.defer_mixed = tune(FN_TUNE_GEMM_COLAUNCH) != 0;      // ... and layer 0's
     rq.rider = e->adam_rider;
 
@@ -2224,7 +1994,7 @@ int fn_encoder_backward(const fn_encoder* e, const float* out_atoms, const float
             // source pass + the edge term <new_bond, a[:, d:d+128]> (dL/dnew_bond accumulates into g_pre of the bonds, dL/da mid block)
             FN_TRY(bwd_src_and_edge_term(va, sa, bw.g_pre[LV_ATOM], sa.g_h, vb.a.raw, bw.g_pre[LV_BOND], have[LV_BOND], &n_a, &gr, hs));
             if (gr) have[LV_BOND] = true;
-            FN_TRY(rq.level_params(va, level_weights(g, LV_ATOM), sa, ParamWork{n_a, 0, false, nullptr, false, false, gr}, hs));
+            FN_TRY(rq.level_params(va, level_weights(g, LV_ATOM), sa, ParamWork{n_a, 0, gr}, hs));
             if (l) input_grad(va, sa);
         }
 
@@ -2267,9 +2037,7 @@ int fn_encoder_backward_inputs(const fn_encoder* e, const float* scratch, int64_
     if (!e->training && e->no_backward != 0)
         return fail(FN_EINVAL, "fn_encoder_backward_inputs: the forward pass of this descriptor saved nothing for a backward pass (fn_encoder.no_backward)");
     if (!form_matches_forward(e))
-        return fail(FN_EINVAL, "fn_encoder_backward_inputs: FN_TUNE_BWD_ONE / FN_TUNE_DEFER_GSD changed since the forward pass that wrote this workspace");
-    if (defer_on(e, 0))
-        return fail(FN_EUNSUPPORTED, "fn_encoder_backward_inputs: the deferred backward form of layer 0 (FN_TUNE_DEFER_GSD = 1) leaves the g_s_dst a_dst term out of the rows this call reads");
+        return fail(FN_EINVAL, "fn_encoder_backward_inputs: FN_TUNE_BWD_ONE changed since the forward pass that wrote this workspace");
     const BwdLayout bw = bwd_layout(e, const_cast<float*>(scratch));
     if (bw.total > scratch_floats) return fail(FN_EINVAL, "fn_encoder_backward_inputs: scratch too small");
     const fn_layer_weights& w0 = e->w[0];

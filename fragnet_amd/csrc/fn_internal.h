@@ -80,13 +80,6 @@ struct CuEpi {
     float *c, *u;             // c == null: no such epilogue
     int heads;
 };
-struct GsdEpi {
-    const float* dz;          // [m][4]; null: no such term
-    const int32_t* rowptr;    // the level's by-destination CSR (M + 1 words); positions are rowptr[.] - pos_base
-    int pos_base;
-    const float* R;           // [4][128], see above
-    float* gsd;               // out [M][4]
-};
 // up to three independent [M_i,K]·[K,128] products in one launch: the three projections of a layer (forward) or
 // their three input-gradient products (backward) depend only on the previous layer, never on each other
 struct LinTask {
@@ -100,7 +93,6 @@ struct LinTask {
     int K;                    // 0: the group's K (LinTasks::K); else this task's own reduction length (layer 0: 17 bond / 6 connection features)
     RowAdd ra;                // riding input-gradient products only (lin_side_block)
     CuEpi cu;                 // ... of the one-pass backward (lin_side_block<true>)
-    GsdEpi gs;                // ... of its deferred form (lin_side_block<true, true>)
     const int32_t* n_real;    // nullable device word: row tiles that start at or behind *n_real are padding and are not computed
 };
 struct LinTasks {
@@ -134,7 +126,7 @@ struct GatBwdOneArgs {
     const float* x_src;     // mode 2, nullable: the raw attribute [K][m] in SOURCE order (streamed) instead of gathers from et.x_sorted
     const int32_t* n_real;        // nullable device word: source rows >= *n_real are padding (zero gradient row out, nothing gathered)
     int tier6;                    // gather tiers 4 / 6 / 8 / 12 (1) or 4 / 8 / 12 (0)
-    float* dz_em;                 // deferred form (DF instances, below): dL/dz of every edge at its destination-order slot, EDGE-major [m][H]
+    float* dz_em;                 // operator-level deferred form (fn_gat_bwd_one_f32 only; the engine leaves it null): dL/dz of every edge at its destination-order slot, EDGE-major [m][H]
     unsigned long long* stamps;   // dev aid (fn_debug_set_stamps): 16 s_memtime values per wave -- entry, loop start, per row (loads issued,
                                   // data arrived, row done) x 4, loop end, exit; null in production (one uniform branch per stamp)
 };

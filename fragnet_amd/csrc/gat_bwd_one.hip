@@ -1,5 +1,5 @@
 // gat_bwd_one.hip -- the backward of an attention level as ONE source-owner pass (k_gat_bwd_one, k_gat_bwd_one3), the node-local dots
-// it needs where no GEMM epilogue forms them (k_gat_cu) and the segment sums of its deferred form (k_gsd_seg); their launchers and C
+// it needs where no GEMM epilogue forms them (k_gat_cu) and the segment sums of its operator-level deferred form (k_gsd_seg); their launchers and C
 // entry points.  A translation unit of its own since round 5: the twenty instantiations of the pass were a quarter of the main
 // unit's device code and of its compile time.
 #include "fn_internal.h"
@@ -75,7 +75,7 @@ int launch_gat_bwd_one(const GatBwdOneArgs& A, int heads, hipStream_t st) {
         with_edge_class(kl, [&](auto KL) { hipLaunchKernelGGL((k_gat_bwd_one<4, FN_CV(KL), kBwdRows, false, true>), dim3(A.nblk), dim3(kBwdRows * 32), 0, st, A); });
         return launch_status("fn_gat_bwd_one_f32");
     }
-    if (A.dz_em) {            // the deferred form (DF): four heads
+    if (A.dz_em) {            // the operator-level deferred form (DF): four heads; the engine never sets dz_em
         if (heads != 4) return fail(FN_EUNSUPPORTED, "one-pass backward, deferred form: four heads");
         with_edge_class(kl, [&](auto KL) { hipLaunchKernelGGL((k_gat_bwd_one<4, FN_CV(KL), kBwdRows, true>), dim3(A.nblk), dim3(kBwdRows * 32), 0, st, A); });
         return launch_status("fn_gat_bwd_one_f32 (deferred form)");
@@ -88,6 +88,7 @@ int launch_gat_bwd_one(const GatBwdOneArgs& A, int heads, hipStream_t st) {
 // bond (edge class 1) + atom (class 0) + fragment-bond (class FN_MAX_EDGE_K) levels as one launch; any of them may be absent
 // (nblk == 0).  Levels whose edge class does not fit their slot take launches of their own.
 int launch_gat_bwd_one3(const GatBwdOneArgs& A, const GatBwdOneArgs& B, const GatBwdOneArgs& C, int heads, hipStream_t st) {
+    if (A.dz_em || B.dz_em || C.dz_em) return fail(FN_EINVAL, "attention backward, one pass: the deferred form (dz_em) is single-level only");
     const bool okA = A.nblk == 0 || edge_class(&A.et) == 1, okB = B.nblk == 0 || edge_class(&B.et) == 0,
                okC = C.nblk == 0 || edge_class(&C.et) == FN_MAX_EDGE_K;
     const int live = (A.nblk > 0) + (B.nblk > 0) + (C.nblk > 0);
@@ -97,20 +98,8 @@ int launch_gat_bwd_one3(const GatBwdOneArgs& A, const GatBwdOneArgs& B, const Ga
         return launch_gat_bwd_one(C, heads, st);
     }
     const int interleave = tune(FN_TUNE_ONE_INTERLEAVE) != 0 ? 1 : 0;
-    const bool df = (A.nblk && A.dz_em) || (B.nblk && B.dz_em) || (C.nblk && C.dz_em);
-    if (df) {
-        // every level of the launch deferred, or -- the mixed form's boundary launch -- the bond / fragment-bond levels deferred and the
-        // atom level (the layer below's) not
-        const bool ac = !(A.nblk && !A.dz_em) && !(C.nblk && !C.dz_em);
-        if (heads != 4 || !ac) return fail(FN_EUNSUPPORTED, "one-pass backward, deferred form: four heads; the bond and fragment-bond levels of a launch share a form");
-        if (B.nblk && !B.dz_em)
-            hipLaunchKernelGGL((k_gat_bwd_one3<4, kBwdRows, true, false>), dim3(A.nblk + B.nblk + C.nblk), dim3(kBwdRows * 32), 0, st, A, B, C, interleave);
-        else
-            hipLaunchKernelGGL((k_gat_bwd_one3<4, kBwdRows, true>), dim3(A.nblk + B.nblk + C.nblk), dim3(kBwdRows * 32), 0, st, A, B, C, interleave);
-        return launch_status("attention backward, one pass, deferred form (bond + atom + fragment-bond levels)");
-    }
     if (heads == 4 && one_kind_en(A) && one_kind_en(B) && one_kind_en(C)) {      // the engine's launches (four heads)
-        hipLaunchKernelGGL((k_gat_bwd_one3<4, kBwdRows, false, false, true>), dim3(A.nblk + B.nblk + C.nblk), dim3(kBwdRows * 32), 0, st, A, B, C, interleave);
+        hipLaunchKernelGGL((k_gat_bwd_one3<4, kBwdRows, true>), dim3(A.nblk + B.nblk + C.nblk), dim3(kBwdRows * 32), 0, st, A, B, C, interleave);
         return launch_status("attention backward, one pass (bond + atom + fragment-bond levels)");
     }
     FN_TRY(with_heads(heads, [&](auto H) {

@@ -25,14 +25,13 @@ template <int NX> struct OneRaw {
 
 // source rows [blk0, se) interleaved over the block's RB half-waves; bid: the block's slot (row) in part_a / part_e
 //
-// DF ("deferred", round 5): the kernel does not read g_s_dst at all -- so the forward needs no second output (out2 / sigma) and
-// nobody computes <g, out2>.  It leaves the two terms that need it OUT of its results and writes dz at the edges' destination-order
-// slots instead (dz_em [m][H]: one 16-byte line per edge, a node's in-edges contiguous).  Whoever reads g_h next adds them:
-//   * g_s_dst[t] = sum over t's contiguous dz_em segment -- formed in the epilogue of the input-gradient product that reads g_h
-//     (linear128_body GS) or by k_gsd_seg (layer 0);
-//   * g_h[s] += g_s_dst[s] a_dst  is linear, so the product adds  g_s_dst[s] (a_dst W)  to its OUTPUT row (four FMAs per element),
-//     and the weight-gradient kernels add it to their dY operand as they read it (wgrad128.inc, wgrad_body);
-//   * dL/da_dst = sum_s g_s_dst[s] h[s] = W (G^T X) + b sum(G): from U = G^T X, a side product of the weight-gradient kernels.
+// DF ("deferred", round 5): an OPERATOR-level form (fn_gat_bwd_one_f32 with dz_em, four heads) that the engine does not use -- its
+// own deferred backward was retired (FN_TUNE_RETIRED_29); the single-level kernel keeps the flag because the benchmark times the
+// operator with it.  The kernel does not read g_s_dst at all -- so the forward needs no second output (out2 / sigma) and nobody
+// computes <g, out2>.  It leaves the two terms that need it OUT of its results and writes dz at the edges' destination-order slots
+// instead (dz_em [m][H]: one 16-byte line per edge, a node's in-edges contiguous).  The caller completes them: k_gsd_seg
+// (fn_gat_gsd_f32) forms g_s_dst[t] = the sum over t's contiguous dz_em segment and dL/da_dst = sum_t g_s_dst[t] h[t]; adding
+// g_s_dst[s] a_dst to g_h[s] is left to whoever reads g_h next.
 // EN (round 6): the ENGINE's launches -- probabilities edge-major, no stamp buffer, a level of at least two edges, the source-order
 // attribute copy at hand (single-attribute class), dz wanted in original edge order only (stored-term class) -- make those run-time
 // flags compile-time constants (one_kind_en() on the host checks exactly that): the tests of uniform flags inside the row loop were
@@ -355,9 +354,7 @@ __global__ __launch_bounds__(RB * 32, 3) void k_gat_bwd_one(GatBwdOneArgs A) {
 }
 // the three levels whose gradients are complete at the same point of the backward pass -- bond graph (single attribute), atom graph
 // (stored edge term), fragment-bond graph (K <= FN_MAX_EDGE_K attributes) -- in one launch; a level with nblk == 0 is absent
-// (DFB: the atom level's own form -- in the mixed form layer 0's atom level, which has its second forward output, shares a launch with
-// layer 1's deferred bond / fragment-bond levels)
-template <int H, int RB, bool DF = false, bool DFB = DF, bool EN = false>
+template <int H, int RB, bool EN = false>
 __global__ __launch_bounds__(RB * 32, 3) void k_gat_bwd_one3(GatBwdOneArgs A, GatBwdOneArgs B, GatBwdOneArgs C, int interleave) {
     __shared__ float sA[RB][2 * FN_D];
     __shared__ float sP[RB][8][kWfLd];
@@ -369,9 +366,9 @@ __global__ __launch_bounds__(RB * 32, 3) void k_gat_bwd_one3(GatBwdOneArgs A, Ga
     if (interleave && b < 2 * mn) { g = b & 1;  b >>= 1; }
     else if (interleave) { g = nX > nY ? 0 : 1;  b -= mn; }
     else { g = b < nX ? 0 : 1;  b -= g ? nX : 0; }
-    if (g == 0) gat_bwd_one_body<H, 1, RB, DF, EN>(A, sA, sP, b, A.nblk);
-    else if (b < B.nblk) gat_bwd_one_body<H, 0, RB, DFB, EN>(B, sA, sP, b, B.nblk);
-    else gat_bwd_one_body<H, FN_MAX_EDGE_K, RB, DF, EN>(C, sA, sP, b - B.nblk, C.nblk);
+    if (g == 0) gat_bwd_one_body<H, 1, RB, false, EN>(A, sA, sP, b, A.nblk);
+    else if (b < B.nblk) gat_bwd_one_body<H, 0, RB, false, EN>(B, sA, sP, b, B.nblk);
+    else gat_bwd_one_body<H, FN_MAX_EDGE_K, RB, false, EN>(C, sA, sP, b - B.nblk, C.nblk);
 }
 
 // c[t, h] = scale <g[t, h, :], out[t, h, :]>,  u[t, h] = <g[t, h, :], out2[t, h, :]> - c[t, h] sigma[t, h]: the two node-local
@@ -393,7 +390,7 @@ __global__ __launch_bounds__(kBlock) void k_gat_cu(CuTasks T) {
         const float4 g = ld4(t.g + r * FN_D + lane * 4);
         const float4 o = ld4(t.out + r * FN_D + lane * 4);
         const float c = t.scale * head_sum<LPH>(dot4(g, o));
-        if (t.out2) {        // (null: the deferred form of the one-pass backward -- only c is wanted)
+        if (t.out2) {        // (null: only c is wanted -- the operator-level deferred form, DF above)
             const float4 o2 = ld4(t.out2 + r * FN_D + lane * 4);
             const float sg = t.sigma[r * H + head];
             const float u = head_sum<LPH>(dot4(g, o2)) - c * sg;
@@ -403,10 +400,9 @@ __global__ __launch_bounds__(kBlock) void k_gat_cu(CuTasks T) {
     }
 }
 
-// g_s_dst[t, 0..4) = the sum of row t's contiguous dz_em segment, for levels whose deferred pass (DF above) is followed by no
-// input-gradient product that would form it in its epilogue (GsdEpi): layer 0, whose inputs are data.  Same lane mapping as that
-// epilogue: sixteen lanes per row, lane i adds the floats (beg + 4 j) * 4 + i, two row rotations add the four parts -- every lane
-// then holds the sum of head i & 3.  The same lanes also take the level's dL/da_dst = sum_t g_s_dst[t, h] h[t, head h's columns]
+// g_s_dst[t, 0..4) = the sum of row t's contiguous dz_em segment, behind a deferred pass (DF above; fn_gat_gsd_f32 -- operator level,
+// the engine does not launch it).  Sixteen lanes per row, lane i adds the floats (beg + 4 j) * 4 + i, two row rotations add the four
+// parts -- every lane then holds the sum of head i & 3.  The same lanes also take the level's dL/da_dst = sum_t g_s_dst[t, h] h[t, head h's columns]
 // (lane i: the eight columns 32 (i & 3) + 8 (i >> 2) .. of its row): the pass itself left zeros in those columns of part_a, this
 // kernel overwrites them -- one row of partial sums per block, as many blocks as the pass had (the deferred reduction adds n_a rows).
 using fni::GsdSegTask;

@@ -35,29 +35,13 @@ using fni::RowAdd;
 constexpr int kCuRows = 4;        // rows of a lane's four whose epilogue operands are in flight together (CuEpi): all four.  Two at a time
                                   // fit four waves per SIMD only with spills: the launch measured 43-45 us against 34-36
 using fni::CuEpi;
-// The deferred form of the one-pass attention backward inside an input-gradient product (GS instances, four heads; gat_bwd_one.inc,
-// DF).  The product's A rows are the level's g_h WITHOUT the term g_s_dst[row] a_dst, and g_s_dst itself is not known yet: the
-// level's pass left dL/dz of every edge at its destination-order slot (dz [m][4]: a row's in-edges contiguous, four heads per edge).
-// The missing term is linear, (g_s_dst a_dst) W = sum_h g_s_dst[row, h] R[h, :] with R[h, :] = sum_{c in head h} a_dst[c] W[c, :]
-// ([4][128], from the parameters alone: the forward prologue writes it) -- exactly ONE more step of the 16x16x4 MFMA chain with
-// k = the four heads: lane (i, kq) supplies A[row i][k = kq] = g_s_dst[row, head kq] and the R rows are four more rows of the
-// operand tile in LDS.  So every lane sums ONE segment (its row, head kq: <= 12 strided loads that leave before the chain and are
-// added behind it -- no cross-lane step at all), the tile's workgroup of column half 0 writes the g_s_dst table for the
-// weight-gradient kernels (which add the term to their dY operand, wgrad128.inc), and the epilogue is the plain one.
-using fni::GsdEpi;
-// GO (GS instances only): the MIXED form -- the rows this product finishes belong to a layer that still has its second forward output,
-// so the epilogue forms u = <g, out2> - c sigma as the plain CU instances do, for the tasks whose CuEpi carries out2 (run-time, per task)
-template <int KQ, bool VEC, bool PF, bool RA = false, bool CU = false, bool GS = false, bool GO = false>
+template <int KQ, bool VEC, bool PF, bool RA = false, bool CU = false>
 __device__ __forceinline__ void linear128_body(float* sBt, const float* __restrict__ X, int K, const float* __restrict__ Bt,
                                                const float* __restrict__ bias, float* __restrict__ Y, int64_t M,
                                                const fn_act_epilogue& mk, const NodeScalarEpi& ns, int bid, int nblk,
                                                const RowAdd& ra = RowAdd{nullptr, nullptr, 0},
                                                const CuEpi& cu = CuEpi{nullptr, nullptr, nullptr, nullptr, nullptr, 0},
-                                               const int32_t* n_real = nullptr,
-                                               const GsdEpi& gs = GsdEpi{nullptr, nullptr, 0, nullptr, nullptr}) {
-    static_assert(!GS || (CU && KQ == 32 && VEC), "the deferred term rides in the one-pass backward's K = 128 products");
-    static_assert(!GO || GS, "GO is a variant of the GS instances");
-    constexpr bool O2 = !GS || GO;                           // the epilogue reads out2 / sigma and writes u
+                                               const int32_t* n_real = nullptr) {
     // A block is 4 waves = 64 rows x 64 COLUMNS (column half wc = bid & 1) and walks the row tiles bid>>1, += nblk>>1.
     // sBt: the [4*KQ][kLinLd] operand tile of this column half, staged ONCE; after that the block never synchronises
     // again: A rows live in registers (PF: the next tile's rows are requested before this tile's MFMA chain), and
@@ -123,14 +107,6 @@ __device__ __forceinline__ void linear128_body(float* sBt, const float* __restri
         }
     };
 
-    // GS: the by-destination extent of this lane's A row of a tile, requested with the row itself so that the segment loads can
-    // leave right before the MFMA chain and land behind it
-    int rp0 = 0, rp1 = 0;
-    auto load_rp = [&](int64_t t) {
-        const int64_t ra_ = t * kLinRows + w * 16 + i;
-        rp0 = gs.dz ? gs.rowptr[ra_ < M ? ra_ : M] : 0;
-        rp1 = gs.dz ? gs.rowptr[ra_ + 1 < M ? ra_ + 1 : M] : 0;
-    };
     float cur[KQ], nxt[KQ];
     {   // stage Bt [4*KQ][this half's 64 columns] -> LDS with 16-byte loads; the first A rows ride in the same round trip
         constexpr int N4 = 4 * KQ * 16;                 // float4 count
@@ -142,17 +118,11 @@ __device__ __forceinline__ void linear128_body(float* sBt, const float* __restri
             v[q] = (idx < N4 && k < K) ? ld4(Bt + (size_t)k * 128 + 64 * wc + n4 * 4) : make_float4(0.f, 0.f, 0.f, 0.f);
         }
         load_rows(tile, cur);
-        float4 vr = make_float4(0.f, 0.f, 0.f, 0.f);
-        if constexpr (GS) {
-            load_rp(tile);
-            if (tid < 64 && gs.dz) vr = ld4(gs.R + (tid >> 4) * 128 + 64 * wc + (tid & 15) * 4);      // R: rows 4 KQ .. 4 KQ + 3 of the tile
-        }
 #pragma unroll
         for (int q = 0; q < PER; ++q) {
             const int idx = tid + q * kLinThreads, k = idx >> 4, n4 = idx & 15;
             if (idx < N4) st4(sBt + k * kLinLd + n4 * 4, v[q]);
         }
-        if constexpr (GS) { if (tid < 64) st4(sBt + (4 * KQ + (tid >> 4)) * kLinLd + (tid & 15) * 4, vr); }
     }
     // this lane's four columns of bias and of the two attention vectors stay in registers for every tile
     const int col = 64 * wc + 4 * i;
@@ -170,7 +140,6 @@ __device__ __forceinline__ void linear128_body(float* sBt, const float* __restri
         for (int hh = 0; hh < 4; ++hh) ra_a[hh] = ra.z ? ld4(ra.a + hh * ra.lda + col) : make_float4(0.f, 0.f, 0.f, 0.f);
     }
     __syncthreads();
-    const int64_t nr_rows = n_real ? (int64_t)*n_real : M;          // rows at or behind it: padding (no gradient, segments never written)
 
     // MFMA tile t of a wave covers the columns {4 i + t}: one 16-byte LDS read per step feeds all four tiles
     const float* bbase = sBt + (IL ? 4 * kq : kq * KQ) * kLinLd + 4 * i;
@@ -179,36 +148,6 @@ __device__ __forceinline__ void linear128_body(float* sBt, const float* __restri
         const int64_t next = tile + stride;
         const bool more = next < tiles;
         if constexpr (PF) load_rows(more ? next : tile, nxt);
-        // GS: the dz segment of (this lane's A row, head kq), in flight across the MFMA chain: four / eight / twelve loads by the
-        // wave's largest in-degree (wave-uniform tiers), rows of more in-edges finish behind the chain
-        float dzv[12], ahub = 0.f;
-        int gdeg = 0, gbeg = 0;
-        if constexpr (GS) {
-            const int64_t ra_ = tile * kLinRows + w * 16 + i;
-            gbeg = rp0 - gs.pos_base;
-            gdeg = (gs.dz && ra_ < nr_rows) ? rp1 - rp0 : 0;
-            const float* dzl = gs.dz + kq;
-#pragma unroll
-            for (int jj = 0; jj < 12; ++jj) dzv[jj] = 0.f;
-#pragma unroll
-            for (int jj = 0; jj < 4; ++jj) dzv[jj] = gs.dz ? ld1_off(dzl, jj < gdeg ? (uint32_t)(gbeg + jj) * 16u : 0u) : 0.f;
-            if (__any(gdeg > 4)) {
-#pragma unroll
-                for (int jj = 4; jj < 8; ++jj) dzv[jj] = ld1_off(dzl, jj < gdeg ? (uint32_t)(gbeg + jj) * 16u : 0u);
-            }
-            if (__any(gdeg > 8)) {
-#pragma unroll
-                for (int jj = 8; jj < 12; ++jj) dzv[jj] = ld1_off(dzl, jj < gdeg ? (uint32_t)(gbeg + jj) * 16u : 0u);
-            }
-            // hubs (in-degree > 12): rare; their tail is summed HERE, in front of the chain (dependent loads, a stall only for such a
-            // wave) -- the same loop between the chain and the last step made the register allocator spill 145 registers
-            if (__any(gdeg > 12)) {
-                for (int jj = 12; __any(jj < gdeg); ++jj) {
-                    const float x = ld1_off(dzl, jj < gdeg ? (uint32_t)(gbeg + jj) * 16u : 0u);
-                    ahub += jj < gdeg ? x : 0.f;
-                }
-            }
-        }
         __builtin_amdgcn_sched_barrier(0);
         f32x4 acc[4];
 #pragma unroll
@@ -239,19 +178,6 @@ __device__ __forceinline__ void linear128_body(float* sBt, const float* __restri
                 }
             }
         }
-        if constexpr (GS) {      // step 4 KQ / 4 + 1 of the chain: k = the four heads
-            float a = 0.f;
-#pragma unroll
-            for (int jj = 0; jj < 12; ++jj) a += jj < gdeg ? dzv[jj] : 0.f;
-            a += ahub;
-            const int64_t ra_ = tile * kLinRows + w * 16 + i;
-            if (wc == 0 && gs.dz && ra_ < M) gs.gsd[ra_ * 4 + kq] = a;
-            const float4 b = *reinterpret_cast<const float4*>(sBt + (4 * KQ + kq) * kLinLd + 4 * i);
-            acc[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, b.x, acc[0], 0, 0, 0);
-            acc[1] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, b.y, acc[1], 0, 0, 0);
-            acc[2] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, b.z, acc[2], 0, 0, 0);
-            acc[3] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, b.w, acc[3], 0, 0, 0);
-        }
         // acc[t][r] is (row kq*4 + r, column 4 i + t) of the wave's 16 x 64 tile
         __builtin_amdgcn_sched_barrier(0);
         const int64_t r0 = tile * kLinRows + w * 16 + kq * 4;
@@ -279,9 +205,9 @@ __device__ __forceinline__ void linear128_body(float* sBt, const float* __restri
                     const int64_t at = row * 128 + col;
                     yv[q] = gate ? ld4(mk.y + at) : make_float4(1.f, 1.f, 1.f, 1.f);
                     ov[q] = cu.c && cu.out ? ld4(cu.out + at) : make_float4(0.f, 0.f, 0.f, 0.f);
-                    if constexpr (O2) o2v[q] = cu.c && cu.out2 ? ld4(cu.out2 + at) : make_float4(0.f, 0.f, 0.f, 0.f);
+                    o2v[q] = cu.c && cu.out2 ? ld4(cu.out2 + at) : make_float4(0.f, 0.f, 0.f, 0.f);
                     zv[q] = ra.z ? ld4(ra.z + row * 4) : make_float4(0.f, 0.f, 0.f, 0.f);
-                    if constexpr (O2) sgv[r] = cu.c && cu.out2 ? cu.sigma[row * cu.heads + cu_hd] : 0.f;
+                    sgv[r] = cu.c && cu.out2 ? cu.sigma[row * cu.heads + cu_hd] : 0.f;
                 }
 #pragma unroll
                 for (int q = 0; q < CR; ++q) {
@@ -294,7 +220,7 @@ __device__ __forceinline__ void linear128_body(float* sBt, const float* __restri
                     fma4(o, zv[q].x, ra_a[0]);  fma4(o, zv[q].y, ra_a[1]);  fma4(o, zv[q].z, ra_a[2]);  fma4(o, zv[q].w, ra_a[3]);
                     if (r0 + r < M) st4(Y + (r0 + r) * 128 + col, o);
                     pd[r] = dot4(o, cu.out ? ov[q] : yv[q]);
-                    if constexpr (O2) ps[r] = dot4(o, o2v[q]);
+                    ps[r] = dot4(o, o2v[q]);
                 }
                 __builtin_amdgcn_sched_barrier(0);
             }
@@ -307,16 +233,14 @@ __device__ __forceinline__ void linear128_body(float* sBt, const float* __restri
                     if (cu_d >= 32) pd[r] += dpp_mov<kDppHalfMirror>(pd[r]);
                     pd[r] += dpp_mov<kDppXor2>(pd[r]);
                     pd[r] += dpp_mov<kDppXor1>(pd[r]);
-                    if constexpr (O2) {
-                        if (cu_d >= 64) ps[r] += dpp_mov<kDppMirror>(ps[r]);
-                        if (cu_d >= 32) ps[r] += dpp_mov<kDppHalfMirror>(ps[r]);
-                        ps[r] += dpp_mov<kDppXor2>(ps[r]);
-                        ps[r] += dpp_mov<kDppXor1>(ps[r]);
-                    }
+                    if (cu_d >= 64) ps[r] += dpp_mov<kDppMirror>(ps[r]);
+                    if (cu_d >= 32) ps[r] += dpp_mov<kDppHalfMirror>(ps[r]);
+                    ps[r] += dpp_mov<kDppXor2>(ps[r]);
+                    ps[r] += dpp_mov<kDppXor1>(ps[r]);
                     if ((4 * i) % cu_d == 0 && r0 + r < M) {
                         const float cc = cu_scale * pd[r];
                         cu.c[(r0 + r) * cu.heads + cu_hd] = cc;
-                        if constexpr (O2) { if (!GS || cu.out2) cu.u[(r0 + r) * cu.heads + cu_hd] = ps[r] - cc * sgv[r]; }
+                        cu.u[(r0 + r) * cu.heads + cu_hd] = ps[r] - cc * sgv[r];
                     }
                 }
             }
@@ -374,7 +298,6 @@ __device__ __forceinline__ void linear128_body(float* sBt, const float* __restri
         } else {
             load_rows(next, cur);
         }
-        if constexpr (GS) load_rp(next);
         tile = next;
     }
 }
@@ -390,12 +313,12 @@ using fni::LinTasks;
 // The attention passes are bound by dependent round trips with the matrix cores idle, the projections are a few microseconds
 // of MFMA work behind a launch floor of their own -- so the GEMM tiles ride along as extra workgroups of the attention launch
 // (one 64 x 64 tile each, the k_linear128_multi body) and the layer loses a kernel boundary per pass.
-template <bool CU = false, bool GS = false, bool GO = false>
+template <bool CU = false>
 __device__ __forceinline__ void lin_side_block(float* sBt, const LinTasks& T, int b) {
     int ti = 0;
     while (ti + 1 < T.n && b >= T.t[ti + 1].first) ++ti;
     const LinTask& t = T.t[ti];
-    linear128_body<32, true, false, true, CU, GS, GO>(sBt, t.X, 128, t.Bt, t.bias, t.Y, t.M, t.mk, t.ns, b - t.first, t.nblk, t.ra, t.cu, t.n_real, t.gs);
+    linear128_body<32, true, false, true, CU>(sBt, t.X, 128, t.Bt, t.bias, t.Y, t.M, t.mk, t.ns, b - t.first, t.nblk, t.ra, t.cu, t.n_real);
 }
 // Which workgroup is which: the GEMM workgroups are blocks [T.base, T.base + T.total) of the launch -- first, so that the
 // dispatcher starts them before the attention workgroups (measured best of first / last / interleaved: profiles/r02e_colaunch_ab.txt).
@@ -409,5 +332,4 @@ __device__ __forceinline__ bool lin_side_role(const LinTasks& T, int gat_base, i
 
 // dynamic LDS of a launch that carries side blocks: the [128][64] operand tile of one column half
 constexpr size_t kLinSideLds = (size_t)(4 * 32 * kLinLd) * sizeof(float);
-constexpr size_t kLinSideLdsGs = kLinSideLds + 4 * kLinLd * sizeof(float);    // + four operand rows: R of the deferred term (GsdEpi)
 static_assert(kLinSideLds <= 64 * 1024, "the co-launched GEMM tile fits the default dynamic LDS limit");

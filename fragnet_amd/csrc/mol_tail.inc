@@ -304,7 +304,7 @@ __device__ __forceinline__ void row_cu_dots(float4 g, float4 o, float4 o2, float
     if (lane % LPH == 0) {
         const int64_t at = row * H + lane / LPH;
         c[at] = cc;
-        if (u) u[at] = uu - cc * sg;       // (u == null: the deferred one-pass backward wants c only; o2 / sg are zeros then)
+        if (u) u[at] = uu - cc * sg;       // (u == null: only c is wanted; o2 / sg are zeros then)
     }
 }
 

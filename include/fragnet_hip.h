@@ -110,15 +110,14 @@ int fn_abi_version(void);
 #define FN_TUNE_RIDER_AT 28           /* which launch of the one-pass encoder backward carries fn_encoder.adam_rider: 0 (default) the last one (the
                                        * deferred reductions: + 7 us there for the 12.9 - 4.5 us the step's Adam launch saves), 1 the first one (the
                                        * molecule-resident fragment tail, when it runs: + 11.7 us) */
-#define FN_TUNE_DEFER_GSD 29           /* 1: with the one-pass backward and four heads (gat2) the forward writes NO second output (out2 / sigma): the
-                                       * pass leaves dz at the edges' destination-order slots and the terms that need g_s_dst = the sum of a row's
-                                       * segment are added by whoever reads g_h next -- the input-gradient product (one more MFMA step, k = the four
-                                       * heads), the weight-gradient kernels (the block's partial; side product U = G^T X for dL/da_dst), one small
-                                       * launch for layer 0.  0 (default): out2 / sigma in the forward, <g, out2> in the producers' epilogues.
-                                       * Measured at ESOL batch 512 (round 5, same call): the forward launches 18 us shorter, the backward 32 us
-                                       * longer (weight-gradient launch + 21, layer 0's launch + 12): 0.797 against 0.783 ms per step.
-                                       * 2 (round 6): the MIXED form -- layers >= 1 deferred, layer 0 keeps out2 / sigma (no k_gsd_seg, layer 0's
-                                       * weight-gradient kernels plain); the two boundary launches carry both epilogues */
+#define FN_TUNE_RETIRED_29 29          /* (retired, no effect: the DEFERRED forms of the engine's one-pass backward, four heads.  1: the forward wrote no
+                                       * out2 / sigma, the pass left dz at the edges' destination-order slots and the consumers of g_h added the
+                                       * g_s_dst a_dst term -- one more MFMA step in the input-gradient products, the weight-gradient kernels' side
+                                       * product U = G^T X for dL/da_dst, k_gsd_seg for layer 0; 2: the mixed form, layers >= 1 deferred and layer 0
+                                       * plain.  Both measured slower than the default at ESOL batch 512: 0.797 against 0.783 ms per step for the
+                                       * all-layer form (round 5), 0.782 against 0.764 ms for the mixed form (round 6,
+                                       * profiles/r06_mixed_deferred_form_ab.txt).  Last commit that contains it: 38e95ae.  The stand-alone operator
+                                       * keeps its deferred form: fn_gat_bwd_one_f32 with dz_em, fn_gat_gsd_f32) */
 #define FN_TUNE_FWD_BLOCKS_EVAL_LARGE 30 /* the plain forward (inference) of a level with more than 4 x FN_TUNE_FWD_BLOCKS_EVAL row groups (2048+ molecules
                                        * per batch) runs this many workgroups instead (default 6144): with the fixed count every half-wave walked 12-46
                                        * rows and the launch waited for its slowest workgroups.  0: one count for every size (rounds 1-4) */
@@ -339,13 +338,12 @@ int fn_gat_bwd_one_f32(const float* g_out, const float* h, const float* p_sorted
                        float neg_slope, float* g_h, float* dz_sorted, float* g_s_orig, float* part_a, int* n_part_a,
                        float* part_e, int* n_part_e, int p_edge_major /*layout of p_sorted, as fn_gat_fwd_f32 wrote it*/,
                        float* dz_em /*nullable; non-null (four heads): the DEFERRED form, see below*/, int heads, fn_stream_t stream);
-/* The deferred form (ABI 11; what fn_encoder_backward runs for four heads when FN_TUNE_DEFER_GSD is set -- it is OFF by default): g_s_dst is not read and the forward
- * needs no out2 / sigma.  The pass writes dz of every edge at its destination-order slot, dz_em [m,4] edge-major, and leaves the two
- * terms that need g_s_dst[t,h] = the sum of row t's contiguous dz_em segment OUT of its results: g_h lacks g_s_dst[s] a_dst, and the
- * a_dst columns of part_a are zero.  fn_gat_gsd_f32 forms g_s_dst [n,4] from dz_em and overwrites those columns of part_a (rows
- * 0 .. n_part_a-1) with the partials of dL/da_dst = sum_t g_s_dst[t,h] h[t, head h's columns]; the caller adds g_s_dst[s] a_dst to
- * g_h (inside the engine the consumers of g_h do: the input-gradient product as one more MFMA step, the weight-gradient kernels
- * on their dY operand). */
+/* The deferred form (ABI 11): an OPERATOR-level form -- the engine (fn_encoder_backward) does not use it, its own deferred backward was
+ * retired (FN_TUNE_RETIRED_29).  g_s_dst is not read and the forward needs no out2 / sigma.  The pass writes dz of every edge at its
+ * destination-order slot, dz_em [m,4] edge-major, and leaves the two terms that need g_s_dst[t,h] = the sum of row t's contiguous
+ * dz_em segment OUT of its results: g_h lacks g_s_dst[s] a_dst, and the a_dst columns of part_a are zero.  fn_gat_gsd_f32 forms
+ * g_s_dst [n,4] from dz_em and overwrites those columns of part_a (rows 0 .. n_part_a-1) with the partials of dL/da_dst =
+ * sum_t g_s_dst[t,h] h[t, head h's columns]; the caller adds g_s_dst[s] a_dst to g_h. */
 int fn_gat_gsd_f32(const float* dz_em, const fn_gat_plan* plan, const float* h, float* g_s_dst, float* part_a, int n_part_a,
                    fn_stream_t stream);
 /* c[t,h] = scale <g_out[t,h,:], out[t,h,:]>, u[t,h] = <g_out[t,h,:], out2[t,h,:]> - c[t,h] sigma[t,h] for n rows.  `out` may be the
@@ -914,9 +912,8 @@ int fn_encoder_backward(const fn_encoder* e, const float* out_atoms, const float
  * hands fn_encoder_backward a zero-filled scratch, and reads zeros here.
  * Refused before anything is launched: variant 2, gat2_edge (FN_EUNSUPPORTED); fragment-bond outputs with variant 1, gat2_lite, which has
  * no fragment-bond level (FN_EINVAL); a training pass with drop_p > 0 (FN_EUNSUPPORTED: the input dropout's gate on x_atoms, gat2.py:396,
- * would have to be replayed); a descriptor whose evaluation forward ran with no_backward (FN_EINVAL); the deferred backward form of layer 0
- * (FN_TUNE_DEFER_GSD = 1: its rows lack the g_s_dst a_dst term, FN_EUNSUPPORTED -- the mixed form, 2, keeps layer 0 complete and is
- * served); FN_TUNE_BWD_ONE / FN_TUNE_DEFER_GSD changed since the forward (FN_EINVAL).  Added under ABI 12. */
+ * would have to be replayed); a descriptor whose evaluation forward ran with no_backward (FN_EINVAL); FN_TUNE_BWD_ONE
+ * changed since the forward (FN_EINVAL).  Added under ABI 12. */
 typedef struct fn_input_grads {
     float *dx_atoms /*[N,k_atom0]*/, *dx_bonds /*[E,k_bond0]*/, *dx_fbonds /*[EF,k_fbond0]*/;
     const float *delta_atoms, *delta_bonds, *delta_fbonds;     /* same shapes */

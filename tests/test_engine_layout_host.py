@@ -14,7 +14,7 @@ import sys
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "engine_ws_sizes.json")
 
 # key -> (value under test, default to restore); "default" runs the table as the library starts with it
-TUNINGS = {"default": None, "22=0": (22, 0, 1), "29=1": (29, 1, 0), "29=2": (29, 2, 0), "24=0": (24, 0, 1)}
+TUNINGS = {"default": None, "22=0": (22, 0, 1), "24=0": (24, 0, 1)}
 N, E, F, EF, N_MOLS = 37, 78, 11, 20, 5          # odd on purpose: no count is a multiple of the 64-float granule
 
 

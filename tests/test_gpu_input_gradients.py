@@ -25,7 +25,6 @@ from tests.conftest import GOLDEN
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
-FN_TUNE_DEFER_GSD = 29
 
 
 @pytest.fixture(scope="module", autouse=True)
@@ -244,31 +243,7 @@ def test_linear128_input_gradient_ragged_k(M, K):
     ic.assert_within(w.grad.cpu().numpy(), w2.grad.numpy(), f"linear128 weight gradient K={K}")
 
 
-# =============================================================================== 7. the deferred backward forms
-@pytest.mark.parametrize("value", [1, 2])
-def test_deferred_forms(value):
-    """FN_TUNE_DEFER_GSD applies to training passes (the one-pass backward).  1: every layer deferred -- layer 0's rows lack the
-    g_s_dst a_dst term, the library refuses with its message.  2, the mixed form: layer 0 keeps its second forward output, its rows are
-    complete, the gradients are the golden's."""
-    from fragnet_amd import _lib
-    z = _z("input_grad_b6")
-    _lib.call("fn_set_tuning", FN_TUNE_DEFER_GSD, value)
-    try:
-        net = _model(train=True)
-        if value == 1:
-            with pytest.raises(_lib.FragnetHipError, match="deferred backward form of layer 0"):
-                _grads(net, _batch())
-        else:
-            logits, grads, _ = _grads(net, _batch())
-            _plain(logits, z["logits"], "logits (mixed deferred form)")
-            for key, g in zip(ic.TABLE_KEYS, grads):
-                ic.assert_within(g.cpu().numpy(), z[f"grad/{key}"], f"d out / d {key} (FN_TUNE_DEFER_GSD = 2)")
-    finally:
-        _lib.call("fn_set_tuning", FN_TUNE_DEFER_GSD, 0)
-        torch.cuda.synchronize()
-
-
-# =============================================================================== 8. the attributions against ig_b6.npz
+# =============================================================================== 7. the attributions against ig_b6.npz
 def _flat(z, kind):
     return np.concatenate([z[f"m{i}/{kind}"] for i in range(6)])
 
@@ -363,7 +338,7 @@ def test_integrated_gradients_baseline_vectors(ig_run):
         ga.integrated_gradients(_model(), ic.molecules(), steps=2, target=1)
 
 
-# =============================================================================== 9. refusals
+# =============================================================================== 8. refusals
 def test_training_pass_with_dropout_is_refused_and_without_it_works():
     z = _z("input_grad_b6")
     net = _model(train=True, drop=0.1)

@@ -12,14 +12,13 @@ cp $O/bench_full_kernel_trace_summary.md $P/${TAG}_bench_full_kernel_trace_summa
 cp $O/kernel_trace_summary.md $P/${TAG}_kernel_trace_summary.md
 cp $O/step_sequence.txt $P/${TAG}_step_sequence.txt
 cp $O/step_sequence_shard_of_8.txt $P/${TAG}_step_sequence_shard_of_8.txt
-cp $O/step_sequence_deferred_form.txt $P/${TAG}_step_sequence_deferred_form.txt
 cp $O/in_graph_kernels.json $P/in_graph_kernels.json
 cp $O/pmc_per_launch.json $P/pmc_per_launch.json
 cp $O/pmc_step.json $P/${TAG}_pmc_step.json
 cp $O/pmc_sq_ta_step.json $P/${TAG}_pmc_sq_ta_step.json
 python3 $R/tools/pmc_sq_ta_md.py $P/${TAG}_pmc_sq_ta_step.json $TAG > $P/${TAG}_pmc_sq_ta_step.md
 cp $O/hbm_cold_stream_table.md $P/${TAG}_hbm_cold_stream.md
-for f in bench_two_pass bench_deferred_form bench_no_riders bench_spawn_1rank bench_2ranks_gloo_one_gpu forward_sweep store_sweep strong_shards variants; do cp $O/$f.json $P/${TAG}_$f.json; done
+for f in bench_two_pass bench_no_riders bench_spawn_1rank bench_2ranks_gloo_one_gpu forward_sweep store_sweep strong_shards variants; do cp $O/$f.json $P/${TAG}_$f.json; done
 cp $O/pretrain_step_sequence.txt $P/${TAG}_pretrain_step_sequence.txt
 cp $O/pretrain_kernel_trace_summary.md $P/${TAG}_pretrain_kernel_trace_summary.md
 { echo "# tools/tox21_bench.py"; grep -v amdgpu.ids $O/tox21.txt; echo; echo "# tools/pretrain_bench.py"; grep -v amdgpu.ids $O/pretrain.txt; echo

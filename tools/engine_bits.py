@@ -26,7 +26,7 @@ from fragnet_amd import viz_model as V
 
 DEV = "cuda:0"
 OFFSET = 999
-DEFAULTS = {7: 1, 14: 2, 20: 1, 22: 1, 28: 0, 29: 0, 33: 1}
+DEFAULTS = {7: 1, 14: 2, 20: 1, 22: 1, 28: 0, 33: 1}
 
 
 def digest(items):
@@ -150,11 +150,11 @@ def main():
     encoder_pass("single_fragment_train", net_for(), single_fragment_batch(6, False))
     encoder_pass("single_molecule_train", net_for(drop=0.1), data.batch_to(data.collate_fn(mols[:1]), DEV))
 
-    for key, value in ((22, 0), (29, 1), (29, 2), (14, 0), (7, 0), (20, 0), (20, 2), (33, 0)):
+    for key, value in ((22, 0), (14, 0), (7, 0), (20, 0), (20, 2), (33, 0)):
         try:
             _lib.call("fn_set_tuning", key, value)
             encoder_pass(f"train_key{key}={value}", net_for(drop=0.1), batch)
-            if key in (22, 29):
+            if key == 22:
                 encoder_pass(f"train_6layers_key{key}={value}", net_for(layers=6, drop=0.1), batch)
         finally:
             _lib.call("fn_set_tuning", key, DEFAULTS[key])
