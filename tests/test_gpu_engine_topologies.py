@@ -1,0 +1,367 @@
+"""The encoder engine (fn_encoder_forward / fn_encoder_backward) on hand-built molecule topologies that sit ON the boundaries of its
+kernels' classes (tests/topologies.py), against the oracle.
+
+synth.synth_molecules gives rows of at most 5 in-edges (12 on the bond graph) and molecules of a handful of fragments; inside the engine
+the serial walk of the attention kernels, the gather tiers above 8 and the per-molecule choice between the fused tail's LDS path and its
+global-memory path are otherwise never taken.  Two batches:
+
+  "edges"  51 molecules the one-launch plan builder takes (asserted): stars of 3 .. 18 leaves, uncut and cut at every bond, with ordinary
+           molecules between them; cut chains of 12 / 24 / 25 / 32 / 33 fragments; the two-atom molecules
+  "wide"   35 molecules that need the general plan builder (asserted): stars of 31 .. 34 and 63 .. 65 leaves, and the component molecules
+           of 128 / 130 / 156 fragment-graph edges -- each of those has more than 4000 fragment-bond-graph edges, which alone overflows
+           the one-launch builder's tile, so they cannot sit in "edges"
+
+  row length at a level          kernel branch                                             carried by
+  4|5, 6|7, 8|9, 12|13           gather tiers wide / tier6 / wide8 / wide2                  star(3 .. 13), cut stars (fragment levels)
+  2 (32 / heads) | + 1           fast path's end -> serial walk: 8|9 (8 heads), 16|17 (4)   star(7, 8), star(15, 16), cut star(16, 17)
+                                 32|33 (2), 64|65 (1)                                       "wide": star(31, 32), star(63, 64) + cut stars
+  bond graphs (even rows only)   16|18, 32|34, 64|66                                        star(9, 10), star(17, 18), "wide" star(33, 34)
+  24|25 fragments                tail backward LDS | global at 1 / 2 / 4 heads              chain(24), chain(25)
+  32|33 fragments                tail forward LDS | global (and backward at 8 heads)        chain(32), chain(33); "wide" cut star(31, 32)
+  128|130 fragment-graph edges   tail forward and backward LDS | global                     "wide" components([1, 5, 8]), ([3, 16]), ([8, 8])
+
+Every test first checks, from the records and from the built plan's row pointers, that its batch holds those rows and classes.
+Tolerances: the suite's 1e-4 + 1e-4 |ref| against the float32 oracle (tests/test_topologies_host.py asserts that the oracle itself is a
+hundred times closer to float64 on these batches); the key comparisons use tests/test_gpu_tuning_keys.py's."""
+import pytest
+import torch
+
+from tests import topologies as T
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda:0"
+ATOL = 1e-4
+KEY_DEFAULTS = {14: 2, 20: 1, 22: 1, 26: 1, 33: 1}
+
+
+@pytest.fixture(scope="module", autouse=True)
+def _need_gpu():
+    if not torch.cuda.is_available():
+        pytest.skip("needs an MI355X")
+
+
+_CACHE = {}
+
+
+def _records(name, pretrain=False):
+    key = ("recs", name, pretrain)
+    if key not in _CACHE:
+        _CACHE[key] = T.BATCHES[name](pretrain_targets=pretrain)
+    return _CACHE[key]
+
+
+def _cpu_batch(name, pretrain=False):
+    key = ("cpu", name, pretrain)
+    if key not in _CACHE:
+        _CACHE[key] = T.collate(_records(name, pretrain), pretrain)
+    return _CACHE[key]
+
+
+def _dev_batch(name, pretrain=False):
+    """A fresh device copy (tests pop the cached plan, set requires_grad, ...)."""
+    from fragnet_amd import data
+    return data.batch_to(_cpu_batch(name, pretrain), DEV)
+
+
+def _oracle(name, heads):
+    """(float32 oracle model, logits, gradients) of one training step on the batch: computed once, read by every test."""
+    key = ("oracle", name, heads)
+    if key not in _CACHE:
+        gold, res = T.oracle_finetune(_cpu_batch(name), heads)
+        _CACHE[key] = (gold, res["f32"][0], res["f32"][1])
+    return _CACHE[key]
+
+
+def _check_batch(name, heads, plan, pretrain=False, padded=False):
+    """The preconditions: the records hold the rows and molecule classes the test is about, and so does the plan the kernels walk."""
+    T.assert_batch_claims(name, _records(name, pretrain), heads)
+    assert plan.mol_built == (name == "edges"), f"{name}: plan built by the {'one-launch' if plan.mol_built else 'general'} builder"
+    assert plan.mol_contiguous
+    got = T.plan_row_lengths(plan)
+    for lv, want in T.required_rows(name, heads).items():
+        assert want <= got[lv], f"{name}, {heads} heads: the plan's {lv} level has no row of {sorted(want - got[lv])} edges"
+    if not padded:
+        ins, _ = T.row_lengths(_records(name, pretrain))
+        assert {lv: max(v) for lv, v in got.items()} == {lv: max(v) for lv, v in ins.items()}
+
+
+def _set(key, value):
+    from fragnet_amd import _lib
+    _lib.call("fn_set_tuning", key, value)
+
+
+def _model(heads, drop=0.0, state=None, seed=3):
+    from fragnet_amd.model import FragNetFineTune
+    torch.manual_seed(seed)
+    net = FragNetFineTune(**dict(T.CFG, drop_ratio=drop), num_heads=heads, fthead="FTHead3")
+    if state is not None:
+        net.load_state_dict(state)
+    return net.to(DEV).train()
+
+
+def _compare_grads(model, want, atol=ATOL, rtol=1e-4):
+    checked = 0
+    for n, p in model.named_parameters():
+        if n in want:
+            assert p.grad is not None, f"{n}: missing gradient"
+            print(f"{n}: max|diff| = {float((p.grad.cpu() - want[n]).abs().max()):.3e}, max|ref| = {float(want[n].abs().max()):.3e}")
+            torch.testing.assert_close(p.grad.cpu(), want[n], atol=atol, rtol=rtol, msg=lambda m, n=n: f"{n}: {m}")
+            checked += 1
+    assert checked == len(want) and checked >= 30
+
+
+# ----------------------------------------------------------------------------------------------- a. training step against the oracle
+@pytest.mark.parametrize("one_pass", [1, 0], ids=["one_pass_bwd", "two_pass_bwd"])
+@pytest.mark.parametrize("heads", [1, 2, 4, 8])
+@pytest.mark.parametrize("name", ["edges", "wide"])
+def test_training_step_matches_the_oracle(name, heads, one_pass):
+    """Logits and every parameter gradient of FragNetFineTune (2 layers, no dropout) with the one-pass backward (key 22 = 1) and with
+    the destination + source passes (0)."""
+    gold, want, want_g = _oracle(name, heads)
+    model = _model(heads, state=gold.state_dict())
+    b = _dev_batch(name)
+    try:
+        _set(22, one_pass)
+        got = model(b)
+        torch.nn.functional.mse_loss(got.view(-1), b["y"]).backward()
+        torch.cuda.synchronize()
+    finally:
+        _set(22, 1)
+    b["_fragnet_plan"].check()
+    _check_batch(name, heads, b["_fragnet_plan"])
+    print(f"logits: max|diff| = {float((got.detach().cpu() - want).abs().max()):.3e}")
+    torch.testing.assert_close(got.detach().cpu(), want, atol=ATOL, rtol=1e-4)
+    _compare_grads(model, want_g)
+
+
+# ----------------------------------------------------------------------------------------------- b. the pretrain model
+@pytest.mark.parametrize("one_pass", [1, 0], ids=["one_pass_bwd", "two_pass_bwd"])
+@pytest.mark.parametrize("name", ["edges", "wide"])
+def test_pretrain_step_matches_the_oracle(name, one_pass):
+    """FragNetPreTrain, four heads: all four head outputs and every gradient.  The bond rows and dL/d(out_atoms) enter the tail's
+    backward here."""
+    from fragnet_amd.model import FragNetPreTrain
+    from oracle import fragnet_ref as ref
+    heads = 4
+    key = ("oracle_pt", name)
+    if key not in _CACHE:
+        torch.manual_seed(5)
+        gold = ref.FragNetPreTrain(num_layer=2, drop_ratio=0.0, num_heads=heads, edge_features=17).train()
+        outs = gold(_cpu_batch(name, True))
+        sum(o.square().mean() for o in outs).backward()
+        _CACHE[key] = (gold, [o.detach() for o in outs], {n: p.grad.detach() for n, p in gold.named_parameters() if p.grad is not None})
+    gold, want, want_g = _CACHE[key]
+    model = FragNetPreTrain(num_layer=2, drop_ratio=0.0, num_heads=heads, edge_features=17)
+    model.load_state_dict(gold.state_dict())
+    model = model.to(DEV).train()
+    b = _dev_batch(name, True)
+    try:
+        _set(22, one_pass)
+        outs = model(b)
+        assert len(outs) == 4 and all(o is not None for o in outs)
+        sum(o.square().mean() for o in outs).backward()
+        torch.cuda.synchronize()
+    finally:
+        _set(22, 1)
+    b["_fragnet_plan"].check()
+    _check_batch(name, heads, b["_fragnet_plan"], pretrain=True)
+    for i, (o, w) in enumerate(zip(outs, want)):
+        torch.testing.assert_close(o.detach().cpu(), w, atol=ATOL, rtol=1e-4, msg=lambda m, i=i: f"head output {i}: {m}")
+    _compare_grads(model, want_g)
+
+
+# ----------------------------------------------------------------------------------------------- c. the alternative kernels
+def _key_runs(name, key, values, heads=4):
+    from tests.test_gpu_tuning_keys import _encoder_run
+    net = _model(heads, drop=0.1)
+    b = _dev_batch(name)
+    res = []
+    try:
+        for v in values:
+            _set(key, v)
+            res.append(_encoder_run(net, b, 999))
+    finally:
+        _set(key, KEY_DEFAULTS[key])
+    _check_batch(name, heads, b["_fragnet_plan"])
+    return res
+
+
+@pytest.mark.parametrize("name,key,value", [("edges", 20, 0), ("edges", 20, 2), ("edges", 26, 0), ("edges", 14, 0),
+                                            ("wide", 20, 0), ("wide", 20, 2)])
+def test_alternative_kernels_reproduce_the_default_path(name, key, value):
+    """Dropout 0.1, fixed Philox offset.  Key 20: the fused tail chosen per molecule (1) against the separate launches (0) and against
+    the global-memory path for every molecule (2) -- on "edges" the chains of 25 .. 33 fragments take the global path beside LDS-class
+    molecules in the same launch, on "wide" the molecules of 130 / 156 edges do; 26 = 0: no tier at six rows; 14 = 0: no riding GEMMs."""
+    (o0, g0), (o1, g1) = _key_runs(name, key, [KEY_DEFAULTS[key], value])
+    for a, c in zip(o0, o1):
+        torch.testing.assert_close(c, a, atol=1e-5, rtol=1e-5)
+    assert set(g0) == set(g1)
+    for n in g0:
+        torch.testing.assert_close(g1[n], g0[n], atol=1e-5, rtol=1e-4, msg=lambda m, n=n: f"{n}: {m}")
+
+
+def test_engine_constant_instances_do_not_change_a_bit_on_long_rows():
+    (o0, g0), (o1, g1) = _key_runs("edges", 33, [0, 1])
+    for a, c in zip(o0, o1):
+        assert torch.equal(a, c)
+    assert set(g0) == set(g1)
+    for n in g0:
+        assert torch.equal(g0[n], g1[n]), n
+
+
+# ----------------------------------------------------------------------------------------------- d. evaluation without a backward pass
+@pytest.mark.parametrize("heads", [4, 8])
+def test_evaluation_without_a_backward_pass_returns_the_training_forward_bits(heads):
+    """Dropout 0: the no_backward kinds of the attention launches (nothing saved) give the training forward's logits bit for bit."""
+    net = _model(heads)
+    b = _dev_batch("edges")
+    train = net(b).detach().clone()
+    _check_batch("edges", heads, b["_fragnet_plan"])
+    b.pop("_fragnet_plan", None)
+    net.eval()
+    with torch.no_grad():
+        lean = net(b).clone()
+    torch.cuda.synchronize()
+    assert torch.equal(train, lean)
+
+
+# ----------------------------------------------------------------------------------------------- e. the captured step
+def test_graph_step_matches_the_oracle_with_long_rows_beside_padding():
+    """Static-shape staging + hipGraph replay (pad skip on): the "edges" batch padded to the shapes of itself and an ordinary batch;
+    loss and the flat gradient buffer against the oracle, no fall-back."""
+    from fragnet_amd import data, graphstep, parallel, synth
+    from oracle import fragnet_ref as ref
+    heads = 4
+    gold, want, want_g = _oracle("edges", heads)
+    cpu = _cpu_batch("edges")
+    loss_ref = float(ref.finetune_regr_loss(want, cpu["y"]))
+    model = _model(heads, state=gold.state_dict())
+    b = _dev_batch("edges")
+    other = data.batch_to(data.collate_fn(synth.synth_molecules(40, seed=77, profile="esol")), DEV)
+    opt = parallel.FlatAdam.for_live_parameters(
+        model, lambda: torch.nn.functional.mse_loss(model(b).view(-1), b["y"]).backward(), lr=0.0)
+    b.pop("_fragnet_plan", None)
+    shapes = graphstep.StaticShapes.from_batches([b, other], margin=0.02)
+    # from_batches sizes the one-launch plan builder's tile for molecules half as large again; at 1.5 x these stars six of its eleven
+    # tasks want four waves each and its schedule (32 wave slots) declines -> general builder.  The exact maxima keep the builder the
+    # benchmarked step runs, so that the long rows meet the padding rows of ITS plan.
+    shapes.max_per_mol = {sp: max(b.max_per_mol[sp], other.max_per_mol[sp]) for sp in b.max_per_mol}
+    step = graphstep.GraphedTrainStep(model, opt, shapes, other, loss="regr")       # collated batches: the fused kernels, the one-launch plan
+    loss = float(step(b))
+    torch.cuda.synchronize()
+    assert step.replays == 1 and step.fallbacks == 0
+    assert step.static.collated and step.static.with_offsets
+    plan = step.static.t["_fragnet_plan"]
+    plan.check()
+    _check_batch("edges", heads, plan, padded=True)
+    n_atoms = int(b["x_atoms"].shape[0])
+    assert step.static.t["x_atoms"].shape[0] > n_atoms                  # there are padding rows behind the long rows
+    assert abs(loss - loss_ref) < ATOL, (loss, loss_ref)
+    checked = 0
+    for name, p in model.named_parameters():
+        slot = getattr(p, "_fn_grad_slot", None)
+        if slot is None or name not in want_g:
+            continue
+        flat, off = slot
+        got = flat[off: off + p.numel()].view(p.shape).cpu()
+        torch.testing.assert_close(got, want_g[name], atol=ATOL, rtol=1e-4, msg=lambda s, name=name: f"{name}: {s}")
+        checked += 1
+    assert checked == len(want_g)
+
+
+# ----------------------------------------------------------------------------------------------- f. nothing read that was not written
+@pytest.mark.parametrize("name,heads", [("edges", 4), ("edges", 8), ("wide", 4)])
+def test_training_step_reads_nothing_it_did_not_write(name, heads):
+    """tests/test_gpu_tail.py's NaN poisoning with the default tail: the global-memory path is chosen per molecule here, beside LDS-class
+    molecules in the same launch -- where a row can be read before it is written.  Two runs: finite, bit-identical gradients."""
+    from tests.test_gpu_tail import _poison
+    net = _model(heads, drop=0.1)
+    b = _dev_batch(name)
+    res = []
+    for _ in range(2):
+        net.zero_grad(set_to_none=True)
+        net.pretrain.rng.offset = 5
+        b.pop("_fragnet_plan", None)
+        _poison()
+        loss = net(b).square().mean()
+        _poison()
+        loss.backward()
+        torch.cuda.synchronize()
+        res.append({n: p.grad.detach().clone() for n, p in net.named_parameters() if p.grad is not None})
+    _check_batch(name, heads, b["_fragnet_plan"])
+    assert len(res[0]) >= 30
+    for n, g in res[0].items():
+        assert torch.isfinite(g).all(), n
+        assert torch.equal(res[1][n], g), n
+
+
+# ----------------------------------------------------------------------------------------------- g. the two plan builders
+@pytest.mark.parametrize("pt", [False, True])
+def test_mol_plan_equals_the_general_plan_on_long_rows(pt):
+    from tests.test_gpu_plan_mol import _both
+    T.assert_batch_claims("edges", _records("edges", pt), 4)
+    _both(_dev_batch("edges", pt), edge_ends=pt)
+
+
+# ----------------------------------------------------------------------------------------------- h. input gradients
+def test_input_gradients_match_the_oracle():
+    """fn_encoder_backward_inputs: d out[:, 0].sum() / d (atom features, bond features, connection features) against autograd of the
+    oracle.  The collate hands the bond features out twice (edge_attr, node_features_bonds) and the connection features too (cnx_attr,
+    node_features_fbonds); the oracle reads both keys of each from ONE leaf here, the engine reads the node_features_* keys."""
+    from tests import inputgrad_common as ic
+    heads = 4
+    gold, _, _ = _oracle("edges", heads)
+    cpu = dict(_cpu_batch("edges"))
+    leaves = [cpu[k].clone().requires_grad_(True) for k in ic.TABLE_KEYS]
+    cpu["x_atoms"], cpu["node_features_bonds"], cpu["node_features_fbonds"] = leaves
+    cpu["edge_attr"], cpu["cnx_attr"] = leaves[1], leaves[2]
+    gold.eval()
+    try:
+        want = gold(cpu)
+        want_g = torch.autograd.grad(want[:, 0].sum(), leaves)
+    finally:
+        gold.train()
+    net = _model(heads, state=gold.state_dict()).eval()
+    b = _dev_batch("edges")
+    for k in ic.TABLE_KEYS:
+        b[k] = b[k].detach().clone().requires_grad_(True)
+    out = net(b)
+    out[:, 0].sum().backward()
+    torch.cuda.synchronize()
+    _check_batch("edges", heads, b["_fragnet_plan"])
+    torch.testing.assert_close(out.detach().cpu(), want.detach(), atol=ATOL, rtol=1e-4)
+    for k, w in zip(ic.TABLE_KEYS, want_g):
+        assert b[k].grad is not None, f"{k}: no gradient"
+        ic.assert_within(b[k].grad.cpu().numpy(), w.numpy(), f"d out / d {k}")
+
+
+# ----------------------------------------------------------------------------------------------- i. the GCN encoder
+def test_gcn2_matches_its_float64_restatement_on_long_rows():
+    """model_version gcn2 (csrc/gcn.hip: long rows "take more trips") against the float64 restatement of tests/test_gpu_gcn.py
+    (dense operators from the raw index lists), no dropout: logits and every live gradient."""
+    from fragnet_amd import plan as P
+    from fragnet_amd.gcn import FragNetFineTune
+    from tests.test_gpu_gcn import _restated
+    L, dims = 2, [T.CFG[k] for k in ("h1", "h2", "h3", "h4")]
+    T.assert_batch_claims("edges", _records("edges"), 4)
+    torch.manual_seed(9)
+    model = FragNetFineTune(n_classes=1, atom_features=167, frag_features=167, edge_features=17, num_layer=L, drop_ratio=0.0,
+                            act="relu", fthead="FTHead3", **dict(zip(("h1", "h2", "h3", "h4"), dims))).to(DEV).train()
+    cpu = _cpu_batch("edges")
+    b = _dev_batch("edges")
+    logits = model(b)
+    torch.nn.functional.mse_loss(logits.view(-1), b["y"]).backward()
+    torch.cuda.synchronize()
+    rows = T.plan_row_lengths(b[P.GCN_PLAN_KEY])
+    assert {4, 5, 8, 9, 12, 13, 16, 17, 19} <= rows["atom"] and {4, 5, 8, 9, 12, 13, 16, 17, 18} <= rows["frag"]
+    want, Pm = _restated(model.state_dict(), cpu, [1.0] * (1 + L + 1 + len(dims)), L, len(dims))
+    torch.nn.functional.mse_loss(want.view(-1), cpu["y"].double()).backward()
+    torch.testing.assert_close(logits.detach().cpu().double(), want.detach(), atol=ATOL, rtol=1e-4)
+    checked = 0
+    for name, q in model.named_parameters():
+        if q.grad is None:
+            assert Pm[name].grad is None or float(Pm[name].grad.abs().sum()) == 0.0, name
+            continue
+        torch.testing.assert_close(q.grad.cpu().double(), Pm[name].grad, atol=ATOL, rtol=1e-4, msg=lambda s, name=name: f"{name}: {s}")
+        checked += 1
+    assert checked == 2 * L + 4 + 2 * (len(dims) + 1)
