@@ -212,6 +212,7 @@ SIGNATURES = {
     "fn_stage_padded": [C.POINTER(StageField), C.c_int, vp],
     "fn_pool_cat_f32": [vp, vp, C.POINTER(SegPlan), C.POINTER(SegPlan), vp, vp],
     "fn_pool_cat_groups_f32": [vp, vp, C.POINTER(SegPlan), C.POINTER(SegPlan), vp, vp, vp, i64, vp, vp],
+    "fn_pool_cat_coalitions_f32": [vp, vp, C.POINTER(SegPlan), C.POINTER(SegPlan), vp, vp, vp, i64, vp, vp],
     "fn_pool_cat_bwd_f32": [vp, vp, vp, vp, vp, i64, i64, vp],
     "fn_masked_mse_f32": [vp, vp, vp, i64, C.c_int, vp, vp, vp],
     "fn_bond_graph_ws": [i64, i64],

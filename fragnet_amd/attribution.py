@@ -309,15 +309,7 @@ class FragmentAttribution:
 
     def atom_weights(self, i: int) -> np.ndarray:
         """[n_atoms of molecule i, C]: every atom carries its group's attribution, an atom in no group 0 (model_attr.py:767-781)."""
-        i = self._index(i)
-        lo, hi = int(self.offsets[i]), int(self.offsets[i + 1])
-        g = self.atom_group[int(self.atom_offsets[i]): int(self.atom_offsets[i + 1])]
-        out = np.zeros((g.shape[0], self.attr.shape[1]), dtype=self.attr.dtype)
-        if hi > lo:
-            pos = np.minimum(np.searchsorted(self.group[lo:hi], g), hi - lo - 1)          # the molecule's ids are ascending
-            hit = self.group[lo:hi][pos] == g
-            out[hit] = self.attr[lo:hi][pos[hit]]
-        return out
+        return _spread_to_atoms(self.attr, self.group, self.offsets, self.atom_group, self.atom_offsets, self._index(i))
 
     def arrays(self) -> Dict[str, np.ndarray]:
         return {"pred_no_mask": self.pred_no_mask, "offsets": self.offsets, "group": self.group, "n_atoms": self.n_atoms,
@@ -350,27 +342,79 @@ def _contribution_kind(model) -> str:
                      "dta.DTAModel2")
 
 
-def _contribution_rows(kind, model, batch, atom_group, row_mol, row_group):
-    """One encoder pass, one leave-group-out read-out and one head call: the predictions [rows, C] of ``row_mol`` / ``row_group``."""
+def _contribution_rows(kind, model, batch, read_out, row_mol, head_rows=None):
+    """One encoder pass, one read-out ``read_out(x_atoms, x_frags, plan) -> [rows, 256]`` and the head over its rows -- one call, or
+    slices of at most ``head_rows`` rows: the predictions [rows, C] of the read-out's rows, row r a row of molecule ``row_mol[r]``."""
     import torch
     from . import ops
     from .plan import plan_for
     encoder = (model.drug_model if kind in ("drp", "dta") else model).pretrain
     x_atoms, x_frags = encoder(batch, edge_outputs=False)[:2]
-    enc = ops.pool_cat_groups(x_atoms, x_frags, plan_for(batch), atom_group, row_mol, row_group, check=False)      # rows checked by the caller
-    if kind == "property":
-        model.fthead.live_rows = None
-        out = model.fthead(enc)
-    elif kind == "energy":
-        out = model.head._tower(model.head.FC_layers, enc)
-    else:
-        rows = row_mol.to(torch.long)
-        if kind == "drp":         # the second tower once per molecule, expanded to the rows
-            out = ops.pair_head(enc, model.cell_model(batch["gene_expr"]).index_select(0, rows), model.fc1, model.fc2)
+    enc = read_out(x_atoms, x_frags, plan_for(batch))
+    second = None                 # the pair models' second tower: once per molecule, expanded to the rows
+    if kind == "drp":
+        second = model.cell_model(batch["gene_expr"])
+    elif kind == "dta":
+        second = ops.protein_tower(batch["protein"].reshape(-1, model.in_channels), model.embedding_xt, model.conv_xt_1, model.fc1_xt)
+    total = int(row_mol.shape[0])
+    step = total if head_rows is None else int(head_rows)
+    outs = []
+    for lo in range(0, max(total, 1), max(step, 1)):
+        part = enc[lo: lo + step] if step < total else enc
+        if kind == "property":
+            model.fthead.live_rows = None
+            out = model.fthead(part)
+        elif kind == "energy":
+            out = model.head._tower(model.head.FC_layers, part)
         else:
-            xt = ops.protein_tower(batch["protein"].reshape(-1, model.in_channels), model.embedding_xt, model.conv_xt_1, model.fc1_xt)
-            out = ops.pair_head_dta(enc, xt.index_select(0, rows), model.fc1, model.fc2)
-    return out.reshape(row_mol.shape[0], -1).float()
+            rows = row_mol[lo: lo + step].to(torch.long)
+            if kind == "drp":
+                out = ops.pair_head(part, second.index_select(0, rows), model.fc1, model.fc2)
+            else:
+                out = ops.pair_head_dta(part, second.index_select(0, rows), model.fc1, model.fc2)
+        outs.append(out.reshape(part.shape[0], -1).float())
+    return outs[0] if len(outs) == 1 else torch.cat(outs, 0)
+
+
+def _group_source(who, kind, model, source, groups):
+    """What the fragment-level calls share: ``(store or None, records or None, collate or None, flat group id of every atom, first atom
+    of every molecule, flat_group_table)`` of ``source`` under ``groups``; refuses a model that is not on the GPU."""
+    import torch
+    from . import data
+    from .dataset import FlatMolStore
+    store = records = None
+    if isinstance(source, FlatMolStore):
+        if kind in ("drp", "dta"):
+            raise ValueError(f"{who}: a {type(model).__name__} takes a list of records (they carry "
+                             f"{'gene_expr' if kind == 'drp' else 'protein'}), not a FlatMolStore")
+        store = source
+        n_atoms = store._host_lengths()["atom"]
+        if groups is None:
+            flat = _store_fragment_table(store)[0]
+    else:
+        records = list(source)
+        if not records:
+            raise ValueError(f"{who}: no molecules")
+        n_atoms = np.array([int(r.x_atoms.shape[0]) for r in records], dtype=np.int64)
+        if groups is None:
+            flat = torch.cat([r.atom_id_frag_id for r in records]).to(torch.long).numpy()
+    if groups is not None:
+        flat = _flat_groups(groups, n_atoms)
+    atom_off = np.concatenate([[0], np.cumsum(n_atoms)]).astype(np.int64)
+    if store is not None and groups is None:
+        table = _store_fragment_table(store)[1]
+    else:
+        table = flat_group_table(flat, atom_off)
+    device = next(model.parameters()).device
+    if device.type != "cuda":
+        from . import _lib
+        raise _lib.FragnetHipError(f"{who} runs on the GPU engine; there is no CPU fallback")
+    collate = None
+    if kind in ("drp", "dta"):
+        collate = data.collate_fn_cdrp if kind == "drp" else data.collate_fn_dta
+    else:
+        store = _as_store(source if store is not None else records, device)
+    return store, records, collate, flat, atom_off, table
 
 
 def fragment_contributions(model, source, groups=None, batch_size: int = 512) -> FragmentAttribution:
@@ -382,45 +426,15 @@ def fragment_contributions(model, source, groups=None, batch_size: int = 512) ->
     group), one replica per distinct id >= 0 in ascending order.  Per chunk of ``batch_size`` molecules: one evaluation encoder pass,
     one read-out whose rows are the chunk's unmasked rows followed by its replica rows, one head call over all of them."""
     import torch
-    from . import data
+    from . import data, ops
     kind = _contribution_kind(model)
     if batch_size < 1:
         raise ValueError("batch_size must be positive")
-    from .dataset import FlatMolStore
-    store = records = None
-    if isinstance(source, FlatMolStore):
-        if kind in ("drp", "dta"):
-            raise ValueError(f"fragment_contributions: a {type(model).__name__} takes a list of records (they carry "
-                             f"{'gene_expr' if kind == 'drp' else 'protein'}), not a FlatMolStore")
-        store = source
-        n_atoms = store._host_lengths()["atom"]
-        if groups is None:
-            flat = _store_fragment_table(store)[0]
-    else:
-        records = list(source)
-        if not records:
-            raise ValueError("fragment_contributions: no molecules")
-        n_atoms = np.array([int(r.x_atoms.shape[0]) for r in records], dtype=np.int64)
-        if groups is None:
-            flat = torch.cat([r.atom_id_frag_id for r in records]).to(torch.long).numpy()
-    if groups is not None:
-        flat = _flat_groups(groups, n_atoms)
-    n = len(n_atoms)
-    atom_off = np.concatenate([[0], np.cumsum(n_atoms)]).astype(np.int64)
-    if store is not None and groups is None:
-        rep_mol, ids, sizes, counts = _store_fragment_table(store)[1]
-    else:
-        rep_mol, ids, sizes, counts = flat_group_table(flat, atom_off)
+    store, records, collate, flat, atom_off, (rep_mol, ids, sizes, counts) = _group_source("fragment_contributions", kind, model, source, groups)
+    n = atom_off.shape[0] - 1
     offsets = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
     R = int(offsets[-1])
     device = next(model.parameters()).device
-    if device.type != "cuda":
-        from . import _lib
-        raise _lib.FragnetHipError("fragment_contributions runs on the GPU engine; there is no CPU fallback")
-    if kind in ("drp", "dta"):
-        collate = data.collate_fn_cdrp if kind == "drp" else data.collate_fn_dta
-    else:
-        store = _as_store(source if store is not None else records, device)
     # every chunk's rows in ONE upload: [row groups int64 | row molecules int32 | atom groups int64], rows chunk-major, a chunk's B
     # unmasked rows (group -1) in front of its replica rows; chunks are runs of molecules, so each takes contiguous slices.  The atom
     # groups are not uploaded where they are the fragment map of a store that lives on the device.
@@ -454,8 +468,9 @@ def fragment_contributions(model, source, groups=None, batch_size: int = 512) ->
                 e = min(n, b + batch_size)
                 rows = e - b + int(offsets[e] - offsets[b])
                 batch = store.collate(np.arange(b, e)) if store is not None else data.batch_to(collate(records[b:e]), device)
-                preds.append(_contribution_rows(kind, model, batch, atom_group_d[int(atom_off[b]): int(atom_off[e])], row_mol_d[r0: r0 + rows],
-                                                row_group_d[r0: r0 + rows]))
+                rm, rg, ag = row_mol_d[r0: r0 + rows], row_group_d[r0: r0 + rows], atom_group_d[int(atom_off[b]): int(atom_off[e])]
+                preds.append(_contribution_rows(kind, model, batch, lambda xa, xf, plan: ops.pool_cat_groups(xa, xf, plan, ag, rm, rg, check=False),
+                                                rm))          # rows built and checked here, on the host
             pred_h = (preds[0] if len(preds) == 1 else torch.cat(preds, 0)).cpu().numpy()
     finally:
         model.train(was_training)
@@ -464,3 +479,320 @@ def fragment_contributions(model, source, groups=None, batch_size: int = 512) ->
         unmasked[r0: r0 + min(n, b + batch_size) - b] = True
     base_h, masked_h = pred_h[unmasked], pred_h[~unmasked]
     return FragmentAttribution(base_h, offsets, ids, sizes, masked_h, base_h[rep_mol] - masked_h, flat, atom_off)
+
+
+# ================================================================================================ fragment Shapley values
+# fragment_contributions reports leave-one-out numbers; with a non-linear head they do not add up to pred - v(no fragment).  The Shapley
+# values of the set function v(S) = prediction with the atoms of every group OUTSIDE S zeroed behind the encoder do: sum_f phi_f =
+# v(all) - v(none).  The mask sits behind the encoder, so a coalition costs one pooled sum (ops.pool_cat_coalitions) and one head row.
+DEFAULT_SHAPLEY_ROWS = 1 << 16
+_WEIGHTS, _PREFIX_ROWS = {}, {}
+
+
+def shapley_weights(F: int):
+    """The exact-mode template of F groups, cached: ``(without [F, 2^(F-1)], with [F, 2^(F-1)], weight [F, 2^(F-1)])`` -- for group f
+    the masks S without f in ascending order, S | 1 << f, and s! (F - s - 1)! / F! with s = |S|.  A mask is its own row index."""
+    hit = _WEIGHTS.get(F)
+    if hit is None:
+        if not 1 <= F <= 30:
+            raise ValueError(f"shapley_weights: 1 <= F <= 30 (got {F})")
+        from math import factorial
+        masks = np.arange(1 << F, dtype=np.int64)
+        size = np.zeros(1 << F, dtype=np.int64)
+        for f in range(F):
+            size += (masks >> f) & 1
+        by_size = np.array([factorial(s) * factorial(F - s - 1) / factorial(F) for s in range(F)], dtype=np.float64)
+        without = np.stack([masks[((masks >> f) & 1) == 0] for f in range(F)])
+        hit = _WEIGHTS[F] = (without, without | (np.int64(1) << np.arange(F, dtype=np.int64))[:, None], by_size[size[without]])
+    return hit
+
+
+def shapley_exact(values: np.ndarray, F: int) -> np.ndarray:
+    """phi [M, F, C] (float64) of M set functions on F groups from their values [M, 2^F, C], row index = mask:
+    phi_f = sum over S without f of s! (F - s - 1)! / F! (v(S + f) - v(S))."""
+    v = np.asarray(values, dtype=np.float64)
+    if F == 0:
+        return np.zeros((v.shape[0], 0, v.shape[2]), dtype=np.float64)
+    without, with_f, w = shapley_weights(F)
+    return np.einsum("fs,mfsc->mfc", w, v[:, with_f] - v[:, without])
+
+
+def draw_permutations(F: int, samples: int, seed: int, molecule: int) -> np.ndarray:
+    """[samples, F]: samples / 2 permutations of the groups from ``np.random.default_rng([seed, molecule])``, each followed by its
+    reverse (antithetic pairs) -- a function of the molecule's own index and F alone."""
+    rng = np.random.default_rng([int(seed), int(molecule)])
+    half = np.stack([rng.permutation(F) for _ in range(samples // 2)]).astype(np.int64).reshape(samples // 2, F)
+    out = np.empty((samples, F), dtype=np.int64)
+    out[0::2], out[1::2] = half, half[:, ::-1]
+    return out
+
+
+def _full_mask(F: int) -> np.uint64:
+    return np.uint64((1 << F) - 1)
+
+
+def permutation_masks(perms: np.ndarray) -> np.ndarray:
+    """The rows of a sampled molecule: uint64 [2 + K (F - 1)] -- the empty coalition, the full one, then per permutation its F - 1
+    interior prefixes {pi_0}, {pi_0, pi_1}, ..."""
+    K, F = perms.shape
+    bits = np.left_shift(np.uint64(1), perms.astype(np.uint64))
+    prefixes = np.bitwise_or.accumulate(bits, axis=1)[:, : max(F - 1, 0)]
+    return np.concatenate([np.array([0, _full_mask(F)], dtype=np.uint64), prefixes.reshape(-1)])
+
+
+def shapley_sampled(values: np.ndarray, perms: np.ndarray, paired: bool):
+    """(phi [F, C], stderr [F, C]) from the values [2 + K (F - 1), C] of ``permutation_masks(perms)``: the mean marginal of every group
+    over the K permutations; the standard error over the K / 2 means of consecutive pairs (``paired``: the antithetic draw) or over the K
+    permutations (a caller's design); NaN where there is a single one."""
+    v = np.asarray(values, dtype=np.float64)
+    K, F = perms.shape
+    rows = _PREFIX_ROWS.get((K, F))
+    if rows is None:            # [K, F + 1]: row 0 (empty), the permutation's interior prefixes, row 1 (full)
+        rows = np.empty((K, F + 1), dtype=np.int64)
+        rows[:, 0], rows[:, F] = 0, 1
+        rows[:, 1:F] = 2 + np.arange(K * (F - 1), dtype=np.int64).reshape(K, F - 1)
+        _PREFIX_ROWS[(K, F)] = rows
+    steps = v[rows]                                                   # [K, F + 1, C]
+    marginal = np.take_along_axis(steps[:, 1:] - steps[:, :-1], np.argsort(perms, axis=1)[:, :, None], axis=1)      # by group
+    units = 0.5 * (marginal[0::2] + marginal[1::2]) if paired else marginal
+    if units.shape[0] > 1:
+        stderr = units.std(axis=0, ddof=1) / np.sqrt(units.shape[0])
+    else:
+        stderr = np.full(marginal.shape[1:], np.nan)
+    return marginal.mean(axis=0), stderr
+
+
+def plan_coalition_chunks(rows_per_mol, batch_size: int, max_rows: int) -> List[Tuple[int, int]]:
+    """Runs ``(first molecule, end molecule)`` of at most ``batch_size`` molecules whose rows sum to at most ``max_rows``; a molecule's
+    rows are never split, so one that alone needs more than ``max_rows`` is refused."""
+    if batch_size < 1 or max_rows < 1:
+        raise ValueError("batch_size and max_rows must be positive")
+    rows = np.asarray(rows_per_mol, dtype=np.int64)
+    big = np.flatnonzero(rows > max_rows)
+    if big.size:
+        raise ValueError(f"fragment_shapley: molecule {int(big[0])} alone needs {int(rows[big[0]])} coalition rows, more than max_rows = {max_rows} "
+                         "(lower exact_max or samples, or raise max_rows)")
+    chunks, b, used = [], 0, 0
+    for i, r in enumerate(rows.tolist()):
+        if i > b and (i - b == batch_size or used + r > max_rows):
+            chunks.append((b, i))
+            b, used = i, 0
+        used += r
+    if len(rows):
+        chunks.append((b, len(rows)))
+    return chunks
+
+
+def coalition_design(counts, additive=False, exact_max=10, samples=256, permutations=None):
+    """``(mode [n], permutations {molecule: [K, F]}, rows [n])``: per molecule its mode -- ``"exact"`` (F <= exact_max: all 2^F masks, the
+    row index is the mask), ``"sampled"`` (the antithetic draw, made when the molecule's chunk is built, or the caller's
+    ``permutations[i]``), ``"additive"`` (an additive v: the empty row, the full row and all-but-one per group) -- and its number of rows."""
+    counts = np.asarray(counts, dtype=np.int64).reshape(-1)
+    n = counts.shape[0]
+    if samples < 2 or samples % 2:
+        raise ValueError(f"fragment_shapley: samples must be even and positive, permutations come in antithetic pairs (got {samples})")
+    if exact_max < 0:
+        raise ValueError("fragment_shapley: exact_max must not be negative")
+    if n and counts.max() > 64:
+        i = int(np.argmax(counts > 64))
+        raise ValueError(f"fragment_shapley: molecule {i} has {int(counts[i])} groups; a coalition mask holds 64")
+    if additive:
+        return np.full(n, "additive"), {}, 2 + counts
+    exact = counts <= exact_max
+    mode = np.where(exact, "exact", "sampled")
+    rows = np.where(exact, np.left_shift(np.int64(1), np.minimum(counts, 62)), 2 + samples * (counts - 1))
+    given = {}
+    for i, perms in dict(permutations or {}).items():
+        if not 0 <= int(i) < n:
+            raise ValueError(f"fragment_shapley: permutations names molecule {i}; there are {n}")
+        F, perms = int(counts[i]), np.asarray(perms)
+        if perms.ndim != 2 or perms.shape[1] != F or perms.shape[0] < 1 or perms.dtype.kind not in "iu" or \
+                (np.sort(perms, axis=1) != np.arange(F)).any():
+            raise ValueError(f"fragment_shapley: permutations[{i}] must be an int array [K, {F}] whose rows are permutations of 0..{F - 1}")
+        given[int(i)] = perms.astype(np.int64)
+        mode[i], rows[i] = "sampled", 2 + perms.shape[0] * max(F - 1, 0)
+    return mode, given, rows.astype(np.int64)
+
+
+def _shapley_host(counts, evaluate, additive=False, batch_size=512, exact_max=10, samples=256, seed=0, permutations=None,
+                  max_rows=DEFAULT_SHAPLEY_ROWS, return_values=False):
+    """Everything of ``fragment_shapley`` that runs on the host: the design, the chunks, the rows of every chunk and the reduction in
+    float64.  ``evaluate(first molecule, end molecule, row_mol int32 [rows] (chunk-local, non-decreasing), row_mask uint64 [rows])``
+    returns the values [rows, C] of a chunk.  Molecules in exact mode are handled per F, all at once; only the others one by one."""
+    counts = np.asarray(counts, dtype=np.int64).reshape(-1)
+    n = counts.shape[0]
+    mode, given, rows = coalition_design(counts, additive, exact_max, samples, permutations)
+    chunks = plan_coalition_chunks(rows, batch_size, max_rows)
+    offsets = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+    is_exact = mode == "exact"
+    pred = base = phi = stderr = None
+    exact = mode != "sampled"
+    values = [None] * n if return_values else None
+    for b, e in chunks:
+        first = np.concatenate([[0], np.cumsum(rows[b:e])]).astype(np.int64)
+        row_mol = np.repeat(np.arange(e - b, dtype=np.int32), rows[b:e])
+        row_mask = (np.arange(first[-1], dtype=np.int64) - np.repeat(first[:-1], rows[b:e])).astype(np.uint64)      # exact mode: the row index
+        others = (b + np.flatnonzero(~is_exact[b:e])).tolist()
+        perms_of = {}
+        for i in others:
+            F, lo = int(counts[i]), int(first[i - b])
+            if additive:
+                full = _full_mask(F)
+                row_mask[lo], row_mask[lo + 1] = 0, full
+                row_mask[lo + 2: lo + 2 + F] = full ^ np.left_shift(np.uint64(1), np.arange(F, dtype=np.uint64))
+            else:
+                perms_of[i] = given[i] if i in given else draw_permutations(F, samples, seed, i)
+                row_mask[lo: lo + int(rows[i])] = permutation_masks(perms_of[i])
+        v = np.asarray(evaluate(b, e, row_mol, row_mask))
+        if v.ndim != 2 or v.shape[0] != first[-1]:
+            raise ValueError(f"fragment_shapley: {first[-1]} rows went in, values of shape {v.shape} came back")
+        if phi is None:
+            C = v.shape[1]
+            pred, base = np.empty((n, C), dtype=v.dtype), np.empty((n, C), dtype=v.dtype)
+            phi, stderr = np.zeros((int(offsets[-1]), C), dtype=np.float64), np.zeros((int(offsets[-1]), C), dtype=np.float64)
+        v64 = v.astype(np.float64)
+        local = np.arange(b, e)
+        for F in np.unique(counts[b:e][is_exact[b:e]]).tolist():          # all exact molecules of one F at once
+            sel = local[is_exact[b:e] & (counts[b:e] == F)]
+            at = first[sel - b][:, None] + np.arange(1 << F)
+            pred[sel], base[sel] = v[at[:, -1]], v[at[:, 0]]
+            if F:
+                phi[(offsets[sel][:, None] + np.arange(F)).reshape(-1)] = shapley_exact(v64[at], F).reshape(-1, v.shape[1])
+        for i in others:
+            F, lo, g0 = int(counts[i]), int(first[i - b]), int(offsets[i])
+            base[i], pred[i] = v[lo], v[lo + 1]
+            if additive:
+                phi[g0: g0 + F] = v64[lo + 1] - v64[lo + 2: lo + 2 + F]
+            else:
+                phi[g0: g0 + F], stderr[g0: g0 + F] = shapley_sampled(v64[lo: lo + int(rows[i])], perms_of[i], paired=i not in given)
+        if return_values:
+            for i in range(b, e):
+                lo = int(first[i - b])
+                values[i] = {"mask": row_mask[lo: lo + int(rows[i])].copy(), "value": v[lo: lo + int(rows[i])].copy()}
+    return dict(pred=pred, base=base, offsets=offsets, phi=phi, stderr=stderr, exact=exact, values=values, rows=rows, chunks=chunks)
+
+
+def _spread_to_atoms(table, group, offsets, atom_group, atom_offsets, i):
+    """[n_atoms of molecule i, C]: every atom carries its group's row of ``table``, an atom in no group 0 (model_attr.py:767-781)."""
+    lo, hi = int(offsets[i]), int(offsets[i + 1])
+    g = atom_group[int(atom_offsets[i]): int(atom_offsets[i + 1])]
+    out = np.zeros((g.shape[0], table.shape[1]), dtype=table.dtype)
+    if hi > lo:
+        pos = np.minimum(np.searchsorted(group[lo:hi], g), hi - lo - 1)          # the molecule's ids are ascending
+        hit = group[lo:hi][pos] == g
+        out[hit] = table[lo:hi][pos[hit]]
+    return out
+
+
+class FragmentShapley:
+    """Result of ``fragment_shapley``.  ``pred [n, C]`` = v(all groups), ``base [n, C]`` = v(no group); rows ``offsets[i] : offsets[i + 1]``
+    of ``group`` / ``n_atoms`` / ``phi`` / ``stderr`` (float64 ``[R, C]``) are molecule i's groups in ascending order; ``exact [n]``: the
+    molecule's values are exact (``stderr`` 0), not a permutation sample.  ``result[i]`` is molecule i as a dict, ``atom_weights(i)`` its
+    phi spread over its atoms, ``arrays()`` what the command-line script writes.  ``values`` (``return_values=True``): per molecule
+    ``{"mask": uint64 [rows], "value": [rows, C]}``, every evaluated coalition."""
+
+    def __init__(self, pred, base, offsets, group, n_atoms, phi, stderr, exact, atom_group, atom_offsets, values=None):
+        self.pred, self.base, self.offsets, self.group, self.n_atoms = pred, base, offsets, group, n_atoms
+        self.phi, self.stderr, self.exact, self.atom_group, self.atom_offsets, self.values = phi, stderr, exact, atom_group, atom_offsets, values
+
+    def __len__(self):
+        return self.pred.shape[0]
+
+    def _index(self, i: int) -> int:
+        if not -len(self) <= i < len(self):
+            raise IndexError(i)
+        return i % len(self)
+
+    def __getitem__(self, i: int) -> dict:
+        i = self._index(i)
+        lo, hi = int(self.offsets[i]), int(self.offsets[i + 1])
+        return {"pred": self.pred[i], "base": self.base[i], "group": self.group[lo:hi], "n_atoms": self.n_atoms[lo:hi],
+                "phi": self.phi[lo:hi], "stderr": self.stderr[lo:hi], "exact": bool(self.exact[i])}
+
+    def atom_weights(self, i: int) -> np.ndarray:
+        return _spread_to_atoms(self.phi, self.group, self.offsets, self.atom_group, self.atom_offsets, self._index(i))
+
+    def arrays(self) -> Dict[str, np.ndarray]:
+        return {"pred": self.pred, "base": self.base, "offsets": self.offsets, "group": self.group, "n_atoms": self.n_atoms, "phi": self.phi,
+                "stderr": self.stderr, "exact": self.exact, "atom_offsets": self.atom_offsets, "atom_group": self.atom_group}
+
+
+def atom_bits(flat, atom_off, table) -> np.ndarray:
+    """int8 [N]: for every atom the position of its group among its molecule's groups (ascending ids: the order of ``flat_group_table``),
+    -1 for an atom in no group."""
+    rep_mol, ids, _, counts = table
+    flat = np.asarray(flat, dtype=np.int64)
+    n = atom_off.shape[0] - 1
+    out = np.full(flat.shape[0], -1, dtype=np.int8)
+    keep = np.flatnonzero(flat >= 0)
+    if keep.size:
+        span = int(ids.max()) + 1
+        if n * span >= 1 << 62:
+            raise ValueError("fragment_shapley: group ids too large to index (molecules x largest id must stay below 2^62)")
+        mol = np.repeat(np.arange(n, dtype=np.int64), np.diff(atom_off))[keep]
+        first = np.concatenate([[0], np.cumsum(counts)])
+        pos = np.searchsorted(rep_mol * span + ids, mol * span + flat[keep]) - first[mol]
+        if counts.max() > 64:
+            i = int(np.argmax(counts > 64))
+            raise ValueError(f"fragment_shapley: molecule {i} has {int(counts[i])} groups; a coalition mask holds 64")
+        out[keep] = pos.astype(np.int8)
+    return out
+
+
+def fragment_shapley(model, source, groups=None, batch_size: int = 512, exact_max: int = 10, samples: int = 256, seed: int = 0,
+                     permutations=None, max_rows: int = DEFAULT_SHAPLEY_ROWS, return_values: bool = False) -> FragmentShapley:
+    """Shapley values of the fragments (or ``groups``) of every molecule of ``source`` under ``model`` on the GPU; models, sources and
+    the ``groups`` convention are ``fragment_contributions``'.  The set function: v(S) = the prediction with the atoms of every group
+    outside S zeroed behind the encoder (ungrouped atoms and the fragment rows always stay); ``pred`` = v(all), ``base`` = v(none), and
+    sum_f phi_f = pred - base.
+
+    A molecule with F <= ``exact_max`` groups is enumerated (2^F rows, phi exact); one with more is sampled: ``samples`` permutations in
+    antithetic pairs from ``np.random.default_rng([seed, molecule index])`` -- so its answer does not depend on ``batch_size``, on its
+    neighbours or on chunking -- phi the mean marginal, ``stderr`` the standard error over the pair means.  ``permutations={molecule:
+    int array [K, F]}`` replaces the draw for those molecules whatever their F (``stderr`` then over the K permutations).  At most 64
+    groups per molecule.
+
+    The pair models (``cdrp.CDRPModel``, ``dta.DTAModel2``): their head is ``fc2(fc1(cat(enc, second)))`` with nothing between the two
+    Linears, so v is ADDITIVE in the groups and a group's Shapley value is its leave-one-out contribution v(all) - v(all but f).  Nothing
+    is enumerated for them: rows full, empty and all-but-one per group, flagged exact.
+
+    Per chunk (a run of at most ``batch_size`` molecules whose rows sum to at most ``max_rows``; a molecule's rows are never split): one
+    evaluation encoder pass, ONE coalition read-out, head calls over slices of ``ops.DENSE_MAX_ROWS`` rows, one upload of the rows.  The
+    reduction over rows runs on the host in float64."""
+    import torch
+    from . import data, ops
+    kind = _contribution_kind(model)
+    additive = kind in ("drp", "dta")
+    design_args = dict(additive=additive, batch_size=batch_size, exact_max=exact_max, samples=samples, seed=seed, permutations=permutations,
+                       max_rows=max_rows, return_values=return_values)
+    store, records, collate, flat, atom_off, table = _group_source("fragment_shapley", kind, model, source, groups)
+    rep_mol, ids, sizes, counts = table
+    if store is not None and groups is None:          # the fragment map of a store: derived once and kept on it, like its replica table
+        bits = getattr(store, "_frag_bits_cpu", None)
+        if bits is None:
+            bits = store._frag_bits_cpu = atom_bits(flat, atom_off, table)
+    else:
+        bits = atom_bits(flat, atom_off, table)
+    device = next(model.parameters()).device
+
+    def evaluate(b, e, row_mol, row_mask):
+        R, N = row_mol.shape[0], int(atom_off[e] - atom_off[b])
+        words = R + (R + 1) // 2
+        host = np.empty(words + (N + 7) // 8, dtype=np.int64)          # one upload: [masks int64 | molecules int32 | atom bits int8]
+        host[:R] = row_mask.view(np.int64)
+        host[R: words].view(np.int32)[:R] = row_mol
+        host[words:].view(np.int8)[:N] = bits[int(atom_off[b]): int(atom_off[e])]
+        dev = torch.from_numpy(host).to(device)
+        mask_d, mol_d, bit_d = dev[:R], dev[R: words].view(torch.int32)[:R], dev[words:].view(torch.int8)[:N]
+        batch = store.collate(np.arange(b, e)) if store is not None else data.batch_to(collate(records[b:e]), device)
+        read_out = lambda xa, xf, plan: ops.pool_cat_coalitions(xa, xf, plan, bit_d, mol_d, mask_d, check=False)      # rows built here
+        return _contribution_rows(kind, model, batch, read_out, mol_d, head_rows=ops.DENSE_MAX_ROWS).cpu().numpy()
+
+    was_training = model.training
+    model.eval()
+    try:
+        with torch.no_grad():
+            r = _shapley_host(counts, evaluate, **design_args)
+    finally:
+        model.train(was_training)
+    return FragmentShapley(r["pred"], r["base"], r["offsets"], ids, sizes, r["phi"], r["stderr"], r["exact"], flat, atom_off, r["values"])

@@ -206,6 +206,135 @@ __global__ __launch_bounds__(kBlock) void k_pool_cat_groups(const float* __restr
         out[(size_t)r * 2 * FN_D + blockIdx.y * FN_D + threadIdx.x] = v;
     }
 }
+// coalition form of k_pool_cat (fragment Shapley values): output row r is molecule row_mol[r] pooled over the atoms that are in no group
+// (atom_bit < 0) or whose bit atom_bit[i] of row_mask[r] is set; the fragments' half is never masked.  Partition, order of additions and
+// the treatment of a left-out atom (0.0, load skipped) are k_pool_cat_groups', so the same bit-for-bit statements hold.
+// The simple form: one workgroup per row and half, grid (R, 2) -- the yardstick of the tiled form below (FN_TUNE_COALITION_STAGED).
+__global__ __launch_bounds__(kBlock) void k_pool_cat_coalitions_rows(const float* __restrict__ x_atoms, const float* __restrict__ x_frags,
+                                                                     fn_seg_plan sa, fn_seg_plan sf, const int8_t* __restrict__ atom_bit,
+                                                                     const int32_t* __restrict__ row_mol, const uint64_t* __restrict__ row_mask,
+                                                                     float* __restrict__ out) {
+    __shared__ float sS[kRows][FN_D];
+    const fn_seg_plan& sp = blockIdx.y ? sf : sa;
+    const float* src = blockIdx.y ? x_frags : x_atoms;
+    const int lane = threadIdx.x & 31, hw = threadIdx.x >> 5;
+    const int64_t r = blockIdx.x;
+    const int64_t s = row_mol[r];
+    const uint64_t mask = row_mask[r];
+    const int beg = sp.rowptr[s] - sp.pos_base, deg = sp.rowptr[s + 1] - sp.rowptr[s];
+    float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+    for (int i = hw; i < deg; i += kRows) {
+        const int32_t row = sp.perm[beg + i];
+        const int b = blockIdx.y ? -1 : (int)atom_bit[row];
+        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (b < 0 || ((mask >> (unsigned)b) & 1ull)) v = ld4(src + (size_t)row * FN_D + lane * 4);
+        acc.x += v.x; acc.y += v.y; acc.z += v.z; acc.w += v.w;
+    }
+    st4(&sS[hw][lane * 4], acc);
+    __syncthreads();
+    if (threadIdx.x < FN_D) {
+        float v = 0.f;
+#pragma unroll
+        for (int w = 0; w < kRows; ++w) v += sS[w][threadIdx.x];
+        out[(size_t)r * 2 * FN_D + blockIdx.y * FN_D + threadIdx.x] = v;
+    }
+}
+
+// One whole output row by ONE half-wave: the eight partial rows of k_pool_cat (partial w = items w, w + 8, ... in ascending order) live
+// in registers and are added as ((0 + p0) + p1) + ... + p7.  kStaged: item i is row i of `src` (LDS) and `bit` is indexed by i; else
+// item i is row perm[i] of `src` (global memory) and `bit` by that row.  bit == nullptr: nothing is masked.
+template <bool kStaged>
+__device__ __forceinline__ float4 coalition_row(const float* src, const int32_t* __restrict__ perm, const int8_t* bit, int deg,
+                                                uint64_t mask, int lane) {
+    float4 p[kRows];
+#pragma unroll
+    for (int w = 0; w < kRows; ++w) p[w] = make_float4(0.f, 0.f, 0.f, 0.f);
+    for (int i0 = 0; i0 < deg; i0 += kRows) {
+#pragma unroll
+        for (int w = 0; w < kRows; ++w) {
+            const int i = i0 + w;
+            if (i < deg) {
+                const int32_t row = kStaged ? i : perm[i];
+                const int b = bit ? (int)bit[row] : -1;
+                float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+                if (b < 0 || ((mask >> (unsigned)b) & 1ull)) v = ld4(src + (size_t)row * FN_D + lane * 4);
+                p[w].x += v.x; p[w].y += v.y; p[w].z += v.z; p[w].w += v.w;
+            }
+        }
+    }
+    float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+    for (int w = 0; w < kRows; ++w) { acc.x += p[w].x; acc.y += p[w].y; acc.z += p[w].z; acc.w += p[w].w; }
+    return acc;
+}
+
+// The tiled form: a workgroup owns the tile of kCoTile consecutive output rows blockIdx.x and walks the runs of equal row_mol in it
+// (row_mol is non-decreasing, so a molecule's rows are one run; a run that crosses a tile boundary belongs to both tiles).  Half-wave hw
+// takes the tile's rows hw, hw + 8, ... that lie in the run, each whole (coalition_row), and writes both halves: no cross-wave traffic.
+// A run of at least min_run rows whose molecule has at most kCoStage atoms is STAGED: the molecule's atom rows and atom_bit values go
+// to LDS once, in pooling order, half-wave 0 adds the fragment rows into sF, one barrier before the rows and one behind them.  A 512-B
+// LDS row per atom and a 16-byte read per lane: the 16-lane groups of ds_read_b128 inside a half-wave cover 64 distinct banks, the two
+// half-waves of a wave are separate groups -- no conflict, no padding.  Any other run takes the same loop over global memory, without
+// LDS and without barriers: a short run would pay the staging round trip for nothing (2048 rows at 4 per molecule: 93 us with every run
+// staged against 7 us one workgroup per row).
+constexpr int kCoTile = 64, kCoStage = 112, kCoMinRun = 16, kCoAutoRows = 64;
+__global__ __launch_bounds__(kBlock) void k_pool_cat_coalitions(const float* __restrict__ x_atoms, const float* __restrict__ x_frags,
+                                                                fn_seg_plan sa, fn_seg_plan sf, const int8_t* __restrict__ atom_bit,
+                                                                const int32_t* __restrict__ row_mol, const uint64_t* __restrict__ row_mask,
+                                                                int64_t R, int min_run, float* __restrict__ out) {
+    __shared__ float sX[kCoStage * FN_D];
+    __shared__ float sF[FN_D];
+    __shared__ int32_t sMol[kCoTile];
+    __shared__ unsigned long long sStarts;
+    __shared__ int8_t sBit[kCoStage];
+    const int lane = threadIdx.x & 31, hw = threadIdx.x >> 5;
+    const int64_t r0 = (int64_t)blockIdx.x * kCoTile;
+    const int n = (int)((R - r0) < (int64_t)kCoTile ? (R - r0) : (int64_t)kCoTile);
+    if (threadIdx.x < kCoTile) {                     // wave 0: the tile's molecules and the first row of every run
+        const int t = threadIdx.x;
+        const int32_t m = t < n ? row_mol[r0 + t] : -1;
+        const int32_t before = (t > 0 && t < n) ? row_mol[r0 + t - 1] : -1;
+        sMol[t] = m;
+        const unsigned long long first = __ballot(t < n && (t == 0 || m != before));
+        if (t == 0) sStarts = first;
+    }
+    __syncthreads();
+    unsigned long long starts = sStarts;
+    while (starts) {                                 // uniform over the workgroup, and so is `staged`
+        const int a = __ffsll(starts) - 1;
+        starts &= starts - 1;
+        const int e = starts ? __ffsll(starts) - 1 : n;
+        const int64_t s = sMol[a];
+        const int beg = sa.rowptr[s] - sa.pos_base, deg = sa.rowptr[s + 1] - sa.rowptr[s];
+        const int fbeg = sf.rowptr[s] - sf.pos_base, fdeg = sf.rowptr[s + 1] - sf.rowptr[s];
+        const bool staged = deg <= kCoStage && e - a >= min_run;
+        if (staged) {
+            if (hw == 0) st4(&sF[lane * 4], coalition_row<false>(x_frags, sf.perm + fbeg, nullptr, fdeg, 0, lane));
+            for (int idx = threadIdx.x; idx < deg * 32; idx += kBlock) {
+                const int i = idx >> 5, c = idx & 31;
+                const int32_t row = sa.perm[beg + i];
+                st4(&sX[i * FN_D + c * 4], ld4(x_atoms + (size_t)row * FN_D + c * 4));
+                if (c == 0) sBit[i] = atom_bit[row];
+            }
+            __syncthreads();
+        }
+        for (int j = a + ((hw - a) & (kRows - 1)); j < e; j += kRows) {
+            const uint64_t mask = row_mask[r0 + j];
+            float4 acc, frag;
+            if (staged) {
+                acc = coalition_row<true>(sX, nullptr, sBit, deg, mask, lane);
+                frag = ld4(&sF[lane * 4]);
+            } else {
+                acc = coalition_row<false>(x_atoms, sa.perm + beg, atom_bit, deg, mask, lane);
+                frag = coalition_row<false>(x_frags, sf.perm + fbeg, nullptr, fdeg, 0, lane);
+            }
+            float* o = out + (size_t)(r0 + j) * 2 * FN_D + lane * 4;
+            st4(o, acc);
+            st4(o + FN_D, frag);
+        }
+        if (staged) __syncthreads();                 // the next staged run overwrites the staging area
+    }
+}
 // its backward: g_atoms[i,:] = g[batch[i], 0:128], g_frags[f,:] = g[frag_batch[f], 128:256]
 __global__ void k_pool_cat_bwd(const float* __restrict__ g, const int64_t* __restrict__ batch, const int64_t* __restrict__ frag_batch,
                                float* __restrict__ g_atoms, float* __restrict__ g_frags, int64_t N, int64_t F) {
@@ -535,7 +664,7 @@ int prof_event(int i, hipStream_t st) {
     }
     return 0;
 }
-int g_tune[FN_TUNE_COUNT] = {1024, 0, 0, 192, 0, 0, 0, 1, 1, 0, 1792, 1536, 512, 512, 2, -1, 0, 1, 0, 0, 1, 23, 1, 768, 1, 0, 1, 1, 0, 0, 6144, 1, 1, 1};   // in the order of the FN_TUNE_* keys
+int g_tune[FN_TUNE_COUNT] = {1024, 0, 0, 192, 0, 0, 0, 1, 1, 0, 1792, 1536, 512, 512, 2, -1, 0, 1, 0, 0, 1, 23, 1, 768, 1, 0, 1, 1, 0, 0, 6144, 1, 1, 1, 1};   // in the order of the FN_TUNE_* keys
 }  // namespace
 namespace fni {      // hooks for the other translation units (fn_internal.h)
 int fail(int code, const char* what) { return ::fail(code, what); }
@@ -868,6 +997,27 @@ int fn_pool_cat_groups_f32(const float* x_atoms, const float* x_frags, const fn_
     hipLaunchKernelGGL(k_pool_cat_groups, dim3((unsigned)R, 2), dim3(kBlock), 0, S(stream), x_atoms, x_frags, *mol_atoms, *mol_frags,
                        atom_group, row_mol, row_group, out);
     return launch_status("fn_pool_cat_groups_f32");
+}
+
+int fn_pool_cat_coalitions_f32(const float* x_atoms, const float* x_frags, const fn_seg_plan* mol_atoms, const fn_seg_plan* mol_frags,
+                               const int8_t* atom_bit, const int32_t* row_mol, const uint64_t* row_mask, int64_t R, float* out,
+                               fn_stream_t stream) {
+    if (!mol_atoms || !mol_frags || mol_atoms->n_seg != mol_frags->n_seg || R < 0 || R > 0x7fffffffLL)
+        return fail(FN_EINVAL, "fn_pool_cat_coalitions_f32: bad argument");
+    if (R == 0) return 0;
+    if (mol_atoms->n_seg == 0) return fail(FN_EINVAL, "fn_pool_cat_coalitions_f32: output rows of a batch without molecules");
+    if (!out || !row_mol || !row_mask || (mol_atoms->n_items > 0 && (!x_atoms || !atom_bit || !mol_atoms->perm)) ||
+        (mol_frags->n_items > 0 && (!x_frags || !mol_frags->perm)) || !mol_atoms->rowptr || !mol_frags->rowptr)
+        return fail(FN_EINVAL, "fn_pool_cat_coalitions_f32: null buffer");
+    const int form = fni::tune(FN_TUNE_COALITION_STAGED);
+    // the tiled form measured faster from 64 rows per molecule on (1.03 - 1.06 x there, 1.4 x at 1024); below it, one workgroup per row is
+    if (form == 0 || (form == 1 && R < (int64_t)kCoAutoRows * mol_atoms->n_seg))
+        hipLaunchKernelGGL(k_pool_cat_coalitions_rows, dim3((unsigned)R, 2), dim3(kBlock), 0, S(stream), x_atoms, x_frags, *mol_atoms,
+                           *mol_frags, atom_bit, row_mol, row_mask, out);
+    else
+        hipLaunchKernelGGL(k_pool_cat_coalitions, dim3((unsigned)((R + kCoTile - 1) / kCoTile)), dim3(kBlock), 0, S(stream), x_atoms, x_frags,
+                           *mol_atoms, *mol_frags, atom_bit, row_mol, row_mask, R, form == 1 ? kCoMinRun : form - 1, out);
+    return launch_status("fn_pool_cat_coalitions_f32");
 }
 
 int fn_pool_cat_bwd_f32(const float* g, const int64_t* batch, const int64_t* frag_batch, float* g_atoms, float* g_frags,

@@ -401,6 +401,44 @@ def pool_cat_groups(x_atoms, x_frags, plan, atom_group, row_mol, row_group, chec
     return out
 
 
+def pool_cat_coalitions(x_atoms, x_frags, plan, atom_bit, row_mol, row_mask, check: bool = True):
+    """The coalition read-out (fn_pool_cat_coalitions_f32): row r of the result [R, 256] is ``pool_cat``'s row of molecule
+    ``row_mol[r]`` over the atoms i with ``atom_bit[i] < 0`` (in no group: always present) or bit ``atom_bit[i]`` of ``row_mask[r]``
+    set; the fragments' half is never masked.  ``atom_bit`` int8 [N] (the position 0..63 of the atom's group among its molecule's
+    groups), ``row_mol`` int32 [R], non-decreasing, ``row_mask`` int64 [R] (the 64 bits of the mask; bit 63 is the sign bit), on
+    the batch's device.  An evaluation read-out: no autograd node.  ``check=True`` validates ``row_mol`` (range, order) and
+    ``atom_bit`` (< 64) here, on the host (one synchronisation: the kernel has no status word); ``check=False``: the caller built
+    them on the host and has checked them there."""
+    x_atoms, x_frags = _f32c(x_atoms, "x_atoms"), _f32c(x_frags, "x_frags")
+    dev = x_atoms.device
+    for t, name in ((atom_bit, "atom_bit"), (row_mol, "row_mol"), (row_mask, "row_mask")):
+        if not torch.is_tensor(t) or not t.is_cuda:
+            raise _lib.FragnetHipError(f"pool_cat_coalitions: {name} must be a GPU tensor; there is no CPU fallback")
+    sa, sf = plan.segs["mol_atoms"], plan.segs["mol_frags"]
+    if x_atoms.shape != (sa.n_items, FN_D) or x_frags.shape != (sf.n_items, FN_D):
+        raise ValueError("pool_cat_coalitions: feature tables do not match the batch / frag_batch index")
+    for t, name, dtype, rows in ((atom_bit, "atom_bit", torch.int8, sa.n_items), (row_mol, "row_mol", torch.int32, None),
+                                 (row_mask, "row_mask", torch.int64, row_mol.shape[0])):
+        if t.dtype != dtype or t.dim() != 1 or not t.is_contiguous() or t.device != dev or (rows is not None and t.shape[0] != rows):
+            raise ValueError(f"pool_cat_coalitions: {name} must be a contiguous {dtype} vector" + (f" of {rows} entries" if rows is not None else "")
+                             + f" on {dev}")
+    R = int(row_mol.shape[0])
+    out = torch.empty((R, 2 * FN_D), dtype=torch.float32, device=dev)
+    if R == 0:
+        return out
+    if check:
+        if bool(((row_mol < 0) | (row_mol >= sa.n_seg)).any()):
+            raise IndexError(f"pool_cat_coalitions: row_mol must lie in [0, {sa.n_seg}) (got {int(row_mol.min())} .. {int(row_mol.max())})")
+        if R > 1 and bool((row_mol[1:] < row_mol[:-1]).any()):
+            raise ValueError("pool_cat_coalitions: row_mol must be non-decreasing (a molecule's rows are one run)")
+        if sa.n_items and int(atom_bit.max()) >= 64:
+            raise IndexError(f"pool_cat_coalitions: atom_bit must be < 64 (got {int(atom_bit.max())})")
+    a, f = _seg_struct(sa), _seg_struct(sf)
+    _lib.call("fn_pool_cat_coalitions_f32", x_atoms.data_ptr(), x_frags.data_ptr(), C.byref(a), C.byref(f), atom_bit.data_ptr(),
+              row_mol.data_ptr(), row_mask.data_ptr(), R, out.data_ptr(), _stream_ptr(dev))
+    return out
+
+
 class _MaskedLoss(torch.autograd.Function):
     """A loss over a padded batch, loss and d loss / d out from one single-block kernel ``fn_<name>_f32``:
     ``masked_mse``: sum_i w_i |out_i - y_i|^2 / (sum_i w_i * T); ``masked_bce``: compute_bce_loss (train/utils.py:297-304)."""

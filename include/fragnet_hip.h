@@ -135,7 +135,13 @@ int fn_abi_version(void);
                                        * arithmetic, bit-identical results, fewer scalar tests and branches in the issue-bound row loops (round 6: 0.769 ->
                                        * 0.755 ms per training step, the forward-only sweep - 4 ... - 7 %); 0: the general instances for every launch (A/B,
                                        * and the parity test of the two against each other) */
-#define FN_TUNE_COUNT 34
+#define FN_TUNE_COALITION_STAGED 34     /* the form of fn_pool_cat_coalitions_f32's kernel.  0: one workgroup per output row and half, the form of
+                                       * fn_pool_cat_groups_f32.  n >= 2: the tiled form -- a workgroup owns 64 consecutive output rows and walks the runs
+                                       * of one molecule in them; a run of at least n - 1 rows is staged (the molecule's atom rows go to LDS once for all
+                                       * of its rows), a shorter one reads global memory (2: every run is staged; a large n: none).  1 (default): the
+                                       * tiled form with n = 17 for a call with at least 64 rows per molecule on average, where it measured faster,
+                                       * else the form of 0.  Same bits in every form */
+#define FN_TUNE_COUNT 35
 int fn_set_tuning(int key, int value);
 /* Profiling aid (process-wide, like the tuning knobs): while `buf` (device, n_u64 >= 16 * 4 * workgroups 64-bit words) is set, every wave
  * of the one-pass attention backward (fn_gat_bwd_one_f32) writes s_memtime stamps of its phases into it (tools/probe/bwd_one_probe.py
@@ -685,6 +691,17 @@ int fn_pool_cat_f32(const float* x_atoms /*[N,128]*/, const float* x_frags /*[F,
 int fn_pool_cat_groups_f32(const float* x_atoms /*[N,128]*/, const float* x_frags /*[F,128]*/, const struct fn_seg_plan* mol_atoms,
                            const struct fn_seg_plan* mol_frags, const int64_t* atom_group /*[N]*/, const int32_t* row_mol /*[R]*/,
                            const int64_t* row_group /*[R]*/, int64_t R, float* out /*[R,256]*/, fn_stream_t stream);
+/* coalition read-out (fragment Shapley values: every row keeps a SET of the molecule's groups): atom_bit[i] is the position 0..63 of
+ * atom i's group among its molecule's groups, < 0 for an atom in no group.  out[r, 0:128] = sum of x_atoms[i, :] over the atoms i of
+ * molecule row_mol[r] with atom_bit[i] < 0 or bit atom_bit[i] of row_mask[r] set (an atom whose bit is clear enters as 0.0, its load is
+ * skipped; an ungrouped atom is in every row, the empty coalition included); out[r, 128:256] = that molecule's fragment sum, never
+ * masked.  Partition and order of additions are fn_pool_cat_f32's, so bit for bit: a row with every group's bit set is fn_pool_cat_f32's
+ * row of its molecule, a row with all bits but one is the leave-group-out row of that group, any row is fn_pool_cat_f32's of the table
+ * with the left-out atom rows overwritten by 0.0.  row_mol must be non-decreasing and lie in [0, n_seg): the caller validates it (the
+ * kernel has no status word).  R == 0 launches nothing.  Form of the kernel: FN_TUNE_COALITION_STAGED. */
+int fn_pool_cat_coalitions_f32(const float* x_atoms /*[N,128]*/, const float* x_frags /*[F,128]*/, const struct fn_seg_plan* mol_atoms,
+                               const struct fn_seg_plan* mol_frags, const int8_t* atom_bit /*[N]*/, const int32_t* row_mol /*[R]*/,
+                               const uint64_t* row_mask /*[R]*/, int64_t R, float* out /*[R,256]*/, fn_stream_t stream);
 int fn_pool_cat_bwd_f32(const float* g /*[B,256]*/, const int64_t* batch /*[N]*/, const int64_t* frag_batch /*[F]*/,
                         float* g_atoms /*[N,128]*/, float* g_frags /*[F,128]*/, int64_t N, int64_t F, fn_stream_t stream);
 int fn_masked_mse_f32(const float* out /*[B,T]*/, const float* y /*[B,T]*/, const float* w /*[B]*/, int64_t B, int T,
