@@ -242,6 +242,8 @@ SIGNATURES = {
     "fn_head_act_param_grad_f32": [vp, i64, vp, vp],
     "fn_cdrp_gene_fwd_f32": [vp, vp, vp, vp, i64, i64, i64, vp],
     "fn_cdrp_gene_bwd_f32": [vp, vp, vp, vp, vp, i64, i64, i64, vp],
+    "fn_cdrp_gene_fwd_path_f32": [vp, vp, vp, vp, vp, vp, i64, i64, i64, i64, vp],
+    "fn_cdrp_gene_dx_f32": [vp, vp, vp, vp, vp, vp, vp, i64, i64, i64, i64, vp],
     "fn_dta_conv_fwd_f32": [vp, vp, vp, vp, vp, vp, i64, i64, i64, i64, i64, i64, vp],
     "fn_dta_conv_bwd_ws": [i64, i64, i64, i64],
     "fn_dta_conv_bwd_f32": [vp, vp, vp, vp, vp, vp, vp, vp, i64, i64, i64, i64, i64, i64, vp],

@@ -1295,15 +1295,102 @@ def cell_tower(gene_expr, linears):
     if not gene_expr.is_cuda:
         raise _lib.FragnetHipError(f"cell_tower: fragnet_amd kernels need GPU tensors (got {gene_expr.device}); there is no CPU fallback")
     linears = list(linears)
-    rows = gene_expr.shape[0]
-    ok = gene_expr.dtype == torch.int64 and gene_expr.dim() == 2 and rows <= DENSE_MAX_ROWS and linears[0].out_features % 4 == 0 \
-        and all(lin.bias is not None for lin in linears) and all(_dense_ok(rows, lin.weight) for lin in linears[1:])
-    if not ok:
+    if not cell_tower_ok(gene_expr, gene_expr.shape[0], linears):
         v = gene_expr.float()
         for lin in linears:
             v = torch.relu(torch.nn.functional.linear(v, lin.weight, lin.bias))
         return v
     return _CellTower.apply(gene_expr, *[q for lin in linears for q in (lin.weight, lin.bias)])
+
+
+def cell_tower_ok(gene_expr, rows: int, linears) -> bool:
+    """Whether ``rows`` rows of ``gene_expr`` run ``linears`` on the tower's kernels (``cell_tower``'s fast path)."""
+    return gene_expr.dtype == torch.int64 and gene_expr.dim() == 2 and rows <= DENSE_MAX_ROWS and linears[0].out_features % 4 == 0 \
+        and all(lin.bias is not None for lin in linears) and all(_dense_ok(rows, lin.weight) for lin in linears[1:])
+
+
+def _cell_path_forward(gene, P, alpha, base, st):
+    """The tower on the path rows ``x0 + alpha[j] (gene[c] - x0)`` (row c S + j): every layer's output, as ``_CellTower.forward`` saves
+    them, the first from fn_cdrp_gene_fwd_path_f32 -- the path rows themselves are never in memory."""
+    (C_, K), S = gene.shape, alpha.shape[0]
+    M = C_ * S
+    h = torch.empty((M, P[0].shape[0]), dtype=torch.float32, device=gene.device)
+    _lib.call("fn_cdrp_gene_fwd_path_f32", gene.data_ptr(), _ptr(base), alpha.data_ptr(), P[0].data_ptr(), P[1].data_ptr(), h.data_ptr(), C_, S, K,
+              h.shape[1], st)
+    acts = [h]
+    for i in range(1, len(P) // 2):
+        W, b = P[2 * i], P[2 * i + 1]
+        y = torch.empty((M, W.shape[0]), dtype=torch.float32, device=gene.device)
+        act = _lib.ActEpilogue(y.data_ptr(), 0.0, 1, 0, 0, None)
+        _lib.call("fn_dense_fwd_f32", h.data_ptr(), W.data_ptr(), b.data_ptr(), y.data_ptr(), M, W.shape[1], W.shape[0], C.byref(act), st)
+        h = y
+        acts.append(h)
+    return acts
+
+
+def _cell_path_args(gene_expr, linears, v, alpha, base, what):
+    gene = _i64c(gene_expr, "gene_expr")
+    linears = list(linears)
+    alpha = _f32c(alpha, "alpha").reshape(-1)
+    rows = gene.shape[0] * alpha.shape[0] if gene.dim() == 2 else 0
+    if alpha.shape[0] < 1 or not cell_tower_ok(gene, rows, linears):
+        raise ValueError(f"{what}: the cell-line tower's kernels take int64 [C, gene_dim] rows, C * steps <= {DENSE_MAX_ROWS}, Linears with a "
+                         "bias and output widths that are multiples of 4; there is no other path")
+    P = tuple(_f32c(q.detach(), "tower parameter") for lin in linears for q in (lin.weight, lin.bias))
+    _gene_shapes(gene, P[0], P[1])
+    v = _f32c(v, "v").reshape(1, -1)
+    if v.shape[1] != P[-2].shape[0]:
+        raise ValueError(f"{what}: v has {v.shape[1]} entries, the tower's output {P[-2].shape[0]}")
+    if base is not None:
+        base = _f32c(base, "baseline").reshape(-1)
+        if base.shape[0] != gene.shape[1]:
+            raise ValueError(f"{what}: the baseline has {base.shape[0]} entries, gene_expr {gene.shape[1]} columns")
+    return gene, P, v, alpha, base
+
+
+def cell_path_scores(gene_expr, linears, v, alpha, base=None):
+    """``<cell_enc, v>`` on the path rows ``x0 + alpha[j] (gene_expr[c] - x0)``, [C, S] (``base`` None: x0 = 0): the tower's kernels and
+    fn_small_linear_f32 for the dot, no autograd.  ``alpha = [1]`` scores the cell lines themselves, with the model's own bits."""
+    gene, P, v, alpha, base = _cell_path_args(gene_expr, linears, v, alpha, base, "cell_path_scores")
+    st = _stream_ptr(gene.device)
+    top = _cell_path_forward(gene, P, alpha, base, st)[-1]
+    out = torch.empty((top.shape[0], 1), dtype=torch.float32, device=gene.device)
+    if top.shape[0]:
+        _lib.call("fn_small_linear_f32", top.data_ptr(), v.data_ptr(), None, out.data_ptr(), top.shape[0], v.shape[1], 1, top.shape[0], st)
+    return out.view(gene.shape[0], alpha.shape[0])
+
+
+def cell_path_attributions(gene_expr, linears, v, alpha, base=None, want_gradient: bool = False):
+    """Attributions of ``s = <cell_enc, v>`` to the genes over the path nodes ``alpha`` [S] (row c S + j is node j of cell line c):
+    ``attr[c, k] = (gene_expr[c, k] - x0[k]) * mean_j d s / d x[c S + j, k]`` as float32 [C, gene_dim] -- gradient x input for ``alpha =
+    [1]``, integrated gradients for a quadrature's nodes.  The call sequence of ``_CellTower`` without autograd: the path forward
+    (fn_cdrp_gene_fwd_path_f32, then fn_dense_fwd_f32), the seed ``v`` through the last ReLU (fn_small_linear_bwd_f32 with ones for the
+    upstream gradient), fn_dense_bwd_f32 top-down for the input gradients (gate_scale = 1; the weight gradients it also writes go to
+    scratch) and fn_cdrp_gene_dx_f32, which multiplies by the first weight and folds the S nodes.  Returns ``(attr, gradient)``,
+    ``gradient`` [C, gene_dim] the path-averaged input gradient with ``want_gradient``, else None."""
+    gene, P, v, alpha, base = _cell_path_args(gene_expr, linears, v, alpha, base, "cell_path_attributions")
+    dev, st = gene.device, _stream_ptr(gene.device)
+    (C_, K), S = gene.shape, alpha.shape[0]
+    M = C_ * S
+    attr = torch.empty((C_, K), dtype=torch.float32, device=dev)
+    grad = torch.empty_like(attr) if want_gradient else None
+    if M == 0:
+        return attr, grad
+    acts = _cell_path_forward(gene, P, alpha, base, st)
+    top = acts[-1]
+    ones = torch.ones((M, 1), dtype=torch.float32, device=dev)
+    g, dv, dvb = torch.empty_like(top), torch.empty_like(v), torch.empty(1, dtype=torch.float32, device=dev)
+    ws = _scratch(_lib.load().fn_small_linear_bwd_ws(M, v.shape[1], 1), dev)
+    _lib.call("fn_small_linear_bwd_f32", ones.data_ptr(), top.data_ptr(), v.data_ptr(), g.data_ptr(), dv.data_ptr(), dvb.data_ptr(), M, v.shape[1], 1,
+              1.0, _ptr(ws), st)
+    for i in range(len(P) // 2 - 1, 0, -1):
+        W, x = P[2 * i], acts[i - 1]
+        gx, dW = torch.empty_like(x), torch.empty_like(W)
+        _lib.call("fn_dense_bwd_f32", g.data_ptr(), x.data_ptr(), W.data_ptr(), gx.data_ptr(), 1.0, dW.data_ptr(), None, M, W.shape[1], W.shape[0], M, st)
+        g = gx
+    _lib.call("fn_cdrp_gene_dx_f32", g.data_ptr(), None, P[0].data_ptr(), gene.data_ptr(), _ptr(base), attr.data_ptr(), _ptr(grad), C_, S, K,
+              P[0].shape[0], st)
+    return attr, grad
 
 
 class _PairInstance(NamedTuple):

@@ -954,7 +954,18 @@ int fn_encoder_backward_inputs(const fn_encoder* e, const float* scratch, int64_
  *                          with y_gate = the saved output Y, g = g_y where Y > 0 and 0 elsewhere.  No input gradient: gene_expr is data.
  * Tower layers 2-4 (1024 -> 256 -> 64 -> 256, ReLU after each, no dropout) are fn_dense_fwd_f32 (ReLU epilogue, p = 0) and
  * fn_dense_bwd_f32 (gate_scale = 1).
- *   fn_cdrp_pair_fwd_f32   h[M,H] = drug[M,Kd] W1[:, :Kd]^T + cell[M,Kc] W1[:, Kd:]^T + b1 (W1 [H, Kd + Kc]; no cat is written; h is saved
+ * Attributions of gene_expr (gradient x input and integrated gradients over a straight path; entry points added under ABI 12, nothing
+ * existing changes).  M = C S rows: row r is path node j = r % S of cell line c = r / S.  S >= 1, M <= FN_DENSE_MAX_ROWS, C = 0 is legal
+ * (nothing is launched or written); K, N and the alignment rules as for fn_cdrp_gene_fwd_f32.
+ *   fn_cdrp_gene_fwd_path_f32  Y[M,N] = relu(X W[N,K]^T + bias) with X[r,k] = base[k] + alpha[j] (float(G[c,k]) - base[k]) formed in the load
+ *                          from the int64 rows G[C,K], base[K] (nullable: zeros) and alpha[S]; no float [M,K] table is written.  With
+ *                          S = 1, alpha = {1} and base == NULL the result is fn_cdrp_gene_fwd_f32's, bit for bit.
+ *   fn_cdrp_gene_dx_f32    the layer's input gradient dX[r,k] = sum_n g[r,n] W[n,k] (g gated as in fn_cdrp_gene_bwd_f32: y_gate == NULL
+ *                          means g_y is already through the ReLU), folded where it is produced:
+ *                          attr[c,k] = (float(G[c,k]) - base[k]) * grad_mean[c,k],  grad_mean[c,k] = (sum_j dX[c S + j, k]) / S,
+ *                          the S rows of a cell line added in ascending j.  grad_mean [C,K] is stored only when non-null; the [M,K]
+ *                          gradient table never is.  With S = 1 this is gradient x input.  One launch.
+ *   fn_cdrp_pair_fwd_f32  h[M,H] = drug[M,Kd] W1[:, :Kd]^T + cell[M,Kc] W1[:, Kd:]^T + b1 (W1 [H, Kd + Kc]; no cat is written; h is saved
  *                          for the backward), out[M] = h w2 + b2 (w2 [C,H], C = 1).  With target [M] (nullable): g[M] = d MSE / d out =
  *                          2 (out - target) / M and loss_part[fn_cdrp_pair_loss_ws(M)] = per-workgroup partial sums of mean((out - target)^2),
  *                          whose sum in order is the loss.  One launch.
@@ -972,6 +983,10 @@ int fn_cdrp_gene_fwd_f32(const int64_t* G, const float* W, const float* bias /*n
                          fn_stream_t stream);
 int fn_cdrp_gene_bwd_f32(const float* g_y, const float* y_gate /*nullable*/, const int64_t* G, float* dW, float* db /*nullable*/, int64_t M,
                          int64_t K, int64_t N, fn_stream_t stream);
+int fn_cdrp_gene_fwd_path_f32(const int64_t* G, const float* base /*nullable*/, const float* alpha, const float* W, const float* bias /*nullable*/,
+                              float* Y, int64_t C, int64_t S, int64_t K, int64_t N, fn_stream_t stream);
+int fn_cdrp_gene_dx_f32(const float* g_y, const float* y_gate /*nullable*/, const float* W, const int64_t* G, const float* base /*nullable*/,
+                        float* attr, float* grad_mean /*nullable*/, int64_t C, int64_t S, int64_t K, int64_t N, fn_stream_t stream);
 int64_t fn_cdrp_pair_loss_ws(int64_t M);
 int fn_cdrp_pair_fwd_f32(const float* drug, const float* cell, const float* W1, const float* b1, const float* w2, const float* b2,
                          const float* target /*nullable*/, float* h, float* out, float* g /*nullable without target*/,
