@@ -255,6 +255,11 @@ for _fam in ("fn_cdrp_pair", "fn_dta_pair"):
     SIGNATURES[_fam + "_loss_ws"] = [i64]
     SIGNATURES[_fam + "_fwd_f32"] = [vp] * 11 + [i64] * 5 + [vp]
     SIGNATURES[_fam + "_bwd_f32"] = [vp] * 13 + [i64, vp] + [i64] * 5 + [vp]
+    # the same head on a factored batch (csrc/pair_factored.hip): unique rows, pair lists, pair orderings
+    SIGNATURES[_fam + "_factored_ws"] = [i64, i64]
+    SIGNATURES[_fam + "_factored_fwd_f32"] = [vp] * 15 + [i64] * 7 + [vp]
+    SIGNATURES[_fam + "_factored_bwd_f32"] = [vp] * 19 + [i64, vp] + [i64] * 7 + [vp]
+    SIGNATURES[_fam + "_factored_grid_f32"] = [vp] * 7 + [i64] * 6 + [vp]
 
 _lib = None
 

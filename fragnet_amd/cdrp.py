@@ -14,6 +14,7 @@ from __future__ import annotations
 import torch.nn as nn
 
 from . import ops
+from .data import PAIR_DRUG_KEY, PAIR_GRID_KEY, PAIR_ORDER_KEYS, PAIR_SECOND_KEY
 from .model import FragNet, FTHead1, FTHead2, FTHead3, FTHead4, pooled
 
 
@@ -65,7 +66,19 @@ class CDRPModel(nn.Module):
 
     def forward(self, batch, loss=None):
         """``loss = (_lib.LOSS_MSE, y, None)``: the fused-loss call of a training step (``ops.pair_head``); returns ``(out, loss)``, ``loss``
-        None where the fused launch does not apply."""
+        None where the fused launch does not apply.  A factored batch (``data.collate_fn_cdrp_factored``, ``data.as_factored``: it carries
+        ``pair_drug``) runs the encoder on its U distinct drugs, the tower on its C distinct cell lines and ``ops.pair_head_factored``: [M, 1]
+        in pair order.  A grid batch (``data.pair_grid_batch``) returns every drug against every cell line, [U, C]."""
         drug_enc = self.drug_model(batch)
         cell_enc = self.cell_model(batch["gene_expr"])
+        if batch.get(PAIR_GRID_KEY):
+            return ops.pair_head_grid(drug_enc, cell_enc, self.fc1, self.fc2)
+        if PAIR_DRUG_KEY in batch:
+            return ops.pair_head_factored(drug_enc, cell_enc, batch[PAIR_DRUG_KEY], batch[PAIR_SECOND_KEY], self.fc1, self.fc2, loss=loss,
+                                          orderings=pair_orderings_of(batch), check=False)
         return ops.pair_head(drug_enc, cell_enc, self.fc1, self.fc2, loss=loss)
+
+
+def pair_orderings_of(batch):
+    """The pair orderings a factored batch carries (``data.PAIR_ORDER_KEYS``), None where it has none: the head then builds them."""
+    return tuple(batch[k] for k in PAIR_ORDER_KEYS) if all(k in batch for k in PAIR_ORDER_KEYS) else None

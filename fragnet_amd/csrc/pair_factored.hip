@@ -1,0 +1,439 @@
+// pair_factored.hip -- the pair head of pair_head.hip on a FACTORED batch: U distinct drug rows D[U,256], C distinct second rows S[C,K1] and
+// two pair lists pd[M], ps[M] instead of M duplicated rows.  There is nothing between the two Linears, so with W1 = [W1d | W1s],
+// A = D W1d^T [U,128], B = S W1s^T [C,128]:
+//   out[m]   = alpha[pd[m]] + beta[ps[m]] + (b1 . w2 + b2),    alpha = A w2, beta = B w2
+//   g[m]     = 2 (out[m] - y[m]) / M
+//   sd[u]    = sum of g over the pairs of drug u,  ss[c] likewise,  G = sum_m g[m]
+//   g_D[u,:] = sd[u] v_d,  g_S[c,:] = ss[c] v_s,  v = W1^T w2      (GATE: g_S zeroed where S <= 0, the ReLU that produced S)
+//   dW1[j,k] = w2[j] [D^T sd | S^T ss][k],  db1 = w2 G,  db2 = G,  dW2[j] = sum_u sd[u] A[u,j] + sum_c ss[c] B[c,j] + G b1[j]
+// Nothing of size M x 128 or M x 256 exists; a pair costs a few scalars.  The same two instances as pair_head.hip and no other:
+// <256, gated> (fn_cdrp_pair_factored_*), <300, not gated> (fn_dta_pair_factored_*; 300 = 18 x 16 + 12, the last MFMA step masked).
+// Arithmetic as there: fp32 in, fp32 accumulate, v_mfma_f32_16x16x4_f32 for A and B, no float atomics, every sum over pairs or rows in a
+// fixed order (the one integer atomic is the forward's arrival counter).  A pair-list value is range-tested before it indexes anything:
+// a pair outside [0,U) x [0,C) gets out = 0, g = 0 and adds nothing to the loss or to a gradient.
+#include <stdint.h>
+#include <stdio.h>
+
+#include "fn_internal.h"
+
+namespace {
+using fni::fail;
+using fni::launch_status;
+
+constexpr int kIn0 = 256, kHid = 128, kTileRows = 16, kSegRows = 64;
+
+__device__ __forceinline__ void pf_step(const float* xp, const float* wp0, const float* wp1, bool ok, f32x4& acc0, f32x4& acc1) {
+    const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
+    const float4 a = ok ? ld4(xp) : z, p = ok ? ld4(wp0) : z, q = ok ? ld4(wp1) : z;
+    DN_MFMA(acc0, a.x, p.x);  DN_MFMA(acc1, a.x, q.x);
+    DN_MFMA(acc0, a.y, p.y);  DN_MFMA(acc1, a.y, q.y);
+    DN_MFMA(acc0, a.z, p.z);  DN_MFMA(acc1, a.z, q.z);
+    DN_MFMA(acc0, a.w, p.w);  DN_MFMA(acc1, a.w, q.w);
+}
+
+// one 16 x 128 tile of X[N,K] Wh^T (Wh = the K columns of W1 at `wcol`, rows LD long) into sh and into P[N,128]: wave w the 32 columns
+// [32 w, +32), K in steps of 16 of which the last is masked where K is no multiple of 16
+template <int K, int LD>
+__device__ __forceinline__ void pf_tile(const float* __restrict__ X, const float* __restrict__ W1, int wcol, int N, int i0,
+                                        float (*sh)[kHid + 1], float* __restrict__ P) {
+    constexpr int kfull = K & ~15;
+    const int l = threadIdx.x & 63, n = l & 15, gq = l >> 4, wv = threadIdx.x >> 6, j0 = wv * 32;
+    const int row = min(i0 + n, N - 1);
+    f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
+    const float* xp = X + (size_t)row * K + 4 * gq;
+    const float* wp0 = W1 + (size_t)(j0 + n) * LD + wcol + 4 * gq;
+    const float* wp1 = wp0 + (size_t)16 * LD;
+#pragma unroll 2
+    for (int k0 = 0; k0 < kfull; k0 += 16) pf_step(xp + k0, wp0 + k0, wp1 + k0, true, acc0, acc1);
+    if constexpr (kfull < K) pf_step(xp + kfull, wp0 + kfull, wp1 + kfull, kfull + 4 * gq < K, acc0, acc1);
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+        const int col = j0 + 16 * u + n;
+        const f32x4 acc = u ? acc1 : acc0;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const int r = 4 * gq + e;
+            sh[r][col] = acc[e];
+            if (i0 + r < N) P[(size_t)(i0 + r) * kHid + col] = acc[e];
+        }
+    }
+}
+
+// forward, one launch.  Workgroups [0, nbU): 16 rows of A and their alpha; the next nbC: 16 rows of B and their beta.  Each publishes its
+// rows (agent-scope release, then one relaxed add on the arrival counter, which the host zeroes in front of the launch); the workgroup
+// that arrives last acquires and writes out[M] and, with a target, g[M] and the one loss partial (already divided by M).
+template <int K1>
+__global__ __launch_bounds__(256) void k_pairf_fwd(const float* __restrict__ D, const float* __restrict__ Sx, const int64_t* __restrict__ pd,
+                                                   const int64_t* __restrict__ ps, const float* __restrict__ W1, const float* __restrict__ b1,
+                                                   const float* __restrict__ w2, const float* __restrict__ b2, const float* __restrict__ target,
+                                                   float* __restrict__ A, float* __restrict__ B, float* ab, unsigned* counter,
+                                                   float* __restrict__ out, float* __restrict__ g, float* __restrict__ loss_part, int M, int U,
+                                                   int C, int nbU) {
+    constexpr int kInT = kIn0 + K1;
+    __shared__ float sh[kTileRows][kHid + 1];
+    __shared__ float sred[256];
+    __shared__ unsigned s_ticket;
+    const int t = threadIdx.x, b = blockIdx.x;
+    const bool first = b < nbU;
+    const int i0 = (first ? b : b - nbU) * kTileRows, N = first ? U : C;
+    if (first) pf_tile<kIn0, kInT>(D, W1, 0, U, i0, sh, A);
+    else pf_tile<K1, kInT>(Sx, W1, kIn0, C, i0, sh, B);
+    __syncthreads();
+    {
+        const int r = t >> 4, sub = t & 15;
+        float s = 0.f;
+#pragma unroll
+        for (int c = 0; c < kHid / 16; ++c) s = fmaf(sh[r][sub + 16 * c], w2[sub + 16 * c], s);
+        s += __shfl_xor(s, 8);  s += __shfl_xor(s, 4);  s += __shfl_xor(s, 2);  s += __shfl_xor(s, 1);
+        if (sub == 0 && i0 + r < N) ab[(first ? 0 : U) + i0 + r] = s;
+    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    if (t == 0) {
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        s_ticket = __hip_atomic_fetch_add(counter, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    __syncthreads();
+    if (s_ticket != gridDim.x - 1) return;
+    if (t == 0) {
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        float c0 = 0.f;
+        for (int j = 0; j < kHid; ++j) c0 = fmaf(b1[j], w2[j], c0);
+        sred[0] = c0 + b2[0];
+    }
+    __syncthreads();
+    const float cst = sred[0];
+    __syncthreads();
+    float d2 = 0.f;
+    for (int m = t; m < M; m += 256) {
+        const int64_t u = pd[m], c = ps[m];
+        float o = 0.f, gm = 0.f;
+        if (u >= 0 && u < U && c >= 0 && c < C) {
+            o = ab[u] + ab[U + c] + cst;
+            if (target) {
+                const float d = o - target[m];
+                gm = 2.f * d / (float)M;
+                d2 += d * d;
+            }
+        }
+        out[m] = o;
+        if (target) g[m] = gm;
+    }
+    if (!target) return;
+    sred[t] = d2;
+    __syncthreads();
+    if (t == 0) {
+        float s = sred[0];
+        for (int q = 1; q < 256; ++q) s += sred[q];
+        loss_part[0] = s / (float)M;
+    }
+}
+
+template <int LD> __device__ __forceinline__ float pf_v(const float* __restrict__ w2, const float* __restrict__ W1, int k) {
+    float v = 0.f;
+#pragma unroll 8
+    for (int c = 0; c < kHid; ++c) v = fmaf(w2[c], W1[(size_t)c * LD + k], v);
+    return v;
+}
+template <int K1> constexpr int kColBlocks = (kIn0 + K1 + 15) / 16;
+
+// sig[r] = the sum of g over the pairs of row base + r, r < 64: 4 lanes per row walk the row's segment of the ordering (ascending pair
+// index), added ((0 + 1) + (2 + 3)).  rowptr and perm are range-tested; a row without pairs gives exactly 0.  The caller barriers.
+__device__ __forceinline__ void pf_sigma(const float* __restrict__ g, const int32_t* __restrict__ rowptr, const int32_t* __restrict__ perm, int N,
+                                         int M, int base, float* sig) {
+    const int r = threadIdx.x >> 2, sub = threadIdx.x & 3, row = base + r;
+    float s = 0.f;
+    if (row < N) {
+        const int beg = min(max(rowptr[row], 0), M), end = min(max(rowptr[row + 1], beg), M);
+        for (int i = beg + sub; i < end; i += 4) {
+            const int p = perm[i];
+            if ((unsigned)p < (unsigned)M) s += g[p];
+        }
+    }
+    s += __shfl_xor(s, 1);
+    s += __shfl_xor(s, 2);
+    if (sub == 0) sig[r] = s;
+}
+
+// backward, one launch.  Workgroups [0, rbU): 64 rows of g_D; the next rbC: 64 rows of g_S (v's half recomputed per workgroup); the next
+// ceil((256 + K1) / 16): 16 columns of [D^T sd | S^T ss] over all rows (64 row lanes, added through LDS in order) and their 128 x 16
+// block of dW1; the last: dW2, db2, db1 and, with loss != null, loss[0] = the sum of the forward's partials.
+template <int K1, bool GATE>
+__global__ __launch_bounds__(256) void k_pairf_bwd(const float* __restrict__ g, const float* __restrict__ D, const float* __restrict__ Sx,
+                                                   const float* __restrict__ A, const float* __restrict__ B, const float* __restrict__ W1,
+                                                   const float* __restrict__ b1, const float* __restrict__ w2,
+                                                   const int32_t* __restrict__ rp_d, const int32_t* __restrict__ pm_d,
+                                                   const int32_t* __restrict__ rp_s, const int32_t* __restrict__ pm_s, float* __restrict__ g_D,
+                                                   float* __restrict__ g_S, float* __restrict__ dW1, float* __restrict__ db1,
+                                                   float* __restrict__ dW2, float* __restrict__ db2, const float* __restrict__ loss_part,
+                                                   int n_part, float* __restrict__ loss, int M, int U, int C, int rbU, int rbC) {
+    constexpr int kInT = kIn0 + K1;
+    static_assert(K1 % 4 == 0 && K1 <= 1024, "float4 columns; v's half fits the LDS array");
+    __shared__ __attribute__((aligned(16))) float sm[1024 + 16];
+    __shared__ float sig[kSegRows];
+    __shared__ float s1[1];
+    const int t = threadIdx.x, b = blockIdx.x;
+    if (b < rbU + rbC) {
+        const bool first = b < rbU;
+        const int base = (first ? b : b - rbU) * kSegRows, N = first ? U : C, Kx = first ? kIn0 : K1, k0 = first ? 0 : kIn0;
+        for (int k = t; k < Kx; k += 256) sm[k] = pf_v<kInT>(w2, W1, k0 + k);
+        pf_sigma(g, first ? rp_d : rp_s, first ? pm_d : pm_s, N, M, base, sig);
+        __syncthreads();
+        const int q4 = Kx / 4;
+        float* go = first ? g_D : g_S;
+        for (int e = t; e < kSegRows * q4; e += 256) {
+            const int r = e / q4, k = 4 * (e % q4), row = base + r;
+            if (row >= N) break;
+            const float s = sig[r];
+            float4 o = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (s != 0.f) {
+                o = make_float4(s * sm[k], s * sm[k + 1], s * sm[k + 2], s * sm[k + 3]);
+                if (GATE && !first) {
+                    const float4 xv = ld4(Sx + (size_t)row * K1 + k);
+                    o = make_float4(xv.x > 0.f ? o.x : 0.f, xv.y > 0.f ? o.y : 0.f, xv.z > 0.f ? o.z : 0.f, xv.w > 0.f ? o.w : 0.f);
+                }
+            }
+            st4(go + (size_t)row * Kx + k, o);
+        }
+        return;
+    }
+    if (b < rbU + rbC + kColBlocks<K1>) {
+        const int c4 = t & 3, rl = t >> 2;
+        const int col = (b - rbU - rbC) * 16 + 4 * c4;               // of [D | S]; 256 = 16 blocks: a block's columns lie in one half
+        const bool first = col < kIn0;
+        const bool ok = kInT % 16 == 0 || col < kInT;
+        const float* x = first ? D + col : Sx + (col - kIn0);
+        const int ldx = first ? kIn0 : K1, N = first ? U : C;
+        const int32_t* rp = first ? rp_d : rp_s;
+        const int32_t* pm = first ? pm_d : pm_s;
+        float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+        for (int base = 0; base < N; base += kSegRows) {              // `first` is uniform over the workgroup: so is the trip count
+            pf_sigma(g, rp, pm, N, M, base, sig);
+            __syncthreads();
+            if (ok && base + rl < N) fma4(acc, sig[rl], ld4(x + (size_t)(base + rl) * ldx));
+            __syncthreads();
+        }
+        st4(sm + 4 * (rl * 4 + c4), acc);
+        __syncthreads();
+        if (rl == 0) {
+            float4 s = ld4(sm + 4 * c4);
+            for (int q = 1; q < 64; ++q) { const float4 o = ld4(sm + 4 * (q * 4 + c4));  s.x += o.x;  s.y += o.y;  s.z += o.z;  s.w += o.w; }
+            st4(sm + 1024 + 4 * c4, s);
+        }
+        __syncthreads();
+        if (!ok) return;
+        const float4 u = ld4(sm + 1024 + 4 * c4);
+#pragma unroll
+        for (int rep = 0; rep < 2; ++rep) {
+            const int c = rl + 64 * rep;
+            const float w = w2[c];
+            st4(dW1 + (size_t)c * kInT + col, make_float4(w * u.x, w * u.y, w * u.z, w * u.w));
+        }
+        return;
+    }
+    {                                                                 // dW2: 32 float4 columns x 8 row lanes, the rows of A, then of B
+        const int c4 = t & 31, rl = t >> 5;
+        float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+        for (int base = 0; base < U; base += kSegRows) {
+            pf_sigma(g, rp_d, pm_d, U, M, base, sig);
+            __syncthreads();
+            for (int r = rl; r < kSegRows && base + r < U; r += 8) fma4(acc, sig[r], ld4(A + (size_t)(base + r) * kHid + 4 * c4));
+            __syncthreads();
+        }
+        for (int base = 0; base < C; base += kSegRows) {
+            pf_sigma(g, rp_s, pm_s, C, M, base, sig);
+            __syncthreads();
+            for (int r = rl; r < kSegRows && base + r < C; r += 8) fma4(acc, sig[r], ld4(B + (size_t)(base + r) * kHid + 4 * c4));
+            __syncthreads();
+        }
+        st4(sm + 4 * (rl * 32 + c4), acc);
+        const int lane = t & 63, wv = t >> 6;
+        if (wv == 0) {                                                // G = db2
+            float s = 0.f;
+            for (int m = lane; m < M; m += 64) s += g[m];
+            for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off);
+            if (lane == 0) s1[0] = s;
+        }
+        if (wv == 3 && loss) {
+            float s = 0.f;
+            for (int i = lane; i < n_part; i += 64) s += loss_part[i];
+            for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off);
+            if (lane == 0) loss[0] = s;
+        }
+        __syncthreads();
+        if (t < kHid) {
+            float s = sm[t];
+            for (int q = 1; q < 8; ++q) s += sm[q * kHid + t];
+            dW2[t] = fmaf(s1[0], b1[t], s);
+            db1[t] = w2[t] * s1[0];
+        }
+        if (t == 0) db2[0] = s1[0];
+    }
+}
+
+// grid: out[u, c] = D[u] . v_d + S[c] . v_s + (b1 . w2 + b2) for every (u, c), v = W1^T w2 recomputed per workgroup.  A workgroup =
+// 16 drug rows (16 lanes each, added across the lanes in a fixed order) x 256 second rows (one thread each).
+template <int K1>
+__global__ __launch_bounds__(256) void k_pairf_grid(const float* __restrict__ D, const float* __restrict__ Sx, const float* __restrict__ W1,
+                                                    const float* __restrict__ b1, const float* __restrict__ w2, const float* __restrict__ b2,
+                                                    float* __restrict__ out, int U, int C) {
+    constexpr int kInT = kIn0 + K1;
+    __shared__ __attribute__((aligned(16))) float sv[kInT];
+    __shared__ float sa[kTileRows + 1];
+    const int t = threadIdx.x, c = blockIdx.x * 256 + t, u0 = blockIdx.y * kTileRows;
+    for (int k = t; k < kInT; k += 256) sv[k] = pf_v<kInT>(w2, W1, k);
+    if (t == 0) {
+        float c0 = 0.f;
+        for (int j = 0; j < kHid; ++j) c0 = fmaf(b1[j], w2[j], c0);
+        sa[kTileRows] = c0 + b2[0];
+    }
+    __syncthreads();
+    {
+        const int r = t >> 4, sub = t & 15, row = min(u0 + r, U - 1);
+        float s = 0.f;
+#pragma unroll 4
+        for (int q = 0; q < kIn0 / 16; ++q) s = fmaf(D[(size_t)row * kIn0 + sub + 16 * q], sv[sub + 16 * q], s);
+        s += __shfl_xor(s, 8);  s += __shfl_xor(s, 4);  s += __shfl_xor(s, 2);  s += __shfl_xor(s, 1);
+        if (sub == 0) sa[r] = s;
+    }
+    __syncthreads();
+    if (c >= C) return;
+    float bt = 0.f;
+    for (int k = 0; k < K1; k += 4) {
+        const float4 x = ld4(Sx + (size_t)c * K1 + k);
+        bt = fmaf(x.x, sv[kIn0 + k], bt);  bt = fmaf(x.y, sv[kIn0 + k + 1], bt);
+        bt = fmaf(x.z, sv[kIn0 + k + 2], bt);  bt = fmaf(x.w, sv[kIn0 + k + 3], bt);
+    }
+    bt += sa[kTileRows];
+    for (int r = 0; r < kTileRows && u0 + r < U; ++r) out[(size_t)(u0 + r) * C + c] = sa[r] + bt;
+}
+
+// ---- host side
+int fail_at(int code, const char* who, const char* what) {
+    char msg[200];
+    snprintf(msg, sizeof(msg), "%s: %s", who, what);
+    return fail(code, msg);
+}
+template <int K1> int check_widths(int64_t Kd, int64_t K, int64_t H, int64_t Co) {
+    if (Kd == kIn0 && K == K1 && H == kHid && Co == 1) return 0;
+    return fail(FN_EUNSUPPORTED, K1 == 256 ? "fn_cdrp_pair_factored_*: the pair head is 256 + 256 -> 128 -> 1 (Kd = Kc = 256, H = 128, C = 1); other widths are not built"
+                                           : "fn_dta_pair_factored_*: the pair head is 256 + 300 -> 128 -> 1 (Kd = 256, Kx = 300, H = 128, C = 1); other widths are not built");
+}
+int check_counts(const char* who, int64_t M, int64_t U, int64_t C) {
+    if (M < 0 || M > FN_DENSE_MAX_ROWS || U < 0 || U > FN_DENSE_MAX_ROWS || C < 0 || C > FN_DENSE_MAX_ROWS)
+        return fail_at(FN_EINVAL, who, "0 <= M, U, C <= FN_DENSE_MAX_ROWS");
+    return 0;
+}
+int64_t factored_ws(int64_t U, int64_t C) { return U < 0 || C < 0 ? 0 : U + C + 4; }      // alpha[U], beta[C], the arrival counter
+
+template <int K1>
+int pairf_fwd(const char* who, const float* D, const float* Sx, const int64_t* pd, const int64_t* ps, const float* W1, const float* b1,
+              const float* w2, const float* b2, const float* target, float* A, float* B, float* ws, float* out, float* g, float* loss_part,
+              int64_t M, int64_t U, int64_t C, int64_t Kd, int64_t K, int64_t H, int64_t Co, fn_stream_t stream) {
+    FN_TRY(check_widths<K1>(Kd, K, H, Co));
+    FN_TRY(check_counts(who, M, U, C));
+    if (M == 0) return 0;
+    if (U == 0 || C == 0) return fail_at(FN_EINVAL, who, "pairs (M > 0) need U >= 1 and C >= 1");
+    if (!D || !Sx || !pd || !ps || !W1 || !b1 || !w2 || !b2 || !A || !B || !ws || !out || (target && (!g || !loss_part)) ||
+        misaligned(15, D, Sx, W1) || misaligned(7, pd, ps) || misaligned(3, ws))
+        return fail_at(FN_EINVAL, who, "null or misaligned buffer");
+    unsigned* counter = reinterpret_cast<unsigned*>(ws + U + C);
+    if (hipMemsetAsync(counter, 0, sizeof(unsigned), S(stream)) != hipSuccess) return launch_status(who);
+    const int nbU = (int)((U + kTileRows - 1) / kTileRows), nbC = (int)((C + kTileRows - 1) / kTileRows);
+    hipLaunchKernelGGL(k_pairf_fwd<K1>, dim3((unsigned)(nbU + nbC)), dim3(256), 0, S(stream), D, Sx, pd, ps, W1, b1, w2, b2, target, A, B, ws,
+                       counter, out, g, loss_part, (int)M, (int)U, (int)C, nbU);
+    return launch_status(who);
+}
+
+template <int K1, bool GATE>
+int pairf_bwd(const char* who, const float* g, const float* D, const float* Sx, const float* A, const float* B, const float* W1,
+              const float* b1, const float* w2, const int32_t* rp_d, const int32_t* pm_d, const int32_t* rp_s, const int32_t* pm_s,
+              float* g_D, float* g_S, float* dW1, float* db1, float* dW2, float* db2, const float* loss_part, int64_t n_part, float* loss,
+              int64_t M, int64_t U, int64_t C, int64_t Kd, int64_t K, int64_t H, int64_t Co, fn_stream_t stream) {
+    FN_TRY(check_widths<K1>(Kd, K, H, Co));
+    FN_TRY(check_counts(who, M, U, C));
+    if (n_part < 0 || n_part > INT32_MAX) return fail_at(FN_EINVAL, who, "n_part out of range");
+    if (!W1 || !b1 || !w2 || !dW1 || !db1 || !dW2 || !db2 || (U > 0 && !g_D) || (C > 0 && !g_S) ||
+        (M > 0 && (!g || !D || !Sx || !A || !B || !rp_d || !pm_d || !rp_s || !pm_s)) || (loss && n_part > 0 && !loss_part) ||
+        misaligned(15, D, Sx, A, B) || misaligned(15, g_D, g_S, dW1) || misaligned(3, rp_d, pm_d, rp_s, pm_s))
+        return fail_at(FN_EINVAL, who, "null or misaligned buffer");
+    if (M == 0 || U == 0 || C == 0) {                     // no pairs: the sums are empty
+        char where[96];
+        snprintf(where, sizeof(where), "%s (no pairs)", who);
+        if (U > 0) FN_TRY(zero_async(g_D, U * kIn0, stream, where));
+        if (C > 0) FN_TRY(zero_async(g_S, C * K1, stream, where));
+        FN_TRY(zero_async(dW1, kHid * (kIn0 + K1), stream, where));
+        FN_TRY(zero_async(db1, kHid, stream, where));
+        FN_TRY(zero_async(dW2, kHid, stream, where));
+        FN_TRY(zero_async(db2, 1, stream, where));
+        if (loss) FN_TRY(zero_async(loss, 1, stream, where));
+        return 0;
+    }
+    const int rbU = (int)((U + kSegRows - 1) / kSegRows), rbC = (int)((C + kSegRows - 1) / kSegRows);
+    hipLaunchKernelGGL((k_pairf_bwd<K1, GATE>), dim3((unsigned)(rbU + rbC + kColBlocks<K1> + 1)), dim3(256), 0, S(stream), g, D, Sx, A, B, W1, b1,
+                       w2, rp_d, pm_d, rp_s, pm_s, g_D, g_S, dW1, db1, dW2, db2, loss_part, (int)n_part, loss, (int)M, (int)U, (int)C, rbU, rbC);
+    return launch_status(who);
+}
+
+template <int K1>
+int pairf_grid(const char* who, const float* D, const float* Sx, const float* W1, const float* b1, const float* w2, const float* b2, float* out,
+               int64_t U, int64_t C, int64_t Kd, int64_t K, int64_t H, int64_t Co, fn_stream_t stream) {
+    FN_TRY(check_widths<K1>(Kd, K, H, Co));
+    FN_TRY(check_counts(who, 0, U, C));
+    if (U == 0 || C == 0) return 0;
+    if (!D || !Sx || !W1 || !b1 || !w2 || !b2 || !out || misaligned(15, Sx) || misaligned(3, D, W1, out))
+        return fail_at(FN_EINVAL, who, "null or misaligned buffer");
+    hipLaunchKernelGGL(k_pairf_grid<K1>, dim3((unsigned)((C + 255) / 256), (unsigned)((U + kTileRows - 1) / kTileRows)), dim3(256), 0, S(stream),
+                       D, Sx, W1, b1, w2, b2, out, (int)U, (int)C);
+    return launch_status(who);
+}
+}  // namespace
+
+extern "C" {
+
+int64_t fn_cdrp_pair_factored_ws(int64_t U, int64_t C) { return factored_ws(U, C); }
+int64_t fn_dta_pair_factored_ws(int64_t U, int64_t C) { return factored_ws(U, C); }
+
+int fn_cdrp_pair_factored_fwd_f32(const float* drug, const float* cell, const int64_t* pair_drug, const int64_t* pair_cell, const float* W1,
+                                  const float* b1, const float* w2, const float* b2, const float* target, float* A, float* B, float* ws,
+                                  float* out, float* g, float* loss_part, int64_t M, int64_t U, int64_t Cn, int64_t Kd, int64_t Kc, int64_t H,
+                                  int64_t C, fn_stream_t stream) {
+    return pairf_fwd<256>("fn_cdrp_pair_factored_fwd_f32", drug, cell, pair_drug, pair_cell, W1, b1, w2, b2, target, A, B, ws, out, g, loss_part,
+                          M, U, Cn, Kd, Kc, H, C, stream);
+}
+int fn_dta_pair_factored_fwd_f32(const float* drug, const float* xt, const int64_t* pair_drug, const int64_t* pair_prot, const float* W1,
+                                 const float* b1, const float* w2, const float* b2, const float* target, float* A, float* B, float* ws,
+                                 float* out, float* g, float* loss_part, int64_t M, int64_t U, int64_t Cn, int64_t Kd, int64_t Kx, int64_t H,
+                                 int64_t C, fn_stream_t stream) {
+    return pairf_fwd<300>("fn_dta_pair_factored_fwd_f32", drug, xt, pair_drug, pair_prot, W1, b1, w2, b2, target, A, B, ws, out, g, loss_part, M,
+                          U, Cn, Kd, Kx, H, C, stream);
+}
+
+int fn_cdrp_pair_factored_bwd_f32(const float* g, const float* drug, const float* cell, const float* A, const float* B, const float* W1,
+                                  const float* b1, const float* w2, const int32_t* rowptr_drug, const int32_t* perm_drug,
+                                  const int32_t* rowptr_cell, const int32_t* perm_cell, float* g_drug, float* g_cell, float* dW1, float* db1,
+                                  float* dW2, float* db2, const float* loss_part, int64_t n_part, float* loss, int64_t M, int64_t U, int64_t Cn,
+                                  int64_t Kd, int64_t Kc, int64_t H, int64_t C, fn_stream_t stream) {
+    return pairf_bwd<256, true>("fn_cdrp_pair_factored_bwd_f32", g, drug, cell, A, B, W1, b1, w2, rowptr_drug, perm_drug, rowptr_cell, perm_cell,
+                                g_drug, g_cell, dW1, db1, dW2, db2, loss_part, n_part, loss, M, U, Cn, Kd, Kc, H, C, stream);
+}
+int fn_dta_pair_factored_bwd_f32(const float* g, const float* drug, const float* xt, const float* A, const float* B, const float* W1,
+                                 const float* b1, const float* w2, const int32_t* rowptr_drug, const int32_t* perm_drug,
+                                 const int32_t* rowptr_prot, const int32_t* perm_prot, float* g_drug, float* g_xt, float* dW1, float* db1,
+                                 float* dW2, float* db2, const float* loss_part, int64_t n_part, float* loss, int64_t M, int64_t U, int64_t Cn,
+                                 int64_t Kd, int64_t Kx, int64_t H, int64_t C, fn_stream_t stream) {
+    return pairf_bwd<300, false>("fn_dta_pair_factored_bwd_f32", g, drug, xt, A, B, W1, b1, w2, rowptr_drug, perm_drug, rowptr_prot, perm_prot,
+                                 g_drug, g_xt, dW1, db1, dW2, db2, loss_part, n_part, loss, M, U, Cn, Kd, Kx, H, C, stream);
+}
+
+int fn_cdrp_pair_factored_grid_f32(const float* drug, const float* cell, const float* W1, const float* b1, const float* w2, const float* b2,
+                                   float* out, int64_t U, int64_t Cn, int64_t Kd, int64_t Kc, int64_t H, int64_t C, fn_stream_t stream) {
+    return pairf_grid<256>("fn_cdrp_pair_factored_grid_f32", drug, cell, W1, b1, w2, b2, out, U, Cn, Kd, Kc, H, C, stream);
+}
+int fn_dta_pair_factored_grid_f32(const float* drug, const float* xt, const float* W1, const float* b1, const float* w2, const float* b2,
+                                  float* out, int64_t U, int64_t Cn, int64_t Kd, int64_t Kx, int64_t H, int64_t C, fn_stream_t stream) {
+    return pairf_grid<300>("fn_dta_pair_factored_grid_f32", drug, xt, W1, b1, w2, b2, out, U, Cn, Kd, Kx, H, C, stream);
+}
+}  // extern "C"

@@ -22,7 +22,7 @@ from typing import Dict, List, Sequence
 
 import torch
 
-from .plan import CollatedBatch, mol_offsets
+from .plan import N_MOLS_KEY, CollatedBatch, batch_n_mols, mol_offsets
 
 _F32_EXACT = 1 << 24
 
@@ -117,10 +117,10 @@ def batch_to(batch: Dict[str, torch.Tensor], device) -> Dict[str, torch.Tensor]:
             out.offsets = out.offsets.to(device)
     if "edge_index_bonds_graph" not in out and "edge_index" in out and out["edge_index"].is_cuda:
         from . import ops
-        out["edge_index_bonds_graph"] = ops.bond_graph(out["edge_index"], out["batch"], int(out["y"].shape[0]))
+        out["edge_index_bonds_graph"] = ops.bond_graph(out["edge_index"], out["batch"], batch_n_mols(out))
     if "edge_index_fbonds" not in out and "frag_index" in out and out["frag_index"].is_cuda:
         from . import ops
-        eifb = ops.bond_graph(out["frag_index"], out["frag_batch"], int(out["y"].shape[0]), fragments=True)
+        eifb = ops.bond_graph(out["frag_index"], out["frag_batch"], batch_n_mols(out), fragments=True)
         out["edge_index_fbonds"] = eifb
         out["edge_attr_fbonds"] = out["node_features_fbonds"][eifb[0]] + out["node_features_fbonds"][eifb[1]]
     if "positions" in out and out["positions"].is_cuda and "edge_index_bonds_graph" in out:
@@ -131,7 +131,7 @@ def batch_to(batch: Dict[str, torch.Tensor], device) -> Dict[str, torch.Tensor]:
         if "bnd_lngth" not in out:
             m = getattr(out, "max_per_mol", None)
             out["bnd_lngth"], out["bnd_angl"], out["dh_angl"] = ops.pretrain_geometry(
-                out["positions"], out["edge_index"], out["batch"], int(out["y"].shape[0]),
+                out["positions"], out["edge_index"], out["batch"], batch_n_mols(out),
                 max_per_mol=(m["atom"], m["edge"]) if m else None)
     return out
 
@@ -167,3 +167,122 @@ def collate_fn_dta(data_list: List) -> Dict[str, torch.Tensor]:
 
 
 BATCH_KEYS_DTA = BATCH_KEYS_FT + ("protein",)
+
+
+# ------------------------------------------------------------------------------------ factored pair batches
+# A drug-response or drug-target table has many rows over few distinct drugs and second inputs.  A factored batch holds every distinct
+# input ONCE -- the molecule keys describe the U distinct drugs, ``gene_expr`` / ``protein`` the C distinct second inputs, both in order
+# of first occurrence -- and says which pair uses which: ``pair_drug`` [M], ``pair_second`` [M] (int64), ``y`` [M] in data_list order.
+# The models then run the encoder on U molecules, the tower on C rows and the factored pair head (ops.pair_head_factored).
+PAIR_DRUG_KEY, PAIR_SECOND_KEY = "pair_drug", "pair_second"
+PAIR_ORDER_KEYS = ("pair_drug_rowptr", "pair_drug_perm", "pair_second_rowptr", "pair_second_perm")      # int32: ops.pair_orderings
+PAIR_GRID_KEY = "_pair_grid"         # python bool: no pair lists, the models return every drug against every second input, [U, C]
+
+# every tensor _collate_common reads from a record
+_MOL_FIELDS = ("x_atoms", "n_frags", "node_features_bonds", "node_feautures_fbondg", "edge_index", "frag_index", "edge_index_bonds",
+               "edge_index_fbondg", "x_frags", "edge_attr", "cnx_attr", "atom_id_frag_id", "edge_attr_bonds", "edge_attr_fbondg", "positions")
+
+
+def _digest(tensors) -> bytes:
+    """A content key: dtype, shape and bytes of every tensor (None: absent).  ``smiles`` plays no part: synthetic records leave it empty."""
+    import hashlib
+    h = hashlib.blake2b(digest_size=16)
+    for t in tensors:
+        if t is None:
+            h.update(b"-;")
+            continue
+        t = t.detach().cpu().contiguous()
+        h.update(f"{t.dtype}{tuple(t.shape)};".encode())
+        h.update(t.reshape(-1).view(torch.uint8).numpy().tobytes() if t.numel() else b"")
+    return h.digest()
+
+
+def _first_occurrence(keys):
+    """(indices of the first occurrence of every distinct key, in order; for every key the position of its first occurrence in that list)"""
+    seen, first, which = {}, [], []
+    for i, k in enumerate(keys):
+        if k not in seen:
+            seen[k] = len(first)
+            first.append(i)
+        which.append(seen[k])
+    return first, torch.as_tensor(which, dtype=torch.long)
+
+
+def _orderings_host(pair_list: torch.Tensor, n_rows: int):
+    """ops.pair_orderings on the host: a stable sort of the pair list, so ascending pair index inside a row."""
+    perm = torch.sort(pair_list, stable=True)[1].to(torch.int32)
+    rowptr = torch.zeros(n_rows + 1, dtype=torch.int32)
+    rowptr[1:] = torch.cumsum(torch.bincount(pair_list, minlength=n_rows), 0)
+    return rowptr, perm
+
+
+def _check_tokens(protein, who):
+    if protein.numel() and (int(protein.min()) < 0 or int(protein.max()) >= DTA_VOCAB):
+        raise ValueError(f"{who}: protein tokens must lie in [0, {DTA_VOCAB - 1}] (got {int(protein.min())} .. {int(protein.max())})")
+
+
+def _collate_factored(data_list: List, field: str, key: str, who: str) -> Dict[str, torch.Tensor]:
+    if len(data_list) == 0:
+        raise ValueError(f"{who}: empty data_list")
+    rows = [getattr(d, field).view(1, -1).type(torch.long) for d in data_list]          # exactly what collate_fn_cdrp / _dta emit
+    first_d, pair_drug = _first_occurrence([_digest(getattr(d, f, None) for f in _MOL_FIELDS) for d in data_list])
+    first_s, pair_second = _first_occurrence([_digest((r,)) for r in rows])
+    out = _collate_common([data_list[i] for i in first_d])
+    out["y"] = torch.cat([d.y for d in data_list], dim=0).type(torch.float)
+    second = torch.cat([rows[i] for i in first_s], dim=0)
+    if key == "protein":
+        _check_tokens(second, who)
+    out[key] = second
+    out[PAIR_DRUG_KEY], out[PAIR_SECOND_KEY] = pair_drug, pair_second
+    for k, v in zip(PAIR_ORDER_KEYS, _orderings_host(pair_drug, len(first_d)) + _orderings_host(pair_second, len(first_s))):
+        out[k] = v
+    out[N_MOLS_KEY] = len(first_d)
+    return out
+
+
+def collate_fn_cdrp_factored(data_list: List) -> Dict[str, torch.Tensor]:
+    """``collate_fn_cdrp`` without the copies: the molecule keys hold the U DISTINCT drugs of ``data_list`` and ``gene_expr`` [C, gene_dim]
+    its C distinct cell lines, each in order of first occurrence; ``pair_drug`` / ``pair_second`` [M] int64 say which pair uses which,
+    ``y`` [M] is in ``data_list`` order.  Distinct means different CONTENT: every tensor the collate reads from the record for a drug,
+    the int64 row as ``collate_fn_cdrp`` emits it (after the truncating cast) for a cell line; ``smiles`` is not looked at.  Also carried:
+    the pair orderings of the head's backward (``PAIR_ORDER_KEYS``) and the molecule count (``plan.N_MOLS_KEY``: ``y`` has M entries)."""
+    return _collate_factored(data_list, "gene_expr", "gene_expr", "collate_fn_cdrp_factored")
+
+
+def collate_fn_dta_factored(data_list: List) -> Dict[str, torch.Tensor]:
+    """``collate_fn_dta`` without the copies (``collate_fn_cdrp_factored``): ``protein`` [C, length] holds the distinct token rows.  A token
+    outside [0, 25] raises ValueError, as in ``collate_fn_dta``."""
+    return _collate_factored(data_list, "protein", "protein", "collate_fn_dta_factored")
+
+
+def pair_grid_batch(drug_records: List, second_rows, kind: str) -> Dict[str, torch.Tensor]:
+    """A screening batch: U drug records and C second inputs (``kind`` "cdrp": gene-expression rows, "dta": token rows; a [C, n] tensor or
+    a list of rows), no pair lists and no ``y``.  ``CDRPModel`` / ``DTAModel2`` return [U, C] for it: every drug against every second input."""
+    if kind not in ("cdrp", "dta"):
+        raise ValueError(f"pair_grid_batch: kind must be 'cdrp' or 'dta' (got {kind!r})")
+    out = _collate_common(list(drug_records))
+    if torch.is_tensor(second_rows) and second_rows.dim() == 2:
+        second = second_rows.type(torch.long)
+    else:
+        second = torch.cat([torch.as_tensor(r).view(1, -1) for r in second_rows], dim=0).type(torch.long)
+    if kind == "dta":
+        _check_tokens(second, "pair_grid_batch")
+    out["gene_expr" if kind == "cdrp" else "protein"] = second
+    out[PAIR_GRID_KEY] = True
+    out[N_MOLS_KEY] = len(drug_records)
+    return out
+
+
+def as_factored(batch: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
+    """An already collated pair batch (``collate_fn_cdrp`` / ``collate_fn_dta``: one molecule and one second row per pair) with the
+    identity pair lists, so that the models take the factored path on it.  The tensors are shared, not copied."""
+    M = int(batch["y"].shape[0])
+    dev = batch["y"].device
+    out = batch.like(dict(batch)) if isinstance(batch, CollatedBatch) else dict(batch)
+    out[PAIR_DRUG_KEY] = torch.arange(M, dtype=torch.long, device=dev)
+    out[PAIR_SECOND_KEY] = torch.arange(M, dtype=torch.long, device=dev)
+    rowptr, perm = torch.arange(M + 1, dtype=torch.int32, device=dev), torch.arange(M, dtype=torch.int32, device=dev)
+    for k, v in zip(PAIR_ORDER_KEYS, (rowptr, perm, rowptr, perm)):
+        out[k] = v
+    out[N_MOLS_KEY] = M
+    return out

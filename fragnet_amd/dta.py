@@ -16,7 +16,8 @@ from __future__ import annotations
 import torch.nn as nn
 
 from . import ops
-from .cdrp import FragNetFineTuneBase  # noqa: F401  (finetune_dta.py:64-105 defines the same class)
+from .cdrp import FragNetFineTuneBase, pair_orderings_of  # noqa: F401  (finetune_dta.py:64-105 defines the same class)
+from .data import PAIR_DRUG_KEY, PAIR_GRID_KEY, PAIR_SECOND_KEY
 
 
 class DTAModel2(nn.Module):
@@ -42,10 +43,17 @@ class DTAModel2(nn.Module):
 
     def forward(self, batch, loss=None):
         """``loss = (_lib.LOSS_MSE, y, None)``: the fused-loss call of a training step (``ops.pair_head_dta``); returns ``(out, loss)``,
-        ``loss`` None where the fused launch does not apply."""
+        ``loss`` None where the fused launch does not apply.  A factored batch (``data.collate_fn_dta_factored``, ``data.as_factored``)
+        runs the encoder on its U distinct drugs, the tower on its C distinct proteins and ``ops.pair_head_dta_factored``: [M, 1] in pair
+        order.  A grid batch (``data.pair_grid_batch``) returns every drug against every protein, [U, C]."""
         drug_enc = self.drug_model(batch)
         tokens = batch["protein"].reshape(-1, self.in_channels)
         xt = ops.protein_tower(tokens, self.embedding_xt, self.conv_xt_1, self.fc1_xt)
+        if batch.get(PAIR_GRID_KEY):
+            return ops.pair_head_dta_grid(drug_enc, xt, self.fc1, self.fc2)
+        if PAIR_DRUG_KEY in batch:
+            return ops.pair_head_dta_factored(drug_enc, xt, batch[PAIR_DRUG_KEY], batch[PAIR_SECOND_KEY], self.fc1, self.fc2, loss=loss,
+                                              orderings=pair_orderings_of(batch), check=False)
         return ops.pair_head_dta(drug_enc, xt, self.fc1, self.fc2, loss=loss)
 
 

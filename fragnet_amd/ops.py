@@ -1589,6 +1589,172 @@ def pair_head_dta(drug_enc, xt, fc1, fc2, loss=None):
 
 
 # ======================================================================================
+# the two pair heads on a factored batch: U distinct drugs, C distinct second inputs, pair lists; csrc/pair_factored.hip
+# ======================================================================================
+def pair_orderings(pair_list: torch.Tensor, n_rows: int):
+    """``(rowptr int32 [n_rows + 1], perm int32 [M])`` of ``pair_list`` [M]: ``perm[rowptr[r] : rowptr[r + 1]]`` are the pairs of row r
+    in ascending order (a stable sort of the list).  Values outside ``[0, n_rows)`` belong to no row.  Plain torch ops on the list's
+    device, no synchronisation; ``data.collate_fn_*_factored`` builds the same on the host and carries them in the batch."""
+    pl = pair_list.reshape(-1).to(torch.int64)
+    inside = (pl >= 0) & (pl < n_rows)
+    key = torch.where(inside, pl, torch.full_like(pl, n_rows))
+    perm = torch.sort(key, stable=True)[1].to(torch.int32)
+    counts = torch.bincount(key, minlength=n_rows + 1)[:n_rows]
+    rowptr = torch.zeros(n_rows + 1, dtype=torch.int32, device=pl.device)
+    rowptr[1:] = torch.cumsum(counts, 0)
+    return rowptr, perm
+
+
+def _i32c(t: torch.Tensor, name: str, numel: int) -> torch.Tensor:
+    if not t.is_cuda or t.dtype != torch.int32 or t.numel() != numel:
+        raise ValueError(f"{name}: expected {numel} int32 entries on the GPU (ops.pair_orderings), got {tuple(t.shape)} {t.dtype} on {t.device}")
+    return t if t.is_contiguous() else t.contiguous()
+
+
+class _PairHeadFactored(torch.autograd.Function):
+    """``_PairHead`` on U distinct drug rows, C distinct second rows and the pair lists: <prefix>_factored_fwd_f32 saves A = D W1d^T
+    [U,128] and B = S W1s^T [C,128] in place of ``h`` [M,128] and writes out [M,1]; <prefix>_factored_bwd_f32 folds the per-pair gradient
+    over the pair orderings, so both input gradients come back per DISTINCT row.  The fused-loss contract, the ``_fn_relu_gated`` tag and
+    the gate are ``_PairHead``'s."""
+
+    @staticmethod
+    def forward(ctx, inst, drug, x1, pd, ps, orderings, target, W1, b1, w2, b2):
+        drug, x1 = _f32c(drug, "drug_enc"), _f32c(x1, inst.second)
+        W1, b1, w2, b2 = (_f32c(q, "pair-head parameter") for q in (W1, b1, w2, b2))
+        (U, Kd), (C_, K1), M, dev = drug.shape, x1.shape, pd.numel(), drug.device
+        H, C_out = W1.shape[0], w2.shape[0]
+        st = _stream_ptr(dev)
+        A = torch.empty((U, H), dtype=torch.float32, device=dev)
+        B = torch.empty((C_, H), dtype=torch.float32, device=dev)
+        ws = torch.empty(getattr(_lib.load(), inst.prefix + "_factored_ws")(U, C_), dtype=torch.float32, device=dev)
+        out = torch.empty((M, C_out), dtype=torch.float32, device=dev)
+        g = parts = loss_t = None
+        if target is not None:
+            target = _f32c(target, "y").reshape(-1)
+            if target.numel() != M * C_out:
+                raise ValueError(f"{inst.name}_factored: {target.numel()} targets for {M} pairs")
+            g = torch.empty(M, dtype=torch.float32, device=dev)
+            parts = torch.empty(1, dtype=torch.float32, device=dev)
+            loss_t = torch.empty((), dtype=torch.float32, device=dev)
+        _lib.call(inst.prefix + "_factored_fwd_f32", drug.data_ptr(), x1.data_ptr(), pd.data_ptr(), ps.data_ptr(), W1.data_ptr(), b1.data_ptr(),
+                  w2.data_ptr(), b2.data_ptr(), _ptr(target), A.data_ptr(), B.data_ptr(), ws.data_ptr(), out.data_ptr(), _ptr(g), _ptr(parts),
+                  M, U, C_, Kd, K1, H, C_out, st)
+        ctx.inst, ctx.params, ctx.slots = inst, (W1, b1, w2, b2), [grad_slot(q) for q in (W1, b1, w2, b2)]
+        ctx.M, ctx.fused = M, target is not None
+        if ctx.fused:
+            ctx.save_for_backward(drug, x1, A, B, *orderings, g, parts, loss_t)
+            ctx.mark_non_differentiable(out)
+            ctx.set_materialize_grads(False)
+            return out, loss_t
+        ctx.save_for_backward(drug, x1, A, B, *orderings)
+        return out
+
+    @staticmethod
+    def backward(ctx, g_out, g_loss=None):
+        drug, x1, A, B, rp_d, pm_d, rp_s, pm_s = ctx.saved_tensors[:8]
+        dev = drug.device
+        parts = loss_t = None
+        if ctx.fused:
+            g, parts, loss_t = ctx.saved_tensors[8:]
+            if g_loss is not None and not _is_unit_grad(g_loss):
+                g = g * g_loss
+        else:
+            g = _f32c(g_out, "g").reshape(-1)
+        P, slots = ctx.params, ctx.slots
+        dW1, db1, dW2, db2 = (grad_buffer(q, s) for q, s in zip(P, slots))
+        g_drug, g_x1 = torch.empty_like(drug), torch.empty_like(x1)
+        _lib.call(ctx.inst.prefix + "_factored_bwd_f32", g.data_ptr(), drug.data_ptr(), x1.data_ptr(), A.data_ptr(), B.data_ptr(), P[0].data_ptr(),
+                  P[1].data_ptr(), P[2].data_ptr(), rp_d.data_ptr(), pm_d.data_ptr(), rp_s.data_ptr(), pm_s.data_ptr(), g_drug.data_ptr(),
+                  g_x1.data_ptr(), dW1.data_ptr(), db1.data_ptr(), dW2.data_ptr(), db2.data_ptr(), _ptr(parts),
+                  0 if parts is None else parts.numel(), _ptr(loss_t), ctx.M, drug.shape[0], x1.shape[0], drug.shape[1], x1.shape[1],
+                  P[0].shape[0], P[2].shape[0], _stream_ptr(dev))
+        if ctx.inst.gated:
+            g_x1._fn_relu_gated = x1
+        return (None, g_drug if ctx.needs_input_grad[1] else None, g_x1 if ctx.needs_input_grad[2] else None, None, None, None, None,
+                dW1, db1, dW2, db2)
+
+
+def _pair_widths_ok(inst, drug_enc, x1, fc1, fc2) -> bool:
+    return (tuple(fc1.weight.shape), tuple(fc2.weight.shape)) == inst.shapes and fc1.bias is not None and fc2.bias is not None \
+        and drug_enc.dim() == 2 and x1.dim() == 2 and drug_enc.shape[1] == FN_D * 2 and x1.shape[1] == inst.width
+
+
+def _pair_head_factored(inst, drug_enc, x1, pair_drug, pair_second, fc1, fc2, loss, orderings, check):
+    name = inst.name + "_factored"
+    if not (drug_enc.is_cuda and x1.is_cuda and pair_drug.is_cuda and pair_second.is_cuda):
+        raise _lib.FragnetHipError(f"{name}: fragnet_amd kernels need GPU tensors; there is no CPU fallback")
+    if pair_drug.dtype != torch.int64 or pair_second.dtype != torch.int64 or pair_drug.dim() != 1 or pair_drug.shape != pair_second.shape:
+        raise TypeError(f"{name}: the pair lists are two int64 vectors of one length")
+    pd, ps = pair_drug.contiguous(), pair_second.contiguous()
+    U, C_, M = drug_enc.shape[0], x1.shape[0], pd.numel()
+    if check and M:          # one synchronisation; check=False: the caller built the lists on the host and has checked them there
+        lo_hi = torch.stack((pd.min(), pd.max(), ps.min(), ps.max())).tolist()
+        if lo_hi[0] < 0 or lo_hi[1] >= U or lo_hi[2] < 0 or lo_hi[3] >= C_:
+            raise IndexError(f"{name}: pair lists reach outside the {U} drug rows / {C_} {inst.second} rows")
+    ok = _pair_widths_ok(inst, drug_enc, x1, fc1, fc2) and max(U, C_, M) <= DENSE_MAX_ROWS and (M == 0 or (U > 0 and C_ > 0))
+    if not ok:
+        out = fc2(fc1(torch.cat((drug_enc[pd], x1[ps]), 1)))
+        return (out, None) if loss is not None else out
+    if orderings is None:
+        orderings = pair_orderings(pd, U) + pair_orderings(ps, C_)
+    orderings = tuple(_i32c(t, f"{name}: pair ordering", n) for t, n in zip(orderings, (U + 1, M, C_ + 1, M)))
+    params = (fc1.weight, fc1.bias, fc2.weight, fc2.bias)
+    if loss is None:
+        return _PairHeadFactored.apply(inst, drug_enc, x1, pd, ps, orderings, None, *params)
+    kind, y, row_w = loss
+    fuse = FUSED_HEAD_LOSS and kind == _lib.LOSS_MSE and row_w is None and torch.is_grad_enabled() and M > 0 \
+        and (drug_enc.requires_grad or x1.requires_grad or any(q.requires_grad for q in params))
+    if not fuse:
+        return _PairHeadFactored.apply(inst, drug_enc, x1, pd, ps, orderings, None, *params), None
+    return _PairHeadFactored.apply(inst, drug_enc, x1, pd, ps, orderings, y, *params)
+
+
+def pair_head_factored(drug_enc, cell_enc, pair_drug, pair_second, fc1, fc2, loss=None, orderings=None, check: bool = True):
+    """``pair_head`` on a factored batch: ``out[m] = fc2(fc1(cat(drug_enc[pair_drug[m]], cell_enc[pair_second[m]])))`` [M, 1] from the U
+    distinct rows of ``drug_enc``, the C distinct rows of ``cell_enc`` (the output of a ReLU: its gradient comes back gated) and the two
+    int64 pair lists -- no duplicated row is ever built.  ``loss`` as for ``pair_head`` (the mean is over the M pairs).  ``orderings``:
+    ``pair_orderings`` of both lists (drug's, then the second's), built here when None.  ``check=True`` validates the pair lists' range
+    on the host (one synchronisation; the kernels skip an outside pair instead of indexing with it); ``check=False``: the caller built
+    them on the host and has checked them there.  Other widths, or more than ``DENSE_MAX_ROWS`` rows or pairs, fall back to plain torch
+    ops on the gathered rows."""
+    return _pair_head_factored(_PAIR_CDRP, drug_enc, cell_enc, pair_drug, pair_second, fc1, fc2, loss, orderings, check)
+
+
+def pair_head_dta_factored(drug_enc, xt, pair_drug, pair_second, fc1, fc2, loss=None, orderings=None, check: bool = True):
+    """``pair_head_dta`` on a factored batch (``pair_head_factored``; ``xt``'s gradient is not gated)."""
+    return _pair_head_factored(_PAIR_DTA, drug_enc, xt, pair_drug, pair_second, fc1, fc2, loss, orderings, check)
+
+
+def _pair_head_grid(inst, drug_enc, x1, fc1, fc2):
+    name = inst.name + "_grid"
+    if not (drug_enc.is_cuda and x1.is_cuda):
+        raise _lib.FragnetHipError(f"{name}: fragnet_amd kernels need GPU tensors; there is no CPU fallback")
+    U, C_ = drug_enc.shape[0], x1.shape[0]
+    if not (_pair_widths_ok(inst, drug_enc, x1, fc1, fc2) and max(U, C_) <= DENSE_MAX_ROWS):
+        pd = torch.arange(U, device=drug_enc.device).repeat_interleave(C_)
+        ps = torch.arange(C_, device=drug_enc.device).repeat(U)
+        return fc2(fc1(torch.cat((drug_enc[pd], x1[ps]), 1))).view(U, C_)
+    drug, x = _f32c(drug_enc.detach(), "drug_enc"), _f32c(x1.detach(), inst.second)
+    W1, b1, w2, b2 = (_f32c(q.detach(), "pair-head parameter") for q in (fc1.weight, fc1.bias, fc2.weight, fc2.bias))
+    out = torch.empty((U, C_), dtype=torch.float32, device=drug.device)
+    _lib.call(inst.prefix + "_factored_grid_f32", drug.data_ptr(), x.data_ptr(), W1.data_ptr(), b1.data_ptr(), w2.data_ptr(), b2.data_ptr(),
+              out.data_ptr(), U, C_, drug.shape[1], x.shape[1], W1.shape[0], w2.shape[0], _stream_ptr(drug.device))
+    return out
+
+
+def pair_head_grid(drug_enc, cell_enc, fc1, fc2):
+    """Every drug against every cell line: ``out[u, c] = fc2(fc1(cat(drug_enc[u], cell_enc[c])))`` [U, C] in one launch
+    (fn_cdrp_pair_factored_grid_f32).  An evaluation read-out: no autograd node.  Other widths or more than ``DENSE_MAX_ROWS`` rows on
+    a side: plain torch ops."""
+    return _pair_head_grid(_PAIR_CDRP, drug_enc, cell_enc, fc1, fc2)
+
+
+def pair_head_dta_grid(drug_enc, xt, fc1, fc2):
+    """``pair_head_grid`` for the drug-target-affinity head (fn_dta_pair_factored_grid_f32)."""
+    return _pair_head_grid(_PAIR_DTA, drug_enc, xt, fc1, fc2)
+
+
+# ======================================================================================
 # graph-convolution baseline (reference model/gcn/gcn2.py, model_version gcn2): the degree-normalised neighbour sum, csrc/gcn.hip, and the
 # fragment MLP on the dense kernels
 # ======================================================================================

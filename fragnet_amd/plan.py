@@ -244,7 +244,7 @@ class GraphPlan:
         F = batch["x_frags"].shape[0]
         EF = batch["node_features_fbonds"].shape[0]
         if n_mols is None:
-            n_mols = batch["y"].shape[0] if "y" in batch else int(batch["batch"].max()) + 1
+            n_mols = batch_n_mols(batch)
         ei, fi = batch["edge_index"], batch["frag_index"]
         eib, eifb = batch["edge_index_bonds_graph"], batch["edge_index_fbonds"]
         if ei.shape[1] != E:
@@ -297,7 +297,7 @@ class GraphPlan:
     def for_gcn(cls, batch: Dict[str, torch.Tensor], n_mols: Optional[int] = None):
         """The reduced plan of model_version gcn2 (``gcn_specs``), built by the general builder (fn_plan_build)."""
         if n_mols is None:
-            n_mols = batch["y"].shape[0] if "y" in batch else int(batch["batch"].max()) + 1
+            n_mols = batch_n_mols(batch)
         plan = cls(cls.gcn_specs(batch, n_mols), batch["x_atoms"].device)
         plan.n_mols = n_mols
         plan.mol_contiguous = bool(getattr(batch, "mol_contiguous", False))
@@ -376,6 +376,15 @@ def mol_offsets(counts: Dict[str, "torch.Tensor"]) -> "torch.Tensor":
 PLAN_KEY = "_fragnet_plan"
 REAL_MOLS_KEY = "_real_mols"      # StaticBatch: device-side count of the real molecules of a padded batch
 LIVE_MOLS_KEY = "_live_mols"      # StaticBatch: python int, molecule rows >= this are padding in EVERY batch (capacity - slack)
+N_MOLS_KEY = "_n_mols"            # factored pair batches (data.collate_fn_*_factored): python int, the molecule count -- y has one entry per PAIR there
+
+
+def batch_n_mols(batch) -> int:
+    """The molecule count of a batch dict: what the batch carries (``N_MOLS_KEY``), else one per entry of ``y``, else (a host
+    synchronisation) the largest molecule id."""
+    if N_MOLS_KEY in batch:
+        return int(batch[N_MOLS_KEY])
+    return batch["y"].shape[0] if "y" in batch else int(batch["batch"].max()) + 1
 
 
 def plan_for(batch: Dict[str, torch.Tensor], edge_ends: bool = False) -> GraphPlan:

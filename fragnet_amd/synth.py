@@ -355,6 +355,46 @@ def attach_protein(mols: List[MolRecord], seed: int, length: int = 1000, pinned=
     return mols
 
 
+def pair_records(n_pairs: int, n_drugs: int, n_seconds: int, kind: str, seed: int, gene_dim: int = 903, length: int = 1000) -> List[MolRecord]:
+    """``n_pairs`` (drug, second input, y) records over exactly ``n_drugs`` distinct drugs and ``n_seconds`` distinct second inputs
+    (``kind`` "cdrp": ``gene_expr`` rows that stay distinct after collate_fn_cdrp's truncating cast; "dta": ``protein`` token rows) -- the
+    shape of a real drug-response or drug-target table, as the reference's dataset/cdrp.py builds it: one record per table row, so a
+    repeated drug is a deep COPY with equal content, not a shared object.  Every drug and every second input occurs at least once;
+    ``y`` is a pair effect, a drug effect plus a second-input effect plus noise."""
+    import copy
+    if kind not in ("cdrp", "dta"):
+        raise ValueError(f"pair_records: kind must be 'cdrp' or 'dta' (got {kind!r})")
+    if min(n_drugs, n_seconds) < 1 or n_pairs < max(n_drugs, n_seconds):
+        raise ValueError("pair_records: n_pairs >= max(n_drugs, n_seconds) >= 1, so that every input can occur")
+    rng = np.random.default_rng(seed)
+    drugs = synth_molecules(n_drugs, seed=seed + 1, profile="esol")
+    holders = [copy.deepcopy(drugs[0]) for _ in range(n_seconds)]
+    field = "gene_expr" if kind == "cdrp" else "protein"
+    for attempt in range(64):          # distinct AFTER the int64 cast: redraw in the (vanishingly rare) event of a collision
+        if kind == "cdrp":
+            attach_gene_expr(holders, gene_dim, seed + 2 + attempt)
+        else:
+            attach_protein(holders, seed + 2 + attempt, length=length)
+        rows = {tuple(getattr(h, field).type(torch.long).tolist()) for h in holders}
+        if len(rows) == n_seconds:
+            break
+    else:
+        raise RuntimeError("pair_records: could not draw distinct second inputs")
+    seconds = [getattr(h, field) for h in holders]
+    # every input once, then uniform draws; shuffled so that first occurrences are not in index order
+    du = np.concatenate([np.arange(n_drugs), rng.integers(0, n_drugs, size=n_pairs - n_drugs)])
+    sc = np.concatenate([np.arange(n_seconds), rng.integers(0, n_seconds, size=n_pairs - n_seconds)])
+    du, sc = rng.permutation(du), rng.permutation(sc)
+    e_d, e_s = rng.normal(0.0, 1.0, size=n_drugs), rng.normal(0.0, 1.0, size=n_seconds)
+    out = []
+    for u, c in zip(du, sc):
+        rec = copy.deepcopy(drugs[int(u)])
+        setattr(rec, field, seconds[int(c)].clone())
+        rec.y = torch.tensor([e_d[u] + e_s[c] + 0.1 * rng.normal()], dtype=torch.float32).reshape(drugs[0].y.shape)
+        out.append(rec)
+    return out
+
+
 # ----------------------------------------------------------------------------------------
 # Geometry from one conformer: the bond-graph edge attribute and the three pretraining targets as the reference's featuriser derives
 # them (dataset/data.py:185-211 get_edge_attr_bond_graph, :224-260 get_bond_angle_dhangle), restated from their definitions:

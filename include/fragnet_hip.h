@@ -1037,6 +1037,51 @@ int fn_dta_pair_bwd_f32(const float* g, const float* drug, const float* xt, cons
                         int64_t n_part, float* loss /*nullable*/, int64_t M, int64_t Kd, int64_t Kx, int64_t H, int64_t C, fn_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * The pair head on a FACTORED batch; csrc/pair_factored.hip.  Entry points added under ABI 12 (nothing existing changes).  U distinct
+ * drug rows drug[U,256], Cn distinct second rows second[Cn,K1] and the pair lists pair_drug[M], pair_second[M] (int64) stand for the M
+ * duplicated rows of fn_*_pair_fwd_f32: out[m] = fc2(fc1(cat(drug[pair_drug[m]], second[pair_second[m]]))).  With W1 = [W1d | W1s]:
+ *   fn_*_pair_factored_fwd_f32   A[U,H] = drug W1d^T and B[Cn,H] = second W1s^T (no bias; saved for the backward), alpha = A w2,
+ *                          beta = B w2 (ws), out[m] = alpha[pair_drug[m]] + beta[pair_second[m]] + (b1 . w2 + b2) and, with a target,
+ *                          g[m] = 2 (out[m] - target[m]) / M and loss_part[0] = mean((out - target)^2).  One launch behind a 4-byte
+ *                          memset of the arrival counter in ws (fn_*_pair_factored_ws(U, Cn) floats).  M = 0: nothing is written.
+ *   fn_*_pair_factored_bwd_f32   from g[M] and the pair orderings (per side rowptr[n + 1] and perm[M], int32: perm[rowptr[r] ..
+ *                          rowptr[r + 1]) = the pairs of row r, ascending -- a stable sort of the pair list): g_drug[U,256] =
+ *                          sd[u] v_d, g_second[Cn,K1] = ss[c] v_s (v = W1^T w2; sd, ss the sums of g over a row's pairs; the cdrp
+ *                          instance zeroes g_second where second <= 0), dW1, db1, dW2, db2 and, with loss, loss[0] = the sum of
+ *                          loss_part[n_part].  One launch.  A row no pair refers to gets exactly zero; M = 0 writes zeros everywhere.
+ *   fn_*_pair_factored_grid_f32  out[U,Cn]: out[u,c] = the forward's value for the pair (u, c).  One launch, no backward.
+ * Built for the widths of fn_cdrp_pair_* (K1 = 256, gated) and fn_dta_pair_* (K1 = 300, not gated) only: others FN_EUNSUPPORTED.  M, U,
+ * Cn in [0, FN_DENSE_MAX_ROWS] (M > 0 needs U, Cn >= 1), else FN_EINVAL; both decided before anything is written.  No float atomics,
+ * every sum in a fixed order: results are reproducible bit for bit.  A pair-list or ordering value is range-tested before it is used as
+ * an index: a pair outside [0,U) x [0,Cn) gets out = 0, g = 0 and contributes to nothing.  drug, second, A, B, W1, g_drug, g_second,
+ * dW1: 16-byte aligned.
+ * ------------------------------------------------------------------------------------------ */
+int64_t fn_cdrp_pair_factored_ws(int64_t U, int64_t Cn);
+int fn_cdrp_pair_factored_fwd_f32(const float* drug, const float* cell, const int64_t* pair_drug, const int64_t* pair_cell, const float* W1,
+                                  const float* b1, const float* w2, const float* b2, const float* target /*nullable*/, float* A, float* B,
+                                  float* ws, float* out, float* g /*nullable without target*/, float* loss_part /*nullable without target*/,
+                                  int64_t M, int64_t U, int64_t Cn, int64_t Kd, int64_t Kc, int64_t H, int64_t C, fn_stream_t stream);
+int fn_cdrp_pair_factored_bwd_f32(const float* g, const float* drug, const float* cell, const float* A, const float* B, const float* W1,
+                                  const float* b1, const float* w2, const int32_t* rowptr_drug, const int32_t* perm_drug,
+                                  const int32_t* rowptr_cell, const int32_t* perm_cell, float* g_drug, float* g_cell, float* dW1, float* db1,
+                                  float* dW2, float* db2, const float* loss_part /*nullable*/, int64_t n_part, float* loss /*nullable*/,
+                                  int64_t M, int64_t U, int64_t Cn, int64_t Kd, int64_t Kc, int64_t H, int64_t C, fn_stream_t stream);
+int fn_cdrp_pair_factored_grid_f32(const float* drug, const float* cell, const float* W1, const float* b1, const float* w2, const float* b2,
+                                   float* out, int64_t U, int64_t Cn, int64_t Kd, int64_t Kc, int64_t H, int64_t C, fn_stream_t stream);
+int64_t fn_dta_pair_factored_ws(int64_t U, int64_t Cn);
+int fn_dta_pair_factored_fwd_f32(const float* drug, const float* xt, const int64_t* pair_drug, const int64_t* pair_prot, const float* W1,
+                                 const float* b1, const float* w2, const float* b2, const float* target /*nullable*/, float* A, float* B,
+                                 float* ws, float* out, float* g /*nullable without target*/, float* loss_part /*nullable without target*/,
+                                 int64_t M, int64_t U, int64_t Cn, int64_t Kd, int64_t Kx, int64_t H, int64_t C, fn_stream_t stream);
+int fn_dta_pair_factored_bwd_f32(const float* g, const float* drug, const float* xt, const float* A, const float* B, const float* W1,
+                                 const float* b1, const float* w2, const int32_t* rowptr_drug, const int32_t* perm_drug,
+                                 const int32_t* rowptr_prot, const int32_t* perm_prot, float* g_drug, float* g_xt, float* dW1, float* db1,
+                                 float* dW2, float* db2, const float* loss_part /*nullable*/, int64_t n_part, float* loss /*nullable*/,
+                                 int64_t M, int64_t U, int64_t Cn, int64_t Kd, int64_t Kx, int64_t H, int64_t C, fn_stream_t stream);
+int fn_dta_pair_factored_grid_f32(const float* drug, const float* xt, const float* W1, const float* b1, const float* w2, const float* b2,
+                                  float* out, int64_t U, int64_t Cn, int64_t Kd, int64_t Kx, int64_t H, int64_t C, fn_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Graph-convolution baseline, model_version gcn2 (reference model/gcn/gcn2.py:48-65); csrc/gcn.hip.  Entry points added under ABI 12
  * (nothing existing changes).  The aggregate is a degree-normalised neighbour sum over one of a level's two CSRs:
  *     y[i] = c[i] * sum over the items k of row i, in plan order, of c[nbr(k)] * x[nbr(k)]

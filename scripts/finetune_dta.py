@@ -67,9 +67,12 @@ if __name__ == "__main__":
         print("loaded pretrained encoder", pt.chkpoint_name)
     model.to(device)
     sets = {k: load_pickle_dataset(ft[k].path) for k in ("train", "val", "test")}
-    train_loader = _OnDevice(DataLoader(sets["train"], collate_fn=data.collate_fn_dta, batch_size=ft.batch_size, shuffle=True, drop_last=True), device)
-    val_loader = _OnDevice(DataLoader(sets["val"], collate_fn=data.collate_fn_dta, batch_size=64, shuffle=False), device)
-    test_loader = _OnDevice(DataLoader(sets["test"], collate_fn=data.collate_fn_dta, batch_size=64, shuffle=False), device)
+    # finetune.factored_pairs: true -- every distinct drug and second input of a batch goes through its encoder once
+    # (data.collate_fn_dta_factored); with drop_ratio > 0 a training step then draws one dropout mask per distinct drug, not per pair
+    collate = data.collate_fn_dta_factored if ft.get("factored_pairs") else data.collate_fn_dta
+    train_loader = _OnDevice(DataLoader(sets["train"], collate_fn=collate, batch_size=ft.batch_size, shuffle=True, drop_last=True), device)
+    val_loader = _OnDevice(DataLoader(sets["val"], collate_fn=collate, batch_size=64, shuffle=False), device)
+    test_loader = _OnDevice(DataLoader(sets["test"], collate_fn=collate, batch_size=64, shuffle=False), device)
     trainer = train.TrainerFineTuneDTA(target_type=ft.target_type)
     labels = np.array([float(r.y) for r in sets["train"]])
     stats = dict(label_mean=float(labels.mean()), label_sdev=float(labels.std()))

@@ -17,10 +17,15 @@ ap.add_argument("--out", required=True, help="output directory")
 ap.add_argument("--gene-dim", type=int, default=903)
 ap.add_argument("--n", type=int, nargs=3, default=[512, 64, 64], metavar=("TRAIN", "VAL", "TEST"))
 ap.add_argument("--seed", type=int, default=0)
+ap.add_argument("--drugs", type=int, default=0, help="distinct drugs per split (0: every record its own, the default)")
+ap.add_argument("--cells", type=int, default=0, help="distinct cell lines per split (0: every record its own, the default)")
 args = ap.parse_args()
 os.makedirs(args.out, exist_ok=True)
 for split, n, s in zip(("train", "val", "test"), args.n, (0, 1, 2)):
-    mols = synth.attach_gene_expr(synth.synth_molecules(n, seed=args.seed * 3 + s, profile="esol"), args.gene_dim, args.seed * 3 + s + 100)
+    if args.drugs or args.cells:      # a table of (drug, cell line, y) rows over few distinct entities (synth.pair_records)
+        mols = synth.pair_records(n, min(n, args.drugs or n), min(n, args.cells or n), "cdrp", args.seed * 3 + s, gene_dim=args.gene_dim)
+    else:
+        mols = synth.attach_gene_expr(synth.synth_molecules(n, seed=args.seed * 3 + s, profile="esol"), args.gene_dim, args.seed * 3 + s + 100)
     path = os.path.join(args.out, f"{split}.pkl")
     with open(path, "wb") as f:
         pickle.dump(mols, f)

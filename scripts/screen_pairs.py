@@ -1,0 +1,83 @@
+#!/usr/bin/env python3
+"""Screens every drug against every cell line (CDRP) or protein (DTA) with a trained pair model: the [U, C] matrix of predictions,
+computed from ONE encoder pass per drug and ONE tower pass per second input (data.pair_grid_batch, ops.pair_head_grid) instead of
+U x C pair records.
+
+    python scripts/screen_pairs.py --model cdrp --config exps/ft/cdrp_synth/config.yaml --checkpoint ft.pt \\
+        --drugs drugs.pkl --second cells.pkl --out grid.npz
+
+``--drugs``: a pickled list of per-molecule records (the finetune datasets' format; ``gene_expr`` / ``protein`` / ``y`` on them are not
+looked at).  ``--second``: a pickled list whose items are either rows (tensors / arrays: gene-expression vectors or token vectors) or
+records carrying ``gene_expr`` (cdrp) / ``protein`` (dta).  Works in chunks of at most ``--drug-chunk`` x ``--second-chunk`` (each within
+the kernels' row limit); a second input's tower pass is repeated once per drug chunk.  DTA predictions are de-normalised with
+``--label-mean`` / ``--label-sdev`` (the trainer's ``out * sdev + mean``; train_stats.pkl of the finetune run holds them).
+Writes ``grid`` float32 [U, C] and, where the records have them, ``smiles`` to ``--out`` (np.savez)."""
+import argparse
+import os
+import pickle
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import numpy as np
+import torch
+
+from fragnet_amd import data, ops, train
+from fragnet_amd.cdrp import CDRPModel, FragNetFineTuneBase
+from fragnet_amd.dataset import load_pickle_dataset
+from fragnet_amd.dta import DTAModel2
+
+
+def second_rows(items, field):
+    """[C, n] from a list of rows or of records carrying ``field``"""
+    rows = [getattr(it, field) if hasattr(it, field) else it for it in items]
+    return torch.cat([torch.as_tensor(np.asarray(r) if not torch.is_tensor(r) else r).reshape(1, -1) for r in rows], dim=0)
+
+
+def screen(model, kind, drugs, second, device, drug_chunk, second_chunk):
+    """The [U, C] prediction matrix, float32 on the host, chunk by chunk"""
+    if not (1 <= drug_chunk <= ops.DENSE_MAX_ROWS and 1 <= second_chunk <= ops.DENSE_MAX_ROWS):
+        raise ValueError(f"chunks must lie in [1, {ops.DENSE_MAX_ROWS}]")
+    out = torch.empty((len(drugs), second.shape[0]), dtype=torch.float32)
+    model.eval()
+    with torch.no_grad():
+        for u0 in range(0, len(drugs), drug_chunk):
+            for c0 in range(0, second.shape[0], second_chunk):
+                b = data.batch_to(data.pair_grid_batch(drugs[u0:u0 + drug_chunk], second[c0:c0 + second_chunk], kind), device)
+                out[u0:u0 + drug_chunk, c0:c0 + second_chunk] = model(b).cpu()
+    return out
+
+
+if __name__ == "__main__":
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--model", choices=("cdrp", "dta"), required=True)
+    ap.add_argument("--config", required=True)
+    ap.add_argument("--checkpoint", required=True, help="state_dict written by scripts/finetune_cdrp.py / finetune_dta.py")
+    ap.add_argument("--drugs", required=True)
+    ap.add_argument("--second", required=True)
+    ap.add_argument("--out", required=True)
+    ap.add_argument("--drug-chunk", type=int, default=1024)
+    ap.add_argument("--second-chunk", type=int, default=ops.DENSE_MAX_ROWS)
+    ap.add_argument("--label-mean", type=float, default=0.0)
+    ap.add_argument("--label-sdev", type=float, default=1.0)
+    cli = ap.parse_args()
+    args = train.load_config(cli.config, config=cli.config)
+    device = torch.device("cuda", 0)
+    torch.cuda.set_device(device)
+    m = args.finetune.model
+    gat2 = FragNetFineTuneBase(n_classes=m.n_classes, atom_features=args.atom_features, frag_features=args.frag_features,
+                               edge_features=args.edge_features, num_layer=m.num_layer, drop_ratio=m.drop_ratio, num_heads=m.num_heads,
+                               emb_dim=m.emb_dim, h1=m.h1, h2=m.h2, h3=m.h3, h4=m.h4, act=m.act, fthead=m.fthead)
+    model = CDRPModel(gat2, int(args.gene_dim), device) if cli.model == "cdrp" else DTAModel2(gat2)
+    model.load_state_dict(torch.load(cli.checkpoint, map_location="cpu"))
+    model.to(device)
+    drugs = list(load_pickle_dataset(cli.drugs))
+    with open(cli.second, "rb") as f:
+        second = second_rows(pickle.load(f), "gene_expr" if cli.model == "cdrp" else "protein")
+    grid = screen(model, cli.model, drugs, second, device, cli.drug_chunk, cli.second_chunk)
+    if cli.model == "dta":
+        grid = grid * cli.label_sdev + cli.label_mean
+    extra = {}
+    if all(getattr(r, "smiles", "") for r in drugs):
+        extra["smiles"] = np.asarray([r.smiles for r in drugs])
+    np.savez(cli.out, grid=grid.numpy(), **extra)
+    print(f"{cli.model}: {grid.shape[0]} drugs x {grid.shape[1]} second inputs -> {cli.out}")
