@@ -160,6 +160,7 @@ SIGNATURES = {
     "fn_abi_version": [],
     "fn_last_error": [],
     "fn_set_tuning": [C.c_int, C.c_int],
+    "fn_get_tuning": [C.c_int],
     "fn_debug_set_stamps": [vp, i64],
     "fn_debug_set_profile_events": [vp],
     "fn_plan_layout": [C.POINTER(CsrTask), C.c_int, C.POINTER(i64), C.POINTER(i64)],

@@ -665,6 +665,43 @@ int prof_event(int i, hipStream_t st) {
     return 0;
 }
 int g_tune[FN_TUNE_COUNT] = {1024, 0, 0, 192, 0, 0, 0, 1, 1, 0, 1792, 1536, 512, 512, 2, -1, 0, 1, 0, 0, 1, 23, 1, 768, 1, 0, 1, 1, 0, 0, 6144, 1, 1, 1, 1};   // in the order of the FN_TUNE_* keys
+// What fn_set_tuning accepts, in the order of the FN_TUNE_* keys (the ranges stated at the defines in the header).  A block-count key
+// is at least 1 and at most what the partial-sum buffers behind its launch hold (every block writes one row of them); the clamps at the
+// use sites stay, as the second line of defence of whoever calls a launcher with a table this function did not fill.
+struct TuneRange { const char* name; int lo, hi; };
+constexpr int kTuneAny = 0x7fffffff, kTuneBlocks = 1 << 20;
+constexpr TuneRange kRetired{"retired", -kTuneAny - 1, kTuneAny};
+constexpr TuneRange kTuneRange[FN_TUNE_COUNT] = {
+    {"FWD_BLOCKS", 1, kTuneBlocks},              //  0
+    {"GEMM_SLOTS", 0, kTuneBlocks},              //  1
+    kRetired,                                    //  2
+    {"WGRAD_BLOCKS", 1, kTuneBlocks},            //  3
+    kRetired, kRetired, kRetired,                //  4, 5, 6
+    {"FUSE_ROWDOTS", 0, 1},                      //  7
+    {"WGRAD_DIRECT", 0, 1},                      //  8
+    kRetired,                                    //  9
+    {"FWD_BLOCKS_EVAL", 1, kTuneBlocks},         // 10
+    {"DST_BLOCKS", 1, FN_MAX_PART},              // 11: a row of part_e per block
+    {"SRC_BLOCKS", 1, 1024},                     // 12: prep_gat_bwd_src's bound
+    {"RD_BLOCKS", 1, FN_MAX_PART},               // 13: the column stride of part_rd
+    {"GEMM_COLAUNCH", 0, 2},                     // 14
+    kRetired, kRetired, kRetired, kRetired, kRetired,      // 15 .. 19
+    {"MOL_TAIL", 0, 2},                          // 20
+    {"WGRAD0_ROWS", 1, 99},                      // 21: two decimal digits
+    {"BWD_ONE", 0, 1},                           // 22
+    {"ONE_BLOCKS", 1, FN_MAX_PART},              // 23: prep_gat_bwd_one's bound
+    {"PAD_SKIP", 0, 1},                          // 24
+    {"ONE_INTERLEAVE", 0, 1},                    // 25
+    {"ONE_TIER6", 0, 1},                         // 26
+    {"RIDER_PIECES", 1, 4096},                   // 27
+    {"RIDER_AT", 0, 1},                          // 28
+    kRetired,                                    // 29
+    {"FWD_BLOCKS_EVAL_LARGE", 0, kTuneBlocks},   // 30
+    {"FWD_TAIL_ROWS", 0, kTuneBlocks},           // 31
+    {"DENSE_TILES", 0, 1},                       // 32
+    {"ENGINE_CONST", 0, 1},                      // 33
+    {"COALITION_STAGED", 0, kTuneAny},           // 34
+};
 }  // namespace
 namespace fni {      // hooks for the other translation units (fn_internal.h)
 int fail(int code, const char* what) { return ::fail(code, what); }
@@ -794,10 +831,16 @@ int fn_debug_set_profile_events(void* const* events) {
 
 int fn_set_tuning(int key, int value) {
     if (key < 0 || key >= FN_TUNE_COUNT) return fail(FN_EINVAL, "fn_set_tuning: unknown key");
-    if (key == FN_TUNE_FWD_BLOCKS && value < 1) return fail(FN_EINVAL, "fn_set_tuning: block count must be positive");
+    const TuneRange& r = kTuneRange[key];
+    if (value < r.lo || value > r.hi) {
+        static thread_local char msg[160];
+        snprintf(msg, sizeof msg, "fn_set_tuning: key %d (%s) takes %d .. %d, not %d", key, r.name, r.lo, r.hi, value);
+        return fail(FN_EINVAL, msg);
+    }
     g_tune[key] = value;
     return 0;
 }
+int fn_get_tuning(int key) { return fni::tune(key); }
 const char* fn_last_error(void) { return tl_err; }
 
 

@@ -50,36 +50,38 @@ int fn_abi_version(void);
  *   dropout epilogue, source pass of the backward): default 1024 = 256 CUs x 4 (768 until round 5's re-sweep of the launch
  *   shapes, profiles/r05_launch_shape_sweep.txt); a level with more row groups than that gives
  *   every half-wave several consecutive rows to software-pipeline (4 at ESOL batch 512).  FN_TUNE_FWD_BLOCKS_EVAL (1792 =
- *   256 x 7) is the same for the plain forward (inference, or training without dropout). */
+ *   256 x 7) is the same for the plain forward (inference, or training without dropout).
+ * fn_set_tuning refuses (FN_EINVAL, table untouched) a value outside a key's range, stated in [] below; retired keys take anything.
+ *   FN_TUNE_FWD_BLOCKS [1, 2^20]; FN_TUNE_FWD_BLOCKS_EVAL [1, 2^20]. */
 #define FN_TUNE_FWD_BLOCKS 0
 #define FN_TUNE_GEMM_SLOTS 1   /* > 0: cap on the workgroups of a projection GEMM launch (1024 = 256 CUs x 4 resident); a launch with
                                 * more 64x64 output tiles then walks several row tiles per workgroup, prefetching the next tile's
-                                * rows.  Default 0 = one tile per workgroup (faster at every measured size) */
+                                * rows.  Default 0 = one tile per workgroup (faster at every measured size).  [0, 2^20] */
 #define FN_TUNE_RETIRED_2 2     /* (retired in round 3, no effect: parameter-gradient work and the fragment-bond chain forked onto side streams --
                                 * a forked hipGraph replays SLOWER than the serial one on ROCm 7.2, 1.84 vs 1.69 ms per step) */
-#define FN_TUNE_WGRAD_BLOCKS 3 /* target workgroup count of the grouped weight-gradient launch of a backward pass (default 192 since round 5's re-sweep -- with layer 0's workgroups the launch then has 1.6 per CU; 256: + 1 % per step; 512 wrote twice the partials) */
+#define FN_TUNE_WGRAD_BLOCKS 3 /* target workgroup count of the grouped weight-gradient launch of a backward pass (default 192 since round 5's re-sweep -- with layer 0's workgroups the launch then has 1.6 per CU; 256: + 1 % per step; 512 wrote twice the partials).  [1, 2^20] */
 #define FN_TUNE_RETIRED_4 4     /* (retired in round 3, no effect: the molecule-resident fused FORWARD of round 2 -- measured equal at 512
                                 * molecules, slower elsewhere; source kept out of the build under tools/probe/retired/mol_fused.inc) */
 #define FN_TUNE_RETIRED_5 5     /* (retired: phase skew of that kernel) */
 #define FN_TUNE_RETIRED_6 6     /* (retired: register-resident-weights projection kernel k_proj128, 1-4 % slower per step) */
 #define FN_TUNE_FUSE_ROWDOTS 7 /* 1 (default): inside fn_encoder_forward the bond-graph attention kernel also writes the atom graph's edge
-                                * term <new_bond, a[:, d:d+128]> from the row it holds in registers; 0: a separate row-dots launch */
+                                * term <new_bond, a[:, d:d+128]> from the row it holds in registers; 0: a separate row-dots launch.  [0, 1] */
 #define FN_TUNE_WGRAD_DIRECT 8 /* 1 (default): the grouped K = 128 weight-gradient partials run as k_wgrad128_multi (operands straight from
                                 * global memory in the MFMA layout, csrc/wgrad128.inc); 0: the LDS-staged k_linear128_wgrad_multi (also
-                                * what layer 0's narrow products use) */
+                                * what layer 0's narrow products use).  [0, 1] */
 #define FN_TUNE_RETIRED_9 9     /* (retired: wave-independent projection kernel k_proj_direct, 1 % slower per step) */
 #define FN_TUNE_FWD_BLOCKS_EVAL 10
 #define FN_TUNE_DST_BLOCKS 11  /* target workgroup count of the backward destination pass (default 1536: three rows per half-wave at ESOL batch
-                                * 512; never more than three rows, see prep_gat_bwd_dst) */
-#define FN_TUNE_SRC_BLOCKS 12  /* resident workgroups of the backward source pass (default 512; <= 1024: every block writes a row of partial sums) */
-#define FN_TUNE_RD_BLOCKS 13   /* (default 512; 256 until round 5) workgroups of the edge-term backward that shares the source pass's launch (each writes a row of partial sums) */
+                                * 512; never more than three rows, see prep_gat_bwd_dst).  [1, FN_MAX_PART] */
+#define FN_TUNE_SRC_BLOCKS 12  /* resident workgroups of the backward source pass (default 512; every block writes a row of partial sums).  [1, 1024] */
+#define FN_TUNE_RD_BLOCKS 13   /* (default 512; 256 until round 5) workgroups of the edge-term backward that shares the source pass's launch (each writes a row of partial sums, FN_MAX_PART is their column stride).  [1, FN_MAX_PART] */
 #define FN_TUNE_GEMM_COLAUNCH 14 /* inside fn_encoder_*: the 128 -> 128 projections (forward) and input-gradient products (backward) that do
                                  * not depend on an attention pass ride along as extra workgroups of that pass's launch (the atom projection
                                  * beside the bond + fragment-bond levels, the next layer's bond / fragment-bond projections beside the atom
                                  * level; mirrored in the backward), layer 0's three raw-feature projections share a launch and all weight-gradient
                                  * partial products of a backward pass are one launch.  != 0 (default 2): on, the GEMM workgroups first in the
                                  * launch (after / interleaved with the attention workgroups measured slower and were removed in round 3:
-                                 * profiles/r02e_colaunch_ab.txt); 0: separate launches */
+                                 * profiles/r02e_colaunch_ab.txt); 0: separate launches.  [0, 2] */
 #define FN_TUNE_RETIRED_15 15    /* (retired: persistent riding GEMM workgroups walking several tiles, slower) */
 #define FN_TUNE_RETIRED_16 16    /* (retired: raised wave priority of the riding workgroups, no effect) */
 #define FN_TUNE_RETIRED_17 17    /* (retired in round 5: the two-pass backward's atom chain beside the bond chain -- superseded by the one-pass
@@ -90,26 +92,26 @@ int fn_abi_version(void);
 #define FN_TUNE_MOL_TAIL 20           /* 1 (default): batches marked molecule-contiguous (fn_encoder.mol_contiguous) run the last layer's
                                        * fragment tail -- fragment sums, fragment graph, readout and their backward -- as one
                                        * molecule-resident launch each way (csrc/mol_tail.inc); 0: the separate launches;
-                                       * 2 (test hook): fused, every molecule on the global-memory path of oversize molecules */
+                                       * 2 (test hook): fused, every molecule on the global-memory path of oversize molecules.  [0, 2] */
 #define FN_TUNE_WGRAD0_ROWS 21        /* layer 0's weight-gradient products (K = 167 / 17 / 6): rows per block as a multiple of the
                                        * per-product rule (M / 256 rounded up to 32); tens digit = the product with K > 128 (atoms),
-                                       * units digit = the narrow ones.  Default 23 */
+                                       * units digit = the narrow ones (a digit 0 counts as 1).  Default 23.  [1, 99] */
 #define FN_TUNE_BWD_ONE 22            /* 1: fn_encoder_backward runs every attention level's backward (bond / atom / fragment-bond graph) as
                                        * ONE source-owner pass (csrc/gat_bwd_one.inc): the forward then also writes out2 / sigma and the
-                                       * producers of the gradient rows write the node-local dots c, g_s_dst; 0: the two-pass backward */
+                                       * producers of the gradient rows write the node-local dots c, g_s_dst; 0: the two-pass backward.  [0, 1] */
 #define FN_TUNE_ONE_BLOCKS 23         /* target workgroups per LEVEL of a one-pass backward launch (default 768 = five rows per half-wave at the bond level of ESOL batch 512; every block writes a row of
-                                       * partial sums, so at most FN_MAX_PART).  Round 5's re-sweep: 1024 + 1.0 %, 512-896 within noise, 384 and fewer slower */
+                                       * partial sums, so at most FN_MAX_PART).  Round 5's re-sweep: 1024 + 1.0 %, 512-896 within noise, 384 and fewer slower.  [1, FN_MAX_PART] */
 #define FN_TUNE_PAD_SKIP 24           /* 1 (default): with the one-pass backward on a molecule-contiguous static-shape batch the kernels skip the
-                                       * padding rows (zero rows out, no gathers, no GEMM tiles, no weight-gradient rows); 0: they are processed */
+                                       * padding rows (zero rows out, no gathers, no GEMM tiles, no weight-gradient rows); 0: they are processed.  [0, 1] */
 #define FN_TUNE_ONE_INTERLEAVE 25      /* 1: in the one-pass backward's three-level launch the bond level's workgroups alternate with the atom /
-                                       * fragment-bond levels'; 0 (default): level after level (alternating measured 42-46 us against 37-40) */
+                                       * fragment-bond levels'; 0 (default): level after level (alternating measured 42-46 us against 37-40).  [0, 1] */
 #define FN_TUNE_ONE_TIER6 26           /* 1 (default): the attention kernels' gather tiers include 6 rows (forward 4 / 6 / 8, one-pass backward
-                                       * 4 / 6 / 8 / 12 per round trip); 0: 4 / 8 (/ 12) */
+                                       * 4 / 6 / 8 / 12 per round trip); 0: 4 / 8 (/ 12).  [0, 1] */
 #define FN_TUNE_RIDER_PIECES 27       /* 16-byte pieces per thread of the Adam slice that rides in the deferred-reduction launch (fn_encoder.adam_rider):
-                                       * 1 (default) = as many 1024-thread workgroups as the slice has KiB x 16 */
+                                       * 1 (default) = as many 1024-thread workgroups as the slice has KiB x 16.  [1, 4096] */
 #define FN_TUNE_RIDER_AT 28           /* which launch of the one-pass encoder backward carries fn_encoder.adam_rider: 0 (default) the last one (the
                                        * deferred reductions: + 7 us there for the 12.9 - 4.5 us the step's Adam launch saves), 1 the first one (the
-                                       * molecule-resident fragment tail, when it runs: + 11.7 us) */
+                                       * molecule-resident fragment tail, when it runs: + 11.7 us).  [0, 1] */
 #define FN_TUNE_RETIRED_29 29          /* (retired, no effect: the DEFERRED forms of the engine's one-pass backward, four heads.  1: the forward wrote no
                                        * out2 / sigma, the pass left dz at the edges' destination-order slots and the consumers of g_h added the
                                        * g_s_dst a_dst term -- one more MFMA step in the input-gradient products, the weight-gradient kernels' side
@@ -120,29 +122,33 @@ int fn_abi_version(void);
                                        * keeps its deferred form: fn_gat_bwd_one_f32 with dz_em, fn_gat_gsd_f32) */
 #define FN_TUNE_FWD_BLOCKS_EVAL_LARGE 30 /* the plain forward (inference) of a level with more than 4 x FN_TUNE_FWD_BLOCKS_EVAL row groups (2048+ molecules
                                        * per batch) runs this many workgroups instead (default 6144): with the fixed count every half-wave walked 12-46
-                                       * rows and the launch waited for its slowest workgroups.  0: one count for every size (rounds 1-4) */
+                                       * rows and the launch waited for its slowest workgroups.  0: one count for every size (rounds 1-4).  [0, 2^20] */
 #define FN_TUNE_FWD_TAIL_ROWS 31       /* > 0: in the two-level forward launch (bond + fragment-bond graph) the SECOND level's half-waves take at most this
                                        * many rows: its workgroups are dispatched last, so long-lived ones are the launch's tail (only large batches
                                        * reach the cap: 2048 molecules per batch forward-only 1.13 -> 1.28 M molecules/s).  Evaluation passes only (no dropout
-                                       * epilogue), as FN_TUNE_FWD_BLOCKS_EVAL_LARGE.  Default 1; 0: no cap */
+                                       * epilogue), as FN_TUNE_FWD_BLOCKS_EVAL_LARGE.  Default 1; 0: no cap.  [0, 2^20] */
 #define FN_TUNE_DENSE_TILES 32         /* 1 (default): fn_dense_fwd_f32 runs inputs of >= 192 tiles of 64 x 128 (1536+ rows at N = 1024) with K a multiple of 32 on
                                        * workgroup-shared LDS macro-tiles (k_dense_fwd_tiles, round 6: 62 -> 43 us at M = 2048, K = N = 1024); 0: the per-wave
-                                       * operand kernel for every shape (A/B, and the parity test of the two against each other) */
+                                       * operand kernel for every shape (A/B, and the parity test of the two against each other).  [0, 1] */
 #define FN_TUNE_ENGINE_CONST 33        /* 1 (default): the attention launches of the engine (four heads, levels of >= 2 edges, no probs_orig / stamp buffer)
                                        * run kernel instances in which their uniform run-time flags are compile-time constants -- a training pass:
                                        * edge-major probabilities, relu(dropout(.)) epilogues with p > 0 (forward kind 2, the one-pass backward's EN
                                        * instances); an evaluation pass: head-major probabilities, ReLU epilogues without dropout (forward kind 3).  Same
                                        * arithmetic, bit-identical results, fewer scalar tests and branches in the issue-bound row loops (round 6: 0.769 ->
                                        * 0.755 ms per training step, the forward-only sweep - 4 ... - 7 %); 0: the general instances for every launch (A/B,
-                                       * and the parity test of the two against each other) */
+                                       * and the parity test of the two against each other).  [0, 1] */
 #define FN_TUNE_COALITION_STAGED 34     /* the form of fn_pool_cat_coalitions_f32's kernel.  0: one workgroup per output row and half, the form of
                                        * fn_pool_cat_groups_f32.  n >= 2: the tiled form -- a workgroup owns 64 consecutive output rows and walks the runs
                                        * of one molecule in them; a run of at least n - 1 rows is staged (the molecule's atom rows go to LDS once for all
                                        * of its rows), a shorter one reads global memory (2: every run is staged; a large n: none).  1 (default): the
                                        * tiled form with n = 17 for a call with at least 64 rows per molecule on average, where it measured faster,
-                                       * else the form of 0.  Same bits in every form */
+                                       * else the form of 0.  Same bits in every form.  [0, INT_MAX] */
 #define FN_TUNE_COUNT 35
+/* The table at load, in key order (fn_get_tuning reads it back):
+ *   1024, 0, 0, 192, 0, 0, 0, 1, 1, 0, 1792, 1536, 512, 512, 2, -1, 0, 1, 0, 0, 1, 23, 1, 768, 1, 0, 1, 1, 0, 0, 6144, 1, 1, 1, 1 */
 int fn_set_tuning(int key, int value);
+/* The current value of a key; 0 for a key outside the table.  Added under ABI 12 (nothing existing changes). */
+int fn_get_tuning(int key);
 /* Profiling aid (process-wide, like the tuning knobs): while `buf` (device, n_u64 >= 16 * 4 * workgroups 64-bit words) is set, every wave
  * of the one-pass attention backward (fn_gat_bwd_one_f32) writes s_memtime stamps of its phases into it (tools/probe/bwd_one_probe.py
  * --stamps).  NULL switches it off (the default: the kernel then pays one uniform branch per phase). */

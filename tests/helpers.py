@@ -1,6 +1,8 @@
-"""Shared loaders for the golden fixtures (tests/golden/*.npz, written by make_golden.py)."""
+"""Shared loaders for the golden fixtures (tests/golden/*.npz, written by make_golden.py), and the tuning-table context manager."""
+import contextlib
 import json
 import os
+import re
 
 import numpy as np
 import torch
@@ -29,6 +31,35 @@ def check_params_match(model, pkeys, psums, rtol=1e-12):
         v = sd[k].double()
         assert abs(float(v.sum()) - s) <= rtol * max(1.0, abs(a)), k
         assert abs(float(v.abs().sum()) - a) <= rtol * max(1.0, abs(a)), k
+
+
+@contextlib.contextmanager
+def tuning(settings=None, **named):
+    """Sets keys of the library's tuning table (include/fragnet_hip.h FN_TUNE_*) for the body and puts back the values it found there
+    -- read through fn_get_tuning, so a test never carries a copy of a default: ``with tuning({23: 7, 25: 1}):`` or, by the name
+    behind FN_TUNE_, ``with tuning(ONE_BLOCKS=7):``.  A refused value raises before the body runs, with everything restored."""
+    from fragnet_amd import _lib
+    lib = _lib.load()
+    todo = {int(k): int(v) for k, v in (settings or {}).items()}
+    for name, v in named.items():
+        todo[tuning_key(name)] = int(v)
+    old = {}
+    try:
+        for k, v in todo.items():
+            old.setdefault(k, lib.fn_get_tuning(k))
+            _lib.call("fn_set_tuning", k, v)
+        yield
+    finally:
+        for k, v in old.items():
+            _lib.call("fn_set_tuning", k, v)
+
+
+def tuning_key(name):
+    """The number behind ``#define FN_TUNE_<name>`` in the header."""
+    text = open(os.path.join(os.path.dirname(GOLDEN), os.pardir, "include", "fragnet_hip.h")).read()
+    found = re.search(r"#define FN_TUNE_%s\s+(\d+)" % re.escape(name.upper()), text)
+    assert found, f"no tuning key FN_TUNE_{name.upper()}"
+    return int(found.group(1))
 
 
 def sample_like_golden(g):

@@ -28,6 +28,22 @@ def test_library_exports_every_declared_symbol():
     assert lib.fn_abi_version() == _lib.ABI_VERSION == 12
 
 
+def test_tuning_table_reads_back_through_the_abi():
+    """fn_get_tuning (added under ABI 12: additions do not bump the version) is declared, exported and bound, and is the inverse of
+    fn_set_tuning; tests/test_tuning_ranges_host.py has the ranges."""
+    from fragnet_amd import _lib
+    lib = _lib.load()
+    assert "fn_get_tuning" in _declared() and _lib.SIGNATURES["fn_get_tuning"] == _lib.SIGNATURES["fn_set_tuning"][:1]
+    old = lib.fn_get_tuning(31)
+    try:
+        _lib.call("fn_set_tuning", 31, old + 5)
+        assert lib.fn_get_tuning(31) == old + 5
+    finally:
+        _lib.call("fn_set_tuning", 31, old)
+    assert lib.fn_get_tuning(31) == old
+    assert lib.fn_set_tuning(31, -1) == -1 and b"FWD_TAIL_ROWS" in lib.fn_last_error() and lib.fn_get_tuning(31) == old
+
+
 def test_library_exports_nothing_but_the_declared_entry_points():
     """Every defined function symbol of the .so is a declared fn_* entry point (helpers must be static: a namespace-scope
     function inside the extern "C" block is exported under its plain name)."""

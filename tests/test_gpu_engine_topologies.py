@@ -27,11 +27,11 @@ import pytest
 import torch
 
 from tests import topologies as T
+from tests.helpers import tuning
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 ATOL = 1e-4
-KEY_DEFAULTS = {14: 2, 20: 1, 22: 1, 26: 1, 33: 1}
 
 
 @pytest.fixture(scope="module", autouse=True)
@@ -85,11 +85,6 @@ def _check_batch(name, heads, plan, pretrain=False, padded=False):
         assert {lv: max(v) for lv, v in got.items()} == {lv: max(v) for lv, v in ins.items()}
 
 
-def _set(key, value):
-    from fragnet_amd import _lib
-    _lib.call("fn_set_tuning", key, value)
-
-
 def _model(heads, drop=0.0, state=None, seed=3):
     from fragnet_amd.model import FragNetFineTune
     torch.manual_seed(seed)
@@ -120,13 +115,10 @@ def test_training_step_matches_the_oracle(name, heads, one_pass):
     gold, want, want_g = _oracle(name, heads)
     model = _model(heads, state=gold.state_dict())
     b = _dev_batch(name)
-    try:
-        _set(22, one_pass)
+    with tuning({22: one_pass}):
         got = model(b)
         torch.nn.functional.mse_loss(got.view(-1), b["y"]).backward()
         torch.cuda.synchronize()
-    finally:
-        _set(22, 1)
     b["_fragnet_plan"].check()
     _check_batch(name, heads, b["_fragnet_plan"])
     print(f"logits: max|diff| = {float((got.detach().cpu() - want).abs().max()):.3e}")
@@ -155,14 +147,11 @@ def test_pretrain_step_matches_the_oracle(name, one_pass):
     model.load_state_dict(gold.state_dict())
     model = model.to(DEV).train()
     b = _dev_batch(name, True)
-    try:
-        _set(22, one_pass)
+    with tuning({22: one_pass}):
         outs = model(b)
         assert len(outs) == 4 and all(o is not None for o in outs)
         sum(o.square().mean() for o in outs).backward()
         torch.cuda.synchronize()
-    finally:
-        _set(22, 1)
     b["_fragnet_plan"].check()
     _check_batch(name, heads, b["_fragnet_plan"], pretrain=True)
     for i, (o, w) in enumerate(zip(outs, want)):
@@ -172,16 +161,14 @@ def test_pretrain_step_matches_the_oracle(name, one_pass):
 
 # ----------------------------------------------------------------------------------------------- c. the alternative kernels
 def _key_runs(name, key, values, heads=4):
+    """One run per value; None = the value the table holds (the default path)."""
     from tests.test_gpu_tuning_keys import _encoder_run
     net = _model(heads, drop=0.1)
     b = _dev_batch(name)
     res = []
-    try:
-        for v in values:
-            _set(key, v)
+    for v in values:
+        with tuning({} if v is None else {key: v}):
             res.append(_encoder_run(net, b, 999))
-    finally:
-        _set(key, KEY_DEFAULTS[key])
     _check_batch(name, heads, b["_fragnet_plan"])
     return res
 
@@ -192,7 +179,7 @@ def test_alternative_kernels_reproduce_the_default_path(name, key, value):
     """Dropout 0.1, fixed Philox offset.  Key 20: the fused tail chosen per molecule (1) against the separate launches (0) and against
     the global-memory path for every molecule (2) -- on "edges" the chains of 25 .. 33 fragments take the global path beside LDS-class
     molecules in the same launch, on "wide" the molecules of 130 / 156 edges do; 26 = 0: no tier at six rows; 14 = 0: no riding GEMMs."""
-    (o0, g0), (o1, g1) = _key_runs(name, key, [KEY_DEFAULTS[key], value])
+    (o0, g0), (o1, g1) = _key_runs(name, key, [None, value])
     for a, c in zip(o0, o1):
         torch.testing.assert_close(c, a, atol=1e-5, rtol=1e-5)
     assert set(g0) == set(g1)
@@ -226,9 +213,10 @@ def test_evaluation_without_a_backward_pass_returns_the_training_forward_bits(he
 
 
 # ----------------------------------------------------------------------------------------------- e. the captured step
-def test_graph_step_matches_the_oracle_with_long_rows_beside_padding():
-    """Static-shape staging + hipGraph replay (pad skip on): the "edges" batch padded to the shapes of itself and an ordinary batch;
-    loss and the flat gradient buffer against the oracle, no fall-back."""
+@pytest.mark.parametrize("pad_skip", [1, 0], ids=["pad_skip", "pad_rows_processed"])
+def test_graph_step_matches_the_oracle_with_long_rows_beside_padding(pad_skip):
+    """Static-shape staging + hipGraph replay: the "edges" batch padded to the shapes of itself and an ordinary batch; loss and the flat
+    gradient buffer against the oracle, no fall-back.  Key 24: the kernels skip the padding rows (1, the default) or process them (0)."""
     from fragnet_amd import data, graphstep, parallel, synth
     from oracle import fragnet_ref as ref
     heads = 4
@@ -246,9 +234,10 @@ def test_graph_step_matches_the_oracle_with_long_rows_beside_padding():
     # tasks want four waves each and its schedule (32 wave slots) declines -> general builder.  The exact maxima keep the builder the
     # benchmarked step runs, so that the long rows meet the padding rows of ITS plan.
     shapes.max_per_mol = {sp: max(b.max_per_mol[sp], other.max_per_mol[sp]) for sp in b.max_per_mol}
-    step = graphstep.GraphedTrainStep(model, opt, shapes, other, loss="regr")       # collated batches: the fused kernels, the one-launch plan
-    loss = float(step(b))
-    torch.cuda.synchronize()
+    with tuning({24: pad_skip}):
+        step = graphstep.GraphedTrainStep(model, opt, shapes, other, loss="regr")       # collated batches: the fused kernels, the one-launch plan
+        loss = float(step(b))
+        torch.cuda.synchronize()
     assert step.replays == 1 and step.fallbacks == 0
     assert step.static.collated and step.static.with_offsets
     plan = step.static.t["_fragnet_plan"]

@@ -5,7 +5,7 @@ It runs for batches that carry collate_fn's layout promise (plan.CollatedBatch);
 import pytest
 import torch
 
-from tests.helpers import check_grads, load_case
+from tests.helpers import check_grads, load_case, tuning
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -62,9 +62,7 @@ def test_fused_tail_equals_the_separate_launches(heads, drop, path):
     model = FragNetFineTune(n_classes=1, num_layer=2, num_heads=heads, drop_ratio=drop, h1=64, h2=64, h3=64, h4=32, act="relu",
                             fthead="FTHead3").to(DEV).train()
     res = []
-    from fragnet_amd import _lib
-    try:
-        _lib.call("fn_set_tuning", 20, path)        # 2: every molecule on the global-memory path of oversize molecules
+    with tuning({20: path}):                        # 2: every molecule on the global-memory path of oversize molecules
         for b in (coll, plain):
             model.zero_grad(set_to_none=True)
             model.pretrain.rng.offset = 77
@@ -72,8 +70,6 @@ def test_fused_tail_equals_the_separate_launches(heads, drop, path):
             torch.nn.functional.mse_loss(out.view(-1), b["y"]).backward()
             res.append((out.detach().clone(), {n: p.grad.detach().clone() for n, p in model.named_parameters() if p.grad is not None}))
         assert _fused(model, coll) and not _fused(model, plain)
-    finally:
-        _lib.call("fn_set_tuning", 20, 1)
     torch.testing.assert_close(res[0][0], res[1][0], atol=1e-5, rtol=1e-5)
     assert set(res[0][1]) == set(res[1][1])
     for n, g in res[1][1].items():
@@ -160,7 +156,7 @@ def test_training_step_reads_nothing_it_did_not_write(kind, layers, tail):
     backward pass, four runs of the same step give finite, bit-identical gradients -- i.e. no kernel reads a buffer (or a
     masked lane multiplies a row) that this pass has not written.  (Found on the way: a lane without an edge gathered a row of
     another molecule and multiplied it by 0; the molecule-resident tail made that row possibly unwritten.)"""
-    from fragnet_amd import _lib, data, synth
+    from fragnet_amd import data, synth
     from fragnet_amd.model import FragNetFineTune, FragNetPreTrain
     pt = kind == "pt"
     mols = synth.synth_molecules(48, seed=9, profile="esol", pretrain_targets=pt)
@@ -169,8 +165,7 @@ def test_training_step_reads_nothing_it_did_not_write(kind, layers, tail):
     model = (FragNetPreTrain(num_layer=layers, drop_ratio=0.1, edge_features=17) if pt else
              FragNetFineTune(n_classes=1, num_layer=layers, drop_ratio=0.1, h1=64, h2=64, h3=64, h4=32, act="relu", fthead="FTHead3")).to(DEV).train()
     res = []
-    try:
-        _lib.call("fn_set_tuning", 20, tail)
+    with tuning({20: tail}):
         for _ in range(4):
             model.zero_grad(set_to_none=True)
             model.pretrain.rng.offset = 5
@@ -183,8 +178,6 @@ def test_training_step_reads_nothing_it_did_not_write(kind, layers, tail):
             loss.backward()
             torch.cuda.synchronize()
             res.append({n: p.grad.detach().clone() for n, p in model.named_parameters() if p.grad is not None})
-    finally:
-        _lib.call("fn_set_tuning", 20, 1)
     for n, g in res[0].items():
         assert torch.isfinite(g).all(), n
         for r in res[1:]:

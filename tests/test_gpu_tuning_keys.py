@@ -2,6 +2,8 @@
 import pytest
 import torch
 
+from tests.helpers import tuning
+
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 
@@ -31,18 +33,14 @@ def test_alternative_kernels_behind_tuning_keys_stay_parity_green(key, value):
     attention launches, 20 = 0 the last layer's fragment tail as separate launches instead of the
     molecule-resident pair, 22 = 0 the destination + source passes, 33 = 0 the general kernel instances instead of the engine-constant ones (round 6).  Each must reproduce the default path's outputs and gradients (same Philox
     stream) on a training step with dropout."""
-    from fragnet_amd import _lib, data, model as M, synth
+    from fragnet_amd import data, model as M, synth
     torch.manual_seed(0)
     net = M.FragNetFineTune(n_classes=1, num_layer=3, drop_ratio=0.1, h1=32, h2=32, h3=32, h4=32, act="relu", fthead="FTHead3").to(DEV)
     net.train()
     batch = data.batch_to(data.collate_fn(synth.synth_molecules(96, seed=17, profile="esol")), DEV)
-    default = {7: 1, 8: 1, 14: 2, 20: 1, 22: 1, 33: 1}[key]
-    try:
-        o0, g0 = _encoder_run(net, batch, 999)
-        _lib.call("fn_set_tuning", key, value)
+    o0, g0 = _encoder_run(net, batch, 999)
+    with tuning({key: value}):
         o1, g1 = _encoder_run(net, batch, 999)
-    finally:
-        _lib.call("fn_set_tuning", key, default)
     for a, b in zip(o0, o1):
         torch.testing.assert_close(b, a, atol=1e-5, rtol=1e-5)
     assert set(g0) == set(g1)
@@ -54,7 +52,7 @@ def test_launch_geometry_keys_of_the_plain_forward_do_not_change_a_bit():
     """FN_TUNE_FWD_BLOCKS_EVAL (10), FN_TUNE_FWD_BLOCKS_EVAL_LARGE (30) and FN_TUNE_FWD_TAIL_ROWS (31) only decide how many rows a
     half-wave of the attention forward walks; a row's arithmetic does not depend on it.  Forced into play on a small batch (8 workgroups
     per level -> many rows per half-wave; then the large-level count and the second level's cap), the inference outputs stay bit-identical."""
-    from fragnet_amd import _lib, data, model as M, synth
+    from fragnet_amd import data, model as M, synth
     torch.manual_seed(1)
     net = M.FragNetFineTune(n_classes=1, num_layer=3, drop_ratio=0.1, h1=32, h2=32, h3=32, h4=32, act="relu", fthead="FTHead3").to(DEV)
     net.eval()
@@ -68,21 +66,16 @@ def test_launch_geometry_keys_of_the_plain_forward_do_not_change_a_bit():
         return out.detach().clone()
 
     base = run()
-    try:
-        for settings in ({10: 8, 30: 0, 31: 0}, {10: 8, 30: 64, 31: 0}, {10: 8, 30: 0, 31: 1}, {10: 8, 30: 64, 31: 1}):
-            for k, v in settings.items():
-                _lib.call("fn_set_tuning", k, v)
+    for settings in ({10: 8, 30: 0, 31: 0}, {10: 8, 30: 64, 31: 0}, {10: 8, 30: 0, 31: 1}, {10: 8, 30: 64, 31: 1}):
+        with tuning(settings):
             assert torch.equal(run(), base), settings
-    finally:
-        for k, v in {10: 1792, 30: 6144, 31: 1}.items():
-            _lib.call("fn_set_tuning", k, v)
 
 
 def test_engine_constant_instances_do_not_change_a_bit():
     """FN_TUNE_ENGINE_CONST (33): the attention launches of the engine run kernel instances whose uniform run-time flags are
     compile-time constants (forward kinds 2 / 3, the one-pass backward's EN instances).  Same arithmetic: an inference pass and a
     training step with dropout (outputs and every gradient) are BIT-identical with the key off."""
-    from fragnet_amd import _lib, data, model as M, synth
+    from fragnet_amd import data, model as M, synth
     torch.manual_seed(2)
     net = M.FragNetFineTune(n_classes=1, num_layer=3, drop_ratio=0.1, h1=32, h2=32, h3=32, h4=32, act="relu", fthead="FTHead3").to(DEV)
     batch = data.batch_to(data.collate_fn(synth.synth_molecules(96, seed=29, profile="esol")), DEV)
@@ -99,13 +92,10 @@ def test_engine_constant_instances_do_not_change_a_bit():
         net.train()
         return _encoder_run(net, batch, 777)
 
-    try:
-        _lib.call("fn_set_tuning", 33, 0)
+    with tuning({33: 0}):
         e0, (o0, g0) = infer(), train()
-        _lib.call("fn_set_tuning", 33, 1)
+    with tuning({33: 1}):
         e1, (o1, g1) = infer(), train()
-    finally:
-        _lib.call("fn_set_tuning", 33, 1)
     assert torch.equal(e0, e1)
     for a, b in zip(o0, o1):
         assert torch.equal(a, b)

@@ -5,6 +5,8 @@ import copy
 import pytest
 import torch
 
+from tests.helpers import tuning
+
 gpu = pytest.mark.gpu
 
 
@@ -141,12 +143,9 @@ def test_dense_forward_on_workgroup_shared_tiles_matches_float64_and_the_per_wav
     plain = y[:M].contiguous()
     _lib.call("fn_dropout_act_f32", plain.data_ptr(), want.data_ptr(), plain.numel(), 0.25, 99, 1040, None, 1, st)
     torch.testing.assert_close(z, want, atol=3e-5, rtol=1e-5)
-    try:
-        _lib.call("fn_set_tuning", 32, 0)
+    with tuning({32: 0}):
         z0 = torch.full((M, N), 7.0, device=dev)
         _lib.call("fn_dense_fwd_f32", x.data_ptr(), w.data_ptr(), b.data_ptr(), z0.data_ptr(), M, K, N, C.byref(act), st)
-    finally:
-        _lib.call("fn_set_tuning", 32, 1)
     assert ((z > 0) != (z0 > 0)).sum() <= 2                          # the same masks; pre-activations within rounding of 0 may flip
     torch.testing.assert_close(z, z0, atol=3e-5, rtol=1e-5)
 
