@@ -429,6 +429,43 @@ __device__ __forceinline__ void st4_off(float* base, uint32_t byte_off, float4 v
 __device__ __forceinline__ void st1_off(float* base, uint32_t byte_off, float v) {
     *reinterpret_cast<float*>(reinterpret_cast<char*>(base) + byte_off) = v;
 }
+// ---- store policy of the row tables (DESIGN.md §3 classifies every table of the training step by its next reader;
+// profiles/store_policy_probe.txt is the measurement).  A table is written through a wave-uniform base + a 32-bit byte offset, as with
+// st4_off / st1_off, because the flavours below exist only as buffer stores the compiler itself tracks (it counts vmcnt; no inline
+// assembly): the base becomes an unbounded raw-buffer descriptor in four SGPRs, the offset is the one address register.
+//   st4_next / st1_next : tables the NEXT launch reads -- write-through (sc1): the line is not left dirty in the XCD's L2 for the
+//                         kernel boundary to write back (boundary 3.1-4.2 -> 1.3-1.6 us behind 16-64 MB), and the memory-side cache still
+//                         holds it for the consumer (a consumer's pass: 9.6 us of 64 MB either way; behind nt stores 23.8 us)
+//   st4_late / st1_late : tables only the backward pass reads, hundreds of microseconds later -- write-through and non-temporal
+//                         (nt sc1): the same boundary, and the follower's own reads are not pushed out of the memory-side cache
+// The 4-byte twins (the [n, H] and per-edge tables) take their class's flavour only under -DFN_STORE_POLICY=2: the probe measured 16-byte
+// stores, and a write-through store is one fabric write whatever its width, so until a 4-byte arm is measured they stay plain.
+// -DFN_STORE_POLICY=0: every one of them is the plain st4_off / st1_off (the A/B arm; same values either way, only the cache policy differs)
+#ifndef FN_STORE_POLICY
+#define FN_STORE_POLICY 1
+#endif
+constexpr int kStNext = 16, kStLate = 18;      // cache-policy bits of a gfx950 buffer store: 1 sc0, 2 nt, 16 sc1
+template <int AUX> __device__ __forceinline__ void st4_policy(float* base, uint32_t byte_off, float4 v) {
+#if FN_STORE_POLICY && defined(__HIP_DEVICE_COMPILE__)
+    typedef unsigned u32x4 __attribute__((__vector_size__(16)));
+    typedef float f32x4_t __attribute__((ext_vector_type(4)));
+    const f32x4_t w = {v.x, v.y, v.z, v.w};
+    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, w), __builtin_amdgcn_make_buffer_rsrc(base, 0, -1, 0x00020000), (int)byte_off, 0, AUX);
+#else
+    st4_off(base, byte_off, v);
+#endif
+}
+template <int AUX> __device__ __forceinline__ void st1_policy(float* base, uint32_t byte_off, float v) {
+#if FN_STORE_POLICY >= 2 && defined(__HIP_DEVICE_COMPILE__)
+    __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), __builtin_amdgcn_make_buffer_rsrc(base, 0, -1, 0x00020000), (int)byte_off, 0, AUX);
+#else
+    st1_off(base, byte_off, v);
+#endif
+}
+__device__ __forceinline__ void st4_next(float* base, uint32_t byte_off, float4 v) { st4_policy<kStNext>(base, byte_off, v); }
+__device__ __forceinline__ void st4_late(float* base, uint32_t byte_off, float4 v) { st4_policy<kStLate>(base, byte_off, v); }
+__device__ __forceinline__ void st1_next(float* base, uint32_t byte_off, float v) { st1_policy<kStNext>(base, byte_off, v); }
+__device__ __forceinline__ void st1_late(float* base, uint32_t byte_off, float v) { st1_policy<kStLate>(base, byte_off, v); }
 
 
 

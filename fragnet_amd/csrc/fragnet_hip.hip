@@ -569,7 +569,7 @@ __global__ __launch_bounds__(kLinThreads) void k_linear128(const float* __restri
                                                    const float* __restrict__ bias, float* __restrict__ Y, int64_t M,
                                                    fn_act_epilogue mk, NodeScalarEpi ns) {
     extern __shared__ __attribute__((aligned(16))) float sBt[];
-    linear128_body<KQ, VEC, PF>(sBt, X, K, Bt, bias, Y, M, mk, ns, (int)blockIdx.x, (int)gridDim.x);
+    linear128_body<KQ, VEC, PF, false, false, false>(sBt, X, K, Bt, bias, Y, M, mk, ns, (int)blockIdx.x, (int)gridDim.x);
 }
 
 template <int KQ, bool VEC, bool PF>

@@ -241,12 +241,12 @@ __device__ __forceinline__ void gat_bwd_one_rows(const GatBwdOneArgs& A, float (
             }
             if (KL == 0) {
                 if (want_sorted) {                                // dL/d(edge term) at the edge's destination-order slot, [H][m]
-                    if (has0) st1_off(dz_sorted, ((uint32_t)head * (uint32_t)m + (uint32_t)d0) * 4u, dz0);
-                    if (has1) st1_off(dz_sorted, ((uint32_t)head * (uint32_t)m + (uint32_t)d1) * 4u, dz1);
+                    if (has0) st1_next(dz_sorted, ((uint32_t)head * (uint32_t)m + (uint32_t)d0) * 4u, dz0);
+                    if (has1) st1_next(dz_sorted, ((uint32_t)head * (uint32_t)m + (uint32_t)d1) * 4u, dz1);
                 }
                 if (want_orig) {                                  // ... in ORIGINAL edge order, [m_real][H]
-                    if (has0 && eq0 < pl.m_real) st1_off(g_s_orig, ((uint32_t)eq0 * H + head) * 4u, dz0);
-                    if (has1 && eq1 < pl.m_real) st1_off(g_s_orig, ((uint32_t)eq1 * H + head) * 4u, dz1);
+                    if (has0 && eq0 < pl.m_real) st1_next(g_s_orig, ((uint32_t)eq0 * H + head) * 4u, dz0);
+                    if (has1 && eq1 < pl.m_real) st1_next(g_s_orig, ((uint32_t)eq1 * H + head) * 4u, dz1);
                 }
             } else {
                 pw[NE] += dz0 + dz1;
@@ -289,7 +289,7 @@ __device__ __forceinline__ void gat_bwd_one_rows(const GatBwdOneArgs& A, float (
             // (storing the row one iteration late, behind the next row's gathers, measured SLOWER: 18.5 -> 20.0 us at B = 512)
             if constexpr (!DF) fma4(acc, cur_gsd, ad);
             fma4(acc, gss, as);
-            st4_off(g_h, (uint32_t)s * (FN_D * 4) + lane * 16, acc);
+            st4_next(g_h, (uint32_t)s * (FN_D * 4) + lane * 16, acc);        // the product launch behind this one reads it (store policy: fn_internal.h)
             if constexpr (!DF) fma4(qd, cur_gsd, hr);
             fma4(qs, gss, hr);
         }

@@ -306,8 +306,8 @@ __device__ __forceinline__ void gat_fwd_rows(const GatFwdArgs& A, float (*sWf)[k
         if (fast) {
             const int pos0 = beg + 2 * j;
             if (TR || (!EV && A.p_edge_major)) {
-                if (has0 && wp) st1_off(p_sorted, ((uint32_t)pos0 * H + head) * 4u, sp0);
-                if (has1 && wp) st1_off(p_sorted, ((uint32_t)(pos0 + 1) * H + head) * 4u, sp1);
+                if (has0 && wp) st1_late(p_sorted, ((uint32_t)pos0 * H + head) * 4u, sp0);        // (store policy: fn_internal.h)
+                if (has1 && wp) st1_late(p_sorted, ((uint32_t)(pos0 + 1) * H + head) * 4u, sp1);
             } else if (wp) {
                 float* pdst = p_sorted + (size_t)head * m + pos0;
                 if (has1) stp(pdst, sp0, sp1);
@@ -359,10 +359,10 @@ __device__ __forceinline__ void gat_fwd_rows(const GatFwdArgs& A, float (*sWf)[k
         }
         if (deg >= 0) {
             const uint32_t row_off = (uint32_t)t * (FN_D * 4) + lane * 16;          // (n <= 2^23 rows: fits)
-            if (out) st4_off(out, row_off, acc);
+            if (out) st4_next(out, row_off, acc);               // raw rows: the next launch reads them; out2 / sigma: only the backward
             if constexpr (o2) {
-                st4_off(out2, row_off, acc2);
-                if (j == 0) st1_off(A.sigma, ((uint32_t)t * H + head) * 4u, sg);
+                st4_late(out2, row_off, acc2);
+                if (j == 0) st1_late(A.sigma, ((uint32_t)t * H + head) * 4u, sg);
             }
             if (RD) {            // the next level's edge term from the row in registers (saves a launch that re-reads every row)
                 float mine = 0.f;
@@ -373,7 +373,7 @@ __device__ __forceinline__ void gat_fwd_rows(const GatFwdArgs& A, float (*sWf)[k
                     const float dsum = head_sum<32>(dot4(acc, ld4_off(A.rd_A, (uint32_t)(q * A.rd_lda + lane * 4) * 4u)));
                     if (lane == q) mine = dsum;
                 }
-                if (lane < rdJ) st1_off(A.rd_out, ((uint32_t)lane * (uint32_t)A.rd_m + (uint32_t)rd_p) * 4u, mine);
+                if (lane < rdJ) st1_next(A.rd_out, ((uint32_t)lane * (uint32_t)A.rd_m + (uint32_t)rd_p) * 4u, mine);
             }
             if (ep.y) {          // fused act(dropout(.)): same Philox block index (element / 4) as k_dropout_act
                 float4 r = acc;
@@ -384,7 +384,7 @@ __device__ __forceinline__ void gat_fwd_rows(const GatFwdArgs& A, float (*sWf)[k
                     r.z *= keep_scale(rnd.z, ep.p, ik); r.w *= keep_scale(rnd.w, ep.p, ik);
                 }
                 if (KC || ep.relu) { r.x = fmaxf(r.x, 0.f); r.y = fmaxf(r.y, 0.f); r.z = fmaxf(r.z, 0.f); r.w = fmaxf(r.w, 0.f); }
-                st4_off(ep.y, row_off, r);
+                st4_next(ep.y, row_off, r);
             }
         }
     }

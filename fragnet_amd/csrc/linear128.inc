@@ -35,7 +35,9 @@ using fni::RowAdd;
 constexpr int kCuRows = 4;        // rows of a lane's four whose epilogue operands are in flight together (CuEpi): all four.  Two at a time
                                   // fit four waves per SIMD only with spills: the launch measured 43-45 us against 34-36
 using fni::CuEpi;
-template <int KQ, bool VEC, bool PF, bool RA = false, bool CU = false>
+// POL: the output rows take the next-launch store policy (fn_internal.h).  The stand-alone operator kernel k_linear128 passes false: with
+// the buffer store two of its instances (K <= 8, and K = 167 with the fused gate) would lose a wave per SIMD.
+template <int KQ, bool VEC, bool PF, bool RA = false, bool CU = false, bool POL = true>
 __device__ __forceinline__ void linear128_body(float* sBt, const float* __restrict__ X, int K, const float* __restrict__ Bt,
                                                const float* __restrict__ bias, float* __restrict__ Y, int64_t M,
                                                const fn_act_epilogue& mk, const NodeScalarEpi& ns, int bid, int nblk,
@@ -181,6 +183,10 @@ __device__ __forceinline__ void linear128_body(float* sBt, const float* __restri
         // acc[t][r] is (row kq*4 + r, column 4 i + t) of the wave's 16 x 64 tile
         __builtin_amdgcn_sched_barrier(0);
         const int64_t r0 = tile * kLinRows + w * 16 + kq * 4;
+        // the output rows are a next-launch table (store policy: fn_internal.h): the row tile's first row is the wave-uniform base, so the
+        // 32-bit byte offset stays inside the tile whatever M is
+        float* const Yt = Y + tile * (kLinRows * 128);
+        const uint32_t yoff = (uint32_t)((w * 16 + kq * 4) * 128 + col) * 4u;
         float pd[4], ps[4];
         if constexpr (CU) {
             // one-pass backward: the gate's saved output, the raw / second output rows and the edge-term gradient of all four rows
@@ -218,7 +224,7 @@ __device__ __forceinline__ void linear128_body(float* sBt, const float* __restri
                         o.z = yv[q].z > 0.f ? o.z * sc : 0.f; o.w = yv[q].w > 0.f ? o.w * sc : 0.f;
                     }
                     fma4(o, zv[q].x, ra_a[0]);  fma4(o, zv[q].y, ra_a[1]);  fma4(o, zv[q].z, ra_a[2]);  fma4(o, zv[q].w, ra_a[3]);
-                    if (r0 + r < M) st4(Y + (r0 + r) * 128 + col, o);
+                    if (r0 + r < M) st4_next(Yt, yoff + r * 512, o);
                     pd[r] = dot4(o, cu.out ? ov[q] : yv[q]);
                     ps[r] = dot4(o, o2v[q]);
                 }
@@ -273,7 +279,7 @@ __device__ __forceinline__ void linear128_body(float* sBt, const float* __restri
                         fma4(o, z.x, ra_a[0]);  fma4(o, z.y, ra_a[1]);  fma4(o, z.z, ra_a[2]);  fma4(o, z.w, ra_a[3]);
                     }
                 }
-                st4(Y + (r0 + r) * 128 + col, o);
+                if (POL) st4_next(Yt, yoff + r * 512, o); else st4(Y + (r0 + r) * 128 + col, o);
             }
             __builtin_amdgcn_sched_barrier(0);               // one row at a time: four interleaved Philox chains cost 60 VGPRs
         }
