@@ -198,6 +198,10 @@ SIGNATURES = {
     "fn_encoder_forward": [C.POINTER(Encoder), vp, vp, vp, vp, vp],
     "fn_encoder_forward_masked": [C.POINTER(Encoder), C.POINTER(RowMasks), vp, vp, vp, vp, vp],
     "fn_encoder_forward_attn": [C.POINTER(Encoder), C.POINTER(AttnReadout), vp, vp, vp, vp, vp],
+    "fn_encoder_keep_ws_floats": [C.POINTER(Encoder)],
+    "fn_encoder_forward_keep": [C.POINTER(Encoder), vp, vp, vp, vp, vp, vp],
+    "fn_select_rows_u8": [vp, i64, i64, vp, C.c_double, vp, vp],
+    "fn_sample_rows_u8": [u64, u64, vp, i64, i64, vp, C.c_double, vp, vp],
     "fn_loo_row_masks_u8": [vp, i64, vp, vp, vp, vp, i64, vp, i64, vp, i64, vp, vp],
     "fn_encoder_backward": [C.POINTER(Encoder), vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(LayerWeights), vp, i64, vp],
     "fn_encoder_backward_inputs": [C.POINTER(Encoder), vp, i64, C.POINTER(InputGrads), vp],

@@ -382,11 +382,15 @@ struct EncPrologue {
     float* bt_base;
     int n_t;                                                        // 24 blocks per matrix
     const float* dx;  float* dy;  int64_t dnumel;  float p;  uint64_t seed, offset;  const uint64_t* offset_dev;  int n_d;
+    const uint8_t* dgate;  int dgate_w;                             // fn_encoder_forward_keep: the input gate of x_atoms (null: none), one byte per dgate_w elements
     const float* sx[2];  float* so[2];  int sK[2];  fn_gat_plan spl[2];  int n_s[2];
     const float* ssr[2];  const float* sss[2];  float* sso[2];  int n_ss[2];   // the same two attributes in SOURCE order (one-pass backward): from raw, else from sorted
     float* zp;  int64_t zn;  int n_z;                               // buffer zeroed once per forward (edge-term scratch: loop positions stay 0)
     MolExtArgs mx;  int n_x;                                        // molecule extents for the molecule-resident backward (256 molecules per block)
 };
+// GATED: the gated pass's instance (fn_encoder_forward_keep).  An instance of its own, so that the plain pass's dropout range carries no
+// test of the gate pointer
+template <bool GATED>
 __global__ __launch_bounds__(256) void k_enc_prologue(EncPrologue A) {
     __shared__ float tile[32][33];
     int b = blockIdx.x;
@@ -397,7 +401,8 @@ __global__ __launch_bounds__(256) void k_enc_prologue(EncPrologue A) {
     }
     b -= A.n_t;
     if (b < A.n_d) {
-        dropout_act_body<false>(A.dx, nullptr, A.dy, A.dnumel, A.p, A.seed, A.offset, A.offset_dev, 0, b, A.n_d);
+        if (GATED) dropout_act_body<false>(A.dx, nullptr, A.dy, A.dnumel, A.p, A.seed, A.offset, A.offset_dev, 0, b, A.n_d, A.dgate, A.dgate_w);
+        else dropout_act_body<false>(A.dx, nullptr, A.dy, A.dnumel, A.p, A.seed, A.offset, A.offset_dev, 0, b, A.n_d);
         return;
     }
     b -= A.n_d;
@@ -845,7 +850,7 @@ struct LayerActs {
 
 struct EncLayout {
     LayerActs L[FN_MAX_LAYERS];
-    float* in_atoms0;        // dropout(x_atoms) when training with p > 0, else null (use x_atoms)
+    float* in_atoms0;        // dropout(x_atoms) when training with p > 0 or gate(x_atoms) of a gated pass, else null (use x_atoms)
     // forward scratch (s_dst / s_src: a level's node scalars; the bond level's pair is sized for the largest index space and also
     // serves the fragment graph, which runs when the bond level is done)
     float *atoms_new, *frags_new, *s_sorted, *s_dst[kLevels], *s_src[kLevels], *bt;
@@ -875,15 +880,15 @@ bool one_pass_on(const fn_encoder* e) {
 // fn_encoder_backward refuses a descriptor whose form -- read from the process-wide tuning table -- is no longer the one its forward
 // wrote the workspace in (FN_TUNE_BWD_ONE flipped in between would leave out2 / sigma null or unwritten for the other half).
 int enc_form(const fn_encoder* e) { return one_pass_on(e) ? 1 : 0; }
-struct FormLatch { const float* ws; int form; };
+struct FormLatch { const float* ws; int form; bool gated; };     // gated: the forward ran with an input gate (fn_encoder_forward_keep)
 FormLatch g_form_latch[64];
 int g_form_latch_next = 0;
 std::mutex g_form_latch_mu;
-void latch_form(const fn_encoder* e) {
+void latch_form(const fn_encoder* e, bool gated) {
     std::lock_guard<std::mutex> lk(g_form_latch_mu);
     for (FormLatch& f : g_form_latch)
-        if (f.ws == e->ws) { f.form = enc_form(e);  return; }
-    g_form_latch[g_form_latch_next] = FormLatch{e->ws, enc_form(e)};
+        if (f.ws == e->ws) { f.form = enc_form(e);  f.gated = gated;  return; }
+    g_form_latch[g_form_latch_next] = FormLatch{e->ws, enc_form(e), gated};
     g_form_latch_next = (g_form_latch_next + 1) % 64;
 }
 bool form_matches_forward(const fn_encoder* e) {      // (a workspace this process ran no forward into: nothing to compare with)
@@ -892,8 +897,16 @@ bool form_matches_forward(const fn_encoder* e) {      // (a workspace this proce
         if (f.ws == e->ws && f.ws) return f.form == enc_form(e);
     return true;
 }
+// did the last forward pass into this workspace run with an input gate?  Its backward then reads the gated copy of x_atoms, which
+// with p_eff == 0 lives behind the plain workspace (enc_layout's `gated`)
+bool forward_was_gated(const fn_encoder* e) {
+    std::lock_guard<std::mutex> lk(g_form_latch_mu);
+    for (const FormLatch& f : g_form_latch)
+        if (f.ws == e->ws && f.ws) return f.gated;
+    return false;
+}
 
-EncLayout enc_layout(const fn_encoder* e, float* ws) {
+EncLayout enc_layout(const fn_encoder* e, float* ws, bool gated = false) {
     EncLayout o{};
     Bump b(ws);
     const int H = e->heads;
@@ -933,6 +946,8 @@ EncLayout enc_layout(const fn_encoder* e, float* ws) {
     }
     o.bt = b.take((int64_t)3 * e->n_layers * 192 * FN_D);
     o.mol_ext = e->n_mols > 0 ? b.take(e->n_mols * (int64_t)(sizeof(MolExt) / sizeof(float))) : nullptr;
+    // a gated pass without dropout keeps its gated copy of x_atoms behind everything else: no other offset moves
+    if (gated && !drop) o.in_atoms0 = b.take(e->N * e->k_atom0);
     o.total = b.used;
     return o;
 }
@@ -1649,13 +1664,14 @@ int encoder_backward_one(const fn_encoder* e, const EncLayout& lay, const BwdLay
 
 // forward declaration: the pass behind fn_encoder_forward and fn_encoder_forward_masked (defined with them, below)
 static int encoder_forward_impl(const fn_encoder* e, const fn_row_masks* masks, const fn_attn_readout* readout, float* out_atoms,
-                                float* out_frags, float* out_bond, float* out_fbond, fn_stream_t st);
+                                float* out_frags, float* out_bond, float* out_fbond, fn_stream_t st, const uint8_t* keep_atoms = nullptr);
 
 extern "C" {
 
 int fn_encoder_fused_tail(const fn_encoder* e) { return e && tail_mol_on(e) ? 1 : 0; }
 
 int64_t fn_encoder_ws_floats(const fn_encoder* e) { return e ? enc_layout(e, nullptr).total : 0; }
+int64_t fn_encoder_keep_ws_floats(const fn_encoder* e) { return e ? enc_layout(e, nullptr, true).total : 0; }
 int64_t fn_encoder_bwd_ws_floats(const fn_encoder* e) { return e ? bwd_layout(e, nullptr).total : 0; }
 uint64_t fn_encoder_rng_blocks(const fn_encoder* e) { return e ? rng_plan(e).total : 0; }
 
@@ -1676,6 +1692,15 @@ int fn_encoder_forward_masked(const fn_encoder* e, const fn_row_masks* m, float*
     return encoder_forward_impl(e, m, nullptr, out_atoms, out_frags, out_bond, out_fbond, st);
 }
 
+int fn_encoder_forward_keep(const fn_encoder* e, const uint8_t* keep_atoms, float* out_atoms, float* out_frags, float* out_bond,
+                            float* out_fbond, fn_stream_t st) {
+    if (!keep_atoms) return encoder_forward_impl(e, nullptr, nullptr, out_atoms, out_frags, out_bond, out_fbond, st);
+    // everything a gated pass can be refused for is decided here, before the first launch
+    FN_TRY(enc_check(e));
+    if (e->variant != 0) return fail(FN_EUNSUPPORTED, "fn_encoder_forward_keep: the input gate exists for variant 0 (gat2): the reference masks atoms in FragNetPreTrainMasked2 only");
+    return encoder_forward_impl(e, nullptr, nullptr, out_atoms, out_frags, out_bond, out_fbond, st, keep_atoms);
+}
+
 int fn_encoder_forward_attn(const fn_encoder* e, const fn_attn_readout* r, float* out_atoms, float* out_frags, float* out_bond,
                             float* out_fbond, fn_stream_t st) {
     if (!r || (!r->atoms && !r->frags && !r->bonds && !r->fbonds)) return encoder_forward_impl(e, nullptr, nullptr, out_atoms, out_frags, out_bond, out_fbond, st);
@@ -1693,15 +1718,17 @@ int fn_encoder_forward_attn(const fn_encoder* e, const fn_attn_readout* r, float
 // The fragment graph has no mask (gat2.py has none), and everything behind the three levels reads stored rows.
 // readout != null (never together with masks; the caller has checked variant 0 and an evaluation pass): the last layer's levels store
 // their probabilities whatever no_backward says, and ONE more launch behind the last level sums them by source (attn_readout.hip).
+// keep_atoms != null (never together with masks or a read-out; the caller has checked variant 0): the input gate of x_atoms, folded into
+// the prologue's dropout block range; everything behind it reads the gated (and dropped) copy through the atom level's view.
 static int encoder_forward_impl(const fn_encoder* e, const fn_row_masks* masks, const fn_attn_readout* readout, float* out_atoms,
-                                float* out_frags, float* out_bond, float* out_fbond, fn_stream_t st) {
+                                float* out_frags, float* out_bond, float* out_fbond, fn_stream_t st, const uint8_t* keep_atoms) {
     FN_TRY(enc_check(e));
     if (!out_atoms || !out_frags) return fail(FN_EINVAL, "fn_encoder_forward: null output");
     if ((out_bond == nullptr) != (out_fbond == nullptr)) return fail(FN_EINVAL, "fn_encoder_forward: out_bond and out_fbond are wanted together or not at all");
     if (e->pooled && !tail_mol_on(e)) return fail(FN_EINVAL, "fn_encoder_forward: the readout is only produced by the fused fragment tail (fn_encoder_fused_tail)");
-    const EncLayout lay = enc_layout(e, e->ws);
+    const EncLayout lay = enc_layout(e, e->ws, keep_atoms != nullptr);
     if (lay.total > e->ws_floats) return fail(FN_EINVAL, "fn_encoder_forward: workspace too small");
-    latch_form(e);
+    latch_form(e, keep_atoms != nullptr);
     const RngPlan rng = rng_plan(e);
     const int H = e->heads;
     const float p = e->training ? e->drop_p : 0.f;
@@ -1732,6 +1759,7 @@ static int encoder_forward_impl(const fn_encoder* e, const fn_row_masks* masks, 
         if (lay.in_atoms0) {
             A.dx = e->x_atoms;  A.dy = lay.in_atoms0;  A.dnumel = e->N * e->k_atom0;  A.p = p;  A.seed = e->seed;
             A.offset = rng.in_atoms;  A.offset_dev = e->offset_dev;
+            A.dgate = keep_atoms;  A.dgate_w = e->k_atom0;
             A.n_d = flat_grid((A.dnumel + 3) / 4, 512);
         }
         if (e->cos_raw && e->bond.m > 0) {
@@ -1762,7 +1790,9 @@ static int encoder_forward_impl(const fn_encoder* e, const fn_row_masks* masks, 
         if (fuse_rd) {
             A.zp = lay.s_sorted;  A.zn = e->atom.m * H;  A.n_z = flat_grid(A.zn, 64);
         }
-        hipLaunchKernelGGL(k_enc_prologue, dim3(A.n_t + A.n_d + A.n_s[0] + A.n_s[1] + A.n_ss[0] + A.n_ss[1] + A.n_z + A.n_x), dim3(256), 0, S(st), A);
+        const dim3 grid(A.n_t + A.n_d + A.n_s[0] + A.n_s[1] + A.n_ss[0] + A.n_ss[1] + A.n_z + A.n_x);
+        if (keep_atoms) hipLaunchKernelGGL(k_enc_prologue<true>, grid, dim3(256), 0, S(st), A);
+        else hipLaunchKernelGGL(k_enc_prologue<false>, grid, dim3(256), 0, S(st), A);
         FN_TRY(launch_status("fn_encoder_forward: prologue"));
     }
 
@@ -1945,7 +1975,8 @@ int fn_encoder_backward(const fn_encoder* e, const float* out_atoms, const float
         return fail(FN_EINVAL, "fn_encoder_backward: the forward pass of this descriptor saved nothing for a backward pass (fn_encoder.no_backward)");
     if (!form_matches_forward(e))
         return fail(FN_EINVAL, "fn_encoder_backward: FN_TUNE_BWD_ONE changed since the forward pass that wrote this workspace");
-    const EncLayout lay = enc_layout(e, e->ws);
+    const EncLayout lay = enc_layout(e, e->ws, forward_was_gated(e));      // a gated forward: layer 0's weight gradient reads the gated copy
+    if (lay.total > e->ws_floats) return fail(FN_EINVAL, "fn_encoder_backward: workspace too small");
     const BwdLayout bw = bwd_layout(e, scratch);
     if (bw.total > scratch_floats) return fail(FN_EINVAL, "fn_encoder_backward: scratch too small");
     const RngPlan rng = rng_plan(e);
@@ -2038,6 +2069,8 @@ int fn_encoder_backward_inputs(const fn_encoder* e, const float* scratch, int64_
         return fail(FN_EINVAL, "fn_encoder_backward_inputs: the forward pass of this descriptor saved nothing for a backward pass (fn_encoder.no_backward)");
     if (!form_matches_forward(e))
         return fail(FN_EINVAL, "fn_encoder_backward_inputs: FN_TUNE_BWD_ONE changed since the forward pass that wrote this workspace");
+    if (forward_was_gated(e))
+        return fail(FN_EUNSUPPORTED, "fn_encoder_backward_inputs: the forward pass ran with an input gate (fn_encoder_forward_keep); there are no input gradients of a masked pass");
     const BwdLayout bw = bwd_layout(e, const_cast<float*>(scratch));
     if (bw.total > scratch_floats) return fail(FN_EINVAL, "fn_encoder_backward_inputs: scratch too small");
     const fn_layer_weights& w0 = e->w[0];

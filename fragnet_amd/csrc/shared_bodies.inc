@@ -6,7 +6,9 @@
 template <bool BWD>
 __device__ __forceinline__ void dropout_act_body(const float* __restrict__ a, const float* __restrict__ y_saved, float* __restrict__ o,
                                                  int64_t numel, float p, uint64_t seed, uint64_t offset, const uint64_t* offset_dev,
-                                                 int relu, int vb, int nb) {
+                                                 int relu, int vb, int nb, const uint8_t* __restrict__ gate = nullptr, int gate_w = 1) {
+    // gate (the engine's prologue only: fn_encoder_forward_keep): one byte per row of gate_w elements, zero = the row reads as zero
+    // BEFORE the mask is applied; the Philox words are those of the ungated tensor
     const int64_t n4 = (numel + 3) / 4;
     if (offset_dev) offset += *offset_dev;
     const float inv_keep = p < 1.f ? 1.f / (1.f - p) : 0.f;
@@ -19,7 +21,17 @@ __device__ __forceinline__ void dropout_act_body(const float* __restrict__ a, co
         }
         const int64_t e0 = i * 4;
         if (e0 + 3 < numel) {
-            const float4 v = ld4(a + e0);
+            float4 v = ld4(a + e0);
+            if (gate) {      // one division per four elements: the row of e0, then walk (a row of fewer than four elements is walked past)
+                int64_t row = e0 / gate_w;
+                int rem = (int)(e0 - row * gate_w);
+                float* V = &v.x;
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    if (!gate[row]) V[q] = 0.f;
+                    if (++rem == gate_w) { rem = 0;  ++row; }
+                }
+            }
             float4 res;
             if (!BWD) {
                 res = make_float4(v.x * m[0], v.y * m[1], v.z * m[2], v.w * m[3]);
@@ -32,7 +44,7 @@ __device__ __forceinline__ void dropout_act_body(const float* __restrict__ a, co
             st4(o + e0, res);
         } else {
             for (int q = 0; q < 4 && e0 + q < numel; ++q) {
-                float v = a[e0 + q] * m[q];
+                float v = (gate && !gate[(e0 + q) / gate_w] ? 0.f : a[e0 + q]) * m[q];
                 if (!BWD) { if (relu) v = fmaxf(v, 0.f); }
                 else if (relu && !(y_saved[e0 + q] > 0.f)) v = 0.f;
                 o[e0 + q] = v;

@@ -89,7 +89,7 @@ def _describe(plan: GraphPlan, x_atoms, bond_nodes, fbond_nodes, cos_sorted, fat
 class _EncoderFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x_atoms, bond_nodes, fbond_nodes, cos_sorted, fattr_sorted, plan, n_layers, heads, drop_p, training,
-                seed, offset, offset_dev, variant, no_backward, edge_outputs, *params):
+                seed, offset, offset_dev, variant, no_backward, edge_outputs, keep_atoms, *params):
         x_atoms, bond_nodes, fbond_nodes = _f32(x_atoms, "x_atoms"), _f32(bond_nodes, "node_features_bonds"), _f32(fbond_nodes, "node_features_fbonds")
         ctx.param_objs, ctx.slots = params, [ops.grad_slot(p) for p in params]
         params = tuple(_f32(p, "parameter") for p in params)
@@ -97,7 +97,8 @@ class _EncoderFn(torch.autograd.Function):
         lib = _lib.load()
         e = _describe(plan, x_atoms, bond_nodes, fbond_nodes, cos_sorted, fattr_sorted, params, n_layers, heads, drop_p,
                       training, seed, offset, offset_dev, variant, no_backward)
-        ws = torch.empty(lib.fn_encoder_ws_floats(C.byref(e)), dtype=torch.float32, device=dev)
+        # keep_atoms: the input gate of x_atoms (fn_encoder_forward_keep); its gated copy may live behind the plain workspace
+        ws = torch.empty((lib.fn_encoder_ws_floats if keep_atoms is None else lib.fn_encoder_keep_ws_floats)(C.byref(e)), dtype=torch.float32, device=dev)
         e.ws, e.ws_floats = ws.data_ptr(), ws.numel()
         # edge_outputs = False: the caller reads neither the bond nor the fragment-bond output (a finetune head): the library gets NULL for
         # them and does not store the last layer's activated rows; two empty, non-differentiable tensors stand in
@@ -108,14 +109,17 @@ class _EncoderFn(torch.autograd.Function):
         if lib.fn_encoder_fused_tail(C.byref(e)):
             pooled = torch.empty((e.n_mols, 2 * FN_D), dtype=torch.float32, device=dev)
             e.pooled = pooled.data_ptr()
-        _lib.check(lib.fn_encoder_forward(C.byref(e), *((o.data_ptr() if (edge_outputs or k < 2) else None) for k, o in enumerate(outs)),
-                                          _stream_ptr(dev)), "fn_encoder_forward")
+        out_ptrs = [(o.data_ptr() if (edge_outputs or k < 2) else None) for k, o in enumerate(outs)]
+        if keep_atoms is None:
+            _lib.check(lib.fn_encoder_forward(C.byref(e), *out_ptrs, _stream_ptr(dev)), "fn_encoder_forward")
+        else:
+            _lib.check(lib.fn_encoder_forward_keep(C.byref(e), keep_atoms.data_ptr(), *out_ptrs, _stream_ptr(dev)), "fn_encoder_forward_keep")
         e.pooled = None
         plan.pending.pop("bond", None)
         plan.pending.pop("frag" if variant == 2 else "fbond", None)
         e.cos_raw = e.fattr_raw = None           # the backward pass reads the sorted copies only
         ctx.desc = e
-        ctx.keep = (plan, x_atoms, bond_nodes, fbond_nodes, cos_sorted, fattr_sorted, ws, offset_dev)
+        ctx.keep = (plan, x_atoms, bond_nodes, fbond_nodes, cos_sorted, fattr_sorted, ws, offset_dev, keep_atoms)
         ctx.n_layers = n_layers
         ctx.variant = int(variant)
         ctx.edge_outputs = bool(edge_outputs)
@@ -174,7 +178,7 @@ class _EncoderFn(torch.autograd.Function):
                 if ctx.variant == 2 and (k in EDGE_DEAD or (k in EDGE_LAST_ONLY and not (l == n_layers - 1 and have_frags))):
                     live = False
                 out.append(grads[l * NP + k] if live else None)
-        return tuple(g_in) + (None,) * 13 + tuple(out)
+        return tuple(g_in) + (None,) * 14 + tuple(out)
 
 
 def _input_grads(ctx, e, scratch, need, dev):
@@ -326,7 +330,7 @@ def _attn_forward(plan, x_atoms, bond_nodes, fbond_nodes, cos_sorted, fattr_sort
 
 def encoder_forward(layers, plan: GraphPlan, x_atoms, bond_nodes, fbond_nodes, cos_sorted, fattr_sorted, heads: int,
                     drop_p: float, training: bool, rng, variant: int = 0, edge_outputs: bool = True, row_masks=None,
-                    attn_readout: bool = False) -> tuple:
+                    attn_readout: bool = False, keep_atoms=None) -> tuple:
     """Runs all ``layers`` (FragNetLayerA modules) + the inter-layer act(dropout(.)); returns the four outputs and, fifth,
     the readout [n_mols, 256] when the fused fragment tail produced it (an empty tensor otherwise).
 
@@ -337,7 +341,12 @@ def encoder_forward(layers, plan: GraphPlan, x_atoms, bond_nodes, fbond_nodes, c
 
     ``row_masks``: None, or a triple (atoms [N], bonds [E], fragment bonds [EF]) of uint8 CUDA tensors or None -- 1 = that row of
     the level's output is zero for every reader, in every layer (fn_encoder_forward_masked).  A masked pass is an evaluation pass
-    without a backward: in training mode, or with a gradient required anywhere, it raises."""
+    without a backward: in training mode, or with a gradient required anywhere, it raises.
+
+    ``keep_atoms``: None, or a uint8 CUDA tensor [N], 1 = keep -- the input gate of masked-atom pretraining (fn_encoder_forward_keep):
+    a row of ``x_atoms`` with 0 reads as zero for every consumer, gated before the input dropout, in the prologue's own pass over
+    ``x_atoms``.  Training passes (with a backward) and evaluation passes alike; model_version gat2 only; not together with row
+    masks or the attention read-out, and not with a gradient required on the three input tables."""
     params = [p for layer in layers for p in layer_param_list(layer)]
     n_layers = len(layers)
     # the C side takes widths from the batch and pointers from the parameters: a model built for other feature widths would
@@ -350,6 +359,16 @@ def encoder_forward(layers, plan: GraphPlan, x_atoms, bond_nodes, fbond_nodes, c
                                f"layer 0 {name} expects {w.shape[-1]} input features, the batch has {x.shape[-1]}")
     if row_masks is not None and len(row_masks) != 3:
         raise ValueError("row_masks: a triple (atoms, bonds, fragment bonds)")
+    if keep_atoms is not None:
+        if attn_readout or (row_masks is not None and any(t is not None for t in row_masks)):
+            raise ValueError("keep_atoms: the input gate does not combine with row masks or the attention read-out")
+        if int(variant) != 0:
+            raise ValueError("keep_atoms: the input gate exists for model_version gat2 (the reference masks atoms in FragNetPreTrainMasked2 only)")
+        if not torch.is_tensor(keep_atoms) or keep_atoms.dtype != torch.uint8 or not keep_atoms.is_cuda or keep_atoms.dim() != 1 or \
+                keep_atoms.numel() != x_atoms.shape[0] or not keep_atoms.is_contiguous():
+            raise ValueError(f"keep_atoms must be a contiguous uint8 CUDA tensor of {x_atoms.shape[0]} rows (1 = keep, 0 = the row reads as zero)")
+        if torch.is_grad_enabled() and any(t.requires_grad for t in (x_atoms, bond_nodes, fbond_nodes)):
+            raise NotImplementedError("keep_atoms: there are no input gradients of a masked pass (fn_encoder_backward_inputs refuses it)")
     if attn_readout:
         if row_masks is not None and any(t is not None for t in row_masks):
             raise ValueError("attn_readout: there is no attention read-out of a masked pass (row_masks)")
@@ -387,4 +406,4 @@ def encoder_forward(layers, plan: GraphPlan, x_atoms, bond_nodes, fbond_nodes, c
     # stores nothing for one (fn_encoder.no_backward).  (Inside Function.forward grad mode is always off: it is read here.)
     no_backward = not _EVAL_SAVES and not (torch.is_grad_enabled() and any(t.requires_grad for t in (x_atoms, bond_nodes, fbond_nodes, *params)))
     return _EncoderFn.apply(x_atoms, bond_nodes, fbond_nodes, cos_sorted, fattr_sorted, plan, n_layers, heads, p_eff,
-                            bool(training), seed, offset, rng.dev if p_eff > 0.0 else None, int(variant), no_backward, bool(edge_outputs), *params)
+                            bool(training), seed, offset, rng.dev if p_eff > 0.0 else None, int(variant), no_backward, bool(edge_outputs), keep_atoms, *params)

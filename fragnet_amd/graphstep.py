@@ -33,7 +33,7 @@ import torch
 import os
 
 from . import _lib
-from .plan import LIVE_MOLS_KEY, PLAN_KEY, REAL_MOLS_KEY, SPACES, CollatedBatch, prezeroed_plans
+from .plan import LIVE_MOLS_KEY, PLAN_KEY, REAL_ATOMS_KEY, REAL_MOLS_KEY, SPACES, CollatedBatch, prezeroed_plans
 
 # field -> (index space of the ragged axis, layout, index space its VALUES point into)
 FIELDS = {
@@ -290,6 +290,22 @@ class StaticBatch:
             raise ValueError("too many batch fields for one staging launch")
         self.counts: Optional[Dict[str, int]] = None
         self._n_static = self.n_fields
+        self._extra_counts = []          # add_count: (field index, space)
+
+    def add_count(self, space: str, key: str) -> torch.Tensor:
+        """One more device-side count written by the staging launch: ``self.t[key]`` = int32 [1], the number of REAL rows of ``space``
+        in the staged batch (the masked-atom sampler reads the real atom count there).  Before set_bumps."""
+        if self.n_fields != self._n_static:
+            raise RuntimeError("add_count comes before set_bumps")
+        if self.n_fields >= _lib.FN_MAX_STAGE_FIELDS:
+            raise ValueError("too many batch fields for one staging launch")
+        self.t[key] = torch.zeros(1, dtype=torch.int32, device=self.device)
+        c = self._fields[self.n_fields]
+        c.src, c.dst, c.n_real, c.cap, c.width, c.kind, c.pad_hi, c.pad_mod = None, self.t[key].data_ptr(), 0, 1, 1, _lib.STAGE_COUNT, 0, 1
+        self._extra_counts.append((self.n_fields, space))
+        self.n_fields += 1
+        self._n_static = self.n_fields
+        return self.t[key]
 
     def set_bumps(self, bumps, zeros=()):
         """Extra work of the staging launch in front of every replay of a captured step.  ``bumps`` = [(int64 device tensor
@@ -335,6 +351,8 @@ class StaticBatch:
             m.src, m.n_real = None, counts[space]
         c = self._fields[len(self._desc) + len(self._mask_spaces)]
         c.src, c.n_real = None, counts["mol"]
+        for i, space in self._extra_counts:
+            self._fields[i].n_real = counts[space]
         _lib.call("fn_stage_padded", self._fields, self.n_fields, torch.cuda.current_stream(self.device).cuda_stream)
         self.counts = counts
         self._keep = (keep, batch.offsets if self.with_offsets else None)       # alive until the launch has run
@@ -392,6 +410,17 @@ class GraphedTrainStep:
         # replays the device counter is ONE STEP BEHIND when _stage_bumps is set -- the staging launch in front of every
         # replay moves it on -- so anything that replays without staging (or stages without replaying) must go through replay()
         self._rng_base, self._per_step, self._stage_bumps = 0, 0, False
+        # a masked-atom model (FragNetPreTrainMasked2) draws its row mask inside the step, from a stream of its own: the sampler launch is
+        # captured behind the staging / plan launches, reads the real atom count the staging launch writes, and its device counter is kept
+        # exactly like the dropout counter's (baked host offset + a device word the staging launch moves on; the same invariant)
+        self.mask_rng = getattr(model, "mask_rng", None) if loss == "pretrain" else None
+        self._mask_base, self._mask_per_step = 0, 0
+        self.keep_mask: Optional[torch.Tensor] = None      # the latest step's mask (uint8 [atom capacity]): a persistent buffer, for tests and tools
+        if self.mask_rng is not None:
+            self._mask_counter = torch.zeros(1, dtype=torch.int64, device=self.device)
+            self.mask_rng.dev = self._mask_counter
+            self.static.add_count("atom", REAL_ATOMS_KEY)
+            self.keep_mask = model.keep_buffer = torch.ones(shapes.cap["atom"], dtype=torch.uint8, device=self.device)
         from . import ops
         self._unit = ops.unit_grad(self.static.device)
         self.graph_b: Optional[torch.cuda.CUDAGraph] = None
@@ -497,6 +526,7 @@ class GraphedTrainStep:
             for _ in range(warmup):
                 self.opt.zero_grad()
                 before = self.rng.offset
+                mask_before = self.mask_rng.offset if self.mask_rng is not None else 0
                 if self.split:
                     _, pooled_t, leaf = self._part_a()
                     if not self._head_grads_in_place():      # e.g. a non-ReLU head (torch's own backward): one graph
@@ -510,6 +540,8 @@ class GraphedTrainStep:
                     off = self._head_offset()
                     self._rider_lo = off if (off is not None and off % 4 == 0 and self._head_grads_in_place()) else None
                 per_step = self.rng.offset - before              # Philox blocks one step draws (fixed by the static shapes)
+                if self.mask_rng is not None:
+                    self._mask_per_step = self.mask_rng.offset - mask_before
         torch.cuda.current_stream(self.device).wait_stream(side)
         torch.cuda.synchronize(self.device)
         self.opt.zero_grad()
@@ -520,6 +552,8 @@ class GraphedTrainStep:
         self._sync_adam_state()
         graph = torch.cuda.CUDAGraph()
         off0 = self._rng_base = self.rng.offset
+        if self.mask_rng is not None:
+            self._mask_base = self.mask_rng.offset
         if self.split:
             pool = torch.cuda.graph_pool_handle()
             with torch.cuda.graph(graph, pool=pool, capture_error_mode=_CAPTURE_MODE):
@@ -537,6 +571,8 @@ class GraphedTrainStep:
                 loss, rode = self._fwd_bwd_static(ride_adam=self.adam_in_graph)
                 if self.rng.offset - off0 != per_step:
                     raise RuntimeError("the captured step drew a different number of Philox blocks than the warm-up steps")
+                if self.mask_rng is not None and self.mask_rng.offset - self._mask_base != self._mask_per_step:
+                    raise RuntimeError("the captured step drew a different number of mask blocks than the warm-up steps")
                 # fresh dropout masks and the next Adam step number on every replay: the staging launch in front of the replay
                 # advances both counters (FN_STAGE_BUMP), so the graph has no launch of its own for them
                 if self.adam_in_graph:
@@ -552,6 +588,9 @@ class GraphedTrainStep:
                 self._counters[0:1] -= per_step
             if self.adam_in_graph:
                 bumps.append((self._counters[1:2], 1))
+            if self.mask_rng is not None and self._mask_per_step:
+                bumps.append((self._mask_counter, self._mask_per_step))
+                self._mask_counter -= self._mask_per_step
             self._captured_plans = pz.plans          # keep their arenas (the regions below) alive with the graph
             self.static.set_bumps(bumps, zeros=[r for plan in pz.plans for r in plan.zero_regions])
 
@@ -589,6 +628,12 @@ class GraphedTrainStep:
         behind = self._per_step if self._stage_bumps else 0      # see _capture: the staging launch bumps the counter
         if behind:
             self._counters[0:1] += behind
+        mask_after = mask_behind = 0
+        if self.mask_rng is not None:        # the mask stream, the same way: this step's masks come from where the replay's would
+            mask_after, self.mask_rng.offset = self.mask_rng.offset, self._mask_base
+            mask_behind = self._mask_per_step if self._stage_bumps else 0
+            if mask_behind:
+                self._mask_counter += mask_behind
         if self.loss_kind == "pretrain":
             from .train import pretrain_loss
             sc = self._rank_scales(batch)
@@ -613,6 +658,11 @@ class GraphedTrainStep:
         if drawn - behind:
             self._counters[0:1] += drawn - behind
         self.rng.offset = host_after
+        if self.mask_rng is not None:
+            mask_drawn = self.mask_rng.offset - self._mask_base
+            if mask_drawn - mask_behind:
+                self._mask_counter += mask_drawn - mask_behind
+            self.mask_rng.offset = mask_after
         return loss.detach()
 
     def replay(self, batch: Dict[str, torch.Tensor]) -> bool:

@@ -28,7 +28,7 @@ import torch.nn.functional as F
 
 from . import _lib, engine, ops
 from ._lib import FN_D
-from .plan import LIVE_MOLS_KEY, plan_for
+from .plan import LIVE_MOLS_KEY, REAL_ATOMS_KEY, plan_for
 
 # dev switch for A/B measurements: the finetune models ask the encoder for its bond / fragment-bond outputs although they read neither
 _KEEP_EDGE_OUTPUTS = os.environ.get("FRAGNET_KEEP_EDGE_OUTPUTS", "0") == "1"
@@ -294,6 +294,17 @@ class FragNet(nn.Module):
         plan = plan_for(batch)
         p, train = self.dropout.p, self.training
         row_masks = batch_row_masks(batch)
+        keep_atoms = batch.get(KEEP_KEY)
+        if keep_atoms is not None:
+            # the input gate of masked-atom pretraining (engine.encoder_forward's keep_atoms): on the engine's gat2 path only
+            if row_masks is not None:
+                raise ValueError(f"{KEEP_KEY}: the input gate does not combine with row masks ({', '.join(MASK_KEYS)})")
+            if self.variant != "gat2":
+                raise ValueError(f"{KEEP_KEY}: model_version {self.variant!r} has no input gate (gat2 only)")
+            if not self.use_engine or any(l.return_attentions or l.bond_mask is not None or l.frag_bond_mask is not None
+                                          or l.atom_mask_individual is not None for l in self.layers):
+                raise ValueError(f"{KEEP_KEY} runs on the engine only: not with use_engine=False, return_attentions or the per-layer "
+                                 "scalar mask attributes")
         if row_masks is not None:
             return self._forward_masked(batch, plan, row_masks, edge_outputs)
         if self.variant == "gat2_edge" and self.use_engine and not any(l.return_attentions for l in self.layers):
@@ -321,7 +332,7 @@ class FragNet(nn.Module):
             outs = engine.encoder_forward(self.layers, plan, batch["x_atoms"], batch["node_features_bonds"],
                                           batch["node_features_fbonds"], plan.sorted_attr("bond", batch["edge_attr_bonds"], defer=True),
                                           plan.sorted_attr("fbond", batch["edge_attr_fbonds"], defer=True), self.layers[0].num_heads,
-                                          p, train, self.rng, variant=1 if lite else 0, edge_outputs=edge_outputs)
+                                          p, train, self.rng, variant=1 if lite else 0, edge_outputs=edge_outputs, keep_atoms=keep_atoms)
             if outs[4].numel():      # the fused fragment tail also produced the readout: pooled() below hands it out
                 # (with the versions of both tensors at this point: an in-place edit of either -- a mask, an attribution hook --
                 # between the encoder and pooled() must not be answered with the readout of the unedited rows)
@@ -360,6 +371,7 @@ class FragNet(nn.Module):
         return outs[:4]
 
 
+KEEP_KEY = "keep_atoms"       # optional batch key: uint8 [N], 1 = keep, 0 = this row of x_atoms reads as zero (masked-atom pretraining)
 MASK_KEYS = ("mask_atoms", "mask_bonds", "mask_fbonds")      # optional batch keys: uint8 [N] / [E] / [EF], 1 = zero this row in every layer
 
 
@@ -604,3 +616,65 @@ class FragNetPreTrain(nn.Module):
         plan_for(batch, edge_ends=self.head.need_bond_length)      # build the plan once, with the bond-length head's CSRs
         x_atoms, x_frags, e_edge, _ = self.pretrain(batch)
         return self.head(x_atoms, x_frags, e_edge, batch)
+
+
+class FragNetPreTrainMasked2(FragNetPreTrain):
+    """The reference's masked-atom pretraining model (pretrain_heads.py:187-236, model_version gat2_masked2): per call, int(n_atoms *
+    (1 - mask_ratio)) atom rows are kept and the other rows of ``x_atoms`` read as zero; then the ordinary encoder and PretrainTask.
+    Constructor arguments, construction order, RNG consumption and state-dict keys are FragNetPreTrain's (a masked checkpoint feeds
+    finetune_gat2.py through the existing loader).  Like the reference it masks in evaluation mode too.
+
+    The mask is ``batch["keep_atoms"]`` (uint8 [N], 1 = keep) when the batch carries one; otherwise it is drawn on the GPU
+    (ops.sample_rows: an exact-count sample without replacement, keys from ``self.mask_rng``, a Philox stream of its own that is
+    rank-aware like ``pretrain.rng``).  A padded batch of a captured step carries ``real_atoms`` (int32 [1] on the device): the count
+    is taken there, and padding rows are kept.
+
+    Differences from the reference: the rows are chosen by Philox keys, not by Python's ``random.sample`` (the same count, another
+    generator), and ``batch["x_atoms"]`` is NOT overwritten -- the gate is applied inside the engine's pass over the atom features
+    (fn_encoder_forward_keep), the batch keeps its original rows."""
+
+    def __init__(self, num_layer=4, drop_ratio=0.15, num_heads=4, emb_dim=128, atom_features=167,
+                 frag_features=167, edge_features=16, fedge_in=6, fbond_edge_in=6, mask_ratio=0.15):
+        super().__init__(num_layer, drop_ratio, num_heads, emb_dim, atom_features, frag_features, edge_features, fedge_in, fbond_edge_in)
+        if not 0.0 <= float(mask_ratio) <= 1.0:
+            raise ValueError(f"mask_ratio = {mask_ratio}: a fraction in [0, 1]")
+        self.mask_ratio = float(mask_ratio)
+        self.mask_rng = ops.mask_stream()
+        self.last_keep = None        # the mask of the latest forward (tests and tools read it back)
+        self.keep_buffer = None      # optional persistent uint8 buffer the mask is drawn into when its size fits (graphstep: the captured step's)
+
+    @property
+    def keep_frac(self) -> float:
+        # the reference's literal 0.85 for its mask ratio 0.15: 1 - 0.15 in doubles is 0.85 exactly as written
+        return 1.0 - self.mask_ratio
+
+    def draw_keep(self, batch):
+        x = batch["x_atoms"]
+        out = self.keep_buffer
+        if out is not None and (out.numel() != x.shape[0] or out.device != x.device):
+            out = None
+        return ops.sample_rows(x.shape[0], self.keep_frac, self.mask_rng, x.device, n_dev=batch.get(REAL_ATOMS_KEY), out=out)
+
+    def forward(self, batch):
+        keep = batch.get(KEEP_KEY)
+        if keep is None:
+            keep = self.draw_keep(batch)
+        self.last_keep = keep
+        plan_for(batch, edge_ends=self.head.need_bond_length)
+        had = KEEP_KEY in batch
+        batch[KEEP_KEY] = keep              # FragNet.forward hands it to the engine; the batch's x_atoms stays what it was
+        try:
+            x_atoms, x_frags, e_edge, _ = self.pretrain(batch)
+        finally:
+            if not had:
+                del batch[KEEP_KEY]
+        return self.head(x_atoms, x_frags, e_edge, batch)
+
+
+class FragNetPreTrainMasked(FragNetPreTrain):
+    """The reference's first masked model (model_version gat2_masked): constructible, with FragNetPreTrain's keys, but its ``forward``
+    ends without a ``return`` (pretrain_heads.py:174-184), so the reference cannot train it and neither does this class."""
+
+    def forward(self, batch):
+        raise NotImplementedError("FragNetPreTrainMasked: the reference's forward builds a masked copy of the encoder's OUTPUT and returns "
+                                  "None (pretrain_heads.py:174-184); use FragNetPreTrainMasked2 (model_version gat2_masked2)")

@@ -631,9 +631,10 @@ def scatter_softmax(src, index, dim: int = 0, dim_size=None):
 class PhiloxStream:
     """Counter-based dropout stream: (seed, running offset). One Philox block = 4 floats."""
 
-    def __init__(self, seed: Optional[int] = None, rank: int = 0):
+    def __init__(self, seed: Optional[int] = None, rank: int = 0, salt: int = 0):
         self.seed = None if seed is None else (int(seed) & 0xFFFFFFFFFFFFFFFF)
         self.rank = rank
+        self.salt = int(salt)    # xor-ed into a DERIVED seed: a second stream of the same process (mask_stream) gets a key of its own
         self.offset = 0
         self.dev = None          # optional device-resident counter added to every offset when the kernels run
 
@@ -652,7 +653,7 @@ class PhiloxStream:
 
     def take(self, numel: int):
         if self.seed is None:
-            self.seed = (torch.initial_seed() * 0x9E3779B97F4A7C15 + self.rank * 0xD1B54A32D192ED03) & 0xFFFFFFFFFFFFFFFF
+            self.seed = ((torch.initial_seed() * 0x9E3779B97F4A7C15 + self.rank * 0xD1B54A32D192ED03) ^ self.salt) & 0xFFFFFFFFFFFFFFFF
         off = self.offset
         self.offset += (numel + 3) // 4
         return self.seed, off
@@ -688,6 +689,64 @@ def dropout_act(x, p: float, training: bool, relu: bool, rng: PhiloxStream):
         return x
     seed, off = rng.take(x.numel()) if p_eff > 0.0 else (0, 0)
     return _DropoutAct.apply(x, p_eff, relu, seed, off, rng.dev if p_eff > 0.0 else None)
+
+
+MASK_STREAM_SALT = 0xA0761D6478BD642F      # the mask stream's seed derivation: never the dropout stream's (seed, counter) pair
+
+
+def mask_stream(rank: int = 0) -> "PhiloxStream":
+    """A PhiloxStream for row masks (sample_rows): seeded like the dropout stream from torch.initial_seed() and the rank, under a salt
+    of its own, with its own host offset and device counter -- drawing a mask never moves the dropout stream."""
+    return PhiloxStream(rank=rank, salt=MASK_STREAM_SALT)
+
+
+def _row_count(n, n_dev, cap: int, dev):
+    if n_dev is not None:
+        if not torch.is_tensor(n_dev) or n_dev.dtype != torch.int32 or n_dev.numel() != 1 or n_dev.device != dev:
+            raise ValueError("n_dev: a one-element int32 tensor on the output's device (the real row count of a padded batch)")
+        return 0
+    n = cap if n is None else int(n)
+    if not 0 <= n <= cap:
+        raise ValueError(f"n = {n}: the real row count must lie in [0, cap = {cap}]")
+    return n
+
+
+def select_rows(keys: torch.Tensor, keep_frac: float, n: Optional[int] = None, n_dev: Optional[torch.Tensor] = None,
+                out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """uint8 [cap]: 1 on the k = int(n * keep_frac) rows i < n with the smallest (key, index) pairs and on the padding rows n <= i < cap,
+    0 elsewhere (fn_select_rows_u8).  ``keys``: contiguous uint32-valued int32 / uint32 CUDA tensor [cap]; ``n`` defaults to cap;
+    ``n_dev`` (int32 [1] on the device) replaces it and is clamped to [0, cap] by the kernel."""
+    if not keys.is_cuda:
+        raise _lib.FragnetHipError(f"select_rows: the keys must live on the GPU (got {keys.device}); there is no CPU fallback")
+    if keys.dtype not in (torch.int32, torch.uint32) or keys.dim() != 1 or not keys.is_contiguous():
+        raise TypeError("select_rows: keys must be a contiguous one-dimensional int32 / uint32 tensor (the 32 key bits)")
+    cap = keys.numel()
+    if out is None:
+        out = torch.empty(cap, dtype=torch.uint8, device=keys.device)
+    elif out.dtype != torch.uint8 or out.numel() != cap or not out.is_contiguous() or out.device != keys.device:
+        raise ValueError("select_rows: out must be a contiguous uint8 tensor of cap rows on the keys' device")
+    _lib.call("fn_select_rows_u8", keys.data_ptr(), cap, _row_count(n, n_dev, cap, keys.device), _ptr(n_dev), float(keep_frac),
+              out.data_ptr(), _stream_ptr(keys.device))
+    return out
+
+
+def sample_rows(cap: int, keep_frac: float, rng: "PhiloxStream", device, n: Optional[int] = None, n_dev: Optional[torch.Tensor] = None,
+                out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The same selection on keys the kernel draws itself (fn_sample_rows_u8): row i's key is word i % 4 of Philox block
+    offset + i // 4 of ``rng`` (plus its device counter), which moves on by (cap + 3) // 4 blocks -- a function of cap alone, so a
+    captured step and its eager fallback consume the stream alike."""
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise _lib.FragnetHipError(f"sample_rows: masks are drawn on the GPU (got {device}); there is no CPU fallback")
+    cap = int(cap)
+    if out is None:
+        out = torch.empty(cap, dtype=torch.uint8, device=device)
+    elif out.dtype != torch.uint8 or out.numel() != cap or not out.is_contiguous() or out.device != device:
+        raise ValueError("sample_rows: out must be a contiguous uint8 tensor of cap rows on the device")
+    nn_ = _row_count(n, n_dev, cap, device)
+    seed, off = rng.take(cap)
+    _lib.call("fn_sample_rows_u8", seed, off, _ptr(rng.dev), cap, nn_, _ptr(n_dev), float(keep_frac), out.data_ptr(), _stream_ptr(device))
+    return out
 
 
 # ======================================================================================

@@ -375,6 +375,7 @@ def mol_offsets(counts: Dict[str, "torch.Tensor"]) -> "torch.Tensor":
 
 PLAN_KEY = "_fragnet_plan"
 REAL_MOLS_KEY = "_real_mols"      # StaticBatch: device-side count of the real molecules of a padded batch
+REAL_ATOMS_KEY = "_real_atoms"    # StaticBatch.add_count("atom"): device-side count of its real atoms (the masked-atom sampler reads it)
 LIVE_MOLS_KEY = "_live_mols"      # StaticBatch: python int, molecule rows >= this are padding in EVERY batch (capacity - slack)
 N_MOLS_KEY = "_n_mols"            # factored pair batches (data.collate_fn_*_factored): python int, the molecule count -- y has one entry per PAIR there
 

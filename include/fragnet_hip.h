@@ -907,7 +907,34 @@ typedef struct fn_attn_readout {
 } fn_attn_readout;
 int fn_encoder_forward_attn(const fn_encoder* e, const fn_attn_readout* r, float* out_atoms, float* out_frags, float* out_bond,
                             float* out_fbond, fn_stream_t stream);
-/* The three masks of a batch of leave-one-out replicas, zero-filled and set in ONE launch.  replicas: int32 [n_mols][2] = (kind, local
+/* Input gate of the atom features (masked-atom pretraining, the reference's FragNetPreTrainMasked2, pretrain_heads.py:187-236): one
+ * byte per row of x_atoms, ZERO = the row reads as zero for every consumer, non-zero = kept.  The gate is applied BEFORE the input
+ * dropout (the reference zeroes the rows, then FragNet.forward drops out), inside the prologue's existing pass over x_atoms: that
+ * block range writes dropout(gate(x_atoms)) -- with p_eff == 0 (evaluation, or drop_p == 0) a gated copy -- and layer 0's projection
+ * and its weight-gradient product read that copy; no launch is added, and kept rows draw the dropout bits they draw without a gate.
+ * Training passes (fn_encoder_backward may follow: the pass remembers per workspace that it was gated) and evaluation passes with both
+ * values of no_backward.  With p_eff == 0 the gated copy lives behind the plain workspace: e->ws_floats must be at least
+ * fn_encoder_keep_ws_floats(e) (fn_encoder_ws_floats(e) + N * k_atom0, rounded as the workspace rounds).
+ * keep == NULL: fn_encoder_forward itself, bit for bit.  Otherwise variant == 0 is needed (FN_EUNSUPPORTED, before anything is
+ * launched), and fn_encoder_backward_inputs after a gated forward returns FN_EUNSUPPORTED (no input gradients of masked passes).
+ * ABI 12. */
+int64_t fn_encoder_keep_ws_floats(const fn_encoder* e);
+int fn_encoder_forward_keep(const fn_encoder* e, const uint8_t* keep_atoms /*[N], nullable*/, float* out_atoms, float* out_frags,
+                            float* out_bond, float* out_fbond, fn_stream_t stream);
+/* An exact-count sample of rows without replacement, drawn on the device in ONE launch (csrc/row_sample.hip).  Of the n real rows
+ * of a table of cap rows, k = (int)((double)n * keep_frac) are kept -- Python's int(n * keep_frac), the same IEEE double product:
+ * out[i] = 1 for i < n iff fewer than k rows j < n have (key_j, j) < (key_i, i) lexicographically (the k smallest keys, ties broken
+ * by row index: exactly k ones, a function of the keys alone), else 0; padding rows n <= i < cap get 1.  n_dev (nullable device int32)
+ * replaces n when given -- the real row count of a padded batch -- and is clamped to [0, cap] before use.  cap <= 2^24; keep_frac in
+ * [0, 1]; anything else is FN_EINVAL.
+ * fn_select_rows_u8 takes the keys [cap] (those of rows >= n are not read).  fn_sample_rows_u8 generates them: the key of row i is
+ * word i % 4 of Philox block offset + *offset_dev + i / 4 under `seed` -- fn_dropout_act_f32's convention -- so one draw consumes
+ * (cap + 3) / 4 blocks of whatever stream (seed, counter) the caller dedicates to it.  ABI 12. */
+int fn_select_rows_u8(const uint32_t* keys /*[cap]*/, int64_t cap, int64_t n, const int32_t* n_dev, double keep_frac, uint8_t* out /*[cap]*/,
+                      fn_stream_t stream);
+int fn_sample_rows_u8(uint64_t seed, uint64_t offset, const uint64_t* offset_dev, int64_t cap, int64_t n, const int32_t* n_dev,
+                      double keep_frac, uint8_t* out /*[cap]*/, fn_stream_t stream);
+/* The three masks of a batch of leave-one-out replicas, zero-filled and set in ONE launch. replicas: int32 [n_mols][2] = (kind, local
  * index) of molecule i of the batch; kind 0 masks nothing, 1 the atom `index`, 2 the bond `index` (directed rows 2 index, 2 index + 1),
  * 3 the fragment connection `index` (rows 2 index, 2 index + 1), all local to the molecule.  *_off: int32 [n_mols + 1], first row of
  * molecule i in the atom / directed-bond / directed-fragment-connection space (rows of a CollatedBatch's offsets table); they must end

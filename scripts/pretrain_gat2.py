@@ -11,7 +11,28 @@ import torch
 
 from fragnet_amd import parallel, train
 from fragnet_amd.dataset import FlatMolStore
-from fragnet_amd.model import FragNetPreTrain
+from fragnet_amd.model import FragNetPreTrain, FragNetPreTrainMasked2
+
+
+def build_model(args):
+    """The reference's dispatch on ``model_version`` (pretrain_gat2.py:97-128).  gat2 (or no key): FragNetPreTrain; gat2_masked2:
+    FragNetPreTrainMasked2 with ``pretrain.mask_ratio`` (optional, 0.15 = the reference's literal 0.85 kept); gat2_masked: refused, the
+    reference's class cannot train; anything else: refused (the reference would fail later, with ``model`` unbound)."""
+    pt = args.pretrain
+    version = args.get("model_version") or "gat2"
+    kw = dict(num_layer=pt.num_layer, drop_ratio=pt.drop_ratio, num_heads=pt.num_heads, emb_dim=pt.emb_dim,
+              atom_features=args.atom_features, frag_features=args.frag_features,
+              edge_features=args.edge_features, fedge_in=args.fedge_in, fbond_edge_in=args.fbond_edge_in)
+    if version == "gat2":
+        return FragNetPreTrain(**kw)
+    if version == "gat2_masked2":
+        ratio = pt.get("mask_ratio")
+        return FragNetPreTrainMasked2(**kw, mask_ratio=0.15 if ratio is None else float(ratio))
+    if version == "gat2_masked":
+        raise SystemExit("model_version gat2_masked: the reference's FragNetPreTrainMasked.forward returns None (pretrain_heads.py:174-184 "
+                         "ends without a return), so it cannot be trained there either; use gat2_masked2")
+    raise SystemExit(f"model_version {version!r}: pretrain_gat2 knows gat2, gat2_masked2 (and refuses gat2_masked)")
+
 
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
@@ -28,13 +49,13 @@ if __name__ == "__main__":
     exp_dir = args["exp_dir"]
     os.makedirs(exp_dir, exist_ok=True)
     pt = args.pretrain
-    model = FragNetPreTrain(num_layer=pt.num_layer, drop_ratio=pt.drop_ratio, num_heads=pt.num_heads, emb_dim=pt.emb_dim,
-                            atom_features=args.atom_features, frag_features=args.frag_features,
-                            edge_features=args.edge_features, fedge_in=args.fedge_in, fbond_edge_in=args.fbond_edge_in)
+    model = build_model(args)
     if pt.get("saved_checkpoint"):
         model.load_state_dict(torch.load(pt.saved_checkpoint, map_location="cpu"))
     model.to(device)
     model.pretrain.rng.rank = rank
+    if hasattr(model, "mask_rng"):
+        model.mask_rng.rank = rank          # data-parallel ranks draw different masks
     # pretrain.data: list of directories holding train.pt / val.pt flat stores (the reference splits 90/10 itself,
     # pretrain_gat2.py:141; the synthetic stores come pre-split)
     d0 = pt.data[0]

@@ -1,0 +1,378 @@
+"""Masked-atom pretraining on the GPU (model_version gat2_masked2): the exact-count row sampler (csrc/row_sample.hip) against its numpy
+restatement (tests/row_sample_ref.py), the encoder's input gate (fn_encoder_forward_keep) against the reference's
+FragNetPreTrainMasked2 (tests/golden/pt_masked2_*.npz, the reference's own mask injected), its neutrality, and the captured step."""
+import copy
+import ctypes as C
+import os
+
+import numpy as np
+import pytest
+import torch
+
+from tests import row_sample_ref as rs
+from tests.helpers import GOLDEN, check_grads, check_params_match, load_case
+from tests.test_gpu_dropout_stream import SEEDS
+
+pytestmark = pytest.mark.gpu
+DEV = torch.device("cuda:0")
+ATOL = 1e-4                     # tests/test_gpu_parity.py's tolerance for pt_esol_b4 (with rtol 1e-4)
+NAMES = ("bond_length", "bond_angle", "dihedral", "graph_rep")
+CASES = ["pt_masked2_b4", "pt_masked2_edge6"]
+# wave, workgroup (1024 threads x 4 rows), one-pass and loop boundaries of the single-workgroup kernel; 16384 / 16385: the last
+# capacity whose keys a thread holds in registers and the first that re-reads them per pass
+SIZES = [1, 2, 7, 63, 64, 65, 255, 256, 257, 1023, 1025, 4099, 16384, 16385, 70001]
+GUARD = 64
+
+
+def _keys(kind, n):
+    rng = np.random.default_rng(1000 + n)
+    if kind == "equal":
+        return np.full(n, 0x9E3779B9, dtype=np.uint32)
+    if kind == "two_values":                       # ties straddle the pivot whatever k is
+        return np.where(rng.random(n) < 0.5, np.uint32(7), np.uint32(0xF0000001)).astype(np.uint32)
+    if kind == "low_byte":                         # equal in their top 24 bits: the last radix pass decides, with many ties
+        return (np.uint32(0xABCDEF00) | rng.integers(0, 256, size=n, dtype=np.uint32)).astype(np.uint32)
+    return rng.integers(0, 2 ** 32, size=n, dtype=np.uint64).astype(np.uint32)
+
+
+def _dev_keys(keys):
+    return torch.from_numpy(keys.view(np.int32).copy()).to(DEV)
+
+
+def _guarded(cap):
+    buf = torch.full((cap + 2 * GUARD,), 0xAB, dtype=torch.uint8, device=DEV)
+    return buf, buf[GUARD: GUARD + cap]
+
+
+def _guards_intact(buf, cap):
+    b = buf.cpu().numpy()
+    return bool((b[:GUARD] == 0xAB).all() and (b[GUARD + cap:] == 0xAB).all())
+
+
+@pytest.mark.parametrize("kind", ["equal", "two_values", "low_byte", "random"])
+def test_selection_on_injected_keys_is_the_restatement(kind):
+    from fragnet_amd import ops
+    for n in SIZES:
+        keys = _keys(kind, n)
+        dk = _dev_keys(keys)
+        for kf in (0.0, 0.85, 1.0):
+            buf, out = _guarded(n)
+            ops.select_rows(dk, kf, out=out)
+            got = out.cpu().numpy()
+            want = rs.select(keys, kf)
+            assert int(got.sum()) == int(n * kf), (kind, n, kf)
+            assert np.array_equal(got, want), (kind, n, kf, int(np.argmax(got != want)))
+            assert _guards_intact(buf, n), (kind, n, kf)
+
+
+@pytest.mark.parametrize("cap", [65, 1025, 4099])
+def test_device_row_count_padding_and_clamp(cap):
+    from fragnet_amd import ops
+    keys = _keys("two_values", cap)
+    dk = _dev_keys(keys)
+    for n_real in (0, 1, cap - 3, cap, cap + 1000, -5):
+        n_dev = torch.tensor([n_real], dtype=torch.int32, device=DEV)
+        buf, out = _guarded(cap)
+        ops.select_rows(dk, 0.85, n_dev=n_dev, out=out)
+        got = out.cpu().numpy()
+        n = min(max(n_real, 0), cap)
+        assert np.array_equal(got, rs.select(keys, 0.85, n=n_real)), (cap, n_real)
+        assert bool(got[n:].all()) and int(got[:n].sum()) == int(n * 0.85)
+        assert _guards_intact(buf, cap), (cap, n_real)       # a count beyond cap is clamped: nothing is written past cap
+        if 0 <= n_real <= cap:
+            host = ops.select_rows(dk, 0.85, n=n_real)
+            assert np.array_equal(host.cpu().numpy(), got)
+    from fragnet_amd import _lib
+    with pytest.raises(_lib.FragnetHipError, match="keep_frac"):
+        ops.select_rows(dk, 1.5)
+    with pytest.raises(ValueError):
+        ops.select_rows(dk, 0.85, n=cap + 1)
+
+
+@pytest.mark.parametrize("seed", SEEDS)
+def test_sampler_matches_the_philox_restatement(seed):
+    from fragnet_amd import ops
+    for offset in (0, 5, 2 ** 32 - 1):
+        for cap in (7, 257, 4099):
+            blocks = (cap + 3) // 4
+            for with_dev in (False, True):
+                rng = ops.PhiloxStream(seed=seed)
+                if with_dev:                     # the whole offset in the device counter, none on the host
+                    rng.dev = torch.tensor([offset], dtype=torch.int64, device=DEV)
+                else:
+                    rng.offset = offset
+                first = ops.sample_rows(cap, 0.85, rng, DEV).cpu().numpy()
+                n_dev = torch.tensor([cap - 3], dtype=torch.int32, device=DEV)
+                second = ops.sample_rows(cap, 0.85, rng, DEV, n_dev=n_dev).cpu().numpy()
+                assert rng.offset == (0 if with_dev else offset) + 2 * blocks
+                assert np.array_equal(first, rs.sample(cap, 0.85, seed, offset)), (seed, offset, cap, with_dev)
+                # the second draw starts where the first one's last block ended: no Philox block is shared
+                assert np.array_equal(second, rs.sample(cap, 0.85, seed, offset + blocks, n=cap - 3)), (seed, offset, cap, with_dev)
+                assert int(first.sum()) == int(cap * 0.85) and int(second[:cap - 3].sum()) == int((cap - 3) * 0.85)
+
+
+# ------------------------------------------------------------------------------------------------ the gate against the reference
+def _to_dev(batch):
+    return {k: v.to(DEV) for k, v in batch.items()}
+
+
+_FIXTURES = {}
+
+
+def _fixture(case):
+    """(cfg, batch, out, grads, pkeys, psums, keep uint8 [N], unmasked outputs): loaded once, shared, never modified."""
+    if case not in _FIXTURES:
+        z = np.load(os.path.join(GOLDEN, case + ".npz"))
+        _FIXTURES[case] = load_case(case) + (torch.from_numpy(z["keep_atoms"]), {nm: z[f"out_unmasked/{nm}"] for nm in NAMES})
+    return _FIXTURES[case]
+
+
+def _model(cfg, cls=None, **kw):
+    from fragnet_amd import model as M
+    torch.manual_seed(cfg["seed"])
+    return (cls or M.FragNetPreTrainMasked2)(**cfg["ctor"], **kw).to(DEV)
+
+
+def _worst_excess(outs, want):
+    """max over the four outputs of |got - want| / (ATOL + 1e-4 |want|): above 1 = outside the parity tolerance"""
+    worst = 0.0
+    for nm, t in zip(NAMES, outs):
+        w = torch.from_numpy(want[nm])
+        worst = max(worst, float(((t.detach().cpu() - w).abs() / (ATOL + 1e-4 * w.abs())).max()))
+    return worst
+
+
+@pytest.mark.parametrize("case", CASES)
+def test_injected_reference_mask_reproduces_the_reference(case):
+    from oracle import fragnet_ref as ref
+    cfg, batch, out, grads, pkeys, psums, keep, unmasked = _fixture(case)
+    model = _model(cfg)
+    check_params_match(model, pkeys, psums)
+    model.train()
+    b = _to_dev(batch)
+    b["keep_atoms"] = keep.to(DEV)
+    x_before = b["x_atoms"].clone()
+    outs = model(b)
+    assert torch.equal(b["x_atoms"], x_before), "the batch's x_atoms must not be overwritten"
+    assert torch.equal(model.last_keep, b["keep_atoms"])
+    for nm, t in zip(NAMES, outs):
+        torch.testing.assert_close(t.detach().cpu(), torch.from_numpy(out[nm]), atol=ATOL, rtol=1e-4)
+    loss = ref.pretrain_loss(outs, b)
+    assert abs(loss.item() - float(out["loss"])) < ATOL
+    loss.backward()
+    check_grads(model, grads, atol=ATOL, rtol=1e-4)
+    # a port that ignores the mask is caught: all rows kept gives the unmasked outputs, outside the tolerance of the masked ones
+    b_all = _to_dev(batch)
+    b_all["keep_atoms"] = torch.ones_like(b["keep_atoms"])
+    with torch.no_grad():
+        outs_all = model(b_all)
+    assert _worst_excess(outs_all, unmasked) <= 1.0
+    assert _worst_excess(outs_all, out) > 1.0
+    # and so does the same call without the key (the model then draws a mask of its own, other rows than the reference's)
+    with torch.no_grad():
+        outs_own = model(_to_dev(batch))
+    assert _worst_excess(outs_own, out) > 1.0
+    n = batch["x_atoms"].shape[0]
+    assert model.last_keep.shape == (n,) and int(model.last_keep.sum()) == int(n * 0.85)
+
+
+@pytest.mark.parametrize("case", CASES)
+@pytest.mark.parametrize("no_backward", [True, False], ids=["no_backward", "saves_for_backward"])
+def test_gate_in_evaluation_mode(case, no_backward):
+    """the reference masks in eval() too; drop_ratio = 0 in the fixture, so the evaluation pass has the training pass's outputs"""
+    cfg, batch, out, grads, pkeys, psums, keep, unmasked = _fixture(case)
+    model = _model(cfg).eval()
+    b = _to_dev(batch)
+    b["keep_atoms"] = keep.to(DEV)
+    if no_backward:
+        with torch.no_grad():
+            outs = model(b)
+    else:
+        outs = model(b)
+        assert outs[1].requires_grad
+    for nm, t in zip(NAMES, outs):
+        torch.testing.assert_close(t.detach().cpu(), torch.from_numpy(out[nm]), atol=ATOL, rtol=1e-4)
+    if not no_backward:
+        from oracle import fragnet_ref as ref
+        ref.pretrain_loss(outs, b).backward()
+        check_grads(model, grads, atol=ATOL, rtol=1e-4)
+
+
+# ------------------------------------------------------------------------------------------------ neutrality and refusals
+def test_keeping_every_row_is_the_plain_model_bit_for_bit():
+    """keep_frac = 1 under drop_ratio = 0.15 in train(): the gate passes every row and kept rows draw the dropout bits they draw without
+    a gate, so outputs and gradients are FragNetPreTrain's bits on the same seed."""
+    from fragnet_amd import model as M
+    from oracle import fragnet_ref as ref
+    cfg, batch = _fixture("pt_masked2_b4")[:2]
+    cfg = dict(cfg, ctor=dict(cfg["ctor"], drop_ratio=0.15))
+    masked = _model(cfg, mask_ratio=0.0).train()
+    plain = _model(cfg, cls=M.FragNetPreTrain).train()
+    got, want = masked(_to_dev(batch)), plain(_to_dev(batch))
+    assert bool(masked.last_keep.all()) and masked.pretrain.rng.offset == plain.pretrain.rng.offset > 0
+    for a, b in zip(got, want):
+        assert torch.equal(a, b)
+    ref.pretrain_loss(got, _to_dev(batch)).backward()
+    ref.pretrain_loss(want, _to_dev(batch)).backward()
+    for (n1, p1), (_, p2) in zip(masked.named_parameters(), plain.named_parameters()):
+        assert (p1.grad is None) == (p2.grad is None), n1
+        if p1.grad is not None:
+            assert torch.equal(p1.grad, p2.grad), n1
+
+
+def _raw_pass(model, batch, entry, keep=None, variant=0, no_backward=True, gated_ws=False):
+    """One evaluation pass through ``entry`` (fn_encoder_forward / fn_encoder_forward_keep) on a descriptor built the way the
+    engine's autograd node builds it; returns (rc, outputs, descriptor, workspace)."""
+    from fragnet_amd import _lib, engine
+    from fragnet_amd.plan import _stream_ptr, plan_for
+    lib = _lib.load()
+    b = dict(batch)
+    plan = plan_for(b)
+    layers = model.pretrain.layers
+    params = [p.detach() for layer in layers for p in engine.layer_param_list(layer)]
+    cos = plan.sorted_attr("bond", b["edge_attr_bonds"], defer=True)
+    fattr = plan.sorted_attr("fbond", b["edge_attr_fbonds"], defer=True)
+    e = engine._describe(plan, b["x_atoms"], b["node_features_bonds"], b["node_features_fbonds"], cos, fattr, params, len(layers),
+                         layers[0].num_heads, 0.0, False, 0, 0, None, variant, no_backward)
+    size = lib.fn_encoder_keep_ws_floats(C.byref(e)) if gated_ws else lib.fn_encoder_ws_floats(C.byref(e))
+    ws = torch.empty(size, dtype=torch.float32, device=DEV)
+    e.ws, e.ws_floats = ws.data_ptr(), ws.numel()
+    outs = [torch.zeros((n, 128), dtype=torch.float32, device=DEV) for n in (e.N, e.F, e.E, e.EF)]
+    if lib.fn_encoder_fused_tail(C.byref(e)):
+        pooled = torch.empty((e.n_mols, 256), dtype=torch.float32, device=DEV)
+        e.pooled = pooled.data_ptr()
+        outs.append(pooled)
+    ptrs = [o.data_ptr() for o in outs[:4]]
+    if entry == "fn_encoder_forward":
+        rc = lib.fn_encoder_forward(C.byref(e), *ptrs, _stream_ptr(DEV))
+    else:
+        rc = lib.fn_encoder_forward_keep(C.byref(e), None if keep is None else keep.data_ptr(), *ptrs, _stream_ptr(DEV))
+    torch.cuda.synchronize()
+    return rc, outs, e, ws, (plan, params, cos, fattr, b)
+
+
+def test_null_gate_is_the_plain_entry_point_and_refusals_return_their_codes():
+    from fragnet_amd import _lib
+    cfg, batch, _, _, _, _, keep, _ = _fixture("pt_masked2_b4")
+    model = _model(cfg).eval()
+    b = _to_dev(batch)
+    rc0, plain, *_ = _raw_pass(model, b, "fn_encoder_forward")
+    rc1, null_gate, *_ = _raw_pass(model, b, "fn_encoder_forward_keep", keep=None)
+    assert rc0 == 0 and rc1 == 0
+    for a, c in zip(plain, null_gate):
+        assert torch.equal(a, c)
+    kd = keep.to(DEV)
+    # variant 1 / 2: refused before anything is launched (the outputs keep their zeros)
+    for variant in (1, 2):
+        rc, outs, *_ = _raw_pass(model, b, "fn_encoder_forward_keep", keep=kd, variant=variant, gated_ws=True)
+        assert rc == -2 and b"fn_encoder_forward_keep" in _lib.load().fn_last_error()
+        assert all(float(o.abs().sum()) == 0.0 for o in outs[:4])
+    # a gated pass without dropout needs the larger workspace
+    rc, *_ = _raw_pass(model, b, "fn_encoder_forward_keep", keep=kd, gated_ws=False)
+    assert rc == -1 and b"workspace too small" in _lib.load().fn_last_error()
+    # input gradients of a gated pass: FN_EUNSUPPORTED
+    rc, outs, e, ws, alive = _raw_pass(model, b, "fn_encoder_forward_keep", keep=kd, no_backward=False, gated_ws=True)
+    assert rc == 0 and float(outs[0].abs().sum()) > 0
+    scratch = torch.zeros(64, dtype=torch.float32, device=DEV)
+    ig = _lib.InputGrads()
+    rc = _lib.load().fn_encoder_backward_inputs(C.byref(e), scratch.data_ptr(), scratch.numel(), C.byref(ig), None)
+    assert rc == -2 and b"input gate" in _lib.load().fn_last_error()
+    # an ungated pass into the same workspace clears that
+    e.no_backward = 0
+    assert _lib.load().fn_encoder_forward(C.byref(e), *[o.data_ptr() for o in outs[:4]], None) == 0
+    torch.cuda.synchronize()
+    rc = _lib.load().fn_encoder_backward_inputs(C.byref(e), scratch.data_ptr(), scratch.numel(), C.byref(ig), None)
+    assert rc == -1 and b"scratch too small" in _lib.load().fn_last_error()
+
+
+def test_python_layers_refuse_what_the_gate_does_not_combine_with():
+    from fragnet_amd import model as M
+    cfg, batch, _, _, _, _, keep, _ = _fixture("pt_masked2_b4")
+    model = _model(cfg).eval()
+    b = _to_dev(batch)
+    b["keep_atoms"] = keep.to(DEV)
+    with torch.no_grad():
+        with pytest.raises(ValueError, match="row masks"):
+            model.pretrain(dict(b, mask_atoms=torch.zeros_like(b["keep_atoms"])))
+        model.pretrain.use_engine = False
+        with pytest.raises(ValueError, match="use_engine"):
+            model.pretrain(dict(b))
+        model.pretrain.use_engine = True
+        model.pretrain.layers[0].return_attentions = True
+        with pytest.raises(ValueError, match="return_attentions"):
+            model.pretrain(dict(b))
+        model.pretrain.layers[0].return_attentions = False
+        with pytest.raises(ValueError, match="uint8"):
+            model.pretrain(dict(b, keep_atoms=b["keep_atoms"].float()))
+        lite = M.FragNet(num_layer=1, edge_features=17, variant="gat2_lite").to(DEV).eval()
+        with pytest.raises(ValueError, match="gat2 only"):
+            lite(dict(b))
+    x = dict(b, x_atoms=b["x_atoms"].clone().requires_grad_(True))
+    with pytest.raises(NotImplementedError, match="input gradients"):
+        model.pretrain(x)
+
+
+# ------------------------------------------------------------------------------------------------ the captured step
+def test_captured_masked_step_replays_what_the_eager_step_computes():
+    """Six molecules, static shapes with margin, four steps.  The replayed graph against the SAME static-shape step enqueued
+    eagerly (no graph) from the same stream state -- same kernels on the same padded batch, so loss and parameters agree bit for bit --
+    and every step's mask, read back from the step's debug tensor, against the restatement at that step's counter."""
+    from fragnet_amd import data, graphstep, parallel, synth, train
+    from fragnet_amd.model import FragNetPreTrainMasked2
+    from fragnet_amd.plan import REAL_ATOMS_KEY
+    batches = [data.batch_to(data.collate_fn_pt(synth.synth_molecules(6, seed=80 + i, profile="esol", pretrain_targets=True)), DEV)
+               for i in range(3)]
+    shapes = graphstep.StaticShapes.from_batches(batches, margin=0.05)
+    torch.manual_seed(5)
+    model_a = FragNetPreTrainMasked2(num_layer=2, drop_ratio=0.1, edge_features=17).to(DEV).train()
+    model_b = copy.deepcopy(model_a)
+    steps = []
+    for model in (model_a, model_b):
+        opt = parallel.FlatAdam.for_live_parameters(model, lambda m=model: train.pretrain_loss(m(dict(batches[0])), batches[0]).backward(), lr=1e-3)
+        model.mask_rng.offset = model.pretrain.rng.offset = 0         # the probe drew from both streams: the twins start alike
+        steps.append(graphstep.GraphedTrainStep(model, opt, shapes, dict(batches[0]), loss="pretrain"))
+    step_a, step_b = steps
+    assert step_a.adam_in_graph and step_a._stage_bumps and step_a._mask_per_step == (shapes.cap["atom"] + 3) // 4
+    assert model_a.mask_rng.seed == model_b.mask_rng.seed != model_a.pretrain.rng.seed
+    assert torch.equal(step_a.opt.flat, step_b.opt.flat)
+    cap = shapes.cap["atom"]
+
+    def eager_static(step, batch):
+        step._sync_adam_state()
+        assert step.static.load(batch)              # the staging launch: pads, writes the counts, moves the three counters on
+        step.rng.offset, step.mask_rng.offset = step._rng_base, step._mask_base
+        step.opt.zero_grad()
+        loss, _ = step._fwd_bwd_static()
+        step.opt.adam_in_graph(step._counters[1:2], step._lr_dev)
+        step.opt.steps += 1
+        step._dev_steps += 1
+        return loss.detach().clone()
+
+    previous = None
+    for t in range(4):
+        b = batches[t % 3]
+        loss_a = step_a(dict(b)).clone()
+        loss_b = eager_static(step_b, dict(b))
+        assert torch.equal(loss_a, loss_b), (t, float(loss_a), float(loss_b))
+        assert torch.equal(step_a.opt.flat, step_b.opt.flat), t
+        n_real = b["x_atoms"].shape[0]
+        assert int(step_a.static.t[REAL_ATOMS_KEY]) == n_real and int(step_a._mask_counter) == t * step_a._mask_per_step
+        mask = step_a.keep_mask.cpu().numpy()
+        assert mask.shape == (cap,) and int(mask[:n_real].sum()) == int(n_real * 0.85) and bool(mask[n_real:].all())
+        want = rs.sample(cap, 0.85, model_a.mask_rng.seed, step_a._mask_base + t * step_a._mask_per_step, n=n_real)
+        assert np.array_equal(mask, want), t
+        assert np.array_equal(step_b.keep_mask.cpu().numpy(), mask), t
+        assert previous is None or not np.array_equal(previous[:20], mask[:20])
+        previous = mask
+    assert step_a.replays == 4 and step_a.fallbacks == 0 and torch.isfinite(step_a.opt.flat).all()
+    # the eager fallback of an over-capacity batch draws step 4's keys too: on its own rows, the restatement at that counter
+    big = data.batch_to(data.collate_fn_pt(synth.synth_molecules(12, seed=99, profile="esol", pretrain_targets=True)), DEV)
+    step_a(dict(big))
+    assert step_a.fallbacks == 1
+    n_big = big["x_atoms"].shape[0]
+    want = rs.sample(n_big, 0.85, model_a.mask_rng.seed, step_a._mask_base + 4 * step_a._mask_per_step)
+    assert np.array_equal(model_a.last_keep.cpu().numpy(), want)
+    # and the replay after it shares no mask block with it
+    step_a(dict(batches[0]))
+    assert (n_big + 3) // 4 > step_a._mask_per_step
+    assert int(step_a._mask_counter) == 4 * step_a._mask_per_step + (n_big + 3) // 4
