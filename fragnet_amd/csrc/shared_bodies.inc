@@ -53,6 +53,13 @@ __device__ __forceinline__ void dropout_act_body(const float* __restrict__ a, co
     }
 }
 
+// m' = beta1 m + (1 - beta1) g the way torch's lerp takes it: from the end whose weight is the larger one.  m + (g - m) * (1 - beta1) alone
+// loses g where |g| < 2^-24 |m| (g - m rounds to -m): harmless while beta1 m dominates m' anyway, but at beta1 = 0, where m' is g, the
+// parameter stood still.  (The branch is uniform; beta1 > 0.5, the default included, keeps the form and the bits it always had.)
+__device__ __forceinline__ float adam_lerp(float m, float g, float beta1) {
+    const float w = 1.f - beta1;
+    return w < 0.5f ? m + (g - m) * w : g - (g - m) * beta1;
+}
 // torch.optim.Adam's update rule (no amsgrad) on one flat tensor: the reference's optimiser, finetune_gat2.py:257
 // (vb, nb): this block's index / the number of blocks working on the tensor -- k_adam's own grid, or the riders' range of the
 // deferred-reduction launch (AdamRide below)
@@ -78,7 +85,7 @@ __device__ __forceinline__ void adam_body(float* __restrict__ p, const float* __
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
             const float gq = G[q] + wd * P[q];
-            M[q] = M[q] + (gq - M[q]) * (1.f - beta1);
+            M[q] = adam_lerp(M[q], gq, beta1);
             V[q] = V[q] * beta2 + (1.f - beta2) * gq * gq;
             P[q] -= lr_over_bc1 * (M[q] / (sqrtf(V[q]) * inv_sqrt_bc2 + eps));
         }
@@ -87,7 +94,7 @@ __device__ __forceinline__ void adam_body(float* __restrict__ p, const float* __
     if (vb == 0 && threadIdx.x < (n & 3)) {
         const int64_t i = n4 * 4 + threadIdx.x;
         const float gq = g[i] + wd * p[i];
-        const float mq = m[i] + (gq - m[i]) * (1.f - beta1);
+        const float mq = adam_lerp(m[i], gq, beta1);
         const float vq = v[i] * beta2 + (1.f - beta2) * gq * gq;
         m[i] = mq; v[i] = vq;
         p[i] -= lr_over_bc1 * (mq / (sqrtf(vq) * inv_sqrt_bc2 + eps));

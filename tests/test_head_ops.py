@@ -465,6 +465,45 @@ def test_last_linear_with_loss_in_one_launch_equals_the_three_launches(kind, M, 
     torch.testing.assert_close(db1, db0, atol=tol, rtol=1e-5)
     torch.testing.assert_close(loss1, loss0, atol=1e-6, rtol=1e-5)
     torch.testing.assert_close(dW1, (g0[:M].double().t() @ x.double()).float(), atol=tol, rtol=1e-5)
+    # ... and against a float64 Linear + loss, which shares nothing with the kernels above.  Bounds to first order in u = 2^-24 (plus
+    # the second-order term of the loss), worst case over any summation order:
+    #   prediction   e_y = (4 ceil(K / 256) + 8) u (|x| |w|^T + |b|)               one wave per row: a lane chains 4 ceil(K / 256) products,
+    #                                                                              six butterfly levels, the bias
+    #   g_out        |dg/dy| e_y + 4 u |g| (+ 4 u / N for BCE)                     dg/dy = 2 w_row / (W C) for MSE, <= 1 / (4 N) for BCE
+    #   loss         sum |g| e_y + sum |dg/dy| e_y^2 / 2 + (C + 2 + n_part + 8) u sum|term| / denom
+    #                                                                              C terms per row, a 4-row tree, n_part partials
+    #   dW           (error bound of g_out)^T |x| + (M + 2) u |g|^T |x|            an M-term sum per element
+    u = 2.0 ** -24
+    xd, wd, bd, td, rw = (t.double().cpu() for t in (x, w, b, tgt[:M], row_w[:M]))
+    yl = (xd @ wd.t() + bd).requires_grad_(True)
+    e_y = (4 * ((K + 255) // 256) + 8) * u * (xd.abs() @ wd.abs().t() + bd.abs())
+    if kind == "mse":
+        d = yl - td
+        terms = rw[:, None] * d * d
+        den = rw.sum() * C
+        slope = (2.0 * rw / den)[:, None].expand(M, C)
+        extra = 0.0
+    else:
+        valid = (td > -0.5) & (rw[:, None] > 0)
+        mat = torch.nn.functional.binary_cross_entropy_with_logits(yl, td.clamp(min=0.0), reduction="none")
+        terms = torch.where(valid, mat, torch.zeros_like(mat))
+        den = valid.sum().double()
+        slope = valid.double() / (4.0 * den)
+        extra = 4 * u / float(den)
+    loss64 = terms.sum() / den
+    loss64.backward()
+    g64 = yl.grad
+    g_bound = slope * e_y + 4 * u * g64.abs() + extra
+    loss_bound = float((g64.abs() * e_y).sum() + (slope * e_y * e_y).sum() / 2
+                       + (C + 2 + n_part + 8) * u * terms.detach().abs().sum() / den)
+    dW_bound = g_bound.t() @ xd.abs() + (M + 2) * u * (g64.abs().t() @ xd.abs())
+    g_err, dW_err = (g1.double().cpu() - g64).abs(), (dW1.double().cpu() - g64.t() @ xd).abs()
+    loss_err = abs(float(loss1) - float(loss64.detach()))
+    print(f"float64 Linear + {kind}: loss error {loss_err:.2e} (bound {loss_bound:.2e}), g_out worst {float((g_err / g_bound.clamp_min(1e-300)).max()):.3f} x bound, "
+          f"dW worst {float((dW_err / dW_bound.clamp_min(1e-300)).max()):.3f} x bound")
+    assert loss_err <= loss_bound
+    assert bool((g_err <= g_bound).all()) and bool((dW_err <= dW_bound).all())
+    assert bool((db1.double().cpu() - g64.sum(0)).abs().le(g_bound.sum(0) + (M + 2) * u * g64.abs().sum(0)).all())
 
 
 @gpu
