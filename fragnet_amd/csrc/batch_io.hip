@@ -440,6 +440,8 @@ int fn_plan_build(const fn_csr_task* tasks, int n_tasks, int32_t* rowptr_all, in
         items += tasks[i].n_real + tasks[i].n_loops;
         segs += tasks[i].n_seg;
     }
+    // items without a segment to fall into: every key would be out of range, and the scan would be launched with no blocks
+    if (segs == 0 && items > 0) return fail(FN_EINVAL, "fn_plan_build: items but no segments");
     P.total_items = items;
     P.total_segs = segs;
     hipStream_t st = S(stream);
@@ -606,6 +608,8 @@ extern "C" int fn_bond_graph_count(const int64_t* edge_index, const int64_t* ato
                         int64_t* total, fn_stream_t stream) {
     if (E < 0 || N < 0 || B < 0 || E >= (1ll << 31) - 1 || !ws || !total || (E > 0 && (!edge_index || !atom_mol)) || (mode != 0 && mode != 1))
         return fail(FN_EINVAL, "fn_bond_graph_count: bad argument");
+    // bonds belong to molecules: without one, k_bg_mol_hist would index past mol_first and the molecule scans would have no blocks
+    if (B == 0 && E > 0) return fail(FN_EINVAL, "fn_bond_graph_count: bonds but no molecules");
     BondGraphWs w = bond_graph_ws(edge_index, atom_mol, E, B, ws, mode);
     hipStream_t st = S(stream);
     hipLaunchKernelGGL(k_zero2_i32, dim3(flat_grid(w.zero_n, kGridCap)), dim3(kBlock), 0, st, ws, w.zero_n, ws, (int64_t)0);

@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 import torch
 
+from tests.batch_io_ref import check_level_arena
 from tests.helpers import check_grads, check_params_match, load_case
 
 pytestmark = pytest.mark.gpu
@@ -63,37 +64,12 @@ def test_plan_matches_stable_argsort():
     loops = torch.arange(N)
     dst = torch.cat([ei[1], loops]).numpy()
     src = torch.cat([ei[0], loops]).numpy()
-    c = lv.c
-    arena = plan._arena.cpu().numpy()
-    base_ptr = plan._arena.data_ptr()
-    off = lambda p: (p - base_ptr) // 4
-    rp = arena[off(c.rowptr_d): off(c.rowptr_d) + N + 1].astype(np.int64) - c.pos_base_d
-    eid = arena[off(c.eid_d): off(c.eid_d) + lv.m]
-    srcd = arena[off(c.src_d): off(c.src_d) + lv.m]
-    order = np.argsort(dst, kind="stable")
-    assert np.array_equal(eid, order)
-    assert np.array_equal(srcd, src[order])
-    assert np.array_equal(rp, np.concatenate([[0], np.cumsum(np.bincount(dst, minlength=N))]))
-    rps = arena[off(c.rowptr_s): off(c.rowptr_s) + N + 1].astype(np.int64) - c.pos_base_s
-    dsts = arena[off(c.dst_s): off(c.dst_s) + lv.m]
-    dpos = arena[off(c.dpos_s): off(c.dpos_s) + lv.m]
-    order_s = np.argsort(src, kind="stable")
-    assert np.array_equal(dsts, dst[order_s])
-    inv = np.empty(lv.m, dtype=np.int64)
-    inv[order] = np.arange(lv.m)
-    assert np.array_equal(dpos, inv[order_s])
-    inv_d = arena[off(c.inv_d): off(c.inv_d) + lv.m]
-    assert np.array_equal(inv_d, inv)
-    spos = arena[off(c.spos_d): off(c.spos_d) + lv.m]
-    want_spos = np.empty(lv.m, dtype=np.int64)
-    want_spos[dpos] = np.arange(lv.m)                      # inverse of dpos_s
-    assert np.array_equal(spos, want_spos)
+    order = check_level_arena(plan, lv, dst, src, N)
     # raw edge attributes permuted into destination order, zeros on the loop positions
     attr = torch.arange(ei.shape[1] * 3, dtype=torch.float32, device=DEV).view(-1, 3)
     got = plan.sorted_attr("atom", attr).cpu().numpy().T          # stored [K][m]
     want = np.concatenate([attr.cpu().numpy(), np.zeros((N, 3), np.float32)])[order]
     assert np.array_equal(got, want)
-    assert np.array_equal(rps, np.concatenate([[0], np.cumsum(np.bincount(src, minlength=N))]))
 
 
 def test_plan_flags_out_of_range_index():
