@@ -1,24 +1,22 @@
 // encoder.hip -- the encoder engine: FragNet.forward and its backward as ONE call each (fn_encoder_forward / fn_encoder_backward and
 // their workspace / RNG planners), with every kernel that nothing but the engine launches: the forward prologue (k_enc_prologue), the
 // molecule-resident fragment tail (mol_tail.inc), k_frag_tail, k_gate_many, the input-gradient products with the edge term's
-// backward beside them (k_lin_rd_cu, k_gat_bwd_src_rd), the grouped weight gradients and the deferred reductions (k_reduce_tasks,
-// ReduceQueue).
+// backward beside them (k_lin_rd_cu, k_gat_bwd_src_rd).  The parameters' gradients -- weight-gradient products, the attention vectors'
+// finalize, every reduction of partials -- are param_grads.hip's; the passes here queue them on its fni::ParamGradQueue (level_params).
 // A few operator entry points live here with their kernels, because those kernels run a device body that one of the engine's combined
-// launches runs as well: the weight gradients (fn_linear128_wgrad_f32 / _ws: wgrad_body), the backward of the full-width edge term
-// (fn_row_dots_sorted_bwd_f32: row_dots_sorted_bwd_body), the source pass of the two-pass attention backward (fn_gat_bwd_src_f32:
-// gat_bwd_src_body, also in k_gat_bwd_src_rd), its finalize (fn_gat_bwd_finalize_f32: gat_finalize_body, also in k_reduce_tasks) and the
-// edge-attribute permutations (fn_sort_edge_attr_f32 / _src_f32: the bodies k_enc_prologue runs).  A body and all the kernels that run
+// launches runs as well: the backward of the full-width edge term (fn_row_dots_sorted_bwd_f32: row_dots_sorted_bwd_body), the source
+// pass of the two-pass attention backward (fn_gat_bwd_src_f32: gat_bwd_src_body, also in k_gat_bwd_src_rd) and the edge-attribute
+// permutations (fn_sort_edge_attr_f32 / _src_f32: the bodies k_enc_prologue runs).  A body and all the kernels that run
 // it stay in ONE unit: the compiler's inter-procedural passes run before it inlines the body, so what it knows about the body's
 // arguments depends on the callers it sees in the unit -- with the callers in two units these kernels came out with other registers
 // and schedules than before (profiles/engine_unit_equivalence.txt section 1); and a __global__ function that is no template can be
 // compiled into one unit only.
 // A translation unit of its own: what it takes from the other units is the fni:: interface of fn_internal.h (host launchers of
-// gat_fwd.hip, gat_fwd_lin.hip, gat_bwd_one.hip and fragnet_hip.hip, the tuning table through fni::tune) and single-operator entry
+// gat_fwd.hip, gat_fwd_lin.hip, gat_bwd_one.hip and fragnet_hip.hip, param_grads.hip's queue, the tuning table through fni::tune) and single-operator entry
 // points of the C-ABI (fn_gat_bwd_dst_f32, fn_gat_fwd_f32, ..); device bodies it shares with fragnet_hip.hip are in .inc files both
 // include (gat_fwd.inc, gat_bwd_two.inc, linear128.inc, shared_bodies.inc).
 #include <hip/hip_runtime.h>
 #include <algorithm>
-#include <functional>
 #include <mutex>
 #include <stdint.h>
 
@@ -45,8 +43,8 @@ using fni::launch_linear128_group;
 using fni::launch_linear128_small_group;
 using fni::launch_linear128_ns;
 using fni::launch_gather_rows4;
+using fni::ParamGradQueue;
 
-#include "zero2.inc"
 #include "gat_fwd.inc"
 #include "gat_bwd_two.inc"
 #include "shared_bodies.inc"
@@ -314,7 +312,7 @@ __global__ void k_sort_edge_attr(const float* __restrict__ x, int K, fn_gat_plan
     else sort_edge_attr_body(x, K, pl, x_sorted, (int)blockIdx.x, (int)gridDim.x);
 }
 
-// all projection weights of the encoder in one launch: matrix z -> Bt base + z * 192 * 128
+// all projection weights of the encoder, transposed by the forward prologue's first block range: matrix z -> Bt base + z * 192 * 128
 struct TransposeMany {
     const float* W[3 * FN_MAX_LAYERS];
     int K[3 * FN_MAX_LAYERS];
@@ -330,10 +328,6 @@ __device__ __forceinline__ void transpose_many_body(const TransposeMany& tm, flo
     __syncthreads();
     for (int r = ty; r < 32; r += 8)
         if (k0 + r < K) Bt[(size_t)(k0 + r) * FN_D + n0 + tx] = tile[tx][r];
-}
-__global__ void k_transpose_many(TransposeMany tm, float* __restrict__ bt_base) {
-    __shared__ float tile[32][33];
-    transpose_many_body(tm, bt_base, tile, (int)blockIdx.z, (int)blockIdx.y, (int)blockIdx.x);
 }
 
 // extents of every molecule in the index spaces of a collated batch (fn_internal.h: MolExt), from the molecule CSRs and the level plans
@@ -428,384 +422,6 @@ __global__ __launch_bounds__(256) void k_enc_prologue(EncPrologue A) {
     }
     b -= A.n_z;
     if (b < A.n_x) mol_extents_body(A.mx, b);
-}
-
-// Weight gradient: block = `rows_per_block` rows in chunks of 32 staged through double-buffered LDS.  Wave w owns
-// output rows o in [32(w&3), +32) and the (w>>2)-th group of CTW 16-column tiles of X, so NH = 2 column groups
-// put two waves on every SIMD.  part [grid][128*K + 128]: dW partial followed by the db partial.
-constexpr int kWgChunk = 32;
-template <int CTW, int NH>
-__device__ __forceinline__ void wgrad_body(float* smem, const float* __restrict__ dY, const float* __restrict__ X, int K,
-                                           int64_t M, int rows_per_block, float* __restrict__ part, int bid) {
-    constexpr int NT = 256 * NH;
-    constexpr int XW = 16 * CTW * NH;            // padded X width held in LDS
-    constexpr int XLD = XW + 16;                 // XW is a multiple of 32 for every instantiation but <1,1>
-    float* sY = smem;                                   // [2][32][144]
-    float* sX = smem + 2 * kWgChunk * kBtLd;            // [2][32][XLD]
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, i = lane & 15, kq = lane >> 4;
-    const int wo = w & 3, wc = w >> 2;
-    const int64_t m_begin = (int64_t)bid * rows_per_block;
-    const int64_t m_end = m_begin + rows_per_block < M ? m_begin + rows_per_block : M;
-    const int n_chunks = (int)((m_end - m_begin + kWgChunk - 1) / kWgChunk);
-
-    constexpr int YPT = 1024 / NT;                            // dY float4 per thread per chunk
-    constexpr int XPT = (kWgChunk * XW + NT - 1) / NT;        // X scalars per thread per chunk
-    float4 ry[YPT];
-    float rx[XPT];
-    auto fetch = [&](int c) {
-        const int64_t base = m_begin + (int64_t)c * kWgChunk;
-#pragma unroll
-        for (int q = 0; q < YPT; ++q) {
-            const int idx = tid + q * NT, r = idx >> 5, c4 = idx & 31;
-            ry[q] = (base + r < m_end) ? ld4(dY + (base + r) * 128 + c4 * 4) : make_float4(0.f, 0.f, 0.f, 0.f);
-        }
-#pragma unroll
-        for (int q = 0; q < XPT; ++q) {
-            const int idx = tid + q * NT, r = idx / XW, cc = idx % XW;
-            rx[q] = (r < kWgChunk && base + r < m_end && cc < K) ? X[(base + r) * K + cc] : 0.f;
-        }
-    };
-    auto stash = [&](int buf) {
-#pragma unroll
-        for (int q = 0; q < YPT; ++q) {
-            const int idx = tid + q * NT, r = idx >> 5, c4 = idx & 31;
-            st4(sY + (buf * kWgChunk + r) * kBtLd + c4 * 4, ry[q]);
-        }
-#pragma unroll
-        for (int q = 0; q < XPT; ++q) {
-            const int idx = tid + q * NT, r = idx / XW, cc = idx % XW;
-            if (r < kWgChunk) sX[(buf * kWgChunk + r) * XLD + cc] = rx[q];
-        }
-    };
-
-    f32x4 acc[2][CTW];
-#pragma unroll
-    for (int u = 0; u < 2; ++u)
-#pragma unroll
-        for (int c = 0; c < CTW; ++c) acc[u][c] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    float bsum[2] = {0.f, 0.f};
-
-    if (n_chunks > 0) { fetch(0); stash(0); }
-    __syncthreads();
-    for (int c = 0; c < n_chunks; ++c) {
-        const int buf = c & 1;
-        if (c + 1 < n_chunks) fetch(c + 1);
-#pragma unroll
-        for (int s = 0; s < kWgChunk / 4; ++s) {
-            const float* yrow = sY + (buf * kWgChunk + 4 * s + kq) * kBtLd + 32 * wo + i;
-            const float* xrow = sX + (buf * kWgChunk + 4 * s + kq) * XLD + 16 * CTW * wc + i;
-            const float a0 = yrow[0], a1 = yrow[16];
-            bsum[0] += a0;
-            bsum[1] += a1;
-            float bv[CTW];
-#pragma unroll
-            for (int cc = 0; cc < CTW; ++cc) bv[cc] = xrow[16 * cc];
-#pragma unroll
-            for (int cc = 0; cc < CTW; ++cc) {
-                acc[0][cc] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0, bv[cc], acc[0][cc], 0, 0, 0);
-                acc[1][cc] = __builtin_amdgcn_mfma_f32_16x16x4f32(a1, bv[cc], acc[1][cc], 0, 0, 0);
-            }
-        }
-        if (c + 1 < n_chunks) stash(buf ^ 1);
-        __syncthreads();
-    }
-    // partials are written in the accumulators' native layout: one coalesced 16-byte store per lane and tile;
-    // k_wgrad_reduce maps them back to dW[o][col] while summing over blocks
-    constexpr int PW = 128 * XW + 128;
-    float* pw = part + (size_t)bid * PW;
-#pragma unroll
-    for (int u = 0; u < 2; ++u)
-#pragma unroll
-        for (int cc = 0; cc < CTW; ++cc)
-            st4(pw + ((size_t)((w * 2 + u) * CTW + cc) * 64 + lane) * 4,
-                make_float4(acc[u][cc][0], acc[u][cc][1], acc[u][cc][2], acc[u][cc][3]));
-    if (wc == 0) {
-#pragma unroll
-        for (int u = 0; u < 2; ++u) {
-            float v = bsum[u];
-            v += __shfl_xor(v, 16);
-            v += __shfl_xor(v, 32);
-            if (kq == 0) pw[(size_t)128 * XW + 32 * wo + 16 * u + i] = v;
-        }
-    }
-}
-
-template <int CTW, int NH>
-__global__ __launch_bounds__(256 * NH) void k_linear128_wgrad(const float* __restrict__ dY, const float* __restrict__ X,
-                                                              int K, int64_t M, int rows_per_block,
-                                                              float* __restrict__ part) {
-    extern __shared__ __attribute__((aligned(16))) float smem[];
-    wgrad_body<CTW, NH>(smem, dY, X, K, M, rows_per_block, part, (int)blockIdx.x);
-}
-
-// all weight-gradient partial products of a backward pass that share K (every projection beyond layer 0): one launch
-struct WgradTask {
-    const float *dY, *X;
-    float* part;
-    int64_t M;
-    int rpb, first;
-    int K;                    // k_linear128_wgrad_mixed only: this product's reduction length (0 elsewhere: WgradTasks::K)
-    const int32_t* n_real;    // nullable device word: rows at or behind *n_real are padding (zero gradient rows) and are not read
-};
-constexpr int kMaxWgradTasks = 3 * FN_MAX_LAYERS;
-struct WgradTasks {
-    WgradTask t[kMaxWgradTasks];
-    int n, K;
-};
-#include "wgrad128.inc"
-template <int CTW, int NH>
-__global__ __launch_bounds__(256 * NH) void k_linear128_wgrad_multi(WgradTasks T) {
-    extern __shared__ __attribute__((aligned(16))) float smem[];
-    int ti = 0;
-    while (ti + 1 < T.n && (int)blockIdx.x >= T.t[ti + 1].first) ++ti;
-    const WgradTask& t = T.t[ti];
-    wgrad_body<CTW, NH>(smem, t.dY, t.X, T.K, t.M, t.rpb, t.part, (int)blockIdx.x - t.first);
-}
-
-// the weight-gradient partials of layer 0 (raw-feature widths: 17 / 6 / 167 at the reference's sizes) in one launch: every
-// product picks the instantiation its K needs (all with two column groups, i.e. 512 threads); the launch's LDS size is the
-// largest product's
-__global__ __launch_bounds__(512) void k_linear128_wgrad_mixed(WgradTasks T) {
-    extern __shared__ __attribute__((aligned(16))) float smem[];
-    int ti = 0;
-    while (ti + 1 < T.n && (int)blockIdx.x >= T.t[ti + 1].first) ++ti;
-    const WgradTask& t = T.t[ti];
-    const int bid = (int)blockIdx.x - t.first;
-    const int64_t M = t.n_real && *t.n_real < t.M ? (int64_t)*t.n_real : t.M;
-    if (t.K <= 32) wgrad_body<1, 2>(smem, t.dY, t.X, t.K, M, t.rpb, t.part, bid);
-    else if (t.K <= 128) wgrad_body<4, 2>(smem, t.dY, t.X, t.K, M, t.rpb, t.part, bid);
-    else wgrad_body<6, 2>(smem, t.dY, t.X, t.K, M, t.rpb, t.part, bid);
-}
-
-// every weight-gradient partial product of a backward pass in ONE launch: blocks [0, n128) run the direct K = 128 kernel
-// (csrc/wgrad128.inc, two row slices), the others layer 0's products; the launch's LDS size is the larger of the two needs.
-// Neither group waits for the other, and the short layer-0 workgroups fill the CUs the long K = 128 ones leave towards the end.
-__global__ __launch_bounds__(512) void k_wgrad_all(const WgradTasks W, const WgradTasks W0, int n128) {
-    extern __shared__ __attribute__((aligned(16))) float smem[];
-    if ((int)blockIdx.x < n128) {
-        int ti = 0;
-        while (ti + 1 < W.n && (int)blockIdx.x >= W.t[ti + 1].first) ++ti;
-        wgrad128_block<2>(W.t[ti], (int)blockIdx.x - W.t[ti].first, smem);
-        return;
-    }
-    const int b = (int)blockIdx.x - n128;
-    int ti = 0;
-    while (ti + 1 < W0.n && b >= W0.t[ti + 1].first) ++ti;
-    const WgradTask& t = W0.t[ti];
-    const int bid = b - t.first;
-    const int64_t M = t.n_real && *t.n_real < t.M ? (int64_t)*t.n_real : t.M;
-    if (t.K <= 32) wgrad_body<1, 2>(smem, t.dY, t.X, t.K, M, t.rpb, t.part, bid);
-    else if (t.K <= 128) wgrad_body<4, 2>(smem, t.dY, t.X, t.K, M, t.rpb, t.part, bid);
-    else wgrad_body<6, 2>(smem, t.dY, t.X, t.K, M, t.rpb, t.part, bid);
-}
-
-// sums the native-layout partials over blocks and scatters them to dW [128][K] / db [128]
-template <int CTW, int NH>
-__device__ __forceinline__ void wgrad_reduce_body(int vb, float* sm, const float* __restrict__ part, int n_rows, int K,
-                                                  float* __restrict__ dW, float* __restrict__ db) {
-    constexpr int XW = 16 * CTW * NH;
-    constexpr int PW = 128 * XW + 128;
-    float(*red)[33] = reinterpret_cast<float(*)[33]>(sm);
-    const int c = threadIdx.x & 31, rg = threadIdx.x >> 5;
-    const int col = vb * 32 + c;
-    float acc = 0.f;
-    if (col < PW)
-        for (int r = rg; r < n_rows; r += 32) acc += part[(size_t)r * PW + col];
-    red[rg][c] = acc;
-    __syncthreads();
-    if (threadIdx.x < 32 && col < PW) {
-        float v = 0.f;
-#pragma unroll
-        for (int g = 0; g < 32; ++g) v += red[g][threadIdx.x];
-        if (col >= 128 * XW) {
-            db[col - 128 * XW] = v;
-        } else {
-            const int r = col & 3, lane = (col >> 2) & 63, tile = col >> 8;        // tile = (w*2+u)*CTW + cc
-            const int cc = tile % CTW, wu = tile / CTW, u = wu & 1, w = wu >> 1;
-            const int o = 32 * (w & 3) + 16 * u + 4 * (lane >> 4) + r;
-            const int xc = 16 * (CTW * (w >> 2) + cc) + (lane & 15);
-            if (xc < K) dW[(size_t)o * K + xc] = v;
-        }
-    }
-}
-
-template <int CTW, int NH>
-__global__ __launch_bounds__(1024) void k_wgrad_reduce(const float* __restrict__ part, int n_rows, int K,
-                                                       float* __restrict__ dW, float* __restrict__ db) {
-    __shared__ float sm[32 * 33];
-    wgrad_reduce_body<CTW, NH>(blockIdx.x, sm, part, n_rows, K, dW, db);
-}
-
-// ---- deferred reductions.  The backward pass leaves every per-block partial (attention-vector and edge-embedding
-// partials of each level, the edge-term column sums, the weight-gradient partials) in its own buffer and records a
-// task; ONE launch then runs them all (a dependent kernel costs >= 4.6 us of launch-to-launch latency on this
-// machine however small it is, and there were 27 of these per step).
-enum { RT_FINALIZE = 0, RT_COLSUM = 1, RT_WGRAD = 2 };
-struct ReduceTask {
-    int kind, first, nblk, H;
-    const float *p0, *p1;
-    int n0, n1;
-    fn_edge_term et;
-    const float* att;
-    int att_w, dst_off, src_off, K;
-    float *o0, *o1, *o2;
-    int ld, off, cls, pad_;
-};
-constexpr int kMaxReduceTasks = 36;      // one launch for all 30 tasks of a 4-layer backward pass (5.5 KB of kernel arguments)
-struct ReduceTasks {
-    ReduceTask t[kMaxReduceTasks];
-    int first[kMaxReduceTasks + 1];      // first block of every task, packed: a block finds its task by walking THIS array (three
-                                         // cache lines of the argument block) -- walking t[].first was one dependent scalar load
-                                         // per 152-byte struct, up to 30 in a row from the kernel-argument segment: 10 of the
-                                         // launch's 22 us before the first partial was read
-    int n;
-};
-// "fat" bodies for the task-table kernel: a block reduces 8 columns of a column-major [cols][FN_MAX_PART] partial
-// array (128 threads per column, contiguous reads), or a 256-column strip of the row-major weight-gradient partials
-// (64 float4 columns x 16 row groups: 1 KiB contiguous per wave and row) -- ~1.5 k blocks per backward pass instead
-// of ~10 k one-column blocks.
-// the same sum with 32 threads per column (a 1024-thread block takes 32 columns: a quarter of the blocks of the 128-thread form --
-// the deferred-reduction launch is mostly block scheduling, §6); no LDS, no barrier: the half-wave's butterfly finishes it
-__device__ __forceinline__ float colmajor_sum_32(const float* __restrict__ col, int n_rows) {
-    const int lane = threadIdx.x & 31;
-    float v = 0.f, v1 = 0.f, v2 = 0.f, v3 = 0.f;
-    int r = lane;
-    for (; r + 96 < n_rows; r += 128) { v += col[r];  v1 += col[r + 32];  v2 += col[r + 64];  v3 += col[r + 96]; }
-    for (; r < n_rows; r += 32) v += col[r];
-    v = (v + v1) + (v2 + v3);
-#pragma unroll
-    for (int off = 16; off > 0; off >>= 1) v += __shfl_xor(v, off);
-    return v;
-}
-template <int CTW, int NH, bool PLAIN = false>
-__device__ __forceinline__ void wgrad_reduce_strip(int vb, float* sm, const float* __restrict__ part, int n_rows, int K,
-                                                   float* __restrict__ dW, float* __restrict__ db) {
-    // a block sums a 1024-column strip of the partial rows: 256 float4 columns x 4 row groups (4 KiB contiguous per wave and
-    // row), four loads per thread in flight.  (Round 3: a strip used to be 256 columns x 16 row groups -- 65 blocks of 16
-    // waves per product that loaded two float4 each; a quarter of the waves now.)
-    constexpr int XW = 16 * CTW * NH;
-    constexpr int PW = 128 * XW + 128;
-    const int c4 = threadIdx.x & 255, rg = threadIdx.x >> 8;
-    const int col0 = vb * 1024 + c4 * 4;
-    float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (col0 < PW) {
-        float4 a1 = acc, a2 = acc, a3 = acc;
-        int r = rg;
-        for (; r + 12 < n_rows; r += 16) {
-            const float4 v0 = ld4(part + (size_t)r * PW + col0), v1 = ld4(part + (size_t)(r + 4) * PW + col0);
-            const float4 v2 = ld4(part + (size_t)(r + 8) * PW + col0), v3 = ld4(part + (size_t)(r + 12) * PW + col0);
-            acc.x += v0.x; acc.y += v0.y; acc.z += v0.z; acc.w += v0.w;
-            a1.x += v1.x; a1.y += v1.y; a1.z += v1.z; a1.w += v1.w;
-            a2.x += v2.x; a2.y += v2.y; a2.z += v2.z; a2.w += v2.w;
-            a3.x += v3.x; a3.y += v3.y; a3.z += v3.z; a3.w += v3.w;
-        }
-        for (; r < n_rows; r += 4) {
-            const float4 v = ld4(part + (size_t)r * PW + col0);
-            acc.x += v.x; acc.y += v.y; acc.z += v.z; acc.w += v.w;
-        }
-        acc.x = (acc.x + a1.x) + (a2.x + a3.x);  acc.y = (acc.y + a1.y) + (a2.y + a3.y);
-        acc.z = (acc.z + a1.z) + (a2.z + a3.z);  acc.w = (acc.w + a1.w) + (a2.w + a3.w);
-    }
-    st4(sm + rg * 1024 + c4 * 4, acc);
-    __syncthreads();
-    const int col = vb * 1024 + threadIdx.x;
-    if (col < PW) {
-        const float v = (sm[threadIdx.x] + sm[1024 + threadIdx.x]) + (sm[2048 + threadIdx.x] + sm[3072 + threadIdx.x]);
-        if (col >= 128 * XW) {
-            db[col - 128 * XW] = v;
-        } else if (PLAIN) {                                                          // k_wgrad128_multi: partials are [o][k] already
-            dW[col] = v;
-        } else {
-            const int r = col & 3, lane = (col >> 2) & 63, tile = col >> 8;        // tile = (w*2+u)*CTW + cc
-            const int cc = tile % CTW, wu = tile / CTW, u = wu & 1, w = wu >> 1;
-            const int o = 32 * (w & 3) + 16 * u + 4 * (lane >> 4) + r;
-            const int xc = 16 * (CTW * (w >> 2) + cc) + (lane & 15);
-            if (xc < K) dW[(size_t)o * K + xc] = v;
-        }
-    }
-}
-
-// the stand-alone launch of gat_finalize_body (fn_gat_bwd_finalize_f32): beside the task-table kernel that runs the same body
-__global__ __launch_bounds__(1024) void k_gat_finalize(const float* __restrict__ part_a, int n_a,
-                                                       const float* __restrict__ part_e, int n_e, fn_edge_term et,
-                                                       const float* __restrict__ att, int att_w, int dst_off,
-                                                       int src_off, float* __restrict__ g_att,
-                                                       float* __restrict__ g_embW, float* __restrict__ g_embb, int H) {
-    __shared__ float sm[1200];
-    gat_finalize_body(blockIdx.x, sm, part_a, n_a, part_e, n_e, et, att, att_w, dst_off, src_off, g_att, g_embW, g_embb, H);
-}
-
-__global__ __launch_bounds__(1024) void k_reduce_tasks(ReduceTasks T, AdamRide R) {
-    __shared__ float sm[16 * 256];
-    if (R.nblk && (int)blockIdx.x >= R.first) { adam_ride(R);  return; }
-    int ti = 0;
-    while (ti + 1 < T.n && (int)blockIdx.x >= T.first[ti + 1]) ++ti;
-    const ReduceTask& t = T.t[ti];
-    const int vb = (int)blockIdx.x - T.first[ti];
-    if (t.kind == RT_FINALIZE) {
-        if (vb < 2 * FN_D / 32) {
-            const int col = vb * 32 + (threadIdx.x >> 5);
-            const float v = colmajor_sum_32(t.p0 + (size_t)col * FN_MAX_PART, t.n0);
-            if ((threadIdx.x & 31) == 0) {
-                const int DH = FN_D / t.H, cc = col & 127, part = col >> 7;
-                t.o0[(cc / DH) * t.att_w + (part ? t.src_off : t.dst_off) + (cc % DH)] = v;
-            }
-        } else {             // (the one block behind them: a level with an embedded edge attribute, mode 2)
-            gat_finalize_body(2 * FN_D, sm, t.p0, t.n0, t.p1, t.n1, t.et, t.att, t.att_w, t.dst_off, t.src_off, t.o0, t.o1, t.o2, t.H);
-        }
-    } else if (t.kind == RT_COLSUM) {
-        const int col = vb * 32 + (threadIdx.x >> 5);
-        const float v = colmajor_sum_32(t.p0 + (size_t)col * FN_MAX_PART, t.n0);
-        if ((threadIdx.x & 31) == 0) t.o0[(col / FN_D) * t.ld + t.off + (col % FN_D)] = v;
-    } else {
-        switch (t.cls) {
-            case 0: wgrad_reduce_strip<1, 1>(vb, sm, t.p0, t.n0, t.K, t.o0, t.o1); break;
-            case 1: wgrad_reduce_strip<1, 2>(vb, sm, t.p0, t.n0, t.K, t.o0, t.o1); break;
-            case 2: wgrad_reduce_strip<4, 2>(vb, sm, t.p0, t.n0, t.K, t.o0, t.o1); break;
-            case 4: wgrad_reduce_strip<4, 2, true>(vb, sm, t.p0, t.n0, t.K, t.o0, t.o1); break;
-            default: wgrad_reduce_strip<6, 2>(vb, sm, t.p0, t.n0, t.K, t.o0, t.o1); break;
-        }
-    }
-}
-
-// column sums of part [n_rows][cols]: columns < split go to out0, the rest to out1.  1024 threads = 32 columns x 32 row groups
-__global__ __launch_bounds__(1024) void k_reduce_rows(const float* __restrict__ part, int n_rows, int64_t cols,
-                                                      float* __restrict__ out0, float* __restrict__ out1, int64_t split) {
-    __shared__ float red[32][33];
-    const int c = threadIdx.x & 31, rg = threadIdx.x >> 5;
-    const int64_t col = (int64_t)blockIdx.x * 32 + c;
-    float acc = 0.f;
-    if (col < cols)
-        for (int r = rg; r < n_rows; r += 32) acc += part[(size_t)r * cols + col];
-    red[rg][c] = acc;
-    __syncthreads();
-    if (threadIdx.x < 32 && col < cols) {
-        float v = 0.f;
-#pragma unroll
-        for (int g = 0; g < 32; ++g) v += red[g][threadIdx.x];
-        if (col < split) out0[col] = v;
-        else out1[col - split] = v;
-    }
-}
-
-template <int CTW, int NH>
-int launch_wgrad(const float* dY, const float* X, int K, int64_t M, int rpb, int grid, float* part, float* dW, float* db,
-                 hipStream_t st) {
-    constexpr int XW = 16 * CTW * NH, XLD = XW + 16, PW = 128 * XW + 128;
-    const size_t lds = (size_t)2 * kWgChunk * (kBtLd + XLD) * sizeof(float);
-    if (int rc = allow_lds(k_linear128_wgrad<CTW, NH>, lds)) return rc;
-    hipLaunchKernelGGL((k_linear128_wgrad<CTW, NH>), dim3(grid), dim3(256 * NH), lds, st, dY, X, K, M, rpb, part);
-    if (dW) hipLaunchKernelGGL((k_wgrad_reduce<CTW, NH>), dim3((PW + 31) / 32), dim3(1024), 0, st, part, grid, K, dW, db);
-    return 0;
-}
-inline int64_t wgrad_part_width(int K) {
-    const int xw = K <= 16 ? 16 : K <= 32 ? 32 : K <= 128 ? 128 : 192;
-    return (int64_t)128 * xw + 128;
-}
-inline int wgrad_rows_per_block(int64_t M) {
-    int64_t rpb = (M + 255) / 256;
-    rpb = (rpb + kWgChunk - 1) / kWgChunk * kWgChunk;
-    return (int)(rpb < kWgChunk ? kWgChunk : rpb);
 }
 
 }  // namespace
@@ -1134,161 +750,20 @@ struct ParamWork {
     int n_a = 0, n_e = 0;
     int n_rd = 0;                    // two-pass atom level: partial rows of the edge term's dL/da[:, mid block], reduced between the two
 };
-
-// weight-gradient partials only (the reduction is deferred); *grid = partial rows written, *cls = kernel class
-int wgrad_partials(const float* dY, const float* X, int K, int64_t M, float* ws, hipStream_t st, int* grid, int* cls) {
-    const int rpb = wgrad_rows_per_block(M);
-    *grid = (int)((M + rpb - 1) / rpb);
-    if (K <= 16) { *cls = 0;  return launch_wgrad<1, 1>(dY, X, K, M, rpb, *grid, ws, nullptr, nullptr, st); }
-    if (K <= 32) { *cls = 1;  return launch_wgrad<1, 2>(dY, X, K, M, rpb, *grid, ws, nullptr, nullptr, st); }
-    if (K <= 128) { *cls = 2;  return launch_wgrad<4, 2>(dY, X, K, M, rpb, *grid, ws, nullptr, nullptr, st); }
-    if (K <= 192) { *cls = 3;  return launch_wgrad<6, 2>(dY, X, K, M, rpb, *grid, ws, nullptr, nullptr, st); }
-    return fail(FN_EUNSUPPORTED, "weight gradient: K > 192");
+// ... as the parameter-gradient queue (param_grads.hip) takes it: the level's description unpacked into pointers and counts
+inline fni::AttParamGrads att_param_grads(const LevelView& v, const LevelWeights& g, const LevelScratch& sc, int n_a, int n_e) {
+    return fni::AttParamGrads{v.H, sc.part_a, n_a, sc.part_e, n_e, v.et, v.att, v.att_w, v.src_off, g.att, g.embW, g.embb};
 }
-
-struct ReduceQueue {
-    ReduceTasks T{};
-    WgradTasks W{}, W0{};                   // W: the K = 128 products; W0: the others (layer 0), k_linear128_wgrad_mixed
-    int blocks = 0, wblocks = 0, w0blocks = 0;
-    bool defer_mixed = false;
-    int w_reduce[kMaxWgradTasks] = {};      // index in T of each grouped product's reduction
-    hipStream_t st = nullptr;
-    // launches whatever the caller still holds back that the queued tasks read (the pipelined backward's pending source pass):
-    // a flush in the middle of a pass -- more than kMaxReduceTasks / kMaxWgradTasks queued, i.e. six or more layers -- would
-    // otherwise reduce partials and multiply rows that no kernel has written yet
-    std::function<int()> before_flush;
-    fn_adam_slice* rider = nullptr;         // fn_encoder.adam_rider: rides in the LAST deferred-reduction launch of the pass
-    int flush(bool last = false) {
-        if (before_flush) { if (int rc = before_flush()) return rc; }
-        if (int rc = flush_wgrad()) return rc;
-        const AdamRide R = make_adam_ride(last ? rider : nullptr, blocks, 1024, tune(FN_TUNE_RIDER_PIECES));
-        if (T.n == 0 && R.nblk == 0) return 0;
-        hipLaunchKernelGGL(k_reduce_tasks, dim3(blocks + R.nblk), dim3(1024), 0, st, T, R);
-        T.n = 0;  blocks = 0;
-        const int rc = launch_status("deferred reductions");
-        if (rc == 0 && R.nblk > 0) rider->launched = 1;      // the caller's Adam launch may now skip the slice (fn_adam_slice.launched)
-        return rc;
-    }
-    int push(ReduceTask t, int nblk) {
-        if (T.n == kMaxReduceTasks) { if (int rc = flush()) return rc; }
-        t.first = blocks;  t.nblk = nblk;
-        T.first[T.n] = blocks;
-        T.t[T.n++] = t;
-        blocks += nblk;
-        return 0;
-    }
-    // dL/d(attention vector, edge embedding) of a level from the n_a / n_e partial rows its pass left in the level's scratch
-    int finalize(const LevelView& v, const LevelWeights& g, const LevelScratch& sc, int n_a, int n_e) {
-        ReduceTask t{};
-        t.kind = RT_FINALIZE;  t.H = v.H;  t.p0 = sc.part_a;  t.n0 = n_a;  t.p1 = sc.part_e;  t.n1 = n_e;  t.et = v.et;
-        t.att = v.att;  t.att_w = v.att_w;  t.dst_off = 0;  t.src_off = v.src_off;  t.o0 = g.att;  t.o1 = g.embW;  t.o2 = g.embb;
-        return push(t, 2 * FN_D / 32 + (v.et.mode == 2 ? 1 : 0));
-    }
-    int colsum(const float* part, int n_rows, int cols, float* out, int ld, int off) {
-        ReduceTask t{};
-        t.kind = RT_COLSUM;  t.p0 = part;  t.n0 = n_rows;  t.o0 = out;  t.ld = ld;  t.off = off;
-        if (cols % 32) return fail(FN_EINVAL, "deferred column sum: column count must be a multiple of 32");
-        return push(t, cols / 32);
-    }
-    // dW [128,K], db [128] of a level's projection from its g_h rows: partial kernel now (on `launch_on`), reduction with the rest
-    int wgrad(const LevelView& v, const LevelWeights& g, const LevelScratch& sc, hipStream_t launch_on) {
-        const int K = v.K;
-        const int64_t M = v.rows;
-        float* ws = sc.wg_ws;
-        if (M == 0) {
-            hipLaunchKernelGGL(k_zero2_i32, dim3(flat_grid(128 * (K + 1), kGridCap)), dim3(kBlock), 0, launch_on,
-                               reinterpret_cast<int32_t*>(g.W), (int64_t)128 * K, reinterpret_cast<int32_t*>(g.bias), (int64_t)128);
-            return launch_status("weight gradient (empty)");
-        }
-        ReduceTask t{};
-        int grid = 0;
-        if (K == FN_D) {   // partial product joins the grouped launch in flush(); its block count is set there
-            if (W.n == kMaxWgradTasks || T.n == kMaxReduceTasks) { if (int rc = flush()) return rc; }
-            W.t[W.n] = WgradTask{sc.g_h, v.x, ws, M, 0, 0, 0, v.n_real};
-            w_reduce[W.n++] = T.n;
-            t.cls = tune(FN_TUNE_WGRAD_DIRECT) ? 4 : 2;
-        } else if (defer_mixed && K <= 192) {      // layer 0's products: one launch for them too (flush_wgrad)
-            if (W0.n == kMaxWgradTasks || T.n == kMaxReduceTasks) { if (int rc = flush()) return rc; }
-            // rows per block: a multiple of the per-product rule (FN_TUNE_WGRAD0_ROWS).  Fewer, longer blocks = fewer partial
-            // rows to write and to reduce: at 1 x layer 0's atom product alone wrote 217 partials of 98 KB (21 MB, more than the
-            // nine K = 128 products together).  2 x for it, 3 x for the narrow ones: -6 us per step; 3 x / 4 x for the wide one
-            // or 1 x for it lose (the long blocks become the launch's tail / the partial traffic is back)
-            const int tv = tune(FN_TUNE_WGRAD0_ROWS) > 0 ? tune(FN_TUNE_WGRAD0_ROWS) : 23;
-            const int mult = std::max(1, K > FN_D ? tv / 10 : tv % 10);          // tens: the wide product (atoms), units: the narrow ones
-            const int rpb = wgrad_rows_per_block(M) * mult;
-            grid = (int)((M + rpb - 1) / rpb);
-            W0.t[W0.n++] = WgradTask{sc.g_h, v.x, ws, M, rpb, w0blocks, K, v.n_real};
-            w0blocks += grid;
-            t.cls = K <= 32 ? 1 : K <= 128 ? 2 : 3;              // the instantiation k_linear128_wgrad_mixed runs for this K
-        } else if (int rc = wgrad_partials(sc.g_h, v.x, K, M, ws, launch_on, &grid, &t.cls)) return rc;
-        t.kind = RT_WGRAD;  t.p0 = ws;  t.n0 = grid;  t.K = K;  t.o0 = g.W;  t.o1 = g.bias;
-        // partial width of the instantiation that wrote them (the mixed launch runs K <= 16 in the K <= 32 class)
-        const int64_t pw = t.cls == 1 ? wgrad_part_width(32) : wgrad_part_width(K);
-        return push(t, (int)((pw + 1023) / 1024));
-    }
-    // block counts of the K = 128 group.  Rows per block from the WHOLE group: ~256 blocks (one per CU) instead of ~256 per product,
-    // which for the nine products of a backward pass was 1.6 k blocks writing 104 MB of 64-KB partials (now ~16 MB); never fewer rows
-    // than the per-product rule, so the partial workspace sized by fn_linear128_wgrad_ws still fits
-    void size_group128() {
-        int64_t total = 0;
-        for (int i = 0; i < W.n; ++i) total += W.t[i].M;
-        const int64_t target = tune(FN_TUNE_WGRAD_BLOCKS) > 0 ? tune(FN_TUNE_WGRAD_BLOCKS) : 256;
-        const int group_rpb = (int)(((total + target - 1) / target + kWgChunk - 1) / kWgChunk * kWgChunk);
-        wblocks = 0;
-        for (int i = 0; i < W.n; ++i) {
-            WgradTask& t = W.t[i];
-            t.rpb = std::max(group_rpb, wgrad_rows_per_block(t.M));
-            t.first = wblocks;
-            const int grid = (int)((t.M + t.rpb - 1) / t.rpb);
-            T.t[w_reduce[i]].n0 = grid;
-            wblocks += grid;
-        }
-        W.K = FN_D;
-    }
-    int flush_wgrad() {
-        size_t lds0 = 0;
-        if (W0.n) {
-            int kmax = 0;
-            for (int i = 0; i < W0.n; ++i) kmax = std::max(kmax, W0.t[i].K);
-            const int xw = kmax <= 32 ? 32 : kmax <= 128 ? 128 : 192;
-            lds0 = (size_t)2 * kWgChunk * (kBtLd + xw + 16) * sizeof(float);
-        }
-        if (W0.n && W.n && tune(FN_TUNE_WGRAD_DIRECT) == 1 && tune(FN_TUNE_GEMM_COLAUNCH) != 0) {
-            size_group128();         // both groups in one launch (k_wgrad_all)
-            const size_t lds = std::max(lds0, (size_t)wd_lds_bytes<2>());
-            if (int rc = allow_lds(k_wgrad_all, lds)) return rc;
-            hipLaunchKernelGGL(k_wgrad_all, dim3(wblocks + w0blocks), dim3(512), lds, st, W, W0, wblocks);
-            W.n = 0;  wblocks = 0;  W0.n = 0;  w0blocks = 0;
-            return launch_status("weight-gradient partials (all products)");
-        }
-        if (W0.n) {
-            const size_t lds = lds0;
-            if (int rc = allow_lds(k_linear128_wgrad_mixed, lds)) return rc;
-            hipLaunchKernelGGL(k_linear128_wgrad_mixed, dim3(w0blocks), dim3(512), lds, st, W0);
-            W0.n = 0;  w0blocks = 0;
-            if (int rc = launch_status("weight-gradient partials (layer 0)")) return rc;
-        }
-        if (W.n == 0) return 0;
-        size_group128();
-        if (tune(FN_TUNE_WGRAD_DIRECT)) {
-            if (int rc = allow_lds(k_wgrad128_multi<2>, wd_lds_bytes<2>())) return rc;
-            hipLaunchKernelGGL(k_wgrad128_multi<2>, dim3(wblocks), dim3(wd_threads<2>()), wd_lds_bytes<2>(), st, W);
-        } else {
-            constexpr int XW = 16 * 4 * 2, XLD = XW + 16;
-            const size_t lds = (size_t)2 * kWgChunk * (kBtLd + XLD) * sizeof(float);
-            if (int rc = allow_lds(k_linear128_wgrad_multi<4, 2>, lds)) return rc;
-            hipLaunchKernelGGL((k_linear128_wgrad_multi<4, 2>), dim3(wblocks), dim3(512), lds, st, W);
-        }
-        W.n = 0;  wblocks = 0;
-        return launch_status("grouped weight-gradient partials");
-    }
-    // a level's parameter work (ParamWork), queued in the order finalize, [column sum], weight gradient
-    int level_params(const LevelView& v, const LevelWeights& g, const LevelScratch& sc, const ParamWork& o, hipStream_t launch_on) {
-        if (int rc = finalize(v, g, sc, o.n_a, o.n_e)) return rc;
-        if (o.n_rd) { if (int rc = colsum(sc.part_rd, o.n_rd, v.H * FN_D, g.att, v.att_w, v.mid_off)) return rc; }
-        return wgrad(v, g, sc, launch_on);
-    }
-};
+// the partial rows of the edge term's dL/d(att[:, mid block]) (a level whose edge term is a table of row dots): their column sums
+int edge_term_colsum(ParamGradQueue& rq, const LevelView& v, const LevelWeights& g, const LevelScratch& sc, int n_rd) {
+    return rq.colsum(sc.part_rd, n_rd, v.H * FN_D, g.att, v.att_w, v.mid_off);
+}
+// queued in the order finalize, [column sum], weight gradient (a lone partial product is launched on `launch_on`)
+int level_params(ParamGradQueue& rq, const LevelView& v, const LevelWeights& g, const LevelScratch& sc, const ParamWork& o, hipStream_t launch_on) {
+    FN_TRY(rq.finalize(att_param_grads(v, g, sc, o.n_a, o.n_e)));
+    if (o.n_rd) FN_TRY(edge_term_colsum(rq, v, g, sc, o.n_rd));
+    return rq.wgrad(fni::ProjWgrad{sc.g_h, v.x, v.K, v.rows, sc.wg_ws, v.n_real, g.W, g.bias}, launch_on);
+}
 
 // the source pass alone (fn_gat_bwd_src_f32)
 int launch_gat_bwd_src(const GatBwdSrcArgs& A, int heads, hipStream_t st) {
@@ -1431,7 +906,7 @@ struct LastGrads {
 // one_pass: the caller runs the one-pass backward next -- the molecule-resident tail writes the dots of the rows it finishes and may
 // carry the Adam rider (which then leaves rq)
 int last_layer_output_grads(const fn_encoder* e, const EncLayout& lay, const BwdLayout& bw, const EncOutputs& y, const EncOutputs& gy,
-                            const fn_layer_weights* grads, ReduceQueue& rq, bool one_pass, hipStream_t hs, LastGrads* out) {
+                            const fn_layer_weights* grads, ParamGradQueue& rq, bool one_pass, hipStream_t hs, LastGrads* out) {
     const int H = e->heads, l = e->n_layers - 1;
     const bool lite = e->variant == 1, edge = e->variant == 2;
     const LevelView vf = level_view(e, lay, l, LV_FRAG);
@@ -1465,8 +940,8 @@ int last_layer_output_grads(const fn_encoder* e, const EncLayout& lay, const Bwd
         bool rode = false;
         FN_TRY(launch_tail_bwd(e, lay, bw, y, gy, have_fbond, &n_part, hs, one_pass, one_pass ? &rode : nullptr));
         if (rode) rq.rider = nullptr;          // the head's Adam slice went with this launch
-        FN_TRY(rq.finalize(vf, gf, sf, n_part, 0));
-        FN_TRY(rq.colsum(sf.part_rd, n_part, H * FN_D, gf.att, vf.att_w, vf.mid_off));
+        FN_TRY(rq.finalize(att_param_grads(vf, gf, sf, n_part, 0)));
+        FN_TRY(edge_term_colsum(rq, vf, gf, sf, n_part));
         have_atoms = have_fbond = true;        // g_pre of the atoms and fragment bonds is complete (scatter to the atoms included)
         out->tail_dots_atoms = one_pass;  out->tail_dots_fbond = one_pass && H == 4;
     } else if (have_frags && lite) {
@@ -1475,7 +950,7 @@ int last_layer_output_grads(const fn_encoder* e, const EncLayout& lay, const Bwd
     } else if (have_frags && edge) {   // gat2_edge: the edge term's parameters are the cnx_attr Linear (emb_fb_*) and f's middle block
         FN_TRY(fn_gat_bwd_dst_f32(bw.g_pre[LV_FRAG], vf.a.h, vf.a.p, &vf.et, vf.pl, 0.2f, nullptr, nullptr, sf.pz, sf.g_s_dst, sf.part_e, &n_e, H, hs));
         FN_TRY(fn_gat_bwd_src_f32(bw.g_pre[LV_FRAG], vf.a.h, sf.pz, sf.g_s_dst, vf.att, vf.att_w, 0, vf.src_off, vf.pl, bw.g_frags, sf.part_a, &n_a, H, hs));
-        FN_TRY(rq.finalize(vf, gf, sf, n_a, n_e));
+        FN_TRY(rq.finalize(att_param_grads(vf, gf, sf, n_a, n_e)));
         have_g_frags_h = true;
     } else if (have_frags) {
         FN_TRY(fn_gat_bwd_dst_f32(bw.g_pre[LV_FRAG], vf.a.h, vf.a.p, &vf.et, vf.pl, 0.2f, nullptr, sf.dz, sf.pz, sf.g_s_dst, nullptr, &n_e, H, hs));
@@ -1483,8 +958,8 @@ int last_layer_output_grads(const fn_encoder* e, const EncLayout& lay, const Bwd
         int gr = 0;
         FN_TRY(bwd_src_and_edge_term(vf, sf, bw.g_pre[LV_FRAG], bw.g_frags, lay.L[l].lv[LV_FBOND].raw, bw.g_pre[LV_FBOND], have_fbond, &n_a, &gr, hs));
         if (gr) have_fbond = true;
-        FN_TRY(rq.finalize(vf, gf, sf, n_a, 0));
-        if (gr) FN_TRY(rq.colsum(sf.part_rd, gr, H * FN_D, gf.att, vf.att_w, vf.mid_off));
+        FN_TRY(rq.finalize(att_param_grads(vf, gf, sf, n_a, 0)));
+        if (gr) FN_TRY(edge_term_colsum(rq, vf, gf, sf, gr));
         have_g_frags_h = true;
     }
     // atom -> fragment sum: dL/datoms_new += dL/dfrags[a2f]
@@ -1512,7 +987,7 @@ int encoder_backward_one(const fn_encoder* e, const EncLayout& lay, const BwdLay
                          const EncOutputs& gy, const fn_layer_weights* grads, hipStream_t hs) {
     const int H = e->heads, NL = e->n_layers;
     const bool no_fb = e->variant != 0;          // gat2_lite / gat2_edge: neither has a fragment-bond graph
-    ReduceQueue rq;
+    ParamGradQueue rq;
     rq.st = hs;
     rq.defer_mixed = tune(FN_TUNE_GEMM_COLAUNCH) != 0;
     rq.rider = e->adam_rider;
@@ -1584,7 +1059,7 @@ int encoder_backward_one(const fn_encoder* e, const EncLayout& lay, const BwdLay
         const bool rd_rows_ride = have_atoms && pend_b && H == 4 && e->atom.m_real == e->E && e->E > 0;   // the bond product of layer l+1 carries the rows' term
         const int gr = have_atoms && e->atom.m_real > 0 ? row_grid(e->atom.m_real, tune(FN_TUNE_RD_BLOCKS) > 0 ? tune(FN_TUNE_RD_BLOCKS) : kRowDotsBwdBlocks) : 0;
         if (pend_b) {        // layer l+1's bond level: parameter work + dL/d(pre-activation bond output of layer l)
-            FN_TRY(rq.level_params(vb_up, level_weights(grads[l + 1], LV_BOND), scratch(vb_up), ParamWork{nb.n_a, nb.n_e}, hs));
+            FN_TRY(level_params(rq, vb_up, level_weights(grads[l + 1], LV_BOND), scratch(vb_up), ParamWork{nb.n_a, nb.n_e}, hs));
             const RowAdd ra{sa.dz, va.att + va.mid_off, va.att_w};
             // the rows are complete in this epilogue unless the edge term's rows' part is added behind the product (no RowAdd carrier)
             const bool complete = rd_rows_ride || gr == 0;
@@ -1593,14 +1068,14 @@ int encoder_backward_one(const fn_encoder* e, const EncLayout& lay, const BwdLay
             nxt_bond = true;
         }
         if (pend_fb) {
-            FN_TRY(rq.level_params(vfb_up, level_weights(grads[l + 1], LV_FBOND), scratch(vfb_up), ParamWork{nfb.n_a, nfb.n_e}, hs));
+            FN_TRY(level_params(rq, vfb_up, level_weights(grads[l + 1], LV_FBOND), scratch(vfb_up), ParamWork{nfb.n_a, nfb.n_e}, hs));
             // (the fragment graph's edge term, the only reader of raw fragment-bond rows, exists in the last layer alone)
             product(vfb_up, vfb, nullptr, cu_epi(vfb, false));
             nxt_fbond = true;
         }
         RowDotsBwdArgs R{};
         if (have_atoms) {
-            FN_TRY(rq.level_params(va, ga, sa, ParamWork{na.n_a, 0}, hs));
+            FN_TRY(level_params(rq, va, ga, sa, ParamWork{na.n_a, 0}, hs));
             if (l) {
                 product(va, va_below, nullptr, cu_epi(va_below, false));
                 nxt_atoms = true;
@@ -1612,7 +1087,7 @@ int encoder_backward_one(const fn_encoder* e, const EncLayout& lay, const BwdLay
                 R = RowDotsBwdArgs{sa.dz, vb.a.raw, va.att, va.att_w, va.mid_off, H, *va.pl, rd_rows_ride ? nullptr : bw.g_pre[LV_BOND], sa.part_rd,
                                    (!rd_rows_ride && have_b_now) ? (const float*)bw.g_pre[LV_BOND] : nullptr, 1, gr};
                 R.n_real = vb.n_real;
-                FN_TRY(rq.colsum(sa.part_rd, gr, H * FN_D, ga.att, va.att_w, va.mid_off));
+                FN_TRY(edge_term_colsum(rq, va, ga, sa, gr));
                 if (!pend_b) {
                     // the bond rows of this layer are finished by the edge term's rows' part: with four heads it writes their dots too
                     const LevelScratch& sb = scratch(vb);
@@ -1653,8 +1128,8 @@ int encoder_backward_one(const fn_encoder* e, const EncLayout& lay, const BwdLay
         FN_TRY(prof_event(2, hs));
         FN_TRY(launch_gat_bwd_one3(oB, GatBwdOneArgs{}, oFB, H, hs));
         FN_TRY(prof_event(3, hs));
-        if (pend_b) FN_TRY(rq.level_params(vb, level_weights(grads[0], LV_BOND), sb, ParamWork{nb.n_a, nb.n_e}, hs));
-        if (pend_fb) FN_TRY(rq.level_params(vfb, level_weights(grads[0], LV_FBOND), sfb, ParamWork{nfb.n_a, nfb.n_e}, hs));
+        if (pend_b) FN_TRY(level_params(rq, vb, level_weights(grads[0], LV_BOND), sb, ParamWork{nb.n_a, nb.n_e}, hs));
+        if (pend_fb) FN_TRY(level_params(rq, vfb, level_weights(grads[0], LV_FBOND), sfb, ParamWork{nfb.n_a, nfb.n_e}, hs));
     }
     return rq.flush(true);
 }
@@ -1985,9 +1460,9 @@ int fn_encoder_backward(const fn_encoder* e, const float* out_atoms, const float
     if (one_pass_on(e)) return encoder_backward_one(e, lay, bw, rng, y, gy, grads, S(st));
     const int H = e->heads;
     hipStream_t hs = S(st);
-    ReduceQueue rq;
+    ParamGradQueue rq;
     rq.st = hs;                      // all parameter-gradient reductions run as one launch at the very end, and so do the K = 128
-                                     // weight-gradient partial products (ReduceQueue::wgrad)
+                                     // weight-gradient partial products (ParamGradQueue::wgrad)
     rq.defer_mixed = tune(FN_TUNE_GEMM_COLAUNCH) != 0;      // ... and layer 0's
     rq.rider = e->adam_rider;
 
@@ -2025,7 +1500,7 @@ int fn_encoder_backward(const fn_encoder* e, const float* out_atoms, const float
             // source pass + the edge term <new_bond, a[:, d:d+128]> (dL/dnew_bond accumulates into g_pre of the bonds, dL/da mid block)
             FN_TRY(bwd_src_and_edge_term(va, sa, bw.g_pre[LV_ATOM], sa.g_h, vb.a.raw, bw.g_pre[LV_BOND], have[LV_BOND], &n_a, &gr, hs));
             if (gr) have[LV_BOND] = true;
-            FN_TRY(rq.level_params(va, level_weights(g, LV_ATOM), sa, ParamWork{n_a, 0, gr}, hs));
+            FN_TRY(level_params(rq, va, level_weights(g, LV_ATOM), sa, ParamWork{n_a, 0, gr}, hs));
             if (l) input_grad(va, sa);
         }
 
@@ -2044,10 +1519,10 @@ int fn_encoder_backward(const fn_encoder* e, const float* out_atoms, const float
         // (the fragment-bond level's product and parameter work are queued before the bond level's)
         if (have[LV_FBOND]) {
             if (l) input_grad(vfb, sfb);
-            FN_TRY(rq.level_params(vfb, level_weights(g, LV_FBOND), sfb, ParamWork{nfb.n_a, nfb.n_e}, hs));
+            FN_TRY(level_params(rq, vfb, level_weights(g, LV_FBOND), sfb, ParamWork{nfb.n_a, nfb.n_e}, hs));
         }
         if (have[LV_BOND]) {
-            FN_TRY(rq.level_params(vb, level_weights(g, LV_BOND), sb, ParamWork{nb.n_a, nb.n_e}, hs));
+            FN_TRY(level_params(rq, vb, level_weights(g, LV_BOND), sb, ParamWork{nb.n_a, nb.n_e}, hs));
             if (l) input_grad(vb, sb);
         }
         if (dxT.n) FN_TRY(launch_linear128_group(dxT, hs));
@@ -2106,17 +1581,6 @@ int fn_sort_edge_attr_src_f32(const float* x, int K, const fn_gat_plan* plan, fl
     return launch_status("fn_sort_edge_attr_src_f32");
 }
 
-int fn_gat_bwd_finalize_f32(const float* part_a, int n_part_a, const float* part_e, int n_part_e, const fn_edge_term* et,
-                            const float* att, int att_w, int dst_off, int src_off, float* g_att, float* g_embW,
-                            float* g_embb, int heads, fn_stream_t stream) {
-    if (!part_a || n_part_a < 0 || n_part_e < 0 || !att || !g_att || fni::bad_edge_term(et, 0)) return fail(FN_EINVAL, "fn_gat_bwd_finalize_f32: bad argument");
-    if (et->mode == 2 && (!part_e || !g_embW || !g_embb)) return fail(FN_EINVAL, "fn_gat_bwd_finalize_f32: null mode-2 buffer");
-    if (heads != 1 && heads != 2 && heads != 4 && heads != 8) return fail(FN_EUNSUPPORTED, "heads must be 1, 2, 4 or 8");
-    hipLaunchKernelGGL(k_gat_finalize, dim3(2 * FN_D + (et->mode == 2 ? 1 : 0)), dim3(1024), 0, S(stream), part_a, n_part_a, part_e, n_part_e, *et, att,
-                       att_w, dst_off, src_off, g_att, g_embW, g_embb, heads);
-    return launch_status("fn_gat_bwd_finalize_f32");
-}
-
 int fn_row_dots_sorted_bwd_f32(const float* g_s_sorted, const float* feat, const float* A, int lda, int off, int J,
                                const fn_gat_plan* plan, float* g_feat, float* part, int* n_part, fn_stream_t stream) {
     if (!A || !plan || !part || !n_part || J < 1 || J > 8 || ((lda | off) & 3))
@@ -2128,32 +1592,6 @@ int fn_row_dots_sorted_bwd_f32(const float* g_s_sorted, const float* feat, const
     hipLaunchKernelGGL(k_row_dots_sorted_bwd, dim3(g), dim3(kBlock), 0, S(stream),
                        RowDotsBwdArgs{g_s_sorted, feat, A, lda, off, J, *plan, g_feat, part, nullptr, 0, g});
     return launch_status("fn_row_dots_sorted_bwd_f32");
-}
-
-int64_t fn_linear128_wgrad_ws(int64_t M, int K) {
-    const int rpb = wgrad_rows_per_block(M);
-    const int64_t grid = (M + rpb - 1) / rpb;
-    return (grid < 1 ? 1 : grid) * wgrad_part_width(K);
-}
-
-int fn_linear128_wgrad_f32(const float* dY, const float* X, int K, int64_t M, float* ws, float* dW, float* db, fn_stream_t stream) {
-    if (K < 1 || M < 0 || !dW || !db) return fail(FN_EINVAL, "fn_linear128_wgrad_f32: bad argument");
-    if (M == 0) {
-        hipLaunchKernelGGL(k_zero2_i32, dim3(flat_grid(128 * (K + 1), kGridCap)), dim3(kBlock), 0, S(stream),
-                           reinterpret_cast<int32_t*>(dW), (int64_t)128 * K, reinterpret_cast<int32_t*>(db), (int64_t)128);
-        return launch_status("fn_linear128_wgrad_f32");
-    }
-    if (!dY || !X || !ws || ((uintptr_t)dY & 15)) return fail(FN_EINVAL, "fn_linear128_wgrad_f32: null or misaligned buffer");
-    const int rpb = wgrad_rows_per_block(M);
-    const int grid = (int)((M + rpb - 1) / rpb);
-    int rc;
-    if (K <= 16) rc = launch_wgrad<1, 1>(dY, X, K, M, rpb, grid, ws, dW, db, S(stream));
-    else if (K <= 32) rc = launch_wgrad<1, 2>(dY, X, K, M, rpb, grid, ws, dW, db, S(stream));
-    else if (K <= 128) rc = launch_wgrad<4, 2>(dY, X, K, M, rpb, grid, ws, dW, db, S(stream));
-    else if (K <= 192) rc = launch_wgrad<6, 2>(dY, X, K, M, rpb, grid, ws, dW, db, S(stream));
-    else return fail(FN_EUNSUPPORTED, "fn_linear128_wgrad_f32: K > 192");
-    if (rc) return rc;
-    return launch_status("fn_linear128_wgrad_f32");
 }
 
 }  // extern "C"

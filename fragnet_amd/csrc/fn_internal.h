@@ -36,7 +36,8 @@ static_assert(sizeof(MolExt) == 64, "MolExt is sixteen int32 (include/fragnet_hi
 
 // ---- argument blocks and host-side entry points shared by the translation units, grouped by the unit that defines them: the forward
 // attention family in gat_fwd.hip / gat_fwd_lin.hip, the one-pass attention backward in gat_bwd_one.hip, the operator surface (and the
-// grouped projection launches) in fragnet_hip.hip.  The engine, encoder.hip, offers nothing here: it is the caller of all of them, and
+// grouped projection launches) in fragnet_hip.hip, the parameter-gradient queue in param_grads.hip.  The engine, encoder.hip, offers
+// nothing here: it is the caller of all of them, and
 // besides these hooks it calls the C-ABI's own single-operator entry points where a level or variant runs them one by one
 // (fn_gat_bwd_dst_f32, fn_gat_fwd_f32, fn_node_scalars_f32, fn_row_dots_sorted_f32, fn_dropout_act_f32, fn_linear128_f32,
 // fn_segment_sum_f32).
@@ -180,6 +181,82 @@ struct AttnReadoutTask {
 FNI_HIDDEN int launch_attn_readout(const AttnReadoutTask* tasks, int n_tasks, int heads, hipStream_t st);
 // input_grad.hip: up to FN_MAX_DX_TASKS products dx = g W (+ row dots with a caller table) in ONE launch; fn_linear_dx_f32 itself
 FNI_HIDDEN int launch_linear_dx(const fn_linear_dx_task* tasks, int n_tasks, hipStream_t st);
+// ---- param_grads.hip: the parameter-gradient family.  A backward pass leaves per-block partials behind (attention-vector and
+// edge-embedding partials of each level, the edge term's column sums, the weight-gradient partials) and queues a task per reduction; the
+// queue launches the grouped weight-gradient partial products and then ONE kernel for all reductions (k_reduce_tasks).  The argument
+// blocks of those kernels:
+enum { RT_FINALIZE = 0, RT_COLSUM = 1, RT_WGRAD = 2 };
+struct ReduceTask {
+    int kind, first, nblk, H;
+    const float *p0, *p1;
+    int n0, n1;
+    fn_edge_term et;
+    const float* att;
+    int att_w, dst_off, src_off, K;
+    float *o0, *o1, *o2;
+    int ld, off, cls, pad_;      // cls (RT_WGRAD): the class of the kernel that wrote the partials (param_grads.hip: wgrad_class)
+};
+constexpr int kMaxReduceTasks = 36;      // one launch for all 30 tasks of a 4-layer backward pass (5.5 KB of kernel arguments)
+struct ReduceTasks {
+    ReduceTask t[kMaxReduceTasks];
+    int first[kMaxReduceTasks + 1];      // first block of every task, packed: a block finds its task by walking THIS array (three
+                                         // cache lines of the argument block) -- walking t[].first was one dependent scalar load
+                                         // per 152-byte struct, up to 30 in a row from the kernel-argument segment: 10 of the
+                                         // launch's 22 us before the first partial was read
+    int n;
+};
+struct WgradTask {
+    const float *dY, *X;
+    float* part;
+    int64_t M;
+    int rpb, first;
+    int K;                    // k_linear128_wgrad_mixed only: this product's reduction length (0 elsewhere: WgradTasks::K)
+    const int32_t* n_real;    // nullable device word: rows at or behind *n_real are padding (zero gradient rows) and are not read
+};
+constexpr int kMaxWgradTasks = 3 * FN_MAX_LAYERS;
+struct WgradTasks {
+    WgradTask t[kMaxWgradTasks];
+    int n, K;
+};
+// what the queue's methods take: pointers and counts, nothing of the caller's own types
+struct AttParamGrads {       // dL/d(attention vector [H][att_w], edge embedding) of a level from the partial rows its pass wrote
+    int H;
+    const float* part_a;  int n_a;      // column-major [2 * 128][FN_MAX_PART]: destination / source block partials, n_a rows written
+    const float* part_e;  int n_e;      // mode-2 levels: [n_e][H * (K + 1)] edge-embedding partials (else null / 0)
+    fn_edge_term et;
+    const float* att;  int att_w, src_off;      // the level's attention vector; destination block at 0, source block at src_off
+    float *g_att, *g_embW, *g_embb;     // out (the last two: mode 2 only)
+};
+struct ProjWgrad {           // dW [128][K], db [128] of a projection from its gradient rows g_h [M][128] and input rows x [M][K]
+    const float *g_h, *x;
+    int K;
+    int64_t M;
+    float* ws;                // partial workspace, fn_linear128_wgrad_ws(M, max(K, 128)) floats
+    const int32_t* n_real;    // nullable device word: rows at or behind it are padding
+    float *dW, *db;
+};
+// A stack object of a backward pass; nothing is allocated.  The settings are set once before the first task.  A flush in the middle of a
+// pass (more than kMaxReduceTasks / kMaxWgradTasks queued: six or more layers) runs what is queued, so everything a queued task reads
+// must have been launched on `st` before the task is queued.
+struct FNI_HIDDEN ParamGradQueue {
+    hipStream_t st = nullptr;               // the grouped products and the reductions run here
+    bool defer_mixed = false;               // layer 0's products (K != 128) wait for a grouped launch too, instead of one launch each
+    fn_adam_slice* rider = nullptr;         // fn_encoder.adam_rider: rides in the LAST deferred-reduction launch of the pass (null: none, or gone elsewhere)
+    int finalize(const AttParamGrads& a);
+    // out[(col / 128) * ld + off + col % 128] = sum of the n_rows written rows of column col of part (column-major [cols][FN_MAX_PART])
+    int colsum(const float* part, int n_rows, int cols, float* out, int ld, int off);
+    // partial product now (on `launch_on`) where it is launched alone, else with its group in flush(); reduction with the rest
+    int wgrad(const ProjWgrad& p, hipStream_t launch_on);
+    int flush(bool last = false);           // last: the pass's final flush, which carries the rider
+private:
+    ReduceTasks T{};
+    WgradTasks W{}, W0{};                   // W: the K = 128 products; W0: the others (layer 0), k_linear128_wgrad_mixed
+    int blocks = 0, wblocks = 0, w0blocks = 0;
+    int w_reduce[kMaxWgradTasks] = {};      // index in T of each grouped product's reduction
+    int push(ReduceTask t, int nblk);
+    void size_group128();
+    int flush_wgrad();
+};
 FNI_HIDDEN int prof_event(int i, hipStream_t st);                             // records event i of fn_debug_set_profile_events, if set
 FNI_HIDDEN bool bad_edge_term(const fn_edge_term* et, int64_t m);
 }  // namespace fni
@@ -373,7 +450,17 @@ template <int W> __device__ __forceinline__ float group_max(float v) {
     for (int off = W / 2; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off));
     return v;
 }
-
+// sum of up to 1024 values, one per thread (deterministic: wave butterflies, then 16 wave sums in order)
+__device__ __forceinline__ float block_sum_1024(float v, float* s16) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
+    if ((threadIdx.x & 63) == 0) s16[threadIdx.x >> 6] = v;
+    __syncthreads();
+    float t = 0.f;
+#pragma unroll
+    for (int w = 0; w < 16; ++w) t += s16[w];
+    return t;
+}
 
 // ---- reductions over the LPH lanes of one head group.  DPP row operations (one VALU op each) instead of
 // ds_bpermute: row_half_mirror pairs lane i with 7-i inside each 8 lanes, quad_perm covers xor 1 / xor 2.

@@ -1,9 +1,10 @@
 // gat_bwd_two.inc -- the general TWO-PASS backward of an attention level (destination pass + source pass; rounds 1-3) and the
 // by-source attention read-out (k_attn_by_src): device code and the host-side argument preparation, included inside the anonymous
-// namespace of fragnet_hip.hip (the destination pass, k_attn_by_src) and of encoder.hip (the source pass, the finalize and the combined
+// namespace of fragnet_hip.hip (the destination pass, k_attn_by_src) and of encoder.hip (the source pass and the combined
 // launches that run the same bodies)
 // behind gat_fwd.inc.  Templates and inline functions only: a __global__ function that is no template would be compiled into both
-// units (k_gat_finalize, the stand-alone launch of gat_finalize_body, is in encoder.hip for that reason, beside k_reduce_tasks).  The engine's default since round 4 is the one-pass backward (gat_bwd_one.inc); these kernels serve head counts and
+// units.  (The finalize of the partials these passes write, gat_finalize_body with k_gat_finalize, is in param_grads.hip, beside
+// k_reduce_tasks.)  The engine's default since round 4 is the one-pass backward (gat_bwd_one.inc); these kernels serve head counts and
 // hand-built graphs the one-pass kernel does not take, the fragment graph inside the tail (mol_tail.inc shares their row cores) and
 // the operator path's fallback (fn_gat_bwd_dst_f32 / fn_gat_bwd_src_f32).
 
@@ -383,94 +384,6 @@ __global__ __launch_bounds__(RB * 32) void k_gat_bwd_src(GatBwdSrcArgs A) {
     gat_bwd_src_body<H, RB>(A, sA, (int)blockIdx.x, (int)gridDim.x);
 }
 
-
-// sum of up to 1024 values, one per thread (deterministic: wave butterflies, then 16 wave sums in order)
-__device__ __forceinline__ float block_sum_1024(float v, float* s16) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-    if ((threadIdx.x & 63) == 0) s16[threadIdx.x >> 6] = v;
-    __syncthreads();
-    float t = 0.f;
-#pragma unroll
-    for (int w = 0; w < 16; ++w) t += s16[w];
-    return t;
-}
-
-// blocks 0..255: one column each of the column-major [256][FN_MAX_PART] a_dst/a_src partials; block 256 (mode 2
-// only): the [n_e, H*(K+1)] edge-embedding partials and the chain rule through the folded weights.
-// (body shared by k_gat_finalize and the deferred task-table kernel k_reduce_tasks, both in encoder.hip; vb = virtual block index,
-// sm = 1200 floats of shared memory)
-__device__ __forceinline__ void gat_finalize_body(int vb, float* sm, const float* __restrict__ part_a, int n_a,
-                                                  const float* __restrict__ part_e, int n_e, const fn_edge_term& et,
-                                                  const float* __restrict__ att, int att_w, int dst_off, int src_off,
-                                                  float* __restrict__ g_att, float* __restrict__ g_embW,
-                                                  float* __restrict__ g_embb, int H) {
-    float* s16 = sm;
-    float(*redE)[128] = reinterpret_cast<float(*)[128]>(sm + 16);
-    float* sE = sm + 16 + 1024;
-    const int tid = threadIdx.x;
-    if (vb < 2 * FN_D) {
-        const int col = vb;
-        float mine = 0.f;
-        for (int r = tid; r < n_a; r += 1024) mine += part_a[(size_t)col * FN_MAX_PART + r];
-        const float v = block_sum_1024(mine, s16);
-        if (tid == 0) {
-            const int DH = FN_D / H;
-            const int cc = col & 127, part = col >> 7;
-            g_att[(cc / DH) * att_w + (part ? src_off : dst_off) + (cc % DH)] = v;
-        }
-        return;
-    }
-    const int K = et.K, d_e = et.d_e;
-    const int ne = H * (K + 1);     // <= 72
-    {   // column sums of part_e [n_e][ne]: the 1024 threads form (1024 / cp) row groups x cp columns, cp = pow2 >= ne
-        float* red = &redE[0][0];   // 1024 floats
-        int cp = 8;
-        while (cp < ne) cp <<= 1;
-        const int groups = 1024 / cp, col = tid % cp, grp = tid / cp;
-        float acc = 0.f;
-        if (col < ne) {
-            // four loads in flight per thread: with one, this single block was a chain of ~30 dependent round trips (n_e =
-            // 3888 partial rows for the bond level) and the whole deferred-reduction launch waited for it (25 -> 14 us)
-            float a1 = 0.f, a2 = 0.f, a3 = 0.f;
-            int r = grp;
-            for (; r + 3 * groups < n_e; r += 4 * groups) {
-                acc += part_e[(size_t)r * ne + col];
-                a1 += part_e[(size_t)(r + groups) * ne + col];
-                a2 += part_e[(size_t)(r + 2 * groups) * ne + col];
-                a3 += part_e[(size_t)(r + 3 * groups) * ne + col];
-            }
-            for (; r < n_e; r += groups) acc += part_e[(size_t)r * ne + col];
-            acc = (acc + a1) + (a2 + a3);
-        }
-        red[grp * cp + col] = acc;
-        __syncthreads();
-        if (tid < 128) {
-            float v = 0.f;
-            if (tid < ne)
-                for (int g = 0; g < groups; ++g) v += red[g * cp + tid];
-            sE[tid] = v;
-        }
-        __syncthreads();
-    }
-    if (tid < H * d_e) {
-        const int hh = tid / d_e, c = tid % d_e;
-        float a = sE[hh * (K + 1) + K] * et.embb[c];
-        for (int k = 0; k < K; ++k) a = fmaf(sE[hh * (K + 1) + k], et.embW[c * K + k], a);
-        g_att[hh * att_w + et.mid_off + c] = a;
-    }
-    if (tid < d_e * K) {
-        const int c = tid / K, k = tid % K;
-        float a = 0.f;
-        for (int hh = 0; hh < H; ++hh) a = fmaf(sE[hh * (K + 1) + k], att[hh * att_w + et.mid_off + c], a);
-        g_embW[tid] = a;
-    }
-    if (tid < d_e) {
-        float a = 0.f;
-        for (int hh = 0; hh < H; ++hh) a = fmaf(sE[hh * (K + 1) + K], att[hh * att_w + et.mid_off + tid], a);
-        g_embb[tid] = a;
-    }
-}
 
 template <int H>
 __global__ void k_attn_by_src(const float* __restrict__ p_sorted, fn_gat_plan pl, float* __restrict__ attn) {

@@ -1,5 +1,5 @@
 // Weight-gradient partial products dW[128 o][128 k] = sum_rows dY[r][o] X[r][k] of the K = 128 projections, direct form
-// (included into the anonymous namespace of encoder.hip after WgradTasks; FN_TUNE_WGRAD_DIRECT).
+// (included into the anonymous namespace of param_grads.hip; WgradTask / WgradTasks: fn_internal.h; FN_TUNE_WGRAD_DIRECT).
 //
 // Both operands run ACROSS the reduction index (a row of dY / X is contiguous in o / k), so -- as in csrc/dense_head.inc --
 // lane (n, g) of v_mfma_f32_16x16x4_f32 takes the four columns 4n .. 4n+3 of row r0 + g of each operand as one 16-byte
