@@ -178,11 +178,11 @@ __global__ __launch_bounds__(RB * 32) void k_gat_bwd_src_rd(GatBwdSrcArgs A, Row
     else row_dots_sorted_bwd_body(T, reinterpret_cast<float(*)[FN_D]>(&sA[0][0]), (int)blockIdx.x - A.nblk, T.nblk);
 }
 
-// Last layer's fragment tail, first half, as ONE launch: blocks [0, nblk_seg) = the atom -> fragment sum (the body of
+// Last layer's fragment tail, first half, as ONE launch: blocks [0, nblk_seg) = the atom -> fragment sum (block_rows_sum, the body of
 // k_segment_sum128_wide) followed by the fragment's node scalars <row, att[h, dst/src block]> from the finished row (a head's
 // 128/H columns are consecutive threads: shuffle reduction) -- two launches less than sum, node scalars, edge term; blocks
-// [nblk_seg, +nblk_rd) = the fragment graph's edge term <new_fbond[e], att[h, mid block]> (the body of k_row_dots_sorted),
-// which depends on neither.  Each of the three was a ~5 us latency-floor launch.
+// [nblk_seg, +nblk_rd) = the fragment graph's edge term <new_fbond[e], att[h, mid block]> (row_dots_sorted_body, the body of
+// k_row_dots_sorted), which depends on neither.  Each of the three was a ~5 us latency-floor launch.
 struct FragTailArgs {
     const float* src;  const int32_t* rowptr;  const int32_t* perm;  int32_t pos_base;  float* out;  int64_t n_seg;
     const float* att;  int att_w, dst_off, src_off;  float* s_dst;  float* s_src;  int nblk_seg;
@@ -191,56 +191,25 @@ struct FragTailArgs {
 template <int H>
 __global__ __launch_bounds__(kBlock) void k_frag_tail(FragTailArgs T) {
     __shared__ float sS[kRows][FN_D];
-    const int lane = threadIdx.x & 31, hw = threadIdx.x >> 5;
-    if ((int)blockIdx.x < T.nblk_seg) {
-        constexpr int d = FN_D / H;
-        static_assert(d <= 64, "a head's columns must lie inside one wave");
-        const int t = threadIdx.x, head = (t & 127) / d, c = (t & 127) % d;
-        const float a_d = T.att[head * T.att_w + T.dst_off + c], a_s = T.att[head * T.att_w + T.src_off + c];
-        for (int64_t s = blockIdx.x; s < T.n_seg; s += T.nblk_seg) {
-            const int beg = T.rowptr[s] - T.pos_base, deg = T.rowptr[s + 1] - T.rowptr[s];
-            float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
-            for (int i = hw; i < deg; i += kRows) {
-                const float4 v = ld4(T.src + (size_t)T.perm[beg + i] * FN_D + lane * 4);
-                acc.x += v.x; acc.y += v.y; acc.z += v.z; acc.w += v.w;
-            }
-            st4(&sS[hw][lane * 4], acc);
-            __syncthreads();
-            if (t < FN_D) {                                  // waves 0 and 1, whole
-                float v = 0.f;
-#pragma unroll
-                for (int w = 0; w < kRows; ++w) v += sS[w][t];
-                T.out[s * FN_D + t] = v;
-                float pd = v * a_d, ps = v * a_s;
-#pragma unroll
-                for (int off = d / 2; off > 0; off >>= 1) { pd += __shfl_xor(pd, off);  ps += __shfl_xor(ps, off); }
-                if (c == 0) { T.s_dst[s * H + head] = pd;  T.s_src[s * H + head] = ps; }
-            }
-            __syncthreads();
-        }
+    if ((int)blockIdx.x >= T.nblk_seg) {
+        row_dots_sorted_body<H>(T.feat, T.A, T.lda, T.off, H, T.pl, T.s_sorted, (int)blockIdx.x - T.nblk_seg, T.nblk_rd);
         return;
     }
-    const int vb = (int)blockIdx.x - T.nblk_seg, nb = T.nblk_rd;
-    const fn_gat_plan& pl = T.pl;
-    float4 a[H];
+    constexpr int d = FN_D / H;
+    static_assert(d <= 64, "a head's columns must lie inside one wave");
+    const int t = threadIdx.x, head = (t & 127) / d, c = (t & 127) % d;
+    const float a_d = T.att[head * T.att_w + T.dst_off + c], a_s = T.att[head * T.att_w + T.src_off + c];
+    for (int64_t s = blockIdx.x; s < T.n_seg; s += T.nblk_seg) {
+        float v = 0.f;                                       // the column sum, taken out: the node scalars need waves 0 and 1 whole
+        block_rows_sum(sS, T.src, FN_D, T.perm, T.rowptr[s] - T.pos_base, T.rowptr[s + 1] - T.rowptr[s], KeepAllRows{}, [&](float x) { v = x; });
+        if (t < FN_D) {
+            T.out[s * FN_D + t] = v;
+            float pd = v * a_d, ps = v * a_s;
 #pragma unroll
-    for (int q = 0; q < H; ++q) a[q] = ld4(T.A + q * T.lda + T.off + lane * 4);
-    const int64_t groups = (pl.m + kRows - 1) / kRows, per = (groups + nb - 1) / nb;
-    const int64_t g0 = (int64_t)xcd_block(vb, nb) * per, g1 = g0 + per < groups ? g0 + per : groups;
-    for (int64_t gi = g0; gi < g1; ++gi) {
-        const int64_t pos = gi * kRows + hw;
-        if (pos >= pl.m) continue;
-        const int eid = pl.eid_d[pos];
-        float mine = 0.f;
-        if (eid < pl.m_real) {                               // uniform inside the half-wave
-            const float4 v = ld4(T.feat + (size_t)eid * FN_D + lane * 4);
-#pragma unroll
-            for (int q = 0; q < H; ++q) {
-                const float dd = head_sum<32>(dot4(v, a[q]));
-                if (lane == q) mine = dd;
-            }
+            for (int off = d / 2; off > 0; off >>= 1) { pd += __shfl_xor(pd, off);  ps += __shfl_xor(ps, off); }
+            if (c == 0) { T.s_dst[s * H + head] = pd;  T.s_src[s * H + head] = ps; }
         }
-        if (lane < H) T.s_sorted[(size_t)lane * pl.m + pos] = mine;      // head-major [H][m]
+        __syncthreads();
     }
 }
 

@@ -54,33 +54,11 @@ using fni::GatFwdArgs;
 // =====================================================================================
 // Full-width edge term (atom graph / fragment graph), produced directly in destination-sorted order
 // =====================================================================================
-// s_sorted[pos, j] = <feat[eid(pos), :], A[j, off:off+128]>, 0 at loop positions (eid >= m_real)
+// s_sorted[pos, j] = <feat[eid(pos), :], A[j, off:off+128]>, 0 at loop positions (eid >= m_real): row_dots_sorted_body (shared_bodies.inc)
 __global__ __launch_bounds__(kBlock) void k_row_dots_sorted(const float* __restrict__ feat, const float* __restrict__ A,
                                                             int lda, int off, int J, fn_gat_plan pl,
                                                             float* __restrict__ s_sorted) {
-    const int lane = threadIdx.x & 31;
-    float4 a[8];
-#pragma unroll
-    for (int q = 0; q < 8; ++q) a[q] = (q < J) ? ld4(A + q * lda + off + lane * 4) : make_float4(0.f, 0.f, 0.f, 0.f);
-    int64_t g0, g1;
-    block_groups(pl.m, kRows, g0, g1);
-    for (int64_t gi = g0; gi < g1; ++gi) {
-        const int64_t pos = gi * kRows + (threadIdx.x >> 5);
-        if (pos >= pl.m) continue;
-        const int eid = pl.eid_d[pos];
-        float mine = 0.f;
-        if (eid < pl.m_real) {                       // uniform inside the half-wave
-            const float4 v = ld4(feat + (size_t)eid * FN_D + lane * 4);
-#pragma unroll
-            for (int q = 0; q < 8; ++q) {
-                if (q < J) {
-                    const float d = head_sum<32>(dot4(v, a[q]));
-                    if (lane == q) mine = d;
-                }
-            }
-        }
-        if (lane < J) s_sorted[(size_t)lane * pl.m + pos] = mine;        // head-major [J][m]
-    }
+    row_dots_sorted_body<8>(feat, A, lda, off, J, pl, s_sorted, (int)blockIdx.x, (int)gridDim.x);
 }
 
 // one block per column of the column-major partials [cols][FN_MAX_PART]
@@ -123,93 +101,56 @@ __global__ __launch_bounds__(kBlock) void k_segment_sum128(const float* __restri
 }
 
 // long segments (pooling: ~26 atoms per molecule, few hundred segments): one block per segment, its 8 half-waves
-// take rows hw, hw+8, ... and the 8 partial rows are added in a fixed order
+// take rows hw, hw+8, ... and the 8 partial rows are added in a fixed order: block_rows_sum (shared_bodies.inc), which the kernels
+// down to k_pool_cat_groups run -- "the same order" between them is one text
 __global__ __launch_bounds__(kBlock) void k_segment_sum128_wide(const float* __restrict__ src, int64_t src_ld,
                                                                 const int32_t* __restrict__ rowptr,
                                                                 const int32_t* __restrict__ perm, int32_t pos_base,
                                                                 float* __restrict__ out, int64_t n_seg) {
     __shared__ float sS[kRows][FN_D];
-    const int lane = threadIdx.x & 31, hw = threadIdx.x >> 5;
     for (int64_t s = blockIdx.x; s < n_seg; s += gridDim.x) {
-        const int beg = rowptr[s] - pos_base, deg = rowptr[s + 1] - rowptr[s];
-        float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
-        for (int i = hw; i < deg; i += kRows) {
-            const float4 v = ld4(src + (size_t)perm[beg + i] * src_ld + lane * 4);
-            acc.x += v.x; acc.y += v.y; acc.z += v.z; acc.w += v.w;
-        }
-        st4(&sS[hw][lane * 4], acc);
-        __syncthreads();
-        if (threadIdx.x < FN_D) {
-            float v = 0.f;
-#pragma unroll
-            for (int w = 0; w < kRows; ++w) v += sS[w][threadIdx.x];
-            out[s * FN_D + threadIdx.x] = v;
-        }
+        block_rows_sum(sS, src, src_ld, perm, rowptr[s] - pos_base, rowptr[s + 1] - rowptr[s], KeepAllRows{},
+                       [=](float v) { out[s * FN_D + threadIdx.x] = v; });
         __syncthreads();
     }
 }
 
 // pooled = cat(sum of a molecule's atom rows, sum of its fragment rows): [B, 256] in one launch (gat2.py:820-823).
 // grid (B, 2): y = 0 atoms -> columns 0..127, y = 1 fragments -> columns 128..255; one block per molecule and half.
+// This kernel and its leave-group-out form: choose the segment plan and the table by blockIdx.y, build the predicate, run the body, store.
 __global__ __launch_bounds__(kBlock) void k_pool_cat(const float* __restrict__ x_atoms, const float* __restrict__ x_frags,
                                                      fn_seg_plan sa, fn_seg_plan sf, float* __restrict__ out) {
     __shared__ float sS[kRows][FN_D];
+    const int64_t r = blockIdx.x, s = r;
     const fn_seg_plan& sp = blockIdx.y ? sf : sa;
-    const float* src = blockIdx.y ? x_frags : x_atoms;
-    const int lane = threadIdx.x & 31, hw = threadIdx.x >> 5;
-    const int64_t s = blockIdx.x;
-    const int beg = sp.rowptr[s] - sp.pos_base, deg = sp.rowptr[s + 1] - sp.rowptr[s];
-    float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
-    for (int i = hw; i < deg; i += kRows) {
-        const float4 v = ld4(src + (size_t)sp.perm[beg + i] * FN_D + lane * 4);
-        acc.x += v.x; acc.y += v.y; acc.z += v.z; acc.w += v.w;
-    }
-    st4(&sS[hw][lane * 4], acc);
-    __syncthreads();
-    if (threadIdx.x < FN_D) {
-        float v = 0.f;
-#pragma unroll
-        for (int w = 0; w < kRows; ++w) v += sS[w][threadIdx.x];
-        out[s * 2 * FN_D + blockIdx.y * FN_D + threadIdx.x] = v;
-    }
+    block_rows_sum(sS, blockIdx.y ? x_frags : x_atoms, FN_D, sp.perm, sp.rowptr[s] - sp.pos_base, sp.rowptr[s + 1] - sp.rowptr[s], KeepAllRows{},
+                   [=](float v) { out[(size_t)r * 2 * FN_D + blockIdx.y * FN_D + threadIdx.x] = v; });
 }
 // leave-group-out form of k_pool_cat (fragment contributions, fragnet/vizualize/model_attr.py:186-205: the rows of one fragment are set
 // to 0.0 in the encoder's final x_atoms, x_frags stays): output row r is molecule row_mol[r] pooled without the atoms whose group is
-// row_group[r].  Same partition (half-wave hw takes rows hw, hw + 8, ...) and same order of additions as k_pool_cat; an atom that is
-// left out enters the sum as 0.0, so a row equals k_pool_cat's of the same table with those rows overwritten by 0.0, bit for bit, and
-// a row that leaves nothing out equals k_pool_cat's row of its molecule.  grid (R, 2) like k_pool_cat's (B, 2).
+// row_group[r].  The same body as k_pool_cat with another predicate; an atom that is left out enters the sum as 0.0, so a row equals
+// k_pool_cat's of the same table with those rows overwritten by 0.0, bit for bit, and a row that leaves nothing out equals k_pool_cat's
+// row of its molecule.  grid (R, 2) like k_pool_cat's (B, 2).
 __global__ __launch_bounds__(kBlock) void k_pool_cat_groups(const float* __restrict__ x_atoms, const float* __restrict__ x_frags,
                                                             fn_seg_plan sa, fn_seg_plan sf, const int64_t* __restrict__ atom_group,
                                                             const int32_t* __restrict__ row_mol, const int64_t* __restrict__ row_group,
                                                             float* __restrict__ out) {
     __shared__ float sS[kRows][FN_D];
-    const fn_seg_plan& sp = blockIdx.y ? sf : sa;
-    const float* src = blockIdx.y ? x_frags : x_atoms;
-    const int lane = threadIdx.x & 31, hw = threadIdx.x >> 5;
-    const int64_t r = blockIdx.x;
-    const int64_t s = row_mol[r];
+    const int64_t r = blockIdx.x, s = row_mol[r];
     const int64_t leave = blockIdx.y ? -1 : row_group[r];      // < 0: nothing is left out (ungrouped atoms carry ids < 0 too)
-    const int beg = sp.rowptr[s] - sp.pos_base, deg = sp.rowptr[s + 1] - sp.rowptr[s];
-    float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
-    for (int i = hw; i < deg; i += kRows) {
-        const int32_t row = sp.perm[beg + i];
-        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (leave < 0 || atom_group[row] != leave) v = ld4(src + (size_t)row * FN_D + lane * 4);
-        acc.x += v.x; acc.y += v.y; acc.z += v.z; acc.w += v.w;
-    }
-    st4(&sS[hw][lane * 4], acc);
-    __syncthreads();
-    if (threadIdx.x < FN_D) {
-        float v = 0.f;
-#pragma unroll
-        for (int w = 0; w < kRows; ++w) v += sS[w][threadIdx.x];
-        out[(size_t)r * 2 * FN_D + blockIdx.y * FN_D + threadIdx.x] = v;
-    }
+    const int64_t* grp = leave < 0 ? nullptr : atom_group;     // null: nothing is left out, and atom_group is not read for a fragment row
+    const auto keep = [=](int32_t row) { return !grp || grp[row] != leave; };
+    const fn_seg_plan& sp = blockIdx.y ? sf : sa;
+    block_rows_sum(sS, blockIdx.y ? x_frags : x_atoms, FN_D, sp.perm, sp.rowptr[s] - sp.pos_base, sp.rowptr[s + 1] - sp.rowptr[s], keep,
+                   [=](float v) { out[(size_t)r * 2 * FN_D + blockIdx.y * FN_D + threadIdx.x] = v; });
 }
 // coalition form of k_pool_cat (fragment Shapley values): output row r is molecule row_mol[r] pooled over the atoms that are in no group
-// (atom_bit < 0) or whose bit atom_bit[i] of row_mask[r] is set; the fragments' half is never masked.  Partition, order of additions and
-// the treatment of a left-out atom (0.0, load skipped) are k_pool_cat_groups', so the same bit-for-bit statements hold.
+// (atom_bit < 0) or whose bit atom_bit[i] of row_mask[r] is set; the fragments' half is never masked.
 // The simple form: one workgroup per row and half, grid (R, 2) -- the yardstick of the tiled form below (FN_TUNE_COALITION_STAGED).
+// The body is written out here and reproduces block_rows_sum's partition and order with k_pool_cat_groups' treatment of a left-out atom
+// (0.0, load skipped), so the same bit-for-bit statements hold (tests/test_gpu_pool_sums.py holds it to them).  As a wrapper of
+// block_rows_sum this kernel waited for row_mask[r] in front of the item loop and its launches took 5 to 11 % longer
+// (profiles/pool_bodies_equivalence.txt section 5); here that load stays in flight under the first rows.
 __global__ __launch_bounds__(kBlock) void k_pool_cat_coalitions_rows(const float* __restrict__ x_atoms, const float* __restrict__ x_frags,
                                                                      fn_seg_plan sa, fn_seg_plan sf, const int8_t* __restrict__ atom_bit,
                                                                      const int32_t* __restrict__ row_mol, const uint64_t* __restrict__ row_mask,
@@ -240,9 +181,10 @@ __global__ __launch_bounds__(kBlock) void k_pool_cat_coalitions_rows(const float
     }
 }
 
-// One whole output row by ONE half-wave: the eight partial rows of k_pool_cat (partial w = items w, w + 8, ... in ascending order) live
-// in registers and are added as ((0 + p0) + p1) + ... + p7.  kStaged: item i is row i of `src` (LDS) and `bit` is indexed by i; else
-// item i is row perm[i] of `src` (global memory) and `bit` by that row.  bit == nullptr: nothing is masked.
+// One whole output row by ONE half-wave: the eight partial rows of block_rows_sum (partial w = items w, w + 8, ... in ascending order)
+// live in registers and are added as ((0 + p0) + p1) + ... + p7: another body, the order it reproduces is block_rows_sum's.
+// kStaged: item i is row i of `src` (LDS) and `bit` is indexed by i; else item i is row perm[i] of `src` (global memory) and `bit` by
+// that row.  bit == nullptr: nothing is masked.
 template <bool kStaged>
 __device__ __forceinline__ float4 coalition_row(const float* src, const int32_t* __restrict__ perm, const int8_t* bit, int deg,
                                                 uint64_t mask, int lane) {
@@ -1027,16 +969,30 @@ int fn_pool_cat_f32(const float* x_atoms, const float* x_frags, const fn_seg_pla
     return launch_status("fn_pool_cat_f32");
 }
 
+namespace {
+// what fn_pool_cat_groups_f32 and fn_pool_cat_coalitions_f32 check alike; atom_vec / row_vec: the per-atom and the per-row vector of
+// the read-out.  0 with R == 0: nothing to launch
+static int readout_args(const char* fn, const float* x_atoms, const float* x_frags, const fn_seg_plan* mol_atoms, const fn_seg_plan* mol_frags,
+                        const void* atom_vec, const int32_t* row_mol, const void* row_vec, int64_t R, const float* out) {
+    const char* what = nullptr;
+    if (!mol_atoms || !mol_frags || mol_atoms->n_seg != mol_frags->n_seg || R < 0 || R > 0x7fffffffLL) what = "bad argument";
+    else if (R == 0) return 0;
+    else if (mol_atoms->n_seg == 0) what = "output rows of a batch without molecules";
+    else if (!out || !row_mol || !row_vec || (mol_atoms->n_items > 0 && (!x_atoms || !atom_vec || !mol_atoms->perm)) ||
+             (mol_frags->n_items > 0 && (!x_frags || !mol_frags->perm)) || !mol_atoms->rowptr || !mol_frags->rowptr)
+        what = "null buffer";
+    if (!what) return 0;
+    char text[128];
+    snprintf(text, sizeof(text), "%s: %s", fn, what);
+    return fail(FN_EINVAL, text);
+}
+}  // namespace
+
 int fn_pool_cat_groups_f32(const float* x_atoms, const float* x_frags, const fn_seg_plan* mol_atoms, const fn_seg_plan* mol_frags,
                            const int64_t* atom_group, const int32_t* row_mol, const int64_t* row_group, int64_t R, float* out,
                            fn_stream_t stream) {
-    if (!mol_atoms || !mol_frags || mol_atoms->n_seg != mol_frags->n_seg || R < 0 || R > 0x7fffffffLL)
-        return fail(FN_EINVAL, "fn_pool_cat_groups_f32: bad argument");
-    if (R == 0) return 0;
-    if (mol_atoms->n_seg == 0) return fail(FN_EINVAL, "fn_pool_cat_groups_f32: output rows of a batch without molecules");
-    if (!out || !row_mol || !row_group || (mol_atoms->n_items > 0 && (!x_atoms || !atom_group || !mol_atoms->perm)) ||
-        (mol_frags->n_items > 0 && (!x_frags || !mol_frags->perm)) || !mol_atoms->rowptr || !mol_frags->rowptr)
-        return fail(FN_EINVAL, "fn_pool_cat_groups_f32: null buffer");
+    const int rc = readout_args("fn_pool_cat_groups_f32", x_atoms, x_frags, mol_atoms, mol_frags, atom_group, row_mol, row_group, R, out);
+    if (rc || R == 0) return rc;
     hipLaunchKernelGGL(k_pool_cat_groups, dim3((unsigned)R, 2), dim3(kBlock), 0, S(stream), x_atoms, x_frags, *mol_atoms, *mol_frags,
                        atom_group, row_mol, row_group, out);
     return launch_status("fn_pool_cat_groups_f32");
@@ -1045,13 +1001,8 @@ int fn_pool_cat_groups_f32(const float* x_atoms, const float* x_frags, const fn_
 int fn_pool_cat_coalitions_f32(const float* x_atoms, const float* x_frags, const fn_seg_plan* mol_atoms, const fn_seg_plan* mol_frags,
                                const int8_t* atom_bit, const int32_t* row_mol, const uint64_t* row_mask, int64_t R, float* out,
                                fn_stream_t stream) {
-    if (!mol_atoms || !mol_frags || mol_atoms->n_seg != mol_frags->n_seg || R < 0 || R > 0x7fffffffLL)
-        return fail(FN_EINVAL, "fn_pool_cat_coalitions_f32: bad argument");
-    if (R == 0) return 0;
-    if (mol_atoms->n_seg == 0) return fail(FN_EINVAL, "fn_pool_cat_coalitions_f32: output rows of a batch without molecules");
-    if (!out || !row_mol || !row_mask || (mol_atoms->n_items > 0 && (!x_atoms || !atom_bit || !mol_atoms->perm)) ||
-        (mol_frags->n_items > 0 && (!x_frags || !mol_frags->perm)) || !mol_atoms->rowptr || !mol_frags->rowptr)
-        return fail(FN_EINVAL, "fn_pool_cat_coalitions_f32: null buffer");
+    const int rc = readout_args("fn_pool_cat_coalitions_f32", x_atoms, x_frags, mol_atoms, mol_frags, atom_bit, row_mol, row_mask, R, out);
+    if (rc || R == 0) return rc;
     const int form = fni::tune(FN_TUNE_COALITION_STAGED);
     // the tiled form measured faster from 64 rows per molecule on (1.03 - 1.06 x there, 1.4 x at 1024); below it, one workgroup per row is
     if (form == 0 || (form == 1 && R < (int64_t)kCoAutoRows * mol_atoms->n_seg))

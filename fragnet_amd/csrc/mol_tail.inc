@@ -49,7 +49,7 @@ struct TailFwdLds {
     int src[kTailME];                  // source fragment (local) at each position
 };
 
-// readout of the atoms' half: rows i = hw, hw + 8, ... of the molecule (k_pool_cat's order), four loads in flight
+// readout of the atoms' half: rows i = hw, hw + 8, ... of the molecule (block_rows_sum's order), four loads in flight
 __device__ __forceinline__ float4 tail_rows_sum(const float* __restrict__ rows, int r0, int cnt, int hw, int lane) {
     float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
     for (int i0 = hw; i0 < cnt; i0 += 4 * kRows) {
@@ -181,7 +181,7 @@ __device__ __forceinline__ void tail_fwd_lds(const TailFwdArgs& T, const MolExt&
         accF.x += r.x;  accF.y += r.y;  accF.z += r.z;  accF.w += r.w;
     }
     if (!T.pooled) return;
-    // ---- readout: the eight half-waves' partial rows added in order (k_pool_cat)
+    // ---- readout: the eight half-waves' partial rows added in block_rows_sum's order
     st4(&L.S[hw][lane * 4], accA);
     st4(&L.S[hw][FN_D + lane * 4], accF);
     __syncthreads();
@@ -250,7 +250,7 @@ __device__ __forceinline__ void tail_fwd_global(const TailFwdArgs& T, const MolE
     if (!T.pooled) return;
     __syncthreads();
 
-    // ---- phase 3: readout, cat(sum of the molecule's y_atoms rows, sum of its y_frags rows) -- k_pool_cat's order
+    // ---- phase 3: readout, cat(sum of the molecule's y_atoms rows, sum of its y_frags rows) -- block_rows_sum's order
     st4(&sS[hw][lane * 4], tail_rows_sum(T.y_atoms, x.a0, x.na, hw, lane));
     st4(&sS[hw][FN_D + lane * 4], tail_rows_sum(T.G.ep.y, x.f0, x.nf, hw, lane));
     __syncthreads();

@@ -2,6 +2,69 @@
 // (encoder.hip) both run, each defined once: the dropout + ReLU epilogue (k_dropout_act | k_enc_prologue) and the Adam update with its
 // rider (k_adam | k_reduce_tasks, k_tail_bwd).  Included inside the anonymous namespace of both units.  No __global__ function may live
 // here: one that is no template would be compiled into both.
+// Likewise the pooling row sum (k_segment_sum128_wide, k_pool_cat, k_pool_cat_groups | k_frag_tail) and the destination-sorted edge
+// term (k_row_dots_sorted | k_frag_tail): the order of additions that the read-outs' bit-for-bit statements rest on is written here, once.
+
+// The block row sum.  A 256-thread block adds the `deg` rows src[perm[beg + i] * ld + 0..127]: half-wave hw takes the items hw, hw + 8, ..
+// in ascending order into one float4 per lane, from +0.0; the eight partial rows go to sS; after ONE barrier thread c < FN_D adds column
+// c of them as ((0 + p0) + p1) + .. + p7 and hands the sum to fin(v); the other threads do not call fin.  A row with keep(row) == false
+// enters as 0.0 and is not loaded.  A caller that loops over segments puts a barrier of its own behind the call, before sS is written
+// again.  tests/pool_sum_ref.py restates this order in numpy.
+template <class Keep, class Fin>
+__device__ __forceinline__ void block_rows_sum(float (*sS)[FN_D], const float* __restrict__ src, int64_t ld,
+                                                const int32_t* __restrict__ perm, int beg, int deg, Keep keep, Fin fin) {
+    const int lane = threadIdx.x & 31, hw = threadIdx.x >> 5;
+    float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+    for (int i = hw; i < deg; i += kRows) {
+        const int32_t row = perm[beg + i];
+        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (keep(row)) v = ld4(src + (size_t)row * ld + lane * 4);
+        acc.x += v.x; acc.y += v.y; acc.z += v.z; acc.w += v.w;
+    }
+    st4(&sS[hw][lane * 4], acc);
+    __syncthreads();
+    if (threadIdx.x < FN_D) {
+        float v = 0.f;
+#pragma unroll
+        for (int w = 0; w < kRows; ++w) v += sS[w][threadIdx.x];
+        fin(v);
+    }
+}
+struct KeepAllRows {          // the predicate of a plain sum
+    __device__ __forceinline__ bool operator()(int32_t) const { return true; }
+};
+
+// The destination-sorted full-width edge term: s_sorted[q, pos] = <feat[eid(pos), :], A[q, off:off+128]> for q < J, 0 at loop positions
+// (eid >= m_real); head-major [J][m].  One half-wave per position, dot4 per lane and the head_sum<32> butterfly; (vb, nb): this block's
+// index / the number of blocks working on the level -- block_groups() for a virtual block.  NQ: the register rows, J <= NQ; where the
+// caller's J is the constant NQ the q < J guards fold away.
+template <int NQ>
+__device__ __forceinline__ void row_dots_sorted_body(const float* __restrict__ feat, const float* __restrict__ A, int lda, int off, int J,
+                                                     const fn_gat_plan& pl, float* __restrict__ s_sorted, int vb, int nb) {
+    const int lane = threadIdx.x & 31;
+    float4 a[NQ];
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) a[q] = (q < J) ? ld4(A + q * lda + off + lane * 4) : make_float4(0.f, 0.f, 0.f, 0.f);
+    const int64_t groups = (pl.m + kRows - 1) / kRows, per = (groups + nb - 1) / nb;
+    const int64_t g0 = (int64_t)xcd_block(vb, nb) * per, g1 = g0 + per < groups ? g0 + per : groups;
+    for (int64_t gi = g0; gi < g1; ++gi) {
+        const int64_t pos = gi * kRows + (threadIdx.x >> 5);
+        if (pos >= pl.m) continue;
+        const int eid = pl.eid_d[pos];
+        float mine = 0.f;
+        if (eid < pl.m_real) {                       // uniform inside the half-wave
+            const float4 v = ld4(feat + (size_t)eid * FN_D + lane * 4);
+#pragma unroll
+            for (int q = 0; q < NQ; ++q) {
+                if (q < J) {
+                    const float d = head_sum<32>(dot4(v, a[q]));
+                    if (lane == q) mine = d;
+                }
+            }
+        }
+        if (lane < J) s_sorted[(size_t)lane * pl.m + pos] = mine;        // head-major [J][m]
+    }
+}
 
 template <bool BWD>
 __device__ __forceinline__ void dropout_act_body(const float* __restrict__ a, const float* __restrict__ y_saved, float* __restrict__ o,

@@ -371,33 +371,42 @@ def pool_cat(x_atoms, x_frags, plan):
     return _PoolCat.apply(x_atoms, x_frags, plan)
 
 
+def _readout_args(fn, x_atoms, x_frags, plan, vectors, check):
+    """What ``pool_cat_groups`` and ``pool_cat_coalitions`` check alike.  ``vectors``: (tensor, name, dtype) of the per-atom vector
+    (one entry per atom), of ``row_mol`` (its length is R) and of the per-row vector (R entries), in that order.
+    Returns the feature tables, the two segment plans and the empty result [R, 256]."""
+    x_atoms, x_frags = _f32c(x_atoms, "x_atoms"), _f32c(x_frags, "x_frags")
+    dev = x_atoms.device
+    for t, name, _ in vectors:
+        if not torch.is_tensor(t) or not t.is_cuda:
+            raise _lib.FragnetHipError(f"{fn}: {name} must be a GPU tensor; there is no CPU fallback")
+    sa, sf = plan.segs["mol_atoms"], plan.segs["mol_frags"]
+    if x_atoms.shape != (sa.n_items, FN_D) or x_frags.shape != (sf.n_items, FN_D):
+        raise ValueError(f"{fn}: feature tables do not match the batch / frag_batch index")
+    row_mol = vectors[1][0]
+    R = int(row_mol.shape[0])
+    for (t, name, dtype), rows in zip(vectors, (sa.n_items, None, R)):
+        if t.dtype != dtype or t.dim() != 1 or not t.is_contiguous() or t.device != dev or (rows is not None and t.shape[0] != rows):
+            raise ValueError(f"{fn}: {name} must be a contiguous {dtype} vector" + (f" of {rows} entries" if rows is not None else "")
+                             + f" on {dev}")
+    if check and R and bool(((row_mol < 0) | (row_mol >= sa.n_seg)).any()):
+        raise IndexError(f"{fn}: row_mol must lie in [0, {sa.n_seg}) (got {int(row_mol.min())} .. {int(row_mol.max())})")
+    return x_atoms, x_frags, sa, sf, torch.empty((R, 2 * FN_D), dtype=torch.float32, device=dev)
+
+
 def pool_cat_groups(x_atoms, x_frags, plan, atom_group, row_mol, row_group, check: bool = True):
     """The leave-group-out read-out (fn_pool_cat_groups_f32): row r of the result [R, 256] is ``pool_cat``'s row of molecule
     ``row_mol[r]`` without the atoms i with ``atom_group[i] == row_group[r]`` (``row_group[r] < 0``: the unmasked row; an atom with
     ``atom_group < 0`` is in no group).  ``atom_group`` int64 [N], ``row_mol`` int32 [R], ``row_group`` int64 [R], on the batch's
     device.  An evaluation read-out: no autograd node.  ``row_mol`` is checked here, on the host (one synchronisation: the kernel has
     no status word); ``check=False``: the caller built ``row_mol`` on the host and has checked it there."""
-    x_atoms, x_frags = _f32c(x_atoms, "x_atoms"), _f32c(x_frags, "x_frags")
-    dev = x_atoms.device
-    sa, sf = plan.segs["mol_atoms"], plan.segs["mol_frags"]
-    if x_atoms.shape != (sa.n_items, FN_D) or x_frags.shape != (sf.n_items, FN_D):
-        raise ValueError("pool_cat_groups: feature tables do not match the batch / frag_batch index")
-    for t, name, dtype, rows in ((atom_group, "atom_group", torch.int64, sa.n_items), (row_mol, "row_mol", torch.int32, None),
-                                 (row_group, "row_group", torch.int64, row_mol.shape[0] if torch.is_tensor(row_mol) else None)):
-        if not torch.is_tensor(t) or not t.is_cuda:
-            raise _lib.FragnetHipError(f"pool_cat_groups: {name} must be a GPU tensor; there is no CPU fallback")
-        if t.dtype != dtype or t.dim() != 1 or not t.is_contiguous() or t.device != dev or (rows is not None and t.shape[0] != rows):
-            raise ValueError(f"pool_cat_groups: {name} must be a contiguous {dtype} vector" + (f" of {rows} entries" if rows is not None else "")
-                             + f" on {dev}")
-    R = int(row_mol.shape[0])
-    out = torch.empty((R, 2 * FN_D), dtype=torch.float32, device=dev)
-    if R == 0:
+    vectors = ((atom_group, "atom_group", torch.int64), (row_mol, "row_mol", torch.int32), (row_group, "row_group", torch.int64))
+    x_atoms, x_frags, sa, sf, out = _readout_args("pool_cat_groups", x_atoms, x_frags, plan, vectors, check)
+    if out.shape[0] == 0:
         return out
-    if check and bool(((row_mol < 0) | (row_mol >= sa.n_seg)).any()):
-        raise IndexError(f"pool_cat_groups: row_mol must lie in [0, {sa.n_seg}) (got {int(row_mol.min())} .. {int(row_mol.max())})")
     a, f = _seg_struct(sa), _seg_struct(sf)
     _lib.call("fn_pool_cat_groups_f32", x_atoms.data_ptr(), x_frags.data_ptr(), C.byref(a), C.byref(f), atom_group.data_ptr(),
-              row_mol.data_ptr(), row_group.data_ptr(), R, out.data_ptr(), _stream_ptr(dev))
+              row_mol.data_ptr(), row_group.data_ptr(), out.shape[0], out.data_ptr(), _stream_ptr(out.device))
     return out
 
 
@@ -409,33 +418,19 @@ def pool_cat_coalitions(x_atoms, x_frags, plan, atom_bit, row_mol, row_mask, che
     the batch's device.  An evaluation read-out: no autograd node.  ``check=True`` validates ``row_mol`` (range, order) and
     ``atom_bit`` (< 64) here, on the host (one synchronisation: the kernel has no status word); ``check=False``: the caller built
     them on the host and has checked them there."""
-    x_atoms, x_frags = _f32c(x_atoms, "x_atoms"), _f32c(x_frags, "x_frags")
-    dev = x_atoms.device
-    for t, name in ((atom_bit, "atom_bit"), (row_mol, "row_mol"), (row_mask, "row_mask")):
-        if not torch.is_tensor(t) or not t.is_cuda:
-            raise _lib.FragnetHipError(f"pool_cat_coalitions: {name} must be a GPU tensor; there is no CPU fallback")
-    sa, sf = plan.segs["mol_atoms"], plan.segs["mol_frags"]
-    if x_atoms.shape != (sa.n_items, FN_D) or x_frags.shape != (sf.n_items, FN_D):
-        raise ValueError("pool_cat_coalitions: feature tables do not match the batch / frag_batch index")
-    for t, name, dtype, rows in ((atom_bit, "atom_bit", torch.int8, sa.n_items), (row_mol, "row_mol", torch.int32, None),
-                                 (row_mask, "row_mask", torch.int64, row_mol.shape[0])):
-        if t.dtype != dtype or t.dim() != 1 or not t.is_contiguous() or t.device != dev or (rows is not None and t.shape[0] != rows):
-            raise ValueError(f"pool_cat_coalitions: {name} must be a contiguous {dtype} vector" + (f" of {rows} entries" if rows is not None else "")
-                             + f" on {dev}")
-    R = int(row_mol.shape[0])
-    out = torch.empty((R, 2 * FN_D), dtype=torch.float32, device=dev)
+    vectors = ((atom_bit, "atom_bit", torch.int8), (row_mol, "row_mol", torch.int32), (row_mask, "row_mask", torch.int64))
+    x_atoms, x_frags, sa, sf, out = _readout_args("pool_cat_coalitions", x_atoms, x_frags, plan, vectors, check)
+    R = out.shape[0]
     if R == 0:
         return out
     if check:
-        if bool(((row_mol < 0) | (row_mol >= sa.n_seg)).any()):
-            raise IndexError(f"pool_cat_coalitions: row_mol must lie in [0, {sa.n_seg}) (got {int(row_mol.min())} .. {int(row_mol.max())})")
         if R > 1 and bool((row_mol[1:] < row_mol[:-1]).any()):
             raise ValueError("pool_cat_coalitions: row_mol must be non-decreasing (a molecule's rows are one run)")
         if sa.n_items and int(atom_bit.max()) >= 64:
             raise IndexError(f"pool_cat_coalitions: atom_bit must be < 64 (got {int(atom_bit.max())})")
     a, f = _seg_struct(sa), _seg_struct(sf)
     _lib.call("fn_pool_cat_coalitions_f32", x_atoms.data_ptr(), x_frags.data_ptr(), C.byref(a), C.byref(f), atom_bit.data_ptr(),
-              row_mol.data_ptr(), row_mask.data_ptr(), R, out.data_ptr(), _stream_ptr(dev))
+              row_mol.data_ptr(), row_mask.data_ptr(), R, out.data_ptr(), _stream_ptr(out.device))
     return out
 
 
