@@ -11,6 +11,10 @@
 // Arithmetic as there: fp32 in, fp32 accumulate, v_mfma_f32_16x16x4_f32 for A and B, no float atomics, every sum over pairs or rows in a
 // fixed order (the one integer atomic is the forward's arrival counter).  A pair-list value is range-tested before it indexes anything:
 // a pair outside [0,U) x [0,C) gets out = 0, g = 0 and adds nothing to the loss or to a gradient.
+// Orders of additions: v = W1^T w2 and the last workgroup's sums (dW2, db2, the loss) are pair_bodies.inc's, shared with pair_head.hip; the
+// tile-row dot with w2 and the end of a dW1 column block are written here and, the same statements, in pair_head.hip (why:
+// pair_bodies.inc); this unit's own are the per-row sums of g over the pair orderings (pf_sigma), the forward's one loss partial and
+// the grid's dot, which reads global memory.
 #include <stdint.h>
 #include <stdio.h>
 
@@ -20,16 +24,8 @@ namespace {
 using fni::fail;
 using fni::launch_status;
 
-constexpr int kIn0 = 256, kHid = 128, kTileRows = 16, kSegRows = 64;
-
-__device__ __forceinline__ void pf_step(const float* xp, const float* wp0, const float* wp1, bool ok, f32x4& acc0, f32x4& acc1) {
-    const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
-    const float4 a = ok ? ld4(xp) : z, p = ok ? ld4(wp0) : z, q = ok ? ld4(wp1) : z;
-    DN_MFMA(acc0, a.x, p.x);  DN_MFMA(acc1, a.x, q.x);
-    DN_MFMA(acc0, a.y, p.y);  DN_MFMA(acc1, a.y, q.y);
-    DN_MFMA(acc0, a.z, p.z);  DN_MFMA(acc1, a.z, q.z);
-    DN_MFMA(acc0, a.w, p.w);  DN_MFMA(acc1, a.w, q.w);
-}
+#include "pair_bodies.inc"
+constexpr int kTileRows = 16, kSegRows = 64;
 
 // one 16 x 128 tile of X[N,K] Wh^T (Wh = the K columns of W1 at `wcol`, rows LD long) into sh and into P[N,128]: wave w the 32 columns
 // [32 w, +32), K in steps of 16 of which the last is masked where K is no multiple of 16
@@ -44,8 +40,8 @@ __device__ __forceinline__ void pf_tile(const float* __restrict__ X, const float
     const float* wp0 = W1 + (size_t)(j0 + n) * LD + wcol + 4 * gq;
     const float* wp1 = wp0 + (size_t)16 * LD;
 #pragma unroll 2
-    for (int k0 = 0; k0 < kfull; k0 += 16) pf_step(xp + k0, wp0 + k0, wp1 + k0, true, acc0, acc1);
-    if constexpr (kfull < K) pf_step(xp + kfull, wp0 + kfull, wp1 + kfull, kfull + 4 * gq < K, acc0, acc1);
+    for (int k0 = 0; k0 < kfull; k0 += 16) pair_step(xp + k0, wp0 + k0, wp1 + k0, true, acc0, acc1);
+    if constexpr (kfull < K) pair_step(xp + kfull, wp0 + kfull, wp1 + kfull, kfull + 4 * gq < K, acc0, acc1);
 #pragma unroll
     for (int u = 0; u < 2; ++u) {
         const int col = j0 + 16 * u + n;
@@ -81,7 +77,7 @@ __global__ __launch_bounds__(256) void k_pairf_fwd(const float* __restrict__ D, 
     __syncthreads();
     {
         const int r = t >> 4, sub = t & 15;
-        float s = 0.f;
+        float s = 0.f;                                               // the tile-row dot: the same statements, the same order as k_pair_fwd's
 #pragma unroll
         for (int c = 0; c < kHid / 16; ++c) s = fmaf(sh[r][sub + 16 * c], w2[sub + 16 * c], s);
         s += __shfl_xor(s, 8);  s += __shfl_xor(s, 4);  s += __shfl_xor(s, 2);  s += __shfl_xor(s, 1);
@@ -131,14 +127,6 @@ __global__ __launch_bounds__(256) void k_pairf_fwd(const float* __restrict__ D, 
     }
 }
 
-template <int LD> __device__ __forceinline__ float pf_v(const float* __restrict__ w2, const float* __restrict__ W1, int k) {
-    float v = 0.f;
-#pragma unroll 8
-    for (int c = 0; c < kHid; ++c) v = fmaf(w2[c], W1[(size_t)c * LD + k], v);
-    return v;
-}
-template <int K1> constexpr int kColBlocks = (kIn0 + K1 + 15) / 16;
-
 // sig[r] = the sum of g over the pairs of row base + r, r < 64: 4 lanes per row walk the row's segment of the ordering (ascending pair
 // index), added ((0 + 1) + (2 + 3)).  rowptr and perm are range-tested; a row without pairs gives exactly 0.  The caller barriers.
 __device__ __forceinline__ void pf_sigma(const float* __restrict__ g, const int32_t* __restrict__ rowptr, const int32_t* __restrict__ perm, int N,
@@ -178,7 +166,7 @@ __global__ __launch_bounds__(256) void k_pairf_bwd(const float* __restrict__ g, 
     if (b < rbU + rbC) {
         const bool first = b < rbU;
         const int base = (first ? b : b - rbU) * kSegRows, N = first ? U : C, Kx = first ? kIn0 : K1, k0 = first ? 0 : kIn0;
-        for (int k = t; k < Kx; k += 256) sm[k] = pf_v<kInT>(w2, W1, k0 + k);
+        for (int k = t; k < Kx; k += 256) sm[k] = pair_v<kInT>(w2, W1, k0 + k);
         pf_sigma(g, first ? rp_d : rp_s, first ? pm_d : pm_s, N, M, base, sig);
         __syncthreads();
         const int q4 = Kx / 4;
@@ -190,16 +178,13 @@ __global__ __launch_bounds__(256) void k_pairf_bwd(const float* __restrict__ g, 
             float4 o = make_float4(0.f, 0.f, 0.f, 0.f);
             if (s != 0.f) {
                 o = make_float4(s * sm[k], s * sm[k + 1], s * sm[k + 2], s * sm[k + 3]);
-                if (GATE && !first) {
-                    const float4 xv = ld4(Sx + (size_t)row * K1 + k);
-                    o = make_float4(xv.x > 0.f ? o.x : 0.f, xv.y > 0.f ? o.y : 0.f, xv.z > 0.f ? o.z : 0.f, xv.w > 0.f ? o.w : 0.f);
-                }
+                if (GATE && !first) o = relu_gate4(o, ld4(Sx + (size_t)row * K1 + k));
             }
             st4(go + (size_t)row * Kx + k, o);
         }
         return;
     }
-    if (b < rbU + rbC + kColBlocks<K1>) {
+    if (b < rbU + rbC + kPairColBlocks<K1>) {
         const int c4 = t & 3, rl = t >> 2;
         const int col = (b - rbU - rbC) * 16 + 4 * c4;               // of [D | S]; 256 = 16 blocks: a block's columns lie in one half
         const bool first = col < kIn0;
@@ -215,7 +200,7 @@ __global__ __launch_bounds__(256) void k_pairf_bwd(const float* __restrict__ g, 
             if (ok && base + rl < N) fma4(acc, sig[rl], ld4(x + (size_t)(base + rl) * ldx));
             __syncthreads();
         }
-        st4(sm + 4 * (rl * 4 + c4), acc);
+        st4(sm + 4 * (rl * 4 + c4), acc);                            // from here: the same statements, the same order as k_pair_bwd's
         __syncthreads();
         if (rl == 0) {
             float4 s = ld4(sm + 4 * c4);
@@ -248,28 +233,8 @@ __global__ __launch_bounds__(256) void k_pairf_bwd(const float* __restrict__ g, 
             for (int r = rl; r < kSegRows && base + r < C; r += 8) fma4(acc, sig[r], ld4(B + (size_t)(base + r) * kHid + 4 * c4));
             __syncthreads();
         }
-        st4(sm + 4 * (rl * 32 + c4), acc);
-        const int lane = t & 63, wv = t >> 6;
-        if (wv == 0) {                                                // G = db2
-            float s = 0.f;
-            for (int m = lane; m < M; m += 64) s += g[m];
-            for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off);
-            if (lane == 0) s1[0] = s;
-        }
-        if (wv == 3 && loss) {
-            float s = 0.f;
-            for (int i = lane; i < n_part; i += 64) s += loss_part[i];
-            for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off);
-            if (lane == 0) loss[0] = s;
-        }
-        __syncthreads();
-        if (t < kHid) {
-            float s = sm[t];
-            for (int q = 1; q < 8; ++q) s += sm[q * kHid + t];
-            dW2[t] = fmaf(s1[0], b1[t], s);
-            db1[t] = w2[t] * s1[0];
-        }
-        if (t == 0) db2[0] = s1[0];
+        pair_last_tail(acc, sm, s1, g, M, w2, loss_part, n_part, loss, db1, dW2, db2,
+                       [b1](float s, int j, float G) { return fmaf(G, b1[j], s); });      // G = db2
     }
 }
 
@@ -283,7 +248,7 @@ __global__ __launch_bounds__(256) void k_pairf_grid(const float* __restrict__ D,
     __shared__ __attribute__((aligned(16))) float sv[kInT];
     __shared__ float sa[kTileRows + 1];
     const int t = threadIdx.x, c = blockIdx.x * 256 + t, u0 = blockIdx.y * kTileRows;
-    for (int k = t; k < kInT; k += 256) sv[k] = pf_v<kInT>(w2, W1, k);
+    for (int k = t; k < kInT; k += 256) sv[k] = pair_v<kInT>(w2, W1, k);
     if (t == 0) {
         float c0 = 0.f;
         for (int j = 0; j < kHid; ++j) c0 = fmaf(b1[j], w2[j], c0);
@@ -310,17 +275,7 @@ __global__ __launch_bounds__(256) void k_pairf_grid(const float* __restrict__ D,
     for (int r = 0; r < kTileRows && u0 + r < U; ++r) out[(size_t)(u0 + r) * C + c] = sa[r] + bt;
 }
 
-// ---- host side
-int fail_at(int code, const char* who, const char* what) {
-    char msg[200];
-    snprintf(msg, sizeof(msg), "%s: %s", who, what);
-    return fail(code, msg);
-}
-template <int K1> int check_widths(int64_t Kd, int64_t K, int64_t H, int64_t Co) {
-    if (Kd == kIn0 && K == K1 && H == kHid && Co == 1) return 0;
-    return fail(FN_EUNSUPPORTED, K1 == 256 ? "fn_cdrp_pair_factored_*: the pair head is 256 + 256 -> 128 -> 1 (Kd = Kc = 256, H = 128, C = 1); other widths are not built"
-                                           : "fn_dta_pair_factored_*: the pair head is 256 + 300 -> 128 -> 1 (Kd = 256, Kx = 300, H = 128, C = 1); other widths are not built");
-}
+// ---- host side (fail_at, check_widths, zero_param_grads: pair_bodies.inc)
 int check_counts(const char* who, int64_t M, int64_t U, int64_t C) {
     if (M < 0 || M > FN_DENSE_MAX_ROWS || U < 0 || U > FN_DENSE_MAX_ROWS || C < 0 || C > FN_DENSE_MAX_ROWS)
         return fail_at(FN_EINVAL, who, "0 <= M, U, C <= FN_DENSE_MAX_ROWS");
@@ -332,7 +287,7 @@ template <int K1>
 int pairf_fwd(const char* who, const float* D, const float* Sx, const int64_t* pd, const int64_t* ps, const float* W1, const float* b1,
               const float* w2, const float* b2, const float* target, float* A, float* B, float* ws, float* out, float* g, float* loss_part,
               int64_t M, int64_t U, int64_t C, int64_t Kd, int64_t K, int64_t H, int64_t Co, fn_stream_t stream) {
-    FN_TRY(check_widths<K1>(Kd, K, H, Co));
+    FN_TRY(check_widths<K1>("pair_factored_*", Kd, K, H, Co));
     FN_TRY(check_counts(who, M, U, C));
     if (M == 0) return 0;
     if (U == 0 || C == 0) return fail_at(FN_EINVAL, who, "pairs (M > 0) need U >= 1 and C >= 1");
@@ -352,7 +307,7 @@ int pairf_bwd(const char* who, const float* g, const float* D, const float* Sx, 
               const float* b1, const float* w2, const int32_t* rp_d, const int32_t* pm_d, const int32_t* rp_s, const int32_t* pm_s,
               float* g_D, float* g_S, float* dW1, float* db1, float* dW2, float* db2, const float* loss_part, int64_t n_part, float* loss,
               int64_t M, int64_t U, int64_t C, int64_t Kd, int64_t K, int64_t H, int64_t Co, fn_stream_t stream) {
-    FN_TRY(check_widths<K1>(Kd, K, H, Co));
+    FN_TRY(check_widths<K1>("pair_factored_*", Kd, K, H, Co));
     FN_TRY(check_counts(who, M, U, C));
     if (n_part < 0 || n_part > INT32_MAX) return fail_at(FN_EINVAL, who, "n_part out of range");
     if (!W1 || !b1 || !w2 || !dW1 || !db1 || !dW2 || !db2 || (U > 0 && !g_D) || (C > 0 && !g_S) ||
@@ -364,15 +319,10 @@ int pairf_bwd(const char* who, const float* g, const float* D, const float* Sx, 
         snprintf(where, sizeof(where), "%s (no pairs)", who);
         if (U > 0) FN_TRY(zero_async(g_D, U * kIn0, stream, where));
         if (C > 0) FN_TRY(zero_async(g_S, C * K1, stream, where));
-        FN_TRY(zero_async(dW1, kHid * (kIn0 + K1), stream, where));
-        FN_TRY(zero_async(db1, kHid, stream, where));
-        FN_TRY(zero_async(dW2, kHid, stream, where));
-        FN_TRY(zero_async(db2, 1, stream, where));
-        if (loss) FN_TRY(zero_async(loss, 1, stream, where));
-        return 0;
+        return zero_param_grads<K1>(dW1, db1, dW2, db2, loss, stream, where);
     }
     const int rbU = (int)((U + kSegRows - 1) / kSegRows), rbC = (int)((C + kSegRows - 1) / kSegRows);
-    hipLaunchKernelGGL((k_pairf_bwd<K1, GATE>), dim3((unsigned)(rbU + rbC + kColBlocks<K1> + 1)), dim3(256), 0, S(stream), g, D, Sx, A, B, W1, b1,
+    hipLaunchKernelGGL((k_pairf_bwd<K1, GATE>), dim3((unsigned)(rbU + rbC + kPairColBlocks<K1> + 1)), dim3(256), 0, S(stream), g, D, Sx, A, B, W1, b1,
                        w2, rp_d, pm_d, rp_s, pm_s, g_D, g_S, dW1, db1, dW2, db2, loss_part, (int)n_part, loss, (int)M, (int)U, (int)C, rbU, rbC);
     return launch_status(who);
 }
@@ -380,7 +330,7 @@ int pairf_bwd(const char* who, const float* g, const float* D, const float* Sx, 
 template <int K1>
 int pairf_grid(const char* who, const float* D, const float* Sx, const float* W1, const float* b1, const float* w2, const float* b2, float* out,
                int64_t U, int64_t C, int64_t Kd, int64_t K, int64_t H, int64_t Co, fn_stream_t stream) {
-    FN_TRY(check_widths<K1>(Kd, K, H, Co));
+    FN_TRY(check_widths<K1>("pair_factored_*", Kd, K, H, Co));
     FN_TRY(check_counts(who, 0, U, C));
     if (U == 0 || C == 0) return 0;
     if (!D || !Sx || !W1 || !b1 || !w2 || !b2 || !out || misaligned(15, Sx) || misaligned(3, D, W1, out))

@@ -10,6 +10,9 @@
 // The width and the gate are the only things that differ; both are compile-time, and no other instance is built.
 // A translation unit of its own: nothing of the encoder, of the prediction heads, of cdrp.hip or of dta.hip reaches these kernels.
 // Arithmetic: fp32 in, fp32 accumulate, v_mfma_f32_16x16x4_f32 for the matrix products, no atomics, every sum over rows in a fixed order.
+// Orders of additions: v = W1^T w2 and the last workgroup's sums (dW2, db2, the loss) are pair_bodies.inc's, shared with pair_factored.hip;
+// the tile-row dot with w2 and the end of a dW1 column block are written here and, the same statements, in pair_factored.hip (why:
+// pair_bodies.inc); this unit's own are the forward's two-half accumulation and loss partial and the backward's sums over rows.
 #include <stdint.h>
 #include <stdio.h>
 
@@ -19,17 +22,8 @@ namespace {
 using fni::fail;
 using fni::launch_status;
 
-constexpr int kIn0 = 256, kHid = 128, kPairRows = 16, kPairBwdRows = 32;
-
-// one 16-k step of both accumulators; !ok: this lane's quarter of the step lies behind the row's end
-__device__ __forceinline__ void pair_step(const float* xp, const float* wp0, const float* wp1, bool ok, f32x4& acc0, f32x4& acc1) {
-    const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
-    const float4 a = ok ? ld4(xp) : z, p = ok ? ld4(wp0) : z, q = ok ? ld4(wp1) : z;
-    DN_MFMA(acc0, a.x, p.x);  DN_MFMA(acc1, a.x, q.x);
-    DN_MFMA(acc0, a.y, p.y);  DN_MFMA(acc1, a.y, q.y);
-    DN_MFMA(acc0, a.z, p.z);  DN_MFMA(acc1, a.z, q.z);
-    DN_MFMA(acc0, a.w, p.w);  DN_MFMA(acc1, a.w, q.w);
-}
+#include "pair_bodies.inc"
+constexpr int kPairRows = 16, kPairBwdRows = 32;
 
 // forward: h[M,128] = drug W1[:, :256]^T + x1 W1[:, 256:]^T + b1 (saved), out[M] = h w2 + b2 and, with a target, g[M] = d MSE / d out
 // and one loss partial per workgroup (already divided by M: their sum in order IS the loss).  A workgroup = 16 rows, wave w the 32
@@ -78,7 +72,7 @@ __global__ __launch_bounds__(256) void k_pair_fwd(const float* __restrict__ drug
     }
     __syncthreads();
     const int r = threadIdx.x >> 4, sub = threadIdx.x & 15;
-    float t = 0.f;
+    float t = 0.f;                                                   // the tile-row dot: the same statements, the same order as k_pairf_fwd's
 #pragma unroll
     for (int c = 0; c < kHid / 16; ++c) t = fmaf(sh[r][sub + 16 * c], w2[sub + 16 * c], t);
     t += __shfl_xor(t, 8);  t += __shfl_xor(t, 4);  t += __shfl_xor(t, 2);  t += __shfl_xor(t, 1);
@@ -102,15 +96,6 @@ __global__ __launch_bounds__(256) void k_pair_fwd(const float* __restrict__ drug
         loss_part[blockIdx.x] = s / (float)M;
     }
 }
-
-// v[k] of v = W1^T w2 (below): the sum over c, in order, of w2[c] W1[c, k]; W1's rows are LD long
-template <int LD> __device__ __forceinline__ float pair_v(const float* __restrict__ w2, const float* __restrict__ W1, int k) {
-    float v = 0.f;
-#pragma unroll 8
-    for (int c = 0; c < kHid; ++c) v = fmaf(w2[c], W1[(size_t)c * LD + k], v);
-    return v;
-}
-template <int K1> constexpr int kPairColBlocks = (kIn0 + K1 + 15) / 16;
 
 // backward, one launch.  There is nothing between the two Linears, so d loss / d h = g w2^T has rank one and every product with it folds:
 //   g_x[m, k]  = g[m] v[k],     v = W1^T w2  [256 + K1]   (GATE: the second half zeroed where x1 <= 0, the backward of the ReLU that
@@ -146,10 +131,7 @@ __global__ __launch_bounds__(256) void k_pair_bwd(const float* __restrict__ g, c
             float4 o = make_float4(gm * sm[k], gm * sm[k + 1], gm * sm[k + 2], gm * sm[k + 3]);
             if (k < kIn0) st4(g_drug + (size_t)m * kIn0 + k, o);
             else {
-                if constexpr (GATE) {
-                    const float4 xv = ld4(x1 + (size_t)m * K1 + (k - kIn0));
-                    o = make_float4(xv.x > 0.f ? o.x : 0.f, xv.y > 0.f ? o.y : 0.f, xv.z > 0.f ? o.z : 0.f, xv.w > 0.f ? o.w : 0.f);
-                }
+                if constexpr (GATE) o = relu_gate4(o, ld4(x1 + (size_t)m * K1 + (k - kIn0)));
                 st4(g_x1 + (size_t)m * K1 + (k - kIn0), o);
             }
         }
@@ -164,7 +146,7 @@ __global__ __launch_bounds__(256) void k_pair_bwd(const float* __restrict__ g, c
         float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
         if (ok)
             for (int m = rl; m < M; m += 64) fma4(acc, g[m], ld4(x + (size_t)m * ldx));
-        st4(sm + 4 * (rl * 4 + c4), acc);
+        st4(sm + 4 * (rl * 4 + c4), acc);                            // from here: the same statements, the same order as k_pairf_bwd's
         __syncthreads();
         if (rl == 0) {
             float4 s = ld4(sm + 4 * c4);
@@ -186,49 +168,18 @@ __global__ __launch_bounds__(256) void k_pair_bwd(const float* __restrict__ g, c
         const int c4 = t & 31, rl = t >> 5;
         float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
         for (int m = rl; m < M; m += 8) fma4(acc, g[m], ld4(h + (size_t)m * kHid + 4 * c4));
-        st4(sm + 4 * (rl * 32 + c4), acc);
-        const int lane = t & 63, wv = t >> 6;
-        if (wv == 0) {                                                // db2
-            float s = 0.f;
-            for (int m = lane; m < M; m += 64) s += g[m];
-            for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off);
-            if (lane == 0) s1[0] = s;
-        }
-        if (wv == 3 && loss) {                                        // the loss value: the forward left one partial per workgroup
-            float s = 0.f;
-            for (int i = lane; i < n_part; i += 64) s += loss_part[i];
-            for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off);
-            if (lane == 0) loss[0] = s;
-        }
-        __syncthreads();
-        if (t < kHid) {
-            float s = sm[t];
-            for (int q = 1; q < 8; ++q) s += sm[q * kHid + t];
-            dW2[t] = s;
-            db1[t] = w2[t] * s1[0];
-        }
-        if (t == 0) db2[0] = s1[0];
+        pair_last_tail(acc, sm, s1, g, M, w2, loss_part, n_part, loss, db1, dW2, db2, [](float s, int, float) { return s; });
     }
 }
 
-// ---- host side: the checks and the "no rows" zeroing once; `who` is the entry point's name in fn_last_error()
-int fail_at(int code, const char* who, const char* what) {
-    char msg[160];
-    snprintf(msg, sizeof(msg), "%s: %s", who, what);
-    return fail(code, msg);
-}
-template <int K1> int check_widths(int64_t Kd, int64_t K, int64_t H, int64_t C) {
-    if (Kd == kIn0 && K == K1 && H == kHid && C == 1) return 0;
-    return fail(FN_EUNSUPPORTED, K1 == 256 ? "fn_cdrp_pair_*_f32: the pair head is 256 + 256 -> 128 -> 1 (Kd = Kc = 256, H = 128, C = 1); other widths are not built"
-                                           : "fn_dta_pair_*_f32: the pair head is 256 + 300 -> 128 -> 1 (Kd = 256, Kx = 300, H = 128, C = 1); other widths are not built");
-}
+// ---- host side (fail_at, check_widths, zero_param_grads: pair_bodies.inc)
 int64_t pair_loss_ws(int64_t M) { return M > 0 ? (M + kPairRows - 1) / kPairRows : 0; }
 
 template <int K1>
 int pair_fwd(const char* who, const float* drug, const float* x1, const float* W1, const float* b1, const float* w2, const float* b2,
              const float* target, float* h, float* out, float* g, float* loss_part, int64_t M, int64_t Kd, int64_t K, int64_t H, int64_t C,
              fn_stream_t stream) {
-    FN_TRY(check_widths<K1>(Kd, K, H, C));
+    FN_TRY(check_widths<K1>("pair_*_f32", Kd, K, H, C));
     if (M < 0 || M > FN_DENSE_MAX_ROWS) return fail_at(FN_EINVAL, who, "0 <= M <= FN_DENSE_MAX_ROWS");
     if (M == 0) return 0;
     if (!drug || !x1 || !W1 || !b1 || !w2 || !b2 || !h || !out || (target && (!g || !loss_part)) || misaligned(15, drug, x1, W1))
@@ -242,7 +193,7 @@ template <int K1, bool GATE>
 int pair_bwd(const char* who, const float* g, const float* drug, const float* x1, const float* h, const float* W1, const float* w2,
              float* g_drug, float* g_x1, float* dW1, float* db1, float* dW2, float* db2, const float* loss_part, int64_t n_part, float* loss,
              int64_t M, int64_t Kd, int64_t K, int64_t H, int64_t C, fn_stream_t stream) {
-    FN_TRY(check_widths<K1>(Kd, K, H, C));
+    FN_TRY(check_widths<K1>("pair_*_f32", Kd, K, H, C));
     if (M < 0 || M > FN_DENSE_MAX_ROWS || n_part < 0 || n_part > INT32_MAX) return fail_at(FN_EINVAL, who, "0 <= M <= FN_DENSE_MAX_ROWS");
     if (!W1 || !w2 || !dW1 || !db1 || !dW2 || !db2 || (M > 0 && (!g || !drug || !x1 || !h || !g_drug || !g_x1)) ||
         (loss && n_part > 0 && !loss_part) || misaligned(15, drug, x1, h, g_drug, g_x1) || misaligned(15, dW1))
@@ -250,12 +201,7 @@ int pair_bwd(const char* who, const float* g, const float* drug, const float* x1
     if (M == 0) {                                         // no rows: the sums are empty
         char where[64];
         snprintf(where, sizeof(where), "%s (no rows)", who);
-        FN_TRY(zero_async(dW1, kHid * (kIn0 + K1), stream, where));
-        FN_TRY(zero_async(db1, kHid, stream, where));
-        FN_TRY(zero_async(dW2, kHid, stream, where));
-        FN_TRY(zero_async(db2, 1, stream, where));
-        if (loss) FN_TRY(zero_async(loss, 1, stream, where));
-        return 0;
+        return zero_param_grads<K1>(dW1, db1, dW2, db2, loss, stream, where);
     }
     const int row_blocks = (int)((M + kPairBwdRows - 1) / kPairBwdRows);
     hipLaunchKernelGGL((k_pair_bwd<K1, GATE>), dim3((unsigned)(row_blocks + kPairColBlocks<K1> + 1)), dim3(256), 0, S(stream), g, drug, x1, h, W1, w2,

@@ -4,6 +4,7 @@
 // here: one that is no template would be compiled into both.
 // Likewise the pooling row sum (k_segment_sum128_wide, k_pool_cat, k_pool_cat_groups | k_frag_tail) and the destination-sorted edge
 // term (k_row_dots_sorted | k_frag_tail): the order of additions that the read-outs' bit-for-bit statements rest on is written here, once.
+// The pair heads' shared orders (v = W1^T w2, the last workgroup's dW2 / db2 / loss sums) are pair_bodies.inc's, under the same rule.
 
 // The block row sum.  A 256-thread block adds the `deg` rows src[perm[beg + i] * ld + 0..127]: half-wave hw takes the items hw, hw + 8, ..
 // in ascending order into one float4 per lane, from +0.0; the eight partial rows go to sS; after ONE barrier thread c < FN_D adds column

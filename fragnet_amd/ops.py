@@ -830,6 +830,31 @@ def _dense_bwd(below, gz, h_in, W, gx, dW, db, M_out, tail, st):
               W.shape[1], W.shape[0], M_out, None if tail is None else C.byref(tail), st)
 
 
+def _plain_fwd(x, W, b, relu: bool, st):
+    """a plain dense layer on fn_dense_fwd_f32 (the towers, ``frag_mlp``): relu?(x W^T + b) in new rows, the ReLU as the epilogue at p = 0"""
+    y = torch.empty((x.shape[0], W.shape[0]), dtype=torch.float32, device=x.device)
+    act = _lib.ActEpilogue(y.data_ptr(), 0.0, 1, 0, 0, None) if relu else None
+    _lib.call("fn_dense_fwd_f32", x.data_ptr(), W.data_ptr(), b.data_ptr(), y.data_ptr(), x.shape[0], W.shape[1], W.shape[0],
+              None if act is None else C.byref(act), st)
+    return y
+
+
+def _plain_bwd(g, x, W, gx, relu_below: bool, dW, db, st):
+    """its backward on fn_dense_bwd_f32: dW, db (None: not kept) and the input gradient ``gx`` (None: not wanted), handed down through
+    the ReLU that produced ``x`` (``relu_below``: the gate scale of p = 0) or as it is"""
+    gate = _gate_scale(0.0) if relu_below else _NO_GATE.gate
+    _lib.call("fn_dense_bwd_f32", g.data_ptr(), x.data_ptr(), W.data_ptr(), _ptr(gx), gate, dW.data_ptr(), _ptr(db), x.shape[0], W.shape[1],
+              W.shape[0], x.shape[0], st)
+
+
+def _relu_chain(h, P, st):
+    """relu(Linear(.)) for the Linears P[2:] = weight, bias, .. on top of the first layer's output ``h``: every layer's output, ``h`` first"""
+    acts = [h]
+    for i in range(1, len(P) // 2):
+        acts.append(_plain_fwd(acts[-1], P[2 * i], P[2 * i + 1], True, st))
+    return acts
+
+
 def _small_fwd(h, W, b, out, st):
     """the last Linear (``_small_ok``); ``out`` may have more rows than ``h``: the kernel zeroes them"""
     _lib.call("fn_small_linear_f32", h.data_ptr(), _f32c(W, "W").data_ptr(), b.data_ptr(), out.data_ptr(), h.shape[0], W.shape[1], W.shape[0],
@@ -1296,20 +1321,13 @@ class _CellTower(torch.autograd.Function):
         params = tuple(_f32c(q, "tower parameter") for q in params)
         _gene_shapes(gene, params[0], params[1])
         M, K = gene.shape
-        dev, st = gene.device, _stream_ptr(gene.device)
-        h = torch.empty((M, params[0].shape[0]), dtype=torch.float32, device=dev)
+        st = _stream_ptr(gene.device)
+        h = torch.empty((M, params[0].shape[0]), dtype=torch.float32, device=gene.device)
         _lib.call("fn_cdrp_gene_fwd_f32", gene.data_ptr(), params[0].data_ptr(), params[1].data_ptr(), h.data_ptr(), M, K, h.shape[1], st)
-        acts = [h]
-        for i in range(1, len(params) // 2):
-            W, b = params[2 * i], params[2 * i + 1]
-            y = torch.empty((M, W.shape[0]), dtype=torch.float32, device=dev)
-            act = _lib.ActEpilogue(y.data_ptr(), 0.0, 1, 0, 0, None)
-            _lib.call("fn_dense_fwd_f32", h.data_ptr(), W.data_ptr(), b.data_ptr(), y.data_ptr(), M, W.shape[1], W.shape[0], C.byref(act), st)
-            h = y
-            acts.append(h)
+        acts = _relu_chain(h, params, st)
         ctx.params, ctx.slots = params, [grad_slot(q) for q in params]
         ctx.save_for_backward(gene, *acts)
-        return h
+        return acts[-1]
 
     @staticmethod
     def backward(ctx, g):
@@ -1332,8 +1350,7 @@ class _CellTower(torch.autograd.Function):
             W, x = P[2 * i], acts[i - 1]
             dW, db = grad_buffer(P[2 * i], slots[2 * i]), grad_buffer(P[2 * i + 1], slots[2 * i + 1])
             gx = torch.empty_like(x)
-            _lib.call("fn_dense_bwd_f32", g.data_ptr(), x.data_ptr(), W.data_ptr(), gx.data_ptr(), 1.0, dW.data_ptr(), db.data_ptr(), M, W.shape[1],
-                      W.shape[0], M, st)
+            _plain_bwd(g, x, W, gx, True, dW, db, st)
             grads[2 * i], grads[2 * i + 1] = dW, db
             g = gx
         dW, db = grad_buffer(P[0], slots[0]), grad_buffer(P[1], slots[1])
@@ -1371,15 +1388,7 @@ def _cell_path_forward(gene, P, alpha, base, st):
     h = torch.empty((M, P[0].shape[0]), dtype=torch.float32, device=gene.device)
     _lib.call("fn_cdrp_gene_fwd_path_f32", gene.data_ptr(), _ptr(base), alpha.data_ptr(), P[0].data_ptr(), P[1].data_ptr(), h.data_ptr(), C_, S, K,
               h.shape[1], st)
-    acts = [h]
-    for i in range(1, len(P) // 2):
-        W, b = P[2 * i], P[2 * i + 1]
-        y = torch.empty((M, W.shape[0]), dtype=torch.float32, device=gene.device)
-        act = _lib.ActEpilogue(y.data_ptr(), 0.0, 1, 0, 0, None)
-        _lib.call("fn_dense_fwd_f32", h.data_ptr(), W.data_ptr(), b.data_ptr(), y.data_ptr(), M, W.shape[1], W.shape[0], C.byref(act), st)
-        h = y
-        acts.append(h)
-    return acts
+    return _relu_chain(h, P, st)
 
 
 def _cell_path_args(gene_expr, linears, v, alpha, base, what):
@@ -1439,8 +1448,8 @@ def cell_path_attributions(gene_expr, linears, v, alpha, base=None, want_gradien
               1.0, _ptr(ws), st)
     for i in range(len(P) // 2 - 1, 0, -1):
         W, x = P[2 * i], acts[i - 1]
-        gx, dW = torch.empty_like(x), torch.empty_like(W)
-        _lib.call("fn_dense_bwd_f32", g.data_ptr(), x.data_ptr(), W.data_ptr(), gx.data_ptr(), 1.0, dW.data_ptr(), None, M, W.shape[1], W.shape[0], M, st)
+        gx = torch.empty_like(x)
+        _plain_bwd(g, x, W, gx, True, torch.empty_like(W), None, st)
         g = gx
     _lib.call("fn_cdrp_gene_dx_f32", g.data_ptr(), None, P[0].data_ptr(), gene.data_ptr(), _ptr(base), attr.data_ptr(), _ptr(grad), C_, S, K,
               P[0].shape[0], st)
@@ -1464,12 +1473,61 @@ _PAIR_CDRP = _PairInstance("fn_cdrp_pair", 256, True, "pair_head", "cell_enc")
 _PAIR_DTA = _PairInstance("fn_dta_pair", 300, False, "pair_head_dta", "xt")
 
 
+# What ``_PairHead`` and ``_PairHeadFactored`` share, the fused-loss contract among it.  With a target the forward's launch also leaves
+# g = d MSE / d out and the loss partials, and the node returns (out, loss): ``out`` then carries no gradient and the VALUE of ``loss`` is
+# complete once backward has run (its sum rides in the backward launch), as with ``_DenseHead``'s fused loss.  A node's own part is the
+# buffers its launches fill and read (``keep``: drug, second input, then what its forward saved) and their argument lists.
+def _pair_loss_buffers(target, rows: int, C_out: int, n_parts, dev, name: str, unit: str):
+    """forward: ``(target, g, parts, loss_t)`` of the fused loss over ``rows`` outputs (``n_parts``: how many partials, called with a
+    target only); four None without a target"""
+    if target is None:
+        return None, None, None, None
+    target = _f32c(target, "y").reshape(-1)
+    if target.numel() != rows * C_out:
+        raise ValueError(f"{name}: {target.numel()} targets for {rows} {unit}")
+    return (target, torch.empty(rows, dtype=torch.float32, device=dev), torch.empty(n_parts(), dtype=torch.float32, device=dev),
+            torch.empty((), dtype=torch.float32, device=dev))
+
+
+def _pair_forward_end(ctx, inst, params, keep, out, g, parts, loss_t):
+    """forward, behind the launch: what backward needs, and the node's result"""
+    ctx.inst, ctx.params, ctx.slots = inst, params, [grad_slot(q) for q in params]
+    ctx.n_keep, ctx.fused = len(keep), g is not None
+    if not ctx.fused:
+        ctx.save_for_backward(*keep)
+        return out
+    ctx.save_for_backward(*keep, g, parts, loss_t)
+    ctx.mark_non_differentiable(out)
+    ctx.set_materialize_grads(False)
+    return out, loss_t
+
+
+def _pair_backward_begin(ctx, g_out, g_loss):
+    """backward, in front of the launch: ``(keep, g, parts, loss_t, (dW1, db1, dW2, db2), g_drug, g_second)`` -- g is the forward's
+    (times a non-unit d / d loss) where the loss was fused, else the incoming gradient; the parameters' buffers are claimed here"""
+    keep, parts, loss_t = ctx.saved_tensors[:ctx.n_keep], None, None
+    if ctx.fused:
+        g, parts, loss_t = ctx.saved_tensors[ctx.n_keep:]
+        if g_loss is not None and not _is_unit_grad(g_loss):
+            g = g * g_loss
+    else:
+        g = _f32c(g_out, "g").reshape(-1)
+    grads = tuple(grad_buffer(q, s) for q, s in zip(ctx.params, ctx.slots))
+    return keep, g, parts, loss_t, grads, torch.empty_like(keep[0]), torch.empty_like(keep[1])
+
+
+def _pair_backward_end(ctx, x1, g_drug, g_x1, grads, n_between: int):
+    """backward, behind the launch: the gate tag and the gradients in the order of forward's arguments (instance, drug, second input,
+    ``n_between`` without gradient, target, parameters)"""
+    if ctx.inst.gated:
+        g_x1._fn_relu_gated = x1
+    return (None, g_drug if ctx.needs_input_grad[1] else None, g_x1 if ctx.needs_input_grad[2] else None, *(None,) * (n_between + 1), *grads)
+
+
 class _PairHead(torch.autograd.Function):
     """fc2(fc1(cat(drug_enc, second))) (model/cdrp/model.py:35-42, model/dta/model.py:141-144; nothing between the two Linears) for
     256 + ``inst.width`` -> 128 -> 1: one launch each way (<prefix>_fwd_f32 / <prefix>_bwd_f32), the two inputs read where they are.
-    With ``target`` the forward also leaves d MSE / d out and the loss partials, and the node returns (out, loss): ``out`` then carries
-    no gradient and the VALUE of ``loss`` is complete once backward has run (its sum rides in the backward launch), as with
-    ``_DenseHead``'s fused loss.  Where ``inst.gated`` (CDRP's ``cell_enc``) the gradient handed to the second input is already through the
+    With ``target`` the loss is fused (above).  Where ``inst.gated`` (CDRP's ``cell_enc``) the gradient handed to the second input is already through the
     backward of the ReLU that produced it (tagged ``_fn_relu_gated`` for ``_CellTower``; applying that gate again, as a plain autograd
     ReLU would, changes nothing); otherwise (DTA's ``xt``, a Linear's output) it is NOT gated."""
 
@@ -1481,50 +1539,46 @@ class _PairHead(torch.autograd.Function):
         Kd, K1, H, C_out = drug.shape[1], x1.shape[1], W1.shape[0], w2.shape[0]
         if x1.shape[0] != M or W1.shape[1] != Kd + K1 or w2.shape[1] != H or b1.shape != (H,) or b2.shape != (C_out,):
             raise ValueError(f"{inst.name}: drug_enc / {inst.second} / fc1 / fc2 shapes do not fit together")
-        st = _stream_ptr(dev)
         h = torch.empty((M, H), dtype=torch.float32, device=dev)
         out = torch.empty((M, C_out), dtype=torch.float32, device=dev)
-        g = parts = loss_t = None
-        if target is not None:
-            target = _f32c(target, "y").reshape(-1)
-            if target.numel() != M * C_out:
-                raise ValueError(f"{inst.name}: {target.numel()} targets for {M} rows")
-            g = torch.empty(M, dtype=torch.float32, device=dev)
-            parts = torch.empty(getattr(_lib.load(), inst.prefix + "_loss_ws")(M), dtype=torch.float32, device=dev)
-            loss_t = torch.empty((), dtype=torch.float32, device=dev)
+        target, g, parts, loss_t = _pair_loss_buffers(target, M, C_out, lambda: getattr(_lib.load(), inst.prefix + "_loss_ws")(M), dev,
+                                                      inst.name, "rows")
         _lib.call(inst.prefix + "_fwd_f32", drug.data_ptr(), x1.data_ptr(), W1.data_ptr(), b1.data_ptr(), w2.data_ptr(), b2.data_ptr(),
-                  _ptr(target), h.data_ptr(), out.data_ptr(), _ptr(g), _ptr(parts), M, Kd, K1, H, C_out, st)
-        ctx.inst, ctx.params, ctx.slots = inst, (W1, b1, w2, b2), [grad_slot(q) for q in (W1, b1, w2, b2)]
-        ctx.fused = target is not None
-        if ctx.fused:
-            ctx.save_for_backward(drug, x1, h, g, parts, loss_t)
-            ctx.mark_non_differentiable(out)
-            ctx.set_materialize_grads(False)
-            return out, loss_t
-        ctx.save_for_backward(drug, x1, h)
-        return out
+                  _ptr(target), h.data_ptr(), out.data_ptr(), _ptr(g), _ptr(parts), M, Kd, K1, H, C_out, _stream_ptr(dev))
+        return _pair_forward_end(ctx, inst, (W1, b1, w2, b2), (drug, x1, h), out, g, parts, loss_t)
 
     @staticmethod
     def backward(ctx, g_out, g_loss=None):
-        drug, x1, h = ctx.saved_tensors[:3]
-        M, dev = drug.shape[0], drug.device
-        parts = loss_t = None
-        if ctx.fused:
-            g, parts, loss_t = ctx.saved_tensors[3:]
-            if g_loss is not None and not _is_unit_grad(g_loss):
-                g = g * g_loss
-        else:
-            g = _f32c(g_out, "g").reshape(-1)
-        P, slots = ctx.params, ctx.slots
-        dW1, db1, dW2, db2 = (grad_buffer(q, s) for q, s in zip(P, slots))
-        g_drug, g_x1 = torch.empty_like(drug), torch.empty_like(x1)
+        (drug, x1, h), g, parts, loss_t, grads, g_drug, g_x1 = _pair_backward_begin(ctx, g_out, g_loss)
+        P = ctx.params
         _lib.call(ctx.inst.prefix + "_bwd_f32", g.data_ptr(), drug.data_ptr(), x1.data_ptr(), h.data_ptr(), P[0].data_ptr(), P[2].data_ptr(),
-                  g_drug.data_ptr(), g_x1.data_ptr(), dW1.data_ptr(), db1.data_ptr(), dW2.data_ptr(), db2.data_ptr(), _ptr(parts),
-                  0 if parts is None else parts.numel(), _ptr(loss_t), M, drug.shape[1], x1.shape[1], P[0].shape[0], P[2].shape[0],
-                  _stream_ptr(dev))
-        if ctx.inst.gated:
-            g_x1._fn_relu_gated = x1
-        return (None, g_drug if ctx.needs_input_grad[1] else None, g_x1 if ctx.needs_input_grad[2] else None, None, dW1, db1, dW2, db2)
+                  g_drug.data_ptr(), g_x1.data_ptr(), *(q.data_ptr() for q in grads), _ptr(parts), 0 if parts is None else parts.numel(),
+                  _ptr(loss_t), drug.shape[0], drug.shape[1], x1.shape[1], P[0].shape[0], P[2].shape[0], _stream_ptr(drug.device))
+        return _pair_backward_end(ctx, x1, g_drug, g_x1, grads, 0)
+
+
+def pair_fuses_loss(loss, rows: int, tensors) -> bool:
+    """Whether a pair head with ``loss = (kind, y, row_w)`` runs the loss in its forward launch and the loss's sum in its backward
+    launch: MSE without row weights, live rows, and a training step -- gradients enabled and one of ``tensors`` (the two inputs and the
+    four parameters) taking one."""
+    kind, _, row_w = loss
+    return bool(FUSED_HEAD_LOSS and kind == _lib.LOSS_MSE and row_w is None and torch.is_grad_enabled() and rows > 0
+                and any(t.requires_grad for t in tensors))
+
+
+def _pair_apply(node, args, rows: int, fc1, fc2, loss):
+    """``node`` on ``args`` = (instance, drug, second input, ..), the target and the parameters: the result in ``pair_head``'s three shapes"""
+    params = (fc1.weight, fc1.bias, fc2.weight, fc2.bias)
+    if loss is None:
+        return node.apply(*args, None, *params)
+    if not pair_fuses_loss(loss, rows, (args[1], args[2], *params)):
+        return node.apply(*args, None, *params), None
+    return node.apply(*args, loss[1], *params)
+
+
+def _pair_widths_ok(inst, drug_enc, x1, fc1, fc2) -> bool:
+    return (tuple(fc1.weight.shape), tuple(fc2.weight.shape)) == inst.shapes and fc1.bias is not None and fc2.bias is not None \
+        and drug_enc.dim() == 2 and x1.dim() == 2 and drug_enc.shape[1] == FN_D * 2 and x1.shape[1] == inst.width
 
 
 def _pair_head(inst, drug_enc, x1, fc1, fc2, loss):
@@ -1532,20 +1586,10 @@ def _pair_head(inst, drug_enc, x1, fc1, fc2, loss):
     gradient is gated says where the second input came from."""
     if not (drug_enc.is_cuda and x1.is_cuda):
         raise _lib.FragnetHipError(f"{inst.name}: fragnet_amd kernels need GPU tensors; there is no CPU fallback")
-    ok = (tuple(fc1.weight.shape), tuple(fc2.weight.shape)) == inst.shapes and fc1.bias is not None and fc2.bias is not None \
-        and drug_enc.shape[1:] == (FN_D * 2,) and x1.shape[1:] == (inst.width,) and drug_enc.shape[0] <= DENSE_MAX_ROWS
-    if not ok:
+    if not (_pair_widths_ok(inst, drug_enc, x1, fc1, fc2) and drug_enc.shape[0] <= DENSE_MAX_ROWS):
         out = fc2(fc1(torch.cat((drug_enc, x1), 1)))
         return (out, None) if loss is not None else out
-    params = (fc1.weight, fc1.bias, fc2.weight, fc2.bias)
-    if loss is None:
-        return _PairHead.apply(inst, drug_enc, x1, None, *params)
-    kind, y, row_w = loss
-    fuse = FUSED_HEAD_LOSS and kind == _lib.LOSS_MSE and row_w is None and torch.is_grad_enabled() and drug_enc.shape[0] > 0 \
-        and (drug_enc.requires_grad or x1.requires_grad or any(q.requires_grad for q in params))
-    if not fuse:
-        return _PairHead.apply(inst, drug_enc, x1, None, *params), None
-    return _PairHead.apply(inst, drug_enc, x1, y, *params)
+    return _pair_apply(_PairHead, (inst, drug_enc, x1), drug_enc.shape[0], fc1, fc2, loss)
 
 
 def pair_head(drug_enc, cell_enc, fc1, fc2, loss=None):
@@ -1577,17 +1621,15 @@ class _ProteinTower(torch.autograd.Function):
         M, L = tokens.shape
         V, D = E.shape
         F_, KS = Wc.shape[0], Wc.shape[2]
-        K, N = F_ * (D - KS + 1), Wf.shape[0]
+        K = F_ * (D - KS + 1)
         dev, st = tokens.device, _stream_ptr(tokens.device)
         A = torch.empty((M, V, F_ * KS), dtype=torch.float32, device=dev)
         conv = torch.empty((M, K), dtype=torch.float32, device=dev)
         _lib.call("fn_dta_conv_fwd_f32", tokens.data_ptr(), E.data_ptr(), Wc.data_ptr(), bc.data_ptr(), A.data_ptr(), conv.data_ptr(), M, L, D, V,
                   F_, KS, st)
-        xt = torch.empty((M, N), dtype=torch.float32, device=dev)
-        _lib.call("fn_dense_fwd_f32", conv.data_ptr(), Wf.data_ptr(), bf.data_ptr(), xt.data_ptr(), M, K, N, None, st)
         ctx.params, ctx.slots = (E, Wc, bc, Wf, bf), [grad_slot(q) for q in (E, Wc, bc, Wf, bf)]
         ctx.save_for_backward(tokens, A, conv)
-        return xt
+        return _plain_fwd(conv, Wf, bf, False, st)
 
     @staticmethod
     def backward(ctx, g):
@@ -1597,11 +1639,9 @@ class _ProteinTower(torch.autograd.Function):
         dE, dWc, dbc, dWf, dbf = (grad_buffer(q, s) for q, s in zip(ctx.params, slots))
         M, L = tokens.shape
         V, D = E.shape
-        K, N = conv.shape[1], Wf.shape[0]
         st = _stream_ptr(g.device)
         g_conv = torch.empty_like(conv)
-        _lib.call("fn_dense_bwd_f32", g.data_ptr(), conv.data_ptr(), Wf.data_ptr(), g_conv.data_ptr(), 0.0, dWf.data_ptr(), dbf.data_ptr(), M, K, N,
-                  M, st)
+        _plain_bwd(g, conv, Wf, g_conv, False, dWf, dbf, st)
         ws = _scratch(_lib.load().fn_dta_conv_bwd_ws(M, L, D, V), g.device)
         _lib.call("fn_dta_conv_bwd_f32", g_conv.data_ptr(), tokens.data_ptr(), E.data_ptr(), A.data_ptr(), dWc.data_ptr(), dbc.data_ptr(),
                   dE.data_ptr(), _ptr(ws), M, L, D, V, Wc.shape[0], Wc.shape[2], st)
@@ -1677,60 +1717,26 @@ class _PairHeadFactored(torch.autograd.Function):
         W1, b1, w2, b2 = (_f32c(q, "pair-head parameter") for q in (W1, b1, w2, b2))
         (U, Kd), (C_, K1), M, dev = drug.shape, x1.shape, pd.numel(), drug.device
         H, C_out = W1.shape[0], w2.shape[0]
-        st = _stream_ptr(dev)
         A = torch.empty((U, H), dtype=torch.float32, device=dev)
         B = torch.empty((C_, H), dtype=torch.float32, device=dev)
         ws = torch.empty(getattr(_lib.load(), inst.prefix + "_factored_ws")(U, C_), dtype=torch.float32, device=dev)
         out = torch.empty((M, C_out), dtype=torch.float32, device=dev)
-        g = parts = loss_t = None
-        if target is not None:
-            target = _f32c(target, "y").reshape(-1)
-            if target.numel() != M * C_out:
-                raise ValueError(f"{inst.name}_factored: {target.numel()} targets for {M} pairs")
-            g = torch.empty(M, dtype=torch.float32, device=dev)
-            parts = torch.empty(1, dtype=torch.float32, device=dev)
-            loss_t = torch.empty((), dtype=torch.float32, device=dev)
+        target, g, parts, loss_t = _pair_loss_buffers(target, M, C_out, lambda: 1, dev, inst.name + "_factored", "pairs")
         _lib.call(inst.prefix + "_factored_fwd_f32", drug.data_ptr(), x1.data_ptr(), pd.data_ptr(), ps.data_ptr(), W1.data_ptr(), b1.data_ptr(),
                   w2.data_ptr(), b2.data_ptr(), _ptr(target), A.data_ptr(), B.data_ptr(), ws.data_ptr(), out.data_ptr(), _ptr(g), _ptr(parts),
-                  M, U, C_, Kd, K1, H, C_out, st)
-        ctx.inst, ctx.params, ctx.slots = inst, (W1, b1, w2, b2), [grad_slot(q) for q in (W1, b1, w2, b2)]
-        ctx.M, ctx.fused = M, target is not None
-        if ctx.fused:
-            ctx.save_for_backward(drug, x1, A, B, *orderings, g, parts, loss_t)
-            ctx.mark_non_differentiable(out)
-            ctx.set_materialize_grads(False)
-            return out, loss_t
-        ctx.save_for_backward(drug, x1, A, B, *orderings)
-        return out
+                  M, U, C_, Kd, K1, H, C_out, _stream_ptr(dev))
+        ctx.M = M
+        return _pair_forward_end(ctx, inst, (W1, b1, w2, b2), (drug, x1, A, B, *orderings), out, g, parts, loss_t)
 
     @staticmethod
     def backward(ctx, g_out, g_loss=None):
-        drug, x1, A, B, rp_d, pm_d, rp_s, pm_s = ctx.saved_tensors[:8]
-        dev = drug.device
-        parts = loss_t = None
-        if ctx.fused:
-            g, parts, loss_t = ctx.saved_tensors[8:]
-            if g_loss is not None and not _is_unit_grad(g_loss):
-                g = g * g_loss
-        else:
-            g = _f32c(g_out, "g").reshape(-1)
-        P, slots = ctx.params, ctx.slots
-        dW1, db1, dW2, db2 = (grad_buffer(q, s) for q, s in zip(P, slots))
-        g_drug, g_x1 = torch.empty_like(drug), torch.empty_like(x1)
+        (drug, x1, *saved), g, parts, loss_t, grads, g_drug, g_x1 = _pair_backward_begin(ctx, g_out, g_loss)      # saved: A, B, the orderings
+        P, (A, B) = ctx.params, saved[:2]
         _lib.call(ctx.inst.prefix + "_factored_bwd_f32", g.data_ptr(), drug.data_ptr(), x1.data_ptr(), A.data_ptr(), B.data_ptr(), P[0].data_ptr(),
-                  P[1].data_ptr(), P[2].data_ptr(), rp_d.data_ptr(), pm_d.data_ptr(), rp_s.data_ptr(), pm_s.data_ptr(), g_drug.data_ptr(),
-                  g_x1.data_ptr(), dW1.data_ptr(), db1.data_ptr(), dW2.data_ptr(), db2.data_ptr(), _ptr(parts),
-                  0 if parts is None else parts.numel(), _ptr(loss_t), ctx.M, drug.shape[0], x1.shape[0], drug.shape[1], x1.shape[1],
-                  P[0].shape[0], P[2].shape[0], _stream_ptr(dev))
-        if ctx.inst.gated:
-            g_x1._fn_relu_gated = x1
-        return (None, g_drug if ctx.needs_input_grad[1] else None, g_x1 if ctx.needs_input_grad[2] else None, None, None, None, None,
-                dW1, db1, dW2, db2)
-
-
-def _pair_widths_ok(inst, drug_enc, x1, fc1, fc2) -> bool:
-    return (tuple(fc1.weight.shape), tuple(fc2.weight.shape)) == inst.shapes and fc1.bias is not None and fc2.bias is not None \
-        and drug_enc.dim() == 2 and x1.dim() == 2 and drug_enc.shape[1] == FN_D * 2 and x1.shape[1] == inst.width
+                  P[1].data_ptr(), P[2].data_ptr(), *(q.data_ptr() for q in saved[2:]), g_drug.data_ptr(), g_x1.data_ptr(),
+                  *(q.data_ptr() for q in grads), _ptr(parts), 0 if parts is None else parts.numel(), _ptr(loss_t), ctx.M, drug.shape[0],
+                  x1.shape[0], drug.shape[1], x1.shape[1], P[0].shape[0], P[2].shape[0], _stream_ptr(drug.device))
+        return _pair_backward_end(ctx, x1, g_drug, g_x1, grads, 3)
 
 
 def _pair_head_factored(inst, drug_enc, x1, pair_drug, pair_second, fc1, fc2, loss, orderings, check):
@@ -1752,15 +1758,7 @@ def _pair_head_factored(inst, drug_enc, x1, pair_drug, pair_second, fc1, fc2, lo
     if orderings is None:
         orderings = pair_orderings(pd, U) + pair_orderings(ps, C_)
     orderings = tuple(_i32c(t, f"{name}: pair ordering", n) for t, n in zip(orderings, (U + 1, M, C_ + 1, M)))
-    params = (fc1.weight, fc1.bias, fc2.weight, fc2.bias)
-    if loss is None:
-        return _PairHeadFactored.apply(inst, drug_enc, x1, pd, ps, orderings, None, *params)
-    kind, y, row_w = loss
-    fuse = FUSED_HEAD_LOSS and kind == _lib.LOSS_MSE and row_w is None and torch.is_grad_enabled() and M > 0 \
-        and (drug_enc.requires_grad or x1.requires_grad or any(q.requires_grad for q in params))
-    if not fuse:
-        return _PairHeadFactored.apply(inst, drug_enc, x1, pd, ps, orderings, None, *params), None
-    return _PairHeadFactored.apply(inst, drug_enc, x1, pd, ps, orderings, y, *params)
+    return _pair_apply(_PairHeadFactored, (inst, drug_enc, x1, pd, ps, orderings), M, fc1, fc2, loss)
 
 
 def pair_head_factored(drug_enc, cell_enc, pair_drug, pair_second, fc1, fc2, loss=None, orderings=None, check: bool = True):
@@ -1910,13 +1908,12 @@ class _FragMLP(torch.autograd.Function):
     def forward(ctx, x, W1, b1, W2, b2):
         x = _f32c(x, "x")
         W1, b1, W2, b2 = (_f32c(q, "frag_mlp parameter") for q in (W1, b1, W2, b2))
-        M, dev, st = x.shape[0], x.device, _stream_ptr(x.device)
-        h = torch.empty((M, W1.shape[0]), dtype=torch.float32, device=dev)
-        y = torch.empty((M, W2.shape[0]), dtype=torch.float32, device=dev)
-        if M:
-            act = _lib.ActEpilogue(h.data_ptr(), 0.0, 1, 0, 0, None)
-            _lib.call("fn_dense_fwd_f32", x.data_ptr(), W1.data_ptr(), b1.data_ptr(), h.data_ptr(), M, W1.shape[1], W1.shape[0], C.byref(act), st)
-            _lib.call("fn_dense_fwd_f32", h.data_ptr(), W2.data_ptr(), b2.data_ptr(), y.data_ptr(), M, W2.shape[1], W2.shape[0], None, st)
+        if x.shape[0]:
+            st = _stream_ptr(x.device)
+            h = _plain_fwd(x, W1, b1, True, st)
+            y = _plain_fwd(h, W2, b2, False, st)
+        else:
+            h, y = x.new_empty((0, W1.shape[0])), x.new_empty((0, W2.shape[0]))
         ctx.params, ctx.slots = (W1, b1, W2, b2), [grad_slot(q) for q in (W1, b1, W2, b2)]
         ctx.save_for_backward(x, h)
         return y
@@ -1927,13 +1924,11 @@ class _FragMLP(torch.autograd.Function):
         g = _f32c(g, "g")
         (W1, b1, W2, b2), slots = ctx.params, ctx.slots
         dW1, db1, dW2, db2 = (grad_buffer(q, s) for q, s in zip(ctx.params, slots))
-        M, st = x.shape[0], _stream_ptr(x.device)
+        st = _stream_ptr(x.device)
         g_h = torch.empty_like(h)
-        _lib.call("fn_dense_bwd_f32", g.data_ptr(), h.data_ptr(), W2.data_ptr(), g_h.data_ptr(), 1.0, dW2.data_ptr(), db2.data_ptr(), M, W2.shape[1],
-                  W2.shape[0], M, st)
+        _plain_bwd(g, h, W2, g_h, True, dW2, db2, st)
         g_x = torch.empty_like(x) if ctx.needs_input_grad[0] else None
-        _lib.call("fn_dense_bwd_f32", g_h.data_ptr(), x.data_ptr(), W1.data_ptr(), _ptr(g_x), 0.0, dW1.data_ptr(), db1.data_ptr(), M, W1.shape[1],
-                  W1.shape[0], M, st)
+        _plain_bwd(g_h, x, W1, g_x, False, dW1, db1, st)
         return g_x, dW1, db1, dW2, db2
 
 

@@ -817,6 +817,36 @@ def test_head_fuses_loss_table():
         ops.FUSED_HEAD_LOSS = before
 
 
+def test_pair_fuses_loss_table():
+    """ops.pair_fuses_loss: when a pair head (plain or factored) folds the MSE loss into its two launches."""
+    from fragnet_amd import _lib, ops
+
+    def fuses(rows=5, who=0, kind=_lib.LOSS_MSE, row_w=None, grad=True):
+        # drug, second input, fc1.weight, fc1.bias, fc2.weight, fc2.bias; ``who``: the one that takes a gradient (None: none)
+        tensors = [torch.zeros(3, requires_grad=(i == who)) for i in range(6)]
+        with torch.set_grad_enabled(grad):
+            got = ops.pair_fuses_loss((kind, torch.zeros(max(rows, 1)), row_w), rows, tensors)
+        assert isinstance(got, bool)
+        return got
+
+    before = ops.FUSED_HEAD_LOSS
+    try:
+        ops.FUSED_HEAD_LOSS = True
+        for rows in (1, 4096):
+            assert fuses(rows, who=0) and fuses(rows, who=1) and all(fuses(rows, who=i) for i in (2, 3, 4, 5))
+        assert not fuses(rows=0)                                    # nothing live
+        assert not fuses(kind=_lib.LOSS_BCE)
+        assert not fuses(row_w=torch.ones(5))
+        assert not fuses(grad=False)                                # under torch.no_grad()
+        assert not fuses(who=None)                                  # nothing takes a gradient
+        ops.FUSED_HEAD_LOSS = False
+        for rows in (1, 4096):
+            assert not any(fuses(rows, who=i) for i in range(6))
+        assert not fuses(rows=0) and not fuses(kind=_lib.LOSS_BCE) and not fuses(row_w=torch.ones(5)) and not fuses(grad=False) and not fuses(who=None)
+    finally:
+        ops.FUSED_HEAD_LOSS = before
+
+
 def _fuses_loss_rows(fuses):
     assert fuses() and fuses(rows=6) and fuses(rows=1) and fuses(M=4096, rows=4096)
     assert not fuses(rows=0)                                        # nothing live
