@@ -3,12 +3,18 @@ fn_encoder_forward / fn_encoder_backward walk the layers inside libfragnet_hip.s
 (MFMA projections, node scalars, segmented softmax-aggregate, segment sum, dropout+ReLU) on the current
 stream.  Python does not see the per-level ops, so a training step costs two ctypes calls for the encoder
 instead of ~250 autograd nodes.
+
+``encoder_forward`` is the one way in.  It refuses what no pass serves, then runs one of three passes on the shared body
+``_begin_pass`` / ``_end_pass``: the autograd node ``_EncoderFn`` (fn_encoder_forward, or fn_encoder_forward_keep behind the input
+gate), ``_masked_forward`` (fn_encoder_forward_masked) or ``_attn_forward`` (fn_encoder_forward_attn).  What a pass is, beside its
+three input tables and the parameters, is one ``_Spec``.
 """
 from __future__ import annotations
 
 import ctypes as C
 import os
-from typing import List, Sequence
+from collections import namedtuple
+from typing import List, NamedTuple, Optional, Sequence
 
 import torch
 
@@ -48,29 +54,48 @@ def _f32(t: torch.Tensor, name: str) -> torch.Tensor:
     return t if t.is_contiguous() else t.contiguous()
 
 
-def _describe(plan: GraphPlan, x_atoms, bond_nodes, fbond_nodes, cos_sorted, fattr_sorted, params: Sequence[torch.Tensor],
-              n_layers: int, heads: int, drop_p: float, training: bool, seed: int, offset: int, offset_dev=None,
-              variant: int = 0, no_backward: bool = False) -> Encoder:
+class _Spec(NamedTuple):
+    """Everything of one encoder pass that is no input table and no parameter: _EncoderFn.apply's one non-tensor argument.  None of
+    its tensors is differentiable."""
+    plan: GraphPlan
+    cos_sorted: torch.Tensor
+    fattr_sorted: torch.Tensor
+    n_layers: int
+    heads: int
+    drop_p: float = 0.0
+    training: bool = False
+    seed: int = 0
+    offset: int = 0
+    offset_dev: Optional[torch.Tensor] = None
+    variant: int = 0
+    no_backward: bool = False
+    edge_outputs: bool = True
+    keep_atoms: Optional[torch.Tensor] = None
+
+
+def _describe(tables, params: Sequence[torch.Tensor], spec: _Spec) -> Encoder:
+    plan, variant, fattr_sorted = spec.plan, spec.variant, spec.fattr_sorted
+    x_atoms, bond_nodes, fbond_nodes = tables
     e = Encoder()
-    e.n_layers, e.heads = n_layers, heads
+    e.n_layers, e.heads = spec.n_layers, spec.heads
     e.k_atom0, e.k_bond0, e.k_fbond0 = x_atoms.shape[1], bond_nodes.shape[1], fbond_nodes.shape[1]
     e.k_fattr = fattr_sorted.shape[0]
-    e.training, e.drop_p = int(training), float(drop_p)
-    e.no_backward = int(bool(no_backward) and not training)       # an evaluation pass nobody differentiates saves nothing for a backward pass
+    e.training, e.drop_p = int(spec.training), float(spec.drop_p)
+    e.no_backward = int(bool(spec.no_backward) and not spec.training)       # an evaluation pass nobody differentiates saves nothing for a backward pass
     e.variant = int(variant)
-    e.seed, e.offset = seed, offset
-    e.offset_dev = None if offset_dev is None else offset_dev.data_ptr()
+    e.seed, e.offset = spec.seed, spec.offset
+    e.offset_dev = None if spec.offset_dev is None else spec.offset_dev.data_ptr()
     L = plan.levels
     e.N, e.E, e.F, e.EF = L["atom"].n, L["bond"].n, L["frag"].n, L["fbond"].n
     e.bond, e.atom, e.fbond, e.frag = L["bond"].c, L["atom"].c, L["fbond"].c, L["frag"].c
     s = plan.segs["a2f"]
     e.a2f = SegPlan(s.rowptr.data_ptr(), s.perm.data_ptr(), s.index.data_ptr(), s.n_seg, s.n_items, s.pos_base, 0)
     e.x_atoms, e.bond_nodes, e.fbond_nodes = x_atoms.data_ptr(), bond_nodes.data_ptr(), fbond_nodes.data_ptr()
-    e.cos_sorted, e.fattr_sorted = cos_sorted.data_ptr(), fattr_sorted.data_ptr()
+    e.cos_sorted, e.fattr_sorted = spec.cos_sorted.data_ptr(), fattr_sorted.data_ptr()
     raw_b, raw_f = plan.pending.get("bond"), plan.pending.get("frag" if variant == 2 else "fbond")      # sorted copies not filled yet: the forward does it
     e.cos_raw = None if raw_b is None else raw_b.data_ptr()
     e.fattr_raw = None if raw_f is None else raw_f.data_ptr()
-    for l in range(n_layers):
+    for l in range(spec.n_layers):
         for k, name in enumerate(LAYER_FIELDS):
             setattr(e.w[l], name, params[l * NP + k].data_ptr())
     # molecule CSRs: with them fn_encoder_* runs the molecule-resident fused kernels (include/fragnet_hip.h, fn_encoder.n_mols)
@@ -86,52 +111,74 @@ def _describe(plan: GraphPlan, x_atoms, bond_nodes, fbond_nodes, cos_sorted, fat
     return e
 
 
+def _out_ptrs(outs, edge_outputs: bool, spare=None):
+    """The four output pointers of a pass.  edge_outputs = False: the caller reads neither the bond nor the fragment-bond output (a
+    finetune head): the library gets NULL for them and does not store the last layer's activated rows; two empty tensors stand in.
+    ``spare``: what an output of no rows points at instead of NULL (the read-out pass)."""
+    return [(o.data_ptr() or spare) if (edge_outputs or k < 2) else None for k, o in enumerate(outs)]
+
+
+_Pass = namedtuple("_Pass", "e ws outs out_ptrs pooled fused tables params spare dev lib")
+
+
+def _begin_pass(tables, params, spec: _Spec, stand_in: bool = False) -> _Pass:
+    """What the four forward entry points share: float32 tables and parameters, the descriptor, its workspace, the four outputs, the
+    readout where the fused tail writes one (``fused``; an empty placeholder otherwise) and the output pointers.  ``stand_in`` (the
+    read-out pass only; enc_check refuses a null input on the others): see below."""
+    tables = tuple(_f32(t, name) for t, name in zip(tables, ("x_atoms", "node_features_bonds", "node_features_fbonds")))
+    params = tuple(_f32(p, "parameter") for p in params)
+    dev, lib = tables[0].device, _lib.load()
+    e = _describe(tables, params, spec)
+    # a batch without fragment connections (EF == 0: one-fragment molecules stripped of their placeholder row) has empty fragment-bond
+    # tensors, whose data_ptr() is null; the descriptor wants a pointer for every input, read or not: a stand-in that no launch reads
+    # (a level of no rows launches nothing).  out_bond and out_fbond are wanted together: an output of no rows gets its pointer too
+    spare = None
+    if stand_in and (e.EF == 0 or spec.plan.levels["fbond"].m == 0):
+        spare = torch.zeros(max(e.k_fbond0, e.k_fattr, FN_D), dtype=torch.float32, device=dev)
+        e.fbond_nodes = e.fbond_nodes or spare.data_ptr()
+        e.fattr_sorted = e.fattr_sorted or spare.data_ptr()
+    # keep_atoms: the input gate of x_atoms (fn_encoder_forward_keep); its gated copy may live behind the plain workspace
+    ws_floats = lib.fn_encoder_ws_floats if spec.keep_atoms is None else lib.fn_encoder_keep_ws_floats
+    ws = torch.empty(ws_floats(C.byref(e)), dtype=torch.float32, device=dev)
+    e.ws, e.ws_floats = ws.data_ptr(), ws.numel()
+    outs = [torch.empty((n if (spec.edge_outputs or k < 2) else 0, FN_D), dtype=torch.float32, device=dev) for k, n in enumerate((e.N, e.F, e.E, e.EF))]
+    # molecule-contiguous batches: the last layer's fragment tail is one molecule-resident launch that also writes the
+    # readout cat(scatter_add(x_atoms, batch), scatter_add(x_frags, frag_batch)) (gat2.py:820-823) -- a fifth output
+    fused = bool(lib.fn_encoder_fused_tail(C.byref(e)))
+    pooled = torch.empty((e.n_mols, 2 * FN_D) if fused else 0, dtype=torch.float32, device=dev)      # not fused: the caller pools with ops.pool_cat
+    e.pooled = pooled.data_ptr() if fused else None
+    return _Pass(e, ws, outs, _out_ptrs(outs, spec.edge_outputs, None if spare is None else spare.data_ptr()), pooled, fused, tables, params,
+                 spare, dev, lib)
+
+
+def _end_pass(plan: GraphPlan, variant: int) -> None:
+    """The forward filled the plan's sorted attribute copies: they are pending no more."""
+    plan.pending.pop("bond", None)
+    plan.pending.pop("frag" if variant == 2 else "fbond", None)
+
+
 class _EncoderFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x_atoms, bond_nodes, fbond_nodes, cos_sorted, fattr_sorted, plan, n_layers, heads, drop_p, training,
-                seed, offset, offset_dev, variant, no_backward, edge_outputs, keep_atoms, *params):
-        x_atoms, bond_nodes, fbond_nodes = _f32(x_atoms, "x_atoms"), _f32(bond_nodes, "node_features_bonds"), _f32(fbond_nodes, "node_features_fbonds")
+    def forward(ctx, x_atoms, bond_nodes, fbond_nodes, spec: _Spec, *params):
         ctx.param_objs, ctx.slots = params, [ops.grad_slot(p) for p in params]
-        params = tuple(_f32(p, "parameter") for p in params)
-        dev = x_atoms.device
-        lib = _lib.load()
-        e = _describe(plan, x_atoms, bond_nodes, fbond_nodes, cos_sorted, fattr_sorted, params, n_layers, heads, drop_p,
-                      training, seed, offset, offset_dev, variant, no_backward)
-        # keep_atoms: the input gate of x_atoms (fn_encoder_forward_keep); its gated copy may live behind the plain workspace
-        ws = torch.empty((lib.fn_encoder_ws_floats if keep_atoms is None else lib.fn_encoder_keep_ws_floats)(C.byref(e)), dtype=torch.float32, device=dev)
-        e.ws, e.ws_floats = ws.data_ptr(), ws.numel()
-        # edge_outputs = False: the caller reads neither the bond nor the fragment-bond output (a finetune head): the library gets NULL for
-        # them and does not store the last layer's activated rows; two empty, non-differentiable tensors stand in
-        outs = [torch.empty((n if (edge_outputs or k < 2) else 0, FN_D), dtype=torch.float32, device=dev) for k, n in enumerate((e.N, e.F, e.E, e.EF))]
-        # molecule-contiguous batches: the last layer's fragment tail is one molecule-resident launch that also writes the
-        # readout cat(scatter_add(x_atoms, batch), scatter_add(x_frags, frag_batch)) (gat2.py:820-823) -- a fifth output
-        pooled = None
-        if lib.fn_encoder_fused_tail(C.byref(e)):
-            pooled = torch.empty((e.n_mols, 2 * FN_D), dtype=torch.float32, device=dev)
-            e.pooled = pooled.data_ptr()
-        out_ptrs = [(o.data_ptr() if (edge_outputs or k < 2) else None) for k, o in enumerate(outs)]
+        ps = _begin_pass((x_atoms, bond_nodes, fbond_nodes), params, spec)
+        e, outs, keep_atoms = ps.e, ps.outs, spec.keep_atoms
         if keep_atoms is None:
-            _lib.check(lib.fn_encoder_forward(C.byref(e), *out_ptrs, _stream_ptr(dev)), "fn_encoder_forward")
+            _lib.check(ps.lib.fn_encoder_forward(C.byref(e), *ps.out_ptrs, _stream_ptr(ps.dev)), "fn_encoder_forward")
         else:
-            _lib.check(lib.fn_encoder_forward_keep(C.byref(e), keep_atoms.data_ptr(), *out_ptrs, _stream_ptr(dev)), "fn_encoder_forward_keep")
+            _lib.check(ps.lib.fn_encoder_forward_keep(C.byref(e), keep_atoms.data_ptr(), *ps.out_ptrs, _stream_ptr(ps.dev)), "fn_encoder_forward_keep")
+        _end_pass(spec.plan, spec.variant)
         e.pooled = None
-        plan.pending.pop("bond", None)
-        plan.pending.pop("frag" if variant == 2 else "fbond", None)
         e.cos_raw = e.fattr_raw = None           # the backward pass reads the sorted copies only
         ctx.desc = e
-        ctx.keep = (plan, x_atoms, bond_nodes, fbond_nodes, cos_sorted, fattr_sorted, ws, offset_dev, keep_atoms)
-        ctx.n_layers = n_layers
-        ctx.variant = int(variant)
-        ctx.edge_outputs = bool(edge_outputs)
-        ctx.save_for_backward(*params, *outs)
+        ctx.keep = (spec.plan, *ps.tables, spec.cos_sorted, spec.fattr_sorted, ps.ws, spec.offset_dev, keep_atoms)
+        ctx.n_layers, ctx.variant, ctx.edge_outputs = spec.n_layers, spec.variant, spec.edge_outputs
+        ctx.save_for_backward(*ps.params, *outs)
         ctx.set_materialize_grads(False)
-        dead = [] if edge_outputs else [outs[2], outs[3]]
-        if pooled is None:                   # placeholder: the caller pools with ops.pool_cat
-            pooled = torch.empty(0, dtype=torch.float32, device=dev)
-            dead.append(pooled)
+        dead = ([] if spec.edge_outputs else [outs[2], outs[3]]) + ([] if ps.fused else [ps.pooled])
         if dead:
             ctx.mark_non_differentiable(*dead)           # (at most one call per forward)
-        return tuple(outs) + (pooled,)
+        return tuple(outs) + (ps.pooled,)
 
     @staticmethod
     def backward(ctx, g_atoms, g_frags, g_bond, g_fbond, g_pooled):
@@ -158,8 +205,7 @@ class _EncoderFn(torch.autograd.Function):
         if rider is not None:
             rider.launched = 0
         try:
-            _lib.check(lib.fn_encoder_backward(C.byref(e), *((o.data_ptr() if (ctx.edge_outputs or k < 2) else None) for k, o in enumerate(outs)),
-                                               *(None if g is None else g.data_ptr() for g in gs), gw, scratch.data_ptr(),
+            _lib.check(lib.fn_encoder_backward(C.byref(e), *_out_ptrs(outs, ctx.edge_outputs), *(None if g is None else g.data_ptr() for g in gs), gw, scratch.data_ptr(),
                                                scratch.numel(), _stream_ptr(dev)), "fn_encoder_backward")
         finally:
             e.adam_rider = None
@@ -178,7 +224,7 @@ class _EncoderFn(torch.autograd.Function):
                 if ctx.variant == 2 and (k in EDGE_DEAD or (k in EDGE_LAST_ONLY and not (l == n_layers - 1 and have_frags))):
                     live = False
                 out.append(grads[l * NP + k] if live else None)
-        return tuple(g_in) + (None,) * 14 + tuple(out)
+        return tuple(g_in) + (None,) + tuple(out)
 
 
 def _input_grads(ctx, e, scratch, need, dev):
@@ -257,75 +303,51 @@ def adam_rider_taken() -> bool:
     return taken
 
 
+def _is_row_bytes(t, rows: int) -> bool:
+    return torch.is_tensor(t) and t.dtype == torch.uint8 and t.is_cuda and t.dim() == 1 and t.numel() == rows and t.is_contiguous()
+
+
 def _row_mask(t, rows: int, name: str):
-    if t is None:
-        return None
-    if not torch.is_tensor(t) or t.dtype != torch.uint8 or not t.is_cuda or t.dim() != 1 or t.numel() != rows or not t.is_contiguous():
+    if t is not None and not _is_row_bytes(t, rows):
         raise ValueError(f"row_masks: {name} must be a contiguous uint8 CUDA tensor of {rows} rows (1 = zero this row)")
     return t
 
 
-def _masked_forward(plan, x_atoms, bond_nodes, fbond_nodes, cos_sorted, fattr_sorted, params, n_layers, heads, variant, edge_outputs, row_masks):
-    """fn_encoder_forward_masked: an evaluation pass nobody differentiates, so no autograd node -- the outputs are plain tensors."""
-    x_atoms, bond_nodes, fbond_nodes = _f32(x_atoms, "x_atoms"), _f32(bond_nodes, "node_features_bonds"), _f32(fbond_nodes, "node_features_fbonds")
-    params = tuple(_f32(p.detach(), "parameter") for p in params)
-    dev = x_atoms.device
-    lib = _lib.load()
-    e = _describe(plan, x_atoms, bond_nodes, fbond_nodes, cos_sorted, fattr_sorted, params, n_layers, heads, 0.0, False, 0, 0, None, variant, True)
-    names = ("mask_atoms", "mask_bonds", "mask_fbonds")
-    masks = [_row_mask(t, n, name) for t, n, name in zip(row_masks, (e.N, e.E, e.EF), names)]
+def _masked_forward(tables, params, spec: _Spec, row_masks):
+    """fn_encoder_forward_masked: an evaluation pass nobody differentiates, so no autograd node -- the outputs are plain tensors.
+    no_backward is set unconditionally: the entry point refuses 0."""
+    ps = _begin_pass(tables, params, spec._replace(no_backward=True))
+    e = ps.e
+    masks = [_row_mask(t, n, name) for t, n, name in zip(row_masks, (e.N, e.E, e.EF), ("mask_atoms", "mask_bonds", "mask_fbonds"))]
     m = _lib.RowMasks(*(None if t is None else t.data_ptr() for t in masks))
-    ws = torch.empty(lib.fn_encoder_ws_floats(C.byref(e)), dtype=torch.float32, device=dev)
-    e.ws, e.ws_floats = ws.data_ptr(), ws.numel()
-    outs = [torch.empty((n if (edge_outputs or k < 2) else 0, FN_D), dtype=torch.float32, device=dev) for k, n in enumerate((e.N, e.F, e.E, e.EF))]
-    pooled = torch.empty(0, dtype=torch.float32, device=dev)
-    if lib.fn_encoder_fused_tail(C.byref(e)):
-        pooled = torch.empty((e.n_mols, 2 * FN_D), dtype=torch.float32, device=dev)
-        e.pooled = pooled.data_ptr()
-    _lib.check(lib.fn_encoder_forward_masked(C.byref(e), C.byref(m), *((o.data_ptr() if (edge_outputs or k < 2) else None) for k, o in enumerate(outs)),
-                                             _stream_ptr(dev)), "fn_encoder_forward_masked")
-    plan.pending.pop("bond", None)
-    plan.pending.pop("frag" if variant == 2 else "fbond", None)
-    return tuple(outs) + (pooled,)
+    _lib.check(ps.lib.fn_encoder_forward_masked(C.byref(e), C.byref(m), *ps.out_ptrs, _stream_ptr(ps.dev)), "fn_encoder_forward_masked")
+    _end_pass(spec.plan, spec.variant)
+    return tuple(ps.outs) + (ps.pooled,)
 
 
 _KEEP_ATTN_WS = None      # tests: a list that collects (descriptor, workspace) of every read-out pass (the stored probabilities live there)
 
 
-def _attn_forward(plan, x_atoms, bond_nodes, fbond_nodes, cos_sorted, fattr_sorted, params, n_layers, heads, variant, edge_outputs):
+def _attn_forward(tables, params, spec: _Spec):
     """fn_encoder_forward_attn: an evaluation pass nobody differentiates (no autograd node) that also returns the last layer's four
     by-source attention sums, each [n, heads] for every node of its level."""
-    x_atoms, bond_nodes, fbond_nodes = _f32(x_atoms, "x_atoms"), _f32(bond_nodes, "node_features_bonds"), _f32(fbond_nodes, "node_features_fbonds")
-    params = tuple(_f32(p.detach(), "parameter") for p in params)
-    dev = x_atoms.device
-    lib = _lib.load()
-    e = _describe(plan, x_atoms, bond_nodes, fbond_nodes, cos_sorted, fattr_sorted, params, n_layers, heads, 0.0, False, 0, 0, None, variant,
-                  not _EVAL_SAVES)
-    # a batch without fragment connections (EF == 0: one-fragment molecules stripped of their placeholder row) has empty fragment-bond
-    # tensors, whose data_ptr() is null; the descriptor wants a pointer for every input, read or not: a stand-in that no launch reads
-    # (a level of no rows launches nothing)
-    stand_in = None
-    if e.EF == 0 or plan.levels["fbond"].m == 0:
-        stand_in = torch.zeros(max(e.k_fbond0, e.k_fattr, FN_D), dtype=torch.float32, device=dev)
-        e.fbond_nodes = e.fbond_nodes or stand_in.data_ptr()
-        e.fattr_sorted = e.fattr_sorted or stand_in.data_ptr()
-    ws = torch.empty(lib.fn_encoder_ws_floats(C.byref(e)), dtype=torch.float32, device=dev)
-    e.ws, e.ws_floats = ws.data_ptr(), ws.numel()
-    outs = [torch.empty((n if (edge_outputs or k < 2) else 0, FN_D), dtype=torch.float32, device=dev) for k, n in enumerate((e.N, e.F, e.E, e.EF))]
-    attn = [torch.empty((n, heads), dtype=torch.float32, device=dev) for n in (e.N, e.F, e.E, e.EF)]      # atoms, frags, bonds, fbonds
+    ps = _begin_pass(tables, params, spec._replace(no_backward=not _EVAL_SAVES), stand_in=True)
+    e = ps.e
+    attn = [torch.empty((n, spec.heads), dtype=torch.float32, device=ps.dev) for n in (e.N, e.F, e.E, e.EF)]      # atoms, frags, bonds, fbonds
     r = _lib.AttnReadout(*(t.data_ptr() for t in attn))
-    pooled = torch.empty(0, dtype=torch.float32, device=dev)
-    if lib.fn_encoder_fused_tail(C.byref(e)):
-        pooled = torch.empty((e.n_mols, 2 * FN_D), dtype=torch.float32, device=dev)
-        e.pooled = pooled.data_ptr()
-    # (out_bond and out_fbond are wanted together: an output of no rows gets the stand-in's pointer too)
-    ptrs = [(o.data_ptr() or (stand_in.data_ptr() if stand_in is not None else None)) if (edge_outputs or k < 2) else None for k, o in enumerate(outs)]
-    _lib.check(lib.fn_encoder_forward_attn(C.byref(e), C.byref(r), *ptrs, _stream_ptr(dev)), "fn_encoder_forward_attn")
-    plan.pending.pop("bond", None)
-    plan.pending.pop("frag" if variant == 2 else "fbond", None)
+    _lib.check(ps.lib.fn_encoder_forward_attn(C.byref(e), C.byref(r), *ps.out_ptrs, _stream_ptr(ps.dev)), "fn_encoder_forward_attn")
+    _end_pass(spec.plan, spec.variant)
     if _KEEP_ATTN_WS is not None:
-        _KEEP_ATTN_WS.append((e, ws))
-    return tuple(outs) + (pooled,) + tuple(attn)
+        _KEEP_ATTN_WS.append((e, ps.ws))
+    return tuple(ps.outs) + (ps.pooled,) + tuple(attn)
+
+
+def _evaluation_only(prefix: str, noun: str, training: bool, any_grad: bool) -> None:
+    """The masked and the read-out pass are evaluation passes without a backward."""
+    if training:
+        raise RuntimeError(f"{prefix}: a {noun} pass is an evaluation pass (the model is in training mode)")
+    if any_grad:
+        raise RuntimeError(f"{prefix}: the {noun} pass has no backward; run it under torch.no_grad()")
 
 
 def encoder_forward(layers, plan: GraphPlan, x_atoms, bond_nodes, fbond_nodes, cos_sorted, fattr_sorted, heads: int,
@@ -359,35 +381,33 @@ def encoder_forward(layers, plan: GraphPlan, x_atoms, bond_nodes, fbond_nodes, c
                                f"layer 0 {name} expects {w.shape[-1]} input features, the batch has {x.shape[-1]}")
     if row_masks is not None and len(row_masks) != 3:
         raise ValueError("row_masks: a triple (atoms, bonds, fragment bonds)")
+    masked = row_masks is not None and any(t is not None for t in row_masks)
+    tables = (x_atoms, bond_nodes, fbond_nodes)
+    # (inside Function.forward grad mode is always off: it is read here)
+    in_grad = torch.is_grad_enabled() and any(t.requires_grad for t in tables)
+    any_grad = in_grad or (torch.is_grad_enabled() and any(p.requires_grad for p in params))
     if keep_atoms is not None:
-        if attn_readout or (row_masks is not None and any(t is not None for t in row_masks)):
+        if attn_readout or masked:
             raise ValueError("keep_atoms: the input gate does not combine with row masks or the attention read-out")
         if int(variant) != 0:
             raise ValueError("keep_atoms: the input gate exists for model_version gat2 (the reference masks atoms in FragNetPreTrainMasked2 only)")
-        if not torch.is_tensor(keep_atoms) or keep_atoms.dtype != torch.uint8 or not keep_atoms.is_cuda or keep_atoms.dim() != 1 or \
-                keep_atoms.numel() != x_atoms.shape[0] or not keep_atoms.is_contiguous():
+        if not _is_row_bytes(keep_atoms, x_atoms.shape[0]):
             raise ValueError(f"keep_atoms must be a contiguous uint8 CUDA tensor of {x_atoms.shape[0]} rows (1 = keep, 0 = the row reads as zero)")
-        if torch.is_grad_enabled() and any(t.requires_grad for t in (x_atoms, bond_nodes, fbond_nodes)):
+        if in_grad:
             raise NotImplementedError("keep_atoms: there are no input gradients of a masked pass (fn_encoder_backward_inputs refuses it)")
+    spec = _Spec(plan, cos_sorted, fattr_sorted, n_layers, heads, variant=int(variant), edge_outputs=bool(edge_outputs), keep_atoms=keep_atoms)
     if attn_readout:
-        if row_masks is not None and any(t is not None for t in row_masks):
+        if masked:
             raise ValueError("attn_readout: there is no attention read-out of a masked pass (row_masks)")
         if int(variant) != 0:
             raise ValueError("attn_readout: the attention read-out exists for model_version gat2 (the reference's lite / edge Viz classes cannot run)")
-        if training:
-            raise RuntimeError("attn_readout: a read-out pass is an evaluation pass (the model is in training mode)")
-        if torch.is_grad_enabled() and any(t.requires_grad for t in (x_atoms, bond_nodes, fbond_nodes, *params)):
-            raise RuntimeError("attn_readout: the read-out pass has no backward; run it under torch.no_grad()")
-        return _attn_forward(plan, x_atoms, bond_nodes, fbond_nodes, cos_sorted, fattr_sorted, params, len(layers), heads, 0, bool(edge_outputs))
-    if row_masks is not None and any(t is not None for t in row_masks):
-        if training:
-            raise RuntimeError("row_masks: a masked pass is an evaluation pass (the model is in training mode)")
-        if torch.is_grad_enabled() and any(t.requires_grad for t in (x_atoms, bond_nodes, fbond_nodes, *params)):
-            raise RuntimeError("row_masks: the masked pass has no backward; run it under torch.no_grad()")
-        return _masked_forward(plan, x_atoms, bond_nodes, fbond_nodes, cos_sorted, fattr_sorted, params, len(layers), heads, int(variant),
-                               bool(edge_outputs), row_masks)
+        _evaluation_only("attn_readout", "read-out", training, any_grad)
+        return _attn_forward(tables, params, spec)
+    if masked:
+        _evaluation_only("row_masks", "masked", training, any_grad)
+        return _masked_forward(tables, params, spec, row_masks)
     p_eff = float(drop_p) if training else 0.0
-    if torch.is_grad_enabled() and any(t.requires_grad for t in (x_atoms, bond_nodes, fbond_nodes)):
+    if in_grad:
         # input gradients (fn_encoder_backward_inputs): refused here, before the forward, where the backward could not serve them
         if int(variant) == 2:
             raise NotImplementedError("input gradients: the engine differentiates its inputs for gat2 and gat2_lite, not for gat2_edge")
@@ -400,10 +420,7 @@ def encoder_forward(layers, plan: GraphPlan, x_atoms, bond_nodes, fbond_nodes, c
         F, EF = plan.levels["frag"].n, fbond_nodes.shape[0]
         blocks = (N * x_atoms.shape[1] + 3) // 4 + n_layers * sum((n * FN_D + 3) // 4 for n in (N, F, E, EF))
         seed, offset = rng.take(4 * blocks)
-    else:
-        seed, offset = 0, 0
+        spec = spec._replace(drop_p=p_eff, seed=seed, offset=offset, offset_dev=rng.dev)
     # under torch.no_grad(), or when nothing it reads requires a gradient, no backward pass can follow: an evaluation pass then
-    # stores nothing for one (fn_encoder.no_backward).  (Inside Function.forward grad mode is always off: it is read here.)
-    no_backward = not _EVAL_SAVES and not (torch.is_grad_enabled() and any(t.requires_grad for t in (x_atoms, bond_nodes, fbond_nodes, *params)))
-    return _EncoderFn.apply(x_atoms, bond_nodes, fbond_nodes, cos_sorted, fattr_sorted, plan, n_layers, heads, p_eff,
-                            bool(training), seed, offset, rng.dev if p_eff > 0.0 else None, int(variant), no_backward, bool(edge_outputs), keep_atoms, *params)
+    # stores nothing for one (fn_encoder.no_backward)
+    return _EncoderFn.apply(*tables, spec._replace(training=bool(training), no_backward=not _EVAL_SAVES and not any_grad), *params)

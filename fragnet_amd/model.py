@@ -288,87 +288,90 @@ class FragNet(nn.Module):
                                              edge_in=emb_dim, edge_out=emb_dim, fedge_in=emb_dim,
                                              fbond_edge_in=fbond_edge_in, num_heads=num_heads))
 
-    def forward(self, batch, edge_outputs: bool = True):
-        """``edge_outputs=False`` (what the finetune models pass: their heads pool atoms and fragments only, gat2.py:816-826): the engine does
-        not store the last layer's activated bond / fragment-bond rows; the third and fourth result are then empty tensors."""
-        plan = plan_for(batch)
-        p, train = self.dropout.p, self.training
-        row_masks = batch_row_masks(batch)
-        keep_atoms = batch.get(KEEP_KEY)
-        if keep_atoms is not None:
-            # the input gate of masked-atom pretraining (engine.encoder_forward's keep_atoms): on the engine's gat2 path only
-            if row_masks is not None:
+    def route(self, batch, attn: bool = False) -> str:
+        """Which way ``forward(batch)`` takes, from attributes of the model and the presence of batch keys alone (no GPU, no plan):
+        "engine" (fn_encoder_forward), "engine-keep" (a batch with KEEP_KEY: the input gate), "engine-masked" (a batch with MASK_KEYS),
+        "engine-attn" (``attn=True``, FragNetViz's query: the read-out pass) or "levels" (one autograd node per level); ValueError for a
+        batch no way serves.  The gated and the masked pass exist on the engine's gat2 path only; there is no per-level form of them."""
+        masks = batch_row_masks(batch) is not None
+        layers = list(self.layers)
+        want = [bool(l.return_attentions) for l in layers]
+        # a per-layer attribute forces the level-by-level path (a FragNetLayerEdge has no mask attributes)
+        layer_masks = any(getattr(l, "bond_mask", None) is not None or getattr(l, "frag_bond_mask", None) is not None
+                          or getattr(l, "atom_mask_individual", None) is not None for l in layers)
+        on_engine = self.use_engine and not layer_masks
+        if attn:      # evaluation, only the last layer reads attentions out, no mask of either kind, nothing to differentiate
+            if on_engine and not self.training and not masks and want[-1] and not any(want[:-1]) and \
+                    not (torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())):
+                return "engine-attn"
+            if masks:
+                raise ValueError("row masks in the batch run on the engine's masked pass, which has no attention read-out")
+            return "levels"
+        on_engine = on_engine and not any(want)
+        if batch.get(KEEP_KEY) is not None:
+            if masks:
                 raise ValueError(f"{KEEP_KEY}: the input gate does not combine with row masks ({', '.join(MASK_KEYS)})")
             if self.variant != "gat2":
                 raise ValueError(f"{KEEP_KEY}: model_version {self.variant!r} has no input gate (gat2 only)")
-            if not self.use_engine or any(l.return_attentions or l.bond_mask is not None or l.frag_bond_mask is not None
-                                          or l.atom_mask_individual is not None for l in self.layers):
+            if not on_engine:
                 raise ValueError(f"{KEEP_KEY} runs on the engine only: not with use_engine=False, return_attentions or the per-layer "
                                  "scalar mask attributes")
-        if row_masks is not None:
-            return self._forward_masked(batch, plan, row_masks, edge_outputs)
-        if self.variant == "gat2_edge" and self.use_engine and not any(l.return_attentions for l in self.layers):
-            # whole encoder in two C calls (fn_encoder.variant = 2); the placeholder fragment-bond input is never multiplied
-            outs = engine.encoder_forward(self.layers, plan, batch["x_atoms"], batch["node_features_bonds"],
-                                          batch["node_features_fbonds"], plan.sorted_attr("bond", batch["edge_attr_bonds"], defer=True),
-                                          plan.sorted_attr("frag", batch["cnx_attr"], defer=True), self.layers[0].num_heads,
-                                          p, train, self.rng, variant=2, edge_outputs=edge_outputs)
-            return outs[0], outs[1], outs[2], None
-        if self.variant == "gat2_edge":                      # gat2_edge.py:198-236: three tensors travel between layers
-            x_atoms = ops.dropout_act(batch["x_atoms"], p, train, False, self.rng)
-            bond_nodes, x_frags = batch["node_features_bonds"], None
-            for layer in self.layers:
-                x_atoms, x_frags, bond_nodes = layer.run(x_atoms, bond_nodes, batch["edge_attr_bonds"], batch["cnx_attr"], plan)[:3]
-                x_atoms = ops.dropout_act(x_atoms, p, train, True, self.rng)
-                x_frags = ops.dropout_act(x_frags, p, train, True, self.rng)
-                bond_nodes = ops.dropout_act(bond_nodes, p, train, True, self.rng)
-            return x_atoms, x_frags, bond_nodes, None
-        lite = self.variant == "gat2_lite"
-        for layer in self.layers:
-            layer.lite = lite
-        if self.use_engine and not any(l.return_attentions or l.bond_mask is not None or l.frag_bond_mask is not None
-                                       or l.atom_mask_individual is not None for l in self.layers):
-            # whole encoder in two C calls (fragnet_amd/engine.py); masks / attention outputs use the per-level path
-            outs = engine.encoder_forward(self.layers, plan, batch["x_atoms"], batch["node_features_bonds"],
-                                          batch["node_features_fbonds"], plan.sorted_attr("bond", batch["edge_attr_bonds"], defer=True),
-                                          plan.sorted_attr("fbond", batch["edge_attr_fbonds"], defer=True), self.layers[0].num_heads,
-                                          p, train, self.rng, variant=1 if lite else 0, edge_outputs=edge_outputs, keep_atoms=keep_atoms)
-            if outs[4].numel():      # the fused fragment tail also produced the readout: pooled() below hands it out
-                # (with the versions of both tensors at this point: an in-place edit of either -- a mask, an attribution hook --
-                # between the encoder and pooled() must not be answered with the readout of the unedited rows)
-                outs[0]._fragnet_readout = (outs[1], outs[4], outs[0]._version, outs[1]._version)
-            return (outs[0], outs[1], outs[2], None) if lite else outs[:4]
-        x_atoms = ops.dropout_act(batch["x_atoms"], p, train, False, self.rng)
+            return "engine-keep"
+        if masks:
+            if self.variant != "gat2":
+                raise ValueError(f"row masks ({', '.join(MASK_KEYS)}): model_version {self.variant!r} has no masks (gat2 only)")
+            if not on_engine:
+                raise ValueError("row masks in the batch run on the engine only: not with use_engine=False, return_attentions or the "
+                                 "per-layer scalar mask attributes")
+            return "engine-masked"
+        return "engine" if on_engine else "levels"
+
+    def _engine(self, batch, plan, edge_outputs: bool = True, **kw):
+        """The whole encoder in two C calls (fragnet_amd/engine.py); ``kw``: row_masks, keep_atoms, attn_readout.  gat2_edge: the fragment
+        graph's attribute is cnx_attr, and the placeholder fragment-bond input is never multiplied."""
+        fkey, fattr = ("frag", "cnx_attr") if self.variant == "gat2_edge" else ("fbond", "edge_attr_fbonds")
+        outs = engine.encoder_forward(self.layers, plan, batch["x_atoms"], batch["node_features_bonds"], batch["node_features_fbonds"],
+                                      plan.sorted_attr("bond", batch["edge_attr_bonds"], defer=True),
+                                      plan.sorted_attr(fkey, batch[fattr], defer=True), self.layers[0].num_heads, self.dropout.p, self.training,
+                                      self.rng, variant=("gat2", "gat2_lite", "gat2_edge").index(self.variant), edge_outputs=edge_outputs, **kw)
+        if outs[4].numel():      # the fused fragment tail also produced the readout (never for gat2_edge): pooled() below hands it out
+            # (with the versions of both tensors at this point: an in-place edit of either -- a mask, an attribution hook --
+            # between the encoder and pooled() must not be answered with the readout of the unedited rows)
+            outs[0]._fragnet_readout = (outs[1], outs[4], outs[0]._version, outs[1]._version)
+        return outs
+
+    def _levels(self, batch, plan):
+        """Level by level (gat2.py:381-442, gat2_lite, gat2_edge.py:198-236): (atoms, fragments, bonds, fragment bonds), of which
+        gat2_lite and gat2_edge have no fourth, and the attention sums of the last layer that returns any (None: no layer does).
+        One dropout draw per travelling tensor and layer, in this order."""
+        p, train, edge = self.dropout.p, self.training, self.variant == "gat2_edge"
         # batch["x_frags"] is dead in the reference too: every layer overwrites it with the atom->fragment
         # sum before first use (gat2.py:234); its dropout mask is drawn and discarded there (gat2.py:397).
-        bond_nodes, fbond_nodes = batch["node_features_bonds"], batch["node_features_fbonds"]
-        x_frags = None
+        x = (ops.dropout_act(batch["x_atoms"], p, train, False, self.rng), None, batch["node_features_bonds"],
+             None if edge else batch["node_features_fbonds"])
+        attn, n = None, 3 if edge else 4
         for layer in self.layers:
-            x_atoms, x_frags, bond_nodes, fbond_nodes = layer.run(
-                x_atoms, bond_nodes, fbond_nodes, batch["edge_attr_bonds"], batch["edge_attr_fbonds"], plan)[:4]
-            x_atoms = ops.dropout_act(x_atoms, p, train, True, self.rng)
-            x_frags = ops.dropout_act(x_frags, p, train, True, self.rng)
-            bond_nodes = ops.dropout_act(bond_nodes, p, train, True, self.rng)
-            if not lite:
-                fbond_nodes = ops.dropout_act(fbond_nodes, p, train, True, self.rng)
-        return x_atoms, x_frags, bond_nodes, (None if lite else fbond_nodes)
+            if edge:
+                r = layer.run(x[0], x[2], batch["edge_attr_bonds"], batch["cnx_attr"], plan)
+            else:
+                r = layer.run(x[0], x[2], x[3], batch["edge_attr_bonds"], batch["edge_attr_fbonds"], plan)
+            attn = r[n:] if len(r) > n else attn
+            x = tuple(None if t is None else ops.dropout_act(t, p, train, True, self.rng) for t in r[:n]) + (None,) * (4 - n)
+        return x, attn
 
-
-    def _forward_masked(self, batch, plan, row_masks, edge_outputs):
-        """A batch that carries row masks (MASK_KEYS): one masked evaluation pass of the engine.  There is no per-level form of it."""
-        if self.variant != "gat2":
-            raise ValueError(f"row masks ({', '.join(MASK_KEYS)}): model_version {self.variant!r} has no masks (gat2 only)")
-        if not self.use_engine or any(l.return_attentions or l.bond_mask is not None or l.frag_bond_mask is not None
-                                      or l.atom_mask_individual is not None for l in self.layers):
-            raise ValueError("row masks in the batch run on the engine only: not with use_engine=False, return_attentions or the "
-                             "per-layer scalar mask attributes")
-        outs = engine.encoder_forward(self.layers, plan, batch["x_atoms"], batch["node_features_bonds"],
-                                      batch["node_features_fbonds"], plan.sorted_attr("bond", batch["edge_attr_bonds"], defer=True),
-                                      plan.sorted_attr("fbond", batch["edge_attr_fbonds"], defer=True), self.layers[0].num_heads,
-                                      self.dropout.p, self.training, self.rng, variant=0, edge_outputs=edge_outputs, row_masks=row_masks)
-        if outs[4].numel():
-            outs[0]._fragnet_readout = (outs[1], outs[4], outs[0]._version, outs[1]._version)
-        return outs[:4]
+    def forward(self, batch, edge_outputs: bool = True):
+        """Plan, route, one of two calls (``route``: the engine's plain, gated or masked pass, or level by level).
+        ``edge_outputs=False`` (what the finetune models pass: their heads pool atoms and fragments only, gat2.py:816-826): the engine does
+        not store the last layer's activated bond / fragment-bond rows; the third and fourth result are then empty tensors."""
+        plan = plan_for(batch)
+        route = self.route(batch)
+        if self.variant != "gat2_edge":      # (what the layers' ``run`` reads: set where a forward happens, not by the query)
+            for layer in self.layers:
+                layer.lite = self.variant == "gat2_lite"
+        if route == "levels":
+            return self._levels(batch, plan)[0]
+        outs = self._engine(batch, plan, edge_outputs, row_masks=batch_row_masks(batch), keep_atoms=batch.get(KEEP_KEY))
+        return outs[:4] if self.variant == "gat2" else (outs[0], outs[1], outs[2], None)
 
 
 KEEP_KEY = "keep_atoms"       # optional batch key: uint8 [N], 1 = keep, 0 = this row of x_atoms reads as zero (masked-atom pretraining)

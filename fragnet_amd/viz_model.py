@@ -11,10 +11,11 @@ construction order (= RNG order), return tuples and state-dict keys are the refe
 counts a first, ``num_layer - 2`` inner and a last layer (``num_layer=1`` builds two).
 
 The four attention tensors are the LAST layer's ``scatter_add(attn_probs, source)`` (gat2.py:219, 312, 165, 268): per node of a
-level and head, the attention its out-edges receive.  In ``eval()`` mode, with no gradient required, the whole model is ONE engine
-pass (``engine.encoder_forward(..., attn_readout=True)`` -> fn_encoder_forward_attn: the plain evaluation pass plus one launch).
-In training mode, with a gradient required, with ``use_engine=False`` or with a per-layer mask attribute set, the encoder runs level
-by level (the route ``return_attentions`` always took); both routes return the same tensors.
+level and head, the attention its out-edges receive.  ``FragNet.route(batch, attn=True)`` decides the way: in ``eval()`` mode, with no
+gradient required, the whole model is ONE engine pass ("engine-attn": ``FragNet._engine(..., attn_readout=True)`` ->
+fn_encoder_forward_attn, the plain evaluation pass plus one launch).  In training mode, with a gradient required, with
+``use_engine=False`` or with a per-layer mask attribute set, the encoder runs level by level ("levels": ``FragNet._levels``, the route
+``return_attentions`` always took); both routes return the same tensors.
 
 SHAPE CONTRACT.  Every attention tensor here is ``[n, num_heads]`` with a row for EVERY node of its level: atoms ``[N, H]``,
 fragments ``[F, H]``, directed bonds ``[E, H]``, directed fragment connections ``[EF, H]``.  The reference's ``scatter_add`` is
@@ -24,11 +25,10 @@ of the tensor returned here, and the rows beyond it are exactly zero.
 """
 from __future__ import annotations
 
-import torch
 import torch.nn as nn
 
-from . import engine, ops
-from .model import FragNet, FragNetLayerA, FTHead1, FTHead2, FTHead3, FTHead4, PretrainTask, batch_row_masks, pooled
+from . import ops
+from .model import FragNet, FragNetLayerA, FTHead1, FTHead2, FTHead3, FTHead4, PretrainTask, pooled
 from .plan import LIVE_MOLS_KEY, plan_for
 
 
@@ -56,43 +56,17 @@ class FragNetViz(FragNet):
                                          edge_out=emb_dim, fedge_in=emb_dim, fbond_edge_in=fbond_edge_in, num_heads=num_heads,
                                          return_attentions=True))
 
-    def _engine_route(self, batch) -> bool:
-        """One engine pass: evaluation, nothing to differentiate, only the last layer reads attentions out, no mask of either kind."""
-        if not self.use_engine or self.training or batch_row_masks(batch) is not None:
-            return False
-        if any(l.bond_mask is not None or l.frag_bond_mask is not None or l.atom_mask_individual is not None for l in self.layers):
-            return False
-        if any(l.return_attentions for l in self.layers[:-1]) or not self.layers[-1].return_attentions:
-            return False
-        return not (torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()))
-
     def forward(self, batch):
         plan = plan_for(batch)
-        if self._engine_route(batch):
-            outs = engine.encoder_forward(self.layers, plan, batch["x_atoms"], batch["node_features_bonds"], batch["node_features_fbonds"],
-                                          plan.sorted_attr("bond", batch["edge_attr_bonds"], defer=True),
-                                          plan.sorted_attr("fbond", batch["edge_attr_fbonds"], defer=True), self.layers[0].num_heads,
-                                          self.dropout.p, False, self.rng, variant=0, edge_outputs=True, attn_readout=True)
-            if outs[4].numel():      # the fused fragment tail also produced the readout: model.pooled() hands it out
-                outs[0]._fragnet_readout = (outs[1], outs[4], outs[0]._version, outs[1]._version)
+        if self.route(batch, attn=True) == "engine-attn":
+            outs = self._engine(batch, plan, attn_readout=True)
             return outs[:4] + outs[5:]
-        if batch_row_masks(batch) is not None:
-            raise ValueError("row masks in the batch run on the engine's masked pass, which has no attention read-out")
-        p, train = self.dropout.p, self.training
-        x_atoms = ops.dropout_act(batch["x_atoms"], p, train, False, self.rng)
-        bond_nodes, fbond_nodes, x_frags, attn = batch["node_features_bonds"], batch["node_features_fbonds"], None, None
         for layer in self.layers:
             layer.lite = False
-            r = layer.run(x_atoms, bond_nodes, fbond_nodes, batch["edge_attr_bonds"], batch["edge_attr_fbonds"], plan)
-            x_atoms, x_frags, bond_nodes, fbond_nodes = r[:4]
-            attn = r[4:] if len(r) == 8 else attn          # (the last layer that reads them out: the last layer)
-            x_atoms = ops.dropout_act(x_atoms, p, train, True, self.rng)
-            x_frags = ops.dropout_act(x_frags, p, train, True, self.rng)
-            bond_nodes = ops.dropout_act(bond_nodes, p, train, True, self.rng)
-            fbond_nodes = ops.dropout_act(fbond_nodes, p, train, True, self.rng)
+        x, attn = self._levels(batch, plan)
         if attn is None:
             raise ValueError("FragNetViz: no layer has return_attentions set")
-        return (x_atoms, x_frags, bond_nodes, fbond_nodes) + tuple(attn)
+        return x + tuple(attn)
 
 
 def _make_head(fthead, n_classes, h1, h2, h3, h4, drop_ratio, act):

@@ -232,8 +232,8 @@ def _raw_pass(model, batch, entry, keep=None, variant=0, no_backward=True, gated
     params = [p.detach() for layer in layers for p in engine.layer_param_list(layer)]
     cos = plan.sorted_attr("bond", b["edge_attr_bonds"], defer=True)
     fattr = plan.sorted_attr("fbond", b["edge_attr_fbonds"], defer=True)
-    e = engine._describe(plan, b["x_atoms"], b["node_features_bonds"], b["node_features_fbonds"], cos, fattr, params, len(layers),
-                         layers[0].num_heads, 0.0, False, 0, 0, None, variant, no_backward)
+    e = engine._describe((b["x_atoms"], b["node_features_bonds"], b["node_features_fbonds"]), params,
+                         engine._Spec(plan, cos, fattr, len(layers), layers[0].num_heads, variant=variant, no_backward=no_backward))
     size = lib.fn_encoder_keep_ws_floats(C.byref(e)) if gated_ws else lib.fn_encoder_ws_floats(C.byref(e))
     ws = torch.empty(size, dtype=torch.float32, device=DEV)
     e.ws, e.ws_floats = ws.data_ptr(), ws.numel()

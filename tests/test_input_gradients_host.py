@@ -156,6 +156,54 @@ def test_engine_refuses_what_its_backward_cannot_serve():
                 engine.encoder_forward(layers, None, *tables, None, None, 4, p, training, None, variant=variant)
 
 
+def test_engine_refusal_ladder_comes_before_the_plan():
+    """Every refusal of encoder_forward's argument ladder, in its order, with CPU tensors and ``plan=None``: none of them touches the
+    plan, the library or the GPU."""
+    from fragnet_amd import engine
+    from fragnet_amd import model as M
+    gat2, edge = _tiny().pretrain.layers, _tiny(M.FragNetFineTuneEdge).pretrain.layers
+    lite = _tiny(M.FragNetFineTuneLite).pretrain.layers
+    for layers in (gat2, edge, lite):
+        for p in layers.parameters():
+            p.requires_grad_(False)
+    plain = (torch.zeros(3, 167), torch.zeros(3, 17), torch.zeros(3, 6))
+    wants = (torch.zeros(3, 167, requires_grad=True), torch.zeros(3, 17), torch.zeros(3, 6))
+    keep, mask = torch.ones(3, dtype=torch.uint8), (torch.zeros(3, dtype=torch.uint8), None, None)
+    live = _tiny().pretrain.layers           # parameters that require a gradient
+    rows = [
+        # (layers, tables, training, drop_p, keywords, exception, a word of its message)
+        (gat2, plain, False, 0.0, dict(row_masks=(None, None)), ValueError, "a triple"),
+        (gat2, plain, False, 0.0, dict(keep_atoms=keep, attn_readout=True), ValueError, "does not combine with row masks or the attention read-out"),
+        (gat2, plain, False, 0.0, dict(keep_atoms=keep, row_masks=mask), ValueError, "does not combine with row masks or the attention read-out"),
+        (lite, plain, False, 0.0, dict(keep_atoms=keep, variant=1), ValueError, "exists for model_version gat2"),
+        (gat2, plain, False, 0.0, dict(keep_atoms=keep.float()), ValueError, "contiguous uint8 CUDA tensor of 3 rows"),
+        (gat2, plain, False, 0.0, dict(keep_atoms=keep), ValueError, "contiguous uint8 CUDA tensor of 3 rows"),      # a CPU tensor
+        (gat2, plain, False, 0.0, dict(attn_readout=True, row_masks=mask), ValueError, "no attention read-out of a masked pass"),
+        (lite, plain, False, 0.0, dict(attn_readout=True, variant=1), ValueError, "read-out exists for model_version gat2"),
+        (gat2, plain, True, 0.0, dict(attn_readout=True), RuntimeError, "attn_readout: a read-out pass is an evaluation pass"),
+        (gat2, wants, False, 0.0, dict(attn_readout=True), RuntimeError, "attn_readout: the read-out pass has no backward"),
+        (live, plain, False, 0.0, dict(attn_readout=True), RuntimeError, "attn_readout: the read-out pass has no backward"),
+        (gat2, plain, True, 0.0, dict(row_masks=mask), RuntimeError, "row_masks: a masked pass is an evaluation pass"),
+        (gat2, wants, False, 0.0, dict(row_masks=mask), RuntimeError, "row_masks: the masked pass has no backward"),
+        (live, plain, False, 0.0, dict(row_masks=mask), RuntimeError, "row_masks: the masked pass has no backward"),
+        (edge, wants, False, 0.0, dict(variant=2), NotImplementedError, "not for gat2_edge"),
+        (gat2, wants, True, 0.1, dict(), NotImplementedError, "a training pass with dropout"),
+    ]
+    for layers, tables, training, p, kw, exc, word in rows:
+        with pytest.raises(exc, match=word):
+            engine.encoder_forward(layers, None, *tables, None, None, 4, p, training, None, **kw)
+    # keep_atoms with inputs that require a gradient: behind the tensor check, which wants a CUDA vector -- one that says it is
+    class _OnGpu(torch.Tensor):
+        is_cuda = True
+    gpu_keep = keep.as_subclass(_OnGpu)
+    with pytest.raises(NotImplementedError, match="no input gradients of a masked pass"):
+        engine.encoder_forward(gat2, None, *wants, None, None, 4, 0.0, False, None, keep_atoms=gpu_keep)
+    with torch.no_grad():                  # ... and under no_grad the same call goes on to the CPU-tensor check
+        from fragnet_amd import _lib
+        with pytest.raises(_lib.FragnetHipError):
+            engine.encoder_forward(gat2, None, *wants, None, None, 4, 0.0, False, None, keep_atoms=gpu_keep)
+
+
 # ------------------------------------------------------------------------------- the fixtures' self-checks
 @pytest.mark.parametrize("name,tables", [("input_grad_b6", ic.TABLE_KEYS), ("input_grad_lite_b6", ic.TABLE_KEYS[:2])])
 def test_gradient_fixture_self_checks(name, tables):

@@ -7,8 +7,15 @@ enqueues, with which arguments, in which order) that is meant to leave the arith
 Cases (24 synthetic molecules, profile esol, fixed Philox offset): every head count, the three model versions, 1 / 2 / 3 / 6
 layers (six layers make the deferred-reduction queue flush in mid-pass), training with and without dropout, evaluation with
 gradients and under no_grad, the static-shape padded step (padding skip, Adam rider), the masked pass, the attention read-out, the
-input-gradient call, single-fragment molecules (with and without their placeholder connection), one molecule, and the training
-step under the tuning keys that select another path of the host code."""
+input-gradient call, single-fragment molecules (with and without their placeholder connection), one molecule, the training
+step under the tuning keys that select another path of the host code, and the ways of the encoder's Python front: the input gate
+(a batch with keep_atoms, and FragNetPreTrainMasked2), the level-by-level route of the three model versions (use_engine=False),
+of FragNetFineTuneViz (training mode; evaluation with use_engine=False) and of a plain model with return_attentions on a layer.
+
+    python tools/engine_bits.py --calls > calls.txt
+
+prints, per case, the fn_* entry points of the library in call order instead (runs of one name as ``name xN``): the host code's
+own trace, recorded by wrapping the ctypes functions of ``_lib.load()`` in this process."""
 import hashlib
 import os
 import sys
@@ -43,9 +50,36 @@ def digest(items):
     return h.hexdigest()
 
 
+CALLS = None        # --calls: the names of the library calls since the last report
+
+
+def record_calls():
+    global CALLS
+    CALLS = []
+    lib = _lib.load()
+    for name in _lib.SIGNATURES:
+        if name == "fn_last_error":
+            continue
+
+        def counted(*a, _fn=getattr(lib, name), _name=name):
+            CALLS.append(_name)
+            return _fn(*a)
+        setattr(lib, name, counted)
+
+
 def report(name, items):
     torch.cuda.synchronize()
-    print(f"{name:34s} {digest(items)}", flush=True)
+    if CALLS is None:
+        print(f"{name:34s} {digest(items)}", flush=True)
+        return
+    runs = []
+    for c in CALLS:
+        if runs and runs[-1][0] == c:
+            runs[-1][1] += 1
+        else:
+            runs.append([c, 1])
+    print(f"{name:34s} " + " ".join(c if n == 1 else f"{c} x{n}" for c, n in runs), flush=True)
+    CALLS.clear()
 
 
 def net_for(heads=4, layers=3, drop=0.0, cls=M.FragNetFineTune, seed=0):
@@ -55,7 +89,7 @@ def net_for(heads=4, layers=3, drop=0.0, cls=M.FragNetFineTune, seed=0):
 
 
 def encoder_pass(name, net, batch, train=True, grad=True):
-    """the encoder's four outputs and, with grad, every parameter gradient of sum(mean(out^2))"""
+    """the encoder's outputs and, with grad, every parameter gradient of sum(mean(out^2)) over the first four"""
     net.train(train)
     net.zero_grad(set_to_none=True)
     net.pretrain.rng.offset = OFFSET
@@ -65,7 +99,7 @@ def encoder_pass(name, net, batch, train=True, grad=True):
         outs = net.pretrain(batch)
         items = [(f"out{i}", t) for i, t in enumerate(outs)]
         if grad:
-            sum(t.square().mean() for t in outs if t is not None and t.numel()).backward()
+            sum(t.square().mean() for t in outs[:4] if t is not None and t.numel()).backward()
             items += [(n, p.grad) for n, p in net.named_parameters()]
     report(name, items)
 
@@ -150,6 +184,41 @@ def main():
     encoder_pass("single_fragment_train", net_for(), single_fragment_batch(6, False))
     encoder_pass("single_molecule_train", net_for(drop=0.1), data.batch_to(data.collate_fn(mols[:1]), DEV))
 
+    # the encoder's Python front: the input gate, and the level-by-level routes
+    gated = dict(batch)
+    gated["keep_atoms"] = (torch.rand(batch["x_atoms"].shape[0], generator=torch.Generator().manual_seed(5)) < 0.85).to(torch.uint8).to(DEV)
+    encoder_pass("keep_train_dropout", net_for(drop=0.1), gated)
+    encoder_pass("keep_eval_no_grad", net_for(drop=0.1), gated, train=False, grad=False)
+    pt_mols = synth.synth_molecules(12, seed=19, profile="esol", pretrain_targets=True)
+    pt_batch = data.batch_to(data.collate_fn_pt(pt_mols), DEV)
+    for train in (True, False):
+        torch.manual_seed(0)
+        pm = M.FragNetPreTrainMasked2(num_layer=2, drop_ratio=0.1, edge_features=17).to(DEV).train(train)
+        pm.pretrain.rng.offset = OFFSET
+        b = dict(pt_batch)
+        b.pop("_fragnet_plan", None)
+        with torch.set_grad_enabled(train):
+            outs = pm(b)
+            items = [(f"out{i}", t) for i, t in enumerate(outs)] + [("keep", pm.last_keep)]
+            if train:
+                sum(t.square().mean() for t in outs if t is not None).backward()
+                items += [(n, p.grad) for n, p in pm.named_parameters()]
+        report(f"masked2_{'train_dropout' if train else 'eval'}", items)
+    for label, cls in (("gat2", M.FragNetFineTune), ("gat2_lite", M.FragNetFineTuneLite), ("gat2_edge", M.FragNetFineTuneEdge)):
+        lv = net_for(drop=0.1, cls=cls)
+        lv.pretrain.use_engine = False
+        # (the synthetic cnx_attr is 6 wide; the per-level gat2_edge layer checks its Linear(8 -> 128) against the attribute's width)
+        wide = dict(batch, cnx_attr=torch.nn.functional.pad(batch["cnx_attr"], (0, 2))) if label == "gat2_edge" else batch
+        encoder_pass(f"levels_{label}_train_dropout", lv, wide)
+    viz.pretrain.rng.seed = 5
+    encoder_pass("viz_levels_train_dropout", viz, batch)
+    viz.use_engine = False
+    encoder_pass("viz_levels_eval_no_grad", viz, batch, train=False, grad=False)
+    viz.use_engine = True
+    one = net_for(drop=0.1)
+    one.pretrain.layers[1].return_attentions = True
+    encoder_pass("levels_return_attentions_layer1", one, batch)
+
     for key, value in ((22, 0), (14, 0), (7, 0), (20, 0), (20, 2), (33, 0)):
         try:
             _lib.call("fn_set_tuning", key, value)
@@ -166,4 +235,6 @@ def main():
 
 
 if __name__ == "__main__":
+    if "--calls" in sys.argv[1:]:
+        record_calls()
     main()
