@@ -13,6 +13,8 @@ from typing import Dict, List
 
 import numpy as np
 
+from .attribution import _as_store, _Result, engine_device, evaluation, offsets_of, store_batches
+
 LEVELS = ("atoms", "bonds", "frags", "fbonds")
 LEVEL_SPACE = {"atoms": "atom", "bonds": "edge", "frags": "frag", "fbonds": "fedge"}       # rows of plan.SPACES / CollatedBatch.offsets
 
@@ -32,7 +34,7 @@ def split_rows(rows: np.ndarray, offsets) -> List[np.ndarray]:
     return [rows[offsets[i]: offsets[i + 1]] for i in range(offsets.size - 1)]
 
 
-class AttentionWeights:
+class AttentionWeights(_Result):
     """Result of ``attention_weights``: ``pred [n_mols, n_classes]`` and, per level in ``LEVELS``, the flat rows ``[total, H]`` with
     the per-molecule offsets ``[n_mols + 1]``.  ``result[i]`` is molecule i as a dict: ``pred [n_classes]``, ``atoms [n_atoms, H]``,
     ``bonds [2 n_bonds, H]``, ``frags [n_frags, H]``, ``fbonds [2 n_cnx, H]``, the head sums the app draws ``atom_weights``
@@ -41,13 +43,8 @@ class AttentionWeights:
     def __init__(self, pred: np.ndarray, rows: Dict[str, np.ndarray], offsets: Dict[str, np.ndarray]):
         self.pred, self.rows, self.offsets = pred, rows, offsets
 
-    def __len__(self):
-        return self.pred.shape[0]
-
     def __getitem__(self, i: int) -> dict:
-        if not -len(self) <= i < len(self):
-            raise IndexError(i)
-        i %= len(self)
+        i = self._index(i)
         out = {"pred": self.pred[i]}
         for k in LEVELS:
             out[k] = self.rows[k][int(self.offsets[k][i]): int(self.offsets[k][i + 1])]
@@ -68,7 +65,7 @@ class AttentionWeights:
         out["frag_weights"] = self.rows["frags"].sum(1)
         per_mol = [bond_weights(r) for r in split_rows(self.rows["bonds"], self.offsets["bonds"])]
         out["bond_weights"] = np.concatenate(per_mol) if per_mol else np.zeros(0, np.float32)
-        out["bond_weights_offsets"] = np.concatenate([[0], np.cumsum([len(r) for r in per_mol])]).astype(np.int64)
+        out["bond_weights_offsets"] = offsets_of([len(r) for r in per_mol])
         return out
 
 
@@ -80,8 +77,7 @@ def assemble(preds: List[np.ndarray], tensors: List[Dict[str, np.ndarray]], offs
         for t, o in zip(tensors, offsets):
             split_rows(t[k], o[k])            # validates
         rows[k] = np.concatenate([t[k] for t in tensors], 0)
-        counts = np.concatenate([np.diff(np.asarray(o[k], dtype=np.int64)) for o in offsets])
-        offs[k] = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+        offs[k] = offsets_of(np.concatenate([np.diff(np.asarray(o[k], dtype=np.int64)) for o in offsets]))
     return AttentionWeights(np.concatenate(preds, 0), rows, offs)
 
 
@@ -89,38 +85,25 @@ def attention_weights(model, source, batch_size: int = 512) -> AttentionWeights:
     """Attention weights of every molecule of ``source`` (a ``FlatMolStore`` or a list of ``MolRecord``) under ``model``: a
     ``viz_model.FragNetFineTuneViz`` (or ``FragNetPreTrainViz``) on the GPU.  One read-out pass per batch of ``batch_size`` molecules."""
     import torch
-    from . import _lib
-    from .attribution import _as_store
     from .plan import SPACES
     if batch_size < 1:
         raise ValueError("batch_size must be positive")
     enc = getattr(model, "pretrain", None)
     if enc is None or not getattr(enc.layers[-1], "return_attentions", False):
         raise ValueError("attention_weights: a Viz model (viz_model.FragNetFineTuneViz / FragNetPreTrainViz), whose last layer reads the attentions out")
-    device = next(model.parameters()).device
-    if device.type != "cuda":
-        raise _lib.FragnetHipError("attention_weights runs on the GPU engine; there is no CPU fallback")
-    store = _as_store(source, device)
-    n = len(store)
+    store = _as_store(source, engine_device(model, "attention_weights"))
     preds, tensors, offsets = [], [], []
-    was_training = model.training
-    model.eval()
-    try:
-        with torch.no_grad():
-            for b in range(0, n, batch_size):
-                idx = np.arange(b, min(n, b + batch_size))
-                batch = store.collate(idx)
-                out = model(batch)
-                if len(out) != 5:
-                    raise ValueError("attention_weights: the model must return (prediction, attn_atoms, attn_frags, attn_bonds, attn_fbonds)")
-                pred, attn = out[0], dict(zip(("atoms", "frags", "bonds", "fbonds"), out[1:]))
-                preds.append(pred.reshape(len(idx), -1).float())
-                tensors.append({k: attn[k].float() for k in LEVELS})
-                offsets.append(batch.offsets)
-            # (copied to the host once every batch is queued: no synchronisation between the passes)
-            preds = [t.cpu().numpy() for t in preds]
-            tensors = [{k: v.cpu().numpy() for k, v in t.items()} for t in tensors]
-            offsets = [{k: off[SPACES.index(LEVEL_SPACE[k])] for k in LEVELS} for off in (o.cpu().numpy() for o in offsets)]
-    finally:
-        model.train(was_training)
+    with evaluation(model), torch.no_grad():
+        for b, e, batch in store_batches(store, batch_size):
+            out = model(batch)
+            if len(out) != 5:
+                raise ValueError("attention_weights: the model must return (prediction, attn_atoms, attn_frags, attn_bonds, attn_fbonds)")
+            pred, attn = out[0], dict(zip(("atoms", "frags", "bonds", "fbonds"), out[1:]))
+            preds.append(pred.reshape(e - b, -1).float())
+            tensors.append({k: attn[k].float() for k in LEVELS})
+            offsets.append(batch.offsets)
+        # (copied to the host once every batch is queued: no synchronisation between the passes)
+        preds = [t.cpu().numpy() for t in preds]
+        tensors = [{k: v.cpu().numpy() for k, v in t.items()} for t in tensors]
+        offsets = [{k: off[SPACES.index(LEVEL_SPACE[k])] for k in LEVELS} for off in (o.cpu().numpy() for o in offsets)]
     return assemble(preds, tensors, offsets)

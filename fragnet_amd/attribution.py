@@ -13,6 +13,7 @@ Replica order and indices are viz.py's: atoms ``0 .. n-1``; bonds by their first
 """
 from __future__ import annotations
 
+from contextlib import contextmanager
 from typing import Dict, List, Sequence, Tuple
 
 import numpy as np
@@ -92,34 +93,142 @@ def plan_chunks(rows_per_mol, replicas_per_mol, max_rows: int) -> List[List[Tupl
     return chunks
 
 
-class Attribution:
+def chunk_replicas(chunk) -> Tuple[np.ndarray, np.ndarray]:
+    """``(molecule of every replica, its number among its molecule's replicas)``, int64, of one chunk of ``plan_chunks``."""
+    mols = np.concatenate([np.full(r1 - r0, i, dtype=np.int64) for i, r0, r1 in chunk])
+    return mols, np.concatenate([np.arange(r0, r1, dtype=np.int64) for _, r0, r1 in chunk])
+
+
+# ====================================== what the drivers of this module, gradient_attribution.py, pair_attribution.py and attention.py share
+def offsets_of(counts) -> np.ndarray:
+    """int64 ``[len(counts) + 1]``: 0, then the running sums of ``counts`` -- entry i is where item i's rows start in a flat array."""
+    counts = np.asarray(counts, dtype=np.int64).reshape(-1)
+    out = np.zeros(counts.shape[0] + 1, dtype=np.int64)
+    np.cumsum(counts, out=out[1:])
+    return out
+
+
+def batch_ranges(n: int, batch_size: int) -> List[Tuple[int, int]]:
+    """``(first, end)`` of the batches of ``batch_size`` consecutive items that cover ``0 .. n``, the last one shorter."""
+    return [(b, min(n, b + batch_size)) for b in range(0, n, batch_size)]
+
+
+def store_batches(store, batch_size: int):
+    """``(first, end, collated batch)`` per batch of ``batch_size`` consecutive molecules of a ``FlatMolStore``, collated when reached."""
+    for b, e in batch_ranges(len(store), batch_size):
+        yield b, e, store.collate(np.arange(b, e))
+
+
+@contextmanager
+def evaluation(model):
+    """``model`` in ``eval()`` mode inside the block, back in the mode it came in on the way out, through an exception too.  Gradient
+    mode is the caller's: input_gradients and the chunk loop of integrated_gradients differentiate inside this block."""
+    mode = model.training
+    model.eval()
+    try:
+        yield model
+    finally:
+        model.train(mode)
+
+
+def engine_device(model, who: str):
+    """The device of ``model``'s parameters if it is a GPU; else the drivers' refusal in ``who``'s name.  (pair_attribution's
+    cell_line_attributions words its own: it runs kernels, not the engine, and on its tower's device.)"""
+    device = next(model.parameters()).device
+    if device.type != "cuda":
+        from . import _lib
+        raise _lib.FragnetHipError(f"{who} runs on the GPU engine; there is no CPU fallback")
+    return device
+
+
+def row_vector(v, width: int, device, prefix: str, unit: str):
+    """``v`` -- a 1-d array or tensor of ``width`` real numbers -- as a contiguous float32 tensor on ``device``; the refusals start with
+    ``prefix`` and count the entries in ``unit``."""
+    import torch
+    v = v.detach() if torch.is_tensor(v) else torch.as_tensor(np.asarray(v))
+    if v.dim() != 1 or v.shape[0] != width:
+        raise ValueError(f"{prefix}: a row vector of {width} {unit} (got shape {tuple(v.shape)})")
+    if not (v.dtype.is_floating_point or v.dtype in (torch.int32, torch.int64, torch.uint8, torch.bool)):
+        raise ValueError(f"{prefix}: a real-valued vector (got {v.dtype})")
+    return v.to(device=device, dtype=torch.float32).contiguous()
+
+
+class PackedUpload:
+    """Arrays of several dtypes that reach the device in ONE copy.  ``parts``: ``(numpy dtype, count)`` each; ``host`` holds a numpy view
+    per part into one int64 buffer, every part on an 8-byte boundary, for the caller to fill in place; ``to(device)`` copies the buffer
+    once and returns the matching views of the device tensor."""
+
+    def __init__(self, parts):
+        self._counts, self._first = [int(count) for _, count in parts], [0]
+        for dt, count in parts:          # a part's first int64 word (plain ints: this runs once per chunk of fragment_shapley)
+            self._first.append(self._first[-1] + (np.dtype(dt).itemsize * int(count) + 7) // 8)
+        self.buffer = np.empty(self._first[-1], dtype=np.int64)
+        self.host = [self._part(self.buffer, k, np.dtype(dt)) for k, (dt, _) in enumerate(parts)]
+
+    def _part(self, buffer, k, dtype):
+        return buffer[self._first[k]: self._first[k + 1]].view(dtype)[: self._counts[k]]
+
+    def to(self, device):
+        import torch
+        dev = torch.from_numpy(self.buffer).to(device)
+        return [self._part(dev, k, torch.from_numpy(h).dtype) for k, h in enumerate(self.host)]
+
+
+def kept_on_store(store, name: str, derive):
+    """``derive()``, computed at the first call and kept on the ``FlatMolStore`` as attribute ``name``, like its host-side lengths and
+    offsets (the store is immutable)."""
+    hit = getattr(store, name, None)
+    if hit is None:
+        hit = derive()
+        setattr(store, name, hit)
+    return hit
+
+
+class _Result:
+    """What the result classes share: ``len(result)`` is the first axis of the array that ``_per_item`` names, and ``_index(i)`` is
+    ``i`` checked against it, a negative one counted from the end."""
+    _per_item = "pred"
+
+    def __len__(self):
+        return getattr(self, self._per_item).shape[0]
+
+    def _index(self, i: int) -> int:
+        if not -len(self) <= i < len(self):
+            raise IndexError(i)
+        return i % len(self)
+
+
+class _KindTables(_Result):
+    """A result with ``kinds`` and per kind ``tables[kind] = {"offsets": [n + 1], name: [total, ...], ...}``: flat arrays, molecule i's rows
+    at ``offsets[i] : offsets[i + 1]`` (``_kind_rows(i)``: per kind those rows of every array of its table)."""
+
+    def _kind_rows(self, i: int) -> Dict[str, Dict[str, np.ndarray]]:
+        out = {}
+        for k in self.kinds:
+            t = self.tables[k]
+            lo, hi = int(t["offsets"][i]), int(t["offsets"][i + 1])
+            out[k] = {name: v[lo:hi] for name, v in t.items() if name != "offsets"}
+        return out
+
+    def _kind_arrays(self) -> Dict[str, np.ndarray]:
+        return {f"{k}_{name}": v for k in self.kinds for name, v in self.tables[k].items()}
+
+
+class Attribution(_KindTables):
     """Result of ``leave_one_out``: flat arrays plus per-molecule offsets (``arrays()`` is what the command-line script writes);
     ``result[i]`` is molecule i as a dict ``{"pred_no_mask": [n_classes], kind: {"index": [count], "pred_mask": [count,
     n_classes], "attr": [count, n_classes]}}`` -- the reference's DataFrame columns as arrays."""
+    _per_item = "pred_no_mask"
 
     def __init__(self, pred_no_mask: np.ndarray, kinds: Tuple[str, ...], tables: Dict[str, Dict[str, np.ndarray]]):
         self.pred_no_mask, self.kinds, self.tables = pred_no_mask, kinds, tables
 
-    def __len__(self):
-        return self.pred_no_mask.shape[0]
-
     def __getitem__(self, i: int) -> dict:
-        if not -len(self) <= i < len(self):
-            raise IndexError(i)
-        i %= len(self)
-        out = {"pred_no_mask": self.pred_no_mask[i]}
-        for k in self.kinds:
-            t = self.tables[k]
-            lo, hi = int(t["offsets"][i]), int(t["offsets"][i + 1])
-            out[k] = {"index": t["index"][lo:hi], "pred_mask": t["pred_mask"][lo:hi], "attr": t["attr"][lo:hi]}
-        return out
+        i = self._index(i)
+        return {"pred_no_mask": self.pred_no_mask[i], **self._kind_rows(i)}
 
     def arrays(self) -> Dict[str, np.ndarray]:
-        out = {"pred_no_mask": self.pred_no_mask, "kinds": np.array(self.kinds)}
-        for k in self.kinds:
-            for name, v in self.tables[k].items():
-                out[f"{k}_{name}"] = v
-        return out
+        return {"pred_no_mask": self.pred_no_mask, "kinds": np.array(self.kinds), **self._kind_arrays()}
 
 
 def _as_store(source, device):
@@ -165,53 +274,42 @@ def leave_one_out(model, source, kinds=KIND_ORDER, max_rows: int = DEFAULT_MAX_R
     enc = getattr(model, "pretrain", None)
     if enc is None or getattr(enc, "variant", None) != "gat2":
         raise ValueError(f"leave_one_out: masks exist for model_version gat2 (got {getattr(enc, 'variant', type(model).__name__)!r})")
-    device = next(model.parameters()).device
-    if device.type != "cuda":
-        from . import _lib
-        raise _lib.FragnetHipError("leave_one_out runs on the GPU engine; there is no CPU fallback")
+    device = engine_device(model, "leave_one_out")
     store = _as_store(source, device)
     n = len(store)
     lens = store._host_lengths()
     table = replica_table(lens["atom"], lens["edge"], lens["fedge"], kinds)
     counts = np.array([t.shape[0] for t in table], dtype=np.int64)
     chunks = plan_chunks(lens["atom"] + lens["edge"], counts, max_rows)
-    first = np.concatenate([[0], np.cumsum(counts)])
+    first = offsets_of(counts)
     total = int(first[-1])
-    was_training = model.training
-    model.eval()
-    try:
-        with torch.no_grad():
-            base = []
-            for b in range(0, n, batch_size):
-                base.append(model(store.collate(np.arange(b, min(n, b + batch_size)))).reshape(min(n, b + batch_size) - b, -1).float())
-            base = torch.cat(base, 0)
-            n_classes = base.shape[1]
-            pred_mask = torch.empty((total, n_classes), dtype=torch.float32, device=device)
-            attr = torch.empty_like(pred_mask)
-            status = torch.zeros(1, dtype=torch.int32, device=device)
-            for chunk in chunks:
-                mols = np.concatenate([np.full(r1 - r0, i, dtype=np.int64) for i, r0, r1 in chunk])
-                reps = np.concatenate([local_index(table[i][r0:r1]) for i, r0, r1 in chunk], 0)
-                slots = torch.from_numpy(np.concatenate([np.arange(first[i] + r0, first[i] + r1) for i, r0, r1 in chunk])).to(device)
-                batch = store.collate(mols)
-                masks = build_row_masks(batch, torch.from_numpy(np.ascontiguousarray(reps)).to(device), status)
-                for key, m in zip(MASK_KEYS, masks):
-                    batch[key] = m
-                pm = model(batch).reshape(len(mols), -1).float()
-                pred_mask[slots] = pm
-                attr[slots] = base[torch.from_numpy(mols).to(device)] - pm
-            if int(status.item()):
-                raise IndexError("leave_one_out: a replica index lies outside its molecule (FN_STATUS_BAD_REPLICA)")
-            base_h, pred_h, attr_h = base.cpu().numpy(), pred_mask.cpu().numpy(), attr.cpu().numpy()
-    finally:
-        model.train(was_training)
     flat = np.concatenate(table, 0) if total else np.zeros((0, 2), np.int32)
+    flat_local = local_index(flat)
+    with evaluation(model), torch.no_grad():
+        base = torch.cat([model(batch).reshape(e - b, -1).float() for b, e, batch in store_batches(store, batch_size)], 0)
+        n_classes = base.shape[1]
+        pred_mask = torch.empty((total, n_classes), dtype=torch.float32, device=device)
+        attr = torch.empty_like(pred_mask)
+        status = torch.zeros(1, dtype=torch.int32, device=device)
+        for chunk in chunks:
+            mols, rep = chunk_replicas(chunk)
+            slots_h = first[mols] + rep          # the replicas' rows of the flat table, and of the result
+            slots = torch.from_numpy(slots_h).to(device)
+            batch = store.collate(mols)
+            masks = build_row_masks(batch, torch.from_numpy(flat_local[slots_h]).to(device), status)
+            for key, m in zip(MASK_KEYS, masks):
+                batch[key] = m
+            pm = model(batch).reshape(len(mols), -1).float()
+            pred_mask[slots] = pm
+            attr[slots] = base[torch.from_numpy(mols).to(device)] - pm
+        if int(status.item()):
+            raise IndexError("leave_one_out: a replica index lies outside its molecule (FN_STATUS_BAD_REPLICA)")
+        base_h, pred_h, attr_h = base.cpu().numpy(), pred_mask.cpu().numpy(), attr.cpu().numpy()
     mol_of = np.repeat(np.arange(n), counts)
     tables = {}
     for k in kinds:
         sel = flat[:, 0] == KINDS[k]
-        per_mol = np.bincount(mol_of[sel], minlength=n)
-        tables[k] = {"offsets": np.concatenate([[0], np.cumsum(per_mol)]).astype(np.int64), "index": flat[sel, 1].astype(np.int32),
+        tables[k] = {"offsets": offsets_of(np.bincount(mol_of[sel], minlength=n)), "index": flat[sel, 1].astype(np.int32),
                      "pred_mask": pred_h[sel], "attr": attr_h[sel]}
     return Attribution(base_h, kinds, tables)
 
@@ -263,7 +361,7 @@ def group_table(atom_groups) -> Tuple[List[np.ndarray], List[np.ndarray]]:
     arrays = [_group_array(g, f"groups[{i}]") for i, g in enumerate(atom_groups)]
     if not arrays:
         return [], []
-    atom_off = np.concatenate([[0], np.cumsum([g.shape[0] for g in arrays])]).astype(np.int64)
+    atom_off = offsets_of([g.shape[0] for g in arrays])
     _, ids, sizes, counts = flat_group_table(np.concatenate(arrays) if arrays else np.zeros(0, np.int64), atom_off)
     cut = np.cumsum(counts)[:-1]
     return np.split(ids, cut), np.split(sizes, cut)
@@ -283,33 +381,35 @@ def _flat_groups(groups, n_atoms) -> np.ndarray:
     return np.concatenate(arrays).astype(np.int64)
 
 
-class FragmentAttribution:
+class _GroupResult(_Result):
+    """A result per group of atoms.  Rows ``offsets[i] : offsets[i + 1]`` of ``group`` (ids, ascending) and ``n_atoms`` are molecule
+    i's groups; ``atom_group`` / ``atom_offsets``: every atom's group id, flat, and the first atom of every molecule.  ``_per_group`` names
+    the array ``[R, C]`` that ``atom_weights`` spreads over the atoms."""
+
+    def _set_groups(self, offsets, group, n_atoms, atom_group, atom_offsets):
+        self.offsets, self.group, self.n_atoms, self.atom_group, self.atom_offsets = offsets, group, n_atoms, atom_group, atom_offsets
+
+    def atom_weights(self, i: int) -> np.ndarray:
+        """[n_atoms of molecule i, C]: every atom carries its group's attribution, an atom in no group 0 (model_attr.py:767-781)."""
+        return _spread_to_atoms(getattr(self, self._per_group), self.group, self.offsets, self.atom_group, self.atom_offsets, self._index(i))
+
+
+class FragmentAttribution(_GroupResult):
     """Result of ``fragment_contributions``.  ``result[i]`` is molecule i as ``{"pred_no_mask": [C], "group": [count] ids, "n_atoms":
     [count], "pred_mask": [count, C], "attr": [count, C]}``; ``arrays()`` the flat arrays plus per-molecule offsets that the command-line
     script writes; ``atom_weights(i)`` the reference's ``add_atom_weights``.  ``atom_group`` / ``atom_offsets``: every atom's group id,
     flat, and the first atom of every molecule."""
+    _per_item, _per_group = "pred_no_mask", "attr"
 
     def __init__(self, pred_no_mask, offsets, group, n_atoms, pred_mask, attr, atom_group, atom_offsets):
-        self.pred_no_mask, self.offsets, self.group, self.n_atoms = pred_no_mask, offsets, group, n_atoms
-        self.pred_mask, self.attr, self.atom_group, self.atom_offsets = pred_mask, attr, atom_group, atom_offsets
-
-    def __len__(self):
-        return self.pred_no_mask.shape[0]
-
-    def _index(self, i: int) -> int:
-        if not -len(self) <= i < len(self):
-            raise IndexError(i)
-        return i % len(self)
+        self._set_groups(offsets, group, n_atoms, atom_group, atom_offsets)
+        self.pred_no_mask, self.pred_mask, self.attr = pred_no_mask, pred_mask, attr
 
     def __getitem__(self, i: int) -> dict:
         i = self._index(i)
         lo, hi = int(self.offsets[i]), int(self.offsets[i + 1])
         return {"pred_no_mask": self.pred_no_mask[i], "group": self.group[lo:hi], "n_atoms": self.n_atoms[lo:hi],
                 "pred_mask": self.pred_mask[lo:hi], "attr": self.attr[lo:hi]}
-
-    def atom_weights(self, i: int) -> np.ndarray:
-        """[n_atoms of molecule i, C]: every atom carries its group's attribution, an atom in no group 0 (model_attr.py:767-781)."""
-        return _spread_to_atoms(self.attr, self.group, self.offsets, self.atom_group, self.atom_offsets, self._index(i))
 
     def arrays(self) -> Dict[str, np.ndarray]:
         return {"pred_no_mask": self.pred_no_mask, "offsets": self.offsets, "group": self.group, "n_atoms": self.n_atoms,
@@ -318,13 +418,13 @@ class FragmentAttribution:
 
 def _store_fragment_table(store):
     """(fragment map of every atom on the host, its replica table ``flat_group_table``) of a ``FlatMolStore``: derived once and kept on
-    the store, like its host-side lengths and offsets (the store is immutable)."""
+    the store (``kept_on_store``)."""
     import torch
-    hit = getattr(store, "_frag_table_cpu", None)
-    if hit is None:
+
+    def derive():
         flat = store.t["atom_id_frag_id"].to("cpu", torch.long).numpy()
-        hit = store._frag_table_cpu = (flat, flat_group_table(flat, store._host_offsets()["atom"]))
-    return hit
+        return flat, flat_group_table(flat, store._host_offsets()["atom"])
+    return kept_on_store(store, "_frag_table_cpu", derive)
 
 
 def _contribution_kind(model) -> str:
@@ -378,7 +478,7 @@ def _contribution_rows(kind, model, batch, read_out, row_mol, head_rows=None):
 
 def _group_source(who, kind, model, source, groups):
     """What the fragment-level calls share: ``(store or None, records or None, collate or None, flat group id of every atom, first atom
-    of every molecule, flat_group_table)`` of ``source`` under ``groups``; refuses a model that is not on the GPU."""
+    of every molecule, flat_group_table, the model's device)`` of ``source`` under ``groups``; refuses a model that is not on the GPU."""
     import torch
     from . import data
     from .dataset import FlatMolStore
@@ -400,21 +500,18 @@ def _group_source(who, kind, model, source, groups):
             flat = torch.cat([r.atom_id_frag_id for r in records]).to(torch.long).numpy()
     if groups is not None:
         flat = _flat_groups(groups, n_atoms)
-    atom_off = np.concatenate([[0], np.cumsum(n_atoms)]).astype(np.int64)
+    atom_off = offsets_of(n_atoms)
     if store is not None and groups is None:
         table = _store_fragment_table(store)[1]
     else:
         table = flat_group_table(flat, atom_off)
-    device = next(model.parameters()).device
-    if device.type != "cuda":
-        from . import _lib
-        raise _lib.FragnetHipError(f"{who} runs on the GPU engine; there is no CPU fallback")
+    device = engine_device(model, who)          # (behind the table: a source or groups that are wrong are refused on any device)
     collate = None
     if kind in ("drp", "dta"):
         collate = data.collate_fn_cdrp if kind == "drp" else data.collate_fn_dta
     else:
         store = _as_store(source if store is not None else records, device)
-    return store, records, collate, flat, atom_off, table
+    return store, records, collate, flat, atom_off, table, device
 
 
 def fragment_contributions(model, source, groups=None, batch_size: int = 512) -> FragmentAttribution:
@@ -430,53 +527,40 @@ def fragment_contributions(model, source, groups=None, batch_size: int = 512) ->
     kind = _contribution_kind(model)
     if batch_size < 1:
         raise ValueError("batch_size must be positive")
-    store, records, collate, flat, atom_off, (rep_mol, ids, sizes, counts) = _group_source("fragment_contributions", kind, model, source, groups)
-    n = atom_off.shape[0] - 1
-    offsets = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+    store, records, collate, flat, atom_off, table, device = _group_source("fragment_contributions", kind, model, source, groups)
+    (rep_mol, ids, sizes, counts), n = table, atom_off.shape[0] - 1
+    offsets = offsets_of(counts)
     R = int(offsets[-1])
-    device = next(model.parameters()).device
     # every chunk's rows in ONE upload: [row groups int64 | row molecules int32 | atom groups int64], rows chunk-major, a chunk's B
     # unmasked rows (group -1) in front of its replica rows; chunks are runs of molecules, so each takes contiguous slices.  The atom
     # groups are not uploaded where they are the fragment map of a store that lives on the device.
-    starts = list(range(0, n, batch_size))
-    N = int(atom_off[-1])
+    chunks = batch_ranges(n, batch_size)
     frag_map = store.t["atom_id_frag_id"] if store is not None and groups is None else None
     on_device = frag_map is not None and frag_map.dtype == torch.long and frag_map.is_contiguous() and frag_map.device == device
-    words = (n + R) + (n + R + 1) // 2
-    host = np.empty(words + (0 if on_device else N), dtype=np.int64)
-    row_group_h, row_mol_h = host[: n + R], host[n + R: words].view(np.int32)[: n + R]
+    upload = PackedUpload([(np.int64, n + R), (np.int32, n + R)] + ([] if on_device else [(np.int64, int(atom_off[-1]))]))
+    row_group_h, row_mol_h = upload.host[:2]
     if not on_device:
-        host[words:] = flat
-    row0 = []
-    for b in starts:
-        e = min(n, b + batch_size)
-        r0, lo, hi = b + int(offsets[b]), int(offsets[b]), int(offsets[e])
-        row0.append(r0)
+        upload.host[2][:] = flat
+    unmasked = np.zeros(n + R, dtype=bool)
+    for b, e in chunks:
+        r0, lo, hi = b + int(offsets[b]), int(offsets[b]), int(offsets[e])          # the chunk's first row: its molecules' and replicas' sum
+        unmasked[r0: r0 + e - b] = True
         row_group_h[r0: r0 + e - b] = -1
         row_group_h[r0 + e - b: r0 + e - b + hi - lo] = ids[lo:hi]
         row_mol_h[r0: r0 + e - b] = np.arange(e - b)
         row_mol_h[r0 + e - b: r0 + e - b + hi - lo] = rep_mol[lo:hi] - b          # in [0, B) by construction: ops' own check is skipped
-    dev_buf = torch.from_numpy(host).to(device)
-    row_group_d, row_mol_d = dev_buf[: n + R], dev_buf[n + R: words].view(torch.int32)[: n + R]
-    atom_group_d = frag_map if on_device else dev_buf[words:]
-    was_training = model.training
-    model.eval()
+    row_group_d, row_mol_d, *rest = upload.to(device)
+    atom_group_d = frag_map if on_device else rest[0]
     preds = []
-    try:
-        with torch.no_grad():
-            for b, r0 in zip(starts, row0):
-                e = min(n, b + batch_size)
-                rows = e - b + int(offsets[e] - offsets[b])
-                batch = store.collate(np.arange(b, e)) if store is not None else data.batch_to(collate(records[b:e]), device)
-                rm, rg, ag = row_mol_d[r0: r0 + rows], row_group_d[r0: r0 + rows], atom_group_d[int(atom_off[b]): int(atom_off[e])]
-                preds.append(_contribution_rows(kind, model, batch, lambda xa, xf, plan: ops.pool_cat_groups(xa, xf, plan, ag, rm, rg, check=False),
-                                                rm))          # rows built and checked here, on the host
-            pred_h = (preds[0] if len(preds) == 1 else torch.cat(preds, 0)).cpu().numpy()
-    finally:
-        model.train(was_training)
-    unmasked = np.zeros(n + R, dtype=bool)
-    for b, r0 in zip(starts, row0):
-        unmasked[r0: r0 + min(n, b + batch_size) - b] = True
+    with evaluation(model), torch.no_grad():
+        for b, e in chunks:
+            r0 = b + int(offsets[b])
+            rows = e - b + int(offsets[e] - offsets[b])
+            batch = store.collate(np.arange(b, e)) if store is not None else data.batch_to(collate(records[b:e]), device)
+            rm, rg, ag = row_mol_d[r0: r0 + rows], row_group_d[r0: r0 + rows], atom_group_d[int(atom_off[b]): int(atom_off[e])]
+            preds.append(_contribution_rows(kind, model, batch, lambda xa, xf, plan: ops.pool_cat_groups(xa, xf, plan, ag, rm, rg, check=False),
+                                            rm))          # rows built and checked here, on the host
+        pred_h = (preds[0] if len(preds) == 1 else torch.cat(preds, 0)).cpu().numpy()
     base_h, masked_h = pred_h[unmasked], pred_h[~unmasked]
     return FragmentAttribution(base_h, offsets, ids, sizes, masked_h, base_h[rep_mol] - masked_h, flat, atom_off)
 
@@ -623,13 +707,13 @@ def _shapley_host(counts, evaluate, additive=False, batch_size=512, exact_max=10
     n = counts.shape[0]
     mode, given, rows = coalition_design(counts, additive, exact_max, samples, permutations)
     chunks = plan_coalition_chunks(rows, batch_size, max_rows)
-    offsets = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+    offsets = offsets_of(counts)
     is_exact = mode == "exact"
     pred = base = phi = stderr = None
     exact = mode != "sampled"
     values = [None] * n if return_values else None
     for b, e in chunks:
-        first = np.concatenate([[0], np.cumsum(rows[b:e])]).astype(np.int64)
+        first = offsets_of(rows[b:e])
         row_mol = np.repeat(np.arange(e - b, dtype=np.int32), rows[b:e])
         row_mask = (np.arange(first[-1], dtype=np.int64) - np.repeat(first[:-1], rows[b:e])).astype(np.uint64)      # exact mode: the row index
         others = (b + np.flatnonzero(~is_exact[b:e])).tolist()
@@ -684,33 +768,24 @@ def _spread_to_atoms(table, group, offsets, atom_group, atom_offsets, i):
     return out
 
 
-class FragmentShapley:
+class FragmentShapley(_GroupResult):
     """Result of ``fragment_shapley``.  ``pred [n, C]`` = v(all groups), ``base [n, C]`` = v(no group); rows ``offsets[i] : offsets[i + 1]``
     of ``group`` / ``n_atoms`` / ``phi`` / ``stderr`` (float64 ``[R, C]``) are molecule i's groups in ascending order; ``exact [n]``: the
     molecule's values are exact (``stderr`` 0), not a permutation sample.  ``result[i]`` is molecule i as a dict, ``atom_weights(i)`` its
     phi spread over its atoms, ``arrays()`` what the command-line script writes.  ``values`` (``return_values=True``): per molecule
     ``{"mask": uint64 [rows], "value": [rows, C]}``, every evaluated coalition."""
 
+    _per_group = "phi"
+
     def __init__(self, pred, base, offsets, group, n_atoms, phi, stderr, exact, atom_group, atom_offsets, values=None):
-        self.pred, self.base, self.offsets, self.group, self.n_atoms = pred, base, offsets, group, n_atoms
-        self.phi, self.stderr, self.exact, self.atom_group, self.atom_offsets, self.values = phi, stderr, exact, atom_group, atom_offsets, values
-
-    def __len__(self):
-        return self.pred.shape[0]
-
-    def _index(self, i: int) -> int:
-        if not -len(self) <= i < len(self):
-            raise IndexError(i)
-        return i % len(self)
+        self._set_groups(offsets, group, n_atoms, atom_group, atom_offsets)
+        self.pred, self.base, self.phi, self.stderr, self.exact, self.values = pred, base, phi, stderr, exact, values
 
     def __getitem__(self, i: int) -> dict:
         i = self._index(i)
         lo, hi = int(self.offsets[i]), int(self.offsets[i + 1])
         return {"pred": self.pred[i], "base": self.base[i], "group": self.group[lo:hi], "n_atoms": self.n_atoms[lo:hi],
                 "phi": self.phi[lo:hi], "stderr": self.stderr[lo:hi], "exact": bool(self.exact[i])}
-
-    def atom_weights(self, i: int) -> np.ndarray:
-        return _spread_to_atoms(self.phi, self.group, self.offsets, self.atom_group, self.atom_offsets, self._index(i))
 
     def arrays(self) -> Dict[str, np.ndarray]:
         return {"pred": self.pred, "base": self.base, "offsets": self.offsets, "group": self.group, "n_atoms": self.n_atoms, "phi": self.phi,
@@ -730,7 +805,7 @@ def atom_bits(flat, atom_off, table) -> np.ndarray:
         if n * span >= 1 << 62:
             raise ValueError("fragment_shapley: group ids too large to index (molecules x largest id must stay below 2^62)")
         mol = np.repeat(np.arange(n, dtype=np.int64), np.diff(atom_off))[keep]
-        first = np.concatenate([[0], np.cumsum(counts)])
+        first = offsets_of(counts)
         pos = np.searchsorted(rep_mol * span + ids, mol * span + flat[keep]) - first[mol]
         if counts.max() > 64:
             i = int(np.argmax(counts > 64))
@@ -765,34 +840,24 @@ def fragment_shapley(model, source, groups=None, batch_size: int = 512, exact_ma
     additive = kind in ("drp", "dta")
     design_args = dict(additive=additive, batch_size=batch_size, exact_max=exact_max, samples=samples, seed=seed, permutations=permutations,
                        max_rows=max_rows, return_values=return_values)
-    store, records, collate, flat, atom_off, table = _group_source("fragment_shapley", kind, model, source, groups)
+    store, records, collate, flat, atom_off, table, device = _group_source("fragment_shapley", kind, model, source, groups)
     rep_mol, ids, sizes, counts = table
     if store is not None and groups is None:          # the fragment map of a store: derived once and kept on it, like its replica table
-        bits = getattr(store, "_frag_bits_cpu", None)
-        if bits is None:
-            bits = store._frag_bits_cpu = atom_bits(flat, atom_off, table)
+        bits = kept_on_store(store, "_frag_bits_cpu", lambda: atom_bits(flat, atom_off, table))
     else:
         bits = atom_bits(flat, atom_off, table)
-    device = next(model.parameters()).device
 
     def evaluate(b, e, row_mol, row_mask):
         R, N = row_mol.shape[0], int(atom_off[e] - atom_off[b])
-        words = R + (R + 1) // 2
-        host = np.empty(words + (N + 7) // 8, dtype=np.int64)          # one upload: [masks int64 | molecules int32 | atom bits int8]
-        host[:R] = row_mask.view(np.int64)
-        host[R: words].view(np.int32)[:R] = row_mol
-        host[words:].view(np.int8)[:N] = bits[int(atom_off[b]): int(atom_off[e])]
-        dev = torch.from_numpy(host).to(device)
-        mask_d, mol_d, bit_d = dev[:R], dev[R: words].view(torch.int32)[:R], dev[words:].view(torch.int8)[:N]
+        upload = PackedUpload([(np.int64, R), (np.int32, R), (np.int8, N)])          # one upload: [masks | molecules | atom bits]
+        upload.host[0][:] = row_mask.view(np.int64)
+        upload.host[1][:] = row_mol
+        upload.host[2][:] = bits[int(atom_off[b]): int(atom_off[e])]
+        mask_d, mol_d, bit_d = upload.to(device)
         batch = store.collate(np.arange(b, e)) if store is not None else data.batch_to(collate(records[b:e]), device)
         read_out = lambda xa, xf, plan: ops.pool_cat_coalitions(xa, xf, plan, bit_d, mol_d, mask_d, check=False)      # rows built here
         return _contribution_rows(kind, model, batch, read_out, mol_d, head_rows=ops.DENSE_MAX_ROWS).cpu().numpy()
 
-    was_training = model.training
-    model.eval()
-    try:
-        with torch.no_grad():
-            r = _shapley_host(counts, evaluate, **design_args)
-    finally:
-        model.train(was_training)
+    with evaluation(model), torch.no_grad():
+        r = _shapley_host(counts, evaluate, **design_args)
     return FragmentShapley(r["pred"], r["base"], r["offsets"], ids, sizes, r["phi"], r["stderr"], r["exact"], flat, atom_off, r["values"])

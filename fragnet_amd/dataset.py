@@ -447,6 +447,13 @@ def load_pickle_dataset(path):
     return [it for it in items if it]
 
 
+def load_source(path, device):
+    """The molecules a command-line driver is given: a flat store (``.pt``) loaded onto ``device``, else a pickled list of records."""
+    if path.endswith(".pt"):
+        return FlatMolStore.load(path, device=device)
+    return load_pickle_dataset(path)
+
+
 def load_data_parts(path, select_name=None):
     """Concatenation of every pickled part file in ``path`` whose name contains ``select_name`` (dataset/dataset.py:280-292)."""
     import os

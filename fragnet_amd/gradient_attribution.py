@@ -22,7 +22,8 @@ from typing import Dict, Optional, Sequence, Tuple
 
 import numpy as np
 
-from .attribution import DEFAULT_MAX_ROWS, KIND_ORDER, _as_store, plan_chunks
+from .attribution import (DEFAULT_MAX_ROWS, KIND_ORDER, _as_store, _KindTables, chunk_replicas, engine_device, evaluation, offsets_of,
+                          plan_chunks, row_vector, store_batches)
 
 TABLE_KEYS = ("x_atoms", "node_features_bonds", "node_features_fbonds")      # the differentiated inputs, in KIND_ORDER
 TABLE_SPACES = ("atom", "edge", "fedge")
@@ -48,10 +49,10 @@ def entry_rows(n_bonds_directed, n_fbonds_directed):
         raise ValueError("entry_rows: one non-negative count per molecule, directed-row counts even (one placeholder fragment-bond row aside)")
 
     def pairs(counts):
-        off = np.concatenate([[0], np.cumsum(counts)])[:-1]
+        off = offsets_of(counts)[:-1]
         per = counts // 2
         mol = np.repeat(np.arange(counts.shape[0]), per)
-        k = np.arange(int(per.sum())) - np.repeat(np.concatenate([[0], np.cumsum(per)])[:-1], per)
+        k = np.arange(int(per.sum())) - np.repeat(offsets_of(per)[:-1], per)
         return off[mol] + 2 * k, k, per, off
 
     b_first, b_k, b_per, _ = pairs(nb)
@@ -60,7 +61,7 @@ def entry_rows(n_bonds_directed, n_fbonds_directed):
     return (b_first, (2 * b_k).astype(np.int32), b_per, f_first, f_k.astype(np.int32), f_per, f_off[odd] + 2 * f_per[odd])
 
 
-class GradientAttribution:
+class GradientAttribution(_KindTables):
     """Result of ``input_gradients`` / ``integrated_gradients``: flat arrays plus per-molecule offsets.  ``result[i]`` is molecule i as
     ``{"pred": float, kind: {"index": [count], "attr": [count]}, "attr_other": float, ...}`` (integrated gradients adds
     ``pred_baseline`` and ``gap``); ``arrays()`` is what the command-line script writes.  ``gradients``: None, or the raw gradient
@@ -72,21 +73,12 @@ class GradientAttribution:
         self.pred_baseline, self.gap, self.gradients, self.steps, self.target = pred_baseline, gap, gradients, steps, target
         self.kinds = KIND_ORDER
 
-    def __len__(self):
-        return self.pred.shape[0]
-
     def __getitem__(self, i: int) -> dict:
-        if not -len(self) <= i < len(self):
-            raise IndexError(i)
-        i %= len(self)
+        i = self._index(i)
         out = {"pred": self.pred[i], "attr_other": self.attr_other[i]}
         if self.pred_baseline is not None:
             out["pred_baseline"], out["gap"] = self.pred_baseline[i], self.gap[i]
-        for k in self.kinds:
-            t = self.tables[k]
-            lo, hi = int(t["offsets"][i]), int(t["offsets"][i + 1])
-            out[k] = {"index": t["index"][lo:hi], "attr": t["attr"][lo:hi]}
-        return out
+        return {**out, **self._kind_rows(i)}
 
     def arrays(self) -> Dict[str, np.ndarray]:
         out = {"method": np.array(self.method), "target": np.array(self.target), "pred": self.pred, "attr_other": self.attr_other,
@@ -95,9 +87,7 @@ class GradientAttribution:
             out["steps"] = np.array(self.steps)
         if self.pred_baseline is not None:
             out["pred_baseline"], out["gap"] = self.pred_baseline, self.gap
-        for k in self.kinds:
-            for name, v in self.tables[k].items():
-                out[f"{k}_{name}"] = v
+        out.update(self._kind_arrays())
         if self.gradients is not None:
             for key, g in zip(TABLE_KEYS, self.gradients):
                 if g is not None:
@@ -114,11 +104,10 @@ def assemble(lens, row_scores: Sequence[np.ndarray]) -> Tuple[Dict[str, Dict[str
     if a.shape[0] != na.sum() or b.shape[0] != nb.sum() or f.shape[0] != nf.sum():
         raise ValueError("assemble: row scores do not match the molecules' row counts")
     b_first, b_index, b_per, f_first, f_index, f_per, f_other = entry_rows(nb, nf)
-    offs = lambda per: np.concatenate([[0], np.cumsum(per)]).astype(np.int64)
-    k_atom = np.arange(int(na.sum())) - np.repeat(offs(na)[:-1], na)
-    tables = {"atom": {"offsets": offs(na), "index": k_atom.astype(np.int32), "attr": a},
-              "bond": {"offsets": offs(b_per), "index": b_index, "attr": b[b_first] + b[b_first + 1]},
-              "fbond": {"offsets": offs(f_per), "index": f_index, "attr": f[f_first] + f[f_first + 1]}}
+    k_atom = np.arange(int(na.sum())) - np.repeat(offsets_of(na)[:-1], na)
+    tables = {"atom": {"offsets": offsets_of(na), "index": k_atom.astype(np.int32), "attr": a},
+              "bond": {"offsets": offsets_of(b_per), "index": b_index, "attr": b[b_first] + b[b_first + 1]},
+              "fbond": {"offsets": offsets_of(f_per), "index": f_index, "attr": f[f_first] + f[f_first + 1]}}
     other = np.zeros(n, dtype=np.float32)
     f_mol = np.repeat(np.arange(n), nf)
     np.add.at(other, f_mol[f_other], f[f_other])
@@ -136,16 +125,13 @@ def completeness_gap(pred, pred_baseline, tables, attr_other) -> np.ndarray:
 
 
 def _check_model(model, what: str):
-    from . import _lib
     from .model import FragNetFineTune
     if not isinstance(model, FragNetFineTune):
         raise ValueError(f"{what}: {type(model).__name__} is not a FragNetFineTune (CDRP, DTA and gcn2 models are out of scope)")
     variant = getattr(model.pretrain, "variant", None)
     if variant not in ("gat2", "gat2_lite"):
         raise NotImplementedError(f"{what}: the engine differentiates its inputs for model_version gat2 and gat2_lite (got {variant!r})")
-    device = next(model.parameters()).device
-    if device.type != "cuda":
-        raise _lib.FragnetHipError(f"{what} runs on the GPU engine; there is no CPU fallback")
+    device = engine_device(model, what)
     if not model.pretrain.use_engine:
         raise ValueError(f"{what}: the fused row dots come from the engine (use_engine=False has no such output)")
     return device, variant
@@ -186,14 +172,10 @@ def input_gradients(model, source, target: int = 0, batch_size: int = 512, retur
     if batch_size < 1:
         raise ValueError("batch_size must be positive")
     store = _as_store(source, device)
-    n = len(store)
     lens = store._host_lengths()
     preds, rows, grads = [], ([], [], []), ([], [], [])
-    was_training = model.training
-    model.eval()
-    try:
-        for b in range(0, n, batch_size):
-            batch = store.collate(np.arange(b, min(n, b + batch_size)))
+    with evaluation(model):
+        for _, _, batch in store_batches(store, batch_size):
             xs = [batch[k].detach().float().contiguous() for k in TABLE_KEYS]
             leaves = [x.clone() for x in xs]
             col, dots, g = _backward_dots(model, batch, leaves, xs if variant == "gat2" else (xs[0], xs[1], None), target, return_gradients)
@@ -206,8 +188,6 @@ def input_gradients(model, source, target: int = 0, batch_size: int = 512, retur
         grad_h = None
         if return_gradients:
             grad_h = tuple(None if any(t is None for t in g) else torch.cat(g, 0).cpu().numpy() for g in grads)
-    finally:
-        model.train(was_training)
     tables, other = assemble(lens, row_h)
     return GradientAttribution("grad_x_input", pred, tables, other, gradients=grad_h, target=target)
 
@@ -222,17 +202,9 @@ def check_baseline(baseline, widths: Sequence[int], device):
         raise ValueError("baseline: None (zeros) or three row vectors (atoms [Ka], bond nodes [Kb], fragment-bond nodes [Kf])")
     out = []
     for v, w, key in zip(baseline, widths, TABLE_KEYS):
-        if torch.is_tensor(v):
-            if v.device.type != "cpu" and v.device != torch.device(device):
-                raise ValueError(f"baseline of {key}: a tensor on {v.device}, the model is on {device}")
-            v = v.detach()
-        else:
-            v = torch.as_tensor(np.asarray(v))
-        if v.dim() != 1 or v.shape[0] != w:
-            raise ValueError(f"baseline of {key}: a row vector of {w} features (got shape {tuple(v.shape)})")
-        if not (v.dtype.is_floating_point or v.dtype in (torch.int32, torch.int64, torch.uint8, torch.bool)):
-            raise ValueError(f"baseline of {key}: a real-valued vector (got {v.dtype})")
-        out.append(v.to(device=device, dtype=torch.float32).contiguous())
+        if torch.is_tensor(v) and v.device.type != "cpu" and v.device != torch.device(device):
+            raise ValueError(f"baseline of {key}: a tensor on {v.device}, the model is on {device}")
+        out.append(row_vector(v, w, device, f"baseline of {key}", "features"))
     return out
 
 
@@ -257,34 +229,29 @@ def integrated_gradients(model, source, steps: int = 32, baseline=None, target: 
     if batch_size < 1:
         raise ValueError("batch_size must be positive")
     store = _as_store(source, device)
-    n = len(store)
     lens = store._host_lengths()
     widths = [int(store.t[k].shape[1]) for k in STORE_KEYS]
     base = check_baseline(baseline, widths, device)
     chunks = ig_plan(lens, steps, max_rows)
     counts = [np.asarray(lens[s], dtype=np.int64) for s in TABLE_SPACES]
-    offs = [np.concatenate([[0], np.cumsum(c)]) for c in counts]
+    offs = [offsets_of(c) for c in counts]
     totals = [int(o[-1]) for o in offs]
     live = (True, True, variant == "gat2")
-    was_training = model.training
-    model.eval()
-    try:
+    with evaluation(model):
         with torch.no_grad():
             pred, pred0 = [], []
-            for b in range(0, n, batch_size):
-                idx = np.arange(b, min(n, b + batch_size))
-                pred.append(_column(model(store.collate(idx)), len(idx), target).float())
-                batch = store.collate(idx)
+            for b, e, batch in store_batches(store, batch_size):
+                pred.append(_column(model(batch), e - b, target).float())
+                batch = store.collate(np.arange(b, e))
                 for key, x0 in zip(TABLE_KEYS, base):
                     batch[key] = x0.expand(batch[key].shape[0], -1).contiguous()
-                pred0.append(_column(model(batch), len(idx), target).float())
+                pred0.append(_column(model(batch), e - b, target).float())
             pred, pred0 = torch.cat(pred).cpu().numpy(), torch.cat(pred0).cpu().numpy()
         # every step's row scores, [steps, rows of all molecules] per table, then the sum over the steps in ascending j
         per_step = [torch.zeros((steps, t), dtype=torch.float32, device=device) for t in totals]
         alpha_d = torch.from_numpy(alphas).to(device)
         for chunk in chunks:
-            mols = np.concatenate([np.full(r1 - r0, i, dtype=np.int64) for i, r0, r1 in chunk])
-            step = np.concatenate([np.arange(r0, r1, dtype=np.int64) for _, r0, r1 in chunk])
+            mols, step = chunk_replicas(chunk)          # a replica's number is its step
             batch = store.collate(mols)
             step_d = torch.from_numpy(step).to(device)
             leaves, deltas, slots = [], [], []
@@ -298,8 +265,7 @@ def integrated_gradients(model, source, steps: int = 32, baseline=None, target: 
                 leaves.append(torch.addcmul(base[k].expand_as(x), alpha_d[step_d[row_rep]].unsqueeze(1), delta).contiguous())
                 deltas.append(delta if live[k] else None)
                 # destination of the replica's rows in per_step[k]: row (step, first row of the molecule + row within the molecule)
-                first = np.concatenate([[0], np.cumsum(c)])[:-1]
-                dest = np.repeat(step * totals[k] + offs[k][mols] - first, c) + np.arange(int(c.sum()))
+                dest = np.repeat(step * totals[k] + offs[k][mols] - offsets_of(c)[:-1], c) + np.arange(int(c.sum()))
                 slots.append(torch.from_numpy(dest).to(device))
             _, dots, _ = _backward_dots(model, batch, leaves, deltas, target, False)
             for k in range(3):
@@ -311,8 +277,6 @@ def integrated_gradients(model, source, steps: int = 32, baseline=None, target: 
             for j in range(1, steps):
                 acc += t[j]
             row_h.append((acc / steps).cpu().numpy())
-    finally:
-        model.train(was_training)
     tables, other = assemble(lens, row_h)
     gap = completeness_gap(pred, pred0, tables, other)
     return GradientAttribution("ig", pred, tables, other, pred_baseline=pred0, gap=gap, steps=steps, target=target)

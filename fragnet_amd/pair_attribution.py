@@ -25,7 +25,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib, ops
-from .attribution import DEFAULT_MAX_ROWS
+from .attribution import DEFAULT_MAX_ROWS, _Result, row_vector
 from .gradient_attribution import GradientAttribution, input_gradients, integrated_gradients, midpoint_alphas
 from .model import FragNetFineTune
 
@@ -59,21 +59,17 @@ def plan_cell_chunks(n_cells: int, steps: int, max_rows: int) -> List[Tuple[int,
     return [(c, min(n_cells, c + per)) for c in range(0, n_cells, per)]
 
 
-class CellLineAttribution:
+class CellLineAttribution(_Result):
     """Result of ``cell_line_attributions``: ``attr`` float32 [C, gene_dim], ``score`` [C] (= ``<cell_enc, v_s>``), and for integrated
     gradients ``score_baseline`` [C] and ``gap = score - score_baseline - sum_k attr`` [C] (None for gradient x input).  ``result[c]``
     is cell line c as a dict; ``arrays()`` is what the command-line script writes."""
+    _per_item = "attr"
 
     def __init__(self, method: str, attr, score, score_baseline=None, gap=None, steps: Optional[int] = None):
         self.method, self.attr, self.score, self.score_baseline, self.gap, self.steps = method, attr, score, score_baseline, gap, steps
 
-    def __len__(self):
-        return self.attr.shape[0]
-
     def __getitem__(self, c: int) -> dict:
-        if not -len(self) <= c < len(self):
-            raise IndexError(c)
-        c %= len(self)
+        c = self._index(c)
         out = {"attr": self.attr[c], "score": self.score[c]}
         if self.score_baseline is not None:
             out["score_baseline"], out["gap"] = self.score_baseline[c], self.gap[c]
@@ -89,14 +85,7 @@ class CellLineAttribution:
 
 
 def _gene_baseline(baseline, width: int, device):
-    if baseline is None:
-        return None
-    v = baseline.detach() if torch.is_tensor(baseline) else torch.as_tensor(np.asarray(baseline))
-    if v.dim() != 1 or v.shape[0] != width:
-        raise ValueError(f"baseline: a row vector of {width} genes (got shape {tuple(v.shape)})")
-    if not (v.dtype.is_floating_point or v.dtype in (torch.int32, torch.int64, torch.uint8, torch.bool)):
-        raise ValueError(f"baseline: a real-valued vector (got {v.dtype})")
-    return v.to(device=device, dtype=torch.float32).contiguous()
+    return None if baseline is None else row_vector(baseline, width, device, "baseline", "genes")
 
 
 def cell_line_attributions(model, gene_expr, method: str = "ig", steps: int = 32, baseline=None,
@@ -109,6 +98,7 @@ def cell_line_attributions(model, gene_expr, method: str = "ig", steps: int = 32
     ``steps`` nodes (``gradient_attribution.midpoint_alphas``), a cell line's nodes added in ascending order.  Cell lines are chunked so
     that ``cells * steps <= max_rows`` (default and upper limit ``ops.DENSE_MAX_ROWS``).  Everything runs on the tower's HIP kernels; a
     tower whose widths they do not take raises ValueError -- there is no other path."""
+    # (drug_attributions' two refusals of ``method`` / ``baseline``: each driver has refusals of its own between them, so they stay apart)
     if method not in METHODS:
         raise ValueError(f"method: one of {METHODS} (got {method!r})")
     tower = getattr(getattr(model, "cell_model", None), "predictor", None)
@@ -137,7 +127,7 @@ def cell_line_attributions(model, gene_expr, method: str = "ig", steps: int = 32
         raise ValueError("cell_line_attributions: the tower's kernels take Linears with a bias whose widths behind gene_dim are multiples of "
                          "4; this tower has no kernel path, and there is no other")
     base = _gene_baseline(baseline, gene.shape[1], "cpu" if device.type != "cuda" else device)
-    if device.type != "cuda":
+    if device.type != "cuda":          # (attribution.engine_device's refusal, for the tower's device and in this driver's words)
         raise _lib.FragnetHipError("cell_line_attributions runs on the GPU kernels; there is no CPU fallback")
     gene = gene.to(device).contiguous()
     alpha_d, one = torch.from_numpy(alphas).to(device), torch.ones(1, dtype=torch.float32, device=device)
@@ -160,20 +150,17 @@ def cell_line_attributions(model, gene_expr, method: str = "ig", steps: int = 32
 
 
 # ----------------------------------------------------------------------------------------------------------------- the protein side
-class ProteinAttribution:
+class ProteinAttribution(_Result):
     """Result of ``protein_attributions``: ``attr`` float32 [P, L] per residue position, ``attr_other`` [P] (the bias terms), ``score``
     [P] (= ``<xt, v_s>`` from the tower's own forward) and ``table`` [L, V], the lookup ``attr[p, c] = table[c, tokens[p, c]]``."""
+
+    _per_item = "attr"
 
     def __init__(self, attr, attr_other, score, table):
         self.method, self.attr, self.attr_other, self.score, self.table = "grad_x_input", attr, attr_other, score, table
 
-    def __len__(self):
-        return self.attr.shape[0]
-
     def __getitem__(self, p: int) -> dict:
-        if not -len(self) <= p < len(self):
-            raise IndexError(p)
-        p %= len(self)
+        p = self._index(p)
         return {"attr": self.attr[p], "attr_other": self.attr_other[p], "score": self.score[p]}
 
     def arrays(self) -> Dict[str, np.ndarray]:
@@ -275,7 +262,7 @@ def drug_attributions(model, records, method: str = "ig", steps: int = 32, basel
 
     The result's ``pred`` (and ``pred_baseline``) is the scalar ``<drug_enc, v_d>``, NOT the model's prediction: the second input's share
     and the constant of ``pair_vectors`` are not in it.  The head has one column: ``target`` must be 0."""
-    if method not in METHODS:
+    if method not in METHODS:          # (cell_line_attributions' two refusals, in its words: see the note there)
         raise ValueError(f"method: one of {METHODS} (got {method!r})")
     drug = getattr(model, "drug_model", None)
     if drug is None or not hasattr(drug, "pretrain"):

@@ -78,6 +78,24 @@ def load_config(path: str, **overrides) -> Config:
     return _resolve(cfg, cfg)
 
 
+def finetune_model_kwargs(cfg: Config) -> dict:
+    """The fourteen constructor arguments that a finetune YAML gives a model -- ``FragNetFineTune`` and its Viz, GCN (which takes no
+    ``num_heads``) and pair-model ``FragNetFineTuneBase`` relatives.  ``variant`` (``cfg.model_version``) is the caller's to add: not
+    every class takes one."""
+    m = cfg.finetune.model
+    return dict(n_classes=m.n_classes, atom_features=cfg.atom_features, frag_features=cfg.frag_features, edge_features=cfg.edge_features,
+                num_layer=m.num_layer, drop_ratio=m.drop_ratio, num_heads=m.num_heads, emb_dim=m.emb_dim, h1=m.h1, h2=m.h2, h3=m.h3,
+                h4=m.h4, act=m.act, fthead=m.fthead)
+
+
+def pretrain_model_kwargs(cfg: Config) -> dict:
+    """The constructor arguments that a YAML's ``pretrain`` section and feature widths give ``FragNetPreTrain`` and its masked relatives."""
+    pt = cfg.pretrain
+    return dict(num_layer=pt.num_layer, drop_ratio=pt.drop_ratio, num_heads=pt.num_heads, emb_dim=pt.emb_dim,
+                atom_features=cfg.atom_features, frag_features=cfg.frag_features, edge_features=cfg.edge_features,
+                fedge_in=cfg.fedge_in, fbond_edge_in=cfg.fbond_edge_in)
+
+
 def seed_everything(seed: int):
     random.seed(seed)
     os.environ["PYTHONHASHSEED"] = str(seed)

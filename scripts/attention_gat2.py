@@ -36,22 +36,12 @@ def parse_args(argv=None):
     return args
 
 
-def load_source(path, device):
-    from fragnet_amd.dataset import FlatMolStore, load_pickle_dataset
-    if path.endswith(".pt"):
-        return FlatMolStore.load(path, device=device)
-    return load_pickle_dataset(path)
-
-
 def build_model(cfg):
+    from fragnet_amd import train
     from fragnet_amd.viz_model import FragNetFineTuneViz
-    m = cfg.finetune.model
     if cfg.model_version != "gat2":
         raise SystemExit(f"model_version {cfg.model_version!r}: the attention read-out exists for gat2 only")
-    return FragNetFineTuneViz(n_classes=m.n_classes, atom_features=cfg.atom_features, frag_features=cfg.frag_features,
-                              edge_features=cfg.edge_features, num_layer=m.num_layer, drop_ratio=m.drop_ratio,
-                              num_heads=m.num_heads, emb_dim=m.emb_dim, h1=m.h1, h2=m.h2, h3=m.h3, h4=m.h4, act=m.act,
-                              fthead=m.fthead)
+    return FragNetFineTuneViz(**train.finetune_model_kwargs(cfg))          # (the Viz class takes no ``variant``)
 
 
 def main(argv=None):
@@ -60,6 +50,7 @@ def main(argv=None):
     import torch
     import fragnet_amd
     from fragnet_amd import attention, train
+    from fragnet_amd.dataset import load_source
     cfg = train.load_config(args.config, config=args.config)
     fragnet_amd.prefer_rocblas_for_dense_heads()
     device = torch.device(args.device)

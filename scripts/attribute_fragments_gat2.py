@@ -42,26 +42,13 @@ def parse_args(argv=None):
     return args
 
 
-def load_source(path, device):
-    from fragnet_amd.dataset import FlatMolStore, load_pickle_dataset
-    if path.endswith(".pt"):
-        return FlatMolStore.load(path, device=device)
-    return load_pickle_dataset(path)
-
-
 def build_model(cfg, prop_type="property", device="cuda:0"):
     """The model of the finetune / CDRP / DTA / pretrain drivers, from the same YAML fields."""
-    from fragnet_amd import cdrp, dta
+    from fragnet_amd import cdrp, dta, train
     from fragnet_amd.model import FragNetFineTune, FragNetPreTrain
     if prop_type == "energy":
-        pt = cfg.pretrain
-        return FragNetPreTrain(num_layer=pt.num_layer, drop_ratio=pt.drop_ratio, num_heads=pt.num_heads, emb_dim=pt.emb_dim,
-                               atom_features=cfg.atom_features, frag_features=cfg.frag_features, edge_features=cfg.edge_features,
-                               fedge_in=cfg.fedge_in, fbond_edge_in=cfg.fbond_edge_in)
-    m = cfg.finetune.model
-    kw = dict(n_classes=m.n_classes, atom_features=cfg.atom_features, frag_features=cfg.frag_features, edge_features=cfg.edge_features,
-              num_layer=m.num_layer, drop_ratio=m.drop_ratio, num_heads=m.num_heads, emb_dim=m.emb_dim, h1=m.h1, h2=m.h2, h3=m.h3,
-              h4=m.h4, act=m.act, fthead=m.fthead)
+        return FragNetPreTrain(**train.pretrain_model_kwargs(cfg))
+    kw = train.finetune_model_kwargs(cfg)
     if prop_type == "property":
         return FragNetFineTune(variant=cfg.model_version, **kw)
     if prop_type == "drp":
@@ -75,6 +62,7 @@ def main(argv=None):
     import torch
     import fragnet_amd
     from fragnet_amd import attribution, train
+    from fragnet_amd.dataset import load_source
     cfg = train.load_config(args.config, config=args.config)
     fragnet_amd.prefer_rocblas_for_dense_heads()
     device = torch.device(args.device)

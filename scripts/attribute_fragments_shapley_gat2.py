@@ -19,7 +19,7 @@ import sys
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
-from attribute_fragments_gat2 import PROP_TYPES, build_model, load_source  # noqa: E402
+from attribute_fragments_gat2 import PROP_TYPES, build_model  # noqa: E402  (one model per --prop-type, built in one place)
 
 
 def parse_args(argv=None):
@@ -56,6 +56,7 @@ def main(argv=None):
     import torch
     import fragnet_amd
     from fragnet_amd import attribution, train
+    from fragnet_amd.dataset import load_source
     cfg = train.load_config(args.config, config=args.config)
     fragnet_amd.prefer_rocblas_for_dense_heads()
     device = torch.device(args.device)

@@ -53,12 +53,10 @@ def parse_args(argv=None):
 def build_model(cfg, kind, device):
     from fragnet_amd.cdrp import CDRPModel, FragNetFineTuneBase
     from fragnet_amd.dta import DTAModel2
-    m = cfg.finetune.model
+    from fragnet_amd.train import finetune_model_kwargs
     if cfg.model_version != "gat2":
         raise SystemExit(f"model_version {cfg.model_version!r}: the pair models run model_version gat2")
-    drug = FragNetFineTuneBase(n_classes=m.n_classes, atom_features=cfg.atom_features, frag_features=cfg.frag_features,
-                               edge_features=cfg.edge_features, num_layer=m.num_layer, drop_ratio=m.drop_ratio, num_heads=m.num_heads,
-                               emb_dim=m.emb_dim, h1=m.h1, h2=m.h2, h3=m.h3, h4=m.h4, act=m.act, fthead=m.fthead)
+    drug = FragNetFineTuneBase(**finetune_model_kwargs(cfg))
     return CDRPModel(drug, int(cfg.gene_dim), device) if kind == "cdrp" else DTAModel2(drug)
 
 

@@ -48,20 +48,15 @@ if __name__ == "__main__":
     torch.cuda.set_device(device)
     exp_dir = args["exp_dir"]
     os.makedirs(exp_dir, exist_ok=True)
-    ft, m = args.finetune, args.finetune.model
+    ft = args.finetune
     if args.model_version != "gat2":
         raise SystemExit("DTA: model_version gat2 is on the accelerated path")
     if ft.target_type != "regr":
         raise SystemExit("DTA: target_type regr only")
-    gat2 = FragNetFineTuneBase(n_classes=m.n_classes, atom_features=args.atom_features, frag_features=args.frag_features,
-                               edge_features=args.edge_features, num_layer=m.num_layer, drop_ratio=m.drop_ratio, num_heads=m.num_heads,
-                               emb_dim=m.emb_dim, h1=m.h1, h2=m.h2, h3=m.h3, h4=m.h4, act=m.act, fthead=m.fthead)
-    model = DTAModel2(gat2)
+    model = DTAModel2(FragNetFineTuneBase(**train.finetune_model_kwargs(args)))
     pt = args.pretrain
     if pt.get("chkpoint_name") and os.path.exists(str(pt.chkpoint_name)):
-        modelpt = FragNetPreTrain(num_layer=pt.num_layer, drop_ratio=pt.drop_ratio, num_heads=pt.num_heads, emb_dim=pt.emb_dim,
-                                  atom_features=args.atom_features, frag_features=args.frag_features, edge_features=args.edge_features,
-                                  fedge_in=args.fedge_in, fbond_edge_in=args.fbond_edge_in)
+        modelpt = FragNetPreTrain(**train.pretrain_model_kwargs(args))
         modelpt.load_state_dict(torch.load(pt.chkpoint_name, map_location="cpu"))
         model.drug_model.pretrain.load_state_dict(modelpt.pretrain.state_dict())
         print("loaded pretrained encoder", pt.chkpoint_name)

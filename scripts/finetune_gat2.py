@@ -38,21 +38,16 @@ if __name__ == "__main__":
     gcn = args.model_version == "gcn2"
     if gcn:      # finetune_gat2.py:99-117: the graph-convolution baseline takes no num_heads
         from fragnet_amd.gcn import FragNetFineTune as FragNetFineTuneGCN
-        model = FragNetFineTuneGCN(n_classes=m.n_classes, atom_features=args.atom_features, frag_features=args.frag_features,
-                                   edge_features=args.edge_features, num_layer=m.num_layer, drop_ratio=m.drop_ratio,
-                                   emb_dim=m.emb_dim, h1=m.h1, h2=m.h2, h3=m.h3, h4=m.h4, act=m.act, fthead=m.fthead)
+        kw = train.finetune_model_kwargs(args)
+        del kw["num_heads"]
+        model = FragNetFineTuneGCN(**kw)
     else:
-        model = FragNetFineTune(n_classes=m.n_classes, atom_features=args.atom_features, frag_features=args.frag_features,
-                                edge_features=args.edge_features, num_layer=m.num_layer, drop_ratio=m.drop_ratio,
-                                num_heads=m.num_heads, emb_dim=m.emb_dim, h1=m.h1, h2=m.h2, h3=m.h3, h4=m.h4, act=m.act,
-                                fthead=m.fthead, variant=args.model_version)
+        model = FragNetFineTune(**train.finetune_model_kwargs(args), variant=args.model_version)
     pt = args.pretrain
     if gcn and pt.get("chkpoint_name") and os.path.exists(str(pt.chkpoint_name)):
         raise SystemExit("model_version gcn2: no pretrained encoder to load (gcn2.py's own FragNetPreTrain is not on the accelerated path)")
     if pt.get("chkpoint_name") and os.path.exists(str(pt.chkpoint_name)):
-        modelpt = FragNetPreTrain(num_layer=pt.num_layer, drop_ratio=pt.drop_ratio, num_heads=pt.num_heads, emb_dim=pt.emb_dim,
-                                  atom_features=args.atom_features, frag_features=args.frag_features,
-                                  edge_features=args.edge_features, fedge_in=args.fedge_in, fbond_edge_in=args.fbond_edge_in)
+        modelpt = FragNetPreTrain(**train.pretrain_model_kwargs(args))
         modelpt.load_state_dict(torch.load(pt.chkpoint_name, map_location="cpu"))
         model.pretrain.load_state_dict(modelpt.pretrain.state_dict())
         print("loaded pretrained encoder", pt.chkpoint_name)

@@ -20,9 +20,7 @@ def build_model(args):
     reference's class cannot train; anything else: refused (the reference would fail later, with ``model`` unbound)."""
     pt = args.pretrain
     version = args.get("model_version") or "gat2"
-    kw = dict(num_layer=pt.num_layer, drop_ratio=pt.drop_ratio, num_heads=pt.num_heads, emb_dim=pt.emb_dim,
-              atom_features=args.atom_features, frag_features=args.frag_features,
-              edge_features=args.edge_features, fedge_in=args.fedge_in, fbond_edge_in=args.fbond_edge_in)
+    kw = train.pretrain_model_kwargs(args)
     if version == "gat2":
         return FragNetPreTrain(**kw)
     if version == "gat2_masked2":

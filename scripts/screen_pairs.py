@@ -63,10 +63,7 @@ if __name__ == "__main__":
     args = train.load_config(cli.config, config=cli.config)
     device = torch.device("cuda", 0)
     torch.cuda.set_device(device)
-    m = args.finetune.model
-    gat2 = FragNetFineTuneBase(n_classes=m.n_classes, atom_features=args.atom_features, frag_features=args.frag_features,
-                               edge_features=args.edge_features, num_layer=m.num_layer, drop_ratio=m.drop_ratio, num_heads=m.num_heads,
-                               emb_dim=m.emb_dim, h1=m.h1, h2=m.h2, h3=m.h3, h4=m.h4, act=m.act, fthead=m.fthead)
+    gat2 = FragNetFineTuneBase(**train.finetune_model_kwargs(args))
     model = CDRPModel(gat2, int(args.gene_dim), device) if cli.model == "cdrp" else DTAModel2(gat2)
     model.load_state_dict(torch.load(cli.checkpoint, map_location="cpu"))
     model.to(device)

@@ -189,3 +189,46 @@ def test_leave_one_out_refuses_what_it_cannot_do():
         attr.leave_one_out(FragNetFineTune(**small), mols)
     with pytest.raises(ValueError):
         attr.leave_one_out(FragNetFineTune(**small), mols, kinds=("atoms",))
+
+
+class _Flagged(torch.nn.Module):
+    pass
+
+
+@pytest.mark.parametrize("training", [True, False])
+def test_the_evaluation_scope_restores_the_mode_it_found(training):
+    m = _Flagged().train(training)
+    with attr.evaluation(m) as inside:
+        assert inside is m and not m.training
+        assert torch.is_grad_enabled(), "the scope leaves the gradient mode to its caller"
+    assert m.training is training
+    with pytest.raises(KeyError, match="in the body"):
+        with attr.evaluation(m):
+            assert not m.training
+            raise KeyError("in the body")
+    assert m.training is training
+
+
+def test_a_packed_upload_is_one_buffer_with_aligned_parts():
+    parts = [(np.int64, 0), (np.int32, 1), (np.int8, 7), (np.int64, 1), (np.int32, 7), (np.int8, 0), (np.int8, 1), (np.int64, 7), (np.int32, 0)]
+    up = attr.PackedUpload(parts)
+    assert up.buffer.dtype == np.int64 and up.buffer.shape == (0 + 1 + 1 + 1 + 4 + 0 + 1 + 7 + 0,)
+    lo, hi = up.buffer.ctypes.data, up.buffer.ctypes.data + up.buffer.nbytes
+    want = []
+    for k, ((dtype, count), h) in enumerate(zip(parts, up.host)):
+        assert h.dtype == dtype and h.shape == (count,)
+        assert count == 0 or (np.shares_memory(h, up.buffer) and lo <= h.ctypes.data and h.ctypes.data + h.nbytes <= hi)
+        assert (h.ctypes.data - lo) % 8 == 0, f"part {k} does not start on an 8-byte boundary"
+        want.append((np.arange(count) * (k + 3) - 5).astype(dtype))
+        h[:] = want[-1]          # filled in place, as the drivers do
+    for k, h in enumerate(up.host):          # no part overlaps another
+        np.testing.assert_array_equal(h, want[k])
+    dev = up.to("cpu")
+    assert len(dev) == len(parts)
+    one = dev[1].untyped_storage().data_ptr()
+    assert all(t.untyped_storage().data_ptr() == one for t in dev), "the device views alias ONE tensor: one copy"
+    for k, (t, w) in enumerate(zip(dev, want)):
+        assert t.dtype == torch.from_numpy(w).dtype and tuple(t.shape) == w.shape
+        np.testing.assert_array_equal(t.numpy(), w)
+        at = t.storage_offset() * t.element_size()
+        assert at % 8 == 0 and (w.size == 0 or at == up.host[k].ctypes.data - lo), "the device views are the host's layout"
