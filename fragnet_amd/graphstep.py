@@ -24,13 +24,12 @@ same collective as in the eager step.
 """
 from __future__ import annotations
 
-import ctypes as C
+import contextlib
 import math
-from typing import Callable, Dict, Iterable, Optional
+import os
+from typing import Dict, Iterable, Optional
 
 import torch
-
-import os
 
 from . import _lib
 from .plan import LIVE_MOLS_KEY, PLAN_KEY, REAL_ATOMS_KEY, REAL_MOLS_KEY, SPACES, CollatedBatch, prezeroed_plans
@@ -52,6 +51,7 @@ COUNT_FIELD = {"atom": "x_atoms", "edge": "node_features_bonds", "bedge": "edge_
 MASK_KEY = "mol_weight"           # float32 [mol cap]: 1 for real molecules, 0 for padding
 MASKS = {"mol": MASK_KEY, "atom": "atom_weight", "edge": "edge_weight"}     # 1/0 weights of the mean losses
 SCALE_KEY = "loss_scales"         # float32 [2]: (per-edge, per-atom) rank weights of the pretrain loss, 1 on one GPU
+_OFFSETS = object()               # StaticBatch: the staged field whose source is the batch's offsets table, not one of its keys
 
 
 # "thread_local": HIP calls of OTHER threads (the collective library's watchdog, a data-loader thread) do not invalidate
@@ -246,7 +246,12 @@ class StaticBatch:
         if self.with_offsets:
             self.t.offsets = torch.zeros((len(SPACES), shapes.cap["mol"] + 1), dtype=torch.int32, device=dev)
             self.t.max_per_mol, self.t.pad = dict(shapes.max_per_mol), shapes.pad_info()
-        self._desc = []
+        # the staging table, in the launch's order: data fields (FIELDS order), the three masks, the real-molecule count, the offsets table,
+        # add_count's counts, then set_bumps' bumps and zero regions.  ``_refresh``: one entry per field that changes with the batch, all that
+        # load() walks -- (the field, the index space whose real count is its n_real, its src: a batch key, _OFFSETS, or None)
+        self._fields = (_lib.StageField * _lib.FN_MAX_STAGE_FIELDS)()
+        self.n_fields = 0
+        self._refresh = []
         for name, (space, layout, target) in FIELDS.items():
             if name not in example:
                 continue
@@ -256,55 +261,46 @@ class StaticBatch:
                     raise TypeError(f"{name}: expected float32 rows, got {src.dtype}")
                 self.t[name] = torch.zeros((cap,) + tuple(src.shape[1:]), dtype=torch.float32, device=dev)
                 width = int(src[0].numel()) if src.dim() > 1 else 1
-                self._desc.append((name, space, _lib.STAGE_ROWS, max(width, 1), 0, 1))
+                self._append(_lib.STAGE_ROWS, self.t[name].data_ptr(), cap, max(width, 1), refresh=(space, name))
             else:
                 if src.dtype != torch.int64:
                     raise TypeError(f"{name}: expected int64 indices, got {src.dtype}")
                 hi, mod = shapes.pad_rule(target)
                 self.t[name] = torch.zeros((cap,) if layout == "ids" else (2, cap), dtype=torch.int64, device=dev)
-                self._desc.append((name, space, _lib.STAGE_IDS if layout == "ids" else _lib.STAGE_COLS, 1, hi, mod))
+                self._append(_lib.STAGE_IDS if layout == "ids" else _lib.STAGE_COLS, self.t[name].data_ptr(), cap, pad_hi=hi, pad_mod=mod,
+                             refresh=(space, name))
         for space, key in MASKS.items():
             self.t[key] = torch.zeros(shapes.cap[space], dtype=torch.float32, device=dev)
+            self._append(_lib.STAGE_MASK, self.t[key].data_ptr(), shapes.cap[space], refresh=(space, None))
         self.t[SCALE_KEY] = torch.ones(2, dtype=torch.float32, device=dev)
-        self._fields = (_lib.StageField * _lib.FN_MAX_STAGE_FIELDS)()
-        for i, (name, space, kind, width, hi, mod) in enumerate(self._desc):
-            f = self._fields[i]
-            f.dst, f.cap, f.width, f.kind, f.pad_hi, f.pad_mod = self.t[name].data_ptr(), shapes.cap[space], width, kind, hi, mod
-        self._mask_spaces = list(MASKS)
-        for q, space in enumerate(self._mask_spaces):
-            m = self._fields[len(self._desc) + q]
-            m.dst, m.cap, m.width, m.kind, m.pad_hi, m.pad_mod = self.t[MASKS[space]].data_ptr(), shapes.cap[space], 1, _lib.STAGE_MASK, 0, 1
         # device-side copy of the number of real molecules: the fused encoder kernels skip the padding behind them
         self.t[REAL_MOLS_KEY] = torch.zeros(1, dtype=torch.int32, device=dev)
-        c = self._fields[len(self._desc) + len(self._mask_spaces)]
-        c.dst, c.cap, c.width, c.kind, c.pad_hi, c.pad_mod = self.t[REAL_MOLS_KEY].data_ptr(), 1, 1, _lib.STAGE_COUNT, 0, 1
-        self.n_fields = len(self._desc) + len(self._mask_spaces) + 1
+        self._append(_lib.STAGE_COUNT, self.t[REAL_MOLS_KEY].data_ptr(), 1, refresh=("mol", None))
         if self.with_offsets:
-            o = self._fields[self.n_fields]
-            o.dst, o.cap, o.width, o.kind, o.pad_hi, o.pad_mod = self.t.offsets.data_ptr(), shapes.cap["mol"], len(SPACES), _lib.STAGE_OFFSETS, 0, 1
-            self._off_field = self.n_fields
-            self.n_fields += 1
+            self._append(_lib.STAGE_OFFSETS, self.t.offsets.data_ptr(), shapes.cap["mol"], len(SPACES), refresh=("mol", _OFFSETS))
         # molecule rows behind capacity - slack are padding in every batch that fits: the prediction head skips them
         self.t[LIVE_MOLS_KEY] = shapes.cap["mol"] - shapes.slack["mol"]
-        if self.n_fields > _lib.FN_MAX_STAGE_FIELDS:
-            raise ValueError("too many batch fields for one staging launch")
         self.counts: Optional[Dict[str, int]] = None
-        self._n_static = self.n_fields
-        self._extra_counts = []          # add_count: (field index, space)
+        self._n_static = self.n_fields       # set_bumps rewinds to here
+
+    def _append(self, kind, dst, cap, width=1, pad_hi=0, pad_mod=1, src=None, n_real=0, refresh=None) -> int:
+        """Fill the next entry of the staging table; its index.  ``refresh`` = (space, src source): load() rewrites n_real and src."""
+        if self.n_fields >= _lib.FN_MAX_STAGE_FIELDS:
+            raise ValueError("too many batch fields for one staging launch")
+        i, f = self.n_fields, self._fields[self.n_fields]
+        f.src, f.dst, f.n_real, f.cap, f.width, f.kind, f.pad_hi, f.pad_mod = src, dst, n_real, cap, width, kind, pad_hi, pad_mod
+        if refresh is not None:
+            self._refresh.append((f,) + refresh)
+        self.n_fields += 1
+        return i
 
     def add_count(self, space: str, key: str) -> torch.Tensor:
         """One more device-side count written by the staging launch: ``self.t[key]`` = int32 [1], the number of REAL rows of ``space``
         in the staged batch (the masked-atom sampler reads the real atom count there).  Before set_bumps."""
         if self.n_fields != self._n_static:
             raise RuntimeError("add_count comes before set_bumps")
-        if self.n_fields >= _lib.FN_MAX_STAGE_FIELDS:
-            raise ValueError("too many batch fields for one staging launch")
         self.t[key] = torch.zeros(1, dtype=torch.int32, device=self.device)
-        c = self._fields[self.n_fields]
-        c.src, c.dst, c.n_real, c.cap, c.width, c.kind, c.pad_hi, c.pad_mod = None, self.t[key].data_ptr(), 0, 1, 1, _lib.STAGE_COUNT, 0, 1
-        self._extra_counts.append((self.n_fields, space))
-        self.n_fields += 1
-        self._n_static = self.n_fields
+        self._n_static = self._append(_lib.STAGE_COUNT, self.t[key].data_ptr(), 1, refresh=(space, None)) + 1
         return self.t[key]
 
     def set_bumps(self, bumps, zeros=()):
@@ -313,14 +309,10 @@ class StaticBatch:
         ``zeros`` = [(device pointer, int32 count)]: workspaces it zeroes (FN_STAGE_ZERO: those of the plans built inside the
         graph).  The graph then needs no launch of its own for either."""
         self.n_fields = self._n_static
-        extra = [(None, t.data_ptr(), int(inc), 1, _lib.STAGE_BUMP) for t, inc in bumps] + \
-                [(None, int(ptr), 0, int(n), _lib.STAGE_ZERO) for ptr, n in zeros]
-        for src, dst, n_real, cap, kind in extra:
-            if self.n_fields >= _lib.FN_MAX_STAGE_FIELDS:
-                raise ValueError("too many batch fields for one staging launch")
-            f = self._fields[self.n_fields]
-            f.src, f.dst, f.n_real, f.cap, f.width, f.kind, f.pad_hi, f.pad_mod = src, dst, n_real, cap, 1, kind, 0, 1
-            self.n_fields += 1
+        for t, inc in bumps:
+            self._append(_lib.STAGE_BUMP, t.data_ptr(), 1, n_real=int(inc))
+        for ptr, n in zeros:
+            self._append(_lib.STAGE_ZERO, int(ptr), int(n))
 
     def load(self, batch: Dict[str, torch.Tensor]) -> bool:
         """Stage ``batch`` (GPU tensors); False when it does not fit the capacities (nothing is written then)."""
@@ -329,34 +321,92 @@ class StaticBatch:
             return False
         if self.collated and not isinstance(batch, CollatedBatch):
             return False        # no layout promise: the caller's eager step takes the general kernels
+        off = batch.offsets if self.with_offsets else None
         if self.with_offsets:
-            off = batch.offsets
             if off is None or not off.is_cuda or batch.max_per_mol is None:
                 return False
             off = off if off.is_contiguous() else off.contiguous()
-            o = self._fields[self._off_field]
-            o.src, o.n_real = off.data_ptr(), counts["mol"]
-        keep = []
-        for i, (name, space, kind, width, hi, mod) in enumerate(self._desc):
-            src = batch[name]
-            if not src.is_cuda:
-                raise _lib.FragnetHipError(f"{name} must live on the GPU to be staged (got {src.device})")
-            if not src.is_contiguous():
-                src = src.contiguous()
-                keep.append(src)
-            f = self._fields[i]
-            f.src, f.n_real = src.data_ptr(), counts[space]
-        for q, space in enumerate(self._mask_spaces):
-            m = self._fields[len(self._desc) + q]
-            m.src, m.n_real = None, counts[space]
-        c = self._fields[len(self._desc) + len(self._mask_spaces)]
-        c.src, c.n_real = None, counts["mol"]
-        for i, space in self._extra_counts:
-            self._fields[i].n_real = counts[space]
+        keep = [off]            # alive until the launch has run
+        for f, space, key in self._refresh:
+            if key is _OFFSETS:
+                f.src = off.data_ptr()
+            elif key is not None:
+                src = batch[key]
+                if not src.is_cuda:
+                    raise _lib.FragnetHipError(f"{key} must live on the GPU to be staged (got {src.device})")
+                if not src.is_contiguous():
+                    src = src.contiguous()
+                    keep.append(src)
+                f.src = src.data_ptr()
+            f.n_real = counts[space]
         _lib.call("fn_stage_padded", self._fields, self.n_fields, torch.cuda.current_stream(self.device).cuda_stream)
-        self.counts = counts
-        self._keep = (keep, batch.offsets if self.with_offsets else None)       # alive until the launch has run
+        self.counts, self._keep = counts, keep
         return True
+
+
+def _warm_up(device, fn, warmup: int):
+    """``fn`` ``warmup`` times on a side stream (a capture must not be the first run of anything), joined and finished."""
+    side = torch.cuda.Stream(device)
+    side.wait_stream(torch.cuda.current_stream(device))
+    with torch.cuda.stream(side):
+        for _ in range(warmup):
+            fn()
+    torch.cuda.current_stream(device).wait_stream(side)
+    torch.cuda.synchronize(device)
+
+
+class ReplayCounter:
+    """One Philox stream inside a captured step: the stream, its device word (``word``: int64 [1], added by the kernels to every offset
+    they are handed), the host offset the capture started from (``base``: the offsets baked into the graph count from it), the blocks
+    one step draws (``per_step``, fixed by the static shapes) and whether the staging launch in front of every replay moves the word on
+    (``staged``: the single-graph step; the two-graph step advances the word inside its first graph).
+
+    Invariant: between replays the device counter is ONE STEP BEHIND when ``staged`` is set -- the staging launch in front of every
+    replay moves it on, which is why it starts at -per_step: the first replay sees 0 -- so anything that replays without staging (or
+    stages without replaying) must go through GraphedTrainStep.replay(), and a step that runs outside the graph goes through eager()."""
+
+    def __init__(self, stream, word: torch.Tensor, what: str = "Philox"):
+        self.stream, self.word, self.what = stream, word, what
+        stream.dev = word
+        self.base, self.per_step, self.staged = 0, 0, False
+
+    def mark(self):
+        self.base = self.stream.offset           # a warm-up step, or the capture, starts here
+
+    def drawn(self) -> int:
+        return self.stream.offset - self.base
+
+    def measure(self):
+        self.per_step = self.drawn()             # a warm-up step that began at mark() has run: every step draws what it drew
+
+    def check(self):
+        if self.drawn() != self.per_step:
+            raise RuntimeError(f"the captured step drew a different number of {self.what} blocks than the warm-up steps")
+
+    def stage(self):
+        """The staging launch moves the word from now on: its (tensor, increment) bump entry, or None for a step that draws nothing."""
+        self.staged = True
+        if not self.per_step:
+            return None
+        self.word -= self.per_step
+        return self.word, self.per_step
+
+    @staticmethod
+    @contextlib.contextmanager
+    def eager(*counters: "ReplayCounter"):
+        """Around a step that runs outside the graph: it draws from the base offsets the captured step has baked in -- the word, which the
+        eager kernels add as well, makes them this step's own -- and afterwards the word has moved past all it drew: fallback steps and
+        replays never share Philox blocks.  The host offsets come back as they were.  Several counters: each half in the order given."""
+        held = [(c, c.stream.offset, c.per_step if c.staged else 0) for c in counters]      # (.., host offset, blocks the word is behind)
+        for c, _, behind in held:
+            c.stream.offset = c.base
+            if behind:                           # the staging launch would have moved it on
+                c.word += behind
+        yield
+        for c, after, behind in held:
+            if c.drawn() - behind:
+                c.word += c.drawn() - behind
+            c.stream.offset = after
 
 
 class GraphedTrainStep:
@@ -392,38 +442,33 @@ class GraphedTrainStep:
         if loss == "pretrain" and hasattr(getattr(model, "head", None), "need_bond_length"):
             model.head.need_bond_length = False      # the loss never reads the bond-length prediction (pretrain_utils.py:17-24)
         self.rng = model.pretrain.rng
-        # [Philox blocks consumed, Adam steps done]: one captured vector add moves both on every replay
+        # [Philox blocks consumed, Adam steps done]: the staging launch in front of every replay moves both on (FN_STAGE_BUMP).  The first
+        # word is the dropout stream's (``rng.dev``), the second the step count the captured Adam reads (_sync_adam_state)
         self._counters = torch.zeros(2, dtype=torch.int64, device=self.device)
-        self.rng.dev = self._counters[0:1]
+        self.rng_counter = ReplayCounter(self.rng, self._counters[0:1])
         import torch.distributed as dist
-        single = (not (dist.is_available() and dist.is_initialized()) or dist.get_world_size(group) == 1) and not self.force_distributed
+        # the ranks exchange gradients and loss weights: more than one of them, or a 1-rank group made to (force_distributed)
+        self._distributed = dist.is_available() and dist.is_initialized() and (dist.get_world_size(group) > 1 or self.force_distributed)
         # one rank, fused HIP Adam: the update is captured too (step count and learning rate live in device memory)
-        self.adam_in_graph = bool(capture_adam) and single and getattr(opt, "opt", 1) is None
+        self.adam_in_graph = bool(capture_adam) and not self._distributed and not self.force_distributed and getattr(opt, "opt", 1) is None
         self._lr_dev = torch.zeros(1, dtype=torch.float32, device=self.device)
-        self._lr_host = None
-        self._dev_steps = -1
-        self.graph: Optional[torch.cuda.CUDAGraph] = None
+        self._lr_host, self._dev_steps = None, -1
+        self.graph = self.graph_b = None             # torch.cuda.CUDAGraph: the step; the encoder backward of a two-graph step
         self.loss: Optional[torch.Tensor] = None
         self.replays = self.fallbacks = 0
-        # Philox bookkeeping of the captured step (set by _capture): the host offset the capture started from, the blocks one
-        # step draws, and whether the staging launch advances the device counters (single-graph step).  Invariant: between
-        # replays the device counter is ONE STEP BEHIND when _stage_bumps is set -- the staging launch in front of every
-        # replay moves it on -- so anything that replays without staging (or stages without replaying) must go through replay()
-        self._rng_base, self._per_step, self._stage_bumps = 0, 0, False
         # a masked-atom model (FragNetPreTrainMasked2) draws its row mask inside the step, from a stream of its own: the sampler launch is
-        # captured behind the staging / plan launches, reads the real atom count the staging launch writes, and its device counter is kept
-        # exactly like the dropout counter's (baked host offset + a device word the staging launch moves on; the same invariant)
+        # captured behind the staging / plan launches, reads the real atom count the staging launch writes, and its device word is kept
+        # exactly like the dropout stream's (a second ReplayCounter)
         self.mask_rng = getattr(model, "mask_rng", None) if loss == "pretrain" else None
-        self._mask_base, self._mask_per_step = 0, 0
+        self.mask_counter: Optional[ReplayCounter] = None
         self.keep_mask: Optional[torch.Tensor] = None      # the latest step's mask (uint8 [atom capacity]): a persistent buffer, for tests and tools
         if self.mask_rng is not None:
-            self._mask_counter = torch.zeros(1, dtype=torch.int64, device=self.device)
-            self.mask_rng.dev = self._mask_counter
+            self.mask_counter = ReplayCounter(self.mask_rng, torch.zeros(1, dtype=torch.int64, device=self.device), "mask")
             self.static.add_count("atom", REAL_ATOMS_KEY)
             self.keep_mask = model.keep_buffer = torch.ones(shapes.cap["atom"], dtype=torch.uint8, device=self.device)
+        self._stream_counters = [c for c in (self.rng_counter, self.mask_counter) if c is not None]      # dropout first: the order of their launches
         from . import ops
         self._unit = ops.unit_grad(self.static.device)
-        self.graph_b: Optional[torch.cuda.CUDAGraph] = None
         self.head_off = self._head_offset()
         self.split = bool(overlap) and self.head_off is not None
         self._rider_lo: Optional[int] = None         # set by the warm-up steps of _capture: where the Adam slice that may ride starts
@@ -453,30 +498,21 @@ class GraphedTrainStep:
                 return False
         return True
 
-    def _part_a(self):
-        """forward, loss, and the backward pass of loss + head; leaves d loss / d pooled in ``leaf.grad``."""
-        from .model import _KEEP_EDGE_OUTPUTS, pooled
+    def _static_loss(self, predict):
+        """The staged batch without a plan (every step builds its own, inside the graph) -> ``predict(batch)`` -> the loss.  A
+        predictor-stack head is told the targets first (``loss_spec``): its last Linear, the loss and that Linear's backward then
+        share one launch (ops.mlp_head) and the predictions come back with the loss attached; every other head, and a stack the
+        fused launch does not cover, goes through the loss kernel of its own."""
         sb = self.static.t
         sb.pop(PLAN_KEY, None)
-        x_atoms, x_frags, _, _ = self.model.pretrain(sb, edge_outputs=_KEEP_EDGE_OUTPUTS)
-        pooled_t = pooled(x_atoms, x_frags, sb)
-        leaf = pooled_t.detach().requires_grad_(True)
-        self.model.fthead.live_rows = sb.get(LIVE_MOLS_KEY)
-        loss = self._head_loss(lambda: self.model.fthead(leaf), sb["y"], sb[MASK_KEY])
-        loss.backward(gradient=self._unit)
-        return loss, pooled_t, leaf
-
-    def _head_loss(self, run, y, w):
-        """predictions -> loss.  A predictor-stack head is told the targets first (``loss_spec``): its last Linear, the loss and that
-        Linear's backward then share one launch (ops.mlp_head) and the predictions come back with the loss attached; every other
-        head, and a stack the fused launch does not cover, goes through the loss kernel of its own."""
-        head = getattr(self.model, "fthead", None)
+        if self.loss_kind == "pretrain":            # single-graph step only: a pretrain model has no head to split at
+            return masked_pretrain_loss(predict(sb), sb)
+        y, w, head = sb["y"], sb[MASK_KEY], getattr(self.model, "fthead", None)
         armed = head is not None and hasattr(head, "loss_spec") and y.is_cuda
         if armed:
-            from . import _lib
             head.loss_spec = (_lib.LOSS_MSE if self.loss_kind == "regr" else _lib.LOSS_BCE, y, w)
         try:
-            out = run()
+            out = predict(sb)
         finally:
             if armed:
                 head.loss_spec = None
@@ -484,6 +520,22 @@ class GraphedTrainStep:
         if fused is not None and fused[1] is y and fused[2] is w:
             return fused[0]
         return self._masked(out, y, w)
+
+    def _part_a(self):
+        """forward, loss, and the backward pass of loss + head; leaves d loss / d pooled in ``leaf.grad``."""
+        from .model import _KEEP_EDGE_OUTPUTS, pooled
+        pooled_t = leaf = None
+
+        def head_on_leaf(sb):
+            nonlocal pooled_t, leaf
+            x_atoms, x_frags, _, _ = self.model.pretrain(sb, edge_outputs=_KEEP_EDGE_OUTPUTS)
+            pooled_t = pooled(x_atoms, x_frags, sb)
+            leaf = pooled_t.detach().requires_grad_(True)
+            self.model.fthead.live_rows = sb.get(LIVE_MOLS_KEY)
+            return self.model.fthead(leaf)
+        loss = self._static_loss(head_on_leaf)
+        loss.backward(gradient=self._unit)
+        return loss, pooled_t, leaf
 
     def _part_b(self, pooled_t, leaf):
         pooled_t.backward(leaf.grad)
@@ -493,12 +545,7 @@ class GraphedTrainStep:
         """forward, loss, backward, gradients gathered.  ``ride_adam`` (the captured single-graph step with Adam inside): the
         head's slice of the Adam update -- its gradients are complete once the head's backward has run -- rides in the encoder
         backward's last launch; returns (loss, first element of the flat buffer that rode, or None)."""
-        sb = self.static.t
-        sb.pop(PLAN_KEY, None)                      # every step builds its own graph plan (inside the graph)
-        if self.loss_kind == "pretrain":
-            loss = masked_pretrain_loss(self.model(sb), sb)
-        else:
-            loss = self._head_loss(lambda: self.model(sb), sb["y"], sb[MASK_KEY])
+        loss = self._static_loss(self.model)
         rode = None
         if ride_adam and ADAM_RIDER and self._rider_lo is not None:
             from . import engine
@@ -519,46 +566,37 @@ class GraphedTrainStep:
             raise RuntimeError("GraphedTrainStep captures a TRAINING step: call model.train() first")
         if not self.static.load(example):
             raise ValueError(f"the example batch {batch_counts(example)} does not fit {self.shapes}")
-        side = torch.cuda.Stream(self.device)
-        side.wait_stream(torch.cuda.current_stream(self.device))
-        per_step = 0
-        with torch.cuda.stream(side):
-            for _ in range(warmup):
-                self.opt.zero_grad()
-                before = self.rng.offset
-                mask_before = self.mask_rng.offset if self.mask_rng is not None else 0
-                if self.split:
-                    _, pooled_t, leaf = self._part_a()
-                    if not self._head_grads_in_place():      # e.g. a non-ReLU head (torch's own backward): one graph
-                        self.split = False
-                    self._part_b(pooled_t, leaf)
-                    del pooled_t, leaf
-                else:
-                    self._fwd_bwd_static()
-                    # may the head's Adam slice ride in the encoder's backward?  Only if its gradients sit in the flat buffer already
-                    # when that backward starts (the fused head writes them there) and its parameters are the buffer's tail
-                    off = self._head_offset()
-                    self._rider_lo = off if (off is not None and off % 4 == 0 and self._head_grads_in_place()) else None
-                per_step = self.rng.offset - before              # Philox blocks one step draws (fixed by the static shapes)
-                if self.mask_rng is not None:
-                    self._mask_per_step = self.mask_rng.offset - mask_before
-        torch.cuda.current_stream(self.device).wait_stream(side)
-        torch.cuda.synchronize(self.device)
+
+        def warm_step():
+            self.opt.zero_grad()
+            for c in self._stream_counters:
+                c.mark()
+            if self.split:
+                _, pooled_t, leaf = self._part_a()
+                if not self._head_grads_in_place():      # e.g. a non-ReLU head (torch's own backward): one graph
+                    self.split = False
+                self._part_b(pooled_t, leaf)
+            else:
+                self._fwd_bwd_static()
+                # may the head's Adam slice ride in the encoder's backward?  Only if its gradients sit in the flat buffer already
+                # when that backward starts (the fused head writes them there) and its parameters are the buffer's tail
+                off = self._head_offset()
+                self._rider_lo = off if (off is not None and off % 4 == 0 and self._head_grads_in_place()) else None
+            for c in self._stream_counters:
+                c.measure()                              # Philox blocks one step draws (fixed by the static shapes)
+        _warm_up(self.device, warm_step, warmup)
         self.opt.zero_grad()
         if self.split:
             self.adam_in_graph = False
-        # what one replay adds to [Philox blocks consumed, Adam steps done]; built here because a captured region cannot copy from the host
-        inc = self._inc = torch.tensor([per_step, 1 if self.adam_in_graph else 0], dtype=torch.int64, device=self.device)      # kept alive: replays read it
         self._sync_adam_state()
         graph = torch.cuda.CUDAGraph()
-        off0 = self._rng_base = self.rng.offset
-        if self.mask_rng is not None:
-            self._mask_base = self.mask_rng.offset
+        for c in self._stream_counters:
+            c.mark()
         if self.split:
             pool = torch.cuda.graph_pool_handle()
             with torch.cuda.graph(graph, pool=pool, capture_error_mode=_CAPTURE_MODE):
                 loss, pooled_t, leaf = self._part_a()
-                consumed = self.rng.offset - off0
+                consumed = self.rng_counter.drawn()
                 if consumed:
                     self.rng.advance_device(consumed)
             self.graph_b = torch.cuda.CUDAGraph()
@@ -569,30 +607,18 @@ class GraphedTrainStep:
             # plans built inside the capture skip their zeroing launch: the staging launch zeroes their workspaces (below)
             with prezeroed_plans() as pz, torch.cuda.graph(graph, capture_error_mode=_CAPTURE_MODE):
                 loss, rode = self._fwd_bwd_static(ride_adam=self.adam_in_graph)
-                if self.rng.offset - off0 != per_step:
-                    raise RuntimeError("the captured step drew a different number of Philox blocks than the warm-up steps")
-                if self.mask_rng is not None and self.mask_rng.offset - self._mask_base != self._mask_per_step:
-                    raise RuntimeError("the captured step drew a different number of mask blocks than the warm-up steps")
+                for c in self._stream_counters:
+                    c.check()
                 # fresh dropout masks and the next Adam step number on every replay: the staging launch in front of the replay
-                # advances both counters (FN_STAGE_BUMP), so the graph has no launch of its own for them
+                # advances the counters (FN_STAGE_BUMP), so the graph has no launch of its own for them
                 if self.adam_in_graph:
                     self.opt.adam_in_graph(self._counters[1:2], self._lr_dev, 0, rode)      # what did not ride in the backward
-        self.graph, self.loss = graph, loss.detach()
-        # single-graph step: the staging launch in front of every replay advances the counters.  The Philox counter is
-        # therefore "one step behind" between replays (it starts at -per_step so that the first replay sees 0).
-        self._per_step, self._stage_bumps = int(per_step), not self.split
-        if self._stage_bumps:
-            bumps = []
-            if per_step:
-                bumps.append((self._counters[0:1], per_step))
-                self._counters[0:1] -= per_step
+            bumps = [c.stage() for c in self._stream_counters]
             if self.adam_in_graph:
-                bumps.append((self._counters[1:2], 1))
-            if self.mask_rng is not None and self._mask_per_step:
-                bumps.append((self._mask_counter, self._mask_per_step))
-                self._mask_counter -= self._mask_per_step
+                bumps.insert(1, (self._counters[1:2], 1))        # the table's order: dropout blocks, Adam steps, mask blocks
             self._captured_plans = pz.plans          # keep their arenas (the regions below) alive with the graph
-            self.static.set_bumps(bumps, zeros=[r for plan in pz.plans for r in plan.zero_regions])
+            self.static.set_bumps([b for b in bumps if b is not None], zeros=[r for plan in pz.plans for r in plan.zero_regions])
+        self.graph, self.loss = graph, loss.detach()
 
     def _sync_adam_state(self):
         """Device copies of the optimiser's step count and learning rate follow the host values (an eager fallback step,
@@ -609,10 +635,9 @@ class GraphedTrainStep:
 
     def _rank_scales(self, batch) -> Optional[torch.Tensor]:
         """(per-edge, per-atom) loss weights local_count * world / global_count as a device tensor (no host sync)."""
-        import torch.distributed as dist
-        if self.loss_kind != "pretrain" or not (dist.is_available() and dist.is_initialized()) or \
-                (dist.get_world_size(self.group) == 1 and not self.force_distributed):
+        if self.loss_kind != "pretrain" or not self._distributed:
             return None
+        import torch.distributed as dist
         local = torch.tensor([float(batch["dh_angl"].shape[0]), float(batch["bnd_angl"].shape[0])], device=self.device)
         total = local.clone()
         dist.all_reduce(total, op=dist.ReduceOp.SUM, group=self.group)
@@ -620,50 +645,30 @@ class GraphedTrainStep:
 
     def _eager(self, batch):
         self.opt.zero_grad()
-        # draw from the same base offsets the captured step has baked in (the device counter, which the eager kernels add as
-        # well, makes them this step's own), then move the device counter past what was drawn: fallback steps and replays
-        # never share Philox blocks
-        host_after = self.rng.offset
-        self.rng.offset = self._rng_base
-        behind = self._per_step if self._stage_bumps else 0      # see _capture: the staging launch bumps the counter
-        if behind:
-            self._counters[0:1] += behind
-        mask_after = mask_behind = 0
-        if self.mask_rng is not None:        # the mask stream, the same way: this step's masks come from where the replay's would
-            mask_after, self.mask_rng.offset = self.mask_rng.offset, self._mask_base
-            mask_behind = self._mask_per_step if self._stage_bumps else 0
-            if mask_behind:
-                self._mask_counter += mask_behind
-        if self.loss_kind == "pretrain":
-            from .train import pretrain_loss
-            sc = self._rank_scales(batch)
-            loss = pretrain_loss(self.model(batch), batch, (1.0, 1.0) if sc is None else (sc[0], sc[1]))
-        else:
-            out = self.model(batch)
-            w = torch.ones(batch["y"].shape[0], dtype=torch.float32, device=out.device)
-            loss = self._masked(out, batch["y"], w)
-        loss.backward()
-        if self.split:
-            # the ranks that replay the two graphs issue two slice all-reduces (head, then encoder): a rank that fell back to
-            # the eager step must issue the same collectives, in the same order and sizes
-            self.opt.gather_grads()
-            self.opt.all_reduce_slice(self.head_off, None, self.group)
-            self.opt.all_reduce_slice(0, self.head_off, self.group)
-            self.opt.apply_gathered(self.group, reduced=True)
-        else:
-            self.opt.step(self.group)
-        # Philox blocks this eager step drew are gone for the replays too: without this the fallback step and the replay after
-        # next would share dropout random numbers (the graph adds the device counter to offsets baked in at capture)
-        drawn = self.rng.offset - self._rng_base
-        if drawn - behind:
-            self._counters[0:1] += drawn - behind
-        self.rng.offset = host_after
-        if self.mask_rng is not None:
-            mask_drawn = self.mask_rng.offset - self._mask_base
-            if mask_drawn - mask_behind:
-                self._mask_counter += mask_drawn - mask_behind
-            self.mask_rng.offset = mask_after
+        with ReplayCounter.eager(*self._stream_counters):
+            if self.loss_kind == "pretrain":
+                from .train import pretrain_loss
+                sc = self._rank_scales(batch)
+                loss = pretrain_loss(self.model(batch), batch, (1.0, 1.0) if sc is None else (sc[0], sc[1]))
+            else:
+                out = self.model(batch)
+                w = torch.ones(batch["y"].shape[0], dtype=torch.float32, device=out.device)
+                loss = self._masked(out, batch["y"], w)
+            loss.backward()
+            if self.split:
+                # the ranks that replay the two graphs issue two slice all-reduces (head, then encoder): a rank that fell back to
+                # the eager step must issue the same collectives, in the same order and sizes
+                self.opt.gather_grads()
+                self.opt.all_reduce_slice(self.head_off, None, self.group)
+                self.opt.all_reduce_slice(0, self.head_off, self.group)
+                self.opt.apply_gathered(self.group, reduced=True)
+            else:
+                self.opt.step(self.group)
         return loss.detach()
+
+    def _count_adam_step(self):      # the update ran inside the graph: the host's counts follow the device word the staging launch moved
+        self.opt.steps += 1
+        self._dev_steps += 1
 
     def replay(self, batch: Dict[str, torch.Tensor]) -> bool:
         """Stage ``batch`` and replay the captured graph(s) -- always as a pair: the staging launch zeroes the plan workspaces
@@ -677,8 +682,7 @@ class GraphedTrainStep:
         if self.graph_b is not None:
             self.graph_b.replay()
         if self.adam_in_graph:
-            self.opt.steps += 1
-            self._dev_steps += 1
+            self._count_adam_step()
         self.replays += 1
         return True
 
@@ -692,9 +696,8 @@ class GraphedTrainStep:
         if sc is not None:
             self.static.t[SCALE_KEY].copy_(sc)
         self.graph.replay()
-        if self.adam_in_graph:                       # the update ran inside the graph
-            self.opt.steps += 1
-            self._dev_steps += 1
+        if self.adam_in_graph:
+            self._count_adam_step()
         elif self.split:
             head = self.opt.all_reduce_slice(self.head_off, None, self.group, async_op=True)     # beside graph_b
             self.graph_b.replay()
@@ -725,13 +728,8 @@ class GraphedForward:
         self.replays = self.fallbacks = 0
         if not self.static.load(example):
             raise ValueError(f"the example batch {batch_counts(example)} does not fit {self.shapes}")
-        side = torch.cuda.Stream(self.device)
-        side.wait_stream(torch.cuda.current_stream(self.device))
-        with torch.cuda.stream(side), torch.no_grad():
-            for _ in range(warmup):
-                self._run()
-        torch.cuda.current_stream(self.device).wait_stream(side)
-        torch.cuda.synchronize(self.device)
+        with torch.no_grad():
+            _warm_up(self.device, self._run, warmup)
         self.graph = torch.cuda.CUDAGraph()
         with torch.no_grad(), torch.cuda.graph(self.graph, capture_error_mode=_CAPTURE_MODE):
             self.out = self._run()

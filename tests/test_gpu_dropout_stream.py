@@ -309,7 +309,8 @@ def test_captured_steps_and_the_eager_fallback_never_share_a_block(monkeypatch):
             model, lambda: torch.nn.functional.mse_loss(model(dict(bs[0])).view(-1), bs[0]["y"]).backward(), lr=0.0)
         shapes = graphstep.StaticShapes.from_batches(bs, margin=0.05)
         step = graphstep.GraphedTrainStep(model, opt, shapes, dict(bs[0]), loss="regr")
-    base, per_step, behind = step._rng_base, step._per_step, (step._per_step if step._stage_bumps else 0)
+    drop = step.rng_counter
+    base, per_step, behind = drop.base, drop.per_step, (drop.per_step if drop.staged else 0)
     captured = log.calls[-5:]                                 # the draws made inside the capture: the offsets baked into the graph
     assert per_step > 0 and _intervals(captured)[0][0] == base
     assert _assert_back_to_back(_intervals(captured), base) == base + per_step
@@ -335,7 +336,7 @@ def test_captured_steps_and_the_eager_fallback_never_share_a_block(monkeypatch):
             assert drawn > per_step                           # it is a larger batch
         else:
             loss = float(step(dict(b)))
-            c = counter() if step._stage_bumps else before
+            c = counter() if drop.staged else before
             drawn = per_step
         torch.cuda.synchronize()
         ranges.append((base + c, base + c + drawn))

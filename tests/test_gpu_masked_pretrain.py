@@ -332,7 +332,7 @@ def test_captured_masked_step_replays_what_the_eager_step_computes():
         model.mask_rng.offset = model.pretrain.rng.offset = 0         # the probe drew from both streams: the twins start alike
         steps.append(graphstep.GraphedTrainStep(model, opt, shapes, dict(batches[0]), loss="pretrain"))
     step_a, step_b = steps
-    assert step_a.adam_in_graph and step_a._stage_bumps and step_a._mask_per_step == (shapes.cap["atom"] + 3) // 4
+    assert step_a.adam_in_graph and step_a.rng_counter.staged and step_a.mask_counter.staged and step_a.mask_counter.per_step == (shapes.cap["atom"] + 3) // 4
     assert model_a.mask_rng.seed == model_b.mask_rng.seed != model_a.pretrain.rng.seed
     assert torch.equal(step_a.opt.flat, step_b.opt.flat)
     cap = shapes.cap["atom"]
@@ -340,12 +340,11 @@ def test_captured_masked_step_replays_what_the_eager_step_computes():
     def eager_static(step, batch):
         step._sync_adam_state()
         assert step.static.load(batch)              # the staging launch: pads, writes the counts, moves the three counters on
-        step.rng.offset, step.mask_rng.offset = step._rng_base, step._mask_base
+        step.rng.offset, step.mask_rng.offset = step.rng_counter.base, step.mask_counter.base
         step.opt.zero_grad()
         loss, _ = step._fwd_bwd_static()
         step.opt.adam_in_graph(step._counters[1:2], step._lr_dev)
-        step.opt.steps += 1
-        step._dev_steps += 1
+        step._count_adam_step()
         return loss.detach().clone()
 
     previous = None
@@ -356,10 +355,10 @@ def test_captured_masked_step_replays_what_the_eager_step_computes():
         assert torch.equal(loss_a, loss_b), (t, float(loss_a), float(loss_b))
         assert torch.equal(step_a.opt.flat, step_b.opt.flat), t
         n_real = b["x_atoms"].shape[0]
-        assert int(step_a.static.t[REAL_ATOMS_KEY]) == n_real and int(step_a._mask_counter) == t * step_a._mask_per_step
+        assert int(step_a.static.t[REAL_ATOMS_KEY]) == n_real and int(step_a.mask_counter.word) == t * step_a.mask_counter.per_step
         mask = step_a.keep_mask.cpu().numpy()
         assert mask.shape == (cap,) and int(mask[:n_real].sum()) == int(n_real * 0.85) and bool(mask[n_real:].all())
-        want = rs.sample(cap, 0.85, model_a.mask_rng.seed, step_a._mask_base + t * step_a._mask_per_step, n=n_real)
+        want = rs.sample(cap, 0.85, model_a.mask_rng.seed, step_a.mask_counter.base + t * step_a.mask_counter.per_step, n=n_real)
         assert np.array_equal(mask, want), t
         assert np.array_equal(step_b.keep_mask.cpu().numpy(), mask), t
         assert previous is None or not np.array_equal(previous[:20], mask[:20])
@@ -370,9 +369,9 @@ def test_captured_masked_step_replays_what_the_eager_step_computes():
     step_a(dict(big))
     assert step_a.fallbacks == 1
     n_big = big["x_atoms"].shape[0]
-    want = rs.sample(n_big, 0.85, model_a.mask_rng.seed, step_a._mask_base + 4 * step_a._mask_per_step)
+    want = rs.sample(n_big, 0.85, model_a.mask_rng.seed, step_a.mask_counter.base + 4 * step_a.mask_counter.per_step)
     assert np.array_equal(model_a.last_keep.cpu().numpy(), want)
     # and the replay after it shares no mask block with it
     step_a(dict(batches[0]))
-    assert (n_big + 3) // 4 > step_a._mask_per_step
-    assert int(step_a._mask_counter) == 4 * step_a._mask_per_step + (n_big + 3) // 4
+    assert (n_big + 3) // 4 > step_a.mask_counter.per_step
+    assert int(step_a.mask_counter.word) == 4 * step_a.mask_counter.per_step + (n_big + 3) // 4
