@@ -81,6 +81,7 @@ class StageField(C.Structure):
 
 FN_MAX_STAGE_FIELDS = 40
 STAGE_ROWS, STAGE_IDS, STAGE_COLS, STAGE_MASK, STAGE_COUNT, STAGE_BUMP, STAGE_ZERO, STAGE_OFFSETS = 0, 1, 2, 3, 4, 5, 6, 7
+STAGE_ROWS_I64 = 8
 PLAN_PREZEROED = 1
 
 
@@ -259,6 +260,7 @@ SIGNATURES = {
 for _fam in ("fn_cdrp_pair", "fn_dta_pair"):
     SIGNATURES[_fam + "_loss_ws"] = [i64]
     SIGNATURES[_fam + "_fwd_f32"] = [vp] * 11 + [i64] * 5 + [vp]
+    SIGNATURES[_fam + "_fwd_rows_f32"] = [vp] * 11 + [i64] * 5 + [vp, vp]      # + the device-side real-row count of a static-shape step
     SIGNATURES[_fam + "_bwd_f32"] = [vp] * 13 + [i64, vp] + [i64] * 5 + [vp]
     # the same head on a factored batch (csrc/pair_factored.hip): unique rows, pair lists, pair orderings
     SIGNATURES[_fam + "_factored_ws"] = [i64, i64]

@@ -303,6 +303,12 @@ __global__ void k_stage_padded(StageFields F) {
         } else {
             for (int64_t i = t0; i < all; i += stride) dst[i] = i < real ? src[i] : 0.f;
         }
+    } else if (f.kind == FN_STAGE_ROWS_I64) {
+        // rows are contiguous: one flat array of 8-byte words (both pointers are 8-byte aligned: fn_stage_padded checks), zeros behind the real ones
+        const int64_t* src = static_cast<const int64_t*>(f.src);
+        int64_t* dst = static_cast<int64_t*>(f.dst);
+        const int64_t real = f.n_real * f.width, all = f.cap * f.width;
+        for (int64_t i = t0; i < all; i += stride) dst[i] = i < real ? src[i] : 0;
     } else if (f.kind == FN_STAGE_MASK) {
         float* dst = static_cast<float*>(f.dst);
         for (int64_t i = t0; i < f.cap; i += stride) dst[i] = i < f.n_real ? 1.f : 0.f;
@@ -505,6 +511,14 @@ int fn_stage_padded(const fn_stage_field* fields, int n_fields, fn_stream_t stre
             if (f.n_real < 0 || !f.dst) return fail(FN_EINVAL, "fn_stage_padded: bad count field");
             F.f[i] = f;
             take(i, 1);
+            continue;
+        }
+        if (f.kind == FN_STAGE_ROWS_I64) {      // FN_STAGE_ROWS's checks, and 8-byte alignment of both tables
+            if (f.n_real < 0 || f.cap < f.n_real || f.width < 1 || (f.cap > 0 && !f.dst) || (f.n_real > 0 && !f.src) ||
+                (((uintptr_t)f.src | (uintptr_t)f.dst) & 7))
+                return fail(FN_EINVAL, "fn_stage_padded: bad int64 rows field");
+            F.f[i] = f;
+            take(i, (f.cap * f.width + 1) / 2);      // a work item = 16 bytes = two words
             continue;
         }
         if (f.n_real < 0 || f.cap < f.n_real || f.width < 1 || f.kind < 0 || f.kind > FN_STAGE_MASK || (f.cap > 0 && !f.dst) ||

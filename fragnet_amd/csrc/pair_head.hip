@@ -30,11 +30,16 @@ constexpr int kPairRows = 16, kPairBwdRows = 32;
 // columns [32 w, + 32) of h over the (256 + K1)-long reduction: 16 full steps of the drug half, then the full steps of the second half
 // and, where K1 is no multiple of 16, one of which the quarters behind K1 are masked; out from the tile in LDS: 16 lanes per row,
 // 8 products each, added across the lanes in a fixed order.
+// real_rows (nullable; fn_*_pair_fwd_rows_f32): the int32 word a static-shape step's staging launch writes (FN_STAGE_COUNT), n = *real_rows
+// clamped to [0, M].  The mean is then over the first n rows: g = 2 (out - y) / n and the partials are divided by n there, g = 0 exactly
+// and no share of the loss behind them (their out is still written); n = 0: every g and every partial is 0, nothing is divided.  The
+// backward needs no count: a zero g makes every term of a padding row an exact zero, in the same place of the same sums.
 template <int K1>
 __global__ __launch_bounds__(256) void k_pair_fwd(const float* __restrict__ drug, const float* __restrict__ x1, const float* __restrict__ W1,
                                                   const float* __restrict__ b1, const float* __restrict__ w2, const float* __restrict__ b2,
                                                   const float* __restrict__ target, float* __restrict__ h, float* __restrict__ out,
-                                                  float* __restrict__ g, float* __restrict__ loss_part, int M) {
+                                                  float* __restrict__ g, float* __restrict__ loss_part, int M,
+                                                  const int* __restrict__ real_rows) {
     constexpr int kInT = kIn0 + K1, kfull = K1 & ~15, kUnroll1 = kfull < K1 ? 2 : 4;
     __shared__ float sh[kPairRows][kHid + 1];
     __shared__ float sd[kPairRows];
@@ -72,6 +77,7 @@ __global__ __launch_bounds__(256) void k_pair_fwd(const float* __restrict__ drug
     }
     __syncthreads();
     const int r = threadIdx.x >> 4, sub = threadIdx.x & 15;
+    const int nr = real_rows ? min(max(*real_rows, 0), M) : M;      // rows the loss is a mean over: all of them without a count
     float t = 0.f;                                                   // the tile-row dot: the same statements, the same order as k_pairf_fwd's
 #pragma unroll
     for (int c = 0; c < kHid / 16; ++c) t = fmaf(sh[r][sub + 16 * c], w2[sub + 16 * c], t);
@@ -82,9 +88,12 @@ __global__ __launch_bounds__(256) void k_pair_fwd(const float* __restrict__ drug
             const float o = t + b2[0];
             out[i0 + r] = o;
             if (target) {
-                const float d = o - target[i0 + r];
-                g[i0 + r] = 2.f * d / (float)M;
-                d2 = d * d;
+                if (i0 + r < nr) {
+                    const float d = o - target[i0 + r];
+                    g[i0 + r] = 2.f * d / (float)nr;
+                    d2 = d * d;
+                } else
+                    g[i0 + r] = 0.f;                                 // a padding row: no gradient, no share of the loss
             }
         }
         sd[r] = d2;
@@ -93,7 +102,7 @@ __global__ __launch_bounds__(256) void k_pair_fwd(const float* __restrict__ drug
     if (threadIdx.x == 0 && target) {
         float s = sd[0];
         for (int q = 1; q < kPairRows; ++q) s += sd[q];
-        loss_part[blockIdx.x] = s / (float)M;
+        loss_part[blockIdx.x] = nr > 0 ? s / (float)nr : 0.f;
     }
 }
 
@@ -178,14 +187,15 @@ int64_t pair_loss_ws(int64_t M) { return M > 0 ? (M + kPairRows - 1) / kPairRows
 template <int K1>
 int pair_fwd(const char* who, const float* drug, const float* x1, const float* W1, const float* b1, const float* w2, const float* b2,
              const float* target, float* h, float* out, float* g, float* loss_part, int64_t M, int64_t Kd, int64_t K, int64_t H, int64_t C,
-             fn_stream_t stream) {
+             const int32_t* real_rows, fn_stream_t stream) {
     FN_TRY(check_widths<K1>("pair_*_f32", Kd, K, H, C));
     if (M < 0 || M > FN_DENSE_MAX_ROWS) return fail_at(FN_EINVAL, who, "0 <= M <= FN_DENSE_MAX_ROWS");
     if (M == 0) return 0;
     if (!drug || !x1 || !W1 || !b1 || !w2 || !b2 || !h || !out || (target && (!g || !loss_part)) || misaligned(15, drug, x1, W1))
         return fail_at(FN_EINVAL, who, "null or misaligned buffer");
+    if (real_rows && (!target || ((uintptr_t)real_rows & 3))) return fail_at(FN_EINVAL, who, "a real-row count goes with a target (and is an aligned int32)");
     hipLaunchKernelGGL(k_pair_fwd<K1>, dim3((unsigned)pair_loss_ws(M)), dim3(256), 0, S(stream), drug, x1, W1, b1, w2, b2, target, h, out, g,
-                       loss_part, (int)M);
+                       loss_part, (int)M, real_rows);
     return launch_status(who);
 }
 
@@ -218,12 +228,22 @@ int64_t fn_dta_pair_loss_ws(int64_t M) { return pair_loss_ws(M); }
 int fn_cdrp_pair_fwd_f32(const float* drug, const float* cell, const float* W1, const float* b1, const float* w2, const float* b2,
                          const float* target, float* h, float* out, float* g, float* loss_part, int64_t M, int64_t Kd, int64_t Kc, int64_t H,
                          int64_t C, fn_stream_t stream) {
-    return pair_fwd<256>("fn_cdrp_pair_fwd_f32", drug, cell, W1, b1, w2, b2, target, h, out, g, loss_part, M, Kd, Kc, H, C, stream);
+    return pair_fwd<256>("fn_cdrp_pair_fwd_f32", drug, cell, W1, b1, w2, b2, target, h, out, g, loss_part, M, Kd, Kc, H, C, nullptr, stream);
+}
+int fn_cdrp_pair_fwd_rows_f32(const float* drug, const float* cell, const float* W1, const float* b1, const float* w2, const float* b2,
+                              const float* target, float* h, float* out, float* g, float* loss_part, int64_t M, int64_t Kd, int64_t Kc, int64_t H,
+                              int64_t C, const int32_t* real_rows, fn_stream_t stream) {
+    return pair_fwd<256>("fn_cdrp_pair_fwd_rows_f32", drug, cell, W1, b1, w2, b2, target, h, out, g, loss_part, M, Kd, Kc, H, C, real_rows, stream);
 }
 int fn_dta_pair_fwd_f32(const float* drug, const float* xt, const float* W1, const float* b1, const float* w2, const float* b2,
                         const float* target, float* h, float* out, float* g, float* loss_part, int64_t M, int64_t Kd, int64_t Kx, int64_t H,
                         int64_t C, fn_stream_t stream) {
-    return pair_fwd<300>("fn_dta_pair_fwd_f32", drug, xt, W1, b1, w2, b2, target, h, out, g, loss_part, M, Kd, Kx, H, C, stream);
+    return pair_fwd<300>("fn_dta_pair_fwd_f32", drug, xt, W1, b1, w2, b2, target, h, out, g, loss_part, M, Kd, Kx, H, C, nullptr, stream);
+}
+int fn_dta_pair_fwd_rows_f32(const float* drug, const float* xt, const float* W1, const float* b1, const float* w2, const float* b2,
+                             const float* target, float* h, float* out, float* g, float* loss_part, int64_t M, int64_t Kd, int64_t Kx, int64_t H,
+                             int64_t C, const int32_t* real_rows, fn_stream_t stream) {
+    return pair_fwd<300>("fn_dta_pair_fwd_rows_f32", drug, xt, W1, b1, w2, b2, target, h, out, g, loss_part, M, Kd, Kx, H, C, real_rows, stream);
 }
 
 int fn_cdrp_pair_bwd_f32(const float* g, const float* drug, const float* cell, const float* h, const float* W1, const float* w2, float* g_drug,

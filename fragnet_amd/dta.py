@@ -43,7 +43,8 @@ class DTAModel2(nn.Module):
 
     def forward(self, batch, loss=None):
         """``loss = (_lib.LOSS_MSE, y, None)``: the fused-loss call of a training step (``ops.pair_head_dta``); returns ``(out, loss)``,
-        ``loss`` None where the fused launch does not apply.  A factored batch (``data.collate_fn_dta_factored``, ``data.as_factored``)
+        ``loss`` None where the fused launch does not apply.  ``(_lib.LOSS_MSE, y, None, real_rows)``: a batch staged to static shapes
+        (graphstep.PairGraphedTrainStep), the mean over its first ``*real_rows`` rows.  A factored batch (``data.collate_fn_dta_factored``, ``data.as_factored``)
         runs the encoder on its U distinct drugs, the tower on its C distinct proteins and ``ops.pair_head_dta_factored``: [M, 1] in pair
         order.  A grid batch (``data.pair_grid_batch``) returns every drug against every protein, [U, C]."""
         drug_enc = self.drug_model(batch)

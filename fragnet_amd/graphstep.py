@@ -21,6 +21,9 @@ Batches that do not fit the capacities fall back to the eager step, sharing opti
 
 The all-reduce and the Adam update stay outside the graph (one RCCL call + one kernel) so the N>1 path is the
 same collective as in the eager step.
+
+``PairGraphedTrainStep`` is the same step for the pair models (cdrp.CDRPModel, dta.DTAModel2): the second input's int64 rows are
+staged too, and the pair head's fused loss reads the real-row count the staging launch wrote instead of a weight vector.
 """
 from __future__ import annotations
 
@@ -48,6 +51,9 @@ FIELDS = {
 }
 COUNT_FIELD = {"atom": "x_atoms", "edge": "node_features_bonds", "bedge": "edge_attr_bonds", "frag": "x_frags",
                "fedge": "node_features_fbonds", "fbedge": "edge_attr_fbonds", "mol": "y"}
+# the second input of a pair model (data.collate_fn_cdrp / collate_fn_dta: one int64 row per pair), staged through FN_STAGE_ROWS_I64 with
+# zero rows behind the real ones.  A table of its own: FIELDS is what a property batch may carry
+PAIR_FIELDS = {"gene_expr": ("mol", "rows_i64", None), "protein": ("mol", "rows_i64", None)}
 MASK_KEY = "mol_weight"           # float32 [mol cap]: 1 for real molecules, 0 for padding
 MASKS = {"mol": MASK_KEY, "atom": "atom_weight", "edge": "edge_weight"}     # 1/0 weights of the mean losses
 SCALE_KEY = "loss_scales"         # float32 [2]: (per-edge, per-atom) rank weights of the pretrain loss, 1 on one GPU
@@ -190,6 +196,19 @@ def pad_batch(batch: Dict[str, torch.Tensor], shapes: StaticShapes) -> Dict[str,
     return out
 
 
+def pad_pair_batch(batch: Dict[str, torch.Tensor], shapes: StaticShapes) -> Dict[str, torch.Tensor]:
+    """``pad_batch`` of a one-record-per-pair batch: the second input's int64 rows (PAIR_FIELDS) with zero rows behind the real ones, up to
+    the ``mol`` capacity -- that of ``y``."""
+    out = pad_batch(batch, shapes)
+    for name in PAIR_FIELDS:
+        if name in batch:
+            src = batch[name]
+            dst = src.new_zeros((shapes.cap["mol"],) + tuple(src.shape[1:]))
+            dst[: src.shape[0]] = src
+            out[name] = dst
+    return out
+
+
 ADAM_RIDER = os.environ.get("FRAGNET_ADAM_RIDER", "1") != "0"      # the head's Adam slice rides in the encoder backward's last launch (A/B: 0)
 
 
@@ -232,11 +251,13 @@ def masked_pretrain_loss(outputs, sb: Dict[str, torch.Tensor]) -> torch.Tensor:
 class StaticBatch:
     """Fixed-capacity device buffers for one batch + the single-launch staging call."""
 
-    def __init__(self, shapes: StaticShapes, example: Dict[str, torch.Tensor]):
+    def __init__(self, shapes: StaticShapes, example: Dict[str, torch.Tensor], extra_fields: Optional[dict] = None):
+        """``extra_fields``: a table in FIELDS' form of fields staged behind FIELDS' own (PAIR_FIELDS for a pair model)."""
         dev = example["x_atoms"].device
         if dev.type != "cuda":
             raise _lib.FragnetHipError("StaticBatch stages batches on the GPU (fn_stage_padded); there is no CPU path")
         self.shapes, self.device = shapes, dev
+        self._extra = dict(extra_fields or {})
         # the padded batch keeps the example's layout promise for its real molecules (the fused kernels treat the padding
         # molecules, whose items point round-robin at the reserved slots, separately: REAL_MOLS_KEY)
         self.collated = isinstance(example, CollatedBatch)
@@ -246,17 +267,22 @@ class StaticBatch:
         if self.with_offsets:
             self.t.offsets = torch.zeros((len(SPACES), shapes.cap["mol"] + 1), dtype=torch.int32, device=dev)
             self.t.max_per_mol, self.t.pad = dict(shapes.max_per_mol), shapes.pad_info()
-        # the staging table, in the launch's order: data fields (FIELDS order), the three masks, the real-molecule count, the offsets table,
+        # the staging table, in the launch's order: data fields (FIELDS order, then ``extra_fields``'), the three masks, the real-molecule count, the offsets table,
         # add_count's counts, then set_bumps' bumps and zero regions.  ``_refresh``: one entry per field that changes with the batch, all that
         # load() walks -- (the field, the index space whose real count is its n_real, its src: a batch key, _OFFSETS, or None)
         self._fields = (_lib.StageField * _lib.FN_MAX_STAGE_FIELDS)()
         self.n_fields = 0
         self._refresh = []
-        for name, (space, layout, target) in FIELDS.items():
+        for name, (space, layout, target) in list(FIELDS.items()) + list((extra_fields or {}).items()):
             if name not in example:
                 continue
             src, cap = example[name], shapes.cap[space]
-            if layout == "rows":
+            if layout == "rows_i64":
+                if src.dtype != torch.int64 or src.dim() != 2:
+                    raise TypeError(f"{name}: expected int64 rows [n, width], got {src.dtype} {tuple(src.shape)}")
+                self.t[name] = torch.zeros((cap, src.shape[1]), dtype=torch.int64, device=dev)
+                self._append(_lib.STAGE_ROWS_I64, self.t[name].data_ptr(), cap, int(src.shape[1]), refresh=(space, name))
+            elif layout == "rows":
                 if src.dtype != torch.float32:
                     raise TypeError(f"{name}: expected float32 rows, got {src.dtype}")
                 self.t[name] = torch.zeros((cap,) + tuple(src.shape[1:]), dtype=torch.float32, device=dev)
@@ -334,6 +360,8 @@ class StaticBatch:
                 src = batch[key]
                 if not src.is_cuda:
                     raise _lib.FragnetHipError(f"{key} must live on the GPU to be staged (got {src.device})")
+                if key in self._extra and tuple(src.shape[1:]) != tuple(self.t[key].shape[1:]):
+                    raise ValueError(f"{key}: rows of {tuple(src.shape[1:])}, the captured step was built for {tuple(self.t[key].shape[1:])}")
                 if not src.is_contiguous():
                     src = src.contiguous()
                     keep.append(src)
@@ -417,6 +445,9 @@ class GraphedTrainStep:
     (pretrain_utils.py:9-31 on the collate_fn_pt batch).
     """
 
+    LOSS_KINDS = ("regr", "clsf", "pretrain")
+    EXTRA_FIELDS: Optional[dict] = None      # StaticBatch's ``extra_fields``
+
     def __init__(self, model, opt, shapes: StaticShapes, example: Dict[str, torch.Tensor], loss: str = "regr",
                  group=None, warmup: int = 3, overlap: Optional[bool] = None, capture_adam: bool = True,
                  force_distributed: bool = False):
@@ -432,16 +463,16 @@ class GraphedTrainStep:
         if self.force_distributed:
             opt.force_collective = True
         self.loss_kind = loss
-        if loss not in ("regr", "clsf", "pretrain"):
+        if loss not in self.LOSS_KINDS:
             raise ValueError(f"unknown loss kind {loss!r}")
-        self._masked = {"regr": masked_regr_loss, "clsf": masked_bce_loss, "pretrain": None}[loss]
-        self.static = StaticBatch(shapes, example)
+        self._masked = {"regr": masked_regr_loss, "clsf": masked_bce_loss}.get(loss)
+        self.static = StaticBatch(shapes, example, self.EXTRA_FIELDS)
         self.device = self.static.device
         if loss == "pretrain" and "dh_angl" not in example:
             raise ValueError("pretrain step needs the collate_fn_pt batch (bnd_lngth, bnd_angl, dh_angl)")
         if loss == "pretrain" and hasattr(getattr(model, "head", None), "need_bond_length"):
             model.head.need_bond_length = False      # the loss never reads the bond-length prediction (pretrain_utils.py:17-24)
-        self.rng = model.pretrain.rng
+        self.rng = self._encoder().rng
         # [Philox blocks consumed, Adam steps done]: the staging launch in front of every replay moves both on (FN_STAGE_BUMP).  The first
         # word is the dropout stream's (``rng.dev``), the second the step count the captured Adam reads (_sync_adam_state)
         self._counters = torch.zeros(2, dtype=torch.int64, device=self.device)
@@ -475,6 +506,14 @@ class GraphedTrainStep:
         self._capture(example, warmup)
 
     # -- pieces
+    def _encoder(self):
+        """The FragNet encoder whose dropout stream the step owns."""
+        return self.model.pretrain
+
+    def _stage(self, batch) -> bool:
+        """Stage ``batch`` for a replay; False: it takes the eager step (nothing was written)."""
+        return self.static.load(batch)
+
     def _head_offset(self) -> Optional[int]:
         """Offset of the head's parameters in the optimiser's flat buffer if they are its contiguous tail (model =
         encoder ``pretrain`` + ``fthead``, regression / classification loss), else None (single-graph step)."""
@@ -564,7 +603,7 @@ class GraphedTrainStep:
     def _capture(self, example, warmup: int):
         if not self.model.training:
             raise RuntimeError("GraphedTrainStep captures a TRAINING step: call model.train() first")
-        if not self.static.load(example):
+        if not self._stage(example):
             raise ValueError(f"the example batch {batch_counts(example)} does not fit {self.shapes}")
 
         def warm_step():
@@ -643,17 +682,19 @@ class GraphedTrainStep:
         dist.all_reduce(total, op=dist.ReduceOp.SUM, group=self.group)
         return (local * dist.get_world_size(self.group) / total).to(torch.float32)
 
+    def _eager_loss(self, batch):
+        if self.loss_kind == "pretrain":
+            from .train import pretrain_loss
+            sc = self._rank_scales(batch)
+            return pretrain_loss(self.model(batch), batch, (1.0, 1.0) if sc is None else (sc[0], sc[1]))
+        out = self.model(batch)
+        w = torch.ones(batch["y"].shape[0], dtype=torch.float32, device=out.device)
+        return self._masked(out, batch["y"], w)
+
     def _eager(self, batch):
         self.opt.zero_grad()
         with ReplayCounter.eager(*self._stream_counters):
-            if self.loss_kind == "pretrain":
-                from .train import pretrain_loss
-                sc = self._rank_scales(batch)
-                loss = pretrain_loss(self.model(batch), batch, (1.0, 1.0) if sc is None else (sc[0], sc[1]))
-            else:
-                out = self.model(batch)
-                w = torch.ones(batch["y"].shape[0], dtype=torch.float32, device=out.device)
-                loss = self._masked(out, batch["y"], w)
+            loss = self._eager_loss(batch)
             loss.backward()
             if self.split:
                 # the ranks that replay the two graphs issue two slice all-reduces (head, then encoder): a rank that fell back to
@@ -676,7 +717,7 @@ class GraphedTrainStep:
         that time or profile the captured part use this instead of ``static.load`` + ``graph.replay``).  False: the batch does
         not fit the capacities (nothing ran)."""
         self._sync_adam_state()
-        if not self.static.load(batch):
+        if not self._stage(batch):
             return False
         self.graph.replay()
         if self.graph_b is not None:
@@ -689,7 +730,7 @@ class GraphedTrainStep:
     def __call__(self, batch: Dict[str, torch.Tensor]) -> torch.Tensor:
         """One optimiser step on ``batch``.  Returns the loss (a tensor that the next call overwrites)."""
         self._sync_adam_state()                      # before the staging launch: it bumps the step counter
-        if not self.static.load(batch):
+        if not self._stage(batch):
             self.fallbacks += 1
             return self._eager(batch)
         sc = self._rank_scales(batch)
@@ -710,6 +751,80 @@ class GraphedTrainStep:
             self.opt.apply_gathered(self.group)
         self.replays += 1
         return self.loss
+
+
+class PairGraphedTrainStep(GraphedTrainStep):
+    """``GraphedTrainStep`` for a pair model (cdrp.CDRPModel, dta.DTAModel2) on the one-record-per-pair batches of
+    ``data.collate_fn_cdrp`` / ``data.collate_fn_dta``: encoder, second-input tower, pair head with its fused MSE, backward, gradient
+    gather and (one rank, fused Adam) the update as ONE hipGraph.  What differs from the property step, and nothing else:
+
+    * staged fields: FIELDS' sixteen encoder fields and ``y``, plus ``gene_expr`` / ``protein`` (PAIR_FIELDS: int64 rows in the ``mol``
+      space, zero rows behind the real ones);
+    * the encoder is ``model.drug_model.pretrain``: its Philox stream is the step's ``ReplayCounter``;
+    * the step is ``model(staged, loss=(LOSS_MSE, y, None, real-row word))``: the pair head's fused launch reads the count the staging
+      launch wrote (plan.REAL_MOLS_KEY), takes the mean over the real pairs and hands the padding rows a zero gradient, so the tower
+      and the encoder see none either.  Padding molecules and padding rows of the tower are computed, not skipped;
+    * ``target_norm = (mean, sdev)`` (the DTA trainer sets it, per call): what is staged as ``y`` is ``(y - mean) / (sdev + 1e-5)``,
+      computed in front of the staging launch -- the graph never sees the two numbers, so they may change between calls;
+    * a factored batch (it carries ``data.PAIR_DRUG_KEY``), a grid batch and a batch beyond the capacities take the eager step on the
+      same optimiser and RNG state (``fallbacks``).  A grid batch has no target: its eager step raises.
+
+    Single graph and single rank only: ``overlap=True`` and a process group of more than one rank raise ValueError."""
+
+    LOSS_KINDS = ("pair",)
+    EXTRA_FIELDS = PAIR_FIELDS
+
+    def __init__(self, model, opt, shapes: StaticShapes, example: Dict[str, torch.Tensor], group=None, warmup: int = 3,
+                 overlap: Optional[bool] = None, capture_adam: bool = True):
+        if overlap:
+            raise ValueError("PairGraphedTrainStep captures one graph: overlap=True (the two-graph step) is not built for pair models")
+        import torch.distributed as dist
+        if dist.is_available() and dist.is_initialized() and dist.get_world_size(group) > 1:
+            raise ValueError("PairGraphedTrainStep is single-GPU: the process group has more than one rank")
+        if not hasattr(getattr(model, "drug_model", None), "pretrain"):
+            raise TypeError("PairGraphedTrainStep takes a pair model (cdrp.CDRPModel / dta.DTAModel2): model.drug_model.pretrain is its encoder")
+        if not any(k in example for k in PAIR_FIELDS):
+            raise ValueError(f"the example is no pair batch: none of {tuple(PAIR_FIELDS)} in it")
+        self.target_norm = None                      # None: y as the batch has it; (mean, sdev): (y - mean) / (sdev + 1e-5)
+        self._y_keep = None
+        super().__init__(model, opt, shapes, example, loss="pair", group=group, warmup=warmup, overlap=False, capture_adam=capture_adam)
+
+    def _encoder(self):
+        return self.model.drug_model.pretrain
+
+    def _target(self, batch) -> torch.Tensor:
+        if self.target_norm is None:
+            return batch["y"]
+        mean, sdev = self.target_norm
+        return (batch["y"] - mean) / (sdev + 1e-5)           # trainer_dta.py:42, the statement of TrainerFineTuneDTA._loss
+
+    @staticmethod
+    def _one_row_per_pair(batch) -> bool:
+        from .data import PAIR_DRUG_KEY, PAIR_GRID_KEY
+        return PAIR_DRUG_KEY not in batch and not batch.get(PAIR_GRID_KEY)
+
+    def _stage(self, batch) -> bool:
+        if not self._one_row_per_pair(batch):
+            return False
+        if self.target_norm is not None:
+            staged = batch.like(dict(batch)) if isinstance(batch, CollatedBatch) else dict(batch)
+            staged["y"] = self._y_keep = self._target(batch)     # alive until the next call: the staging launch reads it
+            batch = staged
+        return self.static.load(batch)
+
+    def _static_loss(self, predict):
+        sb = self.static.t
+        sb.pop(PLAN_KEY, None)
+        _, loss = predict(sb, loss=(_lib.LOSS_MSE, sb["y"], None, sb[REAL_MOLS_KEY]))
+        return loss              # never None: ops._pair_apply refuses a count where the fused launch does not apply
+
+    def _eager_loss(self, batch):
+        from .data import PAIR_GRID_KEY
+        if batch.get(PAIR_GRID_KEY):
+            raise ValueError("a grid batch has no target and no training step")
+        y = self._target(batch)
+        out, loss = self.model(batch, loss=(_lib.LOSS_MSE, y, None))
+        return loss if loss is not None else torch.nn.functional.mse_loss(out.view(-1), y)
 
 
 class GraphedForward:

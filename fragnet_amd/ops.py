@@ -1458,7 +1458,7 @@ def cell_path_attributions(gene_expr, linears, v, alpha, base=None, want_gradien
 
 class _PairInstance(NamedTuple):
     """One built instance of the pair-head kernels (csrc/pair_head.hip): 256 + ``width`` -> 128 -> 1."""
-    prefix: str          # entry points <prefix>_loss_ws, <prefix>_fwd_f32, <prefix>_bwd_f32
+    prefix: str          # entry points <prefix>_loss_ws, <prefix>_fwd_f32 (<prefix>_fwd_rows_f32 with a real-row count), <prefix>_bwd_f32
     width: int           # of the second input
     gated: bool          # the second input is the output of a ReLU: its gradient comes back zero where it is <= 0
     name: str            # the public function, in error messages
@@ -1527,7 +1527,8 @@ def _pair_backward_end(ctx, x1, g_drug, g_x1, grads, n_between: int):
 class _PairHead(torch.autograd.Function):
     """fc2(fc1(cat(drug_enc, second))) (model/cdrp/model.py:35-42, model/dta/model.py:141-144; nothing between the two Linears) for
     256 + ``inst.width`` -> 128 -> 1: one launch each way (<prefix>_fwd_f32 / <prefix>_bwd_f32), the two inputs read where they are.
-    With ``target`` the loss is fused (above).  Where ``inst.gated`` (CDRP's ``cell_enc``) the gradient handed to the second input is already through the
+    With ``target`` the loss is fused (above); ``target = (y, real_rows)`` hands the forward the device-side count of the real rows of a
+    static-shape step (``_pair_apply``: the mean is over them, the rows behind them get g = 0).  Where ``inst.gated`` (CDRP's ``cell_enc``) the gradient handed to the second input is already through the
     backward of the ReLU that produced it (tagged ``_fn_relu_gated`` for ``_CellTower``; applying that gate again, as a plain autograd
     ReLU would, changes nothing); otherwise (DTA's ``xt``, a Linear's output) it is NOT gated."""
 
@@ -1541,10 +1542,15 @@ class _PairHead(torch.autograd.Function):
             raise ValueError(f"{inst.name}: drug_enc / {inst.second} / fc1 / fc2 shapes do not fit together")
         h = torch.empty((M, H), dtype=torch.float32, device=dev)
         out = torch.empty((M, C_out), dtype=torch.float32, device=dev)
+        target, real_rows = target if isinstance(target, tuple) else (target, None)
         target, g, parts, loss_t = _pair_loss_buffers(target, M, C_out, lambda: getattr(_lib.load(), inst.prefix + "_loss_ws")(M), dev,
                                                       inst.name, "rows")
-        _lib.call(inst.prefix + "_fwd_f32", drug.data_ptr(), x1.data_ptr(), W1.data_ptr(), b1.data_ptr(), w2.data_ptr(), b2.data_ptr(),
-                  _ptr(target), h.data_ptr(), out.data_ptr(), _ptr(g), _ptr(parts), M, Kd, K1, H, C_out, _stream_ptr(dev))
+        args = (drug.data_ptr(), x1.data_ptr(), W1.data_ptr(), b1.data_ptr(), w2.data_ptr(), b2.data_ptr(), _ptr(target), h.data_ptr(),
+                out.data_ptr(), _ptr(g), _ptr(parts), M, Kd, K1, H, C_out)
+        if real_rows is None:
+            _lib.call(inst.prefix + "_fwd_f32", *args, _stream_ptr(dev))
+        else:
+            _lib.call(inst.prefix + "_fwd_rows_f32", *args, real_rows.data_ptr(), _stream_ptr(dev))
         return _pair_forward_end(ctx, inst, (W1, b1, w2, b2), (drug, x1, h), out, g, parts, loss_t)
 
     @staticmethod
@@ -1558,20 +1564,33 @@ class _PairHead(torch.autograd.Function):
 
 
 def pair_fuses_loss(loss, rows: int, tensors) -> bool:
-    """Whether a pair head with ``loss = (kind, y, row_w)`` runs the loss in its forward launch and the loss's sum in its backward
-    launch: MSE without row weights, live rows, and a training step -- gradients enabled and one of ``tensors`` (the two inputs and the
-    four parameters) taking one."""
-    kind, _, row_w = loss
+    """Whether a pair head with ``loss = (kind, y, row_w)`` or ``(kind, y, row_w, real_rows)`` runs the loss in its forward launch and the
+    loss's sum in its backward launch: MSE without row weights, live rows, and a training step -- gradients enabled and one of ``tensors``
+    (the two inputs and the four parameters) taking one.  A real-row COUNT (``_pair_apply``) is no row weight and does not stand in the way."""
+    kind, _, row_w = loss[:3]
     return bool(FUSED_HEAD_LOSS and kind == _lib.LOSS_MSE and row_w is None and torch.is_grad_enabled() and rows > 0
                 and any(t.requires_grad for t in tensors))
 
 
 def _pair_apply(node, args, rows: int, fc1, fc2, loss):
-    """``node`` on ``args`` = (instance, drug, second input, ..), the target and the parameters: the result in ``pair_head``'s three shapes"""
+    """``node`` on ``args`` = (instance, drug, second input, ..), the target and the parameters: the result in ``pair_head``'s three shapes.
+    A fourth element of ``loss`` is the device-side count of the REAL rows (int32 [1], ``plan.REAL_MOLS_KEY`` of a batch staged to static
+    shapes): the loss is the mean over the first ``n`` rows and the rows behind them receive no gradient.  It exists in the fused launch
+    of ``_PairHead`` only -- a caller that computes the loss from ``out`` itself would take the padding rows for real ones -- so where that
+    launch does not apply the count is an error."""
     params = (fc1.weight, fc1.bias, fc2.weight, fc2.bias)
     if loss is None:
         return node.apply(*args, None, *params)
-    if not pair_fuses_loss(loss, rows, (args[1], args[2], *params)):
+    real_rows = loss[3] if len(loss) > 3 else None
+    fused = pair_fuses_loss(loss, rows, (args[1], args[2], *params))
+    if real_rows is not None:
+        if node is not _PairHead or not fused:
+            raise _lib.FragnetHipError(f"{args[0].name}: a real-row count needs the fused MSE launch of the one-row-per-pair head (a training "
+                                       "step, no row weights, no factored batch)")
+        if not (real_rows.is_cuda and real_rows.dtype == torch.int32 and real_rows.numel() == 1):
+            raise TypeError(f"{args[0].name}: the real-row count is one int32 word on the GPU, got {tuple(real_rows.shape)} {real_rows.dtype} on {real_rows.device}")
+        return node.apply(*args, (loss[1], real_rows), *params)
+    if not fused:
         return node.apply(*args, None, *params), None
     return node.apply(*args, loss[1], *params)
 
@@ -1587,6 +1606,8 @@ def _pair_head(inst, drug_enc, x1, fc1, fc2, loss):
     if not (drug_enc.is_cuda and x1.is_cuda):
         raise _lib.FragnetHipError(f"{inst.name}: fragnet_amd kernels need GPU tensors; there is no CPU fallback")
     if not (_pair_widths_ok(inst, drug_enc, x1, fc1, fc2) and drug_enc.shape[0] <= DENSE_MAX_ROWS):
+        if loss is not None and len(loss) > 3 and loss[3] is not None:
+            raise _lib.FragnetHipError(f"{inst.name}: a real-row count needs the built widths (256 + {inst.width} -> 128 -> 1)")
         out = fc2(fc1(torch.cat((drug_enc, x1), 1)))
         return (out, None) if loss is not None else out
     return _pair_apply(_PairHead, (inst, drug_enc, x1), drug_enc.shape[0], fc1, fc2, loss)
@@ -1595,7 +1616,8 @@ def _pair_head(inst, drug_enc, x1, fc1, fc2, loss):
 def pair_head(drug_enc, cell_enc, fc1, fc2, loss=None):
     """``fc2(fc1(cat(drug_enc, cell_enc)))`` as ``_PairHead``; ``cell_enc`` must be the output of a ReLU (the tower's: its gradient comes
     back gated by ``cell_enc > 0``).  ``loss = (_lib.LOSS_MSE, y, None)``, in the style of ``mlp_head``: the caller is a training step that
-    calls ``backward`` on the loss right away; returns ``(out, loss)`` with ``loss`` None where the fused launch does not apply (the caller
+    calls ``backward`` on the loss right away (``(_lib.LOSS_MSE, y, None, real_rows)``: the mean over the first ``*real_rows`` rows, see
+    ``_pair_apply``); returns ``(out, loss)`` with ``loss`` None where the fused launch does not apply (the caller
     then computes it from ``out``).  Other widths than 256 + 256 -> 128 -> 1, Linears without bias or more than ``DENSE_MAX_ROWS`` rows
     fall back to plain torch ops (``torch.cat`` + two library GEMMs)."""
     return _pair_head(_PAIR_CDRP, drug_enc, cell_enc, fc1, fc2, loss)

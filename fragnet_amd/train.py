@@ -316,8 +316,9 @@ class TrainerFineTuneCDRP(TrainerFineTune):
             out = model(batch)
         return self.loss_fn(out.view(-1), batch["y"])
 
-    def train(self, model, loader, optimizer, scheduler=None, device=None, val_loader=None, label_mean=None, label_sdev=None):
-        return super().train(model, loader, optimizer, scheduler=scheduler, device=device, val_loader=val_loader)
+    def train(self, model, loader, optimizer, scheduler=None, device=None, val_loader=None, label_mean=None, label_sdev=None, graph_step=None):
+        """``graph_step``: a graphstep.PairGraphedTrainStep over the same model and optimiser (``TrainerFineTune.train``)."""
+        return super().train(model, loader, optimizer, scheduler=scheduler, device=device, val_loader=val_loader, graph_step=graph_step)
 
     def validate(self, model, loader, device=None, label_mean=None, label_sdev=None):
         return super().validate(model, loader, device=device)
@@ -353,9 +354,13 @@ class TrainerFineTuneDTA(TrainerFineTune):
     def _stats(label_mean, label_sdev):
         return (0.0 if label_mean is None else float(label_mean), 1.0 if label_sdev is None else float(label_sdev))
 
-    def train(self, model, loader, optimizer, scheduler=None, device=None, val_loader=None, label_mean=None, label_sdev=None):
+    def train(self, model, loader, optimizer, scheduler=None, device=None, val_loader=None, label_mean=None, label_sdev=None, graph_step=None):
+        """``graph_step``: a graphstep.PairGraphedTrainStep over the same model and optimiser.  It stages the NORMALISED target, computed
+        from this call's ``label_mean`` / ``label_sdev`` in front of its staging launch: the two may change from call to call."""
         self._norm = self._stats(label_mean, label_sdev)
-        return super().train(model, loader, optimizer, scheduler=scheduler, device=device, val_loader=val_loader)
+        if graph_step is not None:
+            graph_step.target_norm = self._norm
+        return super().train(model, loader, optimizer, scheduler=scheduler, device=device, val_loader=val_loader, graph_step=graph_step)
 
     def validate(self, model, loader, device=None, label_mean=None, label_sdev=None):
         self._norm = self._stats(label_mean, label_sdev)
@@ -411,6 +416,26 @@ def make_optimizer(model, lr: float, probe_batch: Optional[Dict[str, torch.Tenso
         loss_of(model, probe_batch).backward()
         model.train(was)
     return parallel.FlatAdam.for_live_parameters(model, probe, lr=lr)
+
+
+def check_pair_graph_step(ft) -> bool:
+    """``finetune.graph_step`` of the pair drivers (scripts/finetune_cdrp.py, finetune_dta.py): absent means off.  The captured step
+    covers one-record-per-pair batches only, so together with ``finetune.factored_pairs`` it is a configuration error."""
+    if not ft.get("graph_step"):
+        return False
+    if ft.get("factored_pairs"):
+        raise SystemExit("finetune.graph_step and finetune.factored_pairs exclude each other: the captured pair step takes one-record-per-pair "
+                         "batches (a factored batch would run eagerly, every step)")
+    return True
+
+
+def make_pair_graph_step(model, optimizer, train_loader, heads: int):
+    """The drivers' ``graphstep.PairGraphedTrainStep``: capacities from eight training batches (margin 5 %), captured on the first."""
+    from . import graphstep
+    sample = [b for _, b in zip(range(8), iter(train_loader))]
+    shapes = graphstep.StaticShapes.from_batches(sample, margin=0.05, heads=heads)
+    model.train()
+    return graphstep.PairGraphedTrainStep(model, optimizer, shapes, sample[0])
 
 
 def save_predictions(trainer, loader, model, exp_dir, save_name="test_res", loss_type="mse", seed=123):

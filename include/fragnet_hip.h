@@ -749,6 +749,8 @@ int fn_masked_mse_multi_f32(const fn_mse_task* tasks, int n_tasks /*<= 4*/, cons
                             *                       entries behind molecule n_real repeat the space's total */
 #define FN_STAGE_BUMP 5  /* int64 [1]          +=  n_real: a device-side counter of a captured step (Philox blocks, optimiser steps)
                           *                       advanced by the staging launch that precedes every replay instead of by a launch of its own */
+#define FN_STAGE_ROWS_I64 8 /* int64 [cap,width]   <- [n_real,width], zero rows after (the second input of a pair model: gene_expr, protein
+                             *                       tokens); FN_STAGE_ROWS's checks, and src and dst 8-byte aligned */
 typedef struct fn_stage_field {
     const void* src;
     void* dst;
@@ -1028,6 +1030,15 @@ int fn_cdrp_pair_fwd_f32(const float* drug, const float* cell, const float* W1, 
 int fn_cdrp_pair_bwd_f32(const float* g, const float* drug, const float* cell, const float* h, const float* W1, const float* w2,
                          float* g_drug, float* g_cell, float* dW1, float* db1, float* dW2, float* db2, const float* loss_part /*nullable*/,
                          int64_t n_part, float* loss /*nullable*/, int64_t M, int64_t Kd, int64_t Kc, int64_t H, int64_t C, fn_stream_t stream);
+/* fn_cdrp_pair_fwd_rows_f32 / fn_dta_pair_fwd_rows_f32 (added under ABI 12, nothing existing changes): fn_*_pair_fwd_f32 with a
+ * DEVICE-side count of the real rows, for the M = capacity rows of a static-shape step: real_rows = the int32 word the staging launch
+ * writes (FN_STAGE_COUNT), n = *real_rows clamped to [0, M].  Rows i < n: out, h, g[i] = 2 (out - target) / n, partials divided by n;
+ * rows i >= n: out and h written, g[i] = 0 exactly, no share of the loss; n = 0: loss 0, every g 0, no division.  fn_*_pair_bwd_f32 is
+ * called as before, on all M rows: a zero g makes every term of a padding row an exact zero (finite inputs), its g_drug / g_cell rows
+ * included.  real_rows == NULL: fn_*_pair_fwd_f32, bit for bit.  real_rows without a target: FN_EINVAL. */
+int fn_cdrp_pair_fwd_rows_f32(const float* drug, const float* cell, const float* W1, const float* b1, const float* w2, const float* b2,
+                              const float* target, float* h, float* out, float* g, float* loss_part, int64_t M, int64_t Kd, int64_t Kc,
+                              int64_t H, int64_t C, const int32_t* real_rows /*nullable, device*/, fn_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
  * Drug-target affinity model, DTA (reference model/dta/model.py: DTAModel2 = FragNet encoder + protein tower Embedding(V, D) ->
@@ -1068,6 +1079,9 @@ int fn_dta_pair_fwd_f32(const float* drug, const float* xt, const float* W1, con
 int fn_dta_pair_bwd_f32(const float* g, const float* drug, const float* xt, const float* h, const float* W1, const float* w2,
                         float* g_drug, float* g_xt, float* dW1, float* db1, float* dW2, float* db2, const float* loss_part /*nullable*/,
                         int64_t n_part, float* loss /*nullable*/, int64_t M, int64_t Kd, int64_t Kx, int64_t H, int64_t C, fn_stream_t stream);
+int fn_dta_pair_fwd_rows_f32(const float* drug, const float* xt, const float* W1, const float* b1, const float* w2, const float* b2,
+                             const float* target, float* h, float* out, float* g, float* loss_part, int64_t M, int64_t Kd, int64_t Kx,
+                             int64_t H, int64_t C, const int32_t* real_rows /*nullable, device*/, fn_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
  * The pair head on a FACTORED batch; csrc/pair_factored.hip.  Entry points added under ABI 12 (nothing existing changes).  U distinct

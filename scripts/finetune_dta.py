@@ -53,6 +53,7 @@ if __name__ == "__main__":
         raise SystemExit("DTA: model_version gat2 is on the accelerated path")
     if ft.target_type != "regr":
         raise SystemExit("DTA: target_type regr only")
+    want_graph_step = train.check_pair_graph_step(ft)      # finetune.graph_step: true -- the training step as one hipGraph (graphstep.PairGraphedTrainStep)
     model = DTAModel2(FragNetFineTuneBase(**train.finetune_model_kwargs(args)))
     pt = args.pretrain
     if pt.get("chkpoint_name") and os.path.exists(str(pt.chkpoint_name)):
@@ -74,13 +75,15 @@ if __name__ == "__main__":
     with open(os.path.join(exp_dir, "train_stats.pkl"), "wb") as f:
         pickle.dump({"mean": stats["label_mean"], "sdev": stats["label_sdev"]}, f)
     optimizer = train.make_optimizer(model, float(ft.lr), next(iter(train_loader)), lambda mdl, b: trainer._loss(mdl, b))
+    graph_step = train.make_pair_graph_step(model, optimizer, train_loader, int(ft.model.num_heads)) if want_graph_step else None
+    step_kw = {} if graph_step is None else {"graph_step": graph_step}      # absent by default: the launch-by-launch step, as ever
     stopper = train.EarlyStopping(patience=ft.es_patience, verbose=True, chkpoint_name=ft.chkpoint_name)
     log = open(os.path.join(exp_dir, "log.jsonl"), "a")
     for epoch in range(ft.n_epochs):
         train_loss = trainer.train(model=model, loader=train_loader, optimizer=optimizer, scheduler=None, device=device, val_loader=val_loader,
-                                   **stats)
+                                   **stats, **step_kw)
         val_loss, _, _ = trainer.test(model=model, loader=val_loader, device=device, **stats)
-        print("epoch: ", epoch, train_loss, val_loss)
+        print("epoch: ", epoch, train_loss, val_loss, "" if graph_step is None else f"(graph replays {graph_step.replays}, eager fallbacks {graph_step.fallbacks})")
         log.write(json.dumps({"epoch": epoch, "Loss/train": train_loss, "Loss/val": val_loss}) + "\n")
         log.flush()
         stopper(val_loss, model)
