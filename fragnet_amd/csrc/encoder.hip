@@ -68,6 +68,7 @@ struct RowDotsBwdArgs {
     const float *cu_out2, *cu_sigma;
     float *cu_c, *cu_u;
     const int32_t* n_real;   // nullable device word: edges (rows of feat) at or behind *n_real are padding: not read, not written
+    int part_ld;             // layout of part (part_at, fn_internal.h): 0 = column-major [J * 128][FN_MAX_PART], else row-major [nblk][part_ld]
 };
 // edges [e0, e1) in original order, taken interleaved by the block's half-waves; vb: the block's slot (row) in T.part
 __device__ __forceinline__ void row_dots_sorted_bwd_range(const RowDotsBwdArgs& T, float (*sR)[FN_D], int64_t e0, int64_t e1, int vb) {
@@ -149,7 +150,7 @@ __device__ __forceinline__ void row_dots_sorted_bwd_range(const RowDotsBwdArgs& 
                 float v = 0.f;
 #pragma unroll
                 for (int w = 0; w < kRows; ++w) v += sR[w][threadIdx.x];
-                part[(size_t)(i * FN_D + threadIdx.x) * FN_MAX_PART + vb] = v;   // column-major
+                part[part_at(T.part_ld, vb, i * FN_D + (int)threadIdx.x)] = v;
             }
             __syncthreads();
         }
@@ -554,6 +555,11 @@ bool tail_mol_on(const fn_encoder* e) {
 // Backward scratch.  Nothing is reused across levels or layers: the kernels that only produce parameter gradients
 // (finalize, weight-gradient GEMMs, column sums) run on an auxiliary stream behind the main dependency chain, so a
 // buffer they read must not be rewritten by the next level.  ~60 MB per layer at ESOL batch 512.
+// part_a / part_rd: one row of partial sums per block, row-major [FN_MAX_PART][256] / [FN_MAX_PART][H * 128] (part_at, fn_internal.h; the
+// same floats as the column-major form the operator entry points keep).  EVERY engine launch that writes one of them and every task that
+// reduces one takes its layout from the two functions below.
+constexpr int part_a_ld() { return FN_PART_ROWMAJOR ? 2 * FN_D : 0; }
+constexpr int part_rd_ld(int H) { return FN_PART_ROWMAJOR ? H * FN_D : 0; }
 struct LevelScratch {
     float *g_h, *dz, *pz, *g_s_dst, *part_a, *part_e, *part_rd, *wg_ws;
     float* cdot;             // one-pass backward: c[n, H] = <g, out> per head (no pz then)
@@ -721,11 +727,11 @@ struct ParamWork {
 };
 // ... as the parameter-gradient queue (param_grads.hip) takes it: the level's description unpacked into pointers and counts
 inline fni::AttParamGrads att_param_grads(const LevelView& v, const LevelWeights& g, const LevelScratch& sc, int n_a, int n_e) {
-    return fni::AttParamGrads{v.H, sc.part_a, n_a, sc.part_e, n_e, v.et, v.att, v.att_w, v.src_off, g.att, g.embW, g.embb};
+    return fni::AttParamGrads{v.H, sc.part_a, n_a, sc.part_e, n_e, v.et, v.att, v.att_w, v.src_off, g.att, g.embW, g.embb, part_a_ld()};
 }
 // the partial rows of the edge term's dL/d(att[:, mid block]) (a level whose edge term is a table of row dots): their column sums
 int edge_term_colsum(ParamGradQueue& rq, const LevelView& v, const LevelWeights& g, const LevelScratch& sc, int n_rd) {
-    return rq.colsum(sc.part_rd, n_rd, v.H * FN_D, g.att, v.att_w, v.mid_off);
+    return rq.colsum(sc.part_rd, n_rd, v.H * FN_D, g.att, v.att_w, v.mid_off, part_rd_ld(v.H));
 }
 // queued in the order finalize, [column sum], weight gradient (a lone partial product is launched on `launch_on`)
 int level_params(ParamGradQueue& rq, const LevelView& v, const LevelWeights& g, const LevelScratch& sc, const ParamWork& o, hipStream_t launch_on) {
@@ -741,6 +747,14 @@ int launch_gat_bwd_src(const GatBwdSrcArgs& A, int heads, hipStream_t st) {
     return launch_status("fn_gat_bwd_src_f32");
 }
 
+// ... of an engine level, into its scratch (the partial rows in the engine's layout)
+int engine_bwd_src(const LevelView& v, const LevelScratch& sc, const float* g_out, float* g_h, int* n_part_a, hipStream_t st) {
+    GatBwdSrcArgs A;
+    if (int rc = prep_gat_bwd_src(g_out, v.a.h, sc.pz, sc.g_s_dst, v.att, v.att_w, 0, v.src_off, v.pl, g_h, sc.part_a, n_part_a, v.H, &A)) return rc;
+    A.part_ld = part_a_ld();
+    return launch_gat_bwd_src(A, v.H, st);
+}
+
 // source pass of a two-pass level + backward of its edge term <feat[e], att[:, mid block]> as ONE launch (k_gat_bwd_src_rd); they
 // share nothing but their input dz.  g_out / g_h: the level's gradient rows in and out; feat: the raw rows of the level that provides
 // the edge features, g_feat their gradient rows (accumulate: they hold a gradient already).  *n_rd = blocks of the edge-term part (0:
@@ -750,9 +764,11 @@ int bwd_src_and_edge_term(const LevelView& v, const LevelScratch& sc, const floa
     const int heads = v.H;
     GatBwdSrcArgs A;
     if (int rc = prep_gat_bwd_src(g_out, v.a.h, sc.pz, sc.g_s_dst, v.att, v.att_w, 0, v.src_off, v.pl, g_h, sc.part_a, n_part_a, heads, &A)) return rc;
+    A.part_ld = part_a_ld();
     *n_rd = v.pl->m_real > 0 ? row_grid(v.pl->m_real, tune(FN_TUNE_RD_BLOCKS) > 0 ? tune(FN_TUNE_RD_BLOCKS) : kRowDotsBwdBlocks) : 0;
     if (*n_rd == 0) return launch_gat_bwd_src(A, heads, st);
-    const RowDotsBwdArgs T{sc.dz, feat, v.att, v.att_w, v.mid_off, heads, *v.pl, g_feat, sc.part_rd, accumulate ? (const float*)g_feat : nullptr, 1, *n_rd};
+    RowDotsBwdArgs T{sc.dz, feat, v.att, v.att_w, v.mid_off, heads, *v.pl, g_feat, sc.part_rd, accumulate ? (const float*)g_feat : nullptr, 1, *n_rd};
+    T.part_ld = part_rd_ld(heads);
     if (A.nblk == 0) {
         hipLaunchKernelGGL(k_row_dots_sorted_bwd, dim3(T.nblk), dim3(kBlock), 0, st, T);
         return launch_status("edge-term backward");
@@ -839,6 +855,7 @@ int launch_tail_bwd(const fn_encoder* e, const EncLayout& lay, const BwdLayout& 
     FN_TRY(prep_gat_bwd_src(bw.g_pre[LV_FRAG], vf.a.h, sf.pz, sf.g_s_dst, vf.att, vf.att_w, 0, vf.src_off, vf.pl, bw.g_frags, sf.part_a, &n_a, H, &T.S));
     T.R = RowDotsBwdArgs{sf.dz, vfb.a.raw, vf.att, vf.att_w, vf.mid_off, H, *vf.pl, bw.g_pre[LV_FBOND], sf.part_rd,
                          accumulate_fbond ? (const float*)bw.g_pre[LV_FBOND] : (const float*)nullptr, 1, 0};
+    T.S.part_ld = part_a_ld();  T.R.part_ld = part_rd_ld(H);
     if (one_pass_dots) {
         const LevelScratch &sa = bw.lv[l][LV_ATOM], &sfb = bw.lv[l][LV_FBOND];
         T.cu_out = va.a.raw;  T.cu_out2 = va.a.o2;  T.cu_sigma = va.a.sg;  T.cu_c = sa.cdot;  T.cu_u = sa.g_s_dst;
@@ -918,7 +935,7 @@ int last_layer_output_grads(const fn_encoder* e, const EncLayout& lay, const Bwd
         have_g_frags_h = true;
     } else if (have_frags && edge) {   // gat2_edge: the edge term's parameters are the cnx_attr Linear (emb_fb_*) and f's middle block
         FN_TRY(fn_gat_bwd_dst_f32(bw.g_pre[LV_FRAG], vf.a.h, vf.a.p, &vf.et, vf.pl, 0.2f, nullptr, nullptr, sf.pz, sf.g_s_dst, sf.part_e, &n_e, H, hs));
-        FN_TRY(fn_gat_bwd_src_f32(bw.g_pre[LV_FRAG], vf.a.h, sf.pz, sf.g_s_dst, vf.att, vf.att_w, 0, vf.src_off, vf.pl, bw.g_frags, sf.part_a, &n_a, H, hs));
+        FN_TRY(engine_bwd_src(vf, sf, bw.g_pre[LV_FRAG], bw.g_frags, &n_a, hs));
         FN_TRY(rq.finalize(att_param_grads(vf, gf, sf, n_a, n_e)));
         have_g_frags_h = true;
     } else if (have_frags) {
@@ -969,6 +986,7 @@ int encoder_backward_one(const fn_encoder* e, const EncLayout& lay, const BwdLay
                                 sc.part_a, &n->n_a, sc.part_e, &n->n_e, H, A));
         A->p_edge_major = 1;
         A->n_real = v.n_real;
+        A->part_ld = part_a_ld();
         return 0;
     };
     auto scratch = [&](const LevelView& v) -> const LevelScratch& { return bw.lv[v.layer][v.lv]; };
@@ -1056,6 +1074,7 @@ int encoder_backward_one(const fn_encoder* e, const EncLayout& lay, const BwdLay
                 R = RowDotsBwdArgs{sa.dz, vb.a.raw, va.att, va.att_w, va.mid_off, H, *va.pl, rd_rows_ride ? nullptr : bw.g_pre[LV_BOND], sa.part_rd,
                                    (!rd_rows_ride && have_b_now) ? (const float*)bw.g_pre[LV_BOND] : nullptr, 1, gr};
                 R.n_real = vb.n_real;
+                R.part_ld = part_rd_ld(H);
                 FN_TRY(edge_term_colsum(rq, va, ga, sa, gr));
                 if (!pend_b) {
                     // the bond rows of this layer are finished by the edge term's rows' part: with four heads it writes their dots too
@@ -1479,7 +1498,7 @@ int fn_encoder_backward(const fn_encoder* e, const float* out_atoms, const float
             return fn_gat_bwd_dst_f32(bw.g_pre[v.lv], v.a.h, v.a.p, &v.et, v.pl, 0.2f, nullptr, nullptr, sc.pz, sc.g_s_dst, sc.part_e, &n->n_e, H, st);
         };
         auto src_pass = [&](const LevelView& v, const LevelScratch& sc, Parts* n) {
-            return fn_gat_bwd_src_f32(bw.g_pre[v.lv], v.a.h, sc.pz, sc.g_s_dst, v.att, v.att_w, 0, v.src_off, v.pl, sc.g_h, sc.part_a, &n->n_a, H, st);
+            return engine_bwd_src(v, sc, bw.g_pre[v.lv], sc.g_h, &n->n_a, S(st));
         };
         if (have[LV_BOND]) FN_TRY(dst_pass(vb, sb, &nb));
         if (have[LV_FBOND]) FN_TRY(dst_pass(vfb, sfb, &nfb));

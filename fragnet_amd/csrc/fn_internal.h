@@ -130,6 +130,8 @@ struct GatBwdOneArgs {
     float* dz_em;                 // operator-level deferred form (fn_gat_bwd_one_f32 only; the engine leaves it null): dL/dz of every edge at its destination-order slot, EDGE-major [m][H]
     unsigned long long* stamps;   // dev aid (fn_debug_set_stamps): 16 s_memtime values per wave -- entry, loop start, per row (loads issued,
                                   // data arrived, row done) x 4, loop end, exit; null in production (one uniform branch per stamp)
+    int part_ld;                  // layout of part_a (part_at, below): 0 = column-major [256][FN_MAX_PART] (the operator entry points), else the
+                                  // leading dimension of row-major [nblk][part_ld] (the engine's tables)
 };
 struct CuTask {
     const float *g, *out, *out2, *sigma;
@@ -194,7 +196,8 @@ struct ReduceTask {
     const float* att;
     int att_w, dst_off, src_off, K;
     float *o0, *o1, *o2;
-    int ld, off, cls, pad_;      // cls (RT_WGRAD): the class of the kernel that wrote the partials (param_grads.hip: wgrad_class)
+    int ld, off, cls, pld;       // cls (RT_WGRAD): the class of the kernel that wrote the partials (param_grads.hip: wgrad_class)
+                                 // pld (RT_FINALIZE: p0, RT_COLSUM): layout of the partials, as part_at takes it (0: column-major)
 };
 constexpr int kMaxReduceTasks = 36;      // one launch for all 30 tasks of a 4-layer backward pass (5.5 KB of kernel arguments)
 struct ReduceTasks {
@@ -221,11 +224,12 @@ struct WgradTasks {
 // what the queue's methods take: pointers and counts, nothing of the caller's own types
 struct AttParamGrads {       // dL/d(attention vector [H][att_w], edge embedding) of a level from the partial rows its pass wrote
     int H;
-    const float* part_a;  int n_a;      // column-major [2 * 128][FN_MAX_PART]: destination / source block partials, n_a rows written
+    const float* part_a;  int n_a;      // destination / source block partials [n_a rows written][2 * 128] in the layout part_ld names
     const float* part_e;  int n_e;      // mode-2 levels: [n_e][H * (K + 1)] edge-embedding partials (else null / 0)
     fn_edge_term et;
     const float* att;  int att_w, src_off;      // the level's attention vector; destination block at 0, source block at src_off
     float *g_att, *g_embW, *g_embb;     // out (the last two: mode 2 only)
+    int part_ld;                        // layout of part_a (part_at): 0 = column-major [2 * 128][FN_MAX_PART], else row-major with this leading dimension
 };
 struct ProjWgrad {           // dW [128][K], db [128] of a projection from its gradient rows g_h [M][128] and input rows x [M][K]
     const float *g_h, *x;
@@ -243,8 +247,9 @@ struct FNI_HIDDEN ParamGradQueue {
     bool defer_mixed = false;               // layer 0's products (K != 128) wait for a grouped launch too, instead of one launch each
     fn_adam_slice* rider = nullptr;         // fn_encoder.adam_rider: rides in the LAST deferred-reduction launch of the pass (null: none, or gone elsewhere)
     int finalize(const AttParamGrads& a);
-    // out[(col / 128) * ld + off + col % 128] = sum of the n_rows written rows of column col of part (column-major [cols][FN_MAX_PART])
-    int colsum(const float* part, int n_rows, int cols, float* out, int ld, int off);
+    // out[(col / 128) * ld + off + col % 128] = sum of the n_rows written rows of column col of part (part_ld == 0: column-major
+    // [cols][FN_MAX_PART]; else row-major [n_rows][part_ld])
+    int colsum(const float* part, int n_rows, int cols, float* out, int ld, int off, int part_ld = 0);
     // partial product now (on `launch_on`) where it is launched alone, else with its group in flush(); reduction with the rest
     int wgrad(const ProjWgrad& p, hipStream_t launch_on);
     int flush(bool last = false);           // last: the pass's final flush, which carries the rider
@@ -388,6 +393,17 @@ __device__ __forceinline__ int xcd_block(int b, int nwg) {
 #ifndef FN_PAD_BLOCK_EXIT
 #define FN_PAD_BLOCK_EXIT 1
 #endif
+// Per-block partial sums of the parameter gradients (part_a, the edge term's part_rd): a table of `cols` columns and one row per
+// block.  The operator entry points keep it column-major [cols][FN_MAX_PART] (ld == 0: what their callers index); the engine's own
+// tables are row-major [rows][ld], so a block's 256 .. 768 values are full cache lines instead of 4-byte stores 16 KB apart.  The
+// deferred reduction adds the rows of a column in the same order either way (param_grads.hip: rowmajor_sum_32).
+// -DFN_PART_ROWMAJOR=0: the engine's tables are column-major too (the A/B arm; same sums bit for bit).
+#ifndef FN_PART_ROWMAJOR
+#define FN_PART_ROWMAJOR 1
+#endif
+__device__ __forceinline__ size_t part_at(int ld, int row, int col) {
+    return ld ? (size_t)row * ld + col : (size_t)col * FN_MAX_PART + row;
+}
 // The same for a static-shape batch whose rows behind logical block `nreal` are padding.  Dealing CAPACITY blocks into eight chunks
 // leaves the last XCD with mostly padding and the other seven with capacity / 8 rows each instead of real / 8 -- 8 % padding made the
 // attention launches 6-9 % longer (round 4).  Here the REAL blocks [0, nreal) are dealt evenly (contiguous chunks as above) and the

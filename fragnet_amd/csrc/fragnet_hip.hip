@@ -625,7 +625,7 @@ constexpr TuneRange kTuneRange[FN_TUNE_COUNT] = {
     {"FWD_BLOCKS_EVAL", 1, kTuneBlocks},         // 10
     {"DST_BLOCKS", 1, FN_MAX_PART},              // 11: a row of part_e per block
     {"SRC_BLOCKS", 1, 1024},                     // 12: prep_gat_bwd_src's bound
-    {"RD_BLOCKS", 1, FN_MAX_PART},               // 13: the column stride of part_rd
+    {"RD_BLOCKS", 1, FN_MAX_PART},               // 13: the rows a part_rd table holds
     {"GEMM_COLAUNCH", 0, 2},                     // 14
     kRetired, kRetired, kRetired, kRetired, kRetired,      // 15 .. 19
     {"MOL_TAIL", 0, 2},                          // 20

@@ -310,7 +310,7 @@ __device__ __forceinline__ void gat_bwd_one_rows(const GatBwdOneArgs& A, float (
         float a = 0.f;
 #pragma unroll
         for (int w = 0; w < RB; ++w) a += sA[w][c];
-        A.part_a[(size_t)c * FN_MAX_PART + bid] = a;        // column-major: finalize reads a column contiguously
+        A.part_a[part_at(A.part_ld, bid, c)] = a;           // (row-major, the engine's tables: consecutive threads, consecutive words)
     }
     if (KL) {
         // deterministic block partial of sum_e dz[e,h] * (x[e,0..K), 1); columns k >= K carry weight-0 duplicates
@@ -337,7 +337,7 @@ __device__ __forceinline__ void gat_bwd_one_body(const GatBwdOneArgs& A, float (
         // zero gradient rows and zero partial sums, without the two dependent round trips and the row loop of the pipeline
         const int lane = threadIdx.x & 31, hw = threadIdx.x >> 5, end = blk0 + per < n ? blk0 + per : n;
         for (int s = blk0 + hw; s < end; s += RB) st4(A.g_h + (size_t)s * FN_D + lane * 4, make_float4(0.f, 0.f, 0.f, 0.f));
-        for (int c = threadIdx.x; c < 2 * FN_D; c += blockDim.x) A.part_a[(size_t)c * FN_MAX_PART + bid] = 0.f;
+        for (int c = threadIdx.x; c < 2 * FN_D; c += blockDim.x) A.part_a[part_at(A.part_ld, bid, c)] = 0.f;
         if (KL) {
             const int ne = H * (A.et.K + 1);
             for (int i = threadIdx.x; i < ne; i += blockDim.x) A.part_e[(size_t)bid * ne + i] = 0.f;

@@ -247,6 +247,7 @@ struct GatBwdSrcArgs {
     fn_gat_plan pl;
     float *g_h, *part_a;
     int rows_per_hw, nblk;
+    int part_ld;              // layout of part_a (part_at, fn_internal.h): 0 = column-major [256][FN_MAX_PART], else row-major [nblk][part_ld]
 };
 // source rows [blk0, se) interleaved over the block's RB half-waves; bid: the block's slot (row) in part_a
 template <int H, int RB>
@@ -369,7 +370,7 @@ __device__ __forceinline__ void gat_bwd_src_rows(const GatBwdSrcArgs& A, float (
         float a = 0.f;
 #pragma unroll
         for (int w = 0; w < RB; ++w) a += sA[w][c];
-        part_a[(size_t)c * FN_MAX_PART + bid] = a;          // column-major: finalize reads a column contiguously
+        part_a[part_at(A.part_ld, bid, c)] = a;
     }
 }
 
@@ -443,7 +444,7 @@ inline int prep_gat_bwd_src(const float* g_out, const float* h, const float* pz_
     if (plan->n == 0) return 0;
     if (plan->n > (1 << 23) || plan->m * heads > (1 << 28))
         return fni::fail(FN_EUNSUPPORTED, "fn_gat_bwd_src_f32: level too large for 32-bit byte offsets (n <= 2^23 rows, m*heads <= 2^28)");
-    // every block writes 256 partial sums column-major (scattered): at most 1024 blocks, each half-wave pipelining R rows
+    // every block writes a row of 256 partial sums: at most 1024 blocks, each half-wave pipelining R rows
     const int64_t groups = (plan->n + kBwdRows - 1) / kBwdRows;
     int64_t resident = (int64_t)fni::tune(FN_TUNE_SRC_BLOCKS);
     if (resident > 1024 || resident < 1) resident = 1024;

@@ -456,7 +456,7 @@ __device__ __forceinline__ void tail_bwd_lds(const TailBwdArgs& T, const MolExt&
         float v = 0.f;
 #pragma unroll
         for (int w = 0; w < kRows; ++w) v += P[w * 2 * FN_D + tid];
-        T.S.part_a[(size_t)tid * FN_MAX_PART + mol] = v;
+        T.S.part_a[part_at(T.S.part_ld, mol, tid)] = v;
     }
     __syncthreads();
 #pragma unroll
@@ -466,7 +466,7 @@ __device__ __forceinline__ void tail_bwd_lds(const TailBwdArgs& T, const MolExt&
         float v = 0.f;
 #pragma unroll
         for (int w = 0; w < kRows; ++w) v += P[w * H * FN_D + c];
-        T.R.part[(size_t)c * FN_MAX_PART + mol] = v;
+        T.R.part[part_at(T.R.part_ld, mol, c)] = v;
     }
     // ---- dL/d(atoms_new) = gate(dL/d(out_atoms) + the readout's share) + dL/d(fragment sums)[fragment of the atom]
     for (int i0 = hw; i0 < x.na; i0 += 4 * kRows) {
@@ -561,8 +561,8 @@ __global__ __launch_bounds__(kBlock) void k_tail_bwd(TailBwdArgs T, AdamRide R) 
         // (zero gradient rows have zero dots)
         if (T.cu_c) for (int i = x.a0 * H + (int)threadIdx.x; i < (x.a0 + x.na) * H; i += kBlock) { T.cu_c[i] = 0.f;  if (T.cu_u) T.cu_u[i] = 0.f; }
         if (T.R.cu_c) for (int c = x.c0 * H + (int)threadIdx.x; c < (x.c0 + x.nc) * H; c += kBlock) { T.R.cu_c[c] = 0.f;  if (T.R.cu_u) T.R.cu_u[c] = 0.f; }
-        T.S.part_a[(size_t)threadIdx.x * FN_MAX_PART + mol] = 0.f;                     // 2 * FN_D == kBlock columns
-        for (int c = threadIdx.x; c < H * FN_D; c += kBlock) T.R.part[(size_t)c * FN_MAX_PART + mol] = 0.f;
+        T.S.part_a[part_at(T.S.part_ld, mol, (int)threadIdx.x)] = 0.f;                   // 2 * FN_D == kBlock columns
+        for (int c = threadIdx.x; c < H * FN_D; c += kBlock) T.R.part[part_at(T.R.part_ld, mol, c)] = 0.f;
         return;
     }
     if (x.nf <= kTailNF && x.mec <= kTailME && x.nc <= kTailME && T.force_global == 0) tail_bwd_lds<H>(T, x, mol, L);

@@ -230,10 +230,10 @@ __global__ __launch_bounds__(1024) void k_wgrad_reduce(const float* __restrict__
 // partials of each level, the edge-term column sums, the weight-gradient partials) in its own buffer and records a
 // task; ONE launch then runs them all (a dependent kernel costs >= 4.6 us of launch-to-launch latency on this
 // machine however small it is, and there were 27 of these per step).  (ReduceTask / ReduceTasks: fn_internal.h)
-// "fat" bodies for the task-table kernel: a block reduces 8 columns of a column-major [cols][FN_MAX_PART] partial
-// array (128 threads per column, contiguous reads), or a 256-column strip of the row-major weight-gradient partials
-// (64 float4 columns x 16 row groups: 1 KiB contiguous per wave and row) -- ~1.5 k blocks per backward pass instead
-// of ~10 k one-column blocks.
+// "fat" bodies for the task-table kernel: a block reduces 32 columns of a per-block partial table (32 threads per column:
+// column-major [cols][FN_MAX_PART] with contiguous reads, or the engine's row-major rows, rowmajor_sum_32 below), or a
+// 1024-column strip of the row-major weight-gradient partials (wgrad_reduce_strip) -- ~1.5 k blocks per backward pass
+// instead of ~10 k one-column blocks.
 // the same sum with 32 threads per column (a 1024-thread block takes 32 columns: a quarter of the blocks of the 128-thread form --
 // the deferred-reduction launch is mostly block scheduling, §6); no LDS, no barrier: the half-wave's butterfly finishes it
 __device__ __forceinline__ float colmajor_sum_32(const float* __restrict__ col, int n_rows) {
@@ -243,6 +243,29 @@ __device__ __forceinline__ float colmajor_sum_32(const float* __restrict__ col, 
     for (; r + 96 < n_rows; r += 128) { v += col[r];  v1 += col[r + 32];  v2 += col[r + 64];  v3 += col[r + 96]; }
     for (; r < n_rows; r += 32) v += col[r];
     v = (v + v1) + (v2 + v3);
+#pragma unroll
+    for (int off = 16; off > 0; off >>= 1) v += __shfl_xor(v, off);
+    return v;
+}
+// The row-major twin (the engine's tables, part_at in fn_internal.h): the 32 columns [col0, col0 + 32) of part [n_rows][ld] by one
+// 1024-thread block, the sum of column col0 + (threadIdx.x >> 5) returned to all 32 threads of that half-wave.  The ADDITIONS are
+// colmajor_sum_32's, operand for operand -- every gradient keeps its bits -- only the threads that do them differ: the four chains of
+// lane r of a column run in thread 32 r + c (c: the column), so a wave reads two rows x 32 consecutive columns (128-byte runs; the
+// stride-ld walk of one column by one half-wave would be 32 sectors per load); the chain sums then change threads through LDS
+// (sm: 32 x 33 floats) to the half-wave that owns the column, which joins them with the very same butterfly.
+__device__ __forceinline__ float rowmajor_sum_32(const float* __restrict__ part, int ld, int col0, int n_rows, float* sm) {
+    const int c = threadIdx.x & 31, lane = threadIdx.x >> 5;
+    const float* __restrict__ p = part + col0 + c;
+    float v = 0.f, v1 = 0.f, v2 = 0.f, v3 = 0.f;
+    int r = lane;
+    for (; r + 96 < n_rows; r += 128) {
+        v += p[(size_t)r * ld];  v1 += p[(size_t)(r + 32) * ld];  v2 += p[(size_t)(r + 64) * ld];  v3 += p[(size_t)(r + 96) * ld];
+    }
+    for (; r < n_rows; r += 32) v += p[(size_t)r * ld];
+    v = (v + v1) + (v2 + v3);
+    sm[lane * 33 + c] = v;
+    __syncthreads();
+    v = sm[(threadIdx.x & 31) * 33 + (threadIdx.x >> 5)];       // lane threadIdx.x & 31 of column threadIdx.x >> 5
 #pragma unroll
     for (int off = 16; off > 0; off >>= 1) v += __shfl_xor(v, off);
     return v;
@@ -392,7 +415,7 @@ __global__ __launch_bounds__(1024) void k_reduce_tasks(ReduceTasks T, AdamRide R
     if (t.kind == RT_FINALIZE) {
         if (vb < 2 * FN_D / 32) {
             const int col = vb * 32 + (threadIdx.x >> 5);
-            const float v = colmajor_sum_32(t.p0 + (size_t)col * FN_MAX_PART, t.n0);
+            const float v = t.pld ? rowmajor_sum_32(t.p0, t.pld, vb * 32, t.n0, sm) : colmajor_sum_32(t.p0 + (size_t)col * FN_MAX_PART, t.n0);
             if ((threadIdx.x & 31) == 0) {
                 const int DH = FN_D / t.H, cc = col & 127, part = col >> 7;
                 t.o0[(cc / DH) * t.att_w + (part ? t.src_off : t.dst_off) + (cc % DH)] = v;
@@ -402,7 +425,7 @@ __global__ __launch_bounds__(1024) void k_reduce_tasks(ReduceTasks T, AdamRide R
         }
     } else if (t.kind == RT_COLSUM) {
         const int col = vb * 32 + (threadIdx.x >> 5);
-        const float v = colmajor_sum_32(t.p0 + (size_t)col * FN_MAX_PART, t.n0);
+        const float v = t.pld ? rowmajor_sum_32(t.p0, t.pld, vb * 32, t.n0, sm) : colmajor_sum_32(t.p0 + (size_t)col * FN_MAX_PART, t.n0);
         if ((threadIdx.x & 31) == 0) t.o0[(col / FN_D) * t.ld + t.off + (col % FN_D)] = v;
     } else {
         switch (t.cls) {      // ReduceTask::cls: the class of the kernel that wrote the partials (wgrad_class, below)
@@ -491,11 +514,12 @@ int ParamGradQueue::finalize(const AttParamGrads& a) {
     ReduceTask t{};
     t.kind = RT_FINALIZE;  t.H = a.H;  t.p0 = a.part_a;  t.n0 = a.n_a;  t.p1 = a.part_e;  t.n1 = a.n_e;  t.et = a.et;
     t.att = a.att;  t.att_w = a.att_w;  t.dst_off = 0;  t.src_off = a.src_off;  t.o0 = a.g_att;  t.o1 = a.g_embW;  t.o2 = a.g_embb;
+    t.pld = a.part_ld;
     return push(t, 2 * FN_D / 32 + (a.et.mode == 2 ? 1 : 0));
 }
-int ParamGradQueue::colsum(const float* part, int n_rows, int cols, float* out, int ld, int off) {
+int ParamGradQueue::colsum(const float* part, int n_rows, int cols, float* out, int ld, int off, int part_ld) {
     ReduceTask t{};
-    t.kind = RT_COLSUM;  t.p0 = part;  t.n0 = n_rows;  t.o0 = out;  t.ld = ld;  t.off = off;
+    t.kind = RT_COLSUM;  t.p0 = part;  t.n0 = n_rows;  t.o0 = out;  t.ld = ld;  t.off = off;  t.pld = part_ld;
     if (cols % 32) return fail(FN_EINVAL, "deferred column sum: column count must be a multiple of 32");
     return push(t, cols / 32);
 }

@@ -74,7 +74,7 @@ int fn_abi_version(void);
 #define FN_TUNE_DST_BLOCKS 11  /* target workgroup count of the backward destination pass (default 1536: three rows per half-wave at ESOL batch
                                 * 512; never more than three rows, see prep_gat_bwd_dst).  [1, FN_MAX_PART] */
 #define FN_TUNE_SRC_BLOCKS 12  /* resident workgroups of the backward source pass (default 512; every block writes a row of partial sums).  [1, 1024] */
-#define FN_TUNE_RD_BLOCKS 13   /* (default 512; 256 until round 5) workgroups of the edge-term backward that shares the source pass's launch (each writes a row of partial sums, FN_MAX_PART is their column stride).  [1, FN_MAX_PART] */
+#define FN_TUNE_RD_BLOCKS 13   /* (default 512; 256 until round 5) workgroups of the edge-term backward that shares the source pass's launch (each writes a row of partial sums; a table holds FN_MAX_PART rows).  [1, FN_MAX_PART] */
 #define FN_TUNE_GEMM_COLAUNCH 14 /* inside fn_encoder_*: the 128 -> 128 projections (forward) and input-gradient products (backward) that do
                                  * not depend on an attention pass ride along as extra workgroups of that pass's launch (the atom projection
                                  * beside the bond + fragment-bond levels, the next layer's bond / fragment-bond projections beside the atom
