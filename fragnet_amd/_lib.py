@@ -265,8 +265,11 @@ for _fam in ("fn_cdrp_pair", "fn_dta_pair"):
     # the same head on a factored batch (csrc/pair_factored.hip): unique rows, pair lists, pair orderings
     SIGNATURES[_fam + "_factored_ws"] = [i64, i64]
     SIGNATURES[_fam + "_factored_fwd_f32"] = [vp] * 15 + [i64] * 7 + [vp]
+    SIGNATURES[_fam + "_factored_fwd_rows_f32"] = [vp] * 15 + [i64] * 7 + [vp, vp]      # + the device-side real-pair count
     SIGNATURES[_fam + "_factored_bwd_f32"] = [vp] * 19 + [i64, vp] + [i64] * 7 + [vp]
     SIGNATURES[_fam + "_factored_grid_f32"] = [vp] * 7 + [i64] * 6 + [vp]
+# both pair orderings of a factored batch in one launch (csrc/pair_factored.hip): pair lists, the real-pair count, 2 x (rowptr, perm)
+SIGNATURES["fn_pair_orderings_i32"] = [vp] * 7 + [i64] * 3 + [vp]
 
 _lib = None
 

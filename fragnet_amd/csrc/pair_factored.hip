@@ -15,6 +15,9 @@
 // tile-row dot with w2 and the end of a dW1 column block are written here and, the same statements, in pair_head.hip (why:
 // pair_bodies.inc); this unit's own are the per-row sums of g over the pair orderings (pf_sigma), the forward's one loss partial and
 // the grid's dot, which reads global memory.
+// For a step over static capacities (graphstep.FactoredPairGraphedTrainStep): fn_pair_orderings_i32 builds both sides' orderings in one
+// launch under a device-side count of the real pairs (k_pair_orderings: integers only, a sort of distinct keys), and
+// fn_*_pair_factored_fwd_rows_f32 is the forward under the same count; the backward is the one above, without a count.
 #include <stdint.h>
 #include <stdio.h>
 
@@ -58,13 +61,18 @@ __device__ __forceinline__ void pf_tile(const float* __restrict__ X, const float
 // forward, one launch.  Workgroups [0, nbU): 16 rows of A and their alpha; the next nbC: 16 rows of B and their beta.  Each publishes its
 // rows (agent-scope release, then one relaxed add on the arrival counter, which the host zeroes in front of the launch); the workgroup
 // that arrives last acquires and writes out[M] and, with a target, g[M] and the one loss partial (already divided by M).
+// real_pairs (nullable; fn_*_pair_factored_fwd_rows_f32): the int32 word a static-shape step's staging launch writes (FN_STAGE_COUNT),
+// n = *real_pairs clamped to [0, M].  The mean is then over the first n pairs: g = 2 (out - y) / n and the partial is divided by n; behind
+// them out = 0, g = 0 exactly, no share of the loss, and the pair lists are not read; n = 0: nothing is divided.  The backward needs no
+// count: with orderings of the first n pairs (k_pair_orderings) a padding pair is in no segment, a distinct row without a real pair has
+// sigma = 0 -- g_D / g_S exact zeros -- and adds 0 * x to dW1 and dW2, in the same lane at the same place of the same sums.
 template <int K1>
 __global__ __launch_bounds__(256) void k_pairf_fwd(const float* __restrict__ D, const float* __restrict__ Sx, const int64_t* __restrict__ pd,
                                                    const int64_t* __restrict__ ps, const float* __restrict__ W1, const float* __restrict__ b1,
                                                    const float* __restrict__ w2, const float* __restrict__ b2, const float* __restrict__ target,
                                                    float* __restrict__ A, float* __restrict__ B, float* ab, unsigned* counter,
                                                    float* __restrict__ out, float* __restrict__ g, float* __restrict__ loss_part, int M, int U,
-                                                   int C, int nbU) {
+                                                   int C, int nbU, const int* __restrict__ real_pairs) {
     constexpr int kInT = kIn0 + K1;
     __shared__ float sh[kTileRows][kHid + 1];
     __shared__ float sred[256];
@@ -102,16 +110,19 @@ __global__ __launch_bounds__(256) void k_pairf_fwd(const float* __restrict__ D, 
     __syncthreads();
     const float cst = sred[0];
     __syncthreads();
+    const int nr = real_pairs ? min(max(*real_pairs, 0), M) : M;    // pairs the loss is a mean over: all of them without a count
     float d2 = 0.f;
     for (int m = t; m < M; m += 256) {
-        const int64_t u = pd[m], c = ps[m];
         float o = 0.f, gm = 0.f;
-        if (u >= 0 && u < U && c >= 0 && c < C) {
-            o = ab[u] + ab[U + c] + cst;
-            if (target) {
-                const float d = o - target[m];
-                gm = 2.f * d / (float)M;
-                d2 += d * d;
+        if (m < nr) {                                                // behind the count the pair lists are not read
+            const int64_t u = pd[m], c = ps[m];
+            if (u >= 0 && u < U && c >= 0 && c < C) {
+                o = ab[u] + ab[U + c] + cst;
+                if (target) {
+                    const float d = o - target[m];
+                    gm = 2.f * d / (float)nr;
+                    d2 += d * d;
+                }
             }
         }
         out[m] = o;
@@ -123,7 +134,7 @@ __global__ __launch_bounds__(256) void k_pairf_fwd(const float* __restrict__ D, 
     if (t == 0) {
         float s = sred[0];
         for (int q = 1; q < 256; ++q) s += sred[q];
-        loss_part[0] = s / (float)M;
+        loss_part[0] = nr > 0 ? s / (float)nr : 0.f;
     }
 }
 
@@ -275,6 +286,65 @@ __global__ __launch_bounds__(256) void k_pairf_grid(const float* __restrict__ D,
     for (int r = 0; r < kTileRows && u0 + r < U; ++r) out[(size_t)(u0 + r) * C + c] = sa[r] + bt;
 }
 
+// the pair orderings of both sides in one launch (ops.pair_orderings is the reference): workgroup 0 the drug list, workgroup 1 the second's.
+// Pair m < n (n = *real_pairs clamped to [0, M]; all M without a count) whose value v lies in [0, N) -- tested as int64, before it is
+// narrowed -- gets the key (v << 12 | m) < 2^24; every other position m < M gets (2^24 | m), and the tail up to the power of two P gets
+// all ones.  The keys are distinct, so their ascending order is unique: a bitonic network in LDS (P <= 4096 words) sorts them, and
+// nothing depends on the order in which anything lands -- there is no atomic.  perm[i] = the key's low 12 bits where it is < 2^24, else
+// -1; rowptr[r] = the number of keys below (r << 12), by binary search, r = 0 .. N (N << 12 <= 2^24: rowptr[N] counts the in-range pairs).
+// Behind n the pair lists are not read.
+constexpr int kOrdThreads = 1024, kOrdShift = 12, kOrdMax = 1 << kOrdShift;
+static_assert(FN_DENSE_MAX_ROWS <= kOrdMax, "a row and a pair index share a 24-bit key");
+__global__ __launch_bounds__(kOrdThreads) void k_pair_orderings(const int64_t* __restrict__ pd, const int64_t* __restrict__ ps,
+                                                                const int* __restrict__ real_pairs, int32_t* __restrict__ rp_d,
+                                                                int32_t* __restrict__ pm_d, int32_t* __restrict__ rp_s,
+                                                                int32_t* __restrict__ pm_s, int M, int U, int C, int P) {
+    __shared__ uint32_t key[kOrdMax];
+    const int t = threadIdx.x;
+    const bool first = blockIdx.x == 0;
+    const int64_t* __restrict__ pl = first ? pd : ps;
+    int32_t* __restrict__ rp = first ? rp_d : rp_s;
+    int32_t* __restrict__ pm = first ? pm_d : pm_s;
+    const int N = first ? U : C;
+    const int n = real_pairs ? min(max(*real_pairs, 0), M) : M;
+    constexpr uint32_t kOut = 1u << (2 * kOrdShift);
+    for (int i = t; i < P; i += kOrdThreads) {
+        uint32_t k = 0xffffffffu;
+        if (i < M) {
+            k = kOut | (uint32_t)i;
+            if (i < n) {
+                const int64_t v = pl[i];
+                if (v >= 0 && v < (int64_t)N) k = ((uint32_t)v << kOrdShift) | (uint32_t)i;
+            }
+        }
+        key[i] = k;
+    }
+    __syncthreads();
+    for (int k = 2; k <= P; k <<= 1)
+        for (int j = k >> 1; j > 0; j >>= 1) {
+            for (int i = t; i < (P >> 1); i += kOrdThreads) {
+                const int lo = ((i & ~(j - 1)) << 1) | (i & (j - 1)), hi = lo | j;
+                const uint32_t a = key[lo], b = key[hi];
+                if ((a > b) == ((lo & k) == 0)) { key[lo] = b;  key[hi] = a; }
+            }
+            __syncthreads();
+        }
+    for (int i = t; i < M; i += kOrdThreads) {
+        const uint32_t k = key[i];
+        pm[i] = k < kOut ? (int32_t)(k & (kOrdMax - 1)) : -1;
+    }
+    for (int r = t; r <= N; r += kOrdThreads) {
+        const uint32_t want = (uint32_t)r << kOrdShift;
+        int lo = 0, hi = P;                                          // the first position whose key is >= want
+        while (lo < hi) {
+            const int mid = (lo + hi) >> 1;
+            if (key[mid] < want) lo = mid + 1;
+            else hi = mid;
+        }
+        rp[r] = min(lo, M);
+    }
+}
+
 // ---- host side (fail_at, check_widths, zero_param_grads: pair_bodies.inc)
 int check_counts(const char* who, int64_t M, int64_t U, int64_t C) {
     if (M < 0 || M > FN_DENSE_MAX_ROWS || U < 0 || U > FN_DENSE_MAX_ROWS || C < 0 || C > FN_DENSE_MAX_ROWS)
@@ -286,9 +356,11 @@ int64_t factored_ws(int64_t U, int64_t C) { return U < 0 || C < 0 ? 0 : U + C + 
 template <int K1>
 int pairf_fwd(const char* who, const float* D, const float* Sx, const int64_t* pd, const int64_t* ps, const float* W1, const float* b1,
               const float* w2, const float* b2, const float* target, float* A, float* B, float* ws, float* out, float* g, float* loss_part,
-              int64_t M, int64_t U, int64_t C, int64_t Kd, int64_t K, int64_t H, int64_t Co, fn_stream_t stream) {
+              int64_t M, int64_t U, int64_t C, int64_t Kd, int64_t K, int64_t H, int64_t Co, const int32_t* real_pairs, fn_stream_t stream) {
     FN_TRY(check_widths<K1>("pair_factored_*", Kd, K, H, Co));
     FN_TRY(check_counts(who, M, U, C));
+    if (real_pairs && (!target || ((uintptr_t)real_pairs & 3)))
+        return fail_at(FN_EINVAL, who, "a real-pair count goes with a target (and is an aligned int32)");
     if (M == 0) return 0;
     if (U == 0 || C == 0) return fail_at(FN_EINVAL, who, "pairs (M > 0) need U >= 1 and C >= 1");
     if (!D || !Sx || !pd || !ps || !W1 || !b1 || !w2 || !b2 || !A || !B || !ws || !out || (target && (!g || !loss_part)) ||
@@ -298,7 +370,7 @@ int pairf_fwd(const char* who, const float* D, const float* Sx, const int64_t* p
     if (hipMemsetAsync(counter, 0, sizeof(unsigned), S(stream)) != hipSuccess) return launch_status(who);
     const int nbU = (int)((U + kTileRows - 1) / kTileRows), nbC = (int)((C + kTileRows - 1) / kTileRows);
     hipLaunchKernelGGL(k_pairf_fwd<K1>, dim3((unsigned)(nbU + nbC)), dim3(256), 0, S(stream), D, Sx, pd, ps, W1, b1, w2, b2, target, A, B, ws,
-                       counter, out, g, loss_part, (int)M, (int)U, (int)C, nbU);
+                       counter, out, g, loss_part, (int)M, (int)U, (int)C, nbU, real_pairs);
     return launch_status(who);
 }
 
@@ -343,6 +415,23 @@ int pairf_grid(const char* who, const float* D, const float* Sx, const float* W1
 
 extern "C" {
 
+int fn_pair_orderings_i32(const int64_t* pair_drug, const int64_t* pair_second, const int32_t* real_pairs, int32_t* rowptr_drug,
+                          int32_t* perm_drug, int32_t* rowptr_second, int32_t* perm_second, int64_t M, int64_t U, int64_t Cn,
+                          fn_stream_t stream) {
+    const char* who = "fn_pair_orderings_i32";
+    if (M < 0 || M > FN_DENSE_MAX_ROWS || U < 0 || U > FN_DENSE_MAX_ROWS || Cn < 0 || Cn > FN_DENSE_MAX_ROWS)
+        return fail_at(FN_EINVAL, who, "0 <= M, U, C <= FN_DENSE_MAX_ROWS");
+    if (!rowptr_drug || !rowptr_second || (M > 0 && (!pair_drug || !pair_second || !perm_drug || !perm_second)) ||
+        misaligned(7, pair_drug, pair_second) || misaligned(3, rowptr_drug, perm_drug, rowptr_second, perm_second) ||
+        ((uintptr_t)real_pairs & 3))
+        return fail_at(FN_EINVAL, who, "null or misaligned buffer");
+    int P = 2;                                            // the sorting network's size: the power of two that holds M keys
+    while (P < M) P <<= 1;
+    hipLaunchKernelGGL(k_pair_orderings, dim3(2), dim3(kOrdThreads), 0, S(stream), pair_drug, pair_second, real_pairs, rowptr_drug, perm_drug,
+                       rowptr_second, perm_second, (int)M, (int)U, (int)Cn, P);
+    return launch_status(who);
+}
+
 int64_t fn_cdrp_pair_factored_ws(int64_t U, int64_t C) { return factored_ws(U, C); }
 int64_t fn_dta_pair_factored_ws(int64_t U, int64_t C) { return factored_ws(U, C); }
 
@@ -351,14 +440,28 @@ int fn_cdrp_pair_factored_fwd_f32(const float* drug, const float* cell, const in
                                   float* out, float* g, float* loss_part, int64_t M, int64_t U, int64_t Cn, int64_t Kd, int64_t Kc, int64_t H,
                                   int64_t C, fn_stream_t stream) {
     return pairf_fwd<256>("fn_cdrp_pair_factored_fwd_f32", drug, cell, pair_drug, pair_cell, W1, b1, w2, b2, target, A, B, ws, out, g, loss_part,
-                          M, U, Cn, Kd, Kc, H, C, stream);
+                          M, U, Cn, Kd, Kc, H, C, nullptr, stream);
+}
+int fn_cdrp_pair_factored_fwd_rows_f32(const float* drug, const float* cell, const int64_t* pair_drug, const int64_t* pair_cell, const float* W1,
+                                       const float* b1, const float* w2, const float* b2, const float* target, float* A, float* B, float* ws,
+                                       float* out, float* g, float* loss_part, int64_t M, int64_t U, int64_t Cn, int64_t Kd, int64_t Kc,
+                                       int64_t H, int64_t C, const int32_t* real_pairs, fn_stream_t stream) {
+    return pairf_fwd<256>("fn_cdrp_pair_factored_fwd_rows_f32", drug, cell, pair_drug, pair_cell, W1, b1, w2, b2, target, A, B, ws, out, g,
+                          loss_part, M, U, Cn, Kd, Kc, H, C, real_pairs, stream);
 }
 int fn_dta_pair_factored_fwd_f32(const float* drug, const float* xt, const int64_t* pair_drug, const int64_t* pair_prot, const float* W1,
                                  const float* b1, const float* w2, const float* b2, const float* target, float* A, float* B, float* ws,
                                  float* out, float* g, float* loss_part, int64_t M, int64_t U, int64_t Cn, int64_t Kd, int64_t Kx, int64_t H,
                                  int64_t C, fn_stream_t stream) {
     return pairf_fwd<300>("fn_dta_pair_factored_fwd_f32", drug, xt, pair_drug, pair_prot, W1, b1, w2, b2, target, A, B, ws, out, g, loss_part, M,
-                          U, Cn, Kd, Kx, H, C, stream);
+                          U, Cn, Kd, Kx, H, C, nullptr, stream);
+}
+int fn_dta_pair_factored_fwd_rows_f32(const float* drug, const float* xt, const int64_t* pair_drug, const int64_t* pair_prot, const float* W1,
+                                      const float* b1, const float* w2, const float* b2, const float* target, float* A, float* B, float* ws,
+                                      float* out, float* g, float* loss_part, int64_t M, int64_t U, int64_t Cn, int64_t Kd, int64_t Kx,
+                                      int64_t H, int64_t C, const int32_t* real_pairs, fn_stream_t stream) {
+    return pairf_fwd<300>("fn_dta_pair_factored_fwd_rows_f32", drug, xt, pair_drug, pair_prot, W1, b1, w2, b2, target, A, B, ws, out, g,
+                          loss_part, M, U, Cn, Kd, Kx, H, C, real_pairs, stream);
 }
 
 int fn_cdrp_pair_factored_bwd_f32(const float* g, const float* drug, const float* cell, const float* A, const float* B, const float* W1,

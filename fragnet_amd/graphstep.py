@@ -24,6 +24,8 @@ same collective as in the eager step.
 
 ``PairGraphedTrainStep`` is the same step for the pair models (cdrp.CDRPModel, dta.DTAModel2): the second input's int64 rows are
 staged too, and the pair head's fused loss reads the real-row count the staging launch wrote instead of a weight vector.
+``FactoredPairGraphedTrainStep`` is that step on FACTORED pair batches: two more index spaces (pairs, distinct second inputs) with
+capacities of their own (``FactoredPairShapes``), and the pair orderings built inside the graph.
 """
 from __future__ import annotations
 
@@ -144,6 +146,10 @@ class StaticShapes:
                     return False
         return True
 
+    def capacity(self, space: str) -> int:
+        """Rows a staged field of ``space`` has (a subclass may know index spaces outside ``cap``)."""
+        return self.cap[space]
+
     def pad_rule(self, target: str):
         """(pad_hi, pad_mod): padding position i of a field pointing into ``target`` holds pad_hi - (i - n_real) % pad_mod."""
         return self.cap[target] - 1, self.slack[target]
@@ -209,6 +215,90 @@ def pad_pair_batch(batch: Dict[str, torch.Tensor], shapes: StaticShapes) -> Dict
     return out
 
 
+# A FACTORED pair batch (data.collate_fn_*_factored) has two index spaces the encoder knows nothing of: ``pair`` (its M pairs: y and the
+# two pair lists) and ``second`` (its C distinct second inputs).  Neither is in plan.SPACES or in the offsets table; nothing points INTO
+# them through a padded index, so they need no slack: a capacity each (FactoredPairShapes).  ``y`` takes the place of FIELDS' entry.
+PAIR_SPACES = ("pair", "second")
+FACTORED_PAIR_FIELDS = {"y": ("pair", "rows", None), "gene_expr": ("second", "rows_i64", None), "protein": ("second", "rows_i64", None),
+                        "pair_drug": ("pair", "vec_i64", None), "pair_second": ("pair", "vec_i64", None)}
+REAL_PAIRS_KEY = "_real_pairs"    # StaticBatch.add_count("pair"): device-side count of the real pairs of a staged factored batch
+
+
+def factored_batch_counts(batch: Dict[str, torch.Tensor]) -> Dict[str, int]:
+    """``batch_counts`` of a factored pair batch: the molecule count is the one the batch carries (``plan.N_MOLS_KEY``; ``y`` has one
+    entry per PAIR), plus the two spaces of PAIR_SPACES."""
+    from .plan import batch_n_mols
+    counts = {sp: int(batch[f].shape[0]) for sp, f in COUNT_FIELD.items() if sp != "mol"}
+    counts["mol"] = batch_n_mols(batch)
+    counts["pair"] = int(batch["y"].shape[0])
+    counts["second"] = int(next(batch[k] for k in PAIR_FIELDS if k in batch).shape[0])
+    return counts
+
+
+class FactoredPairShapes(StaticShapes):
+    """``StaticShapes`` plus ``pair_cap`` and ``second_cap``.  ``cap`` / ``slack`` keep plan.SPACES' seven entries (the plan builder's
+    padding rule reads them); the ``mol`` space holds the U DISTINCT drugs, which vary from batch to batch like any other count."""
+
+    def __init__(self, cap, slack, heads: int = 4, lower=None, max_per_mol=None, pair_cap: int = 0, second_cap: int = 0):
+        super().__init__(cap, slack, heads, lower, max_per_mol)
+        self.pair_cap, self.second_cap = int(pair_cap), int(second_cap)
+
+    @classmethod
+    def from_batches(cls, batches, margin: float = 0.03, heads: int = 4, spread_sigmas: float = 4.0) -> "FactoredPairShapes":
+        """Capacities from sample factored batches.  The encoder's spaces as ``StaticShapes.from_counts`` sizes them, except that the real
+        room of ``mol`` grows by the margin too (there the batch size is exact; here U is not): the slack it computed -- what
+        ``fits``' padding rule needs -- stays and only grows with the rounding.  ``pair`` and ``second``: the largest count, plus the
+        margin, rounded up to 8."""
+        batches = list(batches)
+        counts = [factored_batch_counts(b) for b in batches]
+        base = StaticShapes.from_counts([{sp: c[sp] for sp in COUNT_FIELD} for c in counts], margin, heads, spread_sigmas)
+        cap, slack = dict(base.cap), dict(base.slack)
+        real = int(math.ceil(max(c["mol"] for c in counts) * (1.0 + margin)))
+        cap["mol"] = _up(real + slack["mol"], 8)
+        slack["mol"] = cap["mol"] - real
+        room = {sp: _up(int(math.ceil(max(c[sp] for c in counts) * (1.0 + margin))), 8) for sp in PAIR_SPACES}
+        shapes = cls(cap, slack, heads, base.lower, pair_cap=room["pair"], second_cap=room["second"])
+        bounds = [getattr(b, "max_per_mol", None) for b in batches]
+        if bounds and all(m is not None for m in bounds):
+            shapes.max_per_mol = {sp: (1 if sp == "mol" else _up(int(1.5 * max(m[sp] for m in bounds)) + 8, 8)) for sp in SPACES}
+        return shapes
+
+    def capacity(self, space: str) -> int:
+        return {"pair": self.pair_cap, "second": self.second_cap}[space] if space in PAIR_SPACES else self.cap[space]
+
+    def fits(self, counts: Dict[str, int], max_per_mol: Optional[Dict[str, int]] = None) -> bool:
+        """``counts`` of ``factored_batch_counts`` (the encoder's seven alone are accepted too: ``pad_batch`` asks with those)."""
+        if counts.get("pair", 0) > self.pair_cap or counts.get("second", 0) > self.second_cap:
+            return False
+        return super().fits({sp: n for sp, n in counts.items() if sp not in PAIR_SPACES}, max_per_mol)
+
+    def __repr__(self):
+        return f"FactoredPairShapes(cap={self.cap}, slack={self.slack}, pair_cap={self.pair_cap}, second_cap={self.second_cap})"
+
+
+def pad_factored_pair_batch(batch: Dict[str, torch.Tensor], shapes: FactoredPairShapes) -> Dict[str, torch.Tensor]:
+    """``pad_batch`` of a factored pair batch, the torch counterpart of what FactoredPairGraphedTrainStep stages: the encoder's fields
+    and masks padded over the U distinct drugs, ``y`` and the two pair lists with zeros up to ``pair_cap``, the second input's int64 rows
+    with zero rows up to ``second_cap``, and ``plan.N_MOLS_KEY`` = the ``mol`` capacity.  The pair orderings are left out: the step builds
+    them on the GPU from the staged lists."""
+    from .data import PAIR_ORDER_KEYS
+    from .plan import N_MOLS_KEY
+    counts = factored_batch_counts(batch)
+    if not shapes.fits(counts):
+        raise ValueError(f"batch {counts} does not fit {shapes}")
+    mols = {k: v for k, v in batch.items() if k not in FACTORED_PAIR_FIELDS and k not in PAIR_ORDER_KEYS and k != N_MOLS_KEY}
+    mols["y"] = batch["y"].new_zeros(counts["mol"])          # pad_batch counts molecules by it; replaced below
+    out = pad_batch(batch.like(mols) if isinstance(batch, CollatedBatch) else mols, shapes)
+    for name, (space, _, _) in FACTORED_PAIR_FIELDS.items():
+        if name in batch:
+            src = batch[name]
+            dst = src.new_zeros((shapes.capacity(space),) + tuple(src.shape[1:]))
+            dst[: src.shape[0]] = src
+            out[name] = dst
+    out[N_MOLS_KEY] = shapes.cap["mol"]
+    return out
+
+
 ADAM_RIDER = os.environ.get("FRAGNET_ADAM_RIDER", "1") != "0"      # the head's Adam slice rides in the encoder backward's last launch (A/B: 0)
 
 
@@ -251,8 +341,11 @@ def masked_pretrain_loss(outputs, sb: Dict[str, torch.Tensor]) -> torch.Tensor:
 class StaticBatch:
     """Fixed-capacity device buffers for one batch + the single-launch staging call."""
 
-    def __init__(self, shapes: StaticShapes, example: Dict[str, torch.Tensor], extra_fields: Optional[dict] = None):
-        """``extra_fields``: a table in FIELDS' form of fields staged behind FIELDS' own (PAIR_FIELDS for a pair model)."""
+    def __init__(self, shapes: StaticShapes, example: Dict[str, torch.Tensor], extra_fields: Optional[dict] = None, counts_of=None):
+        """``extra_fields``: a table in FIELDS' form of fields staged behind FIELDS' own (PAIR_FIELDS for a pair model); an entry under one
+        of FIELDS' names takes that field's place.  ``counts_of``: batch -> the real count of every index space a staged field lives in
+        (``batch_counts`` when None)."""
+        self._counts_of = counts_of or batch_counts
         dev = example["x_atoms"].device
         if dev.type != "cuda":
             raise _lib.FragnetHipError("StaticBatch stages batches on the GPU (fn_stage_padded); there is no CPU path")
@@ -273,11 +366,16 @@ class StaticBatch:
         self._fields = (_lib.StageField * _lib.FN_MAX_STAGE_FIELDS)()
         self.n_fields = 0
         self._refresh = []
-        for name, (space, layout, target) in list(FIELDS.items()) + list((extra_fields or {}).items()):
+        for name, (space, layout, target) in {**FIELDS, **self._extra}.items():
             if name not in example:
                 continue
-            src, cap = example[name], shapes.cap[space]
-            if layout == "rows_i64":
+            src, cap = example[name], shapes.capacity(space)
+            if layout == "vec_i64":          # an int64 vector whose padding nobody reads: zeros behind the real entries
+                if src.dtype != torch.int64 or src.dim() != 1:
+                    raise TypeError(f"{name}: expected an int64 vector, got {src.dtype} {tuple(src.shape)}")
+                self.t[name] = torch.zeros(cap, dtype=torch.int64, device=dev)
+                self._append(_lib.STAGE_ROWS_I64, self.t[name].data_ptr(), cap, 1, refresh=(space, name))
+            elif layout == "rows_i64":
                 if src.dtype != torch.int64 or src.dim() != 2:
                     raise TypeError(f"{name}: expected int64 rows [n, width], got {src.dtype} {tuple(src.shape)}")
                 self.t[name] = torch.zeros((cap, src.shape[1]), dtype=torch.int64, device=dev)
@@ -312,7 +410,7 @@ class StaticBatch:
     def _append(self, kind, dst, cap, width=1, pad_hi=0, pad_mod=1, src=None, n_real=0, refresh=None) -> int:
         """Fill the next entry of the staging table; its index.  ``refresh`` = (space, src source): load() rewrites n_real and src."""
         if self.n_fields >= _lib.FN_MAX_STAGE_FIELDS:
-            raise ValueError("too many batch fields for one staging launch")
+            raise ValueError(f"too many batch fields for one staging launch (its table holds FN_MAX_STAGE_FIELDS = {_lib.FN_MAX_STAGE_FIELDS})")
         i, f = self.n_fields, self._fields[self.n_fields]
         f.src, f.dst, f.n_real, f.cap, f.width, f.kind, f.pad_hi, f.pad_mod = src, dst, n_real, cap, width, kind, pad_hi, pad_mod
         if refresh is not None:
@@ -342,7 +440,7 @@ class StaticBatch:
 
     def load(self, batch: Dict[str, torch.Tensor]) -> bool:
         """Stage ``batch`` (GPU tensors); False when it does not fit the capacities (nothing is written then)."""
-        counts = batch_counts(batch)
+        counts = self._counts_of(batch)
         if not self.shapes.fits(counts, getattr(batch, "max_per_mol", None)):
             return False
         if self.collated and not isinstance(batch, CollatedBatch):
@@ -447,6 +545,7 @@ class GraphedTrainStep:
 
     LOSS_KINDS = ("regr", "clsf", "pretrain")
     EXTRA_FIELDS: Optional[dict] = None      # StaticBatch's ``extra_fields``
+    COUNTS_OF = staticmethod(batch_counts)   # StaticBatch's ``counts_of``
 
     def __init__(self, model, opt, shapes: StaticShapes, example: Dict[str, torch.Tensor], loss: str = "regr",
                  group=None, warmup: int = 3, overlap: Optional[bool] = None, capture_adam: bool = True,
@@ -466,8 +565,9 @@ class GraphedTrainStep:
         if loss not in self.LOSS_KINDS:
             raise ValueError(f"unknown loss kind {loss!r}")
         self._masked = {"regr": masked_regr_loss, "clsf": masked_bce_loss}.get(loss)
-        self.static = StaticBatch(shapes, example, self.EXTRA_FIELDS)
+        self.static = StaticBatch(shapes, example, self.EXTRA_FIELDS, self.COUNTS_OF)
         self.device = self.static.device
+        self._extend_static()
         if loss == "pretrain" and "dh_angl" not in example:
             raise ValueError("pretrain step needs the collate_fn_pt batch (bnd_lngth, bnd_angl, dh_angl)")
         if loss == "pretrain" and hasattr(getattr(model, "head", None), "need_bond_length"):
@@ -506,6 +606,9 @@ class GraphedTrainStep:
         self._capture(example, warmup)
 
     # -- pieces
+    def _extend_static(self):
+        """What a subclass stages beyond the field tables (``StaticBatch.add_count``, buffers of its own in ``static.t``); before the capture."""
+
     def _encoder(self):
         """The FragNet encoder whose dropout stream the step owns."""
         return self.model.pretrain
@@ -604,7 +707,7 @@ class GraphedTrainStep:
         if not self.model.training:
             raise RuntimeError("GraphedTrainStep captures a TRAINING step: call model.train() first")
         if not self._stage(example):
-            raise ValueError(f"the example batch {batch_counts(example)} does not fit {self.shapes}")
+            raise ValueError(f"the example batch {self.COUNTS_OF(example)} does not fit {self.shapes}")
 
         def warm_step():
             self.opt.zero_grad()
@@ -776,13 +879,14 @@ class PairGraphedTrainStep(GraphedTrainStep):
 
     def __init__(self, model, opt, shapes: StaticShapes, example: Dict[str, torch.Tensor], group=None, warmup: int = 3,
                  overlap: Optional[bool] = None, capture_adam: bool = True):
+        who = type(self).__name__
         if overlap:
-            raise ValueError("PairGraphedTrainStep captures one graph: overlap=True (the two-graph step) is not built for pair models")
+            raise ValueError(f"{who} captures one graph: overlap=True (the two-graph step) is not built for pair models")
         import torch.distributed as dist
         if dist.is_available() and dist.is_initialized() and dist.get_world_size(group) > 1:
-            raise ValueError("PairGraphedTrainStep is single-GPU: the process group has more than one rank")
+            raise ValueError(f"{who} is single-GPU: the process group has more than one rank")
         if not hasattr(getattr(model, "drug_model", None), "pretrain"):
-            raise TypeError("PairGraphedTrainStep takes a pair model (cdrp.CDRPModel / dta.DTAModel2): model.drug_model.pretrain is its encoder")
+            raise TypeError(f"{who} takes a pair model (cdrp.CDRPModel / dta.DTAModel2): model.drug_model.pretrain is its encoder")
         if not any(k in example for k in PAIR_FIELDS):
             raise ValueError(f"the example is no pair batch: none of {tuple(PAIR_FIELDS)} in it")
         self.target_norm = None                      # None: y as the batch has it; (mean, sdev): (y - mean) / (sdev + 1e-5)
@@ -825,6 +929,82 @@ class PairGraphedTrainStep(GraphedTrainStep):
         y = self._target(batch)
         out, loss = self.model(batch, loss=(_lib.LOSS_MSE, y, None))
         return loss if loss is not None else torch.nn.functional.mse_loss(out.view(-1), y)
+
+
+class FactoredPairGraphedTrainStep(PairGraphedTrainStep):
+    """``PairGraphedTrainStep`` on FACTORED batches (``data.collate_fn_cdrp_factored`` / ``collate_fn_dta_factored``): the encoder on the
+    U distinct drugs, the second tower on the C distinct rows, the pair orderings (``ops.pair_orderings_both``: one launch, no host
+    read), the factored pair head with its fused MSE, backward, gradient gather and the update as ONE hipGraph.  ``shapes``: a
+    ``FactoredPairShapes``.  What differs from the sibling:
+
+    * staged fields: FIELDS' encoder fields in their own spaces (``mol`` = the distinct drugs), and FACTORED_PAIR_FIELDS: ``y`` and the two
+      pair lists in the ``pair`` space, ``gene_expr`` / ``protein`` in the ``second`` space, zeros behind the real entries; two device
+      counts, the real molecules (plan.REAL_MOLS_KEY) and the real pairs (REAL_PAIRS_KEY).  One staging launch; a table beyond
+      FN_MAX_STAGE_FIELDS raises;
+    * the staged batch carries ``plan.N_MOLS_KEY`` = the ``mol`` capacity and four persistent ordering buffers (``data.PAIR_ORDER_KEYS``)
+      that the orderings launch fills under the real-pair count: a padding pair is in no segment, so the head's backward needs no count
+      (csrc/pair_factored.hip) and padding rows of both towers receive exact zeros;
+    * the step is ``model(staged, loss=(LOSS_MSE, y, None, real-pair word))``; the forward's 4-byte memset of its arrival counter is
+      captured as a memset node;
+    * a one-record-per-pair batch is accepted: it is staged (and, beyond the capacities, run eagerly) through ``data.as_factored``;
+    * a grid batch and a batch beyond any capacity -- ``mol``, ``pair``, ``second`` or an encoder space -- take the eager factored step
+      on the same optimiser and Philox state (``fallbacks``); a grid batch has no target: its eager step raises."""
+
+    EXTRA_FIELDS = FACTORED_PAIR_FIELDS
+    COUNTS_OF = staticmethod(factored_batch_counts)
+
+    def __init__(self, model, opt, shapes: FactoredPairShapes, example: Dict[str, torch.Tensor], group=None, warmup: int = 3,
+                 overlap: Optional[bool] = None, capture_adam: bool = True):
+        from . import ops
+        from .data import PAIR_GRID_KEY
+        if not isinstance(shapes, FactoredPairShapes):
+            raise TypeError("FactoredPairGraphedTrainStep takes FactoredPairShapes (capacities of the pair and second spaces too)")
+        if example.get(PAIR_GRID_KEY):
+            raise ValueError("a grid batch has no target and no training step")
+        over = {k: v for k, v in (("mol", shapes.cap["mol"]), ("pair", shapes.pair_cap), ("second", shapes.second_cap)) if v > ops.DENSE_MAX_ROWS}
+        if over:
+            raise ValueError(f"FactoredPairGraphedTrainStep: capacities {over} are beyond the factored pair head's {ops.DENSE_MAX_ROWS} rows")
+        super().__init__(model, opt, shapes, self._factored(example), group=group, warmup=warmup, overlap=overlap, capture_adam=capture_adam)
+
+    @staticmethod
+    def _factored(batch):
+        from .data import PAIR_DRUG_KEY, as_factored
+        return batch if PAIR_DRUG_KEY in batch else as_factored(batch)
+
+    def _extend_static(self):
+        from .data import PAIR_ORDER_KEYS
+        from .plan import N_MOLS_KEY
+        st, sh = self.static, self.shapes
+        st.add_count("pair", REAL_PAIRS_KEY)
+        sizes = (sh.cap["mol"] + 1, sh.pair_cap, sh.second_cap + 1, sh.pair_cap)
+        for key, n in zip(PAIR_ORDER_KEYS, sizes):
+            st.t[key] = torch.zeros(n, dtype=torch.int32, device=st.device)
+        st.t[N_MOLS_KEY] = sh.cap["mol"]
+
+    def _stage(self, batch) -> bool:
+        from .data import PAIR_GRID_KEY
+        if batch.get(PAIR_GRID_KEY):
+            return False
+        batch = self._factored(batch)
+        if self.target_norm is not None:
+            staged = batch.like(dict(batch)) if isinstance(batch, CollatedBatch) else dict(batch)
+            staged["y"] = self._y_keep = self._target(batch)     # alive until the next call: the staging launch reads it
+            batch = staged
+        return self.static.load(batch)
+
+    def _static_loss(self, predict):
+        from . import ops
+        from .data import PAIR_DRUG_KEY, PAIR_ORDER_KEYS, PAIR_SECOND_KEY
+        sb = self.static.t
+        sb.pop(PLAN_KEY, None)
+        ops.pair_orderings_both(sb[PAIR_DRUG_KEY], sb[PAIR_SECOND_KEY], self.shapes.cap["mol"], self.shapes.second_cap,
+                                real_pairs=sb[REAL_PAIRS_KEY], out=tuple(sb[k] for k in PAIR_ORDER_KEYS))
+        _, loss = predict(sb, loss=(_lib.LOSS_MSE, sb["y"], None, sb[REAL_PAIRS_KEY]))
+        return loss              # never None: ops._pair_apply refuses a count where the fused launch does not apply
+
+    def _eager_loss(self, batch):
+        from .data import PAIR_GRID_KEY
+        return super()._eager_loss(batch if batch.get(PAIR_GRID_KEY) else self._factored(batch))
 
 
 class GraphedForward:

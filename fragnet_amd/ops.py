@@ -1575,18 +1575,18 @@ def pair_fuses_loss(loss, rows: int, tensors) -> bool:
 def _pair_apply(node, args, rows: int, fc1, fc2, loss):
     """``node`` on ``args`` = (instance, drug, second input, ..), the target and the parameters: the result in ``pair_head``'s three shapes.
     A fourth element of ``loss`` is the device-side count of the REAL rows (int32 [1], ``plan.REAL_MOLS_KEY`` of a batch staged to static
-    shapes): the loss is the mean over the first ``n`` rows and the rows behind them receive no gradient.  It exists in the fused launch
-    of ``_PairHead`` only -- a caller that computes the loss from ``out`` itself would take the padding rows for real ones -- so where that
-    launch does not apply the count is an error."""
+    shapes; for ``_PairHeadFactored`` the count of its real PAIRS): the loss is the mean over the first ``n`` rows and the rows behind them
+    receive no gradient.  It exists in the fused launches only -- a caller that computes the loss from ``out`` itself would take the
+    padding rows for real ones -- so where the fused launch does not apply the count is an error."""
     params = (fc1.weight, fc1.bias, fc2.weight, fc2.bias)
     if loss is None:
         return node.apply(*args, None, *params)
     real_rows = loss[3] if len(loss) > 3 else None
     fused = pair_fuses_loss(loss, rows, (args[1], args[2], *params))
     if real_rows is not None:
-        if node is not _PairHead or not fused:
-            raise _lib.FragnetHipError(f"{args[0].name}: a real-row count needs the fused MSE launch of the one-row-per-pair head (a training "
-                                       "step, no row weights, no factored batch)")
+        if not fused:
+            raise _lib.FragnetHipError(f"{args[0].name}: a real-row count needs the fused MSE launch of the pair head (a training step, no "
+                                       "row weights)")
         if not (real_rows.is_cuda and real_rows.dtype == torch.int32 and real_rows.numel() == 1):
             raise TypeError(f"{args[0].name}: the real-row count is one int32 word on the GPU, got {tuple(real_rows.shape)} {real_rows.dtype} on {real_rows.device}")
         return node.apply(*args, (loss[1], real_rows), *params)
@@ -1721,6 +1721,31 @@ def pair_orderings(pair_list: torch.Tensor, n_rows: int):
     return rowptr, perm
 
 
+def pair_orderings_both(pair_drug: torch.Tensor, pair_second: torch.Tensor, n_drug: int, n_second: int, real_pairs=None, out=None):
+    """``pair_orderings`` of both pair lists as ONE launch of fn_pair_orderings_i32 (csrc/pair_factored.hip): ``(rowptr_drug [n_drug + 1],
+    perm_drug [M], rowptr_second [n_second + 1], perm_second [M])``, int32, the ``orderings`` of ``pair_head_factored``.  No host read, no
+    sort or scan of the library: it can sit inside a captured step.  ``real_pairs`` (int32 [1] on the GPU, or None): only the first
+    ``n = clamp(*real_pairs, 0, M)`` pairs exist -- what lies behind them is not read, is in no row, and ``perm`` holds -1 from
+    ``rowptr[-1]`` on (``pair_orderings`` has no -1: there every pair is listed, the out-of-range ones last).  ``out``: four int32 tensors
+    to write into.  More than ``DENSE_MAX_ROWS`` pairs or rows on a side is an error."""
+    if not (pair_drug.is_cuda and pair_second.is_cuda):
+        raise _lib.FragnetHipError("pair_orderings_both: fragnet_amd kernels need GPU tensors; there is no CPU fallback")
+    if pair_drug.dtype != torch.int64 or pair_second.dtype != torch.int64 or pair_drug.dim() != 1 or pair_drug.shape != pair_second.shape:
+        raise TypeError("pair_orderings_both: the pair lists are two int64 vectors of one length")
+    if real_pairs is not None and not (real_pairs.is_cuda and real_pairs.dtype == torch.int32 and real_pairs.numel() == 1):
+        raise TypeError(f"pair_orderings_both: the real-pair count is one int32 word on the GPU, got {tuple(real_pairs.shape)} {real_pairs.dtype} on {real_pairs.device}")
+    pd, ps, M, dev = pair_drug.contiguous(), pair_second.contiguous(), pair_drug.numel(), pair_drug.device
+    sizes = (n_drug + 1, M, n_second + 1, M)
+    if out is None:
+        out = tuple(torch.empty(n, dtype=torch.int32, device=dev) for n in sizes)
+    elif any(not t.is_contiguous() for t in out):
+        raise ValueError("pair_orderings_both: the output tensors must be contiguous")
+    out = tuple(_i32c(t, "pair_orderings_both: output", n) for t, n in zip(out, sizes))
+    _lib.call("fn_pair_orderings_i32", pd.data_ptr(), ps.data_ptr(), _ptr(real_pairs), *(t.data_ptr() for t in out), M, n_drug, n_second,
+              _stream_ptr(dev))
+    return out
+
+
 def _i32c(t: torch.Tensor, name: str, numel: int) -> torch.Tensor:
     if not t.is_cuda or t.dtype != torch.int32 or t.numel() != numel:
         raise ValueError(f"{name}: expected {numel} int32 entries on the GPU (ops.pair_orderings), got {tuple(t.shape)} {t.dtype} on {t.device}")
@@ -1731,7 +1756,8 @@ class _PairHeadFactored(torch.autograd.Function):
     """``_PairHead`` on U distinct drug rows, C distinct second rows and the pair lists: <prefix>_factored_fwd_f32 saves A = D W1d^T
     [U,128] and B = S W1s^T [C,128] in place of ``h`` [M,128] and writes out [M,1]; <prefix>_factored_bwd_f32 folds the per-pair gradient
     over the pair orderings, so both input gradients come back per DISTINCT row.  The fused-loss contract, the ``_fn_relu_gated`` tag and
-    the gate are ``_PairHead``'s."""
+    the gate are ``_PairHead``'s; ``target = (y, real_pairs)`` takes <prefix>_factored_fwd_rows_f32 (a static-shape step: the mean over the
+    first ``*real_pairs`` pairs; the orderings must then be those of the same count, ``pair_orderings_both``)."""
 
     @staticmethod
     def forward(ctx, inst, drug, x1, pd, ps, orderings, target, W1, b1, w2, b2):
@@ -1743,10 +1769,14 @@ class _PairHeadFactored(torch.autograd.Function):
         B = torch.empty((C_, H), dtype=torch.float32, device=dev)
         ws = torch.empty(getattr(_lib.load(), inst.prefix + "_factored_ws")(U, C_), dtype=torch.float32, device=dev)
         out = torch.empty((M, C_out), dtype=torch.float32, device=dev)
+        target, real_pairs = target if isinstance(target, tuple) else (target, None)
         target, g, parts, loss_t = _pair_loss_buffers(target, M, C_out, lambda: 1, dev, inst.name + "_factored", "pairs")
-        _lib.call(inst.prefix + "_factored_fwd_f32", drug.data_ptr(), x1.data_ptr(), pd.data_ptr(), ps.data_ptr(), W1.data_ptr(), b1.data_ptr(),
-                  w2.data_ptr(), b2.data_ptr(), _ptr(target), A.data_ptr(), B.data_ptr(), ws.data_ptr(), out.data_ptr(), _ptr(g), _ptr(parts),
-                  M, U, C_, Kd, K1, H, C_out, _stream_ptr(dev))
+        args = (drug.data_ptr(), x1.data_ptr(), pd.data_ptr(), ps.data_ptr(), W1.data_ptr(), b1.data_ptr(), w2.data_ptr(), b2.data_ptr(),
+                _ptr(target), A.data_ptr(), B.data_ptr(), ws.data_ptr(), out.data_ptr(), _ptr(g), _ptr(parts), M, U, C_, Kd, K1, H, C_out)
+        if real_pairs is None:
+            _lib.call(inst.prefix + "_factored_fwd_f32", *args, _stream_ptr(dev))
+        else:
+            _lib.call(inst.prefix + "_factored_fwd_rows_f32", *args, real_pairs.data_ptr(), _stream_ptr(dev))
         ctx.M = M
         return _pair_forward_end(ctx, inst, (W1, b1, w2, b2), (drug, x1, A, B, *orderings), out, g, parts, loss_t)
 
@@ -1775,6 +1805,9 @@ def _pair_head_factored(inst, drug_enc, x1, pair_drug, pair_second, fc1, fc2, lo
             raise IndexError(f"{name}: pair lists reach outside the {U} drug rows / {C_} {inst.second} rows")
     ok = _pair_widths_ok(inst, drug_enc, x1, fc1, fc2) and max(U, C_, M) <= DENSE_MAX_ROWS and (M == 0 or (U > 0 and C_ > 0))
     if not ok:
+        if loss is not None and len(loss) > 3 and loss[3] is not None:
+            raise _lib.FragnetHipError(f"{name}: a real-row count needs the built widths (256 + {inst.width} -> 128 -> 1) and at most "
+                                       f"{DENSE_MAX_ROWS} rows and pairs")
         out = fc2(fc1(torch.cat((drug_enc[pd], x1[ps]), 1)))
         return (out, None) if loss is not None else out
     if orderings is None:

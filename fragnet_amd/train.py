@@ -438,6 +438,28 @@ def make_pair_graph_step(model, optimizer, train_loader, heads: int):
     return graphstep.PairGraphedTrainStep(model, optimizer, shapes, sample[0])
 
 
+def check_factored_pair_graph_step(ft) -> bool:
+    """``finetune.factored_graph_step`` of the pair drivers: absent means off.  It selects the factored collate AND the captured step
+    built for it (graphstep.FactoredPairGraphedTrainStep), so together with ``finetune.graph_step`` -- the captured step on
+    one-record-per-pair batches -- it is a configuration error."""
+    if not ft.get("factored_graph_step"):
+        return False
+    if ft.get("graph_step"):
+        raise SystemExit("finetune.factored_graph_step and finetune.graph_step exclude each other: each captures the training step, the "
+                         "first on factored batches, the second on one-record-per-pair batches")
+    return True
+
+
+def make_factored_pair_graph_step(model, optimizer, train_loader, heads: int):
+    """The drivers' ``graphstep.FactoredPairGraphedTrainStep``: capacities from eight training batches (margin 5 %; the numbers of distinct
+    drugs and second inputs vary from batch to batch, so those two grow by it as well), captured on the first."""
+    from . import graphstep
+    sample = [b for _, b in zip(range(8), iter(train_loader))]
+    shapes = graphstep.FactoredPairShapes.from_batches(sample, margin=0.05, heads=heads)
+    model.train()
+    return graphstep.FactoredPairGraphedTrainStep(model, optimizer, shapes, sample[0])
+
+
 def save_predictions(trainer, loader, model, exp_dir, save_name="test_res", loss_type="mse", seed=123):
     score, true, pred = trainer.test(model=model, loader=loader)
     acc = score ** 0.5 if loss_type == "mse" else score

@@ -1128,6 +1128,33 @@ int fn_dta_pair_factored_bwd_f32(const float* g, const float* drug, const float*
 int fn_dta_pair_factored_grid_f32(const float* drug, const float* xt, const float* W1, const float* b1, const float* w2, const float* b2,
                                   float* out, int64_t U, int64_t Cn, int64_t Kd, int64_t Kx, int64_t H, int64_t C, fn_stream_t stream);
 
+/* fn_cdrp_pair_factored_fwd_rows_f32 / fn_dta_pair_factored_fwd_rows_f32 (added under ABI 12, nothing existing changes):
+ * fn_*_pair_factored_fwd_f32 with a device-side count of the REAL pairs, for a step over static capacities (FN_STAGE_COUNT writes the
+ * word).  n = *real_pairs clamped to [0, M]: pairs m < n get out, g[m] = 2 (out - target) / n and the loss partial is divided by n;
+ * pairs m >= n get out = 0, g = 0 exactly and no share of the loss, and pair_drug / pair_second are not read there; n = 0: loss 0,
+ * every g 0, nothing is divided.  real_pairs NULL: the plain entry point.  A count without a target, or a misaligned one: FN_EINVAL.
+ * fn_*_pair_factored_bwd_f32 takes no count: with fn_pair_orderings_i32's orderings of the first n pairs a padding pair is in no
+ * segment, a row no real pair refers to has a zero sum -- its g_drug / g_second row is exactly zero -- and adds 0 * x to dW1 and dW2
+ * in the place of the sum it would have had, so every result equals, bit for bit, that of the plain calls on the real rows alone. */
+int fn_cdrp_pair_factored_fwd_rows_f32(const float* drug, const float* cell, const int64_t* pair_drug, const int64_t* pair_cell, const float* W1,
+                                       const float* b1, const float* w2, const float* b2, const float* target, float* A, float* B, float* ws,
+                                       float* out, float* g, float* loss_part, int64_t M, int64_t U, int64_t Cn, int64_t Kd, int64_t Kc,
+                                       int64_t H, int64_t C, const int32_t* real_pairs /*nullable, device*/, fn_stream_t stream);
+int fn_dta_pair_factored_fwd_rows_f32(const float* drug, const float* xt, const int64_t* pair_drug, const int64_t* pair_prot, const float* W1,
+                                      const float* b1, const float* w2, const float* b2, const float* target, float* A, float* B, float* ws,
+                                      float* out, float* g, float* loss_part, int64_t M, int64_t U, int64_t Cn, int64_t Kd, int64_t Kx,
+                                      int64_t H, int64_t C, const int32_t* real_pairs /*nullable, device*/, fn_stream_t stream);
+
+/* fn_pair_orderings_i32 (added under ABI 12): the pair orderings of both sides of a factored batch, one launch, no host read, no
+ * allocation, no atomic (a bitonic sort of distinct 24-bit keys in LDS): two runs give identical bits.  n = real_pairs ?
+ * clamp(*real_pairs, 0, M) : M; only the first n pairs exist and what lies behind them in the lists is not read.  Per side (N = U for
+ * pair_drug, Cn for pair_second): perm[rowptr[r] .. rowptr[r + 1]) = the pairs m < n whose value is r, ascending; a value outside
+ * [0, N) -- compared as int64 -- belongs to no row; rowptr[N] = the number of in-range pairs; perm[rowptr[N] .. M) = -1.  M = 0 or
+ * n = 0: all row pointers 0.  rowptr_*: [N + 1], perm_*: [M], int32.  M, U or Cn outside [0, FN_DENSE_MAX_ROWS]: FN_EINVAL. */
+int fn_pair_orderings_i32(const int64_t* pair_drug, const int64_t* pair_second, const int32_t* real_pairs /*nullable, device*/,
+                          int32_t* rowptr_drug, int32_t* perm_drug, int32_t* rowptr_second, int32_t* perm_second, int64_t M, int64_t U,
+                          int64_t Cn, fn_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------
  * Graph-convolution baseline, model_version gcn2 (reference model/gcn/gcn2.py:48-65); csrc/gcn.hip.  Entry points added under ABI 12
  * (nothing existing changes).  The aggregate is a degree-normalised neighbour sum over one of a level's two CSRs:

@@ -49,6 +49,8 @@ if __name__ == "__main__":
     if ft.target_type != "regr":
         raise SystemExit("CDRP: target_type regr only")
     want_graph_step = train.check_pair_graph_step(ft)      # finetune.graph_step: true -- the training step as one hipGraph (graphstep.PairGraphedTrainStep)
+    # finetune.factored_graph_step: true -- factored batches AND their training step as one hipGraph (graphstep.FactoredPairGraphedTrainStep)
+    want_factored_step = train.check_factored_pair_graph_step(ft)
     model = CDRPModel(FragNetFineTuneBase(**train.finetune_model_kwargs(args)), int(args.gene_dim), device)
     pt = args.pretrain
     if pt.get("chkpoint_name") and os.path.exists(str(pt.chkpoint_name)):
@@ -60,13 +62,15 @@ if __name__ == "__main__":
     sets = {k: load_pickle_dataset(ft[k].path) for k in ("train", "val", "test")}
     # finetune.factored_pairs: true -- every distinct drug and second input of a batch goes through its encoder once
     # (data.collate_fn_cdrp_factored); with drop_ratio > 0 a training step then draws one dropout mask per distinct drug, not per pair
-    collate = data.collate_fn_cdrp_factored if ft.get("factored_pairs") else data.collate_fn_cdrp
+    collate = data.collate_fn_cdrp_factored if ft.get("factored_pairs") or want_factored_step else data.collate_fn_cdrp
     train_loader = _OnDevice(DataLoader(sets["train"], collate_fn=collate, batch_size=ft.batch_size, shuffle=True, drop_last=True), device)
     val_loader = _OnDevice(DataLoader(sets["val"], collate_fn=collate, batch_size=64, shuffle=False), device)
     test_loader = _OnDevice(DataLoader(sets["test"], collate_fn=collate, batch_size=64, shuffle=False), device)
     trainer = train.TrainerFineTuneCDRP(target_type=ft.target_type)
     optimizer = train.make_optimizer(model, float(ft.lr), next(iter(train_loader)), lambda mdl, b: trainer._loss(mdl, b))
     graph_step = train.make_pair_graph_step(model, optimizer, train_loader, int(ft.model.num_heads)) if want_graph_step else None
+    if want_factored_step:
+        graph_step = train.make_factored_pair_graph_step(model, optimizer, train_loader, int(ft.model.num_heads))
     step_kw = {} if graph_step is None else {"graph_step": graph_step}      # absent by default: the launch-by-launch step, as ever
     stopper = train.EarlyStopping(patience=ft.es_patience, verbose=True, chkpoint_name=ft.chkpoint_name)
     log = open(os.path.join(exp_dir, "log.jsonl"), "a")
