@@ -747,8 +747,8 @@ def sample_rows(cap: int, keep_frac: float, rng: "PhiloxStream", device, n: Opti
 # ======================================================================================
 # prediction head: Linear -> act(dropout(.)) stack with a hand-written backward
 # ======================================================================================
-SMALL_LINEAR_MAX = 16        # FN_SMALL_LINEAR_MAX
-DENSE_MAX_ROWS = 4096        # FN_DENSE_MAX_ROWS
+SMALL_LINEAR_MAX = _lib.FN_SMALL_LINEAR_MAX
+DENSE_MAX_ROWS = _lib.FN_DENSE_MAX_ROWS
 DENSE_HEAD = True            # hidden layers through fn_dense_fwd/bwd_f32 (False: library GEMMs + the element-wise kernels)
 FUSED_HEAD_LOSS = os.environ.get("FRAGNET_FUSED_HEAD_LOSS", "1") != "0"       # False: last Linear, loss and the Linear's backward as three launches (A/B and tests)
 

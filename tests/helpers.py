@@ -2,7 +2,6 @@
 import contextlib
 import json
 import os
-import re
 
 import numpy as np
 import torch
@@ -56,10 +55,10 @@ def tuning(settings=None, **named):
 
 def tuning_key(name):
     """The number behind ``#define FN_TUNE_<name>`` in the header."""
-    text = open(os.path.join(os.path.dirname(GOLDEN), os.pardir, "include", "fragnet_hip.h")).read()
-    found = re.search(r"#define FN_TUNE_%s\s+(\d+)" % re.escape(name.upper()), text)
-    assert found, f"no tuning key FN_TUNE_{name.upper()}"
-    return int(found.group(1))
+    from fragnet_amd import _lib
+    key = getattr(_lib, "TUNE_" + name.upper(), None)
+    assert key is not None, f"no tuning key FN_TUNE_{name.upper()}"
+    return key
 
 
 def sample_like_golden(g):
