@@ -1996,3 +1996,99 @@ def frag_mlp(x, lin1, lin2):
     if lin1.bias is None or lin2.bias is None or not (_dense_ok(rows, lin1.weight) and _dense_ok(rows, lin2.weight)):
         return torch.nn.functional.linear(torch.relu(torch.nn.functional.linear(x, lin1.weight, lin1.bias)), lin2.weight, lin2.bias)
     return _FragMLP.apply(x, lin1.weight, lin1.bias, lin2.weight, lin2.bias)
+
+
+# ======================================================================================
+# nearest neighbours in embedding space: reciprocal row norms and the fused similarity + top-k update (csrc/topk.hip)
+# ======================================================================================
+TOPK_METRICS = {"dot": 0, "cosine": 1, "l2": 2}
+TOPK_MAX_K = 32
+TOPK_WIDTHS = (128, 256)
+
+
+def rows_rnorm(x: torch.Tensor) -> torch.Tensor:
+    """``1 / max(|x_i|_2, 1e-12)`` of the rows of ``x`` [n, d]: one summation order per row, whatever n."""
+    x = _f32c(x, "rows_rnorm: x")
+    if x.dim() != 2:
+        raise ValueError(f"rows_rnorm: x must be [n, d], got {tuple(x.shape)}")
+    out = torch.empty(x.shape[0], dtype=torch.float32, device=x.device)
+    _lib.call("fn_rows_rnorm_f32", x.data_ptr(), x.shape[0], x.shape[1], out.data_ptr(), _stream_ptr(x.device))
+    return out
+
+
+def topk_metric(metric) -> int:
+    """0 / 1 / 2 of ``"dot"`` / ``"cosine"`` / ``"l2"`` (squared L2: smaller is better); anything else is refused."""
+    if isinstance(metric, str) and metric in TOPK_METRICS:
+        return TOPK_METRICS[metric]
+    if isinstance(metric, int) and not isinstance(metric, bool) and metric in TOPK_METRICS.values():
+        return metric
+    raise ValueError(f"unknown metric {metric!r}: one of {', '.join(TOPK_METRICS)} (or 0, 1, 2)")
+
+
+def topk_k(k) -> int:
+    if not isinstance(k, int) or isinstance(k, bool) or not 1 <= k <= TOPK_MAX_K:
+        raise ValueError(f"k must be an integer in [1, {TOPK_MAX_K}], got {k!r}")
+    return k
+
+
+class TopK:
+    """Running best-``k`` lists of ``n_q`` queries over a library that arrives chunk by chunk (fn_topk_update_f32): the [n_q, n_lib]
+    scores never exist.  Lists are sorted best first under a total order (better score, then smaller global row id), empty slots are
+    index -1 with score -inf (+inf for ``"l2"``), and the lists are bit-identical however the library is cut into chunks.
+    ``splits``: 0 leaves the launch shape to the library; 1..63 forces that many slices per chunk (the result does not depend on it)."""
+
+    def __init__(self, n_q: int, k: int, metric, device, splits: int = 0):
+        self.k, self.metric = topk_k(k), topk_metric(metric)
+        if not isinstance(n_q, int) or n_q < 0:
+            raise ValueError(f"n_q must be a non-negative integer, got {n_q!r}")
+        if not isinstance(splits, int) or not 0 <= splits <= 63:
+            raise ValueError(f"splits must be in [0, 63], got {splits!r}")
+        device = torch.device(device)
+        if device.type != "cuda":
+            raise _lib.FragnetHipError(f"TopK: fragnet_amd kernels need a GPU device (got {device}); there is no CPU fallback")
+        self.n_q, self.device, self.splits = n_q, device, splits
+        self.score = torch.full((n_q, self.k), float("inf") if self.metric == 2 else float("-inf"), dtype=torch.float32, device=device)
+        self.index = torch.full((n_q, self.k), -1, dtype=torch.int64, device=device)
+        self._scratch = None
+
+    def _aux(self, t, rows: int, name: str):
+        if self.metric == 0:
+            return None
+        if t is None:
+            raise ValueError(f"TopK.update: {name} is required for the cosine (reciprocal norms) and l2 (squared norms) metrics")
+        t = _f32c(t, f"TopK.update: {name}")
+        if t.shape != (rows,):
+            raise ValueError(f"TopK.update: {name} must be [{rows}], got {tuple(t.shape)}")
+        return t
+
+    def update(self, q, lib, index_base: int, q_aux=None, lib_aux=None, exclude=None) -> "TopK":
+        """Folds ``lib`` [n_lib, d], whose row 0 is global row ``index_base``, into the lists of ``q`` [n_q, d]; d is 128 or 256.
+        ``q_aux`` / ``lib_aux``: ``rows_rnorm`` of the two for ``"cosine"``, the squared norms for ``"l2"``.  ``exclude`` (int64 [n_q]):
+        the global row a query skips, -1 for none."""
+        q, lib = _f32c(q, "TopK.update: q"), _f32c(lib, "TopK.update: lib")
+        if q.dim() != 2 or lib.dim() != 2 or q.shape[0] != self.n_q or q.shape[1] != lib.shape[1]:
+            raise ValueError(f"TopK.update: q must be [{self.n_q}, d] and lib [n_lib, d], got {tuple(q.shape)} and {tuple(lib.shape)}")
+        if q.shape[1] not in TOPK_WIDTHS:
+            raise _lib.FragnetHipError(f"TopK.update: rows of {q.shape[1]} floats; the kernel is built for {TOPK_WIDTHS}")
+        q_aux, lib_aux = self._aux(q_aux, self.n_q, "q_aux"), self._aux(lib_aux, lib.shape[0], "lib_aux")
+        if exclude is not None:
+            if not exclude.is_cuda:
+                raise _lib.FragnetHipError(f"TopK.update: exclude: fragnet_amd kernels need GPU tensors (got {exclude.device})")
+            if exclude.dtype != torch.int64:
+                raise TypeError(f"TopK.update: exclude: expected int64 row ids, got {exclude.dtype}")
+            exclude = exclude.contiguous()
+            if exclude.shape != (self.n_q,):
+                raise ValueError(f"TopK.update: exclude must be [{self.n_q}], got {tuple(exclude.shape)}")
+        t = _lib.Topk(q.data_ptr(), lib.data_ptr(), _ptr(q_aux), _ptr(lib_aux), _ptr(exclude), self.score.data_ptr(), self.index.data_ptr(),
+                      None, 0, self.n_q, lib.shape[0], int(index_base), q.shape[1], self.k, self.metric, self.splits)
+        need = _lib.load().fn_topk_scratch_bytes(C.byref(t))
+        _lib.check(0 if need >= 0 else need, "fn_topk_scratch_bytes")
+        if self._scratch is None or self._scratch.numel() < need:
+            self._scratch = torch.empty(max(need, 16), dtype=torch.uint8, device=self.device)
+        t.scratch, t.scratch_bytes = self._scratch.data_ptr(), self._scratch.numel()
+        _lib.call("fn_topk_update_f32", C.byref(t), _stream_ptr(self.device))
+        return self
+
+    def result(self):
+        """``(score [n_q, k], index [n_q, k])``: the lists as they stand."""
+        return self.score, self.index

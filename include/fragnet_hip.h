@@ -1174,6 +1174,40 @@ int fn_gcn_coef_f32(const fn_gat_plan* plan, float* coef /*[n]*/, fn_stream_t st
 int fn_gcn_aggregate_f32(const float* x, const fn_gat_plan* plan, int by_source, const float* coef /*nullable*/, float* out /*nullable*/,
                          const fn_act_epilogue* act /*nullable*/, fn_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Nearest neighbours in embedding space; csrc/topk.hip.  Entry points added under ABI 12 (nothing existing changes).
+ *   fn_rows_rnorm_f32   out[i] = 1 / max(|x_i|_2, 1e-12) of the rows of x [n, d]: one summation order per row (lane l of one wave adds
+ *                       columns l, l + 64, .. in order, then a fixed butterfly), whatever n and the launch shape.
+ *   fn_topk_update_f32  folds the library chunk lib [n_lib, d] into the running best lists of the queries q [n_q, d] (both fp32 row-major,
+ *                       16-byte aligned; d = 128 or 256, else FN_EUNSUPPORTED).  k in [1, 32].  metric 0: the dot product, larger is
+ *                       better; 1: cosine = dot * (q_aux[i] * lib_aux[j]) with the reciprocal norms passed in, larger is better; 2: squared
+ *                       L2 = fma(-2, dot, q_aux[i] + lib_aux[j]) with the squared norms passed in, SMALLER is better.  index_base is the
+ *                       global row id of lib[0]; exclude (nullable) [n_q] names the global id query i must skip, -1 for none.
+ *                       best_score [n_q, k] / best_index [n_q, k] are read and written: sorted best first, empty slots index -1 and
+ *                       score -inf (+inf for metric 2); a fresh state is all empty.  The order is total -- better score first, on equal
+ *                       score the smaller global index -- and the dot of a pair is one fp32 fma chain over d in a fixed order (fp32-input
+ *                       MFMA) wherever the row sits, so the lists are bit-identical however the library is cut into chunks and whatever
+ *                       the launch shape (the chunks of one search must not overlap).  No atomics, no workgroup waits on another: a scan
+ *                       launch leaves per-wave candidate lists in scratch, a merge launch folds them in.  Nothing of size n_q x n_lib
+ *                       exists.  splits: 0 = the library's own choice of slices per chunk, 1..63 = that many (a test's handle on the
+ *                       launch shape; fewer when the chunk has fewer 16-row tiles).  scratch: 16-byte aligned device bytes, at least
+ *                       fn_topk_scratch_bytes(t) (which reads n_q, n_lib, k and splits only; FN_EINVAL, negative, when they are invalid).
+ *                       n_lib = 0 or n_q = 0: nothing is launched.  A null pointer, a negative size, k outside [1, 32], a metric outside
+ *                       0..2 or too small a scratch: FN_EINVAL.  The order of NaN scores is undefined.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct fn_topk {
+    const float *q /*[n_q,d]*/, *lib /*[n_lib,d]*/, *q_aux /*[n_q], metric 1, 2*/, *lib_aux /*[n_lib], metric 1, 2*/;
+    const int64_t* exclude;      /* [n_q], nullable */
+    float* best_score;           /* [n_q,k] */
+    int64_t* best_index;         /* [n_q,k] */
+    void* scratch;
+    int64_t scratch_bytes, n_q, n_lib, index_base;
+    int32_t d, k, metric, splits;
+} fn_topk;
+int fn_rows_rnorm_f32(const float* x /*[n,d]*/, int64_t n, int64_t d, float* out /*[n]*/, fn_stream_t stream);
+int64_t fn_topk_scratch_bytes(const fn_topk* t);
+int fn_topk_update_f32(const fn_topk* t, fn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
