@@ -2092,3 +2092,47 @@ class TopK:
     def result(self):
         """``(score [n_q, k], index [n_q, k])``: the lists as they stand."""
         return self.score, self.index
+
+
+# ======================================================================================
+# evaluation metrics on the device: exact pair-concordance counts and fp64 regression sums (csrc/metrics.hip)
+# ======================================================================================
+from .metrics import CONC_FIELDS, SUMS_FIELDS          # noqa: E402  (the columns of the two tables, named where they are read)
+
+CONC_TILE = _lib.CONC_TILE          # rows of the count kernel's i- and j-tiles
+SUMS_CHUNK = _lib.SUMS_CHUNK        # rows of one partial row of the sums
+
+
+def _metrics_launch(name: str, sums: bool, pred, label, label_floor, scale, shift, splits, out_dtype, fields):
+    pred, label = _f32c(pred, f"{name}: pred"), _f32c(label, f"{name}: label")
+    if pred.dim() != 2 or pred.shape != label.shape or pred.device != label.device:
+        raise ValueError(f"{name}: pred and label must be [n, c] on one device, got {tuple(pred.shape)} and {tuple(label.shape)}")
+    n, c = pred.shape
+    if not 1 <= c <= _lib.METRICS_MAX_COLS or n > 1 << 24:
+        raise ValueError(f"{name}: c must be in [1, {_lib.METRICS_MAX_COLS}] and n <= 2^24, got n = {n}, c = {c}")
+    if not isinstance(splits, int) or isinstance(splits, bool) or splits < 0:
+        raise ValueError(f"{name}: splits must be a non-negative integer, got {splits!r}")
+    out = torch.empty((c, fields), dtype=out_dtype, device=pred.device)
+    m = _lib.Metrics(pred.data_ptr(), label.data_ptr(), out.data_ptr(), None, 0, n, float(label_floor), float(scale), float(shift), c, splits)
+    need = _lib.load().fn_metrics_scratch_bytes(C.byref(m), int(sums))
+    _lib.check(0 if need >= 0 else need, "fn_metrics_scratch_bytes")
+    scratch = torch.empty(max(need, 8), dtype=torch.uint8, device=pred.device)
+    m.scratch, m.scratch_bytes = scratch.data_ptr(), scratch.numel()
+    _lib.call(name, C.byref(m), _stream_ptr(pred.device))
+    return out
+
+
+def pair_concordance(pred: torch.Tensor, label: torch.Tensor, label_floor: float = float("-inf"), splits: int = 0) -> torch.Tensor:
+    """Exact ordered-pair counts per column of ``pred`` / ``label`` [n, c] (fn_pair_concordance_f32): int64 [c, 5] on the device, the
+    fields in ``CONC_FIELDS`` order.  Row i is valid in column k iff ``label[i, k] >= label_floor`` (never for a NaN label); -0.5 drops
+    the classification targets' missing labels.  ``splits``: 0 leaves the launch shape to the library, else that many j-slices -- the
+    counts do not depend on it.  No host read: ``metrics.roc_auc`` / ``metrics.concordance_index`` turn the copied table into numbers."""
+    return _metrics_launch("fn_pair_concordance_f32", False, pred, label, label_floor, 1.0, 0.0, splits, torch.int64, len(CONC_FIELDS))
+
+
+def regression_sums(pred: torch.Tensor, label: torch.Tensor, label_floor: float = float("-inf"), scale: float = 1.0, shift: float = 0.0,
+                    splits: int = 0) -> torch.Tensor:
+    """fp64 sums per column over the valid rows (fn_regression_sums_f32): float64 [c, 8] on the device, the fields in ``SUMS_FIELDS``
+    order, with ``p = pred * float32(scale) + float32(shift)`` rounded twice in fp32 as numpy does.  One fixed order of addition: the
+    bits are the same for every run and every ``splits``."""
+    return _metrics_launch("fn_regression_sums_f32", True, pred, label, label_floor, scale, shift, splits, torch.float64, len(SUMS_FIELDS))

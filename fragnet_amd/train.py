@@ -296,6 +296,81 @@ class TrainerFineTune:
                 aucs.append(roc_auc_score(t[ok, c], p[ok, c]))
         return -float(np.mean(aucs)) if aucs else float("nan"), t, p
 
+    # ---- the same evaluation with the metrics computed on the device (csrc/metrics.hip): no host read per batch, one at the end
+    def _eval_norm(self, label_mean, label_sdev):
+        """(shift, scale) applied to the model's output before it is compared with ``y``; only the DTA trainer de-normalises."""
+        return 0.0, 1.0
+
+    @torch.no_grad()
+    def _eval_on_device(self, model, loader, device, label_mean, label_sdev):
+        """-> (metrics dict, true, pred): the two as device tensors [rows, C] (classification) or [rows * C, 1] (regression, which
+        ``test`` scores over all elements alike), ``pred`` de-normalised.  The model is put back into the mode it came in."""
+        from . import metrics, ops
+        shift, scale = self._eval_norm(label_mean, label_sdev)
+        was_training = model.training
+        model.eval()
+        try:
+            true = pred = None
+            total, filled = len(loader.dataset), 0
+            for batch in loader:
+                batch = _on(batch, device)
+                out = model(batch)
+                rows = out.shape[0]
+                out = out.reshape(rows, -1)
+                if pred is None:
+                    pred = torch.empty((total, out.shape[1]), dtype=torch.float32, device=out.device)
+                    true = torch.empty_like(pred)
+                if filled + rows > total:
+                    raise ValueError(f"evaluate: the loader yields more than len(loader.dataset) = {total} rows")
+                pred[filled:filled + rows].copy_(out)
+                true[filled:filled + rows].copy_(batch["y"].reshape(rows, -1))
+                filled += rows
+        finally:
+            model.train(was_training)
+        if pred is None:
+            raise ValueError("evaluate: the loader is empty")
+        true, pred = true[:filled], pred[:filled]
+        if self.target_type == "clsf":
+            counts = ops.pair_concordance(pred, true, metrics.CLSF_LABEL_FLOOR).cpu()          # the one synchronisation
+            auc = metrics.concordance_per_column(counts)
+            neg_auc = -metrics.roc_auc(counts)
+            return {"score": neg_auc, "neg_auc": neg_auc, "auc": auc}, true, pred
+        true, pred = true.reshape(-1, 1), pred.reshape(-1, 1)
+        sums = ops.regression_sums(pred, true, scale=scale, shift=shift)
+        if (shift, scale) != (0.0, 1.0):
+            # what the sums launch computed per element, now in place for the pair counts and the caller: an fp32 product, then an
+            # fp32 sum -- the bits of numpy's ``p * float32(sdev) + float32(mean)`` in ``TrainerFineTuneDTA.test``
+            pred = pred.mul(scale).add_(shift)
+        counts = ops.pair_concordance(pred, true)
+        both = torch.cat([sums.view(torch.uint8).reshape(-1), counts.view(torch.uint8).reshape(-1)]).cpu().numpy()       # the one synchronisation
+        n_sums = sums.numel() * 8
+        sums_h, counts_h = both[:n_sums].view(np.float64).reshape(sums.shape), both[n_sums:].view(np.int64).reshape(counts.shape)
+        res = {k: float(v[0]) for k, v in metrics.regression_metrics(sums_h).items()}
+        res["ci"] = metrics.concordance_index(counts_h)
+        res["score"] = res["mse"]
+        return res, true, pred
+
+    def evaluate(self, model, loader, device=None, label_mean=None, label_sdev=None):
+        """``test``'s pass with the metrics computed on the device: every batch's output and ``y`` go into their slice of two
+        preallocated ``[len(loader.dataset), C]`` device buffers with no host read, one launch pair per metric table follows
+        (ops.pair_concordance, ops.regression_sums), and the tables are copied back once.  Returns a dict --
+        classification: ``neg_auc`` (``test``'s score: minus the mean ROC-AUC over the columns with both classes, NaN when none has)
+        and ``auc`` (per column, NaN where undefined); regression: ``mse``, ``rmse``, ``mae``, ``pearson``, ``r2``, ``ci`` (the
+        concordance index), in float64 from fp64 sums over all elements -- ``test``'s own mse is an fp32 numpy mean and differs from
+        it at the 1e-7 level.  ``score`` is ``test``'s first return value either way.  A NaN prediction in a valid classification
+        row raises.  The model's training / eval mode is left as it was."""
+        return self._eval_on_device(model, loader, device, label_mean, label_sdev)[0]
+
+    def test_on_device(self, model, loader, device=None, label_mean=None, label_sdev=None):
+        """``(score, true, pred)`` as ``test`` returns them -- the arrays bit for bit, copied back once at the end -- with the score
+        from ``evaluate``, whose whole dict is kept as ``self.last_metrics``."""
+        res, true, pred = self._eval_on_device(model, loader, device, label_mean, label_sdev)
+        self.last_metrics = res
+        t, p = true.cpu().numpy(), pred.cpu().numpy()
+        if self.target_type == "regr":
+            t, p = t.ravel(), p.ravel()
+        return res["score"], t, p
+
 
 class TrainerFineTuneCDRP(TrainerFineTune):
     """The reference's ``trainer_cdrp.TrainerFineTune`` for a ``cdrp.CDRPModel`` (regression, MSE on ``model(batch).view(-1)``): the
@@ -353,6 +428,9 @@ class TrainerFineTuneDTA(TrainerFineTune):
     @staticmethod
     def _stats(label_mean, label_sdev):
         return (0.0 if label_mean is None else float(label_mean), 1.0 if label_sdev is None else float(label_sdev))
+
+    def _eval_norm(self, label_mean, label_sdev):
+        return self._stats(label_mean, label_sdev)
 
     def train(self, model, loader, optimizer, scheduler=None, device=None, val_loader=None, label_mean=None, label_sdev=None, graph_step=None):
         """``graph_step``: a graphstep.PairGraphedTrainStep over the same model and optimiser.  It stages the NORMALISED target, computed
@@ -467,3 +545,13 @@ def save_predictions(trainer, loader, model, exp_dir, save_name="test_res", loss
     with open(os.path.join(exp_dir, f"{save_name}_{seed}.pkl"), "wb") as f:
         pickle.dump({"acc": acc, "true": true, "pred": pred, "smiles": getattr(loader.dataset, "smiles", None)}, f)
     return acc
+
+
+def save_predictions_on_device(trainer, loader, model, exp_dir, save_name="test_res", loss_type="mse", seed=123, **test_kw):
+    """``save_predictions`` with the pass and the score from ``trainer.test_on_device`` (``finetune.device_metrics`` of the drivers);
+    the pickle is the same.  ``trainer.last_metrics`` holds every metric of the pass afterwards."""
+    class _OnDevice:
+        @staticmethod
+        def test(model, loader):
+            return trainer.test_on_device(model=model, loader=loader, **test_kw)
+    return save_predictions(_OnDevice, loader, model, exp_dir, save_name, loss_type, seed)

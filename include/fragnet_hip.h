@@ -1208,6 +1208,48 @@ int fn_rows_rnorm_f32(const float* x /*[n,d]*/, int64_t n, int64_t d, float* out
 int64_t fn_topk_scratch_bytes(const fn_topk* t);
 int fn_topk_update_f32(const fn_topk* t, fn_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Evaluation metrics on the device; csrc/metrics.hip.  Entry points added under ABI 12 (nothing existing changes).
+ * Both read pred [n, c] and label [n, c] (fp32, row-major, contiguous, 4-byte aligned) and treat every column on its own.  Row i is
+ * VALID in column k iff label[i,k] >= label_floor (a NaN label is never valid): -0.5 is the "missing label" convention of the
+ * classification targets, -inf takes every non-NaN label.  c in [1, FN_METRICS_MAX_COLS], n <= 2^24.
+ *   fn_pair_concordance_f32  out [c][FN_CONC_FIELDS] uint64, per column: n_valid; n_nan = valid rows whose prediction is NaN (they take
+ *                       part in no pair); n_pairs = ORDERED pairs (i, j) of valid, non-NaN rows with label_i > label_j; n_conc = those
+ *                       with pred_i > pred_j; n_tied = those with pred_i == pred_j.  Plain IEEE compares on the fp32 values (-0 == 0,
+ *                       +inf == +inf is a tie).  (n_conc + n_tied / 2) / n_pairs is the concordance index; on binary labels, ROC-AUC.
+ *                       The counts are exact integers, so they are the same for every launch shape and every run.  A count launch
+ *                       (workgroup = FN_CONC_TILE i-rows x one slice of FN_CONC_TILE-row j-tiles of one column; the j-tile in LDS, four
+ *                       i-rows per lane in registers) leaves one row per workgroup in scratch, a second launch adds them per column: no
+ *                       atomics, no memset.  splits: 0 = the library's choice of j-slices, else that many (fewer when there are fewer
+ *                       j-tiles) -- a test's handle on the tile boundaries.  Cost O(n^2 c).
+ *   fn_regression_sums_f32   out [c][FN_SUMS_FIELDS] double, per column over the valid rows, with p = pred * scale + shift (an fp32
+ *                       multiply, then an fp32 add: never one fma) and y = label: n, sum y, sum p, sum y^2, sum p^2, sum y p,
+ *                       sum (y - p)^2, sum |y - p|, every term formed and added in fp64.  ONE order of addition: rows are cut into
+ *                       chunks of FN_SUMS_CHUNK; inside a chunk thread t of 256 adds rows t, t + 256, .., then a fixed butterfly and the
+ *                       four wave sums in order; the chunk rows of a column are added by a second launch the same way.  The order depends
+ *                       on n alone, so results are bit-identical across runs and across splits (0 = the library's choice of workgroups
+ *                       per column, else that many; each walks chunks splits apart).
+ * scratch: 8-byte aligned device bytes, at least fn_metrics_scratch_bytes(m, sums) (reads n, c and splits only; FN_EINVAL, negative,
+ * when they are invalid).  n = 0: nothing is launched but one fill of zeros (pred, label and scratch may be null).  A null pointer, a negative size, n > 2^24, c outside
+ * [1, FN_METRICS_MAX_COLS], a negative splits or too small a scratch: FN_EINVAL, and the GPU is not touched.
+ * ------------------------------------------------------------------------------------------ */
+#define FN_METRICS_MAX_COLS 64
+#define FN_CONC_FIELDS 5
+#define FN_CONC_TILE 512
+#define FN_SUMS_FIELDS 8
+#define FN_SUMS_CHUNK 1024
+typedef struct fn_metrics {
+    const float *pred /*[n,c]*/, *label /*[n,c]*/;
+    void* out;                   /* [c][FN_CONC_FIELDS] uint64 / [c][FN_SUMS_FIELDS] double */
+    void* scratch;
+    int64_t scratch_bytes, n;
+    float label_floor, scale, shift;     /* scale, shift: fn_regression_sums_f32 only */
+    int32_t c, splits;
+} fn_metrics;
+int64_t fn_metrics_scratch_bytes(const fn_metrics* m, int sums);
+int fn_pair_concordance_f32(const fn_metrics* m, fn_stream_t stream);
+int fn_regression_sums_f32(const fn_metrics* m, fn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

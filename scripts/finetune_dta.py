@@ -81,12 +81,17 @@ if __name__ == "__main__":
     if want_factored_step:
         graph_step = train.make_factored_pair_graph_step(model, optimizer, train_loader, int(ft.model.num_heads))
     step_kw = {} if graph_step is None else {"graph_step": graph_step}      # absent by default: the launch-by-launch step, as ever
+    # finetune.device_metrics: true -- validation and test scores from the metrics kernels (no host read per batch), Pearson and CI in the final lines
+    device_metrics = bool(ft.get("device_metrics"))
     stopper = train.EarlyStopping(patience=ft.es_patience, verbose=True, chkpoint_name=ft.chkpoint_name)
     log = open(os.path.join(exp_dir, "log.jsonl"), "a")
     for epoch in range(ft.n_epochs):
         train_loss = trainer.train(model=model, loader=train_loader, optimizer=optimizer, scheduler=None, device=device, val_loader=val_loader,
                                    **stats, **step_kw)
-        val_loss, _, _ = trainer.test(model=model, loader=val_loader, device=device, **stats)
+        if device_metrics:
+            val_loss = trainer.evaluate(model=model, loader=val_loader, device=device, **stats)["mse"]
+        else:
+            val_loss, _, _ = trainer.test(model=model, loader=val_loader, device=device, **stats)
         print("epoch: ", epoch, train_loss, val_loss, "" if graph_step is None else f"(graph replays {graph_step.replays}, eager fallbacks {graph_step.fallbacks})")
         log.write(json.dumps({"epoch": epoch, "Loss/train": train_loss, "Loss/val": val_loss}) + "\n")
         log.flush()
@@ -96,7 +101,9 @@ if __name__ == "__main__":
             break
     model.load_state_dict(torch.load(ft.chkpoint_name, map_location=device))
     for name, loader in (("val_res", val_loader), ("test_res", test_loader)):
-        score, true, pred = trainer.test(model=model, loader=loader, device=device, **stats)
+        score, true, pred = (trainer.test_on_device if device_metrics else trainer.test)(model=model, loader=loader, device=device, **stats)
         with open(os.path.join(exp_dir, f"{name}_{args.seed}.pkl"), "wb") as f:
             pickle.dump({"acc": score ** 0.5, "true": true, "pred": pred, "smiles": [getattr(r, "smiles", None) for r in loader.dataset]}, f)
         print(f"{name} rmse: {score ** 0.5}")
+        if device_metrics:
+            print(f"{name} pearson: {trainer.last_metrics['pearson']} ci: {trainer.last_metrics['ci']}")

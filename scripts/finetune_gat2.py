@@ -79,11 +79,14 @@ if __name__ == "__main__":
                 self.t += 1
                 self.opt.hyper["lr"] = self.base * (1.0 - 0.5 * min(self.t, 30) / 30)
         scheduler = _Linear(optimizer)
+    # finetune.device_metrics: true -- the validation score (MSE, or minus the mean ROC-AUC) and the final test pass from the metrics kernels:
+    # no host read per batch, no sklearn call per task column
+    device_metrics = bool(ft.get("device_metrics"))
     stopper = train.EarlyStopping(patience=ft.es_patience, verbose=rank == 0, chkpoint_name=ft.chkpoint_name)
     log = open(os.path.join(exp_dir, "log.jsonl"), "a") if rank == 0 else None
     for epoch in range(ft.n_epochs):
         train_loss = trainer.train(model=model, loader=train_loader, optimizer=optimizer, scheduler=scheduler, graph_step=graph_step)
-        val_loss, _, _ = trainer.test(model=model, loader=val_loader)
+        val_loss = trainer.evaluate(model=model, loader=val_loader)["score"] if device_metrics else trainer.test(model=model, loader=val_loader)[0]
         if rank == 0:
             print("epoch: ", epoch, train_loss, val_loss, "" if graph_step is None else f"(graph replays {graph_step.replays}, eager fallbacks {graph_step.fallbacks})")
             log.write(json.dumps({"epoch": epoch, "Loss/train": train_loss, "Loss/val": val_loss}) + "\n")
@@ -98,5 +101,5 @@ if __name__ == "__main__":
     if rank == 0:
         model.load_state_dict(torch.load(ft.chkpoint_name, map_location=device))
         for name, loader in (("val_res", val_loader), ("test_res", test_loader)):
-            acc = train.save_predictions(trainer, loader, model, exp_dir, name, ft.loss, args.seed)
+            acc = (train.save_predictions_on_device if device_metrics else train.save_predictions)(trainer, loader, model, exp_dir, name, ft.loss, args.seed)
             print(f"{name} {'rmse' if ft.loss == 'mse' else '-auc'}: {acc}")
