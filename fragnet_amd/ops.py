@@ -2136,3 +2136,124 @@ def regression_sums(pred: torch.Tensor, label: torch.Tensor, label_floor: float 
     order, with ``p = pred * float32(scale) + float32(shift)`` rounded twice in fp32 as numpy does.  One fixed order of addition: the
     bits are the same for every run and every ``splits``."""
     return _metrics_launch("fn_regression_sums_f32", True, pred, label, label_floor, scale, shift, splits, torch.float64, len(SUMS_FIELDS))
+
+
+# ======================================================================================
+# diverse subsets of embedding rows: greedy k-centre, one launch per pick (csrc/kcenter.hip)
+# ======================================================================================
+KCENTER_METRICS = {"l2": 0, "cosine": 1}
+KCENTER_WIDTHS = (128, 256)
+KCENTER_MAX_SPLITS = 512
+
+
+def kcenter_metric(metric) -> int:
+    """0 / 1 of ``"l2"`` (squared L2, direct form) / ``"cosine"`` (cosine distance); ``"dot"`` is no distance and is refused."""
+    if isinstance(metric, str) and metric in KCENTER_METRICS:
+        return KCENTER_METRICS[metric]
+    if isinstance(metric, int) and not isinstance(metric, bool) and metric in KCENTER_METRICS.values():
+        return metric
+    hint = " (a dot product is not a distance: nothing is farthest under it)" if metric == "dot" else ""
+    raise ValueError(f"unknown metric {metric!r}: one of {', '.join(KCENTER_METRICS)} (or 0, 1){hint}")
+
+
+def _count(v, name: str) -> int:
+    if not isinstance(v, int) or isinstance(v, bool) or v < 0:
+        raise ValueError(f"{name} must be a non-negative integer, got {v!r}")
+    return v
+
+
+class KCenter:
+    """Greedy k-centre over ``n`` rows of width ``d`` (fn_kcenter_pick_f32 / fn_kcenter_seed_f32): ``mind`` [n] the distance of every row
+    to its nearest centre so far, ``label`` [n] that centre's ordinal (-1: none), ``picked`` [cap] the rows in pick order (by ordinal; a
+    seed's slot holds -1), ``radius`` [cap + 1].  A pick is the unpicked row with the largest ``mind``, ties to the smaller row; an update
+    is strict, so the earlier centre keeps a tie.  Every result is bit-identical for every ``splits`` (0 leaves the launch shape to the
+    library; 1..512 allows at most that many workgroups) and for ``pick(a)`` then ``pick(b)`` against ``pick(a + b)``.  Nothing reads
+    device memory on the host.  ``init_distance`` [n] starts ``mind`` there instead of at +inf (negative values count as 0; a NaN row is
+    never lowered and never picked while a number is left)."""
+
+    def __init__(self, n: int, d: int, metric, device, cap: int, splits: int = 0, init_distance=None):
+        self.n, self.cap, self.metric = _count(n, "n"), _count(cap, "cap"), kcenter_metric(metric)
+        if _count(splits, "splits") > KCENTER_MAX_SPLITS:
+            raise ValueError(f"splits must be in [0, {KCENTER_MAX_SPLITS}], got {splits!r}")
+        if d not in KCENTER_WIDTHS:
+            raise _lib.FragnetHipError(f"KCenter: rows of {d!r} floats; the kernel is built for {KCENTER_WIDTHS}")
+        device = torch.device(device)
+        if device.type != "cuda":
+            raise _lib.FragnetHipError(f"KCenter: fragnet_amd kernels need a GPU device (got {device}); there is no CPU fallback")
+        self.d, self.device, self.splits = d, device, splits
+        if init_distance is None:
+            self.mind = torch.full((n,), float("inf"), dtype=torch.float32, device=device)
+        else:
+            init_distance = _f32c(init_distance, "KCenter: init_distance")
+            if init_distance.shape != (n,):
+                raise ValueError(f"KCenter: init_distance must be [{n}], got {tuple(init_distance.shape)}")
+            # a copy; a negative value (the rounding of an expanded-form distance) counts as 0, and -0.0, the kernel's mark of a picked
+            # row, becomes +0.0; a NaN stays
+            self.mind = init_distance.to(device).clamp_min(0.0) + 0.0
+        self.label = torch.full((n,), -1, dtype=torch.int32, device=device)
+        self.picked = torch.full((cap,), -1, dtype=torch.int64, device=device)
+        self.radius = torch.full((cap + 1,), float("nan"), dtype=torch.float32, device=device)
+        self.count = torch.zeros(1, dtype=torch.int64, device=device)
+        self.centres, self.picks = 0, 0                         # the host's mirror of count, and how many of them are rows
+        k = self._descriptor(None, None)
+        need = _lib.load().fn_kcenter_scratch_bytes(C.byref(k))
+        _lib.check(0 if need >= 0 else need, "fn_kcenter_scratch_bytes")
+        self._scratch = torch.empty(max(need, 16), dtype=torch.uint8, device=device)
+
+    def _descriptor(self, x, aux):
+        scratch = getattr(self, "_scratch", None)
+        return _lib.Kcenter(_ptr(x), _ptr(aux), self.mind.data_ptr(), self.label.data_ptr(), self.picked.data_ptr(), self.radius.data_ptr(),
+                            self.count.data_ptr(), _ptr(scratch), 0 if scratch is None else scratch.numel(), self.n, self.cap, self.centres,
+                            self.picks, self.d, self.metric, self.splits)
+
+    def _rows(self, t, rows, name: str):
+        t = _f32c(t, name)
+        if t.dim() != 2 or t.shape[1] != self.d or (rows is not None and t.shape[0] != rows):
+            raise ValueError(f"{name} must be [{'s' if rows is None else rows}, {self.d}], got {tuple(t.shape)}")
+        return t
+
+    def _aux(self, t, rows: int, name: str):
+        if self.metric == 0:
+            return None
+        if t is None:
+            raise ValueError(f"{name} is required for the cosine metric (ops.rows_rnorm of the rows)")
+        t = _f32c(t, name)
+        if t.shape != (rows,):
+            raise ValueError(f"{name} must be [{rows}], got {tuple(t.shape)}")
+        return t
+
+    def seed(self, x, centres, centres_aux=None, aux=None) -> "KCenter":
+        """Folds the rows of ``centres`` [s, d] in as centres ``count .. count + s - 1`` of the rows ``x`` [n, d]: an update launch each,
+        no pick.  ``aux`` / ``centres_aux``: ``rows_rnorm`` of the two for ``"cosine"``."""
+        x, centres = self._rows(x, self.n, "KCenter.seed: x"), self._rows(centres, None, "KCenter.seed: centres")
+        s = centres.shape[0]
+        aux, centres_aux = self._aux(aux, self.n, "KCenter.seed: aux"), self._aux(centres_aux, s, "KCenter.seed: centres_aux")
+        if self.centres + s > self.cap:
+            raise ValueError(f"KCenter.seed: {self.centres} centres + {s} seeds exceed cap = {self.cap}")
+        _lib.call("fn_kcenter_seed_f32", C.byref(self._descriptor(x, aux)), centres.data_ptr(), _ptr(centres_aux), s, _stream_ptr(self.device))
+        self.centres += s
+        return self
+
+    def pick(self, x, k: int, first=None, aux=None) -> "KCenter":
+        """``k`` more picks among the rows ``x`` [n, d] (the same rows in every call of a run).  ``first``: the row of the very first
+        centre -- only before any seed or pick; ``None``: the arg-max, as for every later pick."""
+        x, k = self._rows(x, self.n, "KCenter.pick: x"), _count(k, "k")
+        aux = self._aux(aux, self.n, "KCenter.pick: aux")
+        if k > self.n - self.picks:
+            raise ValueError(f"KCenter.pick: k = {k} exceeds the {self.n - self.picks} rows not yet picked (n = {self.n})")
+        if self.centres + k > self.cap:
+            raise ValueError(f"KCenter.pick: {self.centres} centres + {k} picks exceed cap = {self.cap}")
+        if first is not None:
+            if self.centres > 0:
+                raise ValueError("KCenter.pick: a first row can only be named before any centre; after seeds or picks the arg-max decides")
+            if not isinstance(first, int) or isinstance(first, bool) or not (0 <= first < self.n or (self.n == 0 and k == 0)):
+                raise ValueError(f"KCenter.pick: first must be a row in [0, {self.n}), got {first!r}")
+        _lib.call("fn_kcenter_pick_f32", C.byref(self._descriptor(x, aux)), -1 if first is None or self.n == 0 else first, k,
+                  _stream_ptr(self.device))
+        if self.n > 0:
+            self.centres, self.picks = self.centres + k, self.picks + k
+        return self
+
+    def result(self):
+        """``(picked[:count], radius[:count + 1], mind, label)`` as device tensors; ``count`` is the host's own tally, nothing is read."""
+        return self.picked[:self.centres], self.radius[:self.centres + 1], self.mind, self.label

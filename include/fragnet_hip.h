@@ -1250,6 +1250,58 @@ int64_t fn_metrics_scratch_bytes(const fn_metrics* m, int sums);
 int fn_pair_concordance_f32(const fn_metrics* m, fn_stream_t stream);
 int fn_regression_sums_f32(const fn_metrics* m, fn_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Diverse subsets of embedding rows: greedy k-centre (Gonzalez; farthest-point / MaxMin picking); csrc/kcenter.hip.  Entry points
+ * added under ABI 12 (nothing existing changes).  The run's state is the caller's: mind [n] (distance of every row to its nearest
+ * centre so far; fill +inf -- or a distance to something else, every value >= +0 or NaN -- before the first centre), label [n] (ordinal
+ * of that centre; fill -1), picked [cap], radius [cap + 1], count [1] (centres folded in so far, seeds and picks; fill 0).
+ *   Distances.  metric 0: squared L2 in its direct form, sum_j (x_ij - c_j)^2 as an fma(diff, diff, acc) chain (never
+ *                       |x|^2 + |c|^2 - 2 x.c: nothing cancels, a row is at distance exactly 0 of itself).  metric 1: the cosine
+ *                       distance max(0, 1 - dot * (aux_i * aux_c)), aux = fn_rows_rnorm_f32 of the rows.  The additions of one row have
+ *                       ONE order (lane l of the row's lanes adds its columns 4 l .. 4 l + 3 in order, then a fixed butterfly) whatever
+ *                       n, the grid, splits or the call a pass belongs to: mind, label, picked and radius are bit-identical for every
+ *                       launch shape, and for pick(a) then pick(b) against pick(a + b).
+ *   Update rule.        For a new centre of ordinal t: if (dist < mind[i]) { mind[i] = dist; label[i] = t; } -- strict, the earlier
+ *                       centre keeps a tie.  A NaN distance lowers nothing.
+ *   Pick rule.          A total order: the unpicked row with the largest mind, on equal mind the smallest row.  A NaN mind never wins
+ *                       while a number is left; among NaNs the smallest row.  A row is picked at most once: the picked row's mind is
+ *                       stored as -0.0f (distance zero; the sign bit is the mark, and the only state besides the arrays above).
+ *                       Duplicates of a picked row have mind +0 and may be picked later.
+ *   radius.             radius[t] = mind of the row picked as ordinal t, read when it was picked: the coverage radius of the centres
+ *                       before it (+inf for the first centre of an unseeded run).  When a pick call returns, radius[count] holds the
+ *                       largest remaining mind, the coverage radius of everything chosen (0 when no row is left).  A seed's slot
+ *                       holds picked -1 and radius NaN.
+ *   fn_kcenter_pick_f32 k picks.  first: the row of the very first centre, or -1 = the arg-max like every later pick.  One launch per
+ *                       pick (each reduces the <= 512 per-workgroup (mind, row) pairs of the launch before it, folds the winner in and
+ *                       leaves its own pairs), one scan launch in front when first is -1, one closing launch; no atomics, no workgroup
+ *                       waits on another, nothing synchronises with the host.
+ *   fn_kcenter_seed_f32 folds s given centres [s, d] in (centres_aux [s]: their fn_rows_rnorm_f32, metric 1): one update launch each, no
+ *                       pick, ordinals count .. count + s - 1.  For seed sets of up to a few thousand rows; a distance to a larger set
+ *                       goes in through mind.
+ * host_count / host_picks: what the caller knows *count and the number of picked rows to be (the library does not read device memory);
+ * splits: 0 = the library's choice of workgroups, 1..512 = at most that many (a test's handle on the launch shape).  scratch: 16-byte
+ * aligned device bytes, at least fn_kcenter_scratch_bytes(k); it carries nothing from call to call.  n = 0 or k = 0: nothing is
+ * launched.  A null pointer, a negative size, k > n - host_picks, host_count + k (or + s) > cap, first outside [-1, n), first >= 0 with
+ * host_count > 0, a metric outside 0..1 or too small a scratch: FN_EINVAL; d other than 128 or 256: FN_EUNSUPPORTED; the GPU is not
+ * touched.  Whatever the host says, a launch records nothing at or behind cap and picks nothing when no row is left.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct fn_kcenter {
+    const float* x;              /* [n,d] fp32 row-major, 16-byte aligned */
+    const float* aux;            /* [n], metric 1; else nullable */
+    float* mind;                 /* [n] in/out */
+    int32_t* label;              /* [n] in/out */
+    int64_t* picked;             /* [cap] out: rows in pick order, by ordinal */
+    float* radius;               /* [cap + 1] out */
+    int64_t* count;              /* [1] device word, in/out */
+    void* scratch;
+    int64_t scratch_bytes, n, cap, host_count, host_picks;
+    int32_t d, metric, splits;
+} fn_kcenter;
+int64_t fn_kcenter_scratch_bytes(const fn_kcenter* k);
+int fn_kcenter_seed_f32(const fn_kcenter* k, const float* centres /*[s,d]*/, const float* centres_aux /*[s], nullable*/, int64_t s,
+                        fn_stream_t stream);
+int fn_kcenter_pick_f32(const fn_kcenter* k, int64_t first, int64_t n_picks, fn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
