@@ -2257,3 +2257,102 @@ class KCenter:
     def result(self):
         """``(picked[:count], radius[:count + 1], mind, label)`` as device tensors; ``count`` is the host's own tally, nothing is read."""
         return self.picked[:self.centres], self.radius[:self.centres + 1], self.mind, self.label
+
+
+# ======================================================================================
+# moments and projections of a row table: fp64 count / column sums / Gram matrix, and rows onto a few directions (csrc/moments.hip)
+# ======================================================================================
+MOMENTS_WIDTHS = (128, 256)
+MOMENTS_CHUNK = _lib.MOMENTS_CHUNK      # rows of one fp32 fma chain
+MOMENTS_GROUP = _lib.MOMENTS_GROUP      # chunks of one super-chunk = one scratch slot
+
+
+def _moment_rows(x, d, name: str):
+    x = _f32c(x, name)
+    if x.dim() != 2 or (d is not None and x.shape[1] != d):
+        raise ValueError(f"{name} must be [n, {'d' if d is None else d}], got {tuple(x.shape)}")
+    if x.shape[1] not in MOMENTS_WIDTHS:
+        raise _lib.FragnetHipError(f"{name}: rows of {x.shape[1]} floats; the kernel is built for {MOMENTS_WIDTHS}")
+    return x
+
+
+def _moment_shift(shift, x, name: str):
+    if shift is None:
+        return None
+    shift = _f32c(shift, name)
+    if shift.shape != (x.shape[1],) or shift.device != x.device:
+        raise ValueError(f"{name} must be [{x.shape[1]}] on {x.device}, got {tuple(shift.shape)} on {shift.device}")
+    return shift
+
+
+class Moments:
+    """Running count, column sums and Gram matrix of rows of width ``d`` that arrive batch by batch (fn_rows_moments_f32), in fp64 on the
+    device: with ``z = x - shift`` (one fp32 subtraction), ``sum[j] = sum_i z_ij`` and ``gram[j][l] = sum_i z_ij z_il``.  No [n, d]
+    temporary exists.  Inside chunks of ``MOMENTS_CHUNK`` rows an entry is one fp32 fma chain; everything above that is added in fp64 in an
+    order that depends on the batch's row count alone, so a batch's contribution is bit-identical for every ``splits`` (0 leaves the
+    launch shape to the library; 1..63 allows at most that many workgroups).  Chunks are counted per ``update``: the same rows cut into
+    different batches may differ in the last bits.  The shift is fixed by the first ``update``."""
+
+    def __init__(self, d: int, device, splits: int = 0):
+        if d not in MOMENTS_WIDTHS:
+            raise _lib.FragnetHipError(f"Moments: rows of {d!r} floats; the kernel is built for {MOMENTS_WIDTHS}")
+        if not isinstance(splits, int) or isinstance(splits, bool) or not 0 <= splits <= 63:
+            raise ValueError(f"splits must be in [0, 63], got {splits!r}")
+        device = torch.device(device)
+        if device.type != "cuda":
+            raise _lib.FragnetHipError(f"Moments: fragnet_amd kernels need a GPU device (got {device}); there is no CPU fallback")
+        self.d, self.device, self.splits = d, device, splits
+        self.n, self.shift, self._given, self._updates = 0, None, None, 0
+        self.sum = torch.zeros(d, dtype=torch.float64, device=device)
+        self.gram = torch.zeros((d, d), dtype=torch.float64, device=device)
+        self._scratch = None
+
+    def update(self, x, shift=None) -> "Moments":
+        """Adds the rows ``x`` [n, d] in.  ``shift`` [d] (``None``: zeros) is kept by the first call; a later call hands in the same
+        tensor, an equal one, or ``None`` for "the one in use"."""
+        x = _moment_rows(x, self.d, "Moments.update: x")
+        if x.device != self.device:
+            raise ValueError(f"Moments.update: x is on {x.device}, the moments on {self.device}")
+        shift = _moment_shift(shift, x, "Moments.update: shift")
+        if self._updates == 0:
+            self.shift, self._given = (None if shift is None else shift.clone()), shift
+        elif shift is not None and shift is not self._given and (self.shift is None or not torch.equal(shift, self.shift)):
+            raise ValueError("Moments.update: the shift is fixed by the first update; this one differs")      # (the same tensor object again: no comparison, which would wait for the device)
+        m = _lib.Moments(x.data_ptr(), _ptr(self.shift), self.sum.data_ptr(), self.gram.data_ptr(), None, 0, x.shape[0], self.d, 1, self.splits)
+        need = _lib.load().fn_moments_scratch_bytes(C.byref(m))
+        _lib.check(0 if need >= 0 else need, "fn_moments_scratch_bytes")
+        if self._scratch is None or self._scratch.numel() < need:
+            self._scratch = torch.empty(max(need, 16), dtype=torch.uint8, device=self.device)
+        m.scratch, m.scratch_bytes = self._scratch.data_ptr(), self._scratch.numel()
+        _lib.call("fn_rows_moments_f32", C.byref(m), _stream_ptr(self.device))
+        self.n += int(x.shape[0])
+        self._updates += 1
+        return self
+
+    def result(self):
+        """``(n, sum [d], gram [d, d])``: the host's row count and the two float64 device tensors as they stand."""
+        return self.n, self.sum, self.gram
+
+
+def rows_project(x, W, shift=None, want_rows: bool = True, want_sq: bool = False):
+    """``(out | None, sq | None)`` of the rows ``x`` [n, d] (d 128 or 256) and the directions ``W`` [d, k], 1 <= k <= d
+    (fn_rows_project_f32): ``out[i][c]`` is one fp32 fma chain of ``(x_ip - shift_p) W_pc`` over a fixed order of p, ``sq[i]`` one fp32
+    fma chain of ``out[i][c]^2`` over c ascending.  A row's results depend on that row, ``shift`` and ``W`` alone, so a slice of the rows
+    gives the same bits as the whole table.  ``want_rows=False``: no [n, k] table is written anywhere."""
+    x = _moment_rows(x, None, "rows_project: x")
+    W = _f32c(W, "rows_project: W")
+    d = x.shape[1]
+    if W.dim() != 2 or W.shape[0] != d or W.device != x.device:
+        raise ValueError(f"rows_project: W must be [{d}, k] on {x.device}, got {tuple(W.shape)} on {W.device}")
+    k = int(W.shape[1])
+    if not 1 <= k <= d:
+        raise ValueError(f"rows_project: k must be in [1, {d}], got {k}")
+    shift = _moment_shift(shift, x, "rows_project: shift")
+    if not want_rows and not want_sq:
+        raise ValueError("rows_project: nothing is wanted (want_rows and want_sq are both off)")
+    n = int(x.shape[0])
+    out = torch.empty((n, k), dtype=torch.float32, device=x.device) if want_rows else None
+    sq = torch.empty(n, dtype=torch.float32, device=x.device) if want_sq else None
+    p = _lib.Project(x.data_ptr(), _ptr(shift), W.data_ptr(), _ptr(out), _ptr(sq), n, d, k)
+    _lib.call("fn_rows_project_f32", C.byref(p), _stream_ptr(x.device))
+    return out, sq

@@ -1302,6 +1302,60 @@ int fn_kcenter_seed_f32(const fn_kcenter* k, const float* centres /*[s,d]*/, con
                         fn_stream_t stream);
 int fn_kcenter_pick_f32(const fn_kcenter* k, int64_t first, int64_t n_picks, fn_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Moments and projections of a row table (the chemical-space map and the Mahalanobis domain); csrc/moments.hip.  Entry points added
+ * under ABI 12 (nothing existing changes).  x [n, d] fp32 row-major, 16-byte aligned, d = 128 or 256 (else FN_EUNSUPPORTED); shift [d]
+ * fp32, nullable = zeros; z = x - shift is ONE fp32 subtraction per element.
+ *   fn_rows_moments_f32 sum [d] double, sum[j] = sum_i z_ij; gram [d, d] double, gram[j][l] = sum_i z_ij z_il.  accumulate != 0: the
+ *                       call's result is added onto what sum / gram hold, one fp64 addition per entry (a store arrives batch by
+ *                       batch); else they are overwritten.  ONE order of addition, a function of n alone: the rows of a call are cut
+ *                       into chunks of FN_MOMENTS_CHUNK rows counted from the call's row 0; inside a chunk a Gram entry is one fp32 fma
+ *                       chain over the chunk's rows in ascending order (the fp32-input MFMA 16x16x4 is bit for bit such a chain), a
+ *                       column sum four fp32 chains of adds (rows = 0, 1, 2, 3 mod 4); the chunk results of a SUPER-CHUNK
+ *                       (FN_MOMENTS_GROUP consecutive chunks) are added in fp64 in ascending order by the one workgroup that owns that
+ *                       super-chunk's 64 x 64 block of the Gram matrix (the four partial column sums of a super-chunk then in the order
+ *                       ((0 + 1) + 2) + 3), and a second launch adds the super-chunk results in ascending order.  No atomics, no
+ *                       workgroup waits on another.  Only the blocks on and above the diagonal are computed; gram[l][j] is a copy of
+ *                       gram[j][l].  The result is a function of (x, shift, n, d): bit-identical for every launch shape.  It is NOT
+ *                       promised to be bit-identical when the same rows arrive cut into different calls: chunks are counted per call.
+ *                       splits: 0 = the library's choice of workgroups, else at most that many (a test's handle on the launch shape).
+ *                       scratch: 16-byte aligned device bytes, at least fn_moments_scratch_bytes(m) =
+ *                       ceil(n / (FN_MOMENTS_CHUNK * FN_MOMENTS_GROUP)) * (d * d + d) doubles -- one slot per super-chunk, not per
+ *                       chunk: 32 768 rows a slot, so 1 M rows of 256 floats take 32 slots = 16.8 MB (of 128: 4.2 MB).  n = 0: sum and
+ *                       gram are left alone (accumulate) or zeroed; x and scratch may be null.  Rows past n are never read.
+ *   fn_rows_project_f32 W [d, k] fp32 row-major, 4-byte aligned, 1 <= k <= d.  out [n, k] fp32 (nullable), out[i][c] = one fp32 fma
+ *                       chain, started at 0, of z_ip W_pc over p in the order p = 16 t + 4 h + e for t = 0 .. d/16 - 1 (outer),
+ *                       e = 0 .. 3, h = 0 .. 3 (inner) -- the same permutation for every row and column.  sq [n] fp32 (nullable; one of
+ *                       the two must be given), sq[i] = one fp32 fma chain over c ascending of out[i][c]^2, started at 0.  Row i's
+ *                       results depend on row i, shift and W alone: a slice of the rows gives the same bits as the whole table,
+ *                       whatever the launch shape.  With out null no n x k table exists anywhere.
+ * A null descriptor or required pointer, a negative size or splits, n >= 2^40, k outside [1, d], a misaligned buffer or too small a
+ * scratch: FN_EINVAL, and the GPU is not touched.
+ * ------------------------------------------------------------------------------------------ */
+#define FN_MOMENTS_CHUNK 512       /* rows of one fp32 chain; a multiple of 64, <= 1024 */
+#define FN_MOMENTS_GROUP 64        /* chunks of one super-chunk = one scratch slot */
+typedef struct fn_moments {
+    const float* x;              /* [n,d] */
+    const float* shift;          /* [d], nullable */
+    double* sum;                 /* [d] */
+    double* gram;                /* [d,d] */
+    void* scratch;
+    int64_t scratch_bytes, n;
+    int32_t d, accumulate, splits;
+} fn_moments;
+typedef struct fn_project {
+    const float* x;              /* [n,d] */
+    const float* shift;          /* [d], nullable */
+    const float* W;              /* [d,k] */
+    float* out;                  /* [n,k], nullable */
+    float* sq;                   /* [n], nullable */
+    int64_t n;
+    int32_t d, k;
+} fn_project;
+int64_t fn_moments_scratch_bytes(const fn_moments* m);
+int fn_rows_moments_f32(const fn_moments* m, fn_stream_t stream);
+int fn_rows_project_f32(const fn_project* p, fn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
